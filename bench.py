@@ -369,7 +369,11 @@ def main():
     ap.add_argument("--no-probe", action="store_true", help="N>1: skip the step trace and the link probes after the timed region")
     ap.add_argument("--ctx-opt", action="append", default=[], metavar="KEY=VALUE",
                     help="N=1: a gpt_ctx_set_option pair for the timed context (scratch/prof_r06.sh traces with tail_wait=0)")
+    ap.add_argument("--dump-outputs", default=None, metavar="DIR",
+                    help="write what the last timed step returned (ll_data, logdet_half and, N=1, alpha) as DIR/<name>.npy, float64")
     args = ap.parse_args()
+    if args.steps < 1:
+        ap.error("--steps must be at least 1")
 
     if args.gpus > 1 and "RANK" not in os.environ and int(os.environ.get("WORLD_SIZE", "1")) == 1:
         self_launch(args.gpus)          # plain `python bench.py --gpus N`: start the N ranks (never returns)
@@ -494,15 +498,13 @@ def main():
         # device behind the factorisation (context option eager_alpha) and handed to the host with the call.  `value` counts the
         # full LAPACK potrf + potrs flops.  (Rounds 1-5 timed the evaluation WITHOUT alpha -- what the MAP loop needs -- as the
         # headline; that figure is now the sibling `lazy_alpha`.)
-        # K = --steps evaluations make one ROUND, bracketed by barrier + synchronize on both sides as the contract says; rounds are
-        # repeated until the timed region is at least MIN_TIMED_S long (VERDICT r5 #2c: 20 steps are 0.09 s), `ms_per_step` is the
-        # MEDIAN round's, min / max / all rounds are reported.
+        # The timed region is exactly --steps evaluations, bracketed by barrier + synchronize on both sides; ms_per_step = its
+        # time / --steps.
         # The bench's own instrumentation -- HIP events on every >= 1-GFLOP GEMM launch of the main stream (`roofline`) and around
         # the K-build / factorisation phases -- costs 0.13 ms per C3 step (3 %; scratch/instr_ab.py) and is not part of the
-        # product: it rides on the FIRST step of every INSTR_ROUNDS-th round (with rounds repeated to a second that is 6-11
-        # instrumented steps = 100-180 timed launches), `roofline.sampled_steps` says how many.
-        INSTR_ROUNDS = 2
-        MIN_TIMED_S = float(os.environ.get("GPT_BENCH_MIN_TIMED_S", "1.0"))
+        # product: it runs on INSTR_STEPS further evaluations right after the timed region (100-180 timed launches),
+        # `roofline.sampled_steps` says how many.
+        INSTR_STEPS = 8
         alpha_box = [None]
 
         def step_full():
@@ -510,64 +512,53 @@ def main():
             alpha_box[0] = ctx.get_alpha(N)                     # (a host copy: the fit's own synchronisation covered the transfer)
             return r_
 
-        def timed_rounds(step_fn, instrument, min_s):
-            """Rounds of exactly --steps evaluations each; returns (list of round seconds, per-step lists, counters)."""
-            rounds_, t_instr_, t_plain_, tk_, tp_, n_instr_ = [], [], [], 0.0, 0.0, 0
-            total_ = 0.0
-            while not rounds_ or total_ < min_s:
-                barrier()
-                t0_ = time.perf_counter()
-                for i_ in range(args.steps):
-                    instr_ = instrument and i_ == 0 and (len(rounds_) % INSTR_ROUNDS == 0)
-                    if instr_:
-                        ctx.set_option("profile_gemm", 1)
-                        ctx.set_option("timing", 1)
-                    ts_ = time.perf_counter()
-                    res_ = step_fn()
-                    (t_instr_ if instr_ else t_plain_).append(time.perf_counter() - ts_)
-                    if instr_:
-                        tm_ = ctx.last_timings()
-                        tk_ += tm_["kbuild"]
-                        tp_ += tm_["potrf"]
-                        n_instr_ += 1
-                        ctx.set_option("profile_gemm", 0)
-                        ctx.set_option("timing", 0)
-                barrier()
-                rounds_.append(time.perf_counter() - t0_)
-                total_ += rounds_[-1]
-                if len(rounds_) >= 200:
-                    break
-            return rounds_, t_instr_, t_plain_, tk_, tp_, n_instr_, res_
+        def timed_steps(step_fn):
+            """Exactly --steps evaluations; returns (seconds, result of the last one)."""
+            barrier()
+            t0_ = time.perf_counter()
+            for _ in range(args.steps):
+                res_ = step_fn()
+            barrier()
+            return time.perf_counter() - t0_, res_
 
         ctx.set_option("profile_gemm", 0)
         ctx.set_option("timing", 0)
         ctx.set_option("eager_alpha", 1)
         for _ in range(2):
             ll, ld = step_full()
-        ctx.gemm_profile_read()
         edges0_ = ctx.edge_count
-        rounds, t_instr, t_plain, tk, tp, n_instr, (ll, ld) = timed_rounds(step_full, True, MIN_TIMED_S)
-        nsteps_total = len(rounds) * args.steps
-        elapsed = float(np.median(rounds))                     # seconds of the median round of --steps evaluations
-        gflops_alg, gms, gcount, gbytes = ctx.gemm_profile_read(with_bytes=True)
-        extra["flag_edges_per_step"] = (ctx.edge_count - edges0_) / float(nsteps_total)   # 0: the look-ahead ran on events
-        extra["flag_schedule"] = extra["flag_edges_per_step"] > 0
-        extra["timed_region"] = {"rounds": len(rounds), "steps_per_round": args.steps, "seconds": float(sum(rounds)),
-                                 "ms_per_step_median": 1e3 * elapsed / args.steps,
-                                 "ms_per_step_min": 1e3 * min(rounds) / args.steps, "ms_per_step_max": 1e3 * max(rounds) / args.steps,
-                                 "note": "each round = exactly --steps full evaluations between barrier + synchronize; ms_per_step and "
-                                         "value are the median round's"}
+        elapsed, (ll, ld) = timed_steps(step_full)
         alpha_eager = alpha_box[0].copy()
+        outputs = {"ll_data": ll, "logdet_half": ld, "alpha": alpha_eager}
+        extra["flag_edges_per_step"] = (ctx.edge_count - edges0_) / float(args.steps)   # 0: the look-ahead ran on events
+        extra["flag_schedule"] = extra["flag_edges_per_step"] > 0
+        extra["timed_region"] = {"steps": args.steps, "seconds": elapsed,
+                                 "note": "exactly --steps full evaluations between barrier + synchronize, none of them instrumented; "
+                                         "ms_per_step and value are their mean"}
+        ctx.gemm_profile_read()
+        t_instr, tk, tp, n_instr = [], 0.0, 0.0, 0
+        for _ in range(INSTR_STEPS):
+            ctx.set_option("profile_gemm", 1)
+            ctx.set_option("timing", 1)
+            ts_ = time.perf_counter()
+            step_full()
+            t_instr.append(time.perf_counter() - ts_)
+            tm_ = ctx.last_timings()
+            tk += tm_["kbuild"]
+            tp += tm_["potrf"]
+            n_instr += 1
+            ctx.set_option("profile_gemm", 0)
+            ctx.set_option("timing", 0)
+        gflops_alg, gms, gcount, gbytes = ctx.gemm_profile_read(with_bytes=True)
         # sibling: the evaluation without alpha (what update_hyperparameters costs in the MAP loop, which never reads alpha);
         # executed flops = potrf + the forward half of potrs
         ctx.set_option("eager_alpha", 0)
         for _ in range(2):
             step()
-        rounds_l = timed_rounds(step, False, 0.5 * MIN_TIMED_S)[0]
-        per_l = float(np.median(rounds_l)) / args.steps
+        per_l = timed_steps(step)[0] / args.steps
         extra["lazy_alpha"] = {"ms_per_step": per_l * 1e3, "value": flops_fit(N, alpha=False) / per_l * 1e-9, "unit": "GFLOP/s",
                                "pct_fp64_mfma_peak": 100.0 * flops_fit(N, alpha=False) / per_l * 1e-12 / FP64_MFMA_PEAK_TFLOPS,
-                               "lml_evals_per_s": 1.0 / per_l, "rounds": len(rounds_l),
+                               "lml_evals_per_s": 1.0 / per_l,
                                "alpha_extra_ms": (elapsed / args.steps - per_l) * 1e3,
                                "note": "the same step with alpha left to first use (gp.alpha, predict, the analytic gradient): z = L^-1 y "
                                        "and ll only -- the headline of rounds 1-5; flops counted: potrf + the forward half of potrs"}
@@ -580,7 +571,7 @@ def main():
                     "frac_events": ach / FP64_MFMA_PEAK_TFLOPS,
                     "launch_population": "the >= 1 GFLOP launches of the timed steps' own schedule (flag edges: urgent + rest merged, one "
                                          "launch per panel), HIP events on the dispatch packets of the main stream; in the instrumented "
-                                         "steps (one per two rounds) the main stream's wait for the next panel is a kernel of its own -- "
+                                         "steps (after the timed region) the main stream's wait for the next panel is a kernel of its own -- "
                                          "the other steps let the update's last workgroup wait (option tail_wait), which a timed launch "
                                          "would report as its own duration (the library drops it while profile_gemm is on; the committed "
                                          "kernel trace is taken with --ctx-opt tail_wait=0 for the same reason)",
@@ -612,11 +603,13 @@ def main():
                     roof["traffic_algorithmic_bytes"] = tj_["algorithmic_bytes_per_launch"]
                     roof["traffic_file"] = os.path.relpath(tf_[-1], ROOT)
                     roof["traffic_note"] = tj_.get("note")
-        extra["methodology"] = {"version": 6, "instrumented": "the first step of every %d-th round" % INSTR_ROUNDS,
+        extra["methodology"] = {"version": 7, "instrumented": "%d steps after the timed region" % INSTR_STEPS,
                                 "ms_per_step_instrumented": 1e3 * sum(t_instr) / max(len(t_instr), 1),
-                                "ms_per_step_plain": (1e3 * sum(t_plain) / len(t_plain)) if t_plain else None,
-                                "note": "version 6 (round 6): a step computes and returns alpha (full compute_K_L_alpha_ll, full LAPACK flop "
-                                        "count); versions <= 5: no alpha in the step, executed flops -- compare those with `lazy_alpha`"}
+                                "ms_per_step_plain": 1e3 * elapsed / args.steps,
+                                "note": "version 7: exactly --steps timed steps, none instrumented; version 6: rounds of --steps repeated to "
+                                        "1 s, median round, one instrumented step per two rounds; versions >= 6: a step computes and returns "
+                                        "alpha (full compute_K_L_alpha_ll, full LAPACK flop count); versions <= 5: no alpha in the step, "
+                                        "executed flops -- compare those with `lazy_alpha`"}
         extra["live_contexts"] = 1 if ctx2 is None else 2
         # The same step through the plugin API (north_star's unit: GaussianProcess.update_hyperparameters, ref
         # gaussian_process.py:1332-1416): a GaussianProcess over the same data whose main / pooled contexts ARE the two of this
@@ -631,8 +624,8 @@ def main():
                 gp_ = g.GaussianProcess(kcls_(num_dim=d, initial_params=params, param_bounds=[(1e-3, 10.0)] * (d + 1)),
                                         X=X, y=y, err_y=err, n=n)
             gp_._ctx_obj, gp_._ctx_pool, gp_._data_on_device = ctx, ([[ctx2, -1]] if ctx2 is not None else []), True
-            ctx.set_option("profile_gemm", 0)      # (what a user of the plugin API runs: no bench events at all; the timed loop
-            ctx.set_option("timing", 0)            #  above carries them on one step per two rounds)
+            ctx.set_option("profile_gemm", 0)      # (what a user of the plugin API runs: no bench events at all, like the timed
+            ctx.set_option("timing", 0)            #  steps above)
             for _ in range(2):
                 v_ = gp_.update_hyperparameters(params)
             eg_ = ctx.edge_count
@@ -856,6 +849,7 @@ def main():
         for _ in range(args.warmup):
             ll, ld = step()
         per, (ll, ld) = timed(args.steps, profile=True)
+        outputs = {"ll_data": ll, "logdet_half": ld}
         roof = roof_box[0]
         elapsed = per * args.steps
         parallelism = describe(base_name)
@@ -924,6 +918,7 @@ def main():
             roof = roof_box[0]
             if per2 < per:
                 per, ll, ld = per2, ll2, ld2
+                outputs = {"ll_data": ll, "logdet_half": ld}
                 elapsed = per * args.steps
                 parallelism = describe(best)
                 extra["schedule"] = best
@@ -1057,6 +1052,11 @@ def main():
                 # partitioned line: cpu_baseline was measured right after the first timed leg (same workload, rank 0's
                 # host cores); the gate is re-evaluated on the ll / log|K| of the schedule that became the line
                 out["parity"], parity_ok = parity_report(ll, ld, cpu_ref)
+    if rank == 0 and args.dump_outputs:
+        # (the inputs are seeded, so two builds run with the same arguments can be compared output for output)
+        os.makedirs(args.dump_outputs, exist_ok=True)
+        for name_, v_ in outputs.items():
+            np.save(os.path.join(args.dump_outputs, name_ + ".npy"), np.asarray(v_, dtype=np.float64))
     if wd.finish():
         if rank == 0:
             print(json.dumps(out), flush=True)
