@@ -474,6 +474,7 @@ class CompiledPlan(object):
         self.nevents = recorder.nevents
         self.handle = None
         self._keep = None
+        self._events = [None] * self.nevents         # the Python interpreter's events, made on first record and re-recorded
 
     # ---- native ----
     def build_native(self, hip_ops, X, n, err, channels):
@@ -524,7 +525,7 @@ class CompiledPlan(object):
 
     # ---- Python interpreter of the same list ----
     def run_python(self, ops, engine, kernel_id, params, noise_var, diag_add):
-        events = [None] * self.nevents
+        events = [None] * self.nevents       # this run's recorded events (a wait before the record of its run waits for nothing)
         works = {}
         state = [None, None]                 # the queue that is current, its context manager
 
@@ -558,7 +559,10 @@ class CompiledPlan(object):
                         events[ints[0]].wait()
                     # (else: "ready" of an exchange the engine's _plan_collective did not issue, or an "arrived" nobody recorded)
                 elif opcode == OP_RECORD:
-                    e = events[ints[0]] = ops.new_event()
+                    e = self._events[ints[0]]
+                    if e is None:
+                        e = self._events[ints[0]] = ops.new_event()
+                    events[ints[0]] = e
                     e.record()
                 elif opcode == OP_GEMM:
                     ops.gemm_nt(*py, q=q)
@@ -607,7 +611,199 @@ class _Arrival(object):
             w.wait()
 
 
-class DistributedLML(object):
+def _position(group):
+    """(rank, size) of this process in ``group``; (0, 1) without a process group."""
+    return (dist.get_rank(group), dist.get_world_size(group)) if dist.is_initialized() else (0, 1)
+
+
+class _PanelEngine(object):
+    """What the two partitioned engines share: the replicated inputs and the per-evaluation buffers, how an evaluation is driven
+    (``compiled``), its host traffic and the reduction of three scalars that ends it.  An engine places itself (``rank``,
+    ``world``) before calling ``__init__`` and supplies its layout, ``_assemble``, ``_schedule`` (the step loop, issued against
+    ``self.ops``: the real ops or a PlanRecorder), its collectives and three hooks: ``_plan_key`` (what the recorded op list
+    depends on besides the constructor's arguments), ``_channels`` (the communicators of a native plan) and ``_fold`` (see
+    ``_finish``)."""
+    NBUF = 4
+    # True: a model rank (``layout`` given) runs the step loop unless ``compiled`` says otherwise, and GPT_DIST_COMPILED does
+    # not apply to it (GridLML: the single-GPU models of scratch/)
+    _MODEL_STEP_LOOP = False
+
+    def __init__(self, X, n, nb, group, ops, device, lookahead, layout, compiled):
+        if nb <= 0 or nb % 128:
+            raise ValueError("nb must be a positive multiple of 128")
+        self.group = group
+        if ops is None:
+            ops = HipPanelOps(0 if device is None else device)
+        self.ops = ops
+        self.device = getattr(ops, "device", torch.device("cpu"))
+        # GPT_DIST_FORCE_COLLECTIVES=1 issues the (self-)broadcasts and all-reduces even with a single rank, so the
+        # RCCL call pattern can be exercised on a 1-GPU box (tests/test_gpu_a_dist_processes.py).
+        self.force_collectives = bool(int(os.environ.get("GPT_DIST_FORCE_COLLECTIVES", "0"))) and dist.is_initialized()
+        self.lookahead = bool(lookahead)
+        X = np.ascontiguousarray(X, dtype=np.float64)
+        n = np.ascontiguousarray(n, dtype=np.int32)
+        self.N, self.D = X.shape
+        self._n_maxsum = int(n.sum(axis=1).max()) if n.size else 0
+        self.nb = nb
+        self.NP = (self.N + 1 + nb - 1) // nb * nb
+        self.nblk = self.NP // nb
+        dev = self.device
+        f64 = dict(dtype=torch.float64, device=dev)
+        self.X = torch.from_numpy(X).to(dev)
+        self.n = torch.from_numpy(n).to(dev)
+        self.invd = torch.empty(((nb // 128) * 9216,), **f64)     # GPT_WS_BLOCK per 128 columns
+        self.info = torch.zeros((1,), dtype=torch.int32, device=dev)
+        self.y = torch.empty((self.NP,), **f64)
+        self.err = torch.zeros((self.NP,), **f64)
+        self.red = torch.zeros((3,), **f64)        # sum(log L_ii) part, z.z part, info
+        # pinned staging for the per-fit host traffic (y | err_y up, three scalars down): page-locked by the library's own
+        # allocator (gpt_host_alloc) and only WRAPPED as tensors -- tensors from torch's pinned-memory allocator that live
+        # until interpreter exit crashed the process at teardown ("pure virtual method called", after every result was out)
+        on_gpu = dev.type == "cuda"
+        self._h_in = torch.from_numpy(_lib.pinned_empty((2, self.NP), min_bytes=0)) if on_gpu else None
+        self._h_out = torch.from_numpy(_lib.pinned_empty((3,), min_bytes=0)) if on_gpu else None
+        self.timings = {}
+        self.trace = False          # record the device-timeline position of every step (timings["steps_ms"])
+        self.compiled = self._resolve_compiled(compiled, layout)
+        self._plans = {}            # plan key -> CompiledPlan
+        self._rec = None            # the PlanRecorder while the step loop is being recorded
+
+    def _resolve_compiled(self, compiled, layout):
+        """compiled: how an evaluation is driven.  "native": the step loop recorded once, replayed by gpt_plan_run (C loop, RCCL
+        called from the library); "python": the same op list through the Python interpreter (any ops, torch.distributed);
+        False: the step loop itself issues every operation (what rounds 1-5 did; still what a traced evaluation does).
+        None: "native" with the product ops on ONE rank (no communicator of the plan's own is involved beyond a 1-rank one), else
+        "python".  The native replay on several ranks -- RCCL called from the library on the plan's own communicator -- has never
+        run on more than one GPU (this build had none): it is opt-in (compiled="native", GPT_DIST_COMPILED=native; bench.py tries it
+        as a leg under its watchdog) until it has.  GPT_DIST_COMPILED=0 / native / python overrides.  A model rank: see
+        ``_MODEL_STEP_LOOP``."""
+        if layout is not None and self._MODEL_STEP_LOOP:
+            compiled = False if compiled is None else compiled
+        else:
+            env = os.environ.get("GPT_DIST_COMPILED")
+            if env is not None:
+                compiled = False if env == "0" else env
+            if compiled is None:
+                one_rank = not dist.is_initialized() or dist.get_world_size(self.group) == 1
+                compiled = "native" if (isinstance(self.ops, HipPanelOps) and one_rank and layout is None) else "python"
+        if compiled not in (False, "native", "python"):
+            raise ValueError("compiled must be None, False, 'native' or 'python'")
+        if compiled == "native" and not isinstance(self.ops, HipPanelOps):
+            raise ValueError("compiled='native' needs the product ops (HipPanelOps)")
+        return compiled
+
+    # ---- one evaluation -------------------------------------------------------------------------
+    def fit(self, kernel_id, params, y, err_y, noise_var=0.0, diag_factor=1e2):
+        """One LML evaluation; returns ``(ll_data, logdet_half)`` on every rank (``numpy.linalg.LinAlgError`` on every rank
+        if K_tot is not positive definite)."""
+        # the derivative-order limits gpt_fit / gpt_fit_sum check on the host (the device API takes what it is given)
+        if kernel_id == _lib.KERNEL_M52 and self._n_maxsum > 1:
+            raise ValueError("Matern52Kernel only supports 0th and 1st order derivatives")      # ref matern.py:545-546
+        if kernel_id in (_lib.KERNEL_RQ, _lib.KERNEL_MATERN) and 2 * self._n_maxsum > 16:
+            raise ValueError("RationalQuadratic / Matern kernel: derivative orders of a pair sum to %d, the device builder "
+                             "supports 16" % (2 * self._n_maxsum))
+        t_host0 = time.perf_counter()
+        self._upload(y, err_y)
+        if not self.compiled or self.trace:
+            self._schedule(kernel_id, params, noise_var, diag_factor)
+            return self._finish(t_host0)
+        key = self._plan_key()
+        plan = self._plans.get(key)
+        if plan is None:
+            # walk the step loop once against the recorder (nothing runs), then build the executor
+            real, rec = self.ops, PlanRecorder(self.device)
+            self.ops = self._rec = rec
+            try:
+                self._schedule(None, None, 0.0, 0.0)
+            finally:
+                self.ops, self._rec = real, None
+            plan = CompiledPlan(rec)
+            if self.compiled == "native":
+                plan.build_native(real, self.X, self.n, self.err, self._channels())
+            self._plans[key] = plan
+            self.timings["plan_ops"] = len(plan.ops)
+        diag_add = diag_factor * sys.float_info.epsilon
+        if self.compiled == "native":
+            self.timings["native_enqueue_ms"] = plan.run_native(kernel_id, params, noise_var, diag_add)
+        else:
+            plan.run_python(self.ops, self, kernel_id, params, noise_var, diag_add)
+        return self._finish(t_host0)
+
+    def _upload(self, y, err_y):
+        """Per-evaluation host traffic and resets, on the main queue: y | err_y up, info and the scalar accumulators to zero."""
+        ops, N = self.ops, self.N
+        y = np.ascontiguousarray(y, dtype=np.float64)
+        err_y = np.array(np.broadcast_to(err_y, (N,)), dtype=np.float64)
+        with ops.queue("main"):
+            # y | err_y go up from a pinned staging tensor, asynchronously on the main queue (a pageable source makes the copy
+            # synchronous and costs a staging copy inside the runtime); the scalar accumulators are persistent tensors
+            if self._h_in is not None:
+                self._h_in[0, :N].copy_(torch.from_numpy(y))
+                self._h_in[1, :N].copy_(torch.from_numpy(err_y))
+                self.y[:N].copy_(self._h_in[0, :N], non_blocking=True)
+                self.err[:N].copy_(self._h_in[1, :N], non_blocking=True)
+            else:
+                self.y[:N] = torch.from_numpy(y)
+                self.err[:N] = torch.from_numpy(err_y)
+            self.info.zero_()
+            self.red.zero_()
+
+    def _begin(self, kernel_id, params, noise_var, diag_factor):
+        """Head of the schedule (recorded in a compiled plan): build the local blocks on the main queue; returns the event after
+        them."""
+        ops = self.ops
+        with ops.queue("main"):
+            self._t0 = ops.new_timing_event() if (self.trace and self._rec is None) else None
+            if self._t0 is not None:
+                self._t0.record()
+            self._assemble(kernel_id, params, noise_var, diag_factor * sys.float_info.epsilon)
+            ev_asm = ops.new_event()
+            ev_asm.record()
+        self._marks = []
+        return ev_asm
+
+    def _mark(self, k, tag):
+        """(trace) device-timeline stamp on the current queue: ``tag`` of panel k (arrived, applied, ...)."""
+        if self._t0 is not None:
+            e = self.ops.new_timing_event()
+            e.record()
+            self._marks.append((k, tag, e))
+
+    def _allreduce(self, t, op):
+        dist.all_reduce(t, op=dist.ReduceOp.SUM if op == "sum" else dist.ReduceOp.MAX, group=self.group)
+
+    def _finish(self, t_host0):
+        """Common tail: the three scalars (sum(log L_ii) over i < N, z.z from the augmented row, info) and ll.  ``_fold(red)``
+        adds the engine's other partial sums to ``red`` and says whether the scalars are reduced over the ranks."""
+        ops, N = self.ops, self.N
+        self.timings["host_enqueue_s"] = time.perf_counter() - t_host0      # the host ran this far ahead of the GPU
+        with ops.queue("panel"):
+            red = self.red
+            reduce = self._fold(red)
+            red[2] = self.info.to(torch.float64)[0]
+            if reduce:
+                # info: non-zero on the owner of the failing panel only; max picks it up
+                info_t = red[2:3].clone()
+                self._allreduce(red[:2], "sum")
+                self._allreduce(info_t, "max")
+                red[2] = info_t[0]
+            if self._h_out is not None:
+                self._h_out.copy_(red, non_blocking=True)         # pinned: the wait below is the only synchronisation
+        ops.synchronize()
+        logdet_half, zz, info = (float(v) for v in (self._h_out if self._h_out is not None else red))
+        if self._t0 is not None:
+            self.timings["steps_ms"] = [(k, tag, self._t0.elapsed_ms(e)) for k, tag, e in self._marks]
+        if info != 0 and info <= N:
+            raise np.linalg.LinAlgError("%d-th leading minor of the array is not positive definite" % int(info))
+        ll_data = -0.5 * zz - logdet_half - 0.5 * N * math.log(2.0 * math.pi)
+        if info != 0 or not math.isfinite(ll_data):
+            # like the single-GPU path (api.hip factor_and_ll): a failure in the augmented row -- z.z overflowed, or y / K
+            # held non-finite values -- is an error, not a NaN handed to the optimiser
+            raise np.linalg.LinAlgError("factorisation failed in the augmented row (non-finite y or K_tot?)")
+        return ll_data, logdet_half
+
+
+class DistributedLML(_PanelEngine):
     """Evaluate the LML data term of a GP whose K_tot is partitioned over the ranks of ``group``.
 
     ``X`` (N, D) float64 and ``n`` (N, D) integer derivative orders are replicated on every rank.
@@ -618,29 +814,17 @@ class DistributedLML(object):
     the world size; smaller ones are broadcast); may be changed between ``fit`` calls (bench.py times both).  Several plans
     (e.g. of different ``nb``) may share one ``ops`` object.
     """
-    NBUF = 4
 
     def __init__(self, X, n, nb=512, group=None, ops=None, device=None, lookahead=True, layout=None,
                  schedule="bcast", exchange="bcast", sag_min_bytes=8 << 20, owner_first=None, inv_trsm=True,
                  inv_min_rows=8192, compiled=None):
-        if nb <= 0 or nb % 128:
-            raise ValueError("nb must be a positive multiple of 128")
-        self.group = group
-        self.rank = dist.get_rank(group) if dist.is_initialized() else 0
-        self.world = dist.get_world_size(group) if dist.is_initialized() else 1
+        self.rank, self.world = _position(group)
         self.grank = self.rank                  # position in the process group (``layout`` does not change it)
         if layout is not None:
             # (rank, world) of the block-cyclic layout given explicitly: a subclass then supplies ``_bcast`` /
             # ``_allreduce`` itself (scratch/sim_ranks.py replays one rank's schedule of an 8-rank job on one GPU)
             self.rank, self.world = layout
-        if ops is None:
-            ops = HipPanelOps(0 if device is None else device)
-        self.ops = ops
-        self.device = getattr(ops, "device", torch.device("cpu"))
-        # GPT_DIST_FORCE_COLLECTIVES=1 issues the (self-)broadcasts and all-reduces even with a single rank, so the
-        # RCCL call pattern can be exercised on a 1-GPU box (tests/test_gpu_a_dist_processes.py).
-        self.force_collectives = bool(int(os.environ.get("GPT_DIST_FORCE_COLLECTIVES", "0"))) and dist.is_initialized()
-        self.lookahead = bool(lookahead)
+        _PanelEngine.__init__(self, X, n, nb, group, ops, device, lookahead, layout, compiled)
         if schedule != "bcast" or exchange not in ("bcast", "scatter_gather"):
             raise ValueError("schedule must be 'bcast' (whole panels), exchange 'bcast' or 'scatter_gather'")
         self.schedule = schedule
@@ -661,57 +845,15 @@ class DistributedLML(object):
         self._inv_panel = False
         # RCCL runs the collectives of a communicator in issue order on its stream; other backends need explicit waits
         self._stream_ordered = dist.is_initialized() and dist.get_backend(group) == "nccl"
-        X = np.ascontiguousarray(X, dtype=np.float64)
-        n = np.ascontiguousarray(n, dtype=np.int32)
-        self.N, self.D = X.shape
-        self._n_maxsum = int(n.sum(axis=1).max()) if n.size else 0
-        self.nb = nb
-        self.NP = (self.N + 1 + nb - 1) // nb * nb
-        self.nblk = self.NP // nb
+        nb, NP, dev = self.nb, self.NP, self.device
         self.my_blocks = [J for J in range(self.nblk) if J % self.world == self.rank]
         self.nloc = len(self.my_blocks)
-        dev = self.device
-        self.X = torch.from_numpy(X).to(dev)
-        self.n = torch.from_numpy(n).to(dev)
-        self.A = torch.empty((self.NP, max(self.nloc, 1) * nb), dtype=torch.float64, device=dev)
+        self.A = torch.empty((NP, max(self.nloc, 1) * nb), dtype=torch.float64, device=dev)
         # panel buffers: panel k is read by the main queue's updates while panel k+1 is staged / received and earlier
         # ones may still be in use by updates that have not drained (the slowest rank sets the pace of the exchanges)
-        self.P = [torch.empty((self.NP, nb), dtype=torch.float64, device=dev) for _ in range(self.NBUF)]
-        self.S = torch.empty((self.NP, nb), dtype=torch.float64, device=dev)     # staged column below the head (inv_trsm)
-        self.Winv = torch.empty((nb, nb), dtype=torch.float64, device=dev)       # L_kk^-1 of the panel being produced
-        self.invd = torch.empty(((nb // 128) * 9216,), dtype=torch.float64, device=dev)     # GPT_WS_BLOCK per 128 columns
-        self.info = torch.zeros((1,), dtype=torch.int32, device=dev)
-        self.y = torch.empty((self.NP,), dtype=torch.float64, device=dev)
-        self.err = torch.zeros((self.NP,), dtype=torch.float64, device=dev)
-        self.red = torch.zeros((3,), dtype=torch.float64, device=dev)        # sum(log L_ii) part, z.z part, info
-        # pinned staging for the per-fit host traffic (y | err_y up, three scalars down): page-locked by the library's own
-        # allocator (gpt_host_alloc) and only WRAPPED as tensors -- tensors from torch's pinned-memory allocator that live
-        # until interpreter exit crashed the process at teardown ("pure virtual method called", after every result was out)
-        on_gpu = dev.type == "cuda"
-        self._h_in = torch.from_numpy(_lib.pinned_empty((2, self.NP), min_bytes=0)) if on_gpu else None
-        self._h_out = torch.from_numpy(_lib.pinned_empty((3,), min_bytes=0)) if on_gpu else None
-        self.timings = {}
-        self.trace = False          # record the device-timeline position of every step (timings["steps_ms"])
-        # compiled: how an evaluation is driven.  "native": the step loop recorded once, replayed by gpt_plan_run (C loop, RCCL
-        # called from the library); "python": the same op list through the Python interpreter (any ops, torch.distributed);
-        # False: the step loop itself issues every operation (what rounds 1-5 did; still what a traced evaluation does).
-        # None: "native" with the product ops on ONE rank (no communicator of the plan's own is involved beyond a 1-rank one), else
-        # "python".  The native replay on several ranks -- RCCL called from the library on the plan's own communicator -- has never
-        # run on more than one GPU (this build had none): it is opt-in (compiled="native", GPT_DIST_COMPILED=native; bench.py tries it
-        # as a leg under its watchdog) until it has.  GPT_DIST_COMPILED=0 / native / python overrides.
-        env = os.environ.get("GPT_DIST_COMPILED")
-        if env is not None:
-            compiled = False if env == "0" else env
-        if compiled is None:
-            one_rank = not dist.is_initialized() or dist.get_world_size(group) == 1
-            compiled = "native" if (isinstance(ops, HipPanelOps) and one_rank and layout is None) else "python"
-        if compiled not in (False, "native", "python"):
-            raise ValueError("compiled must be None, False, 'native' or 'python'")
-        if compiled == "native" and not isinstance(ops, HipPanelOps):
-            raise ValueError("compiled='native' needs the product ops (HipPanelOps)")
-        self.compiled = compiled
-        self._plans = {}
-        self._rec = None
+        self.P = [torch.empty((NP, nb), dtype=torch.float64, device=dev) for _ in range(self.NBUF)]
+        self.S = torch.empty((NP, nb), dtype=torch.float64, device=dev)     # staged column below the head (inv_trsm)
+        self.Winv = torch.empty((nb, nb), dtype=torch.float64, device=dev)  # L_kk^-1 of the panel being produced
 
     # ------------------------------------------------------------------------------------------
     def _assemble(self, kernel_id, params, noise_var, diag_add):
@@ -772,8 +914,16 @@ class DistributedLML(object):
         """(Python interpreter of a compiled schedule) issue the recorded exchange; returns the work handles."""
         return self._exchange_now(buf, src, scatter_gather=(opcode == OP_SCATTER))
 
-    def _allreduce(self, t, op):
-        dist.all_reduce(t, op=dist.ReduceOp.SUM if op == "sum" else dist.ReduceOp.MAX, group=self.group)
+    # ---- hooks of _PanelEngine ----
+    def _plan_key(self):
+        return (self.compiled, self.exchange, self.lookahead, self.owner_first, self.inv_trsm, self.inv_min_rows, self.sag_min_bytes,
+                self._collectives_on())
+
+    def _channels(self):
+        return [(0, self.world, self.grank, self.group)] if self._collectives_on() else []
+
+    def _fold(self, red):
+        return self._collectives_on()        # (every partial sum is in red already)
 
     def _stage_panel(self, k, buf, allow_inv=True):
         """Owner side: copy block column k (every update before panel k-1 applied) into the contiguous panel
@@ -840,130 +990,21 @@ class DistributedLML(object):
         self.ops.gemm_nt_stair(self.NP - J0 * nb, len(Js), nb, nb, -1.0, _ptr(buf, off, 0), nb, _ptr(buf, off, 0), nb,
                                W * nb, W * nb, 1.0, _ptr(A, J0 * nb, (J0 // W) * nb), A.stride(0), q="main")
 
-    def _upload(self, y, err_y):
-        """Per-evaluation host traffic and resets, on the main queue: y | err_y up, info and the scalar accumulators to zero."""
-        ops, N = self.ops, self.N
-        y = np.ascontiguousarray(y, dtype=np.float64)
-        err_y = np.array(np.broadcast_to(err_y, (N,)), dtype=np.float64)
-        with ops.queue("main"):
-            # y | err_y go up from a pinned staging tensor, asynchronously on the main queue (a pageable source makes the copy
-            # synchronous and costs a staging copy inside the runtime); the scalar accumulators are persistent tensors
-            if self._h_in is not None:
-                self._h_in[0, :N].copy_(torch.from_numpy(y))
-                self._h_in[1, :N].copy_(torch.from_numpy(err_y))
-                self.y[:N].copy_(self._h_in[0, :N], non_blocking=True)
-                self.err[:N].copy_(self._h_in[1, :N], non_blocking=True)
-            else:
-                self.y[:N] = torch.from_numpy(y)
-                self.err[:N] = torch.from_numpy(err_y)
-            self.info.zero_()
-            self.red.zero_()
-
-    def _begin(self, kernel_id, params, noise_var, diag_factor):
-        """Head of the schedule (recorded in a compiled plan): build the local block columns on the main queue."""
-        ops = self.ops
-        with ops.queue("main"):
-            self._t0 = ops.new_timing_event() if (self.trace and self._rec is None) else None
-            if self._t0 is not None:
-                self._t0.record()
-            self._assemble(kernel_id, params, noise_var, diag_factor * sys.float_info.epsilon)
-            ev_asm = ops.new_event()
-            ev_asm.record()
-        self._factored = []
-        self._marks = []
-        return ev_asm
-
-    def _mark(self, k, tag):
-        """(trace) device-timeline stamp on the current (main) queue: panel k has arrived / has been applied."""
-        if self._t0 is not None:
-            e = self.ops.new_timing_event()
-            e.record()
-            self._marks.append((k, tag, e))
-
-    def _finish(self, t_host0):
-        """Common tail: the three scalars (sum(log L_ii) over i < N, z.z from the augmented row, info) and ll."""
-        ops, N, world = self.ops, self.N, self.world
-        self.timings["host_enqueue_s"] = time.perf_counter() - t_host0      # the host ran this far ahead of the GPU
-        with ops.queue("panel"):
-            red = self.red
-            red[2] = self.info.to(torch.float64)[0]
-            if self._collectives_on():
-                # info: non-zero on the owner of the failing panel only; max picks it up
-                info_t = red[2:3].clone()
-                self._allreduce(red[:2], "sum")
-                self._allreduce(info_t, "max")
-                red[2] = info_t[0]
-            if self._h_out is not None:
-                self._h_out.copy_(red, non_blocking=True)         # pinned: the wait below is the only synchronisation
-        ops.synchronize()
-        logdet_half, zz, info = (float(v) for v in (self._h_out if self._h_out is not None else red))
-        if self._t0 is not None:
-            self.timings["steps_ms"] = [(k, tag, self._t0.elapsed_ms(e)) for k, tag, e in self._marks]
-        if info != 0 and info <= N:
-            raise np.linalg.LinAlgError("%d-th leading minor of the array is not positive definite" % int(info))
-        ll_data = -0.5 * zz - logdet_half - 0.5 * N * math.log(2.0 * math.pi)
-        if info != 0 or not math.isfinite(ll_data):
-            # like the single-GPU path (api.hip factor_and_ll): a failure in the augmented row -- z.z overflowed, or y / K
-            # held non-finite values -- is an error, not a NaN handed to the optimiser
-            raise np.linalg.LinAlgError("factorisation failed in the augmented row (non-finite y or K_tot?)")
-        return ll_data, logdet_half
-
-    def fit(self, kernel_id, params, y, err_y, noise_var=0.0, diag_factor=1e2):
-        """One LML evaluation; returns ``(ll_data, logdet_half)`` on every rank."""
-        # the derivative-order limits gpt_fit / gpt_fit_sum check on the host (the device API takes what it is given)
-        if kernel_id == _lib.KERNEL_M52 and self._n_maxsum > 1:
-            raise ValueError("Matern52Kernel only supports 0th and 1st order derivatives")      # ref matern.py:545-546
-        if kernel_id in (_lib.KERNEL_RQ, _lib.KERNEL_MATERN) and 2 * self._n_maxsum > 16:
-            raise ValueError("RationalQuadratic / Matern kernel: derivative orders of a pair sum to %d, the device builder "
-                             "supports 16" % (2 * self._n_maxsum))
-        return self._fit_bcast(kernel_id, params, y, err_y, noise_var, diag_factor)
-
-    # ------------------------------------------------------------------------------------------
-    def _fit_bcast(self, kernel_id, params, y, err_y, noise_var, diag_factor):
-        """Whole-panel schedule.  Per step k (panel k = block column k of L, contiguous in P[k % NBUF] on every rank):
+    def _schedule(self, kernel_id, params, noise_var, diag_factor):
+        """The step loop of the whole-panel schedule: issues the operations -- or, against a PlanRecorder, lists them.  Per step k
+        (panel k = block column k of L, contiguous in P[k % NBUF] on every rank):
           panel queue: [owner of k+1: stage block column k+1 into P[(k+1) % NBUF]] -> panel k has arrived ->
                        [owner: apply panel k to the staged column, factor it] -> start exchange k+1 (async)
           main queue : panel k has arrived -> apply it to the owned block columns right of k+1, the one that is staged
                        next (k+2) first.
         Edges: "urgent" (column k+2 is up to date with panel k) main -> panel, "done" (step k no longer reads its
         buffer) main -> panel before that buffer is staged / received into again, "arrived" panel -> main."""
-        t_host0 = time.perf_counter()
-        self._upload(y, err_y)
-        if self.compiled and not self.trace:
-            diag_add = diag_factor * sys.float_info.epsilon
-            key = (self.compiled, self.exchange, self.lookahead, self.owner_first, self.inv_trsm, self.inv_min_rows, self.sag_min_bytes,
-                   self._collectives_on())
-            plan = self._plans.get(key)
-            if plan is None:
-                # walk the step loop once against the recorder (nothing runs), then build the executor
-                real, rec = self.ops, PlanRecorder(self.device)
-                self.ops = self._rec = rec
-                try:
-                    self._schedule(None, None, 0.0, 0.0)
-                finally:
-                    self.ops, self._rec = real, None
-                plan = CompiledPlan(rec)
-                if self.compiled == "native":
-                    plan.build_native(real, self.X, self.n, self.err,
-                                      [(0, self.world, self.grank, self.group)] if self._collectives_on() else [])
-                self._plans[key] = plan
-                self.timings["plan_ops"] = len(plan.ops)
-            if self.compiled == "native":
-                self.timings["native_enqueue_ms"] = plan.run_native(kernel_id, params, noise_var, diag_add)
-            else:
-                plan.run_python(self.ops, self, kernel_id, params, noise_var, diag_add)
-            return self._finish(t_host0)
-        self._schedule(kernel_id, params, noise_var, diag_factor)
-        return self._finish(t_host0)
-
-    def _schedule(self, kernel_id, params, noise_var, diag_factor):
-        """The step loop of the whole-panel schedule (see _fit_bcast): issues the operations -- or, against a PlanRecorder, lists
-        them."""
         ops = self.ops
         nb, NP, world, rank, NBUF = self.nb, self.NP, self.world, self.rank, self.NBUF
         nblk = self.nblk
         owner = lambda J: J % world == rank
         ev_asm = self._begin(kernel_id, params, noise_var, diag_factor)
+        self._factored = []
         ev_urg, ev_done = {}, {}
 
         def wait_all(ws):
@@ -1043,7 +1084,7 @@ def _ceil_div(a, b):
     return -((-a) // b)
 
 
-class GridLML(object):
+class GridLML(_PanelEngine):
     """The same LML evaluation with K_tot spread over a ``P_r x P_c`` PROCESS GRID.
 
     Why: in the 1-D layout of :class:`DistributedLML` the serial work per panel -- apply panel k to block column k+1, factor
@@ -1079,28 +1120,23 @@ class GridLML(object):
     ``z = L^-1 y`` rides along as the augmented row N and is summed where its pieces come to rest; one
     all-reduce of (sum log L_ii, z.z, info) ends the evaluation.  ``fit`` returns the same ``(ll_data, logdet_half)`` on every
     rank.  ``grid = (1, W)`` is the 1-D block-column layout, ``(W, 1)`` a block-row layout.  ``compiled`` as for
-    :class:`DistributedLML`: the step loop below is recorded once per (look-ahead) as an op list and replayed by ``gpt_plan_run``
-    ("native": five RCCL channels per rank -- bulk rows / early block on the process row, inverse / column exchange on the process
-    column, head blocks on the whole grid) or by the Python interpreter of the list ("python"); False: the loop issues every
-    operation itself.  UNMEASURED ON MORE THAN ONE GPU:
-    gloo worlds 2-8 on CPU (tests/test_dist_gloo.py), ranks sharing one GPU through the product ops, and the modelled 8-rank
+    :class:`DistributedLML` (a model rank -- ``layout`` given -- runs the step loop by default): the step loop below is recorded
+    once per (look-ahead, channels on) as an op list and replayed by ``gpt_plan_run`` ("native": five RCCL channels per rank --
+    bulk rows / early block on the process row, inverse / column exchange on the process column, head blocks on the whole grid) or
+    by the Python interpreter of the list ("python"); False: the loop issues every operation itself.  UNMEASURED ON MORE THAN ONE
+    GPU: gloo worlds 2-8 on CPU (tests/test_dist_gloo.py), ranks sharing one GPU through the product ops, and the modelled 8-rank
     time of scratch/sim_model.py are what exists.
     """
-    NBUF = 4
+    _MODEL_STEP_LOOP = True
 
     # communication channels of a compiled schedule (queue names of the op list): what moves on which communicator
     CHANNEL = {"H": "comm", "R": "comm1", "R0": "comm2", "W": "comm3", "C": "comm4"}
 
     def __init__(self, X, n, grid, nb=512, group=None, ops=None, device=None, lookahead=True, layout=None, compiled=None):
-        if nb <= 0 or nb % 128:
-            raise ValueError("nb must be a positive multiple of 128")
         self.Pr, self.Pc = int(grid[0]), int(grid[1])
         if self.Pr < 1 or self.Pc < 1:
             raise ValueError("grid must be (P_r, P_c) with both >= 1")
-        self.group = group
-        inited = dist.is_initialized()
-        self.rank = dist.get_rank(group) if inited else 0
-        self.world = dist.get_world_size(group) if inited else 1
+        self.rank, self.world = _position(group)
         self._model = layout is not None
         if layout is not None:
             # position in the grid given explicitly: a subclass supplies ``_xbcast`` / ``_allreduce`` (scratch/sim_model.py
@@ -1109,18 +1145,13 @@ class GridLML(object):
         if self.world != self.Pr * self.Pc:
             raise ValueError("grid %d x %d needs %d ranks, the group has %d" % (self.Pr, self.Pc, self.Pr * self.Pc, self.world))
         self.pr, self.pc = divmod(self.rank, self.Pc)
-        if ops is None:
-            ops = HipPanelOps(0 if device is None else device)
-        self.ops = ops
-        self.device = getattr(ops, "device", torch.device("cpu"))
-        self.force_collectives = bool(int(os.environ.get("GPT_DIST_FORCE_COLLECTIVES", "0"))) and inited
-        self.lookahead = bool(lookahead)
+        _PanelEngine.__init__(self, X, n, nb, group, ops, device, lookahead, layout, compiled)
         # communicators: one per process row (panel rows), two per process column (the inverse of the diagonal block / the
         # column exchange: the latter must never queue behind a diagonal block that is still being factored), the whole grid
         # for the head blocks and the final reduction.  Every rank creates every group, in the same order.
         self.g_row = self.g_row0 = self.g_colw = self.g_colx = None
         self._ranks = list(range(self.world))
-        if inited and layout is None:
+        if dist.is_initialized() and layout is None:
             self._ranks = dist.get_process_group_ranks(group) if group is not None else list(range(dist.get_world_size()))
             if self.world > 1 or self.force_collectives:
                 for r in range(self.Pr):
@@ -1133,22 +1164,15 @@ class GridLML(object):
                     gw, gx = dist.new_group(ranks=members), dist.new_group(ranks=members)
                     if c == self.pc:
                         self.g_colw, self.g_colx = gw, gx
-        X = np.ascontiguousarray(X, dtype=np.float64)
-        n = np.ascontiguousarray(n, dtype=np.int32)
-        self.N, self.D = X.shape
-        self._n_maxsum = int(n.sum(axis=1).max()) if n.size else 0
-        self.nb = nb
-        self.NP = (self.N + 1 + nb - 1) // nb * nb
-        self.nblk = nblk = self.NP // nb
+        nb, nblk = self.nb, self.nblk
         self.my_rows = [I for I in range(nblk) if I % self.Pr == self.pr]
         self.my_cols = [J for J in range(nblk) if J % self.Pc == self.pc]
         self.my_blocks = [(I, J) for J in self.my_cols for I in self.my_rows if I >= J]
         self.nlr, self.nlc = len(self.my_rows), len(self.my_cols)
         self.lcm = self.Pr * self.Pc // math.gcd(self.Pr, self.Pc)
         dev = self.device
-        self.X = torch.from_numpy(X).to(dev)
-        self.n = torch.from_numpy(n).to(dev)
         # the rank's own block rows of X / n, gathered (zero rows stand for the padding beyond N)
+        X, n = np.asarray(X, dtype=np.float64), np.asarray(n, dtype=np.int32)
         Xr = np.zeros((max(self.nlr, 1) * nb, self.D))
         nr = np.zeros((max(self.nlr, 1) * nb, self.D), dtype=np.int32)
         for li, I in enumerate(self.my_rows):
@@ -1172,34 +1196,7 @@ class GridLML(object):
         # sized in whole blocks: one contributing row holds ceil(nlc / sc) of the rank's block columns (rows of
         # ceil(cols / sc) are not a whole number of blocks when nlc % sc != 0)
         self.piece = [[torch.empty((-(-max(self.nlc, 1) // sc) * nb, nb), **f64) for _ in range(nq)] for _ in range(self.NBUF)]
-        self.invd = torch.empty(((nb // 128) * 9216,), **f64)
-        self.info = torch.zeros((1,), dtype=torch.int32, device=dev)
-        self.y = torch.empty((self.NP,), **f64)
-        self.err = torch.zeros((self.NP,), **f64)
-        self.red = torch.zeros((3,), **f64)
         self.red_b = torch.zeros((3,), **f64)                 # the bulk queue's share of the two ll scalars (its own accumulator)
-        on_gpu = dev.type == "cuda"
-        self._h_in = torch.from_numpy(_lib.pinned_empty((2, self.NP), min_bytes=0)) if on_gpu else None
-        self._h_out = torch.from_numpy(_lib.pinned_empty((3,), min_bytes=0)) if on_gpu else None
-        self.timings = {}
-        self.trace = False
-        # compiled: as for DistributedLML -- "native" (gpt_plan_run replays the recorded op list, RCCL from the library: five
-        # communicators per rank), "python" (the same list through the Python interpreter + torch.distributed) or False (the step
-        # loop issues every operation; what a traced evaluation and the single-GPU model of scratch/ do).  None: "native" with the
-        # product ops on one rank, "python" on several (the native replay has not run on more than one GPU), False for a model.
-        env = os.environ.get("GPT_DIST_COMPILED")
-        if env is not None and layout is None:
-            compiled = False if env == "0" else env
-        if compiled is None:
-            one_rank = not inited or dist.get_world_size(group) == 1
-            compiled = False if layout is not None else ("native" if (isinstance(ops, HipPanelOps) and one_rank) else "python")
-        if compiled not in (False, "native", "python"):
-            raise ValueError("compiled must be None, False, 'native' or 'python'")
-        if compiled == "native" and not isinstance(ops, HipPanelOps):
-            raise ValueError("compiled='native' needs the product ops (HipPanelOps)")
-        self.compiled = compiled
-        self._plans = {}
-        self._rec = None
 
     # ---- index helpers ---------------------------------------------------------------------------
     def li_ge(self, I0):
@@ -1239,21 +1236,26 @@ class GridLML(object):
         gsrc = self._ranks[src[0] * self.Pc + src[1]]
         return [dist.broadcast(buf, src=gsrc, group=group, async_op=True)]
 
+    def _channel_table(self):
+        """(kind, communicator size, own position, torch group) of the five channels, in an order every rank shares."""
+        return (("H", self.world, self.rank, self.group), ("R", self.Pc, self.pc, self.g_row), ("R0", self.Pc, self.pc, self.g_row0),
+                ("W", self.Pr, self.pr, self.g_colw), ("C", self.Pr, self.pr, self.g_colx))
+
+    # ---- hooks of _PanelEngine ----
+    def _plan_key(self):
+        # (the op list holds the broadcasts of the channels that are on: force_collectives changes it)
+        return (self.compiled, self.lookahead, tuple(self._on(size) for _, size, _, _ in self._channel_table()))
+
     def _channels(self):
-        """The communicators of a native plan: (channel, ranks, own position, torch group carrying the id), in an order every
-        rank shares."""
+        """The communicators of a native plan: (channel, ranks, own position, torch group carrying the id)."""
         if self._model or not dist.is_initialized():
             return []
-        out = []
-        for kind, size, pos, group in (("H", self.world, self.rank, self.group), ("R", self.Pc, self.pc, self.g_row),
-                                       ("R0", self.Pc, self.pc, self.g_row0), ("W", self.Pr, self.pr, self.g_colw),
-                                       ("C", self.Pr, self.pr, self.g_colx)):
-            if self._on(size):
-                out.append((QUEUE_ID[self.CHANNEL[kind]] - 3, size, pos, group))
-        return out
+        return [(QUEUE_ID[self.CHANNEL[kind]] - 3, size, pos, group) for kind, size, pos, group in self._channel_table()
+                if self._on(size)]
 
-    def _allreduce(self, t, op):
-        dist.all_reduce(t, op=dist.ReduceOp.SUM if op == "sum" else dist.ReduceOp.MAX, group=self.group)
+    def _fold(self, red):
+        red[:2] += self.red_b[:2]            # the bulk queue's share (the chain queue is behind it, see _schedule)
+        return self.world > 1 or self.force_collectives or self._model      # (a model rank reduces through its own _allreduce)
 
     # ---- K build ----------------------------------------------------------------------------------
     def _assemble(self, kernel_id, params, noise_var, diag_add):
@@ -1276,58 +1278,9 @@ class GridLML(object):
             if last % self.Pr == self.pr:
                 ops.pad_block(A, lj, c0, nb, N, self.NP, self.y, BIG_PIVOT, row_shift=(last // self.Pr - last) * nb)
 
-    # ---- one evaluation -------------------------------------------------------------------------
-    def fit(self, kernel_id, params, y, err_y, noise_var=0.0, diag_factor=1e2):
-        """One LML evaluation; returns ``(ll_data, logdet_half)`` on every rank (``numpy.linalg.LinAlgError`` on every rank
-        if K_tot is not positive definite)."""
-        if kernel_id == _lib.KERNEL_M52 and self._n_maxsum > 1:
-            raise ValueError("Matern52Kernel only supports 0th and 1st order derivatives")      # ref matern.py:545-546
-        if kernel_id in (_lib.KERNEL_RQ, _lib.KERNEL_MATERN) and 2 * self._n_maxsum > 16:
-            raise ValueError("RationalQuadratic / Matern kernel: derivative orders of a pair sum to %d, the device builder "
-                             "supports 16" % (2 * self._n_maxsum))
-        t_host0 = time.perf_counter()
-        self._upload(y, err_y)
-        if self.compiled and not self.trace:
-            key = (self.compiled, self.lookahead)
-            plan = self._plans.get(key)
-            if plan is None:
-                # walk the step loop once against the recorder (nothing runs), then build the executor
-                real, rec = self.ops, PlanRecorder(self.device)
-                self.ops = self._rec = rec
-                try:
-                    self._schedule(None, None, 0.0, 0.0)
-                finally:
-                    self.ops, self._rec = real, None
-                plan = CompiledPlan(rec)
-                if self.compiled == "native":
-                    plan.build_native(real, self.X, self.n, self.err, self._channels())
-                self._plans[key] = plan
-                self.timings["plan_ops"] = len(plan.ops)
-            diag_add = diag_factor * sys.float_info.epsilon
-            if self.compiled == "native":
-                self.timings["native_enqueue_ms"] = plan.run_native(kernel_id, params, noise_var, diag_add)
-            else:
-                plan.run_python(self.ops, self, kernel_id, params, noise_var, diag_add)
-            return self._finish(t_host0)
-        self._schedule(kernel_id, params, noise_var, diag_factor)
-        return self._finish(t_host0)
-
     def _upload(self, y, err_y):
-        """Per-evaluation host traffic and resets, on the main queue: y | err_y up, info and the scalar accumulators to zero."""
-        ops, N = self.ops, self.N
-        y = np.ascontiguousarray(y, dtype=np.float64)
-        err_y = np.array(np.broadcast_to(err_y, (N,)), dtype=np.float64)
-        with ops.queue("main"):
-            if self._h_in is not None:
-                self._h_in[0, :N].copy_(torch.from_numpy(y))
-                self._h_in[1, :N].copy_(torch.from_numpy(err_y))
-                self.y[:N].copy_(self._h_in[0, :N], non_blocking=True)
-                self.err[:N].copy_(self._h_in[1, :N], non_blocking=True)
-            else:
-                self.y[:N] = torch.from_numpy(y)
-                self.err[:N] = torch.from_numpy(err_y)
-            self.info.zero_()
-            self.red.zero_()
+        _PanelEngine._upload(self, y, err_y)
+        with self.ops.queue("main"):
             self.red_b.zero_()          # (HERE, on the main queue in front of ev_asm: zeroed on the default stream it raced with the
                                         #  bulk queue's accumulation -- one evaluation in 72 lost part of z.z under queue jitter)
 
@@ -1336,14 +1289,7 @@ class GridLML(object):
         ops, N, nb, NP, nblk, NBUF = self.ops, self.N, self.nb, self.NP, self.nblk, self.NBUF
         Pr, Pc, pr, pc = self.Pr, self.Pc, self.pr, self.pc
         A, ld = self.A, self.A.stride(0)
-        with ops.queue("main"):
-            self._t0 = ops.new_timing_event() if (self.trace and self._rec is None) else None
-            if self._t0 is not None:
-                self._t0.record()
-            self._assemble(kernel_id, params, noise_var, diag_factor * sys.float_info.epsilon)
-            ev_asm = ops.new_event()
-            ev_asm.record()
-        self._marks = []
+        ev_asm = self._begin(kernel_id, params, noise_var, diag_factor)
         for q in ("panel", "recv"):
             with ops.queue(q):
                 ev_asm.wait()
@@ -1577,34 +1523,3 @@ class GridLML(object):
                 w_.wait()
             self._late = []
             ev_bulk_end.wait()
-
-    def _mark(self, k, tag):
-        if self._t0 is not None:
-            e = self.ops.new_timing_event()
-            e.record()
-            self._marks.append((k, tag, e))
-
-    def _finish(self, t_host0):
-        ops, N = self.ops, self.N
-        self.timings["host_enqueue_s"] = time.perf_counter() - t_host0
-        with ops.queue("panel"):
-            red = self.red
-            red[:2] += self.red_b[:2]
-            red[2] = self.info.to(torch.float64)[0]
-            if self.world > 1 or self.force_collectives or self._model:
-                info_t = red[2:3].clone()
-                self._allreduce(red[:2], "sum")
-                self._allreduce(info_t, "max")
-                red[2] = info_t[0]
-            if self._h_out is not None:
-                self._h_out.copy_(red, non_blocking=True)
-        ops.synchronize()
-        logdet_half, zz, info = (float(v) for v in (self._h_out if self._h_out is not None else red))
-        if self._t0 is not None:
-            self.timings["steps_ms"] = [(k, tag, self._t0.elapsed_ms(e)) for k, tag, e in self._marks]
-        if info != 0 and info <= N:
-            raise np.linalg.LinAlgError("%d-th leading minor of the array is not positive definite" % int(info))
-        ll_data = -0.5 * zz - logdet_half - 0.5 * N * math.log(2.0 * math.pi)
-        if info != 0 or not math.isfinite(ll_data):
-            raise np.linalg.LinAlgError("factorisation failed in the augmented row (non-finite y or K_tot?)")
-        return ll_data, logdet_half

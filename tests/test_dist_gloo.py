@@ -355,6 +355,49 @@ def test_grid_fit_matches_single_process_oracle(world, grid, N, d, nb, kid, look
     assert len({r[1] for r in out}) == 1 and len({r[2] for r in out}) == 1
 
 
+def _force_collectives_worker(rank, world, port, q):
+    os.environ["MASTER_ADDR"] = "127.0.0.1"
+    os.environ["MASTER_PORT"] = str(port)
+    dist.init_process_group("gloo", rank=rank, world_size=world)
+    try:
+        from gptools_amd.dist import GridLML
+        X, n, y = _inputs(700, 3)
+        p = np.array([1.0, 0.3, 0.3, 0.3])
+        plan = GridLML(X, n, (1, 2), nb=128, ops=_numpy_ops(), compiled="python")
+        res = plan.fit(1, p, y, 0.05)
+        plan.force_collectives = True            # the process columns' (1-rank) broadcasts join the op list
+        res2 = plan.fit(1, 1.1 * p, y, 0.05)
+        q.put((rank, res, res2, len(plan._plans)))
+    finally:
+        dist.destroy_process_group()
+
+
+def test_grid_plan_follows_force_collectives():
+    """A compiled GridLML plan is keyed by which of its channels carry collectives: switching ``force_collectives`` on after the
+    first evaluation records a second plan instead of replaying the first, and the result still matches the oracle."""
+    from oracle import oracle as O
+    world = 2
+    ctx = mp.get_context("spawn")
+    q = ctx.Queue()
+    port = _free_port()
+    procs = [ctx.Process(target=_force_collectives_worker, args=(r, world, port, q)) for r in range(world)]
+    for p in procs:
+        p.start()
+    out = [q.get(timeout=180) for _ in range(world)]
+    for p in procs:
+        p.join(timeout=60)
+        assert p.exitcode == 0
+    X, n, y = _inputs(700, 3)
+    p = np.array([1.0, 0.3, 0.3, 0.3])
+    ref = O.fit(1, p, X, n, y, 0.05 * np.ones(700))
+    ref2 = O.fit(1, 1.1 * p, X, n, y, 0.05 * np.ones(700))
+    for rank, res, res2, nplans in out:
+        assert nplans == 2, (rank, nplans)
+        assert abs(res[0] - ref["ll_data"]) <= 1e-9 * abs(ref["ll_data"]), (rank, res, ref["ll_data"])
+        assert abs(res2[0] - ref2["ll_data"]) <= 1e-9 * abs(ref2["ll_data"]), (rank, res2, ref2["ll_data"])
+        assert abs(res2[1] - ref2["logdet_half"]) <= 1e-10 * abs(ref2["logdet_half"])
+
+
 def test_grid_not_positive_definite_raises_on_every_rank():
     for grid, world in (((2, 2), 4), ((2, 4), 8)):
         out = _run(world, 300, 2, 128, 0, True, bad=True, plan_kw={"grid": grid})
