@@ -48,6 +48,7 @@ SIGNATURES = {
     "gpt_mem_info": (C.c_int, [_vp, C.POINTER(_i64), C.POINTER(_i64)]),
     "gpt_release_batch_scratch": (C.c_int, [_vp]),
     "gpt_fit_batch_terms": (C.c_int, [_vp, C.c_int, C.c_int, _ip, _ip, _dp, _ip, _ip, _dp, _dp, _dp, C.c_double, _dp, _dp, _ip]),
+    "gpt_predict_batch": (C.c_int, [_vp, _dp, _ip, _i64, _ip, _ip, _dp, _dp, _dp, _dp]),
     "gpt_fit_matrix": (C.c_int, [_vp, _dp, _i64, _dp, _dp, _dp]),
     "gpt_get_L": (C.c_int, [_vp, _dp]),
     "gpt_get_alpha": (C.c_int, [_vp, _dp]),
@@ -425,6 +426,22 @@ class Context(object):
         check(self._lib.gpt_fit_batch_terms(self.handle, B, len(ids), iptr(ids), iptr(ids2), dptr(params), iptr(npar), iptr(npar1),
                                             dptr(noise_var), dptr(y), dptr(err_y), float(diag_add), dptr(ll), dptr(ld), iptr(info)))
         return ll, ld, info
+
+    def predict_batch(self, Xstar, nstar, keep, noise_n=None, want_var=True, want_cov=False, want_cov_sum=False):
+        """gpt_predict_batch: prediction at ``Xstar`` (M, D) from every element of the resident batch (the last
+        :meth:`fit_batch_terms` and its kin); ``keep`` (B,) -- 0 skips an element (its rows stay NaN here).  Returns
+        ``(mean (B, M), var (B, M) or None, cov (B, M, M) or None, cov_sum (M, M) or None)``, ``cov_sum`` the sum of the kept
+        elements' covariances."""
+        Xstar, nstar, keep = f64(Xstar), i32(nstar), i32(np.asarray(keep) != 0)
+        B, M = keep.shape[0], Xstar.shape[0]
+        mean = np.full((B, M), np.nan)
+        var = np.full((B, M), np.nan) if want_var else None
+        cov = np.full((B, M, M), np.nan) if want_cov else None
+        cov_sum = np.empty((M, M)) if want_cov_sum else None
+        nn = None if noise_n is None else i32(np.asarray(noise_n).reshape(-1))
+        check(self._lib.gpt_predict_batch(self.handle, dptr(Xstar), iptr(nstar), M, iptr(nn), iptr(keep), dptr(mean), dptr(var),
+                                          dptr(cov), dptr(cov_sum)))
+        return mean, var, cov, cov_sum
 
     def mem_info(self):
         """(free, total) bytes of this context's GPU."""

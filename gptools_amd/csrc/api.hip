@@ -45,7 +45,8 @@ struct DevBuf {
 
 enum { SLOT_XI = 0, SLOT_XJ, SLOT_NI, SLOT_NJ, SLOT_OUT, SLOT_KST, SLOT_KSS, SLOT_XS, SLOT_NS, SLOT_VEC, SLOT_VEC2,
        SLOT_RHS, SLOT_LOW, SLOT_KFULL, SLOT_TK, SLOT_ZERO, SLOT_UINV, SLOT_WINV, SLOT_GPART, SLOT_BINV, SLOT_BTMP,
-       SLOT_BINV2, SLOT_BINV3, SLOT_BINV3U, SLOT_BINVU, SLOT_BATCH_A, SLOT_BATCH_WS, SLOT_BATCH_MISC, SLOT_SPLITK, SLOT_COUNT };
+       SLOT_BINV2, SLOT_BINV3, SLOT_BINV3U, SLOT_BINVU, SLOT_BATCH_A, SLOT_BATCH_WS, SLOT_BATCH_MISC, SLOT_SPLITK,
+       SLOT_PB_V, SLOT_PB_COV, SLOT_PB_MISC, SLOT_COUNT };
 
 struct gpt_ctx {
     int device = 0;
@@ -159,6 +160,16 @@ struct gpt_ctx {
     hipEvent_t cev[4] = {nullptr, nullptr, nullptr, nullptr};
     double *h_batch = nullptr;         // pinned staging of gpt_fit_batch (y, KParams, noise variances, err_y in; results out)
     size_t h_batch_cap = 0;
+    // The RESIDENT BATCH: what the last successful gpt_fit_batch* left in SLOT_BATCH_A (factors, augmented row z_b) and
+    // SLOT_BATCH_WS (the leaves' packed workspaces), for gpt_predict_batch.  Valid while rb_nbatch > 0 and rb_gen == batch_gen:
+    // everything that frees, reuses or outdates those slots (gpt_set_data, gpt_set_T, gpt_release_batch_scratch, gpt_cov_sample,
+    // the next gpt_fit_batch* until it succeeds) advances batch_gen.
+    uint64_t batch_gen = 1, rb_gen = 0;
+    int rb_nbatch = 0, rb_nterms = 0;
+    int64_t rb_N = 0;
+    bool rb_any_prod = false;
+    std::vector<KParams> rb_kp, rb_kp2;   // term-major [t][b]; rb_kp2 (product terms, kernel_id -1 elsewhere) only with rb_any_prod
+    std::vector<double> rb_nv;            // element noise variances
     int64_t cov_M = 0;                 // > 0: SLOT_KSS holds the lower triangle of the predictive covariance of the last gpt_predict(want = 2, cov_out = NULL)
     KParams kp;                      // first term (single-kernel paths)
     std::vector<KParams> terms;      // the model kernel as a sum of native kernels (gpt_fit_sum)

@@ -123,6 +123,7 @@ static int fit_batch_impl(gpt_ctx *c, int nbatch, int nterms, const int *kernel_
             pb += nparams_t[t];
         }
     }
+    c->batch_gen++;                          // (the resident batch is overwritten: valid again once this call has succeeded)
     // device scratch: the nbatch matrices to factor (+ with a transform every element's K over the latent points and T K)
     const int64_t NxP = c->dT ? c->NxP : 0, NyP = c->dT ? round_up(N, 64) : 0;
     const size_t kfull = (size_t)NxP * NxP, tk = (size_t)NyP * NxP;
@@ -207,6 +208,185 @@ static int fit_batch_impl(gpt_ctx *c, int nbatch, int nterms, const int *kernel_
         info_out[b] = info;
         ll_data_out[b] = ll;
         if (logdet_half_out) logdet_half_out[b] = logdet_half;
+    }
+    // the batch is resident now (gpt_predict_batch): its KParams and noise variances as the device got them
+    const KParams *hk = reinterpret_cast<const KParams *>(hkp);
+    c->rb_kp.assign(hk, hk + (size_t)nterms * nbatch);
+    if (any_prod) c->rb_kp2.assign(hk + (size_t)nterms * nbatch, hk + 2 * (size_t)nterms * nbatch);
+    else c->rb_kp2.clear();
+    c->rb_nv.assign(noise_var, noise_var + nbatch);
+    c->rb_nbatch = nbatch;
+    c->rb_nterms = nterms;
+    c->rb_any_prod = any_prod;
+    c->rb_N = N;
+    c->rb_gen = c->batch_gen;
+    return GPT_OK;
+}
+
+// ------------------------------------------------------------------------------------------------
+// the predictive half of a resident batch
+// ------------------------------------------------------------------------------------------------
+// Prediction at M test points from every element of the batch the last gpt_fit_batch* left resident -- the reference's
+// marginalisation over a hyperparameter trace (ref: gaussian_process.py:1840-1987, :2144-2254: one update_hyperparameters + predict
+// per trace row) at the sizes where one prediction cannot fill the GPU.  Per element b (as gpt_predict, the mean from z_b):
+//   V_b = K*_b^T L_b^-T,  mean_b = V_b z_b,  var_b = diag K**_b - rowsumsq(V_b),  cov_b = K**_b - V_b V_b^T.
+// Layout: V is MP x (nbatch NP), element b in columns [b NP, (b + 1) NP) -- so that the summed covariance
+//   sum_b keep_b cov_b = (sum_b keep_b K**_b) - V V^T
+// is ONE lower-triangular GEMM whose contraction runs over (b, i).  Launches, all batched over the elements:
+//   the cross-covariance K*_b^T into V (builder, one launch per term); the forward substitution left-looking over the 128-column
+//   leaves (GEMM against the leaves before, then the panel TRSM against the workspace the fit left; the same kernels as the fit);
+//   diag K**_b (pair kernel); one fused read of V for mean and variance, which also zeroes the columns >= N of every row (the
+//   augmented column and the padding of the last leaf) and the rows of skipped elements; then either the summed covariance
+//   (one pass over the M x M triangle for sum_b K**_b, the GEMM, a mirror) or the per-element covariances (batched builder +
+//   batched GEMM).
+static int gemm_nt_few(gpt_ctx *c, hipStream_t st, int64_t m, int64_t n, int64_t k, double alpha, const double *A, int64_t lda,
+                       const double *B, int64_t ldb, double beta, double *C, int64_t ldc, int tri);      // (api_solve.inc)
+extern "C" int gpt_predict_batch(gpt_ctx *c, const double *Xstar, const int32_t *nstar, int64_t M, const int32_t *noise_n,
+                                 const int32_t *keep, double *mean_out, double *var_out, double *cov_out, double *cov_sum_out)
+{
+    CTX_ENTER(c);
+    if (c->rb_nbatch <= 0 || c->rb_gen != c->batch_gen) {
+        gpt_set_error("gpt_predict_batch: no batch resident (call gpt_fit_batch* first; gpt_set_data, gpt_set_T, gpt_cov_sample and "
+                      "gpt_release_batch_scratch end its residency)");
+        return GPT_E_STATE;
+    }
+    if (c->dT) {
+        gpt_set_error("gpt_predict_batch: not implemented with a linear transform (gpt_set_T)");
+        return GPT_E_NOTIMPL;
+    }
+    if (M <= 0 || M > 65535 * 32 || !Xstar || !nstar || !keep || !mean_out) {
+        gpt_set_error("gpt_predict_batch: bad arguments");
+        return GPT_E_ARG;
+    }
+    const int D = c->D, nbatch = c->rb_nbatch, nterms = c->rb_nterms;
+    const int64_t N = c->rb_N, NP = round_up(N + 1, 128), nleaf = NP / 128, bs = NP * NP, bws = nleaf * GPT_WS_BLOCK;
+    const int64_t MP = round_up(M, 64), ldv = (int64_t)nbatch * NP;
+    // derivative orders of the test points: the checks of gpt_predict, for the first element's kernels (all elements share them)
+    {
+        bool m52 = false, chain = c->rb_any_prod;
+        for (int t = 0; t < nterms; t++) {
+            const int k1 = c->rb_kp[(size_t)t * nbatch].kernel_id;
+            const int k2 = c->rb_any_prod ? c->rb_kp2[(size_t)t * nbatch].kernel_id : -1;
+            m52 = m52 || k1 == GPT_KERNEL_M52 || k2 == GPT_KERNEL_M52;
+            chain = chain || k1 == GPT_KERNEL_RQ || k1 == GPT_KERNEL_MATERN;
+        }
+        if (m52) GPT_TRY(check_m52_orders(nstar, M, D));
+        if (chain) {
+            long ms = 0;
+            for (int64_t i = 0; i < M; i++) {
+                long sn = 0;
+                for (int d = 0; d < D; d++) sn += nstar[i * D + d];
+                if (sn > ms) ms = sn;
+            }
+            if (ms + (ms > c->n_maxsum ? ms : c->n_maxsum) > GPT_RQ_MAXORD) {
+                gpt_set_error("RationalQuadraticKernel: derivative orders of a pair sum to more than %d", GPT_RQ_MAXORD);
+                return GPT_E_VALUE;
+            }
+        }
+    }
+    double noise_sum = 0.0;
+    for (int b = 0; b < nbatch; b++)
+        if (keep[b]) noise_sum += c->rb_nv[b];
+    std::vector<int32_t> hit((size_t)M, 0);
+    if (noise_n)
+        for (int64_t a = 0; a < M; a++) {
+            bool h = true;
+            for (int d = 0; d < D; d++) h = h && nstar[a * D + d] == noise_n[d];
+            hit[a] = h ? 1 : 0;
+        }
+    // device inputs in one slot: [KParams (| second factors) | noise variances: nbatch | keep: nbatch | hit: M | X*: M D | n*: M D],
+    // then [mean | var]
+    const size_t nkp = (size_t)nterms * nbatch * (c->rb_any_prod ? 2 : 1);
+    const size_t b_kp = nkp * sizeof(KParams) + (size_t)nbatch * 8, b_keep = round_up(nbatch, 2) * 4, b_hit = round_up(M, 2) * 4,
+                 b_xs = (size_t)M * D * 8, b_ns = round_up(M * D, 2) * 4;
+    const size_t o_keep = b_kp, o_hit = o_keep + b_keep, o_xs = o_hit + b_hit, o_ns = o_xs + b_xs, o_mv = o_ns + b_ns;
+    const size_t b_mv = 2 * (size_t)nbatch * MP * 8;
+    char *dmisc;
+    GPT_TRY(ensure(c, SLOT_PB_MISC, o_mv + b_mv, (void **)&dmisc));
+    std::vector<char> hin(o_mv);
+    memcpy(hin.data(), c->rb_kp.data(), (size_t)nterms * nbatch * sizeof(KParams));
+    if (c->rb_any_prod) memcpy(hin.data() + (size_t)nterms * nbatch * sizeof(KParams), c->rb_kp2.data(), (size_t)nterms * nbatch * sizeof(KParams));
+    memcpy(hin.data() + nkp * sizeof(KParams), c->rb_nv.data(), (size_t)nbatch * 8);
+    memcpy(hin.data() + o_keep, keep, (size_t)nbatch * 4);
+    memcpy(hin.data() + o_hit, hit.data(), (size_t)M * 4);
+    memcpy(hin.data() + o_xs, Xstar, b_xs);
+    memcpy(hin.data() + o_ns, nstar, (size_t)M * D * 4);
+    const KParams *dkp = reinterpret_cast<const KParams *>(dmisc);
+    const KParams *dkp2 = c->rb_any_prod ? dkp + (size_t)nterms * nbatch : nullptr;
+    const double *dnv = reinterpret_cast<const double *>(dmisc + nkp * sizeof(KParams));
+    const int32_t *dkeep = reinterpret_cast<const int32_t *>(dmisc + o_keep), *dhit = reinterpret_cast<const int32_t *>(dmisc + o_hit);
+    const double *dXs = reinterpret_cast<const double *>(dmisc + o_xs);
+    const int32_t *dns = reinterpret_cast<const int32_t *>(dmisc + o_ns);
+    double *dmean = reinterpret_cast<double *>(dmisc + o_mv), *dvar = dmean + (size_t)nbatch * MP;
+    double *dV, *dC = nullptr;
+    GPT_TRY(ensure(c, SLOT_PB_V, (size_t)MP * ldv * sizeof(double), (void **)&dV));
+    const bool want_cov = cov_out != nullptr, want_sum = cov_sum_out != nullptr;
+    if (want_cov || want_sum)
+        GPT_TRY(ensure(c, SLOT_PB_COV, (want_cov ? (size_t)nbatch : 1) * MP * MP * sizeof(double), (void **)&dC));
+    const double *dA = (const double *)c->slots[SLOT_BATCH_A].p, *dws = (const double *)c->slots[SLOT_BATCH_WS].p;
+    EvalScope scope(c, true);
+    hipStream_t st = c->panel_stream;                      // (unmasked, as the fit)
+    {
+        hipEvent_t e = get_event(c, 0);
+        if (!e) return GPT_E_HIP;
+        GPT_HIP_CHECK(hipEventRecord(e, c->stream));
+        GPT_HIP_CHECK(hipStreamWaitEvent(st, e, 0));
+    }
+    GPT_HIP_CHECK(hipMemcpyAsync(dmisc, hin.data(), o_mv, hipMemcpyHostToDevice, st));
+    auto term_kp2 = [&](int t) -> const KParams * {
+        return (c->rb_any_prod && c->rb_kp2[(size_t)t * nbatch].kernel_id >= 0) ? dkp2 + (size_t)t * nbatch : nullptr;
+    };
+    // K*_b^T (M x N per element) into V, zeros elsewhere
+    GPT_TRY(launch_zero2d(st, MP, ldv, dV, ldv));
+    for (int t = 0; t < nterms; t++)
+        GPT_TRY(launch_kbuild_batch_cross(st, c->rb_kp[(size_t)t * nbatch].kernel_id, D, dkp + (size_t)t * nbatch, dnv, nbatch, dXs, dns,
+                                          M, c->dX, c->dn, N, dV, ldv, NP, t > 0 ? 1 : 0, term_kp2(t)));
+    // V_b = K*_b^T L_b^-T, left-looking over the leaves: leaf j first receives the update of all leaves before it
+    for (int64_t lc = 0; lc < NP; lc += 128) {
+        if (lc > 0)
+            GPT_TRY(launch_gemm_nt(st, MP, 128, lc, -1.0, dV, ldv, dA + lc * NP, NP, 1.0, dV + lc, ldv, 0, 0, 0, nullptr, nullptr, 0,
+                                   EdgeSig(), EdgeSig(), 0, nbatch, NP, EdgeSig(), bs, NP));
+        GPT_TRY(launch_trsm_panel(st, MP, nullptr, 0, dws + (lc / 128) * GPT_WS_BLOCK, dV + lc, ldv, nullptr, EdgeSig(), nbatch, NP, bws));
+    }
+    GPT_TRY(launch_kdiag_batch(st, D, nterms, dkp, dkp2, nbatch, dXs, dns, M, dvar, MP));
+    GPT_TRY(launch_batch_meanvar(st, M, MP, N, NP, nbatch, dV, ldv, dA, bs, dkeep, dmean, dvar, MP));
+    std::vector<double> hmv(2 * (size_t)nbatch * MP);
+    GPT_HIP_CHECK(hipMemcpyAsync(hmv.data(), dmean, hmv.size() * sizeof(double), hipMemcpyDeviceToHost, st));
+    if (want_sum) {
+        GPT_TRY(launch_zero2d(st, MP, MP, dC, MP));
+        GPT_TRY(launch_kss_sum(st, D, nterms, dkp, dkp2, nbatch, dkeep, dXs, dns, M, MP, noise_n ? dhit : nullptr, noise_sum, dC, MP));
+        // (k = nbatch NP against few output tiles: split along k where that pays, as the few-rows solves do)
+        GPT_TRY(gemm_nt_few(c, st, MP, MP, ldv, -1.0, dV, ldv, dV, ldv, 1.0, dC, MP, 1));
+        GPT_TRY(launch_mirror_rows(st, dC, MP, 0, MP, MP));
+        GPT_HIP_CHECK(hipMemcpy2DAsync(cov_sum_out, (size_t)M * sizeof(double), dC, (size_t)MP * sizeof(double), (size_t)M * sizeof(double),
+                                       (size_t)M, hipMemcpyDeviceToHost, st));
+    }
+    GPT_HIP_CHECK(hipStreamSynchronize(st));
+    if (want_cov) {
+        // per element: K**_b (whole square, batched builder) - V_b V_b^T (batched GEMM)
+        const int64_t cs = MP * MP;
+        GPT_TRY(launch_zero2d(st, (int64_t)nbatch * MP, MP, dC, MP));
+        for (int t = 0; t < nterms; t++)
+            GPT_TRY(launch_kbuild_batch_cross(st, c->rb_kp[(size_t)t * nbatch].kernel_id, D, dkp + (size_t)t * nbatch, dnv, nbatch, dXs,
+                                              dns, M, dXs, dns, M, dC, MP, cs, t > 0 ? 1 : 0, term_kp2(t)));
+        GPT_TRY(launch_gemm_nt(st, MP, MP, NP, -1.0, dV, ldv, dV, ldv, 1.0, dC, MP, 0, 0, 0, nullptr, nullptr, 0, EdgeSig(), EdgeSig(), 0,
+                               nbatch, NP, EdgeSig(), NP, cs));
+        for (int b = 0; b < nbatch; b++)
+            if (keep[b])
+                GPT_HIP_CHECK(hipMemcpy2DAsync(cov_out + (size_t)b * M * M, (size_t)M * sizeof(double), dC + (size_t)b * cs,
+                                               (size_t)MP * sizeof(double), (size_t)M * sizeof(double), (size_t)M, hipMemcpyDeviceToHost, st));
+        GPT_HIP_CHECK(hipStreamSynchronize(st));
+    }
+    for (int b = 0; b < nbatch; b++) {
+        if (!keep[b]) continue;
+        const double *hm = hmv.data() + (size_t)b * MP, *hv = hm + (size_t)nbatch * MP;
+        memcpy(mean_out + (size_t)b * M, hm, (size_t)M * sizeof(double));
+        const double nv = c->rb_nv[b];
+        if (var_out)
+            for (int64_t a = 0; a < M; a++) var_out[(size_t)b * M + a] = hv[a] + (hit[a] ? nv : 0.0);
+        if (cov_out && noise_n)
+            for (int64_t a = 0; a < M; a++)
+                if (hit[a]) cov_out[(size_t)b * M * M + (size_t)a * M + a] += nv;
     }
     return GPT_OK;
 }

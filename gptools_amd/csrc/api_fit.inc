@@ -32,6 +32,7 @@ extern "C" int gpt_set_data(gpt_ctx *c, const double *X, const int32_t *n, int64
     c->factored = false;
     c->h_alpha_valid = c->alpha_valid = c->binv_valid = c->binv2_valid = c->binv3_valid = false;
     c->have_kernel = false;
+    c->batch_gen++;                     // (the resident batch was fitted to the old data)
     if (c->dT) hipFree(c->dT);          // a transform belongs to one data set
     c->dT = nullptr;
     c->Ny = 0;
@@ -55,6 +56,7 @@ extern "C" int gpt_set_T(gpt_ctx *c, const double *T, int64_t Ny)
     c->factored = false;
     c->h_alpha_valid = c->alpha_valid = c->binv_valid = c->binv2_valid = c->binv3_valid = false;
     c->have_kernel = false;
+    c->batch_gen++;
     if (!T || Ny <= 0) return GPT_OK;
     const int64_t NyP = round_up(Ny, 64), NxP = round_up(c->Nx, 16);
     GPT_HIP_CHECK(hipMalloc(&c->dT, (size_t)NyP * NxP * sizeof(double)));

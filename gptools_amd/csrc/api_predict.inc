@@ -186,6 +186,7 @@ extern "C" int gpt_cov_sample(gpt_ctx *c, int64_t M_rows, double diag_add, const
     GPT_TRY(ensure(c, SLOT_RHS, (size_t)SP * LDC * sizeof(double), (void **)&dRt));
     GPT_TRY(ensure(c, SLOT_OUT, (size_t)LDC * SP * sizeof(double), (void **)&dOut));
     c->cov_M = 0;                                                    // (the covariance is consumed)
+    c->batch_gen++;                                                  // (SLOT_BATCH_WS is reused below: no batch resident any more)
     EvalScope scope(c, true);                                        // counted like an evaluation in flight, on event edges
     GPT_HIP_CHECK(hipMemsetAsync(dzero, 0, (size_t)M * sizeof(double), st));
     GPT_HIP_CHECK(hipMemsetAsync(dinfo, 0, sizeof(int32_t), st));

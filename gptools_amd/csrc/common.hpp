@@ -157,15 +157,29 @@ int launch_gemm_nt_gridstair(hipStream_t st, int64_t m, int64_t nseg, int64_t se
 int launch_potf2_trsm(hipStream_t st, double *A, int64_t lda, double *invd, int32_t *info, int64_t info_base, int64_t m,
                       unsigned *flag, unsigned flag_base, hipEvent_t done = nullptr, EdgeSig edge = EdgeSig(),
                       EdgeSig wait = EdgeSig(), int rows64 = 0);
+// (batched: element y of the grid works on B + y * bstride_b with the workspace invd + y * bstride_ws; L itself is never read --
+// the packed workspace carries the block -- so B's stride is the only matrix stride: inside the factor for the batched fit,
+// the element's columns of V for gpt_predict_batch)
 int launch_trsm_panel(hipStream_t st, int64_t m, const double *L, int64_t ldl, const double *invd,
                       double *B, int64_t ldb, hipEvent_t done = nullptr, EdgeSig edge = EdgeSig(), int64_t nbatch = 1,
-                      int64_t bstride_a = 0, int64_t bstride_ws = 0);
+                      int64_t bstride_b = 0, int64_t bstride_ws = 0);
 // batched small fits (gpt_fit_batch)
 int launch_kbuild_batch(hipStream_t st, int kernel_id, int D, const KParams *d_kps, const double *d_noise_var, int64_t nbatch,
                         const double *dX, const int32_t *dn, int64_t N, const double *d_err_y, double diag_add, double *dK,
                         int64_t ldk, int64_t bstride, int accumulate = 0, int full = 0, const KParams *d_kps2 = nullptr);
 int launch_batch_pad(hipStream_t st, const double *h_y, int64_t nbatch, double *A, int64_t lda, int64_t bstride, int64_t n_valid,
                      int64_t n_pad, double big, int32_t *info);
+// the predictive half of a resident batch (gpt_predict_batch)
+int launch_kbuild_batch_cross(hipStream_t st, int kernel_id, int D, const KParams *d_kps, const double *d_nv, int64_t nbatch,
+                              const double *dXi, const int32_t *dni, int64_t M, const double *dXj, const int32_t *dnj, int64_t P, double *dK,
+                              int64_t ldk, int64_t bstride, int accumulate = 0, const KParams *d_kps2 = nullptr);
+int launch_kdiag_batch(hipStream_t st, int D, int nterms, const KParams *d_kps, const KParams *d_kps2, int64_t nbatch, const double *dX,
+                       const int32_t *dn, int64_t M, double *dout, int64_t ldo);
+int launch_kss_sum(hipStream_t st, int D, int nterms, const KParams *d_kps, const KParams *d_kps2, int64_t nbatch, const int32_t *d_keep,
+                   const double *dX, const int32_t *dn, int64_t M, int64_t MP, const int32_t *d_hit, double noise_sum, double *dC,
+                   int64_t ldc);
+int launch_batch_meanvar(hipStream_t st, int64_t M, int64_t MP, int64_t N, int64_t NP, int64_t nbatch, double *V, int64_t ldv,
+                         const double *A, int64_t bs, const int32_t *keep, double *mean, double *var, int64_t ld);
 int launch_batch_logdet_dot(hipStream_t st, const double *A, int64_t lda, int64_t bstride, int64_t n, int64_t nbatch,
                             const int32_t *d_info, double *out3);
 #define GPT_GRAD_MAXH 8

@@ -1471,7 +1471,7 @@ __global__ __launch_bounds__(64 * TP_WAVES, 2) void trsm_panel_kernel(int64_t m,
 }
 
 int launch_trsm_panel(hipStream_t st, int64_t m, const double *L, int64_t ldl, const double *invd, double *B,
-                      int64_t ldb, hipEvent_t done, EdgeSig edge, int64_t nbatch, int64_t bstride_a, int64_t bstride_ws)
+                      int64_t ldb, hipEvent_t done, EdgeSig edge, int64_t nbatch, int64_t bstride_b, int64_t bstride_ws)
 {
     gpt_jitter(st);
     if (m <= 0) {
@@ -1491,9 +1491,9 @@ int launch_trsm_panel(hipStream_t st, int64_t m, const double *L, int64_t ldl, c
     // `done` rides on the kernel's own completion signal (hipExtLaunchKernelGGL stop event): a separate
     // hipEventRecord would put a barrier packet -- ~6 us of command-processor time -- on the panel chain
     if (done) hipExtLaunchKernelGGL(trsm_panel_kernel, dim3(grid, (unsigned)nbatch), dim3(64 * TP_WAVES), 0, st, nullptr, done, 0, m, L, ldl,
-                                    invd, B, ldb, edge.word, edge.value, bstride_a, bstride_ws);
+                                    invd, B, ldb, edge.word, edge.value, bstride_b, bstride_ws);
     else hipLaunchKernelGGL(trsm_panel_kernel, dim3(grid, (unsigned)nbatch), dim3(64 * TP_WAVES), 0, st, m, L, ldl, invd, B, ldb, edge.word,
-                            edge.value, bstride_a, bstride_ws);
+                            edge.value, bstride_b, bstride_ws);
     GPT_LAUNCH_CHECK();
     return GPT_OK;
 }

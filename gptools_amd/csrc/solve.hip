@@ -936,3 +936,50 @@ int launch_row_sumsq(hipStream_t st, const double *row, int64_t w, double *acc)
     GPT_LAUNCH_CHECK();
     return GPT_OK;
 }
+
+// gpt_predict_batch: mean and variance of every element from ONE read of its rows of V = K*^T L^-T.  V is MP x (nbatch NP),
+// element b in columns [b NP, b NP + NP); z_b = L_b^-1 y_b is the augmented row N of element b's factor (A + b bs + N NP).
+//   mean[b ld + a] = V_b[a, :N] . z_b,   var[b ld + a] -= |V_b[a, :N]|^2   (var holds diag K**_b on entry)
+// and the row's columns [N, NP) are set to exactly zero behind the read (the augmented column and the padding of the last leaf),
+// the whole row of a skipped element (keep[b] == 0) too: then sum_b V_b V_b^T is one GEMM over all columns.  One wave per row.
+__global__ __launch_bounds__(256) void batch_meanvar_kernel(int64_t M, int64_t MP, int64_t N, int64_t NP, double *__restrict__ V,
+                                                            int64_t ldv, const double *__restrict__ A, int64_t bs,
+                                                            const int32_t *__restrict__ keep, double *__restrict__ mean,
+                                                            double *__restrict__ var, int64_t ld)
+{
+    const int lane = threadIdx.x & 63;
+    const int64_t a = (int64_t)blockIdx.x * 4 + (threadIdx.x >> 6), b = blockIdx.y;
+    if (a >= MP) return;
+    double *row = V + a * ldv + b * NP;
+    if (!keep[b]) {
+        for (int64_t i = lane; i < NP; i += 64) row[i] = 0.0;
+        return;
+    }
+    const double *z = A + b * bs + N * NP;
+    double s = 0.0, q = 0.0;
+    for (int64_t i = lane; i < N; i += 64) {
+        const double v = row[i];
+        s = fma(v, z[i], s);
+        q = fma(v, v, q);
+    }
+    for (int64_t i = N + lane; i < NP; i += 64) row[i] = 0.0;
+#pragma unroll
+    for (int off = 32; off > 0; off >>= 1) {
+        s += __shfl_xor(s, off, 64);
+        q += __shfl_xor(q, off, 64);
+    }
+    if (lane == 0 && a < M) {
+        mean[b * ld + a] = s;
+        var[b * ld + a] -= q;
+    }
+}
+
+int launch_batch_meanvar(hipStream_t st, int64_t M, int64_t MP, int64_t N, int64_t NP, int64_t nbatch, double *V, int64_t ldv,
+                         const double *A, int64_t bs, const int32_t *keep, double *mean, double *var, int64_t ld)
+{
+    if (MP <= 0 || nbatch <= 0) return GPT_OK;
+    hipLaunchKernelGGL(batch_meanvar_kernel, dim3((unsigned)((MP + 3) / 4), (unsigned)nbatch), dim3(256), 0, st, M, MP, N, NP, V, ldv, A,
+                       bs, keep, mean, var, ld);
+    GPT_LAUNCH_CHECK();
+    return GPT_OK;
+}

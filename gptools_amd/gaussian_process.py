@@ -870,11 +870,23 @@ class GaussianProcess(object):
         """Predictive mean (and std / covariance) at ``Xstar`` (M, D) for derivative orders ``n``.
 
         Returns ``mean``, ``(mean, std)``, ``(mean, cov)`` or the ``full_output`` dict exactly like the
-        reference's non-MCMC branch (``return_samples`` / ``full_MC`` draw through :meth:`draw_sample`); marginalising
-        the hyperparameters by MCMC is outside the accelerated path."""
+        reference's non-MCMC branch (``return_samples`` / ``full_MC`` draw through :meth:`draw_sample`).  ``use_MCMC``:
+        the prediction marginalised over a trace of the hyperparameters -- :meth:`predict_MCMC` with ``flat_trace`` (or
+        ``sampler``), ``burn``, ``thin`` among the keyword arguments, as the reference forwards it (ref :888-912)."""
         if use_MCMC:
-            raise NotImplementedError("MCMC marginalisation of the hyperparameters is outside the accelerated hot "
-                                      "path (SURVEY.md section 8).")
+            res = self.predict_MCMC(Xstar, n=n, noise=noise, return_std=return_std or full_output,
+                                    return_cov=return_cov or full_output,
+                                    return_samples=full_output and bool(return_samples or rejection_func),
+                                    return_mean_func=full_output and return_mean_func, num_samples=num_samples,
+                                    samp_kwargs=samp_kwargs, full_MC=full_MC, rejection_func=rejection_func, ddof=ddof,
+                                    output_transform=output_transform, **kwargs)
+            if full_output:
+                return res
+            if return_cov:
+                return (res["mean"], res["cov"])
+            if return_std:
+                return (res["mean"], res["std"])
+            return res["mean"]
         Xstar, n, output_transform = self._check_predict_args(Xstar, n, output_transform)
         self.compute_K_L_alpha_ll()
         need_cov = (return_cov or full_output or return_samples or full_MC or
@@ -928,6 +940,275 @@ class GaussianProcess(object):
         if return_cov:
             return (mean, covariance)
         return (mean, std)
+
+    # ---- prediction marginalised over hyperparameter samples (ref: gptools/gaussian_process.py:888-912, :1840-1987,
+    # :2144-2330) -----------------------------------------------------------------------------------------------------
+    #: traces with fewer usable rows than this take the loop route (one update_hyperparameters + predict per row) even where
+    #: the batched route (gpt_fit_batch_terms + gpt_predict_batch) could run: see DESIGN.md section 9 for the measurements
+    mcmc_batch_min_rows = 2
+
+    @staticmethod
+    def _mcmc_trace(sampler, flat_trace, burn, thin):
+        """The rows of free hyperparameters to marginalise over, burned and thinned as the reference does (:1935-1940)."""
+        if flat_trace is None:
+            if sampler is None:
+                raise NotImplementedError("drawing the hyperparameter posterior (emcee) is not part of this package: pass "
+                                          "flat_trace (samples of the free hyperparameters, one per row) or a sampler that "
+                                          "has already been run")
+            chain = np.asarray(sampler.chain, dtype=float)[:, burn::thin, :]
+            return chain.reshape((-1, chain.shape[2]))
+        return np.atleast_2d(np.asarray(flat_trace, dtype=float))[burn::thin, :]
+
+    def _mcmc_evaluate(self, X, n, trace, noise, output_transform, want_var, want_cov, want_cov_sum):
+        """Predictive moments at every row of ``trace``.  Returns a dict over the rows that were evaluated (``rows``: their
+        indices, in order): ``mean`` (K, M) with the mean function added, ``mean_func`` (K, M) or None, ``var`` (K, M),
+        ``cov`` (K, M, M), ``cov_sum`` (M, M) = the sum of the rows' covariances -- each None unless asked for -- all
+        after ``output_transform``.  A row is dropped only when its evaluation fails (a NaN parameter, a factor that is not
+        positive definite, parameters the library rejects); rows the hyperprior excludes are evaluated as the reference's
+        ``update_hyperparameters`` + ``predict`` evaluate them.  The GP's own hyperparameters are unchanged afterwards."""
+        if self.X is None:
+            raise GPArgumentError("No data have been added to the GaussianProcess!")
+        Xs, ns, A = self._check_predict_args(X, n, output_transform)
+        if A is not None and want_var:
+            want_cov = True                             # (the transformed variances are the diagonals of A cov A^T)
+        S, M = trace.shape[0], Xs.shape[0]
+        res = {"mean": np.full((S, M), np.nan), "mean_func": None if self.mu is None else np.full((S, M), np.nan),
+               "var": np.full((S, M), np.nan) if want_var and A is None else None,
+               "cov": np.full((S, M, M), np.nan) if want_cov else None,
+               "cov_sum": np.zeros((M, M)) if want_cov_sum else None}
+        ok = np.zeros(S, dtype=bool)
+        noise_n = None
+        if noise and isinstance(self.noise_k, DiagonalNoiseKernel) and not isinstance(self.noise_k, ZeroKernel):
+            noise_n = np.broadcast_to(np.asarray(self.noise_k.n, dtype=np.int32), (self.num_dim,))
+        saved = np.array(self.free_params[:], dtype=float)
+        keep_partitioned = self.partitioned
+        self.partitioned = False
+        try:
+            rows = [i for i in range(S) if not np.isnan(trace[i]).any()]      # (a NaN parameter: the evaluation fails)
+            rest = self._mcmc_batched(Xs, ns, trace, rows, noise_n, res, ok)
+            for i in rest:                                   # the loop route (_ComputeGPWrapper, ref :2256-2330)
+                try:
+                    self.update_hyperparameters(list(trace[i]))      # (+inf where the prior excludes p: predict runs there anyway)
+                    if want_cov or want_cov_sum:
+                        mean, cov = self.predict(Xs, n=ns, noise=noise, return_cov=True)
+                        var = np.diagonal(cov)
+                    else:
+                        mean, std = self.predict(Xs, n=ns, noise=noise, return_std=True)
+                        cov, var = None, std ** 2.0
+                except Exception:
+                    if self.verbose:
+                        warnings.warn("evaluation at trace row %d failed and is dropped:\n%s" % (i, traceback.format_exc()))
+                    continue
+                res["mean"][i] = mean
+                if self.mu is not None:
+                    res["mean_func"][i] = self.mu(Xs, ns)
+                if res["var"] is not None:
+                    res["var"][i] = var
+                if want_cov:
+                    res["cov"][i] = cov
+                if want_cov_sum:
+                    res["cov_sum"] += cov
+                ok[i] = True
+        finally:
+            self._assign_free(saved)
+            self.partitioned = keep_partitioned
+        if not ok.any():
+            raise ValueError("every row of the hyperparameter trace failed to evaluate")
+        out = {"rows": np.flatnonzero(ok)}
+        for key in ("mean", "mean_func", "var", "cov"):
+            out[key] = None if res[key] is None else res[key][ok]
+        out["cov_sum"] = res["cov_sum"]
+        if A is not None:
+            # linear in the prediction: transforming the marginal moments equals transforming each row's first
+            out["mean"] = out["mean"].dot(A.T)
+            if out["mean_func"] is not None:
+                out["mean_func"] = out["mean_func"].dot(A.T)
+            if out["cov"] is not None:
+                out["cov"] = np.matmul(np.matmul(A, out["cov"]), A.T)
+                if want_var:
+                    out["var"] = np.array([np.diagonal(c) for c in out["cov"]])
+            if out["cov_sum"] is not None:
+                out["cov_sum"] = A.dot(out["cov_sum"]).dot(A.T)
+        return out
+
+    def _mcmc_batched(self, Xs, ns, trace, rows, noise_n, res, ok):
+        """The batched route: chunks of rows through gpt_fit_batch_terms + gpt_predict_batch.  Fills ``res`` / ``ok`` for the
+        rows it evaluates and returns the rows left to the loop route."""
+        N = len(self.y)
+        if (not rows or len(rows) < int(self.mcmc_batch_min_rows) or not self._fast_fit_possible() or self.T is not None
+                or max(N, self.X.shape[0]) > self.batch_grid_max_n or int(self.batch_grid) < 1):
+            return rows
+        jobs = []
+        for i in rows:
+            self._assign_free(trace[i])
+            terms = self._native_terms()
+            noise_var = 0.0 if isinstance(self.noise_k, ZeroKernel) else self.noise_k.params[0] ** 2.0
+            mu_star = None if self.mu is None else np.asarray(self.mu(Xs, ns), dtype=float)
+            jobs.append((i, terms, noise_var, np.array(self._y_alph(), dtype=float), mu_star))
+        shape = [(t[0], t[2] if len(t) == 4 else -1) for t in jobs[0][1]]
+        if any([(t[0], t[2] if len(t) == 4 else -1) for t in j[1]] != shape for j in jobs):
+            return rows
+        ctx = self._ctx
+        if not self._data_on_device:
+            self._upload_data(ctx)
+            self._data_on_device = True
+        self._cache = {}
+        want_var, want_cov, want_sum = res["var"] is not None, res["cov"] is not None, res["cov_sum"] is not None
+        M = Xs.shape[0]
+        NP, MP = -(-(N + 1) // 128) * 128, -(-M // 64) * 64
+        per = 8 * (NP * NP + 9216 * (NP // 128) + MP * NP + (MP * MP if want_cov else 0))
+        budget = min(int(self.batch_grid_bytes), ctx.mem_info()[0] // 2)
+        G = max(1, min(int(self.batch_grid), budget // per))
+        err_y = np.asarray(self.err_y, dtype=float)
+        diag_add = self.diag_factor * sys.float_info.epsilon
+        rest, s0 = [], 0
+        while s0 < len(jobs):
+            chunk = jobs[s0:s0 + G]
+            try:
+                _, _, info = ctx.fit_batch_terms([j[1] for j in chunk], np.array([j[2] for j in chunk]),
+                                                 np.array([j[3] for j in chunk]), err_y, diag_add)
+                keep = info == 0
+                if keep.any():
+                    mean, var, cov, cov_sum = ctx.predict_batch(Xs, ns, keep, noise_n, want_var, want_cov, want_sum)
+            except MemoryError:
+                ctx.release_batch_scratch()
+                if G == 1:
+                    rest.extend(j[0] for j in jobs[s0:])
+                    break
+                G //= 2
+                continue
+            except (ValueError, ArithmeticError):
+                # a parameter the library rejects fails the whole chunk: its rows one at a time on the loop route
+                rest.extend(j[0] for j in chunk)
+                s0 += len(chunk)
+                continue
+            for q, j in enumerate(chunk):
+                if not keep[q]:
+                    continue                                 # not positive definite: the evaluation fails, the row is dropped
+                i = j[0]
+                res["mean"][i] = mean[q] if j[4] is None else mean[q] + j[4]
+                if j[4] is not None:
+                    res["mean_func"][i] = j[4]
+                if want_var:
+                    res["var"][i] = var[q]
+                if want_cov:
+                    res["cov"][i] = cov[q]
+                ok[i] = True
+            if want_sum and keep.any():
+                res["cov_sum"] += cov_sum
+            s0 += len(chunk)
+        if 8 * (NP * NP + MP * NP) * min(G, len(jobs)) > (2 << 30):
+            ctx.release_batch_scratch()                      # a large scratch goes back to the device once the trace is done
+        return sorted(rest)
+
+    def compute_from_MCMC(self, X, n=0, return_mean=True, return_std=True, return_cov=False, return_samples=False,
+                          return_mean_func=False, num_samples=1, noise=False, samp_kwargs={}, sampler=None, flat_trace=None,
+                          burn=0, thin=1, **kwargs):
+        """Predictive quantities at each row of a trace of the free hyperparameters (ref: gaussian_process.py:1840-1987):
+        a dict of per-row lists -- ``mean`` (M,), ``std`` (M,), ``cov`` (M, M), ``samp`` (M, num_samples) and, with
+        ``return_mean_func`` and a mean function, the ``*_func`` / ``*_without_func`` entries -- over the rows whose
+        evaluation succeeded, in trace order.  ``flat_trace[burn::thin]`` or, duck-typed, ``sampler.chain[:, burn::thin, :]``
+        flattened; drawing the posterior itself (emcee) is not part of this package.  ``num_proc`` is accepted and ignored:
+        the rows are evaluated in batches on the GPU (gpt_fit_batch_terms + gpt_predict_batch) where the model allows it,
+        else one after another.  Samples are drawn on the host per row, in row order (numpy.random.multivariate_normal).
+        The GP's hyperparameters are unchanged afterwards."""
+        output_transform = kwargs.pop("output_transform", None)
+        trace = self._mcmc_trace(sampler, flat_trace, burn, thin)
+        want_func = bool(return_mean_func) and self.mu is not None
+        need_cov = bool(return_cov or return_samples or want_func)
+        ev = self._mcmc_evaluate(X, n, trace, noise, output_transform, bool(return_std), need_cov, False)
+        K = len(ev["rows"])
+        std = None
+        if return_std or want_func:
+            var = ev["var"] if ev["var"] is not None else np.array([np.diagonal(c) for c in ev["cov"]])
+            std = np.sqrt(var)
+        out = {}
+        if return_mean:
+            out["mean"] = list(ev["mean"])
+        if return_std:
+            out["std"] = list(std)
+        if return_cov:
+            out["cov"] = list(ev["cov"])
+        if return_samples:
+            out["samp"] = [self.draw_sample(X, n=n, num_samp=num_samples, mean=ev["mean"][q], cov=ev["cov"][q], **samp_kwargs)
+                           for q in range(K)]
+        if want_func:
+            mf = ev["mean_func"]
+            out["mean_func"] = list(mf)
+            out["cov_func"] = [np.zeros((mf.shape[1], mf.shape[1])) for _ in range(K)]
+            out["std_func"] = [np.zeros(mf.shape[1]) for _ in range(K)]
+            out["mean_without_func"] = list(ev["mean"] - mf)
+            out["cov_without_func"] = list(ev["cov"])
+            out["std_without_func"] = list(std)
+        return out
+
+    def predict_MCMC(self, X, ddof=1, full_MC=False, rejection_func=None, **kwargs):
+        """Prediction marginalised over a trace of the hyperparameters (ref: gaussian_process.py:2144-2254): the mean of the
+        rows' means, and by the laws of total variance / covariance ``mean(var) + var(means, ddof)`` /
+        ``mean(cov) + cov(means, ddof)`` (numpy's estimators: NaN when no more rows than ``ddof`` survive); ``full_MC``: the
+        sample mean and covariance of draws from every row (filtered by ``rejection_func``).  The keyword arguments are
+        those of :meth:`compute_from_MCMC` (``flat_trace`` or ``sampler``, ``burn``, ``thin``, ``n``, ``noise``,
+        ``return_std``, ``return_cov``, ``return_samples``, ``num_samples``, ``return_mean_func``, ``output_transform``).
+        Only the summed covariance of the rows is formed (on the GPU where the batched route runs), not one per row."""
+        return_std = kwargs.get("return_std", True)
+        return_cov = kwargs.get("return_cov", False)
+        return_samples = bool(full_MC or kwargs.get("return_samples", False))
+        trace = self._mcmc_trace(kwargs.get("sampler"), kwargs.get("flat_trace"), kwargs.get("burn", 0), kwargs.get("thin", 1))
+        X_, n, noise = X, kwargs.get("n", 0), kwargs.get("noise", False)
+        output_transform = kwargs.get("output_transform")
+        want_func = bool(kwargs.get("return_mean_func", False)) and self.mu is not None and not full_MC
+        if full_MC or return_samples:
+            ev = self._mcmc_evaluate(X_, n, trace, noise, output_transform, False, True, False)
+            samps = np.hstack([self.draw_sample(X_, n=n, num_samp=kwargs.get("num_samples", 1), mean=m, cov=c)
+                               for m, c in zip(ev["mean"], ev["cov"])])
+            if not full_MC:
+                ev["cov_sum"] = np.sum(ev["cov"], axis=0)
+        else:
+            use_sum = bool(return_cov or want_func or (return_std and output_transform is not None))
+            ev = self._mcmc_evaluate(X_, n, trace, noise, output_transform, bool(return_std) and not use_sum, False, use_sum)
+        out = {}
+        K = len(ev["rows"])
+        if full_MC:
+            if rejection_func:
+                good = [samp for samp in samps.T if rejection_func(samp)]
+                if len(good) == 0:
+                    raise ValueError("Did not get any good samples!")
+                samps = np.asarray(good, dtype=float).T
+            mean = np.mean(samps, axis=1)
+            cov = np.cov(samps, rowvar=1, ddof=ddof)
+            std = np.sqrt(np.diagonal(cov))
+        else:
+            means = ev["mean"]
+            mean = np.mean(means, axis=0)
+            if return_cov:
+                cov = ev["cov_sum"] / K + np.cov(means, rowvar=0, ddof=ddof)
+                std = np.sqrt(np.diagonal(cov))
+            elif return_std:
+                if ev["var"] is not None:
+                    mvar = np.mean(np.sqrt(ev["var"]) ** 2, axis=0)
+                else:
+                    mvar = np.diagonal(ev["cov_sum"]) / K
+                std = np.sqrt(mvar + np.var(means, axis=0, ddof=ddof))
+            if want_func:
+                mean_funcs = ev["mean_func"]
+                mean_func = np.mean(mean_funcs, axis=0)
+                cov_func = np.cov(mean_funcs, rowvar=0, ddof=ddof)
+                without = means - mean_funcs
+                cov_without_func = ev["cov_sum"] / K + np.cov(without, rowvar=0, ddof=ddof)
+                out["mean_func"] = mean_func
+                out["cov_func"] = cov_func
+                out["std_func"] = np.sqrt(np.diagonal(cov_func))
+                out["mean_without_func"] = np.mean(without, axis=0)
+                out["cov_without_func"] = cov_without_func
+                out["std_without_func"] = np.sqrt(np.diagonal(cov_without_func))
+        out["mean"] = mean
+        if return_samples:
+            out["samp"] = samps
+        if return_std or return_cov:
+            out["std"] = std
+        if return_cov:
+            out["cov"] = cov
+        return out
 
     # ---- posterior samples (ref: gptools/gaussian_process.py:1155-1330) --------------------------------------
     def draw_sample(self, Xstar, n=0, num_samp=1, rand_vars=None, rand_type="standard normal", diag_factor=1e3,

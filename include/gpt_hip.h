@@ -270,6 +270,23 @@ int gpt_fit_batch_terms(gpt_ctx *ctx, int nbatch, int nterms, const int *kernel_
 int gpt_mem_info(gpt_ctx *ctx, int64_t *free_bytes, int64_t *total_bytes);
 int gpt_release_batch_scratch(gpt_ctx *ctx);
 
+/* Prediction from the RESIDENT BATCH: every element of the last successful gpt_fit_batch* at the same M test points -- the
+ * reference's prediction marginalised over a hyperparameter trace (ref: gaussian_process.py:1840-1987 compute_from_MCMC,
+ * :2144-2254 predict_MCMC: one update_hyperparameters + predict per trace row).  Per element b, as gpt_predict:
+ *   V_b = K*_b^T L_b^-T,  mean_b = V_b z_b (z_b = L_b^-1 y_b, the fit's augmented row),  var_b = diag K**_b - rowsumsq(V_b),
+ *   cov_b = K**_b - V_b V_b^T.
+ * Xstar (M, D) / nstar (M, D) test points and derivative orders (the order checks of gpt_predict).  noise_n != NULL (D orders):
+ * element b's own noise variance (the fit's noise_var[b]) is added where a row of nstar equals noise_n (ref: noise.py:103-104).
+ * keep (nbatch): 0 skips element b -- its rows of the outputs are not written and it takes no part in cov_sum_out (pass
+ * keep[b] = (info_out[b] == 0): a factor that is not positive definite must be skipped).  Outputs (host, row-major):
+ *   mean_out (nbatch, M); var_out (nbatch, M) or NULL; cov_out (nbatch, M, M), full symmetric, or NULL;
+ *   cov_sum_out (M, M) = sum over kept b of cov_b (full symmetric), or NULL: built on the device without the per-element
+ *   matrices -- one pass for sum_b K**_b and ONE GEMM over the contraction (b, i) -- so it crosses PCIe once per call.
+ * GPT_E_STATE: no batch resident (before any gpt_fit_batch*, after one that failed, and after gpt_set_data, gpt_set_T,
+ * gpt_cov_sample or gpt_release_batch_scratch); GPT_E_NOTIMPL with a linear transform set.  The resident batch is unchanged. */
+int gpt_predict_batch(gpt_ctx *ctx, const double *Xstar, const int32_t *nstar, int64_t M, const int32_t *noise_n,
+                      const int32_t *keep, double *mean_out, double *var_out, double *cov_out, double *cov_sum_out);
+
 /* Same as gpt_fit but for an explicit, caller-assembled symmetric K_tot (host, (N, N) row-major;
  * only the lower triangle is read): used for the `T` (linear transform) branch,
  * ref: gaussian_process.py:1443-1446, where K_tot = T (K + noise_K) T^T + ... is (N_y, N_y). */
