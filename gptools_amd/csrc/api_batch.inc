@@ -74,9 +74,11 @@ static int fit_batch_impl(gpt_ctx *c, int nbatch, int nterms, const int *kernel_
         const bool prod = kernel_ids2 && kernel_ids2[t] >= 0;
         any_prod = any_prod || prod;
         if (!native_fit_kernel(kernel_ids[t]) || (prod && !native_fit_kernel(kernel_ids2[t]))) {
-            gpt_set_error("gpt_fit_batch: kernel ids must be SE, Matern52, RationalQuadratic or Matern");
+            gpt_set_error("gpt_fit_batch: kernel ids must be SE, Matern52, RationalQuadratic, Matern or Gibbs");
             return GPT_E_ARG;
         }
+        GPT_TRY(check_gibbs_fit(c, kernel_ids[t]));
+        if (prod) GPT_TRY(check_gibbs_fit(c, kernel_ids2[t]));
         const bool any_chain = kernel_ids[t] == GPT_KERNEL_RQ || kernel_ids[t] == GPT_KERNEL_MATERN ||
                                (prod && (kernel_ids2[t] == GPT_KERNEL_RQ || kernel_ids2[t] == GPT_KERNEL_MATERN));
         if ((any_chain || prod) && 2 * c->n_maxsum > GPT_RQ_MAXORD) {
@@ -263,14 +265,16 @@ extern "C" int gpt_predict_batch(gpt_ctx *c, const double *Xstar, const int32_t 
     const int64_t MP = round_up(M, 64), ldv = (int64_t)nbatch * NP;
     // derivative orders of the test points: the checks of gpt_predict, for the first element's kernels (all elements share them)
     {
-        bool m52 = false, chain = c->rb_any_prod;
+        bool m52 = false, chain = c->rb_any_prod, gibbs = false;
         for (int t = 0; t < nterms; t++) {
             const int k1 = c->rb_kp[(size_t)t * nbatch].kernel_id;
             const int k2 = c->rb_any_prod ? c->rb_kp2[(size_t)t * nbatch].kernel_id : -1;
             m52 = m52 || k1 == GPT_KERNEL_M52 || k2 == GPT_KERNEL_M52;
             chain = chain || k1 == GPT_KERNEL_RQ || k1 == GPT_KERNEL_MATERN;
+            gibbs = gibbs || is_gibbs(k1) || is_gibbs(k2);
         }
         if (m52) GPT_TRY(check_m52_orders(nstar, M, D));
+        if (gibbs) GPT_TRY(check_gibbs_orders(nstar, M, D));
         if (chain) {
             long ms = 0;
             for (int64_t i = 0; i < M; i++) {

@@ -225,6 +225,21 @@ static int kbuild_terms(gpt_ctx *c, hipStream_t st, const std::vector<KParams> &
 static int fit_terms(gpt_ctx *c, const std::vector<KParams> &terms, double noise_var, const double *y,
                      const double *err_y, double diag_add, double *ll_data_out, double *logdet_half_out);
 
+static bool native_fit_kernel(int kid)
+{
+    return kid == GPT_KERNEL_SE || kid == GPT_KERNEL_M52 || kid == GPT_KERNEL_RQ || kid == GPT_KERNEL_MATERN || is_gibbs(kid);
+}
+
+// a Gibbs term over the resident points: derivative orders <= 1 (the points' largest order is c->n_maxsum in 1-D)
+static int check_gibbs_fit(const gpt_ctx *c, int kid)
+{
+    if (is_gibbs(kid) && c->n_maxsum > 1) {
+        gpt_set_error("Derivatives greater than [1, 1] are not supported!");
+        return GPT_E_NOTIMPL;
+    }
+    return GPT_OK;
+}
+
 extern "C" int gpt_fit(gpt_ctx *c, int kernel_id, const double *params, int nparams, double noise_var,
                        const double *y, const double *err_y, double diag_add, double *ll_data_out,
                        double *logdet_half_out)
@@ -245,11 +260,11 @@ extern "C" int gpt_fit_sum(gpt_ctx *c, int nterms, const int *kernel_ids, const 
     std::vector<KParams> terms((size_t)nterms);
     const double *p = params;
     for (int t = 0; t < nterms; t++) {
-        if (kernel_ids[t] != GPT_KERNEL_SE && kernel_ids[t] != GPT_KERNEL_M52 && kernel_ids[t] != GPT_KERNEL_RQ &&
-            kernel_ids[t] != GPT_KERNEL_MATERN) {
-            gpt_set_error("gpt_fit: kernel_id must be SE, Matern52, RationalQuadratic or Matern");
+        if (!native_fit_kernel(kernel_ids[t])) {
+            gpt_set_error("gpt_fit: kernel_id must be SE, Matern52, RationalQuadratic, Matern or Gibbs");
             return GPT_E_ARG;
         }
+        GPT_TRY(check_gibbs_fit(c, kernel_ids[t]));
         if ((kernel_ids[t] == GPT_KERNEL_RQ || kernel_ids[t] == GPT_KERNEL_MATERN) && 2 * c->n_maxsum > GPT_RQ_MAXORD) {
             gpt_set_error("RationalQuadratic / Matern kernel: derivative orders of a pair sum to %ld, the device builder supports %d",
                           2 * c->n_maxsum, GPT_RQ_MAXORD);
@@ -264,10 +279,6 @@ extern "C" int gpt_fit_sum(gpt_ctx *c, int nterms, const int *kernel_ids, const 
 }
 
 // The same with product terms (include/gpt_hip.h)
-static bool native_fit_kernel(int kid)
-{
-    return kid == GPT_KERNEL_SE || kid == GPT_KERNEL_M52 || kid == GPT_KERNEL_RQ || kid == GPT_KERNEL_MATERN;
-}
 
 extern "C" int gpt_fit_terms(gpt_ctx *c, int nterms, const int *kernel_ids, const int *kernel_ids2, const double *params,
                              const int *nparams, const int *nparams1, double noise_var, const double *y, const double *err_y,
@@ -284,9 +295,11 @@ extern "C" int gpt_fit_terms(gpt_ctx *c, int nterms, const int *kernel_ids, cons
     for (int t = 0; t < nterms; t++) {
         const bool prod = kernel_ids2[t] >= 0;
         if (!native_fit_kernel(kernel_ids[t]) || (prod && !native_fit_kernel(kernel_ids2[t]))) {
-            gpt_set_error("gpt_fit_terms: kernel ids must be SE, Matern52, RationalQuadratic or Matern");
+            gpt_set_error("gpt_fit_terms: kernel ids must be SE, Matern52, RationalQuadratic, Matern or Gibbs");
             return GPT_E_ARG;
         }
+        GPT_TRY(check_gibbs_fit(c, kernel_ids[t]));
+        if (prod) GPT_TRY(check_gibbs_fit(c, kernel_ids2[t]));
         const int n1 = prod ? nparams1[t] : nparams[t];
         if (n1 < 1 || n1 > nparams[t]) return GPT_E_ARG;
         // derivative orders: a product meets the SUM of both points' orders in either factor

@@ -16,6 +16,10 @@ extern "C" int gpt_kpairs(gpt_ctx *c, int kernel_id, const double *params, int n
         GPT_TRY(check_m52_orders(nj, M, D));
     }
     if ((kernel_id == GPT_KERNEL_RQ || kernel_id == GPT_KERNEL_MATERN) && M > 0) GPT_TRY(check_rq_orders(ni, M, nj, M, D, true));
+    if (is_gibbs(kernel_id) && M > 0) {
+        GPT_TRY(check_gibbs_orders(ni, M, D));
+        GPT_TRY(check_gibbs_orders(nj, M, D));
+    }
     if (M == 0) return GPT_OK;
     double *dXi, *dXj, *dout;
     int32_t *dni, *dnj;
@@ -56,6 +60,10 @@ extern "C" int gpt_kbuild(gpt_ctx *c, int kernel_id, const double *params, int n
     }
     if ((kernel_id == GPT_KERNEL_RQ || kernel_id == GPT_KERNEL_MATERN) && M > 0 && P > 0 && ni && nj)
         GPT_TRY(check_rq_orders(ni, M, nj, P, D, false));
+    if (is_gibbs(kernel_id) && M > 0 && P > 0 && ni && nj) {
+        GPT_TRY(check_gibbs_orders(ni, M, D));
+        GPT_TRY(check_gibbs_orders(nj, P, D));
+    }
     if (M == 0 || P == 0) return GPT_OK;
     if (!Xi || !ni || !Xj || !nj || !K_out) return GPT_E_ARG;
     double *dXi, *dXj, *dK;
@@ -81,8 +89,8 @@ static int make_product(int kid1, const double *p1, int n1, int kid2, const doub
 {
     if (!p1 || !p2) return GPT_E_ARG;
     for (int kid : {kid1, kid2})
-        if (kid != GPT_KERNEL_SE && kid != GPT_KERNEL_M52 && kid != GPT_KERNEL_RQ && kid != GPT_KERNEL_MATERN) {
-            gpt_set_error("product factors must be SE, Matern52, RationalQuadratic or Matern kernels");
+        if (kid != GPT_KERNEL_SE && kid != GPT_KERNEL_M52 && kid != GPT_KERNEL_RQ && kid != GPT_KERNEL_MATERN && !is_gibbs(kid)) {
+            gpt_set_error("product factors must be SE, Matern52, RationalQuadratic, Matern or Gibbs kernels");
             return GPT_E_ARG;
         }
     GPT_TRY(make_kparams(kid1, p1, n1, D, -1, 0, nullptr, k1));
@@ -103,6 +111,10 @@ extern "C" int gpt_kpairs2(gpt_ctx *c, int kernel_id1, const double *params1, in
         GPT_TRY(check_m52_orders(nj, M, D));
     }
     if (M > 0) GPT_TRY(check_rq_orders(ni, M, nj, M, D, true));       // combined order of a pair <= GPT_RQ_MAXORD
+    if ((is_gibbs(kernel_id1) || is_gibbs(kernel_id2)) && M > 0) {      // (Leibniz hands a factor at most the points' own orders)
+        GPT_TRY(check_gibbs_orders(ni, M, D));
+        GPT_TRY(check_gibbs_orders(nj, M, D));
+    }
     if (M == 0) return GPT_OK;
     double *dXi, *dXj, *dout;
     int32_t *dni, *dnj;
@@ -143,6 +155,10 @@ extern "C" int gpt_kbuild2(gpt_ctx *c, int kernel_id1, const double *params1, in
         GPT_TRY(check_m52_orders(nj, P, D));
     }
     GPT_TRY(check_rq_orders(ni, M, nj, P, D, false));
+    if (is_gibbs(kernel_id1) || is_gibbs(kernel_id2)) {
+        GPT_TRY(check_gibbs_orders(ni, M, D));
+        GPT_TRY(check_gibbs_orders(nj, P, D));
+    }
     double *dXi, *dXj, *dK;
     int32_t *dni, *dnj;
     GPT_TRY(ensure(c, SLOT_XI, (size_t)M * D * sizeof(double), (void **)&dXi));

@@ -98,6 +98,42 @@ static int make_kparams(int kernel_id, const double *params, int nparams, int D,
             kp->m_g[q] = tgamma(nus);
             kp->m_gm[q] = tgamma(-nus);
         }
+    } else if (kernel_id == GPT_KERNEL_GIBBS_TANH || kernel_id == GPT_KERNEL_GIBBS_DTANH) {
+        // GibbsKernel1dTanh [sigma_f, l_1, l_2, l_w, x_0] (ref: gibbs.py:426-498); GibbsKernel1dDoubleTanh [sigma_f, l_c, l_m,
+        // l_e, l_a, l_b, x_a, x_b] (ref: gibbs.py:508-590).  Both as l(x) = g_c + sum_q g_amp[q] tanh((x - g_x0[q]) / g_w[q])
+        const bool dbl = kernel_id == GPT_KERNEL_GIBBS_DTANH;
+        if (D != 1) {
+            gpt_set_error("Gibbs kernel only supports 1d data.");
+            return GPT_E_ARG;
+        }
+        if (nparams != (dbl ? 8 : 5)) {
+            gpt_set_error("kernel %d expects %d params, got %d", kernel_id, dbl ? 8 : 5, nparams);
+            return GPT_E_ARG;
+        }
+        if (hyper_deriv >= 0) {
+            gpt_set_error("Hyperparameter derivatives have not been implemented!");      // ref: gibbs.py:319-322
+            return GPT_E_NOTIMPL;
+        }
+        kp->sigma = params[0];
+        if (!dbl) {
+            const double l1 = params[1], l2 = params[2];
+            kp->g_nt = 1;
+            kp->g_c = (l1 + l2) / 2.0;
+            kp->g_amp[0] = -((l1 - l2) / 2.0);
+            kp->g_w[0] = params[3];
+            kp->g_x0[0] = params[4];
+        } else {
+            // the reference's a, b, c: dot([[-0.5, 0, 0.5], [0, 0.5, -0.5], [0.5, 0.5, 0]], [l_c, l_e, l_m]) (gibbs.py:546-551)
+            const double lc = params[1], lm = params[2], le = params[3];
+            kp->g_nt = 2;
+            kp->g_amp[0] = -0.5 * lc + 0.0 * le + 0.5 * lm;
+            kp->g_amp[1] = 0.0 * lc + 0.5 * le - 0.5 * lm;
+            kp->g_c = 0.5 * lc + 0.5 * le + 0.0 * lm;
+            kp->g_w[0] = params[4];
+            kp->g_w[1] = params[5];
+            kp->g_x0[0] = params[6];
+            kp->g_x0[1] = params[7];
+        }
     } else if (kernel_id == GPT_KERNEL_DIAGNOISE || kernel_id == GPT_KERNEL_ZERO) {
         if (nparams != 1) {
             gpt_set_error("noise kernels expect 1 param, got %d", nparams);
@@ -157,5 +193,21 @@ static int check_rq_orders(const int32_t *ni, int64_t M, const int32_t *nj, int6
                       worst, GPT_RQ_MAXORD);
         return GPT_E_VALUE;
     }
+    return GPT_OK;
+}
+
+static bool is_gibbs(int kid)
+{
+    return kid == GPT_KERNEL_GIBBS_TANH || kid == GPT_KERNEL_GIBBS_DTANH;
+}
+
+// The Gibbs kernels evaluate derivative orders 0 and 1 per point (ref: gibbs.py:417-420 raises NotImplementedError beyond)
+static int check_gibbs_orders(const int32_t *n, int64_t M, int D)
+{
+    for (int64_t i = 0; i < M * D; i++)
+        if (n[i] > 1) {
+            gpt_set_error("Derivatives greater than [1, 1] are not supported!");
+            return GPT_E_NOTIMPL;
+        }
     return GPT_OK;
 }

@@ -34,6 +34,11 @@ extern "C" int gpt_predict(gpt_ctx *c, const double *Xstar, const int32_t *nstar
             break;
         }
     for (const auto &t : all_factors)
+        if (is_gibbs(t.kernel_id)) {
+            GPT_TRY(check_gibbs_orders(nstar, M, D));
+            break;
+        }
+    for (const auto &t : all_factors)
         if (t.kernel_id == GPT_KERNEL_RQ || t.kernel_id == GPT_KERNEL_MATERN || any_product) {
             long ms = 0;
             for (int64_t i = 0; i < M; i++) {

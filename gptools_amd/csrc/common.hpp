@@ -59,6 +59,9 @@ struct KParams {
     int pad_;                 //   reference's 0/0 -> 0 rule per dimension (core.py:416); otherwise it is one multiply
     double m_gampl, m_gammi, m_gam1, m_gam2;      // Temme's 1/Gamma(1 +- mu) and their combinations
     double m_g[2], m_gm[2], m_nus[2];             // Gamma(nu_s), Gamma(-nu_s), nu_s for the small-y series (nu_s = nu, or nu -+ 0.001)
+    // Gibbs kernels (1-D): l(x) = g_c + sum_q g_amp[q] tanh((x - g_x0[q]) / g_w[q]) over g_nt terms (1: tanh warp, 2: double tanh)
+    double g_amp[2], g_w[2], g_x0[2], g_c;
+    int g_nt, g_pad_;
 };
 
 // A cross-stream edge without an event: the kernel that completes a piece of work raises a 32-bit word in device

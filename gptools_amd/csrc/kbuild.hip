@@ -53,7 +53,14 @@ static int kbuild_dispatch_d(hipStream_t st, const KParams &kp, const double *dX
                            lower_only, i0, j0, d_err_y, noise_var, diag_add, dK, ldk, accumulate,               \
                            (const KParams *)nullptr, (const double *)nullptr, (int64_t)0, KParams(), (const KParams *)nullptr);  \
         break;
-    switch (kp.D) {
+    if constexpr (KID == GPT_KERNEL_GIBBS_TANH || KID == GPT_KERNEL_GIBBS_DTANH) {      // (1-D kernels: one instantiation)
+        switch (kp.D) {
+            KB_CASE(1)
+        default:
+            gpt_set_error("kbuild: the Gibbs kernels need num_dim 1, got %d", kp.D);
+            return GPT_E_ARG;
+        }
+    } else switch (kp.D) {
         KB_CASE(1) KB_CASE(2) KB_CASE(3) KB_CASE(4) KB_CASE(5) KB_CASE(6) KB_CASE(7) KB_CASE(8)
         KB_CASE(9) KB_CASE(10) KB_CASE(11) KB_CASE(12) KB_CASE(13) KB_CASE(14) KB_CASE(15) KB_CASE(16)
     default:
@@ -94,6 +101,12 @@ int launch_kbuild(hipStream_t st, const KParams &kp, const double *dXi, const in
     case GPT_KERNEL_MATERN:
         return kbuild_dispatch_d<GPT_KERNEL_MATERN>(st, kp, dXi, dni, M, dXj, dnj, P, lower_only, i0, j0, d_err_y,
                                                     noise_var, diag_add, dK, ldk, accumulate);
+    case GPT_KERNEL_GIBBS_TANH:
+        return kbuild_dispatch_d<GPT_KERNEL_GIBBS_TANH>(st, kp, dXi, dni, M, dXj, dnj, P, lower_only, i0, j0, d_err_y,
+                                                        noise_var, diag_add, dK, ldk, accumulate);
+    case GPT_KERNEL_GIBBS_DTANH:
+        return kbuild_dispatch_d<GPT_KERNEL_GIBBS_DTANH>(st, kp, dXi, dni, M, dXj, dnj, P, lower_only, i0, j0, d_err_y,
+                                                         noise_var, diag_add, dK, ldk, accumulate);
     default:
         gpt_set_error("kbuild: unknown kernel_id %d", kp.kernel_id);
         return GPT_E_ARG;
@@ -109,7 +122,14 @@ static int kpairs_dispatch_d(hipStream_t st, const KParams &kp, const double *dX
     case DD:                                                                                          \
         hipLaunchKernelGGL((kpairs_kernel<KID, DD>), grid, block, 0, st, kp, dXi, dXj, dni, dnj, M, dout, accumulate, KParams()); \
         break;
-    switch (kp.D) {
+    if constexpr (KID == GPT_KERNEL_GIBBS_TANH || KID == GPT_KERNEL_GIBBS_DTANH) {
+        switch (kp.D) {
+            KP_CASE(1)
+        default:
+            gpt_set_error("kpairs: the Gibbs kernels need num_dim 1, got %d", kp.D);
+            return GPT_E_ARG;
+        }
+    } else switch (kp.D) {
         KP_CASE(1) KP_CASE(2) KP_CASE(3) KP_CASE(4) KP_CASE(5) KP_CASE(6) KP_CASE(7) KP_CASE(8)
         KP_CASE(9) KP_CASE(10) KP_CASE(11) KP_CASE(12) KP_CASE(13) KP_CASE(14) KP_CASE(15) KP_CASE(16)
     default:
@@ -133,6 +153,8 @@ int launch_kpairs(hipStream_t st, const KParams &kp, const double *dXi, const do
     case GPT_KERNEL_ZERO: return kpairs_dispatch_d<GPT_KERNEL_ZERO>(st, kp, dXi, dXj, dni, dnj, M, dout, accumulate);
     case GPT_KERNEL_RQ: return kpairs_dispatch_d<GPT_KERNEL_RQ>(st, kp, dXi, dXj, dni, dnj, M, dout, accumulate);
     case GPT_KERNEL_MATERN: return kpairs_dispatch_d<GPT_KERNEL_MATERN>(st, kp, dXi, dXj, dni, dnj, M, dout, accumulate);
+    case GPT_KERNEL_GIBBS_TANH: return kpairs_dispatch_d<GPT_KERNEL_GIBBS_TANH>(st, kp, dXi, dXj, dni, dnj, M, dout, accumulate);
+    case GPT_KERNEL_GIBBS_DTANH: return kpairs_dispatch_d<GPT_KERNEL_GIBBS_DTANH>(st, kp, dXi, dXj, dni, dnj, M, dout, accumulate);
     default:
         gpt_set_error("kpairs: unknown kernel_id %d", kp.kernel_id);
         return GPT_E_ARG;

@@ -26,7 +26,14 @@ static int kbuild_batch_d(hipStream_t st, int D, const KParams *d_kps, const dou
         hipLaunchKernelGGL((kbuild_kernel<KID, DD, true>), grid, block, 0, st, dummy, dX, dn, N, dX, dn, N, lower, \
                            (int64_t)0, (int64_t)0, d_err_y, 0.0, diag_add, dK, ldk, accumulate, d_kps, d_nv, bstride, dummy, d_kps2); \
         break;
-    switch (D) {
+    if constexpr (KID == GPT_KERNEL_GIBBS_TANH || KID == GPT_KERNEL_GIBBS_DTANH) {      // (1-D kernels: one instantiation)
+        switch (D) {
+            KBB_CASE(1)
+        default:
+            gpt_set_error("kbuild_batch: the Gibbs kernels need num_dim 1, got %d", D);
+            return GPT_E_ARG;
+        }
+    } else switch (D) {
         KBB_CASE(1) KBB_CASE(2) KBB_CASE(3) KBB_CASE(4) KBB_CASE(5) KBB_CASE(6) KBB_CASE(7) KBB_CASE(8)
         KBB_CASE(9) KBB_CASE(10) KBB_CASE(11) KBB_CASE(12) KBB_CASE(13) KBB_CASE(14) KBB_CASE(15) KBB_CASE(16)
     default:
@@ -51,6 +58,8 @@ int launch_kbuild_batch(hipStream_t st, int kernel_id, int D, const KParams *d_k
     case GPT_KERNEL_M52: return kbuild_batch_d<GPT_KERNEL_M52>(st, D, d_kps, d_noise_var, nbatch, dX, dn, N, d_err_y, diag_add, dK, ldk, bstride, accumulate, full, nullptr);
     case GPT_KERNEL_RQ: return kbuild_batch_d<GPT_KERNEL_RQ>(st, D, d_kps, d_noise_var, nbatch, dX, dn, N, d_err_y, diag_add, dK, ldk, bstride, accumulate, full, nullptr);
     case GPT_KERNEL_MATERN: return kbuild_batch_d<GPT_KERNEL_MATERN>(st, D, d_kps, d_noise_var, nbatch, dX, dn, N, d_err_y, diag_add, dK, ldk, bstride, accumulate, full, nullptr);
+    case GPT_KERNEL_GIBBS_TANH: return kbuild_batch_d<GPT_KERNEL_GIBBS_TANH>(st, D, d_kps, d_noise_var, nbatch, dX, dn, N, d_err_y, diag_add, dK, ldk, bstride, accumulate, full, nullptr);
+    case GPT_KERNEL_GIBBS_DTANH: return kbuild_batch_d<GPT_KERNEL_GIBBS_DTANH>(st, D, d_kps, d_noise_var, nbatch, dX, dn, N, d_err_y, diag_add, dK, ldk, bstride, accumulate, full, nullptr);
     default:
         gpt_set_error("kbuild_batch: kernel_id %d is not a fit kernel", kernel_id);
         return GPT_E_ARG;
@@ -74,7 +83,14 @@ static int kbuild_batch_cross_d(hipStream_t st, int D, const KParams *d_kps, con
         hipLaunchKernelGGL((kbuild_kernel<KID, DD, true>), grid, block, 0, st, dummy, dXi, dni, M, dXj, dnj, P, 0, (int64_t)0, \
                            (int64_t)0, nullptr, 0.0, 0.0, dK, ldk, accumulate, d_kps, d_nv, bstride, dummy, d_kps2);          \
         break;
-    switch (D) {
+    if constexpr (KID == GPT_KERNEL_GIBBS_TANH || KID == GPT_KERNEL_GIBBS_DTANH) {
+        switch (D) {
+            KBC_CASE(1)
+        default:
+            gpt_set_error("kbuild_batch_cross: the Gibbs kernels need num_dim 1, got %d", D);
+            return GPT_E_ARG;
+        }
+    } else switch (D) {
         KBC_CASE(1) KBC_CASE(2) KBC_CASE(3) KBC_CASE(4) KBC_CASE(5) KBC_CASE(6) KBC_CASE(7) KBC_CASE(8)
         KBC_CASE(9) KBC_CASE(10) KBC_CASE(11) KBC_CASE(12) KBC_CASE(13) KBC_CASE(14) KBC_CASE(15) KBC_CASE(16)
     default:
@@ -102,6 +118,8 @@ int launch_kbuild_batch_cross(hipStream_t st, int kernel_id, int D, const KParam
     case GPT_KERNEL_M52: return kbuild_batch_cross_d<GPT_KERNEL_M52>(st, D, d_kps, d_nv, nbatch, dXi, dni, M, dXj, dnj, P, dK, ldk, bstride, accumulate, nullptr);
     case GPT_KERNEL_RQ: return kbuild_batch_cross_d<GPT_KERNEL_RQ>(st, D, d_kps, d_nv, nbatch, dXi, dni, M, dXj, dnj, P, dK, ldk, bstride, accumulate, nullptr);
     case GPT_KERNEL_MATERN: return kbuild_batch_cross_d<GPT_KERNEL_MATERN>(st, D, d_kps, d_nv, nbatch, dXi, dni, M, dXj, dnj, P, dK, ldk, bstride, accumulate, nullptr);
+    case GPT_KERNEL_GIBBS_TANH: return kbuild_batch_cross_d<GPT_KERNEL_GIBBS_TANH>(st, D, d_kps, d_nv, nbatch, dXi, dni, M, dXj, dnj, P, dK, ldk, bstride, accumulate, nullptr);
+    case GPT_KERNEL_GIBBS_DTANH: return kbuild_batch_cross_d<GPT_KERNEL_GIBBS_DTANH>(st, D, d_kps, d_nv, nbatch, dXi, dni, M, dXj, dnj, P, dK, ldk, bstride, accumulate, nullptr);
     default:
         gpt_set_error("kbuild_batch_cross: kernel_id %d is not a fit kernel", kernel_id);
         return GPT_E_ARG;

@@ -67,6 +67,57 @@ __global__ __launch_bounds__(KB_THREADS) void kbuild_kernel(
     // derivative-order loads, no index selection (the ~25 scalar and ~6 vector instructions per row the general loop spends on
     // choosing among four formulas).  The test is once per tile and wave: the orders of the rows in one or two vector loads
     // and a ballot.  C3 (last quarter derivative rows): 56 % of the lower triangle's pairs.
+    if constexpr ((KID == GPT_KERNEL_GIBBS_TANH || KID == GPT_KERNEL_GIBBS_DTANH) && KB_CPT == 1) {
+        static_assert(D == 1, "the Gibbs kernels are one-dimensional");
+        // The warps are hoisted out of the row loop (kpair.hpp, GibbsPt): this lane's column point once, and the tile's
+        // 32 row points once per wave -- lane q (and q + 32) forms row rbase + q, the row loop reads it back with
+        // v_readlane into scalar registers.  Per pair: one v_rsq_f64 + Newton step, one exponential, a few FMAs.
+        const GibbsPt cp = gibbs_point(kp, xj[0][0]);
+        const int lane = (int)(threadIdx.x & 63);
+        const int64_t ir = (rbase + (lane & 31) < M) ? rbase + (lane & 31) : M - 1;
+        const GibbsPt rp = gibbs_point(kp, Xi[ir]);
+        const double s2 = kp.sigma * kp.sigma;
+        const bool col_d = __builtin_amdgcn_ballot_w64(njr[0][0] != 0) != 0;
+        bool row_d = false;
+        {
+            int rn = 0;
+            for (int64_t q = rbase + (threadIdx.x & 63); q < rend; q += 64) rn |= ni[q];
+            row_d = __builtin_amdgcn_ballot_w64(rn != 0) != 0;
+        }
+        if (!col_d && !row_d) {
+            // PLAIN tile: value class only
+            for (int64_t i = rbase; i < rend; i++) {
+                const int q = (int)(i - rbase);
+                const double xi = Xi[i];
+                const double a = readlane_f64(rp.l, q), ra = readlane_f64(rp.r2, q);
+                const double rb = gibbs_col_root(a, cp.rp, cp.rn);
+                double v = gibbs_core(s2, xi, a, 0.0, 0.0, ra, xj[0][0], cp.l, 0.0, 0.0, rb, 0, 0, false);
+                if (accumulate && jfirst < P) v += K[i * ldk + jfirst];
+                if (err_y != nullptr && (i + i0 == jfirst + j0)) {
+                    const double e = err_y[i + i0];
+                    v = ((v + noise_var) + e * e) + diag_add;
+                }
+                if (jfirst < P) K[i * ldk + jfirst] = v;
+            }
+            return;
+        }
+        for (int64_t i = rbase; i < rend; i++) {
+            const int q = (int)(i - rbase);
+            const double xi = Xi[i];
+            const int nir = ni[i];
+            const double a = readlane_f64(rp.l, q), ra = readlane_f64(rp.r2, q);
+            const double A = readlane_f64(rp.A, q), ha = readlane_f64(rp.h, q);
+            const double rb = gibbs_col_root(a, cp.rp, cp.rn);
+            double v = gibbs_core(s2, xi, a, A, ha, ra, xj[0][0], cp.l, cp.A, cp.h, rb, nir, njr[0][0], col_d || nir != 0);
+            if (accumulate && jfirst < P) v += K[i * ldk + jfirst];
+            if (err_y != nullptr && (i + i0 == jfirst + j0)) {
+                const double e = err_y[i + i0];
+                v = ((v + noise_var) + e * e) + diag_add;
+            }
+            if (jfirst < P) K[i * ldk + jfirst] = v;
+        }
+        return;
+    }
     if constexpr ((KID == GPT_KERNEL_SE || KID == GPT_KERNEL_M52) && KB_CPT == 1) {
         int cn = 0;
 #pragma unroll

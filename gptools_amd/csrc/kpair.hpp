@@ -573,6 +573,94 @@ __device__ __forceinline__ double plain_pair(const KParams &kp, const double *xi
     }
 }
 
+// ---- Gibbs kernels in 1-D (ref: gptools/kernel/gibbs.py:229-466, :508-558) ---------------------------------------------
+// k = sigma^2 sqrt(2ab/s) exp(-d^2/s),  a = l(x_i), b = l(x_j), s = a^2 + b^2, d = x_i - x_j.  The reference's derivative
+// classes (Mathematica polynomials up to l^8, gibbs.py:336-416) are k times a short factor; with u = 1/s, du = d u,
+// w = 2 du^2 - u, A = a a', B = b b':
+//     P = a'/(2a) - 2 du + A w                         k_10 = k P
+//     Q = b'/(2b) + 2 du + B w                         k_01 = k Q
+//     R = 2u (1 + 2 du (B - A) - A B (2w + u))         k_11 = k (P Q + R)
+// Everything that depends on one point only is a GibbsPt, formed once per point (the builder: once per column lane and
+// once per row of a tile, kbuild_kernel.hpp); a pair then costs one v_rsq_f64 + Newton step (t = 1/sqrt(s), u = t^2), one
+// exponential and a few FMAs.  sqrt(2ab/s) is split as sqrt(2|a|) sqrt(|b|) t, keeping the reference's signs: both
+// negative is finite, mixed signs NaN (sqrt of a negative), and a zero on either side 0 -- the column carries sqrt(|b|)
+// twice, NaN-masked for a positive row (b < 0) and for a negative row (b > 0).
+// lane `q` (wave-uniform) of a double, into scalar registers
+__device__ __forceinline__ double readlane_f64(double v, int q)
+{
+    const long long b = __double_as_longlong(v);
+    const int lo = __builtin_amdgcn_readlane((int)b, q), hi = __builtin_amdgcn_readlane((int)(b >> 32), q);
+    return __longlong_as_double(((long long)hi << 32) | (long long)(unsigned)lo);
+}
+
+struct GibbsPt {
+    double l, dl;       // l(x), l'(x)
+    double A, h;        // l l', l' / (2 l)
+    double r2;          // sqrt(2 |l|)   (row side)
+    double rp, rn;      // sqrt(|l|), NaN where l < 0 / where l > 0   (column side)
+};
+
+// l(x) = c + sum_q amp_q tanh((x - x0_q) / w_q) and l'(x) = sum_q amp_q / w_q cosh((x - x0_q) / w_q)^-2 in the reference's
+// order of operations (gibbs.py:459-464, :552-556); cosh overflows to inf beyond |u| = 710 and the slope is then 0, as there
+__device__ __forceinline__ GibbsPt gibbs_point(const KParams &kp, double x)
+{
+    double l = 0.0, dl = 0.0;
+    for (int q = 0; q < kp.g_nt; q++) {
+        const double u = (x - kp.g_x0[q]) / kp.g_w[q];
+        const double ch = cosh(u);
+        l = fma(kp.g_amp[q], tanh(u), l);
+        dl += kp.g_amp[q] / kp.g_w[q] * (1.0 / (ch * ch));
+    }
+    GibbsPt p;
+    p.l = l + kp.g_c;
+    p.dl = dl;
+    p.A = p.l * dl;
+    p.h = dl / (2.0 * p.l);
+    const double al = sqrt(fabs(p.l));
+    p.r2 = sqrt(2.0 * fabs(p.l));
+    p.rp = (p.l < 0.0) ? (double)NAN : al;
+    p.rn = (p.l > 0.0) ? (double)NAN : al;
+    return p;
+}
+
+// the column factor sqrt(|b|) that belongs to a row of length scale a (see above; a == 0: the unmasked root)
+__device__ __forceinline__ double gibbs_col_root(double a, double rp, double rn)
+{
+    return (a > 0.0) ? rp : (a < 0.0) ? rn : fmin(rp, rn);
+}
+
+// One pair from the row's (a, A, h_a, sqrt(2|a|)) and the column's (b, B, h_b, root) with orders ni, nj in {0, 1};
+// s2 = sigma^2.  `need_d`: some pair of the wave has a derivative order (else the value class alone).
+__device__ __forceinline__ double gibbs_core(double s2, double xi, double a, double A, double ha, double ra, double xj,
+                                             double b, double B, double hb, double rb, int ni, int nj, bool need_d)
+{
+    const double s = fma(a, a, b * b);
+    const double y0 = __builtin_amdgcn_rsq(s);
+    const double t = fma(0.5 * y0, fma(-(s * y0), y0, 1.0), y0);
+    const double u = t * t;
+    const double d = xi - xj;
+    // exp_neg drops a NaN of d^2 u; every such NaN (s, d) is in ra rb t as well
+    const double k = (s2 * (ra * rb * t)) * exp_neg(d * d * u);
+    if (!need_d) return k;
+    const double du = d * u;
+    const double w = fma(2.0 * du, du, -u);
+    const double P = fma(A, w, fma(-2.0, du, ha));
+    const double Q = fma(B, w, fma(2.0, du, hb));
+    double v = (nj == 1) ? k * Q : k;
+    if (ni == 1) {
+        const double R = 2.0 * u * fma(2.0 * du, B - A, fma(-(A * B), fma(2.0, w, u), 1.0));
+        v = (nj == 1) ? k * fma(P, Q, R) : k * P;
+    }
+    return v;
+}
+
+__device__ __forceinline__ double gibbs_pair(const KParams &kp, const double *xi, const double *xj, const int *ni, const int *nj)
+{
+    const GibbsPt p = gibbs_point(kp, xi[0]), q = gibbs_point(kp, xj[0]);
+    return gibbs_core(kp.sigma * kp.sigma, xi[0], p.l, p.A, p.h, p.r2, xj[0], q.l, q.A, q.h, gibbs_col_root(p.l, q.rp, q.rn),
+                      ni[0], nj[0], (ni[0] | nj[0]) != 0);
+}
+
 template <int KID, int D>
 __device__ __forceinline__ double any_pair(const KParams &kp, const double *xi, const double *xj,
                                            const int *ni, const int *nj)
@@ -582,6 +670,7 @@ __device__ __forceinline__ double any_pair(const KParams &kp, const double *xi, 
     if (KID == GPT_KERNEL_DIAGNOISE) return noise_pair<D>(kp, xi, xj, ni, nj);
     if (KID == GPT_KERNEL_RQ) return rq_pair<D>(kp, xi, xj, ni, nj);
     if (KID == GPT_KERNEL_MATERN) return matern_pair<D>(kp, xi, xj, ni, nj);
+    if (KID == GPT_KERNEL_GIBBS_TANH || KID == GPT_KERNEL_GIBBS_DTANH) return gibbs_pair(kp, xi, xj, ni, nj);
     return 0.0;
 }
 
@@ -597,6 +686,8 @@ __device__ __forceinline__ double factor_pair(const KParams &kp, const double *x
     case GPT_KERNEL_M52: return m52_pair<D>(kp, xi, xj, ni, nj);
     case GPT_KERNEL_RQ: return rq_pair<D>(kp, xi, xj, ni, nj);
     case GPT_KERNEL_MATERN: return matern_pair<D>(kp, xi, xj, ni, nj);
+    case GPT_KERNEL_GIBBS_TANH:
+    case GPT_KERNEL_GIBBS_DTANH: return gibbs_pair(kp, xi, xj, ni, nj);      // (1-D: the host admits no other D, and orders <= 1)
     default: return 0.0;
     }
 }

@@ -33,7 +33,9 @@ from .utils import CombinedBounds
 
 __all__ = ["GaussianProcess"]
 
-_NATIVE_FIT = (_lib.KERNEL_SE, _lib.KERNEL_M52, _lib.KERNEL_RQ, _lib.KERNEL_MATERN)
+_NATIVE_FIT = (_lib.KERNEL_SE, _lib.KERNEL_M52, _lib.KERNEL_RQ, _lib.KERNEL_MATERN, _lib.KERNEL_GIBBS_TANH,
+               _lib.KERNEL_GIBBS_DTANH)
+_GIBBS = (_lib.KERNEL_GIBBS_TANH, _lib.KERNEL_GIBBS_DTANH)
 
 
 def _uniform_to_normal(u):
@@ -127,7 +129,7 @@ class GaussianProcess(object):
         if not self.partitioned or self.use_hyper_deriv or self.T is not None or not self._fast_fit_possible():
             return False
         terms = self._native_terms()
-        if terms is None or len(terms) != 1:
+        if terms is None or len(terms) != 1 or terms[0][0] in _GIBBS:     # (the multi-GPU engines have no Gibbs builder)
             return False
         import torch.distributed as dist
         return dist.is_available() and dist.is_initialized()
@@ -1141,6 +1143,32 @@ class GaussianProcess(object):
             out["cov_without_func"] = list(ev["cov"])
             out["std_without_func"] = list(std)
         return out
+
+    def compute_l_from_MCMC(self, X, n=0, sampler=None, flat_trace=None, burn=0, thin=1, **kwargs):
+        """The covariance length-scale function ``k.l_func`` of a Gibbs kernel (its derivative for ``n = 1``) at ``X`` for each
+        row of a trace of the free hyperparameters (ref: gaussian_process.py:1989-2065, _ComputeLWrapper :2341-2377): an
+        ``(S, M)`` array, one row per trace row, where the reference returns a list (or a lazy ``map``).  A row whose
+        evaluation fails is NaN.  ``flat_trace[burn::thin]`` or, duck-typed, ``sampler.chain[:, burn::thin, :]`` flattened;
+        drawing the posterior itself (emcee) is not part of this package.  ``X`` and ``n`` go to ``l_func`` unchanged.
+        Host numpy (O(M S)); ``num_proc`` is accepted and ignored."""
+        trace = self._mcmc_trace(sampler, flat_trace, burn, thin)
+        X = np.asarray(X, dtype=float)
+        p = np.array(self.k.params, dtype=float)
+        free = ~np.asarray(self.k.fixed_params, dtype=bool)
+        nk = len(self.k.free_params)
+        rows = []
+        for t in trace:
+            try:
+                q = p.copy()
+                q[free] = t[:nk]
+                rows.append(np.asarray(self.k.l_func(X, n, *q[1:]), dtype=float))
+            except Exception:
+                if self.verbose:
+                    warnings.warn("Encountered exception during evaluation of MCMC samples. Exception is:\n%s\nParams are:\n%s"
+                                  % (traceback.format_exc(), str(list(t))))
+                rows.append(None)
+        shape = next((np.shape(r) for r in rows if r is not None), np.shape(X))
+        return np.array([np.full(shape, np.nan) if r is None else np.broadcast_to(r, shape) for r in rows], dtype=float)
 
     def predict_MCMC(self, X, ddof=1, full_MC=False, rejection_func=None, **kwargs):
         """Prediction marginalised over a trace of the hyperparameters (ref: gaussian_process.py:2144-2254): the mean of the

@@ -65,6 +65,14 @@ extern "C" {
                                   * k1^(a) k2^(n - a), evaluated per pair on the device (gpt_kpairs2 / gpt_kbuild2 / gpt_fit_terms);
                                   * combined derivative order of a pair <= GPT_RQ_MAXORD; no hyper-parameter derivatives
                                   * (NotImplementedError in the reference too) */
+#define GPT_KERNEL_GIBBS_TANH 7  /* GibbsKernel1dTanh, num_dim 1, params [sigma_f, l_1, l_2, l_w, x_0] (ref: kernel/gibbs.py:229-466):
+                                  * k = sigma_f^2 sqrt(2 l(x) l(x') / (l(x)^2 + l(x')^2)) exp(-(x - x')^2 / (l(x)^2 + l(x')^2)),
+                                  * l(x) = (l_1 + l_2)/2 - (l_1 - l_2)/2 tanh((x - x_0)/l_w).  Derivative order <= 1 per point
+                                  * (GPT_E_NOTIMPL beyond: "Derivatives greater than [1, 1] are not supported!"); num_dim != 1 or
+                                  * a wrong parameter count GPT_E_ARG; no hyper-parameter derivatives (GPT_E_NOTIMPL) */
+#define GPT_KERNEL_GIBBS_DTANH 8 /* GibbsKernel1dDoubleTanh, the same with params [sigma_f, l_c, l_m, l_e, l_a, l_b, x_a, x_b]
+                                  * (ref: kernel/gibbs.py:508-558): l(x) = a tanh((x - x_a)/l_a) + b tanh((x - x_b)/l_b) + c,
+                                  * a = (l_m - l_c)/2, b = (l_e - l_m)/2, c = (l_c + l_e)/2 */
 
 #define GPT_MAX_DIM 16      /* largest supported num_dim */
 #define GPT_WS_BLOCK 9216    /* doubles of factorisation workspace per 128 columns (d_invd arguments) */
