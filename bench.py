@@ -16,10 +16,18 @@ y / err_y vectors) cross the boundary.
                                                           # itself as child processes (self_launch)
 value  = algorithmic flops of the steps / wall time, in GFLOP/s, with the LAPACK potrf+potrs count
          (N^3/3 + N^2/2 + N/6 + 2 N^2) -- K-build time is in the denominator but adds no flops.
-roofline  : the trailing-update SYRK/GEMM kernel (fp64 MFMA bound), achieved = sum of algorithmic flops of the
-            large GEMM launches / sum of their HIP-event durations, measured in the timed steps.
+
+A plain run does only what `value` needs: set-up, --warmup steps, the --steps timed steps, --dump-outputs, the line.
+(With N > 1 that includes the tuning pass over the other schedules, since the fastest one becomes the line, and
+`roofline`, which HIP events take inside the timed steps.)  Everything else the bench measures or checks runs with --full,
+whose --no-* switches leave single legs out:
+roofline  : N = 1: the trailing-update SYRK/GEMM kernel (fp64 MFMA bound), achieved = sum of algorithmic flops of the
+            large GEMM launches / sum of their HIP-event durations, in instrumented steps after the timed region.
 cpu_baseline : the oracle's fused K-build (OpenMP) + scipy.linalg.cholesky / cho_solve on the host cores
-            (rank 0, N=1 only), a reported baseline and the parity reference for ll.
+            (rank 0), a reported baseline and the reference of the parity gate, which fails the run (exit 4).
+other legs : N = 1: two evaluations in flight (`batched`), the step without alpha (`lazy_alpha`), the plugin API
+            (`via_gp_api`, `with_alpha`), predict, the K build alone.  N > 1: C5 partitioned, C3 replicas, step trace and
+            link probes, the single-GPU run of the same workload.
 """
 import argparse
 import json
@@ -359,14 +367,17 @@ def main():
     ap.add_argument("--warmup", type=int, default=3)
     ap.add_argument("--workload", default=None, choices=sorted(WORKLOADS))
     ap.add_argument("--nb", type=int, default=0, help="outer block width (0 = default)")
-    ap.add_argument("--no-cpu", action="store_true", help="skip the cpu_baseline leg")
+    ap.add_argument("--full", action="store_true",
+                    help="also run every leg beside the headline: CPU baseline + parity gate, roofline of instrumented steps, "
+                         "throughput, plugin API, predict and K-build legs (N=1), C5 / replica / probe / single-GPU legs (N>1)")
+    ap.add_argument("--no-cpu", action="store_true", help="with --full: skip the cpu_baseline leg")
     ap.add_argument("--dist", action="store_true", help="use the block-cyclic DistributedLML path even with one rank")
-    ap.add_argument("--no-batched", action="store_true", help="N=1: skip the two-evaluations-in-flight throughput leg")
-    ap.add_argument("--no-predict", action="store_true", help="N=1: skip the predict leg")
-    ap.add_argument("--no-gp-api", action="store_true", help="N=1: skip the GaussianProcess.update_hyperparameters leg")
-    ap.add_argument("--no-ref", action="store_true", help="N>1: skip the single-GPU run of the same workload on rank 0")
+    ap.add_argument("--no-batched", action="store_true", help="with --full, N=1: skip the two-evaluations-in-flight throughput leg")
+    ap.add_argument("--no-predict", action="store_true", help="with --full, N=1: skip the predict leg")
+    ap.add_argument("--no-gp-api", action="store_true", help="with --full, N=1: skip the GaussianProcess.update_hyperparameters leg")
+    ap.add_argument("--no-ref", action="store_true", help="with --full, N>1: skip the single-GPU run of the same workload on rank 0")
     ap.add_argument("--schedule", default=None, help="N>1: fix the layout (1d+bcast, 1d+scatter_gather, grid2x4, ...) instead of tuning")
-    ap.add_argument("--no-probe", action="store_true", help="N>1: skip the step trace and the link probes after the timed region")
+    ap.add_argument("--no-probe", action="store_true", help="with --full, N>1: skip the step trace and the link probes after the timed region")
     ap.add_argument("--ctx-opt", action="append", default=[], metavar="KEY=VALUE",
                     help="N=1: a gpt_ctx_set_option pair for the timed context (scratch/prof_r06.sh traces with tail_wait=0)")
     ap.add_argument("--dump-outputs", default=None, metavar="DIR",
@@ -439,7 +450,7 @@ def main():
         ctx = _lib.Context(local_rank)
         # (the second context of the throughput leg is created before the first one runs: streams created after
         # another context has been busy share hardware queues with it on ROCm 7 -- 173 instead of 210 evaluations/s)
-        ctx2 = None if args.no_batched else _lib.Context(local_rank)
+        ctx2 = _lib.Context(local_rank) if (args.full and not args.no_batched) else None
         if args.nb:
             ctx.set_option("nb_outer", args.nb)
         for kv_ in args.ctx_opt:
@@ -453,12 +464,12 @@ def main():
             return ctx.fit(KID[kernel], params, 0.0, y, err, diag_add)
         for _ in range(args.warmup):
             ll, ld = step()
-        # The throughput leg (two contexts, two host threads) runs first, inside _lib.concurrent_evaluations(): while several
-        # chains are in flight the library keeps every look-ahead on event edges (a kernel spinning on a flag word must not
+        # With --full, the throughput leg (two contexts, two host threads) runs first, inside _lib.concurrent_evaluations():
+        # while several chains are in flight the library keeps every look-ahead on event edges (a kernel spinning on a flag word must not
         # share the hardware queues with a second chain: gptools_amd/csrc/api.hip, EvalScope).  The second context then
         # STAYS ALIVE through the timed loop -- as GaussianProcess's pooled context does -- because what decides the schedule
         # is the number of evaluations in flight, not of contexts alive; `flag_schedule` / `live_contexts` below say what ran.
-        if not args.no_batched:
+        if ctx2 is not None:
             # Throughput mode (reported beside `value`, never in it): two INDEPENDENT evaluations (different theta, same
             # data) in flight on the GPU, one context + host thread each -- how GaussianProcess.ll_batch /
             # compute_ll_matrix / multi-start MAP run.  One factorisation's latency-bound tail overlaps the other's
@@ -502,7 +513,7 @@ def main():
         # time / --steps.
         # The bench's own instrumentation -- HIP events on every >= 1-GFLOP GEMM launch of the main stream (`roofline`) and around
         # the K-build / factorisation phases -- costs 0.13 ms per C3 step (3 %; scratch/instr_ab.py) and is not part of the
-        # product: it runs on INSTR_STEPS further evaluations right after the timed region (100-180 timed launches),
+        # product: with --full it runs on INSTR_STEPS further evaluations right after the timed region (100-180 timed launches),
         # `roofline.sampled_steps` says how many.
         INSTR_STEPS = 8
         alpha_box = [None]
@@ -535,87 +546,91 @@ def main():
         extra["timed_region"] = {"steps": args.steps, "seconds": elapsed,
                                  "note": "exactly --steps full evaluations between barrier + synchronize, none of them instrumented; "
                                          "ms_per_step and value are their mean"}
-        ctx.gemm_profile_read()
-        t_instr, tk, tp, n_instr = [], 0.0, 0.0, 0
-        for _ in range(INSTR_STEPS):
-            ctx.set_option("profile_gemm", 1)
+        if args.full:
+            # instrumented steps (`roofline`, `kbuild_ms`, `potrf_ms`), then the step without alpha (`lazy_alpha`)
+            ctx.gemm_profile_read()
+            t_instr, tk, tp, n_instr = [], 0.0, 0.0, 0
+            for _ in range(INSTR_STEPS):
+                ctx.set_option("profile_gemm", 1)
+                ctx.set_option("timing", 1)
+                ts_ = time.perf_counter()
+                step_full()
+                t_instr.append(time.perf_counter() - ts_)
+                tm_ = ctx.last_timings()
+                tk += tm_["kbuild"]
+                tp += tm_["potrf"]
+                n_instr += 1
+                ctx.set_option("profile_gemm", 0)
+                ctx.set_option("timing", 0)
+            gflops_alg, gms, gcount, gbytes = ctx.gemm_profile_read(with_bytes=True)
+            # sibling: the evaluation without alpha (what update_hyperparameters costs in the MAP loop, which never reads alpha);
+            # executed flops = potrf + the forward half of potrs
+            ctx.set_option("eager_alpha", 0)
+            for _ in range(2):
+                step()
+            per_l = timed_steps(step)[0] / args.steps
+            extra["lazy_alpha"] = {"ms_per_step": per_l * 1e3, "value": flops_fit(N, alpha=False) / per_l * 1e-9, "unit": "GFLOP/s",
+                                   "pct_fp64_mfma_peak": 100.0 * flops_fit(N, alpha=False) / per_l * 1e-12 / FP64_MFMA_PEAK_TFLOPS,
+                                   "lml_evals_per_s": 1.0 / per_l,
+                                   "alpha_extra_ms": (elapsed / args.steps - per_l) * 1e3,
+                                   "note": "the same step with alpha left to first use (gp.alpha, predict, the analytic gradient): z = L^-1 y "
+                                           "and ll only -- the headline of rounds 1-5; flops counted: potrf + the forward half of potrs"}
             ctx.set_option("timing", 1)
-            ts_ = time.perf_counter()
-            step_full()
-            t_instr.append(time.perf_counter() - ts_)
-            tm_ = ctx.last_timings()
-            tk += tm_["kbuild"]
-            tp += tm_["potrf"]
-            n_instr += 1
-            ctx.set_option("profile_gemm", 0)
-            ctx.set_option("timing", 0)
-        gflops_alg, gms, gcount, gbytes = ctx.gemm_profile_read(with_bytes=True)
-        # sibling: the evaluation without alpha (what update_hyperparameters costs in the MAP loop, which never reads alpha);
-        # executed flops = potrf + the forward half of potrs
-        ctx.set_option("eager_alpha", 0)
-        for _ in range(2):
-            step()
-        per_l = timed_steps(step)[0] / args.steps
-        extra["lazy_alpha"] = {"ms_per_step": per_l * 1e3, "value": flops_fit(N, alpha=False) / per_l * 1e-9, "unit": "GFLOP/s",
-                               "pct_fp64_mfma_peak": 100.0 * flops_fit(N, alpha=False) / per_l * 1e-12 / FP64_MFMA_PEAK_TFLOPS,
-                               "lml_evals_per_s": 1.0 / per_l,
-                               "alpha_extra_ms": (elapsed / args.steps - per_l) * 1e3,
-                               "note": "the same step with alpha left to first use (gp.alpha, predict, the analytic gradient): z = L^-1 y "
-                                       "and ll only -- the headline of rounds 1-5; flops counted: potrf + the forward half of potrs"}
-        ctx.set_option("timing", 1)
-        if gcount:
-            ach = gflops_alg / (gms * 1e-3) * 1e-12
-            import glob
-            roof = {"bound": "mfma", "kernel": "gemm_nt_kernel<64,64> (trailing SYRK/GEMM updates >= 1 GFLOP on the main stream)",
-                    "achieved": ach, "peak": FP64_MFMA_PEAK_TFLOPS, "unit": "TFLOP/s", "frac": ach / FP64_MFMA_PEAK_TFLOPS,
-                    "frac_events": ach / FP64_MFMA_PEAK_TFLOPS,
-                    "launch_population": "the >= 1 GFLOP launches of the timed steps' own schedule (flag edges: urgent + rest merged, one "
-                                         "launch per panel), HIP events on the dispatch packets of the main stream; in the instrumented "
-                                         "steps (after the timed region) the main stream's wait for the next panel is a kernel of its own -- "
-                                         "the other steps let the update's last workgroup wait (option tail_wait), which a timed launch "
-                                         "would report as its own duration (the library drops it while profile_gemm is on; the committed "
-                                         "kernel trace is taken with --ctx-opt tail_wait=0 for the same reason)",
-                    "launches_per_step": gcount / max(n_instr, 1), "sampled_steps": n_instr,
-                    "avg_launch_us": gms * 1e3 / gcount, "flops_per_launch": gflops_alg / gcount,
-                    "algorithmic_bytes": gbytes / gcount, "traffic_unit": "bytes/launch"}
-            # frac_trace: the same launches' average duration in the committed rocprofv3 --kernel-trace --stats run of this command
-            # (scratch/pmc_summary.py writes profiles/rNN_gemm_trace.json beside the summary); traffic: HBM bytes per launch from the
-            # committed PMC passes over a REPLAY of the same launch shapes (scratch/gemm_replay.py: a counter pass runs one kernel at a
-            # time, so the library cannot keep its flag edges there -- the shapes of a flag-schedule evaluation are logged and replayed
-            # one by one): one launch population throughout (VERDICT r5 #2b).
-            tr_ = sorted(glob.glob(os.path.join(ROOT, "profiles", "r*_gemm_trace.json")))
-            if wl == "c3" and tr_:
-                tj_ = json.load(open(tr_[-1]))
-                roof["frac_trace"] = tj_["flops_per_launch"] / (tj_["avg_launch_us"] * 1e-6) * 1e-12 / FP64_MFMA_PEAK_TFLOPS
-                roof["trace_avg_launch_us"] = tj_["avg_launch_us"]
-                roof["trace_flops_per_launch"] = tj_["flops_per_launch"]
-                roof["trace_file"] = tj_.get("trace_file")
-            else:
-                roof["frac_trace"] = None
-            tf_ = sorted(glob.glob(os.path.join(ROOT, "profiles", "r*_gemm_traffic.json")))
-            roof["traffic"] = None
-            if wl == "c3" and tf_:
-                tj_ = json.load(open(tf_[-1]))
-                if tj_.get("population") == "replay of the flag schedule's launches":
-                    roof["traffic"] = tj_["hbm_bytes_per_launch"]
-                    roof["traffic_ratio"] = tj_["hbm_bytes_per_launch"] / tj_["algorithmic_bytes_per_launch"]
-                    roof["traffic_flops_per_launch"] = tj_["flops_per_launch"]
-                    roof["traffic_algorithmic_bytes"] = tj_["algorithmic_bytes_per_launch"]
-                    roof["traffic_file"] = os.path.relpath(tf_[-1], ROOT)
-                    roof["traffic_note"] = tj_.get("note")
-        extra["methodology"] = {"version": 7, "instrumented": "%d steps after the timed region" % INSTR_STEPS,
-                                "ms_per_step_instrumented": 1e3 * sum(t_instr) / max(len(t_instr), 1),
+            if gcount:
+                ach = gflops_alg / (gms * 1e-3) * 1e-12
+                import glob
+                roof = {"bound": "mfma", "kernel": "gemm_nt_kernel<64,64> (trailing SYRK/GEMM updates >= 1 GFLOP on the main stream)",
+                        "achieved": ach, "peak": FP64_MFMA_PEAK_TFLOPS, "unit": "TFLOP/s", "frac": ach / FP64_MFMA_PEAK_TFLOPS,
+                        "frac_events": ach / FP64_MFMA_PEAK_TFLOPS,
+                        "launch_population": "the >= 1 GFLOP launches of the timed steps' own schedule (flag edges: urgent + rest merged, one "
+                                             "launch per panel), HIP events on the dispatch packets of the main stream; in the instrumented "
+                                             "steps (after the timed region) the main stream's wait for the next panel is a kernel of its own -- "
+                                             "the other steps let the update's last workgroup wait (option tail_wait), which a timed launch "
+                                             "would report as its own duration (the library drops it while profile_gemm is on; the committed "
+                                             "kernel trace is taken with --ctx-opt tail_wait=0 for the same reason)",
+                        "launches_per_step": gcount / max(n_instr, 1), "sampled_steps": n_instr,
+                        "avg_launch_us": gms * 1e3 / gcount, "flops_per_launch": gflops_alg / gcount,
+                        "algorithmic_bytes": gbytes / gcount, "traffic_unit": "bytes/launch"}
+                # frac_trace: the same launches' average duration in the committed rocprofv3 --kernel-trace --stats run of this command
+                # (scratch/pmc_summary.py writes profiles/rNN_gemm_trace.json beside the summary); traffic: HBM bytes per launch from the
+                # committed PMC passes over a REPLAY of the same launch shapes (scratch/gemm_replay.py: a counter pass runs one kernel at a
+                # time, so the library cannot keep its flag edges there -- the shapes of a flag-schedule evaluation are logged and replayed
+                # one by one): one launch population throughout (VERDICT r5 #2b).
+                tr_ = sorted(glob.glob(os.path.join(ROOT, "profiles", "r*_gemm_trace.json")))
+                if wl == "c3" and tr_:
+                    tj_ = json.load(open(tr_[-1]))
+                    roof["frac_trace"] = tj_["flops_per_launch"] / (tj_["avg_launch_us"] * 1e-6) * 1e-12 / FP64_MFMA_PEAK_TFLOPS
+                    roof["trace_avg_launch_us"] = tj_["avg_launch_us"]
+                    roof["trace_flops_per_launch"] = tj_["flops_per_launch"]
+                    roof["trace_file"] = tj_.get("trace_file")
+                else:
+                    roof["frac_trace"] = None
+                tf_ = sorted(glob.glob(os.path.join(ROOT, "profiles", "r*_gemm_traffic.json")))
+                roof["traffic"] = None
+                if wl == "c3" and tf_:
+                    tj_ = json.load(open(tf_[-1]))
+                    if tj_.get("population") == "replay of the flag schedule's launches":
+                        roof["traffic"] = tj_["hbm_bytes_per_launch"]
+                        roof["traffic_ratio"] = tj_["hbm_bytes_per_launch"] / tj_["algorithmic_bytes_per_launch"]
+                        roof["traffic_flops_per_launch"] = tj_["flops_per_launch"]
+                        roof["traffic_algorithmic_bytes"] = tj_["algorithmic_bytes_per_launch"]
+                        roof["traffic_file"] = os.path.relpath(tf_[-1], ROOT)
+                        roof["traffic_note"] = tj_.get("note")
+        extra["methodology"] = {"version": 7,
+                                "instrumented": ("%d steps after the timed region" % INSTR_STEPS) if args.full else "none (--full only)",
                                 "ms_per_step_plain": 1e3 * elapsed / args.steps,
                                 "note": "version 7: exactly --steps timed steps, none instrumented; version 6: rounds of --steps repeated to "
                                         "1 s, median round, one instrumented step per two rounds; versions >= 6: a step computes and returns "
                                         "alpha (full compute_K_L_alpha_ll, full LAPACK flop count); versions <= 5: no alpha in the step, "
                                         "executed flops -- compare those with `lazy_alpha`"}
+        if args.full:
+            extra["methodology"]["ms_per_step_instrumented"] = 1e3 * sum(t_instr) / max(len(t_instr), 1)
         extra["live_contexts"] = 1 if ctx2 is None else 2
         # The same step through the plugin API (north_star's unit: GaussianProcess.update_hyperparameters, ref
         # gaussian_process.py:1332-1416): a GaussianProcess over the same data whose main / pooled contexts ARE the two of this
         # bench -- the same streams and hardware queues as the timed loop above, so the difference is what the Python layer
         # costs (parameter bookkeeping, the log-prior, ctypes) and which schedule the library picks for it.
-        if not args.no_gp_api:
+        if args.full and not args.no_gp_api:
             import warnings
             import gptools_amd as g
             kcls_ = {"se": g.SquaredExponentialKernel, "m52": g.Matern52Kernel}[kernel]
@@ -684,7 +699,7 @@ def main():
         # predict leg (SURVEY 8d "Predict (if timed): N^2 M + N M^2"; ref gaussian_process.py:965-1006) on the factor of
         # the last timed step: K* build, mean = K*^T alpha, v = L^-1 K*, then the row norms (std) or the SYRK (cov).
         # Host buffers in and out (Xstar up, mean / std / cov down) are inside the wall time.
-        if not args.no_predict:
+        if args.full and not args.no_predict:
             rsp = np.random.RandomState(4096)
             pl = {}
             lib_ = _lib.load()
@@ -731,38 +746,39 @@ def main():
                           "2 M^2 S for 16 samples, only M x 16 doubles come back); flops = N^2 M (triangular solve) + "
                           "N M^2 (cov) or 2 N M (std)")
             extra["predict"] = pl
-        extra["kbuild_ms"] = tk / max(n_instr, 1)
-        extra["potrf_ms"] = tp / max(n_instr, 1)
-        extra["kbuild_GBps_written"] = (8.0 * N * (N + 1) / 2.0) / (tk / max(n_instr, 1) * 1e-3) * 1e-9
-        # the same K build ALONE on the chip (inside a fit the panel stream starts its first diagonal block under it, so
-        # the in-fit figure above is the time to the K build's end, not the builder's rate): gpt_dev_kbuild on device
-        # buffers, HIP events on the context's stream
-        try:
-            st_ = torch.cuda.ExternalStream(int(ctx.stream))
-            with torch.cuda.stream(st_):
-                dX_ = torch.from_numpy(np.ascontiguousarray(X)).cuda()
-                dn_ = torch.from_numpy(np.ascontiguousarray(n, dtype=np.int32)).cuda()
-                de_ = torch.from_numpy(np.ascontiguousarray(err)).cuda()
-                dK_ = torch.empty((N, N), dtype=torch.float64, device="cuda")
-                lib_ = _lib.load()
-                best_ = 1e9
-                for _ in range(6):
-                    e0_, e1_ = torch.cuda.Event(enable_timing=True), torch.cuda.Event(enable_timing=True)
-                    e0_.record(st_)
-                    _lib.check(lib_.gpt_dev_kbuild(ctx.handle, KID[kernel], _lib.dptr(params), len(params), dX_.data_ptr(),
-                                                   dn_.data_ptr(), N, dX_.data_ptr(), dn_.data_ptr(), N, d, -1, 1, None, 1, 0, 0,
-                                                   de_.data_ptr(), 0.0, float(diag_add), dK_.data_ptr(), N))
-                    e1_.record(st_)
-                    st_.synchronize()
-                    best_ = min(best_, e0_.elapsed_time(e1_))
-            extra["kbuild_standalone"] = {"ms": best_, "GBps_written": (8.0 * N * (N + 1) / 2.0) / (best_ * 1e-3) * 1e-9,
-                                          "frac_hbm": (8.0 * N * (N + 1) / 2.0) / (best_ * 1e-3) * 1e-12 / 6.3,
-                                          "note": "lower triangle + fused diagonal, best of 6, alone on the GPU; frac_hbm against 6.3 TB/s "
-                                                  "achievable write bandwidth (the same store pattern without arithmetic reaches 5.6 TB/s at this "
-                                                  "N; the builder is bound by its arithmetic: DESIGN.md section 7.7)"}
-            del dK_
-        except Exception as e_:       # (reported, never fatal: the headline line does not depend on it)
-            extra["kbuild_standalone"] = {"error": repr(e_)}
+        if args.full:
+            extra["kbuild_ms"] = tk / max(n_instr, 1)
+            extra["potrf_ms"] = tp / max(n_instr, 1)
+            extra["kbuild_GBps_written"] = (8.0 * N * (N + 1) / 2.0) / (tk / max(n_instr, 1) * 1e-3) * 1e-9
+            # the same K build ALONE on the chip (inside a fit the panel stream starts its first diagonal block under it, so
+            # the in-fit figure above is the time to the K build's end, not the builder's rate): gpt_dev_kbuild on device
+            # buffers, HIP events on the context's stream
+            try:
+                st_ = torch.cuda.ExternalStream(int(ctx.stream))
+                with torch.cuda.stream(st_):
+                    dX_ = torch.from_numpy(np.ascontiguousarray(X)).cuda()
+                    dn_ = torch.from_numpy(np.ascontiguousarray(n, dtype=np.int32)).cuda()
+                    de_ = torch.from_numpy(np.ascontiguousarray(err)).cuda()
+                    dK_ = torch.empty((N, N), dtype=torch.float64, device="cuda")
+                    lib_ = _lib.load()
+                    best_ = 1e9
+                    for _ in range(6):
+                        e0_, e1_ = torch.cuda.Event(enable_timing=True), torch.cuda.Event(enable_timing=True)
+                        e0_.record(st_)
+                        _lib.check(lib_.gpt_dev_kbuild(ctx.handle, KID[kernel], _lib.dptr(params), len(params), dX_.data_ptr(),
+                                                       dn_.data_ptr(), N, dX_.data_ptr(), dn_.data_ptr(), N, d, -1, 1, None, 1, 0, 0,
+                                                       de_.data_ptr(), 0.0, float(diag_add), dK_.data_ptr(), N))
+                        e1_.record(st_)
+                        st_.synchronize()
+                        best_ = min(best_, e0_.elapsed_time(e1_))
+                extra["kbuild_standalone"] = {"ms": best_, "GBps_written": (8.0 * N * (N + 1) / 2.0) / (best_ * 1e-3) * 1e-9,
+                                              "frac_hbm": (8.0 * N * (N + 1) / 2.0) / (best_ * 1e-3) * 1e-12 / 6.3,
+                                              "note": "lower triangle + fused diagonal, best of 6, alone on the GPU; frac_hbm against 6.3 TB/s "
+                                                      "achievable write bandwidth (the same store pattern without arithmetic reaches 5.6 TB/s at this "
+                                                      "N; the builder is bound by its arithmetic: DESIGN.md section 7.7)"}
+                del dK_
+            except Exception as e_:       # (reported, never fatal: the headline line does not depend on it)
+                extra["kbuild_standalone"] = {"error": repr(e_)}
         parallelism = "1 GPU, look-ahead on a second HIP stream"
     else:
         from gptools_amd.dist import DistributedLML, GridLML, HipPanelOps
@@ -857,7 +873,7 @@ def main():
         extra["schedules_ms"] = tune
         extra["schedule"] = base_name
         cpu_ref = None
-        if not args.no_cpu:
+        if args.full and not args.no_cpu:
             # The CPU path once on the SAME workload, now (before the legs that run under the watchdog), so that the
             # line kept for the watchdog already carries cpu_baseline and parity: rank 0's host cores work, the other
             # ranks wait at the barrier.
@@ -930,7 +946,7 @@ def main():
         torch.cuda.empty_cache()
         wd.phase = "diagnostics after the timed region"
         extra["host_enqueue_ms"] = plan.timings.get("host_enqueue_s", 0.0) * 1e3
-        if (world > 1 or os.environ.get("GPT_BENCH_C5_TOO")) and wl == "c4" and not args.no_probe:
+        if args.full and (world > 1 or os.environ.get("GPT_BENCH_C5_TOO")) and wl == "c4" and not args.no_probe:
             # SURVEY 8e also asks for the partitioned factorisation at C5's size (N = 16384): same schedule, reported
             # beside the headline (a few evaluations after the timed region; never in `value`)
             try:
@@ -960,7 +976,7 @@ def main():
             except (RuntimeError, ValueError) as e:
                 plan = main_plan
                 extra["c5_partitioned"] = {"error": repr(e)[:200]}
-        if (world > 1 or os.environ.get("GPT_BENCH_C5_TOO")) and not args.no_probe:
+        if args.full and (world > 1 or os.environ.get("GPT_BENCH_C5_TOO")) and not args.no_probe:
             # The other way to use N GPUs (below N ~ 10k a partitioned factorisation cannot beat one
             # GPU): independent evaluations of the metric's own configuration (C3, N = 8192), two in flight per GPU, every
             # rank its own hyperparameters -- aggregate LML evaluations/s of the job (weak scaling; never in `value`).
@@ -1001,7 +1017,7 @@ def main():
                 del pair
             except (RuntimeError, ValueError) as e:
                 extra["replicas_c3"] = {"error": repr(e)[:200]}
-        if not args.no_probe:
+        if args.full and not args.no_probe:
             # after the timed region: where the time of one evaluation goes on rank 0, and what the links deliver
             try:
                 extra["trace"] = dist_trace(plan, step)
@@ -1011,7 +1027,7 @@ def main():
                 extra["probe_error"] = repr(e)[:300]
         # Same workload on ONE GPU (rank 0, single-context path), measured in the same run, so that the speed-up of
         # the partitioned factorisation can be read off this line (the N=1 bench line is a different workload, C3).
-        if (world > 1 or args.dist) and not args.no_ref:
+        if args.full and (world > 1 or args.dist) and not args.no_ref:
             if rank == 0:
                 ctx = _lib.Context(local_rank)
                 ctx.set_data(X, n)
@@ -1036,7 +1052,7 @@ def main():
                               "(executed flops)") if full_eval else
                              ("executed flops: LAPACK potrf count + the forward half of potrs (z = L^-1 y rides along as the augmented "
                               "row); the partitioned engines evaluate ll only"))
-        if not args.no_cpu:
+        if args.full and not args.no_cpu:
             from oracle import oracle as O
             if world == 1 and not args.dist:
                 ref, cb = cpu_baseline(kernel, X, n, y, err, params, workload=WORKLOADS[wl])

@@ -5,11 +5,11 @@ O=$R/gpurun_out/r02c
 rm -rf $O; mkdir -p $O
 cd $R
 python -m pytest tests -m gpu -x -q 2>&1 | tail -6 > $O/pytest.txt
-python bench.py --steps 20 --warmup 5 > $O/bench_c3_line.json 2> $O/bench_c3.err
-python bench.py --steps 10 --warmup 3 --workload c2 --no-batched > $O/bench_c2_line.json 2> $O/bench_c2.err
-python bench.py --steps 10 --warmup 3 --workload c5 --no-batched > $O/bench_c5_line.json 2> $O/bench_c5.err
-python bench.py --steps 5 --warmup 2 --workload c4 --no-batched > $O/bench_c4_line.json 2> $O/bench_c4.err
-python bench.py --gpus 1 --dist --workload c4 --steps 5 --warmup 2 > $O/bench_dist_c4_line.json 2> $O/bench_dist_c4.err
+python bench.py --full --steps 20 --warmup 5 > $O/bench_c3_line.json 2> $O/bench_c3.err
+python bench.py --full --steps 10 --warmup 3 --workload c2 --no-batched > $O/bench_c2_line.json 2> $O/bench_c2.err
+python bench.py --full --steps 10 --warmup 3 --workload c5 --no-batched > $O/bench_c5_line.json 2> $O/bench_c5.err
+python bench.py --full --steps 5 --warmup 2 --workload c4 --no-batched > $O/bench_c4_line.json 2> $O/bench_c4.err
+python bench.py --full --gpus 1 --dist --workload c4 --steps 5 --warmup 2 > $O/bench_dist_c4_line.json 2> $O/bench_dist_c4.err
 # (the stamp programs compile the PRODUCT sources with -DGPT_*_STAMPS: rebuilt here so that they match the library)
 hipcc --offload-arch=gfx950 -O3 -std=c++17 -ffp-contract=off -w -DGPT_PD_STAMPS -Iinclude -o scratch/potf2_stamps scratch/potf2_stamps.hip
 hipcc --offload-arch=gfx950 -O3 -std=c++17 -ffp-contract=off -w -DGPT_GEMM_STAMPS -Iinclude -o scratch/gemm_stamps scratch/gemm_stamps.hip

@@ -6,11 +6,11 @@ rm -rf $O; mkdir -p $O
 cd $R
 cp scratch/HEAD_for_collect.txt $O/HEAD.txt 2>/dev/null
 timeout 1200 python -m pytest tests -m gpu -x -q 2>&1 | tail -8 > $O/pytest.txt
-timeout 300 python bench.py --steps 20 --warmup 5 > $O/bench_c3_line.json 2> $O/bench_c3.err
-timeout 200 python bench.py --steps 10 --warmup 3 --workload c2 --no-batched > $O/bench_c2_line.json 2> $O/bench_c2.err
-timeout 300 python bench.py --steps 10 --warmup 3 --workload c5 --no-batched > $O/bench_c5_line.json 2> $O/bench_c5.err
-timeout 400 python bench.py --steps 5 --warmup 2 --workload c4 --no-batched > $O/bench_c4_line.json 2> $O/bench_c4.err
-timeout 600 python bench.py --gpus 1 --dist --workload c4 --steps 5 --warmup 2 > $O/bench_dist_c4_line.json 2> $O/bench_dist_c4.err
+timeout 300 python bench.py --full --steps 20 --warmup 5 > $O/bench_c3_line.json 2> $O/bench_c3.err
+timeout 200 python bench.py --full --steps 10 --warmup 3 --workload c2 --no-batched > $O/bench_c2_line.json 2> $O/bench_c2.err
+timeout 300 python bench.py --full --steps 10 --warmup 3 --workload c5 --no-batched > $O/bench_c5_line.json 2> $O/bench_c5.err
+timeout 400 python bench.py --full --steps 5 --warmup 2 --workload c4 --no-batched > $O/bench_c4_line.json 2> $O/bench_c4.err
+timeout 600 python bench.py --full --gpus 1 --dist --workload c4 --steps 5 --warmup 2 > $O/bench_dist_c4_line.json 2> $O/bench_dist_c4.err
 for N in 256 1024 2048; do timeout 200 python scratch/batch_grid_bench.py $N 64; done > $O/batch_grid.txt 2>&1
 for N in 512 1024 2048; do timeout 300 python scratch/batch_terms_bench.py $N 64; done >> $O/batch_grid.txt 2>&1
 timeout 200 python scratch/kb_alone.py 8192 > $O/kb_alone.txt 2>&1

@@ -13,12 +13,12 @@ cp $O/prof/gemm_trace.json $O/gemm_trace.json
 cp $O/prof/gemm_traffic.json profiles/r06_gemm_traffic.json
 cp $O/prof/gemm_trace.json profiles/r06_gemm_trace.json
 # (2) the bench lines
-timeout 600 python bench.py --gpus 1 --steps 20 --warmup 5 > $O/bench_c3_N8192_line.json 2> $O/bench_c3.err
-timeout 300 python bench.py > $O/bench_default_line.json 2> $O/bench_default.err
-timeout 300 python bench.py --steps 10 --warmup 3 --workload c2 --no-batched > $O/bench_c2_line.json 2> $O/bench_c2.err
-timeout 400 python bench.py --steps 10 --warmup 3 --workload c5 --no-batched > $O/bench_c5_line.json 2> $O/bench_c5.err
-timeout 600 python bench.py --steps 5 --warmup 2 --workload c4 --no-batched > $O/bench_c4_line.json 2> $O/bench_c4.err
-timeout 900 python bench.py --gpus 1 --dist --workload c4 --steps 5 --warmup 2 > $O/bench_dist_c4_line.json 2> $O/bench_dist_c4.err
+timeout 600 python bench.py --full --gpus 1 --steps 20 --warmup 5 > $O/bench_c3_N8192_line.json 2> $O/bench_c3.err
+timeout 300 python bench.py --full > $O/bench_default_line.json 2> $O/bench_default.err
+timeout 300 python bench.py --full --steps 10 --warmup 3 --workload c2 --no-batched > $O/bench_c2_line.json 2> $O/bench_c2.err
+timeout 400 python bench.py --full --steps 10 --warmup 3 --workload c5 --no-batched > $O/bench_c5_line.json 2> $O/bench_c5.err
+timeout 600 python bench.py --full --steps 5 --warmup 2 --workload c4 --no-batched > $O/bench_c4_line.json 2> $O/bench_c4.err
+timeout 900 python bench.py --full --gpus 1 --dist --workload c4 --steps 5 --warmup 2 > $O/bench_dist_c4_line.json 2> $O/bench_dist_c4.err
 # (3) tests
 timeout 1500 python -m pytest tests -m gpu -q 2>&1 | tail -8 > $O/pytest_gpu.txt
 # (4) stall attribution of the dominant kernel

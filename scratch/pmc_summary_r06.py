@@ -22,7 +22,7 @@ def find(d, pat):
 
 lines = []
 rows = list(csv.DictReader(open(find(src + '/trace', '*kernel_stats.csv'))))
-lines.append("# rocprofv3 --kernel-trace --stats --output-format csv -- python3 bench.py --steps 5 --warmup 2 --no-cpu --no-batched --no-predict "
+lines.append("# rocprofv3 --kernel-trace --stats --output-format csv -- python3 bench.py --full --steps 5 --warmup 2 --no-cpu --no-batched --no-predict "
              "--no-gp-api   (C3: Matern52, N=8192, d=3; every step computes and returns alpha)")
 lines.append("%-44s %7s %14s %12s %10s %10s %7s" % ("kernel", "calls", "total_ns", "avg_ns", "min_ns", "max_ns", "%"))
 for r in rows:
@@ -42,7 +42,7 @@ avg_us = sum(bigd) / len(bigd) * 1e-3
 tr = {"round": rnd, "kernel": "gemm_nt_kernel<64,64>",
       "launch_filter": "main-stream queue, Grid_Size_X >= %d threads (the >= 1 GFLOP trailing updates of the flag schedule)" % MIN_GRID,
       "dispatches": len(bigd), "avg_launch_us": avg_us, "trace_file": "profiles/r%02d_bench_c3_N8192_rocprof_summary.txt" % rnd,
-      "traced_command": "python3 bench.py --steps 5 --warmup 2 --no-cpu --no-batched --no-predict --no-gp-api --ctx-opt tail_wait=0 "
+      "traced_command": "python3 bench.py --full --steps 5 --warmup 2 --no-cpu --no-batched --no-predict --no-gp-api --ctx-opt tail_wait=0 "
                         "(scratch/prof_r06.sh): the timed schedule with the main stream's wait for the next panel in a kernel of its own -- by default "
                         "the update's last workgroup waits (tail_wait), and a trace would count that wait, 20-50 us in the launches of the transition "
                         "to the chain-bound end, as the GEMM's duration; bench.py's own instrumented steps do the same (the library drops the tail "
@@ -75,7 +75,7 @@ def agg(path):
 
 
 lines.append("\n# SQ counter pass over the bench command (event schedule under counter collection): rocprofv3 --kernel-trace --pmc "
-             "SQ_VALU_MFMA_BUSY_CYCLES ... -- python3 bench.py --steps 2 --warmup 1 ...")
+             "SQ_VALU_MFMA_BUSY_CYCLES ... -- python3 bench.py --full --steps 2 --warmup 1 ...")
 f = find(src + '/pmc_sq', '*counter_collection.csv')
 if f:
     acc, cnt = agg(f)

@@ -18,7 +18,7 @@ for P in "$P1" "$P2" "$P3" "$P4" "$P5"; do
   for m in 7168 4096; do
     timeout 300 rocprofv3 --kernel-trace --pmc $P --output-format csv -d $O/one_m${m}_p$i -o t -- python3 $R/scratch/gemm_one.py $m 384 > $O/one_m${m}_p$i.log 2>&1
   done
-  timeout 600 rocprofv3 --kernel-trace --pmc $P --output-format csv -d $O/bench_p$i -o t -- python3 $R/bench.py --steps 2 --warmup 1 --no-cpu --no-batched --no-predict --no-gp-api > $O/bench_p$i.log 2>&1
+  timeout 600 rocprofv3 --kernel-trace --pmc $P --output-format csv -d $O/bench_p$i -o t -- python3 $R/bench.py --full --steps 2 --warmup 1 --no-cpu --no-batched --no-predict --no-gp-api > $O/bench_p$i.log 2>&1
 done
 python3 $R/scratch/r06_gemm_stalls.py $O > $O/summary.txt 2>&1
 find $O -name "*_kernel_trace.csv" -delete; find $O -name "*agent_info.csv" -delete

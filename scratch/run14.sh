@@ -6,6 +6,6 @@ GPT_POTF2_LA=1 timeout 30 ./scratch/potf2_la_stamps > $O/la.txt 2>&1
 GPT_POTF2_LA=1 timeout 30 ./scratch/potf2_la_events > $O/la_ev.txt 2>&1
 GPT_POTF2_LA=0 timeout 30 ./scratch/potf2_la_events > $O/lock.txt 2>&1
 timeout 30 ./scratch/dpp_rate > $O/dpp_rate.txt 2>&1
-timeout 300 python bench.py --steps 20 --warmup 5 > $O/bench_c3.json 2> $O/bench_c3.err
+timeout 300 python bench.py --full --steps 20 --warmup 5 > $O/bench_c3.json 2> $O/bench_c3.err
 cat $O/pytest_full.txt $O/ab_lib.txt; tail -c 600 $O/bench_c3.json | head -c 300; python -c "
 import json; d=json.loads(open('$O/bench_c3.json').read().strip().splitlines()[-1]); print(d['value'], d['ms_per_step'], d['roofline']['frac'], d.get('methodology'))"

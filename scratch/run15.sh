@@ -2,7 +2,7 @@ cd $GRAFT_REPO_ROOT
 O=gpurun_out/multi; mkdir -p $O
 export GPT_BENCH_BACKEND=gloo GPT_BENCH_ONE_GPU=1 GPT_BENCH_WATCHDOG_S=400
 for n in 2 4; do
-  timeout 900 python bench.py --gpus $n --workload c2 --steps 3 --warmup 1 --no-probe --no-ref > $O/b$n.json 2> $O/b$n.err; echo "rc $?" >> $O/b$n.err
+  timeout 900 python bench.py --full --gpus $n --workload c2 --steps 3 --warmup 1 --no-probe --no-ref > $O/b$n.json 2> $O/b$n.err; echo "rc $?" >> $O/b$n.err
   python - <<PY
 import json
 try:

@@ -238,14 +238,14 @@ def test_gaussian_process_partitioned_update_and_map_two_ranks(oracle):
 
 
 def test_bench_partitioned_line_is_complete_two_ranks():
-    """bench.py's N>1 branch end to end -- two gloo ranks sharing cuda:0 (test hook GPT_BENCH_BACKEND), the C2 workload:
+    """bench.py --full's N>1 branch end to end -- two gloo ranks sharing cuda:0 (test hook GPT_BENCH_BACKEND), the C2 workload:
     rank 0 prints ONE JSON line that carries `roofline` (HIP-event timing of the staircase updates), `cpu_baseline`
     (with the K-build / potrf split) and a passing `parity` gate; both ranks exit 0."""
     import json
     env = dict(os.environ, MASTER_ADDR="127.0.0.1", MASTER_PORT="29531", WORLD_SIZE="2", LOCAL_RANK="0",
                GPT_BENCH_BACKEND="gloo", GPT_BENCH_WATCHDOG_S="500")
     cmd = [sys.executable, os.path.join(ROOT, "bench.py"), "--gpus", "2", "--workload", "c2", "--steps", "3", "--warmup", "1",
-           "--schedule", "bcast+bcast", "--no-probe", "--no-ref"]
+           "--schedule", "bcast+bcast", "--full", "--no-probe", "--no-ref"]
     procs = [subprocess.Popen(cmd, env=dict(env, RANK=str(r)), stdout=subprocess.PIPE, stderr=subprocess.PIPE, text=True)
              for r in range(2)]
     outs = [p.communicate(timeout=600) for p in procs]
@@ -332,13 +332,54 @@ def test_bench_plain_python_gpus_2_self_launches():
     env = {k: v for k, v in os.environ.items() if k not in ("RANK", "LOCAL_RANK", "WORLD_SIZE", "MASTER_PORT")}
     env.update(GPT_BENCH_BACKEND="gloo", GPT_BENCH_ONE_GPU="1", GPT_BENCH_WATCHDOG_S="500")
     cmd = [sys.executable, os.path.join(ROOT, "bench.py"), "--gpus", "2", "--workload", "c2", "--steps", "3", "--warmup", "1",
-           "--schedule", "bcast+bcast", "--no-probe", "--no-ref"]
+           "--schedule", "bcast+bcast", "--full", "--no-probe", "--no-ref"]
     out = subprocess.run(cmd, env=env, capture_output=True, text=True, timeout=900)
     assert out.returncode == 0, out.stderr[-2000:]
     lines = [l for l in out.stdout.splitlines() if l.startswith("{")]
     assert len(lines) == 1
     line = json.loads(lines[0])
     assert line["n_gpus"] == 2 and line["config"]["N"] == 4096 and line["parity"]["ok"] and line["roofline"]["achieved"] > 0
+
+
+def _bench_line(args, timeout=900):
+    """One single-GPU bench.py run in a fresh process; returns its one JSON line."""
+    import json
+    out = subprocess.run([sys.executable, os.path.join(ROOT, "bench.py"), "--gpus", "1"] + args, capture_output=True, text=True,
+                         timeout=timeout)
+    assert out.returncode == 0, out.stderr[-2000:]
+    lines = [l for l in out.stdout.splitlines() if l.startswith("{")]
+    assert len(lines) == 1, out.stdout[-2000:]
+    return json.loads(lines[0])
+
+
+def test_bench_plain_single_gpu_line_is_the_headline_only(tmp_path):
+    """A plain `bench.py --gpus 1` run times the steps and nothing else: the headline fields, the timed region and the
+    dumped outputs of its last timed step -- no CPU baseline, no parity gate, no second context, no instrumented or
+    extra legs (those are --full's)."""
+    line = _bench_line(["--workload", "c2", "--steps", "3", "--warmup", "1", "--dump-outputs", str(tmp_path)])
+    assert line["metric"].endswith("N=4096") and line["unit"] == "GFLOP/s" and line["higher_is_better"] is True
+    assert line["dtype"] == "f64" and line["steps"] == 3 and line["warmup"] == 1 and line["n_gpus"] == 1
+    assert line["value"] > 0 and abs(line["ms_per_step"] - 1e3 * line["timed_region"]["seconds"] / 3) < 1e-9
+    assert line["live_contexts"] == 1 and line["methodology"]["version"] == 7
+    for key in ("cpu_baseline", "parity", "roofline", "batched", "lazy_alpha", "via_gp_api", "with_alpha", "predict",
+                "kbuild_ms", "kbuild_standalone"):
+        assert key not in line, key
+    assert float(np.load(str(tmp_path / "ll_data.npy"))) == line["ll_data"]
+    assert float(np.load(str(tmp_path / "logdet_half.npy"))) == line["logdet_half"]
+    alpha = np.load(str(tmp_path / "alpha.npy"))
+    assert alpha.shape == (4096,) and np.isfinite(alpha).all()
+
+
+def test_bench_full_single_gpu_line_is_complete():
+    """`bench.py --gpus 1 --full` still runs every leg beside the headline: CPU baseline with a passing parity gate,
+    the roofline of the instrumented steps, the throughput, plugin-API, predict and K-build legs."""
+    line = _bench_line(["--workload", "c2", "--steps", "3", "--warmup", "1", "--full"])
+    assert line["parity"]["ok"] and line["cpu_baseline"]["value"] > 0 and line["cpu_baseline"]["t_potrf_cpu_s"] > 0
+    assert line["roofline"]["achieved"] > 0 and line["roofline"]["sampled_steps"] == 8
+    assert line["live_contexts"] == 2 and line["batched"]["lml_evals_per_s"] > 0
+    assert line["lazy_alpha"]["ms_per_step"] > 0 and line["via_gp_api"]["ms_per_step"] > 0 and line["with_alpha"]["ms_per_step"] > 0
+    assert set(line["predict"]) >= {"M64_std", "M4096_std", "M4096_cov"} and line["kbuild_standalone"]["ms"] > 0
+    assert line["methodology"]["ms_per_step_instrumented"] > 0
 
 
 def _run_fresh(code, env_extra=None, timeout=900):
