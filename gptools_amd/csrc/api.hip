@@ -148,8 +148,7 @@ struct gpt_ctx {
     int64_t defer_pad = 1;             // option "defer_pad": 0 keeps the pad leaf on the panel stream (A/B)
     bool defer_pad_leaf = false;       // in: set by factor_and_ll around potrf_run
     bool pad_leaf_deferred = false;    // out: the pad leaf went to the main stream (the reduction must follow it there)
-    int pad_upd_n = 0;                 // leaves whose update of the pad block was held back, by first column
-    int64_t pad_upd_lc[8] = {0};
+    std::vector<int64_t> pad_upd_lc;   // leaves whose update of the pad block was held back, by first column
     // (all three are always built for the whole padded order, floor(NP / width) blocks, whatever extent the caller needs:
     // gpt_ll_grad and the solves ask for different extents at N = 512 k - 128, and a valid flag says nothing about how far)
     unsigned alpha_counter = 0;        // value of the step counter of the wide back-substitution (d_edge[40], only ever raised)

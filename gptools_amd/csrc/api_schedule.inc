@@ -361,9 +361,10 @@ static int panel_ext(gpt_ctx *c, hipStream_t st, double *A, int64_t lda, int64_t
         }
         if (lc == c0 && wait_ev) GPT_HIP_CHECK(hipStreamWaitEvent(st, wait_ev, 0));
         int64_t cend_p = cend;                       // this stream's share of the leaf's update: columns [r1, cend_p)
-        if (defer_pad && cend == n && c->pad_upd_n < 8) {
-            // the leaf's update of the pad block (the last 128 columns) is held back for the main stream
-            c->pad_upd_lc[c->pad_upd_n++] = lc;
+        if (defer_pad && cend == n) {
+            // the leaf's update of the pad block (the last 128 columns) is held back for the main stream (all of them: a leaf
+            // that applied its own here would run ahead of the held-back ones -- another order than defer_pad = 0)
+            c->pad_upd_lc.push_back(lc);
             cend_p = n - 128;
             if (cend_p <= r1 && first_ev) {
                 GPT_HIP_CHECK(hipEventRecord(first_ev, st));
@@ -389,7 +390,7 @@ static int panel_ext(gpt_ctx *c, hipStream_t st, double *A, int64_t lda, int64_t
     return GPT_OK;
 }
 
-static int enqueue_early_block_inverses(gpt_ctx *c, hipStream_t S, int64_t cols_final);      // api_solve.inc
+static int enqueue_early_block_inverses(gpt_ctx *c, hipStream_t S, int64_t cols, int64_t cols_final);      // api_solve.inc
 static int potrf_enqueue(gpt_ctx *c, int64_t n, double *A, int64_t lda, double *invd, int32_t *info)
 {
     if (n % 128) {
@@ -401,7 +402,7 @@ static int potrf_enqueue(gpt_ctx *c, int64_t n, double *A, int64_t lda, double *
     hipStream_t S = c->stream, P = c->panel_stream;
     const bool la = c->lookahead && nblk > 1;
     c->pad_leaf_deferred = false;
-    c->pad_upd_n = 0;
+    c->pad_upd_lc.clear();
     if (!la || c->inner != 0) c->defer_pad_leaf = false;        // (the right-looking look-ahead panels only)
     hipEvent_t head = c->head_event;
     c->head_event = nullptr;
@@ -463,6 +464,7 @@ static int potrf_enqueue(gpt_ctx *c, int64_t n, double *A, int64_t lda, double *
     const double rate_s = 46e12, rate_h = 1e11 * (double)c->helper_tf * (double)c->helper_cus / 24.0;
     hipEvent_t e_cu_prev = nullptr, e_help_prev = nullptr, e_rest_prev = nullptr;
     int64_t c0 = 0, s_prev = 0;
+    int64_t awaited = 0;          // end column of the last panel the main stream has waited for (eager alpha's early block inverses)
     // Update-bound head (option early_rows): while more than early_rows rows remain, the trailing updates run on a
     // stream that leaves only a few CUs to the panel stream (the diagonal-block kernel needs ONE free CU; the fused
     // diagonal-block + TRSM kernel of the chain-bound end needs up to 33).  One event hands over between the two.
@@ -578,6 +580,7 @@ static int potrf_enqueue(gpt_ctx *c, int64_t n, double *A, int64_t lda, double *
             } else {
                 GPT_HIP_CHECK(hipStreamWaitEvent(S, e_panel, 0));
             }
+            awaited = c0 + w;        // (panel_awaited: the previous panel's last launch on S waited for it at its end)
             // Tail wait: the last launch of this panel on the main stream ends only when the NEXT panel's flag is up, so the
             // next panel's launch follows it without a wait kernel in between (the flag's value is fixed here, one panel early).
             EdgeSig tail;
@@ -712,10 +715,17 @@ static int potrf_enqueue(gpt_ctx *c, int64_t n, double *A, int64_t lda, double *
     }
     if (pend.on) GPT_TRY(launch_rest(pend));
     c->pad_now = 0;
-    // Eager alpha: the inverses of the 512 x 512 diagonal blocks that are FINAL when the main stream has issued its last update
-    // -- everything left of the last panel -- are built now, on the main stream, which has nothing else to do while the panel
-    // stream factors the last panel (api_solve.inc; the one block that is not final yet follows behind the factorisation).
-    if (c->want_early_binv && A == c->dA && invd == c->d_invd && widths.size() >= 2) GPT_TRY(enqueue_early_block_inverses(c, S0, n - widths.back()));
+    // Eager alpha: the inverses of the 512 x 512 diagonal blocks left of the last panel are built now, on the main stream, which has
+    // nothing else to do while the panel stream factors the last panel (api_solve.inc; the blocks right of them follow behind the
+    // factorisation) -- as far as they are FINAL on S0, i.e. left of the last panel S0 has WAITED for.  That is usually the
+    // panel in front of the last one, but a panel whose update reaches no column (c0 + w + EXT >= n: the one in front of a
+    // 128-wide last panel) is never waited for, and reading its columns would race the panel stream (ADVICE r6).
+    // (on the early stream, S0 has seen its waits only if the loop switched back to S0)
+    // The last helper slice (e_help_prev, joined below) writes nothing left of `awaited` by then: every column there belongs to
+    // a panel S has waited for, and a panel is factored only behind every update of its columns, the helper's included (S waits
+    // for a helper slice before its next urgent update touches the slice's columns, and the panel stream waits for that update).
+    if (c->want_early_binv && A == c->dA && invd == c->d_invd && widths.size() >= 2)
+        GPT_TRY(enqueue_early_block_inverses(c, S0, n - widths.back(), S_cur == S0 ? awaited : 0));
     if (c->pad_leaf_deferred) {
         // The pad leaf (gpt_ctx defer_pad_leaf): behind the last real leaf, on the main stream -- the held-back rank-128 updates of
         // the pad block in leaf order (the order the panel stream would have applied them in: same bits), then its pivot block.
@@ -724,8 +734,7 @@ static int potrf_enqueue(gpt_ctx *c, int64_t n, double *A, int64_t lda, double *
         GPT_HIP_CHECK(hipEventRecord(e_real, P));
         GPT_HIP_CHECK(hipStreamWaitEvent(S0, e_real, 0));
         const int64_t pc = n - 128;
-        for (int i = 0; i < c->pad_upd_n; i++) {
-            const int64_t lc = c->pad_upd_lc[i];
+        for (const int64_t lc : c->pad_upd_lc) {
             GPT_TRY(gemm_nt(c, S0, 128, 128, 128, -1.0, A + pc * lda + lc, lda, A + pc * lda + lc, lda, 1.0, A + pc * lda + pc, lda, 1));
         }
         GPT_TRY(launch_potf2_diag(S0, A + pc * lda + pc, lda, invd + (pc / 128) * GPT_WS_BLOCK, info, pc));

@@ -101,16 +101,21 @@ static int ensure_block_inverses(gpt_ctx *c, int64_t nb, int64_t nfull, double *
 }
 
 // Eager alpha (option eager_alpha), called by potrf_enqueue when the main stream has issued its last trailing update: the columns
-// [0, cols_final) of the factor are final there (the update waited for the second-to-last panel), the panel stream still has the
-// last panel to factor (~70-100 us at N = 8192) and the main stream is idle: the inverses of the whole 512 x 512 diagonal blocks
-// inside those columns are built NOW, on the main stream (one trinv512 launch, ~55 us), instead of behind the factorisation,
-// where the launch was the first 59 us of alpha's critical path; the blocks right of cols_final follow there (one block at
-// N = 8192: 39 us).  c->binv_early says how many were done here, e_binv_early orders other streams behind them.
-static int enqueue_early_block_inverses(gpt_ctx *c, hipStream_t S, int64_t cols_final)
+// [0, cols_final) of the factor are final there (the main stream has waited for the panel that ends there), the panel stream still
+// has the last panel(s) to factor (~70-100 us at N = 8192) and the main stream is idle: the inverses of the whole 512 x 512 diagonal
+// blocks left of the last panel (column `cols`) are built NOW, on the main stream (one trinv512 launch, ~55 us), instead of behind
+// the factorisation, where the launch was the first 59 us of alpha's critical path; the blocks right of them follow there (one
+// block at N = 8192: 39 us).  Only as many as lie inside [0, cols_final): usually all of them (cols_final == cols), fewer when the
+// panel in front of a 128-wide last one is still being factored.  c->binv_early says how many were done here, e_binv_early orders
+// other streams behind them.
+static int enqueue_early_block_inverses(gpt_ctx *c, hipStream_t S, int64_t cols, int64_t cols_final)
 {
-    const int64_t nb = GPT_BINV_NB, nall = (c->NP / nb) * nb, b = cols_final / nb;
+    const int64_t nb = GPT_BINV_NB, nall = (c->NP / nb) * nb;
+    int64_t b = cols / nb;
     c->binv_early = 0;
     if (c->binv_launches || nall < 2 * nb || b <= 0 || b >= nall / nb) return GPT_OK;
+    if (b * nb > cols_final) b = cols_final / nb;
+    if (b <= 0) return GPT_OK;
     double *W, *Us = nullptr;
     GPT_TRY(ensure(c, SLOT_BINV, (size_t)nall * nb * sizeof(double), (void **)&W));
     GPT_TRY(ensure(c, SLOT_BINVU, (size_t)nall * nb * sizeof(double), (void **)&Us));

@@ -920,11 +920,14 @@ def test_schedule_options_agree_with_default(ctx, oracle):
                 # 128-row consumer workgroups everywhere / 64-row ones everywhere / where the default has 32-row ones, 32-row ones
                 # everywhere, 16-row ones, a mix; the unfused leaf (diagonal-block kernel + panel TRSM)
                 {"fuse_rows64": 0}, {"fuse_rows64": 8192}, {"fuse_rows32": 0}, {"fuse_rows32": 8192}, {"fuse_rows16": 8192},
-                {"fuse_rows32": 3000, "fuse_rows16": 1000, "fuse_rows64": 5000}, {"fuse_trsm": 0}, {"merge_urgent": 0})
+                {"fuse_rows32": 3000, "fuse_rows16": 1000, "fuse_rows64": 5000}, {"fuse_trsm": 0}, {"merge_urgent": 0},
+                # the schedule bench.py times its roofline with (profile_gemm drops the tail wait), on flag and on event edges
+                {"tail_wait": 0}, {"tail_wait": 0, "edge_flags": 0})
     defaults = {"nb_outer": 0, "inner": 0, "defer_rows": 0, "purg_rows": 6144, "nb_early": 0, "nb_switch_rows": 4608,
-                "ramp": 0, "edge_flags": 1, "fuse_rows64": 2048, "fuse_rows32": 2048, "fuse_rows16": 0, "fuse_trsm": 8192, "merge_urgent": 1}
-    # (bit-identical to the default schedule by construction: same sums in the same order)
-    exact = ("fuse_rows64", "fuse_rows32", "fuse_rows16", "merge_urgent")
+                "ramp": 0, "edge_flags": 1, "fuse_rows64": 2048, "fuse_rows32": 2048, "fuse_rows16": 0, "fuse_trsm": 8192, "merge_urgent": 1,
+                "tail_wait": 1}
+    # (bit-identical to the default schedule by construction: same sums in the same order; the tail wait moves a wait, not a sum)
+    exact = ("fuse_rows64", "fuse_rows32", "fuse_rows16", "merge_urgent", "tail_wait")
     try:
         for v in variants:
             for k_, d_ in defaults.items():
@@ -937,9 +940,18 @@ def test_schedule_options_agree_with_default(ctx, oracle):
                 assert abs(got[1] - base[1]) <= 1e-12 * abs(base[1]), v
                 if all(k_ in exact for k_ in v):
                     assert got == base, v
+        for k_, d_ in defaults.items():
+            ctx.set_option(k_, d_)
+        # the timed evaluation of bench.py's roofline: every large main-stream launch carries timing events
+        ctx.gemm_profile_read()
+        ctx.set_option("profile_gemm", 1)
+        got = ctx.fit(1, p, 0.0, y, err, 1e2 * EPS)
+        assert got == base
+        assert ctx.gemm_profile_read()[2] > 0          # (the launches were timed)
     finally:
         for k_, d_ in defaults.items():
             ctx.set_option(k_, d_)
+        ctx.set_option("profile_gemm", 0)
     # options that were removed with the code behind them (round 6) are refused, not ignored
     for gone in ("fuse_upd", "pair_rows", "leaf256"):
         with pytest.raises(Exception):
@@ -2136,6 +2148,214 @@ def test_eager_alpha_pad_leaf_beside_the_substitution(oracle, N):
             ll = c.fit(KID["se"], p, 0.0, y, err, 1e2 * EPS)
             grads.append((ll, c.ll_grad([0, 0, 0], [0, 1, 2])))
         assert grads[0][0] == grads[1][0] and np.array_equal(grads[0][1], grads[1][1])
+    finally:
+        c.close()
+
+
+# ---------------------------------------------------------------- eager alpha by panel geometry -------
+# The panel geometry of the look-ahead factorisation at the default schedule options (ramp 0, nb_early 0, inner 0), mirrored from
+# gptools_amd/csrc/api_schedule.inc (potrf_enqueue) and api_solve.inc (enqueue_early_block_inverses): the schedule's edge cases
+# live at particular geometries, not at particular sizes, so the cases below are chosen by the class they reach, and the test
+# asserts that class through the mirror before it touches the GPU.
+PANEL_EXT = 128          # GPT_PANEL_EXT (api_schedule.inc)
+BINV_NB = 512            # GPT_BINV_NB (api_grad.inc): the early block inverses are whole 512 x 512 diagonal blocks
+
+
+def sched_outer_width(NP, nb_outer=0):
+    """outer_width(): the panel width, by size unless set."""
+    if nb_outer > 0:
+        return nb_outer
+    return 256 if NP <= 5120 else 384 if NP <= 12288 else 640
+
+
+def sched_geometry(N, nb_outer=0):
+    """What potrf_enqueue does at the padded order NP of N points: the panel widths (the widths loop), the end column of the last
+    panel the main stream waits for (it does so only for a panel whose update reaches a column, u0 = c0 + w + EXT < n), how many
+    early block inverses an eager evaluation builds -- `early`: the whole 512-blocks left of the last panel, unless all of them
+    (enqueue_early_block_inverses), and no further than that wait -- and how many the schedule built before it capped them there
+    (`early_unawaited`), and, where factor_and_ll sets defer_pad_leaf, how many real leaves hold back an update of the pad block
+    (panel_ext: cend == n)."""
+    NP = -(-(N + 1) // 128) * 128
+    nbo = sched_outer_width(NP, nb_outer)
+    widths, c0 = [], 0
+    while c0 < NP:
+        widths.append(min(nbo, NP - c0))
+        c0 += widths[-1]
+    awaited, c0 = 0, 0
+    for w in widths:
+        if c0 + w + PANEL_EXT < NP:
+            awaited = c0 + w
+        c0 += w
+
+    nblk, b = NP // BINV_NB, (NP - widths[-1]) // BINV_NB
+    early_unawaited = b if len(widths) >= 2 and nblk >= 2 and 0 < b < nblk else 0
+    early = min(early_unawaited, awaited // BINV_NB)
+    defer_pad = N % 512 == 0 and N >= 1024 and NP == N + 128 and len(widths) >= 2
+    pad_leaves, c0 = 0, 0
+    for w in widths:
+        if min(c0 + w + PANEL_EXT, NP) == NP:
+            pad_leaves += sum(1 for lc in range(c0, c0 + w, 128) if lc + 128 < NP)
+        c0 += w
+    return dict(NP=NP, widths=widths, awaited=awaited, early=early, early_unawaited=early_unawaited,
+                defer_pad=defer_pad, pad_leaves=pad_leaves if defer_pad else 0, helper=NP > 12288)
+
+
+def sched_class(geo):
+    """race: early block inverses over columns of a panel the main stream has not waited for (before the fix); pad_cap: more
+    real leaves reach the pad block than the eight the schedule used to hold back; control: neither."""
+    assert geo["early"] * BINV_NB <= geo["awaited"] and geo["early"] <= geo["early_unawaited"]
+    if geo["early_unawaited"] != geo["early"]:
+        return "race"
+    return "pad_cap" if geo["pad_leaves"] > 8 else "control"
+
+
+GEOMETRY_CASES = [
+    # (N, nb_outer, class, what else the case is meant to hit)
+    pytest.param(2000, 640, "race", lambda g_: g_["widths"][-1] == 128 and g_["NP"] % 512 == 0, id="race-2000-640"),
+    pytest.param(3500, 1152, "race", lambda g_: g_["widths"][-1] == 128, id="race-3500-1152"),
+    pytest.param(1000, 896, "race", lambda g_: g_["widths"] == [896, 128] and g_["awaited"] == 0, id="race-1000-896-no-update"),
+    pytest.param(14720, 0, "race", lambda g_: g_["helper"] and g_["widths"][0] == 640, id="race-14720-helper"),
+    pytest.param(32700, 0, "race", lambda g_: g_["NP"] == 32768, id="race-32700"),
+    pytest.param(2560, 1280, "pad_cap", lambda g_: g_["pad_leaves"] == 10, id="padcap-2560-1280"),
+    pytest.param(4608, 1152, "pad_cap", lambda g_: g_["pad_leaves"] == 9, id="padcap-4608-1152"),
+    pytest.param(2100, 640, "control", lambda g_: g_["widths"][-1] == 256, id="control-2100-640"),
+    pytest.param(2560, 640, "control", lambda g_: g_["widths"][-1] == 128 and g_["defer_pad"], id="control-2560-640-pad-alone"),
+    pytest.param(14848, 0, "control", lambda g_: g_["helper"] and g_["defer_pad"], id="control-14848"),
+    pytest.param(4000, 768, "control", lambda g_: g_["NP"] % 768 == 256, id="control-4000-768"),
+    pytest.param(3000, 0, "control", lambda g_: not g_["defer_pad"], id="control-3000"),
+    pytest.param(4608, 0, "control", lambda g_: g_["defer_pad"] and g_["widths"][-1] == 128, id="control-4608"),
+]
+
+
+def test_schedule_geometry_mirror_at_the_benchmark_sizes():
+    """The mirror itself: the early block inverses change only where the race was -- at the benchmark's sizes (C2-C5, with the
+    default widths and bench.py --nb's usual values) an eager evaluation keeps its schedule; and the classes the table relies on
+    are where the mirror says they are (every 2560 rows with the default widths above 12288)."""
+    for N in (4096, 8192, 16384, 32768):
+        for nb in (0, 256, 384, 512, 640):
+            geo = sched_geometry(N, nb)
+            assert geo["early"] == geo["early_unawaited"] and geo["pad_leaves"] <= 8, (N, nb, geo)
+    races = [N for N in range(12800, 33000, 128) if sched_class(sched_geometry(N)) == "race"]
+    assert races == list(range(14720, 32768, 2560)), races
+
+
+def _lbits(L):
+    """A digest of a factor (get_L of N = 32700 is 8.5 GB: one at a time)."""
+    import hashlib
+    return hashlib.sha1(np.ascontiguousarray(L).view(np.uint8)).hexdigest()
+
+
+def _eager_case_inputs(N, d=2):
+    X, n, y = c3_inputs(N, d)
+    rs = np.random.RandomState(N)
+    return X, n, y, np.array([1.0, 0.3, 0.3]), 0.05 * np.ones(N), rs.randn(N, 2), rs.rand(64, d), np.zeros((64, d), dtype=np.int32)
+
+
+@pytest.mark.parametrize("N,nb_outer,cls,pin", GEOMETRY_CASES)
+def test_eager_alpha_at_every_panel_geometry(oracle, N, nb_outer, cls, pin):
+    """ADVICE r6: an eager evaluation builds the inverses of the 512-wide diagonal blocks under the last panel, on the main stream;
+    they must cover only columns of panels the main stream has waited for -- not the second-to-last panel in front of a 128-wide
+    last one, which nothing waits for -- and the pad block's held-back updates must be all of them, in leaf order.  At every class
+    of geometry (race / pad_cap / control, sched_geometry), on flag and on event edges (and at N = 14720 without the helper stream):
+    the eager fit's ll, L, alpha and the cho_solve and predict behind it are the plain route's bits; where the pad leaf moves to the
+    main stream (N % 512 == 0) defer_pad 0 and 1 agree bit for bit, the analytic gradient included; ll and alpha match the oracle
+    up to N = 14720 (8 s on 8 CPU cores; at N = 32700 the plain route is the reference)."""
+    geo = sched_geometry(N, nb_outer)
+    assert sched_class(geo) == cls and pin(geo), geo
+    from gptools_amd import _lib
+    X, n, y, p, err, B, Xs, ns = _eager_case_inputs(N)
+
+    def route(c, eager):
+        c.set_option("eager_alpha", eager)
+        ll = c.fit(KID["m52"], p, 0.0, y, err, 1e2 * EPS)
+        out = {"ll": ll, "alpha": c.get_alpha(N), "cho_solve": c.cho_solve(B.copy())}
+        out["mean"], out["std"], _ = c.predict(Xs, ns, 1)
+        out["L"] = _lbits(c.get_L(N))
+        return out
+
+    def same(got, want, what):
+        for k_, v_ in want.items():
+            assert np.array_equal(np.asarray(got[k_]), np.asarray(v_)), "%s: %s differs (N = %d, nb_outer = %d, %s)" % (
+                what, k_, N, nb_outer, cls)
+
+    c = _lib.Context(0)
+    try:
+        c.set_data(X, n)
+        c.set_option("nb_outer", nb_outer)
+        first = None
+        for ef in (1, 0):
+            c.set_option("edge_flags", ef)
+            for helper_tf in ((None, 0) if N == 14720 else (None,)):
+                if helper_tf is not None:
+                    c.set_option("helper_tf", helper_tf)
+                plain = route(c, 0)
+                eager = route(c, 1)
+                same(eager, plain, "eager against plain, edge_flags %d%s" % (ef, "" if helper_tf is None else ", helper_tf 0"))
+                if geo["defer_pad"]:
+                    c.set_option("defer_pad", 0)
+                    same(route(c, 1), eager, "eager, defer_pad 0 against 1, edge_flags %d" % ef)
+                    c.set_option("defer_pad", 1)
+                if helper_tf is not None:
+                    c.set_option("helper_tf", 45)          # (the default, api.hip)
+                first = first or eager
+        c.set_option("edge_flags", 1)
+        if geo["defer_pad"]:
+            c.set_data(X, np.zeros_like(n))
+            grads = []
+            for mode in (0, 1):
+                c.set_option("defer_pad", mode)
+                ll = c.fit(KID["se"], p, 0.0, y, err, 1e2 * EPS)
+                grads.append((ll, c.ll_grad([0, 0, 0], [0, 1, 2])))
+            assert grads[0][0] == grads[1][0] and np.array_equal(grads[0][1], grads[1][1])
+    finally:
+        c.close()
+    if N <= 14720:
+        ref = oracle.fit("m52", p, X, n, y, err, chol="scipy")
+        assert abs(first["ll"][0] - ref["ll_data"]) <= 1e-9 * abs(ref["ll_data"])
+        np.testing.assert_allclose(first["alpha"], ref["alpha"], rtol=0, atol=2e-7 * np.abs(ref["alpha"]).max())
+
+
+def test_eager_alpha_race_geometries_under_stream_jitter():
+    """The race and pad_cap geometries under GPT_JITTER (a delay kernel of up to 1 ms in front of every dense launch, ~0.25 ms on
+    average): the second-to-last panel's leaves -- two delayed launches each -- then fall milliseconds behind the main stream's
+    last update, the window in which the early block inverses used to read them.  Eager evaluations in a fresh process, three
+    each: alpha and a cho_solve must hash to the undisturbed plain route's bits."""
+    import hashlib
+    import subprocess
+    cases = [tuple(c_.values[:2]) for c_ in GEOMETRY_CASES if c_.values[2] in ("race", "pad_cap") and c_.values[0] < 20000]
+    code = (
+        "import sys, hashlib, numpy as np\n"
+        "sys.path.insert(0, %r); sys.path.insert(0, %r)\n"
+        "from gptools_amd import _lib\n"
+        "from test_gpu_parity import _eager_case_inputs\n"
+        "c = _lib.Context(0)\n"
+        "c.set_option('eager_alpha', 1)\n"
+        "for N, nb in %r:\n"
+        "    X, n, y, p, err, B, Xs, ns = _eager_case_inputs(N)\n"
+        "    c.set_data(X, n)\n"
+        "    c.set_option('nb_outer', nb)\n"
+        "    for rep in range(3):\n"
+        "        ll, ld = c.fit(1, p, 0.0, y, err, 1e2 * sys.float_info.epsilon)\n"
+        "        print('EAGER', N, nb, repr(ll), repr(ld), hashlib.sha1(c.get_alpha(N).tobytes()).hexdigest(),\n"
+        "              hashlib.sha1(c.cho_solve(B.copy()).tobytes()).hexdigest(), flush=True)\n") % (ROOT, os.path.join(ROOT, "tests"), cases)
+    out = subprocess.run([sys.executable, "-c", code], env=dict(os.environ, GPT_JITTER="1000"), stdout=subprocess.PIPE,
+                         stderr=subprocess.PIPE, text=True, timeout=900)
+    assert out.returncode == 0, out.stderr[-2000:]
+    got = [l.split()[1:] for l in out.stdout.splitlines() if l.startswith("EAGER")]
+    assert len(got) == 3 * len(cases)
+    from gptools_amd import _lib
+    c = _lib.Context(0)
+    try:
+        for N, nb in cases:
+            X, n, y, p, err, B, Xs, ns = _eager_case_inputs(N)
+            c.set_data(X, n)
+            c.set_option("nb_outer", nb)
+            ll, ld = c.fit(KID["m52"], p, 0.0, y, err, 1e2 * EPS)
+            want = [repr(ll), repr(ld), hashlib.sha1(c.get_alpha(N).tobytes()).hexdigest(),
+                    hashlib.sha1(c.cho_solve(B.copy()).tobytes()).hexdigest()]
+            for g_ in got:
+                if (int(g_[0]), int(g_[1])) == (N, nb):
+                    assert g_[2:] == want, ((N, nb), g_, want)
     finally:
         c.close()
 
