@@ -1,6 +1,7 @@
 // api.hip -- C ABI (include/gpt_hip.h) and host-side orchestration for libgpt_hip.so.
 // One translation unit, kept in parts by entry-point family (api_*.inc, included at the end of this file in dependency order):
-// this file holds the error channel and struct gpt_ctx.
+// this file holds the error channel and struct gpt_ctx.  What belongs to ONE factorisation (not to the context) travels as
+// arguments: PotrfRequest / PotrfResult / PanelShared, api_schedule.inc.
 //
 // Host logic restated here (not kernels): the blocked right-looking Cholesky with a recursive
 // panel and one-panel look-ahead on a second, high-priority HIP stream; the padded / augmented
@@ -54,33 +55,19 @@ struct gpt_ctx {
     bool own_stream = false;
     hipStream_t panel_stream = nullptr;
     hipStream_t helper_stream = nullptr;   // CU-masked to part of the reserved CUs (own streams only)
-    hipStream_t late_panel_stream = nullptr;   // panel stream of the chain-bound end: masked to the reserved CUs only
-    int64_t late_rows = 0;                 // panels with at most this many rows left run on it (0 = off)
-    hipStream_t early_stream = nullptr;    // main stream of the update-bound head of a factorisation: fewer CUs reserved
-    int64_t early_rows = 0;                // panels with more than this many rows left run their updates there (0 = off)
     int64_t nb_early = 0, nb_switch_rows = 4608;   // see potrf_enqueue (panel widths)
-    int pad_now = 0;                       // (set per panel by potrf_enqueue: LDS pad of the main stream's updates right now)
-    int late_pad = 0;                      // > 0: LDS pad of the main stream's updates once at most late_pad_rows rows remain -- fewer of its
-    int64_t late_pad_rows = 4608;          //      workgroups per CU, so that the panel stream's chain kernels share the CUs with less contention
     unsigned *d_edge = nullptr;            // edge-flag words (EdgeSig, common.hpp): [0,1] "panel k final", [16,17] "urgent update k done"
-    EdgeSig first_wait;                    // ... handed by potrf_enqueue to the first leaf launch (panel_ext)
-    EdgeSig head_wait;                     // set by fit_terms: the first leaf of the next factorisation waits for this word (K-build head)
     unsigned edge_seq = 0;                 // value of the last edge raised (monotonic over the context's life)
-    int64_t merge_min_tiles = 512;         // ... while the merged launch has at least this many 64x64 tiles (>= 512: it needs an order table)
-    int64_t purg_rows_flags = 0;           // purg_rows while flag edges + merged launches are in use
     int64_t tail_wait = 1;                 // 1: the main stream's last launch of a panel awaits the NEXT panel's flag at its end (gemm.hip "tail wait"): no
                                            //    wait kernel between two trailing updates.  Round 4 measured it the same as 0 (4.459 / 4.471 ms at N = 8192); at
                                            //    round 6's schedule: C3 -2 ... -47 us in six same-process A/Bs (mean 19), C2 -11 ... -18 us -- on.  The gain sits in
                                            //    the launches that DO wait (1-6 GFLOP: only-large or only-small launches gain nothing); not while launches are timed.
     int64_t merge_urgent = 1;              // 1: with flag edges, urgent + rest of a panel are ONE launch (urgent tiles first, partial flag)
+                                           //    while the merged launch has at least GPT_MERGE_MIN_TILES 64x64 tiles
     int64_t edge_flags = 1;                // 1: those two edges of the look-ahead may be flag words instead of events (see EvalScope)
     bool flags_now = false;                // ... and ARE, in the evaluation in progress (set by EvalScope)
     int reserve_cus = 0;                   // CUs the main stream's mask leaves to the panel stream (0: unmasked)
-    int64_t head_wait_wgs = 33;            // first leaf: in-kernel wait for the K build's head while its launch has at most this many workgroups
-    bool defer_join = false;               // potrf_enqueue leaves the final panel -> main join to its caller (factor_and_ll)
-    hipStream_t tail_stream = nullptr;     // ... and reports the stream the factorisation ended on
     int64_t gemm_prio = -1;                // >= 0: wave priority of ALL GEMM main loops of this context
-    int64_t panel_prio = 2;                // wave priority (0..3) of the panel stream's GEMM main loops
     int64_t purg_rows = 6144;              // > 0: while more rows than this remain, the panel stream does the "urgent" update itself
                                            // (N=8192: 5.36 against 5.44 ms, bit-identical; no effect below ~7k rows or with the helper stream)
     int64_t defer_rows = 0;             // chain-bound end: with at most this many rows left, the main stream's "rest" update of
@@ -110,8 +97,7 @@ struct gpt_ctx {
                                        // measured: 0 / 25 / 35 / 50 -> 212 / 209 / 206 / 214 ms at N=32768, 30.8 / 30.6 / 30.2 / 32.0 at N=16384
     int ramp = 0;                      // first panels 128, 256, ... wide (see potrf_enqueue); measured slower, off
     int inner = 0;                     // look-ahead panel: 0 right-looking leaves, 1 left-looking (panel_ext_ll), 2 left-looking
-    int64_t inner_rows = 4608;         //   once at most inner_rows rows remain (the chain-bound end of the factorisation)
-    hipEvent_t head_event = nullptr;   // set by gpt_fit: the first nb_outer+128 columns of K_tot are built (panel 0 may start)
+                                       //   once at most GPT_INNER_ROWS rows remain (the chain-bound end of the factorisation)
     // resident training inputs
     int64_t N = 0;             // order of the factorised matrix (= Nx without T, = Ny with T)
     int64_t Nx = 0;            // resident points
@@ -141,14 +127,7 @@ struct gpt_ctx {
     int64_t binv_early = 0;            // this factorisation: the 512-wide inverses of the diagonal blocks [0, binv_early) were enqueued on the
                                        // main stream under the last panel (enqueue_early_block_inverses); e_binv_early follows them there
     hipEvent_t e_binv_early = nullptr;
-    bool want_early_binv = false;      // set by factor_and_ll around potrf_run for an eager evaluation
-    // Eager alpha with N a multiple of 512: the factor's last 128 columns hold only the augmented row and the padding.  alpha needs
-    // nothing of that leaf, so its pivot block (and the rank-128 updates that reach it) leave the panel stream: the substitution
-    // follows the last REAL leaf at once, the pad leaf and the reduction run beside it on the main stream (potrf_enqueue).
-    int64_t defer_pad = 1;             // option "defer_pad": 0 keeps the pad leaf on the panel stream (A/B)
-    bool defer_pad_leaf = false;       // in: set by factor_and_ll around potrf_run
-    bool pad_leaf_deferred = false;    // out: the pad leaf went to the main stream (the reduction must follow it there)
-    std::vector<int64_t> pad_upd_lc;   // leaves whose update of the pad block was held back, by first column
+    int64_t defer_pad = 1;             // option "defer_pad": 0 keeps the pad leaf of an eager evaluation on the panel stream (A/B; see PotrfRequest)
     // (all three are always built for the whole padded order, floor(NP / width) blocks, whatever extent the caller needs:
     // gpt_ll_grad and the solves ask for different extents at N = 512 k - 128, and a valid flag says nothing about how far)
     unsigned alpha_counter = 0;        // value of the step counter of the wide back-substitution (d_edge[40], only ever raised)

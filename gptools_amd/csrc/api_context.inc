@@ -41,26 +41,7 @@ extern "C" int gpt_ctx_create(int device_id, void *stream, gpt_ctx **out)
             // idle most of the time; a slice of every update runs there (potrf_enqueue).
             // NOTE: every extra stream of a context costs: with a FIFTH stream (main, panel, helper + two more) the
             // runtime maps two of them to one hardware queue and the whole factorisation ran 2x slower (5.5 -> 10.7 ms at
-            // N=8192) even with the extra streams unused.  The experimental streams below are therefore created only on
-            // request (environment), never by default.
-            if (getenv("GPT_LATE_STREAM")) {   // the reserved CUs as a stream of their own (see potrf_enqueue)
-                std::vector<uint32_t> lm((ncu + 31) / 32, 0u);
-                for (int i = 0; i < reserve; i++) lm[i / 32] |= (1u << (i % 32));
-                if (masked && hipExtStreamCreateWithCUMask(&c->late_panel_stream, (uint32_t)lm.size(), lm.data()) != hipSuccess) {
-                    (void)hipGetLastError();
-                    c->late_panel_stream = nullptr;
-                }
-            }
-            int reserve_early = 0;
-            if (const char *e = getenv("GPT_RESERVE_EARLY")) reserve_early = atoi(e);
-            if (masked && reserve_early > 0 && reserve_early < reserve) {
-                std::vector<uint32_t> em((ncu + 31) / 32, 0u);
-                for (int i = reserve_early; i < ncu; i++) em[i / 32] |= (1u << (i % 32));
-                if (hipExtStreamCreateWithCUMask(&c->early_stream, (uint32_t)em.size(), em.data()) != hipSuccess) {
-                    (void)hipGetLastError();
-                    c->early_stream = nullptr;
-                }
-            }
+            // N=8192) even with the extra streams unused: no further stream may be added to a context.
             if (masked && reserve >= 16) {
                 std::vector<uint32_t> hm((ncu + 31) / 32, 0u);
                 for (int i = 8; i < reserve; i++) hm[i / 32] |= (1u << (i % 32));
@@ -139,8 +120,6 @@ extern "C" int gpt_ctx_destroy(gpt_ctx *c)
     hipStreamDestroy(c->panel_stream);
     if (c->e_binv_early) hipEventDestroy(c->e_binv_early);
     if (c->helper_stream) hipStreamDestroy(c->helper_stream);
-    if (c->early_stream) hipStreamDestroy(c->early_stream);
-    if (c->late_panel_stream) hipStreamDestroy(c->late_panel_stream);
     if (c->own_stream) hipStreamDestroy(c->stream);
     delete c;
     return GPT_OK;
@@ -162,24 +141,15 @@ extern "C" int gpt_ctx_set_option(gpt_ctx *c, const char *key, int64_t value)
     else if (!strcmp(key, "gemm_pad")) c->gemm_pad = (int)value;
     else if (!strcmp(key, "dev_gemm_pad")) c->dev_gemm_pad = value;
     else if (!strcmp(key, "ramp")) c->ramp = value ? 1 : 0;
-    else if (!strcmp(key, "early_rows")) c->early_rows = value;
     else if (!strcmp(key, "defer_rows")) c->defer_rows = value;
-    else if (!strcmp(key, "late_rows")) c->late_rows = value;
     else if (!strcmp(key, "purg_rows")) c->purg_rows = value;
-    else if (!strcmp(key, "panel_prio")) c->panel_prio = value;
     else if (!strcmp(key, "edge_flags")) c->edge_flags = value;
-    else if (!strcmp(key, "head_wait_wgs")) c->head_wait_wgs = value;
     else if (!strcmp(key, "merge_urgent")) c->merge_urgent = value;
     else if (!strcmp(key, "tail_wait")) c->tail_wait = value;
-    else if (!strcmp(key, "purg_rows_flags")) c->purg_rows_flags = value;
-    else if (!strcmp(key, "merge_min_tiles")) c->merge_min_tiles = value < 512 ? 512 : value;
     else if (!strcmp(key, "gemm_prio")) c->gemm_prio = value;
-    else if (!strcmp(key, "late_pad")) c->late_pad = (int)value;
-    else if (!strcmp(key, "late_pad_rows")) c->late_pad_rows = value;
     else if (!strcmp(key, "nb_early")) c->nb_early = value;
     else if (!strcmp(key, "nb_switch_rows")) c->nb_switch_rows = value;
     else if (!strcmp(key, "inner")) c->inner = (int)value;
-    else if (!strcmp(key, "inner_rows")) c->inner_rows = value;
     else if (!strcmp(key, "helper_tf")) c->helper_tf = (int)value;
     else if (!strcmp(key, "helper_min_n")) c->helper_min_n = value;
     else if (!strcmp(key, "fuse_trsm")) c->fuse_trsm = value;

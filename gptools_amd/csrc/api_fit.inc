@@ -90,7 +90,9 @@ static int ensure_factor_storage(gpt_ctx *c, int64_t N)
 static int harvest_gemm_profile(gpt_ctx *c);
 static int alpha_to_host(gpt_ctx *c, hipStream_t on = nullptr);
 
-static int factor_and_ll(gpt_ctx *c, int64_t N, double *ll_data_out, double *logdet_half_out, bool padded = false)
+// `req`: what the caller knows about the K build in front of the factorisation (PotrfRequest::head_event / head_wait)
+static int factor_and_ll(gpt_ctx *c, int64_t N, double *ll_data_out, double *logdet_half_out, bool padded = false,
+                         PotrfRequest req = PotrfRequest())
 {
     hipStream_t st = c->stream;
     const int64_t NP = c->NP;
@@ -102,21 +104,15 @@ static int factor_and_ll(gpt_ctx *c, int64_t N, double *ll_data_out, double *log
     // The factorisation ends on the panel stream (its last leaf); the reduction over the diagonal and the augmented row
     // and the 24-byte copy follow it THERE -- handing back to the main stream first cost an event edge (~20 us of a 5 ms
     // evaluation) -- and the main stream is joined behind them, off the host's critical path.
-    c->defer_join = true;
-    c->tail_stream = nullptr;
+    req.defer_join = true;
     c->binv_early = 0;
-    c->want_early_binv = c->eager_alpha != 0 && !c->use_graph;
+    req.want_early_binv = c->eager_alpha != 0 && !c->use_graph;
     // (the eager substitution's fast path -- ensure_alpha: N a multiple of 512, at least 1024 -- reads nothing of the last leaf then)
-    c->defer_pad_leaf = c->want_early_binv && c->defer_pad && N % 512 == 0 && N >= 1024 && NP == N + 128;
-    int rc_f = potrf_run(c, NP, c->dA, NP, c->d_invd, c->d_info);
-    c->want_early_binv = false;
-    c->defer_pad_leaf = false;
-    const bool pad_on_main = c->pad_leaf_deferred;
-    c->pad_leaf_deferred = false;
-    c->defer_join = false;
-    GPT_TRY(rc_f);
-    hipStream_t tl = c->tail_stream ? c->tail_stream : st;
-    c->tail_stream = nullptr;
+    req.defer_pad_leaf = req.want_early_binv && c->defer_pad && N % 512 == 0 && N >= 1024 && NP == N + 128;
+    PotrfResult fac;
+    GPT_TRY(potrf_run(c, NP, c->dA, NP, c->d_invd, c->d_info, req, &fac));
+    const bool pad_on_main = fac.pad_leaf_deferred;
+    hipStream_t tl = fac.tail_stream ? fac.tail_stream : st;
     // (the three results go straight to pinned host memory, and the two timing events ride on the kernel's dispatch packet:
     // a copy kernel and two barrier packets less on the tail of every evaluation, ~15 us)
     // (only a STOP event: a start event on the packet holds the kernel back ~7 us like a barrier packet would)
@@ -393,7 +389,6 @@ static int fit_terms_once(gpt_ctx *c, const std::vector<KParams> &terms, double 
         GPT_TRY(launch_add_diag(st, c->dA, NP, N, c->d_erry, diag_add));
         GPT_TRY(launch_fill_pad(st, c->dA, NP, N, NP, c->d_y, 1e300));
         c->have_kernel = true;
-        c->head_event = nullptr;
         return factor_and_ll(c, N, ll_data_out, logdet_half_out, true);
     }
     // The columns the first panel touches are built first so that its pivot chain overlaps the rest of the build.
@@ -405,8 +400,8 @@ static int fit_terms_once(gpt_ctx *c, const std::vector<KParams> &terms, double 
     }
     const int64_t w0 = (c->nb_early > outer_width(c, NP)) ? c->nb_early : outer_width(c, NP);
     int64_t head = round_up((c->ramp ? 128 : w0) + GPT_PANEL_EXT, 256);   // what panel 0 touches
+    PotrfRequest req;                // (how panel 0 learns that the head is built: an event, or a flag word)
     hipEvent_t e_head = nullptr;
-    c->head_wait = EdgeSig();
     const bool head_flag = c->flags_now && c->edge_seq < 0xf0000000u;
     if (c->lookahead && !c->use_graph && head < N && (head_flag || (e_head = get_event(c, 0)) != nullptr)) {
         GPT_TRY(kbuild_terms(c, st, c->terms, 1, c->dX, c->dn, N, c->dX, c->dn, head, 1, 0, 0, c->d_erry, noise_var, diag_add,
@@ -414,14 +409,12 @@ static int fit_terms_once(gpt_ctx *c, const std::vector<KParams> &terms, double 
         if (head_flag) {
             // "the head columns are built" as a flag word raised from this stream (a one-thread kernel behind the build);
             // the first diagonal-block kernel of the panel stream polls it itself: no event record here, no event wait there
-            c->head_wait.word = c->d_edge + 48;
-            c->head_wait.value = ++c->edge_seq;
-            c->head_wait = with_err(c, c->head_wait);
+            req.head_wait = new_edge(c, 48);
             // (option "edge_test_stall", test aid: the flag is NOT raised, once -- the waiter must time out, the evaluation be
             // repeated on events and give the right numbers: tests/test_gpu_a_dist_processes.py.  An explicit option of the
             // context, not an environment variable: a stray variable must not be able to push a process off its flag edges)
             if (c->edge_test_stall) c->edge_test_stall = 0;
-            else GPT_TRY(launch_set_flag(st, c->head_wait.word, c->head_wait.value));
+            else GPT_TRY(launch_set_flag(st, req.head_wait.word, req.head_wait.value));
         } else {
             GPT_HIP_CHECK(hipEventRecord(e_head, st));
         }
@@ -433,8 +426,8 @@ static int fit_terms_once(gpt_ctx *c, const std::vector<KParams> &terms, double 
                              c->dA, NP));
     }
     c->have_kernel = true;
-    c->head_event = e_head;
-    return factor_and_ll(c, N, ll_data_out, logdet_half_out, true);
+    req.head_event = e_head;
+    return factor_and_ll(c, N, ll_data_out, logdet_half_out, true, req);
 }
 
 static int fit_matrix_once(gpt_ctx *c, const double *K_tot, int64_t N, const double *y, double *ll_data_out,

@@ -3,6 +3,7 @@
 // ------------------------------------------------------------------------------------------------
 // Dense drivers on device data
 // ------------------------------------------------------------------------------------------------
+#define GPT_PANEL_PRIO 2           // wave priority (0..3) of the panel stream's GEMM main loops
 static int gemm_nt(gpt_ctx *c, hipStream_t st, int64_t m, int64_t n, int64_t k, double alpha, const double *A,
                    int64_t lda, const double *B, int64_t ldb, double beta, double *C, int64_t ldc, int tri,
                    hipEvent_t done = nullptr, EdgeSig edge = EdgeSig(), EdgeSig wait = EdgeSig(), int64_t edge_cols = 0,
@@ -14,7 +15,7 @@ static int gemm_nt(gpt_ctx *c, hipStream_t st, int64_t m, int64_t n, int64_t k, 
     // (the roofline line of bench.py: the trailing updates on the MAIN stream only -- at large N the panel and helper
     // streams also launch >= 1 GFLOP updates, on the few CUs reserved for them and concurrently with these; summing their
     // durations with the main stream's would count the same wall time twice)
-    const bool on_main = (st == c->stream) || (c->early_stream && st == c->early_stream);
+    const bool on_main = st == c->stream;
     const bool prof = c->prof_gemm && flops >= 1.0e9 && on_main;
     gpt_ctx::GemmProf *gp = nullptr;
     if (prof) {
@@ -33,7 +34,7 @@ static int gemm_nt(gpt_ctx *c, hipStream_t st, int64_t m, int64_t n, int64_t k, 
         gp->bytes = 16.0 * elems + 8.0 * (double)k * (double)(m > n ? m : n);
     }
     // trailing updates on the main stream leave room on every CU for the panel stream (see gemm.hip)
-    const int lds_pad = (on_main && c->lookahead) ? (c->pad_now > 0 ? c->pad_now : c->gemm_pad) : (on_main ? (int)c->dev_gemm_pad : 0);
+    const int lds_pad = on_main ? (c->lookahead ? c->gemm_pad : (int)c->dev_gemm_pad) : 0;
     // `done` (a cross-stream edge) and the timing events ride on the dispatch packet itself where possible
     // (hipExtLaunchKernelGGL): a separate hipEventRecord is a barrier packet, ~6 us of command-processor time
     const bool ext = !c->use_graph && (c->tile == 0 || c->tile == 64);
@@ -59,10 +60,10 @@ static int gemm_nt(gpt_ctx *c, hipStream_t st, int64_t m, int64_t n, int64_t k, 
             fflush(glog);
         }
     }
-    // the panel stream's updates keep a raised wave priority in their main loop (option panel_prio, see gemm.hip)
+    // the panel stream's updates keep a raised wave priority (0..3) in their main loop (see gemm.hip)
     // (option gemm_prio >= 0: every GEMM of this context -- the panel-side context of the block-cyclic engine, whose
     // launches all sit on the chain)
-    const int prio = (c->gemm_prio >= 0) ? (int)c->gemm_prio : (!on_main && c->lookahead) ? (int)c->panel_prio : 0;
+    const int prio = (c->gemm_prio >= 0) ? (int)c->gemm_prio : (!on_main && c->lookahead) ? GPT_PANEL_PRIO : 0;
     int rc = launch_gemm_nt(st, m, n, k, alpha, A, lda, B, ldb, beta, C, ldc, tri, c->tile, lds_pad, e0, e1, prio, edge, wait, edge_cols, 1, 0, tail);
     if (!ext) {
         if (prof) GPT_HIP_CHECK(hipEventRecord(gp->e1, st));
@@ -195,83 +196,95 @@ extern "C" int gpt_concurrency_hint(int delta)
 // into 32x32 tiles (fewer than gemm_small_threshold() 64x64 tiles: 8 KB of LDS and 256 threads per workgroup, many fit
 // beside a trailing update) and only up to 1024 of those workgroups (half the chip's wave slots).  A launch of 64x64 tiles
 // never does: measured at N = 8192 with 750 such workgroups waiting in the kernel, 4.84 against 4.45 ms per evaluation.
-// Everything else waits on the stream, in front of the launch (stream_wait_flag).
+// Everything else waits on the stream, in front of the launch (launch_wait_flag).
 static bool gemm_may_wait_in_kernel(const gpt_ctx *c, int64_t m, int64_t n)
 {
     if (!(c->tile == 0 || c->tile == 64)) return false;
     const int64_t nt64 = ((m + 63) / 64) * ((n + 63) / 64);
     return nt64 < gemm_small_threshold() && ((m + 31) / 32) * ((n + 31) / 32) <= 1024;
 }
-// the error word of the context's bounded flag waits
-static inline EdgeSig with_err(gpt_ctx *c, EdgeSig e)
+// the next edge of the context on word d_edge[word]: the words are only ever raised, and every wait for one is bounded
+// (its error word is d_edge[60], see EdgeSig)
+static inline EdgeSig new_edge(gpt_ctx *c, int word)
 {
-    static const bool unbounded = getenv("GPT_EDGE_UNBOUNDED") != nullptr;      // (measurement aid)
-    e.err = unbounded ? nullptr : c->d_edge + 60;
+    EdgeSig e;
+    e.word = c->d_edge + word;
+    e.value = ++c->edge_seq;
+    e.err = c->d_edge + 60;
     return e;
 }
-// stream-side wait: own bounded kernel, or (GPT_EDGE_WAITVALUE, measurement aid) the runtime's hipStreamWaitValue32
-static int stream_wait_flag(hipStream_t st, EdgeSig w)
+
+// ------------------------------------------------------------------------------------------------
+// Leaves (128-column diagonal block + the TRSM of the rows below it) and panels
+// ------------------------------------------------------------------------------------------------
+// short panel (the head chunk of the row-chunked multi-GPU schedule, the last panels of a factorisation): diagonal block
+// and TRSM in one launch, the substitution trailing the pivots (potf2_trsm_kernel, potrf.hip)
+static bool leaf_is_fused(const gpt_ctx *c, int64_t m) { return c->fuse_trsm > 0 && m >= 128 && m <= c->fuse_trsm && !c->use_graph; }
+// workgroups of the launch that factors a leaf with m rows below it (the pivot block's, plus the fused kernel's consumers)
+static int64_t leaf_workgroups(const gpt_ctx *c, int64_t m)
 {
-    static const bool rt = getenv("GPT_EDGE_WAITVALUE") != nullptr;
-    if (rt) {
-        GPT_HIP_CHECK(hipStreamWaitValue32(st, w.word, w.value, hipStreamWaitValueGte, 0xffffffffu));
-        return GPT_OK;
+    if (!leaf_is_fused(c, m)) return 1;
+    const int code = strip_rows_code(c, m);
+    return code > 0 ? 1 + m / (128 >> code) : 1 + (m + 127) / 128;
+}
+
+// One leaf: the pivot block at Ad (global column `base`, packed workspace ws) and the m rows below it.  done_ev / done_edge
+// are recorded / raised when L of the leaf is final; `wait` is polled by the leaf's first kernel before it reads anything.
+static int leaf_factor(gpt_ctx *c, hipStream_t st, double *Ad, int64_t lda, double *ws, int32_t *info, int64_t base, int64_t m,
+                       hipEvent_t done_ev = nullptr, EdgeSig done_edge = EdgeSig(), EdgeSig wait = EdgeSig())
+{
+    if (leaf_is_fused(c, m)) {
+        if (c->flag_epoch > 0x3fffff00u) {      // (the progress word is only ever raised: start over long before a wrap)
+            GPT_HIP_CHECK(hipMemsetAsync(c->d_flag, 0, 256, st));
+            c->flag_epoch = 0;
+        }
+        c->flag_epoch += 32;           // (a launch raises the word by 8: one per 16-column step)
+        return launch_potf2_trsm(st, Ad, lda, ws, info, base, m, c->d_flag, c->flag_epoch, done_ev, done_edge, wait, strip_rows_code(c, m));
     }
-    return launch_wait_flag(st, w);
+    GPT_TRY(launch_potf2_diag(st, Ad, lda, ws, info, base, wait));
+    // (a stop event on the launch is not recorded by stream capture: under a graph use a plain record)
+    GPT_TRY(launch_trsm_panel(st, m, Ad, lda, ws, Ad + 128 * lda, lda, c->use_graph ? nullptr : done_ev, done_edge));
+    if (done_ev && c->use_graph) GPT_HIP_CHECK(hipEventRecord(done_ev, st));
+    return GPT_OK;
 }
 
 static int panel_rec(gpt_ctx *c, hipStream_t st, double *Ap, int64_t lda, int64_t m, int64_t w, double *invd,
                      int32_t *info, int64_t base)
 {
-    if (w == 128) {
-        const int64_t mb = m - 128;
-        if (c->fuse_trsm > 0 && mb >= 128 && mb <= c->fuse_trsm && !c->use_graph) {
-            // short panel (the head chunk of the row-chunked multi-GPU schedule, the last panels of a factorisation):
-            // diagonal block and TRSM in one launch (potf2_trsm_kernel), as in panel_ext
-            if (c->flag_epoch > 0x3fffff00u) {
-                GPT_HIP_CHECK(hipMemsetAsync(c->d_flag, 0, 256, st));
-                c->flag_epoch = 0;
-            }
-            c->flag_epoch += 32;           // (a launch raises the word by 8: one per 16-column step)
-            return launch_potf2_trsm(st, Ap, lda, invd, info, base, mb, c->d_flag, c->flag_epoch, nullptr, EdgeSig(), EdgeSig(),
-                                     strip_rows_code(c, mb));
-        }
-        GPT_TRY(launch_potf2_diag(st, Ap, lda, invd, info, base));
-        return launch_trsm_panel(st, m - 128, Ap, lda, invd, Ap + 128 * lda, lda);
-    }
+    if (w == 128) return leaf_factor(c, st, Ap, lda, invd, info, base, m - 128);
     const int64_t h = (w / 256) * 128 > 0 ? (w / 256) * 128 : 128;
     GPT_TRY(panel_rec(c, st, Ap, lda, m, h, invd, info, base));
     GPT_TRY(gemm_nt(c, st, m - h, w - h, h, -1.0, Ap + h * lda, lda, Ap + h * lda, lda, 1.0, Ap + h * lda + h, lda, 1));
     return panel_rec(c, st, Ap + h * lda + h, lda, m - h, w - h, invd + (h / 128) * GPT_WS_BLOCK, info, base + h);
 }
 
-// Look-ahead panel: block column [c0, c0+w) of the n x n matrix, right-looking in 128-column leaves.  Every leaf's
-// rank-128 update also reaches the GPT_PANEL_EXT columns that follow the block column, so when the panel is done the
-// first leaf of the NEXT block column is already up to date with respect to this one and its pivot chain can start
-// without waiting for anybody.  `wait_ev` (the other stream's update of the columns this panel reads beyond its first
-// leaf) is waited for before the first update; `done_ev` is recorded once L of the block column is final.
-#define GPT_PANEL_EXT 128
-static int leaf_factor(gpt_ctx *c, hipStream_t st, double *A, int64_t lda, int64_t n, int64_t lc, double *invd,
-                       int32_t *info, hipEvent_t done_ev)
-{
-    double *Ad = A + lc * lda + lc;
-    double *ws = invd + (lc / 128) * GPT_WS_BLOCK;
-    const int64_t m = n - (lc + 128);
-    if (c->fuse_trsm > 0 && m >= 128 && m <= c->fuse_trsm && !c->use_graph) {
-        if (c->flag_epoch > 0x3fffff00u) {
-            GPT_HIP_CHECK(hipMemsetAsync(c->d_flag, 0, 256, st));
-            c->flag_epoch = 0;
-        }
-        c->flag_epoch += 32;           // (a launch raises the word by 8: one per 16-column step)
-        return launch_potf2_trsm(st, Ad, lda, ws, info, lc, m, c->d_flag, c->flag_epoch, done_ev, EdgeSig(), EdgeSig(), strip_rows_code(c, m));
-    }
-    GPT_TRY(launch_potf2_diag(st, Ad, lda, ws, info, lc));
-    GPT_TRY(launch_trsm_panel(st, m, Ad, lda, ws, Ad + 128 * lda, lda, (done_ev && !c->use_graph) ? done_ev : nullptr));
-    if (done_ev && c->use_graph) GPT_HIP_CHECK(hipEventRecord(done_ev, st));
-    return GPT_OK;
-}
+// What the caller of one factorisation asks of it beyond the matrix (potrf_run / potrf_enqueue), and what it is told.
+// The defaults are what every caller but factor_and_ll gets: the factorisation starts behind everything on the main stream
+// and ends joined on it.
+struct PotrfRequest {
+    hipEvent_t head_event = nullptr;   // the columns panel 0 touches (nb_outer + 128) are built: the panel stream may start behind it
+    EdgeSig head_wait;                 // ... the same as a flag word: the first leaf's kernel waits for it (fit_terms_once)
+    bool defer_join = false;           // leave the final panel -> main join to the caller; the result names the stream the work ended on
+    bool want_early_binv = false;      // eager alpha: build the 512-wide block inverses left of the last panel under that panel
+    // Eager alpha with N a multiple of 512: the factor's last 128 columns hold only the augmented row and the padding.  alpha needs
+    // nothing of that leaf, so its pivot block (and the rank-128 updates that reach it) leave the panel stream: the substitution
+    // follows the last REAL leaf at once, the pad leaf and the reduction run beside it on the main stream (potrf_enqueue).
+    bool defer_pad_leaf = false;
+};
+struct PotrfResult {
+    hipStream_t tail_stream = nullptr;   // defer_join: the stream the factorisation ended on (nullptr: the main stream, joined)
+    bool pad_leaf_deferred = false;      // the pad leaf went to the main stream (the reduction must follow it there)
+};
+// What the panels of ONE factorisation share (potrf_enqueue -> panel_ext)
+struct PanelShared {
+    EdgeSig first_wait;                // the first leaf of the factorisation waits for this word (the K build's head), once
+    bool defer_pad = false;            // the pad leaf and what updates it go to the main stream (PotrfRequest::defer_pad_leaf)
+    bool pad_leaf_deferred = false;    // ... and the pad leaf has been met and left out
+    std::vector<int64_t> pad_upd_lc;   // leaves whose update of the pad block was held back, by first column
+};
 
-// The same look-ahead panel, LEFT-looking inside the block column (option "inner" = 1): leaf j first receives the
+#define GPT_PANEL_EXT 128          // columns past its block column that a look-ahead panel's updates reach (panel_ext)
+// The look-ahead panel of panel_ext (below), LEFT-looking inside the block column (option "inner" = 1): leaf j first receives the
 // update of the leaves 0..j-1 of this block column in ONE launch (k = 128 j, 128 columns wide), then is factored; after
 // the last leaf the 128 columns that follow the block column (the next panel's first leaf) get the whole block column's
 // update (k = w).  Same flops as the right-looking form, but every update launch on the chain is 128 columns wide --
@@ -292,7 +305,8 @@ static int panel_ext_ll(gpt_ctx *c, hipStream_t st, double *A, int64_t lda, int6
                             A + lc * lda + lc, lda, 1));
         }
         const bool last = (lc + 128 == c0 + w);
-        GPT_TRY(leaf_factor(c, st, A, lda, n, lc, invd, info, last ? done_ev : nullptr));
+        GPT_TRY(leaf_factor(c, st, A + lc * lda + lc, lda, invd + (lc / 128) * GPT_WS_BLOCK, info, lc, n - (lc + 128),
+                            last ? done_ev : nullptr));
     }
     const int64_t e0 = c0 + w;
     if (e0 < n) {
@@ -304,67 +318,53 @@ static int panel_ext_ll(gpt_ctx *c, hipStream_t st, double *A, int64_t lda, int6
     return GPT_OK;
 }
 
-// `ext`: how many columns past the block column every leaf update reaches (GPT_PANEL_EXT).
-static int panel_ext(gpt_ctx *c, hipStream_t st, double *A, int64_t lda, int64_t n, int64_t c0, int64_t w,
-                     double *invd, int32_t *info, hipEvent_t wait_ev, hipEvent_t done_ev, int64_t ext = GPT_PANEL_EXT,
-                     hipEvent_t first_ev = nullptr, EdgeSig wait_edge = EdgeSig(), EdgeSig done_edge = EdgeSig())
+// Look-ahead panel: block column [c0, c0+w) of the n x n matrix, right-looking in 128-column leaves.  Every leaf's
+// rank-128 update also reaches the GPT_PANEL_EXT columns that follow the block column, so when the panel is done the
+// first leaf of the NEXT block column is already up to date with respect to this one and its pivot chain can start
+// without waiting for anybody.  `wait_ev` (the other stream's update of the columns this panel reads beyond its first
+// leaf) is waited for before the first update; `done_ev` is recorded once L of the block column is final.
+#define GPT_INNER_ROWS 4608        // "inner" = 2: left-looking once at most this many rows remain (the chain-bound end)
+#define GPT_HEAD_WAIT_WGS 33       // first leaf: in-kernel wait for the K build's head while its launch has at most this many workgroups
+// wait_edge / done_edge: the same two dependencies as wait_ev / done_ev carried by flag words (EdgeSig, common.hpp)
+// first_ev: recorded by the panel's FIRST update launch (see "deferred rest" in potrf_enqueue)
+static int panel_ext(gpt_ctx *c, PanelShared &ps, hipStream_t st, double *A, int64_t lda, int64_t n, int64_t c0, int64_t w,
+                     double *invd, int32_t *info, hipEvent_t wait_ev, hipEvent_t done_ev, hipEvent_t first_ev,
+                     EdgeSig wait_edge, EdgeSig done_edge)
 {
-    // wait_edge / done_edge: the same two dependencies as wait_ev / done_ev carried by flag words (EdgeSig, common.hpp)
-    // first_ev: recorded by the panel's FIRST update launch (see "deferred rest" in potrf_enqueue)
-    if (c->inner == 1 || (c->inner == 2 && n - c0 <= c->inner_rows))
+    if (c->inner == 1 || (c->inner == 2 && n - c0 <= GPT_INNER_ROWS))
         return panel_ext_ll(c, st, A, lda, n, c0, w, invd, info, wait_ev, done_ev);
-    const int64_t cend = (c0 + w + ext < n) ? c0 + w + ext : n;
-    const bool defer_pad = c->defer_pad_leaf && !c->use_graph;      // (gpt_ctx: the pad leaf and what updates it go to the main stream)
+    const int64_t cend = (c0 + w + GPT_PANEL_EXT < n) ? c0 + w + GPT_PANEL_EXT : n;
     for (int64_t lc = c0; lc < c0 + w; lc += 128) {
-        double *Ad = A + lc * lda + lc;
-        double *ws = invd + (lc / 128) * GPT_WS_BLOCK;
         const int64_t r1 = lc + 128;
-        const bool last = (r1 == c0 + w) && done_ev;
+        const bool last = (r1 == c0 + w);
         const int64_t m = n - r1;
-        if (defer_pad && m == 0) {
+        if (ps.defer_pad && m == 0) {
             // the pad leaf itself: enqueued by potrf_enqueue on the main stream (nothing on this stream depends on it)
-            c->pad_leaf_deferred = true;
-            if (last) GPT_HIP_CHECK(hipEventRecord(done_ev, st));
+            ps.pad_leaf_deferred = true;
+            if (last && done_ev) GPT_HIP_CHECK(hipEventRecord(done_ev, st));
             if (lc == c0 && wait_ev) GPT_HIP_CHECK(hipStreamWaitEvent(st, wait_ev, 0));
             continue;
         }
         EdgeSig fw;                                   // the first leaf of a factorisation may have to wait for the K build's head
-        if (lc == 0 && c->first_wait.word) {
-            fw = c->first_wait;
-            c->first_wait = EdgeSig();
+        if (lc == 0 && ps.first_wait.word) {
+            fw = ps.first_wait;
+            ps.first_wait = EdgeSig();
             // Inside the leaf's kernel only while that launch fits the CUs reserved for the panel stream: every workgroup of
             // the fused kernel holds a whole CU (135 KB of LDS) while it spins, and beyond the reserved CUs they would be
             // taken from the K build the launch is waiting for.  Otherwise a one-wave wait kernel in front of it.
-            const bool fused = c->fuse_trsm > 0 && m >= 128 && m <= c->fuse_trsm && !c->use_graph;
-            const bool r64 = fused && m <= c->fuse_rows64;      // (64 rows per workgroup)
-            const int64_t wgs = (fused && strip_rows_code(c, m) > 1) ? 1 + m / (128 >> strip_rows_code(c, m)) : r64 ? 1 + m / 64 : fused ? 1 + (m + 127) / 128 : 1;
-            if (wgs > c->head_wait_wgs) {
-                GPT_TRY(stream_wait_flag(st, fw));
+            if (leaf_workgroups(c, m) > GPT_HEAD_WAIT_WGS) {
+                GPT_TRY(launch_wait_flag(st, fw));
                 fw = EdgeSig();
             }
         }
-        if (c->fuse_trsm > 0 && m >= 128 && m <= c->fuse_trsm && !c->use_graph) {
-            // short panel: diagonal block and TRSM in one launch, the substitution trailing the pivots (potrf.hip)
-            if (c->flag_epoch > 0x3fffff00u) {
-                GPT_HIP_CHECK(hipMemsetAsync(c->d_flag, 0, 256, st));
-                c->flag_epoch = 0;
-            }
-            c->flag_epoch += 32;           // (a launch raises the word by 8: one per 16-column step)
-            GPT_TRY(launch_potf2_trsm(st, Ad, lda, ws, info, lc, m, c->d_flag, c->flag_epoch, last ? done_ev : nullptr,
-                                      (r1 == c0 + w) ? done_edge : EdgeSig(), fw, strip_rows_code(c, m)));
-        } else {
-            GPT_TRY(launch_potf2_diag(st, Ad, lda, ws, info, lc, fw));
-            // (a stop event on the launch is not recorded by stream capture: under a graph use a plain record)
-            GPT_TRY(launch_trsm_panel(st, m, Ad, lda, ws, Ad + 128 * lda, lda, (last && !c->use_graph) ? done_ev : nullptr,
-                                      (r1 == c0 + w) ? done_edge : EdgeSig()));
-            if (last && c->use_graph) GPT_HIP_CHECK(hipEventRecord(done_ev, st));
-        }
+        GPT_TRY(leaf_factor(c, st, A + lc * lda + lc, lda, invd + (lc / 128) * GPT_WS_BLOCK, info, lc, m, last ? done_ev : nullptr,
+                            last ? done_edge : EdgeSig(), fw));
         if (lc == c0 && wait_ev) GPT_HIP_CHECK(hipStreamWaitEvent(st, wait_ev, 0));
         int64_t cend_p = cend;                       // this stream's share of the leaf's update: columns [r1, cend_p)
-        if (defer_pad && cend == n) {
+        if (ps.defer_pad && cend == n) {
             // the leaf's update of the pad block (the last 128 columns) is held back for the main stream (all of them: a leaf
             // that applied its own here would run ahead of the held-back ones -- another order than defer_pad = 0)
-            c->pad_upd_lc.push_back(lc);
+            ps.pad_upd_lc.push_back(lc);
             cend_p = n - 128;
             if (cend_p <= r1 && first_ev) {
                 GPT_HIP_CHECK(hipEventRecord(first_ev, st));
@@ -376,11 +376,11 @@ static int panel_ext(gpt_ctx *c, hipStream_t st, double *A, int64_t lda, int64_t
             // update wrote: it waits for that edge itself, see gemm.hip)
             // Its workgroups SPIN until the word is up, so the launch must not be able to fill the chip (the update they
             // wait for needs room to run): in the kernel only while the launch stays under 1024 workgroups = half the wave
-            // slots, otherwise as a stream operation in front of it (a kernel of the runtime, ~5 us).
+            // slots, otherwise as a stream operation in front of it (a one-wave wait kernel, ~5 us).
             EdgeSig inwait;
             if (lc == c0 && wait_edge.word) {
                 if (gemm_may_wait_in_kernel(c, n - r1, cend_p - r1)) inwait = wait_edge;
-                else GPT_TRY(stream_wait_flag(st, wait_edge));
+                else GPT_TRY(launch_wait_flag(st, wait_edge));
             }
             GPT_TRY(gemm_nt(c, st, n - r1, cend_p - r1, 128, -1.0, A + r1 * lda + lc, lda, A + r1 * lda + lc, lda, 1.0,
                             A + r1 * lda + r1, lda, 1, first_ev, EdgeSig(), inwait));
@@ -391,7 +391,9 @@ static int panel_ext(gpt_ctx *c, hipStream_t st, double *A, int64_t lda, int64_t
 }
 
 static int enqueue_early_block_inverses(gpt_ctx *c, hipStream_t S, int64_t cols, int64_t cols_final);      // api_solve.inc
-static int potrf_enqueue(gpt_ctx *c, int64_t n, double *A, int64_t lda, double *invd, int32_t *info)
+#define GPT_MERGE_MIN_TILES 512    // urgent + rest are one launch while it has at least this many 64x64 tiles (it needs an order table)
+static int potrf_enqueue(gpt_ctx *c, int64_t n, double *A, int64_t lda, double *invd, int32_t *info, const PotrfRequest &req,
+                         PotrfResult *res)
 {
     if (n % 128) {
         gpt_set_error("potrf: n must be a multiple of 128 (n=%lld)", (long long)n);
@@ -399,24 +401,19 @@ static int potrf_enqueue(gpt_ctx *c, int64_t n, double *A, int64_t lda, double *
     }
     const int64_t nbo = outer_width(c, n);
     const int64_t nblk = (n + nbo - 1) / nbo;
-    hipStream_t S = c->stream, P = c->panel_stream;
+    const hipStream_t S = c->stream, P = c->panel_stream;
     const bool la = c->lookahead && nblk > 1;
-    c->pad_leaf_deferred = false;
-    c->pad_upd_lc.clear();
-    if (!la || c->inner != 0) c->defer_pad_leaf = false;        // (the right-looking look-ahead panels only)
-    hipEvent_t head = c->head_event;
-    c->head_event = nullptr;
-    const EdgeSig head_wait = c->head_wait;                   // (the K build's head columns as a flag word, see fit_terms)
-    c->head_wait = EdgeSig();
-    c->first_wait = EdgeSig();
+    // the rank-pw update by the block column [pc0, pc0 + pw): the lower trapezoid of the columns [a, b), rows [a, n)
+    auto update = [&](hipStream_t st, int64_t pc0, int64_t pw, int64_t a, int64_t b, hipEvent_t done = nullptr, EdgeSig edge = EdgeSig(),
+                      EdgeSig wait = EdgeSig(), int64_t edge_cols = 0, EdgeSig tail = EdgeSig()) -> int {
+        return gemm_nt(c, st, n - a, b - a, pw, -1.0, A + a * lda + pc0, lda, A + a * lda + pc0, lda, 1.0, A + a * lda + a, lda, 1,
+                       done, edge, wait, edge_cols, tail);
+    };
     if (!la) {
         for (int64_t k = 0; k < nblk; k++) {
             const int64_t c0 = k * nbo, w = (n - c0 < nbo) ? n - c0 : nbo, m = n - c0;
             GPT_TRY(panel_rec(c, S, A + c0 * lda + c0, lda, m, w, invd + (c0 / 128) * GPT_WS_BLOCK, info, c0));
-            const int64_t r0 = c0 + w;
-            if (r0 < n)
-                GPT_TRY(gemm_nt(c, S, n - r0, n - r0, w, -1.0, A + r0 * lda + c0, lda, A + r0 * lda + c0, lda, 1.0,
-                                A + r0 * lda + r0, lda, 1));
+            if (c0 + w < n) GPT_TRY(update(S, c0, w, c0 + w, n));
         }
         return GPT_OK;
     }
@@ -425,17 +422,49 @@ static int potrf_enqueue(gpt_ctx *c, int64_t n, double *A, int64_t lda, double *
     // u0 = c0 + nbo + EXT in two launches: the nbo columns panel k+1 is going to touch first ("urgent", event e_cu),
     // then the rest.  P never waits for a large update: its only dependency is e_cu(k) before the first update of
     // panel k+1, and S has the whole first pivot block + TRSM of that panel to get there.
-    if (head_wait.word && c->inner == 0) {
-        // the first leaf's kernel waits for the word itself (potrf.hip: edge_wait): no event edge in front of the chain
-        c->first_wait = head_wait;
-    } else {
-        if (!head) {
-            head = get_event(c, 0);
-            if (!head) return GPT_E_HIP;
-            GPT_HIP_CHECK(hipEventRecord(head, S));
-        }
-        GPT_HIP_CHECK(hipStreamWaitEvent(P, head, 0));
-    }
+    //
+    // What holds for the whole factorisation:
+    const bool graph = c->use_graph != 0;
+    const bool tile64 = (c->tile == 0 || c->tile == 64);      // (the edge flags and the tail wait live in the 64x64 / 32x32 GEMM kernels only)
+    // Helper: while the trailing updates dominate, the panel stream leaves its reserved CUs idle most of the time.
+    // The bottom-right triangle [s, n)^2 of the rank-w update of panel k therefore runs on H, a stream masked to
+    // those CUs (minus 8 that stay free for the diagonal-block kernel), concurrently with S's share; the split is
+    // sized by the two streams' rates so that they finish together.  The split column only moves right: a helper
+    // region lies inside the previous one, so H needs nothing but "panel k is final"; S waits for helper k before
+    // it next touches columns >= s.
+    // (only where the updates dominate: at n = 8192 the helper costs 0.5-1 %, at 16384 / 32768 it gains 2 / 3 %)
+    const hipStream_t H = (c->helper_stream && !graph && c->helper_tf > 0 && n > c->helper_min_n) ? c->helper_stream : nullptr;
+    const double rate_s = 46e12, rate_h = 1e11 * (double)c->helper_tf * (double)c->helper_cus / 24.0;
+    // Flag edges (EdgeSig): "panel k is final" (panel stream -> main stream) and "the urgent update of panel k is done"
+    // (main -> panel stream) are raised by the last workgroup of the kernel that completes them and waited for by a
+    // kernel -- 1.5 us per edge against 8-9 for an event, and no stop event on the chain's kernels (4.5 us
+    // each).  In the chain-bound end both edges are on the critical path of every panel.
+    // (not with the helper stream: flags + helper -- the helper waiting behind a wait kernel, the merged launch cut at the
+    // split column, code below -- measured the same as events + helper at N = 16384 (27.65 against 27.49 ms), and the helper
+    // in the head of an N = 8192 factorisation still loses, 4.64 against 4.45 ms: round 3)
+    const bool use_flags = c->flags_now && !H && c->inner == 0 && c->defer_rows == 0 && tile64;
+    // Update-bound head (option purg_rows): while more rows than this remain, the PANEL stream applies panel k to the columns
+    // panel k+1 touches ("urgent") itself, right behind the panel -- no event round trip panel -> main -> panel on the chain and
+    // one launch less on the main stream, which sets the pace there.
+    // (with flag edges and merged launches the main stream has one launch per panel anyway and the urgent tiles run at
+    // the large launch's rate: the panel stream's own urgent update no longer pays -- 4.444 against 4.492 ms at N = 8192)
+    const int64_t purg_eff = (H || graph || (use_flags && c->merge_urgent)) ? 0 : c->purg_rows;
+    // (edge_flags >= 2: "the rest of panel k-1 is done" as a flag edge as well -- no stop event on the main
+    // stream's large launches, which set the pace there; the whole C of that launch is then written through)
+    const bool rest_flag = use_flags && c->edge_flags >= 2;
+    // Tail wait: the last launch of a panel on the main stream ends only when the NEXT panel's flag is up, so the next
+    // panel's launch follows it without a wait kernel in between.
+    // NOT while the launches are being timed (option profile_gemm: bench.py's roofline events): a launch that waits at its
+    // end reports its wait as its own duration -- in the transition from the update-bound head to the chain-bound end,
+    // where the main stream does wait for the panel stream, 20-50 us of a 60-110-us launch.  A timed evaluation keeps the
+    // wait in a kernel of its own, like tail_wait = 0, and its launches' durations are the GEMM's.
+    const bool tail_here = use_flags && c->tail_wait != 0 && !c->prof_gemm;
+    // Deferred rest (chain-bound end of the factorisation, option defer_rows).  There the panel stream sets the pace and the
+    // main stream has slack, yet its large "rest" update of panel k used to start right after the urgent one and shared
+    // the chip with the panel stream's first leaf update of panel k+1 -- which is ON the chain and ran 60 us instead of
+    // ~17 (profiles/r01_timeline_c3_N8192.txt).  The rest of panel k is therefore held back until that leaf update is
+    // done (one event), and is enqueued one loop iteration late so that the event is recorded before it is waited for.
+    const int64_t defer_rows = (!H && !graph) ? c->defer_rows : 0;
     // Panel widths: nbo; optionally ("ramp") 128, 256, ... at the start so that the main stream gets its first update
     // after one leaf instead of after a whole panel -- measured slightly slower (N=8192: 5.95 against 5.90 ms,
     // N=16384: 31.4 against 31.2: the rank-128/256 updates it adds are inefficient), so it is off by default.
@@ -453,46 +482,23 @@ static int potrf_enqueue(gpt_ctx *c, int64_t n, double *A, int64_t lda, double *
             w += 128;
         }
     }
-    // Helper: while the trailing updates dominate, the panel stream leaves its reserved CUs idle most of the time.
-    // The bottom-right triangle [s, n)^2 of the rank-w update of panel k therefore runs on H, a stream masked to
-    // those CUs (minus 8 that stay free for the diagonal-block kernel), concurrently with S's share; the split is
-    // sized by the two streams' rates so that they finish together.  The split column only moves right: a helper
-    // region lies inside the previous one, so H needs nothing but "panel k is final"; S waits for helper k before
-    // it next touches columns >= s.
-    // (only where the updates dominate: at n = 8192 the helper costs 0.5-1 %, at 16384 / 32768 it gains 2 / 3 %)
-    hipStream_t H = (c->helper_stream && !c->use_graph && c->helper_tf > 0 && n > c->helper_min_n) ? c->helper_stream : nullptr;
-    const double rate_s = 46e12, rate_h = 1e11 * (double)c->helper_tf * (double)c->helper_cus / 24.0;
-    hipEvent_t e_cu_prev = nullptr, e_help_prev = nullptr, e_rest_prev = nullptr;
-    int64_t c0 = 0, s_prev = 0;
-    int64_t awaited = 0;          // end column of the last panel the main stream has waited for (eager alpha's early block inverses)
-    // Update-bound head (option early_rows): while more than early_rows rows remain, the trailing updates run on a
-    // stream that leaves only a few CUs to the panel stream (the diagonal-block kernel needs ONE free CU; the fused
-    // diagonal-block + TRSM kernel of the chain-bound end needs up to 33).  One event hands over between the two.
-    const bool use_early = c->early_stream && c->early_rows > 0 && !H && !c->use_graph;
-    hipStream_t S0 = S, S_cur = S;
-    if (use_early) {
-        hipEvent_t e_k = get_event(c, 2 + 4 * widths.size());
-        if (!e_k) return GPT_E_HIP;
-        GPT_HIP_CHECK(hipEventRecord(e_k, S0));                     // the K build (and everything before) on the main stream
-        GPT_HIP_CHECK(hipStreamWaitEvent(c->early_stream, e_k, 0));
+    const size_t np = widths.size();
+
+    PanelShared ps;
+    ps.defer_pad = req.defer_pad_leaf && c->inner == 0 && !graph;      // (the right-looking look-ahead panels only)
+    if (req.head_wait.word && c->inner == 0) {
+        // the first leaf's kernel waits for the word itself (potrf.hip: edge_wait): no event edge in front of the chain
+        ps.first_wait = req.head_wait;
+    } else {
+        hipEvent_t head = req.head_event;
+        if (!head) {
+            head = get_event(c, 0);
+            if (!head) return GPT_E_HIP;
+            GPT_HIP_CHECK(hipEventRecord(head, S));
+        }
+        GPT_HIP_CHECK(hipStreamWaitEvent(P, head, 0));
     }
-    // Deferred rest (chain-bound end of the factorisation, option defer_rows).  There the panel stream sets the pace and the
-    // main stream has slack, yet its large "rest" update of panel k used to start right after the urgent one and shared
-    // the chip with the panel stream's first leaf update of panel k+1 -- which is ON the chain and ran 60 us instead of
-    // ~17 (profiles/r01_timeline_c3_N8192.txt).  The rest of panel k is therefore held back until that leaf update is
-    // done (one event), and is enqueued one loop iteration late so that the event is recorded before it is waited for.
-    const bool use_late = c->late_panel_stream && c->late_rows > 0 && !c->use_graph;
-    // Flag edges (EdgeSig): "panel k is final" (panel stream -> main stream) and "the urgent update of panel k is done"
-    // (main -> panel stream) are raised by the last workgroup of the kernel that completes them and waited for with
-    // hipStreamWaitValue32 -- 1.5 us per edge against 8-9 for an event, and no stop event on the chain's kernels (4.5 us
-    // each).  In the chain-bound end both edges are on the critical path of every panel.
-    // (tile: the edge flags live in the 64x64 / 32x32 GEMM kernels only)
-    // (not with the helper stream: flags + helper -- the helper waiting behind a wait kernel, the merged launch cut at the
-    // split column, code below -- measured the same as events + helper at N = 16384 (27.65 against 27.49 ms), and the helper
-    // in the head of an N = 8192 factorisation still loses, 4.64 against 4.45 ms: round 3)
-    const bool use_flags = c->flags_now && !H && c->inner == 0 && !use_early && !use_late
-                           && c->defer_rows == 0 && (c->tile == 0 || c->tile == 64);
-    if (use_flags && c->edge_seq > 0xf0000000u && !head_wait.word) {           // (the words are only ever raised: start over long before a wrap)
+    if (use_flags && c->edge_seq > 0xf0000000u && !req.head_wait.word) {       // (the words are only ever raised: start over long before a wrap)
         GPT_HIP_CHECK(hipStreamSynchronize(S));
         GPT_HIP_CHECK(hipStreamSynchronize(P));
         GPT_HIP_CHECK(hipMemsetAsync(c->d_edge, 0, 256, S));
@@ -500,256 +506,178 @@ static int potrf_enqueue(gpt_ctx *c, int64_t n, double *A, int64_t lda, double *
         c->edge_seq = 0;
         c->alpha_counter = 0;                  // (the step counter of the wide back-substitution lives in the same words)
     }
+    hipEvent_t e_cu_prev = nullptr, e_help_prev = nullptr, e_rest_prev = nullptr;
     EdgeSig cu_edge_prev, rest_edge_prev;
     EdgeSig next_panel_edge;      // the NEXT panel's edge, allocated early: the main stream's last launch of this panel awaits it at its end
-    struct PendingRest { bool on; int64_t c0, w, u1, split; hipStream_t S; } pend = {false, 0, 0, 0, 0, nullptr};
-    auto launch_rest = [&](const PendingRest &r) -> int {
-        return gemm_nt(c, r.S, n - r.u1, r.split - r.u1, r.w, -1.0, A + r.u1 * lda + r.c0, lda, A + r.u1 * lda + r.c0, lda,
-                       1.0, A + r.u1 * lda + r.u1, lda, 1);
-    };
-    for (size_t k = 0; k < widths.size(); k++) {
+    int64_t c0 = 0, s_prev = 0;
+    int64_t awaited = 0;          // end column of the last panel the main stream has waited for (eager alpha's early block inverses)
+    struct PendingRest { bool on; int64_t c0, w, u1, split; } pend = {false, 0, 0, 0, 0};
+    for (size_t k = 0; k < np; c0 += widths[k], k++) {
         const int64_t w = widths[k];
-        if (use_early) {
-            hipStream_t want = (n - c0 > c->early_rows) ? c->early_stream : S0;
-            if (want != S_cur) {
-                hipEvent_t e_sw = get_event(c, 3 + 4 * widths.size());
-                if (!e_sw) return GPT_E_HIP;
-                GPT_HIP_CHECK(hipEventRecord(e_sw, S_cur));
-                GPT_HIP_CHECK(hipStreamWaitEvent(want, e_sw, 0));
-                S_cur = want;
-            }
-            S = S_cur;
-        }
-        const int64_t wn = (k + 1 < widths.size()) ? widths[k + 1] : 0;      // width of the next panel
+        const int64_t wn = (k + 1 < np) ? widths[k + 1] : 0;      // width of the next panel
         hipEvent_t e_panel = get_event(c, 2 + 4 * k), e_cu = get_event(c, 3 + 4 * k), e_help = get_event(c, 4 + 4 * k);
         hipEvent_t e_sdone = get_event(c, 5 + 4 * k);
         if (!e_panel || !e_cu || !e_help || !e_sdone) return GPT_E_HIP;
-        const int64_t ext_k = GPT_PANEL_EXT, ext_k1 = GPT_PANEL_EXT;      // reach of the leaf updates past a panel
-        if (use_late && P == c->panel_stream && n - c0 <= c->late_rows) {
-            hipEvent_t e_pl = get_event(c, 6 + 4 * widths.size());
-            if (!e_pl) return GPT_E_HIP;
-            GPT_HIP_CHECK(hipEventRecord(e_pl, P));
-            GPT_HIP_CHECK(hipStreamWaitEvent(c->late_panel_stream, e_pl, 0));
-            P = c->late_panel_stream;
-        }
-        c->pad_now = (c->late_pad > 0 && n - c0 <= c->late_pad_rows) ? c->late_pad : 0;
-        hipEvent_t e_first = pend.on ? get_event(c, 8 + 4 * widths.size() + k) : nullptr;
+        hipEvent_t e_first = pend.on ? get_event(c, 8 + 4 * np + k) : nullptr;
         if (pend.on && !e_first) return GPT_E_HIP;
+        const int64_t u0 = c0 + w + GPT_PANEL_EXT;      // the first column panel k's own leaf updates did not reach
         EdgeSig panel_edge;
         bool panel_awaited = false;      // (by the tail wait of the previous panel's last main-stream launch)
-        if (use_flags && c0 + w + ext_k < n) {
-            if (next_panel_edge.word) {
-                panel_edge = next_panel_edge;
-                panel_awaited = true;
-            } else {
-                panel_edge.word = c->d_edge;
-                panel_edge.value = ++c->edge_seq;
-                panel_edge = with_err(c, panel_edge);
-            }
+        if (use_flags && u0 < n) {
+            panel_awaited = next_panel_edge.word != nullptr;
+            panel_edge = panel_awaited ? next_panel_edge : new_edge(c, 0);
         }
         next_panel_edge = EdgeSig();
-        GPT_TRY(panel_ext(c, P, A, lda, n, c0, w, invd, info, e_cu_prev, use_flags ? nullptr : e_panel, ext_k, e_first, cu_edge_prev,
+        GPT_TRY(panel_ext(c, ps, P, A, lda, n, c0, w, invd, info, e_cu_prev, use_flags ? nullptr : e_panel, e_first, cu_edge_prev,
                           panel_edge));
+        e_cu_prev = nullptr;
         cu_edge_prev = EdgeSig();
         if (pend.on) {
-            GPT_HIP_CHECK(hipStreamWaitEvent(pend.S, e_first, 0));
-            GPT_TRY(launch_rest(pend));
+            GPT_HIP_CHECK(hipStreamWaitEvent(S, e_first, 0));
+            GPT_TRY(update(S, pend.c0, pend.w, pend.u1, pend.split));
             pend.on = false;
         }
-        e_cu_prev = nullptr;
-        const int64_t u0 = c0 + w + ext_k;
-        if (u0 < n) {
-            // urgent: the columns panel k+1 touches beyond what panel k's own leaf updates reached,
-            // [c0' + ext_k, c0' + w' + ext_k+1)
-            const int64_t u1 = (c0 + w + wn + ext_k1 < n) ? c0 + w + wn + ext_k1 : n;
-            int64_t split = n;                                        // S takes columns [u1, split), H [split, n)
-            if (H && u1 < n) {
-                const double side0 = (double)(n - u1);
-                int64_t side = (int64_t)(sqrt(rate_h / (rate_s + rate_h)) * side0) / 64 * 64;
-                if (n - side < s_prev) side = n - s_prev;
-                // worth a launch only while the update is large (>= ~10 GFLOP) and the slice a real triangle
-                if (side >= 1024 && n - side > u1 && (double)w * side0 * side0 >= 1e10) split = n - side;
+        if (u0 >= n) continue;      // nothing right of what the panel itself updated
+        // urgent: the columns panel k+1 touches beyond what panel k's own leaf updates reached, [u0, u1)
+        const int64_t u1 = (u0 + wn < n) ? u0 + wn : n;
+        int64_t split = n;                                        // S takes columns [u1, split), H [split, n)
+        if (H && u1 < n) {
+            const double side0 = (double)(n - u1);
+            int64_t side = (int64_t)(sqrt(rate_h / (rate_s + rate_h)) * side0) / 64 * 64;
+            if (n - side < s_prev) side = n - s_prev;
+            // worth a launch only while the update is large (>= ~10 GFLOP) and the slice a real triangle
+            if (side >= 1024 && n - side > u1 && (double)w * side0 * side0 >= 1e10) split = n - side;
+        }
+        if (split < n && !e_help_prev) {
+            // first helper (or first after a gap): its region was last written by S (K build / a whole update)
+            GPT_HIP_CHECK(hipEventRecord(e_sdone, S));
+            GPT_HIP_CHECK(hipStreamWaitEvent(H, e_sdone, 0));
+        }
+        if (!use_flags) GPT_HIP_CHECK(hipStreamWaitEvent(S, e_panel, 0));
+        else if (!panel_awaited) GPT_TRY(launch_wait_flag(S, panel_edge));
+        awaited = c0 + w;        // (panel_awaited: the previous panel's last launch on S waited for it at its end)
+        // (the tail wait's flag is the next panel's: its value is fixed here, one panel early)
+        EdgeSig tail;
+        if (tail_here && split == n && k + 1 < np && u0 + wn < n) tail = new_edge(c, 0);
+        if (split < n) {
+            if (use_flags) GPT_TRY(launch_wait_flag(H, panel_edge));
+            else GPT_HIP_CHECK(hipStreamWaitEvent(H, e_panel, 0));
+            GPT_TRY(update(H, c0, w, split, n, e_help));
+        }
+        bool help_waited = false;      // S waits for the previous helper slice before it touches that slice's columns
+        if (e_help_prev && u1 > s_prev) {
+            GPT_HIP_CHECK(hipStreamWaitEvent(S, e_help_prev, 0));
+            help_waited = true;
+        }
+        auto wait_help_prev = [&]() -> int {
+            if (e_help_prev && !help_waited) GPT_HIP_CHECK(hipStreamWaitEvent(S, e_help_prev, 0));
+            e_help_prev = nullptr;
+            return GPT_OK;
+        };
+        // A panel ends in one of three ways:
+        if (purg_eff > 0 && n - c0 > purg_eff && u1 < n) {
+            // (1) urgent update on the PANEL stream, rest on the main stream (no helper here: split == n).  Both streams
+            // read-modify-write the urgent columns (the main stream's rest of panel k-1 covers them too), so the panel stream
+            // waits for that rest.
+            if (e_rest_prev) GPT_HIP_CHECK(hipStreamWaitEvent(P, e_rest_prev, 0));
+            if (!e_rest_prev && !rest_edge_prev.word) {
+                // First update the PANEL stream applies beyond the head columns: whatever the main stream still has in
+                // flight on those columns -- the rest of the K build of this evaluation -- must be through.  (Found with the
+                // `ramp` option, whose 128-wide first panel is done before the K build is: "8064-th leading minor not
+                // positive definite"; with 384-wide panels the build happened to finish first.)
+                hipEvent_t e_k = get_event(c, 9 + 5 * np);
+                if (!e_k) return GPT_E_HIP;
+                GPT_HIP_CHECK(hipEventRecord(e_k, S));
+                GPT_HIP_CHECK(hipStreamWaitEvent(P, e_k, 0));
             }
-            if (split < n && !e_help_prev) {
-                // first helper (or first after a gap): its region was last written by S (K build / a whole update)
-                GPT_HIP_CHECK(hipEventRecord(e_sdone, S));
-                GPT_HIP_CHECK(hipStreamWaitEvent(H, e_sdone, 0));
+            EdgeSig rwait;
+            if (rest_edge_prev.word) {
+                if (gemm_may_wait_in_kernel(c, n - u0, u1 - u0)) rwait = rest_edge_prev;
+                else GPT_TRY(launch_wait_flag(P, rest_edge_prev));
             }
-            if (use_flags) {
-                if (!panel_awaited) GPT_TRY(stream_wait_flag(S, panel_edge));
-            } else {
-                GPT_HIP_CHECK(hipStreamWaitEvent(S, e_panel, 0));
-            }
-            awaited = c0 + w;        // (panel_awaited: the previous panel's last launch on S waited for it at its end)
-            // Tail wait: the last launch of this panel on the main stream ends only when the NEXT panel's flag is up, so the
-            // next panel's launch follows it without a wait kernel in between (the flag's value is fixed here, one panel early).
-            EdgeSig tail;
-            // NOT while the launches are being timed (option profile_gemm: bench.py's roofline events): a launch that waits at its
-            // end reports its wait as its own duration -- in the transition from the update-bound head to the chain-bound end,
-            // where the main stream does wait for the panel stream, 20-50 us of a 60-110-us launch.  A timed evaluation keeps the
-            // wait in a kernel of its own, like tail_wait = 0, and its launches' durations are the GEMM's.
-            const bool tail_here = c->tail_wait != 0 && !c->prof_gemm;
-            if (use_flags && tail_here && split == n && k + 1 < widths.size() && c0 + w + wn + ext_k1 < n) {
-                tail.word = c->d_edge;
-                tail.value = ++c->edge_seq;
-                tail = with_err(c, tail);
-            }
-            if (split < n) {
-                if (use_flags) GPT_TRY(stream_wait_flag(H, panel_edge));
-                else GPT_HIP_CHECK(hipStreamWaitEvent(H, e_panel, 0));
-                GPT_TRY(gemm_nt(c, H, n - split, n - split, w, -1.0, A + split * lda + c0, lda, A + split * lda + c0,
-                                lda, 1.0, A + split * lda + split, lda, 1, e_help));
-            }
-            bool waited = false;
-            if (e_help_prev && u1 > s_prev) {
-                GPT_HIP_CHECK(hipStreamWaitEvent(S, e_help_prev, 0));
-                waited = true;
-            }
-            // Update-bound head (option purg_rows): the PANEL stream applies panel k to the columns panel k+1 touches
-            // ("urgent") itself, right behind the panel -- no event round trip panel -> main -> panel on the chain and
-            // one launch less on the main stream, which sets the pace there.  Both streams read-modify-write those
-            // columns (the main stream's rest of panel k-1 covers them too), so the panel stream waits for that rest.
-            // (with flag edges and merged launches the main stream has one launch per panel anyway and the urgent tiles run at
-            // the large launch's rate: the panel stream's own urgent update no longer pays -- 4.444 against 4.492 ms at N = 8192)
-            const int64_t purg_eff = (use_flags && c->merge_urgent) ? c->purg_rows_flags : c->purg_rows;
-            const bool p_urgent = !H && purg_eff > 0 && n - c0 > purg_eff && !c->use_graph && u1 < n;
-            if (p_urgent) {
-                // (edge_flags >= 2: "the rest of panel k-1 is done" as a flag edge as well -- no stop event on the main
-                // stream's large launches, which set the pace here; the whole C of that launch is then written through)
-                const bool rest_flag = use_flags && c->edge_flags >= 2;
-                EdgeSig rwait;
-                if (e_rest_prev) GPT_HIP_CHECK(hipStreamWaitEvent(P, e_rest_prev, 0));
-                if (!e_rest_prev && !rest_edge_prev.word) {
-                    // First update the PANEL stream applies beyond the head columns: whatever the main stream still has in
-                    // flight on those columns -- the rest of the K build of this evaluation -- must be through.  (Found with the
-                    // `ramp` option, whose 128-wide first panel is done before the K build is: "8064-th leading minor not
-                    // positive definite"; with 384-wide panels the build happened to finish first.)
-                    hipEvent_t e_k = get_event(c, 9 + 5 * widths.size());
-                    if (!e_k) return GPT_E_HIP;
-                    GPT_HIP_CHECK(hipEventRecord(e_k, S));
-                    GPT_HIP_CHECK(hipStreamWaitEvent(P, e_k, 0));
-                }
-                if (rest_edge_prev.word) {
-                    if (gemm_may_wait_in_kernel(c, n - u0, u1 - u0)) rwait = rest_edge_prev;
-                    else GPT_TRY(stream_wait_flag(P, rest_edge_prev));
-                }
-                GPT_TRY(gemm_nt(c, P, n - u0, u1 - u0, w, -1.0, A + u0 * lda + c0, lda, A + u0 * lda + c0, lda, 1.0,
-                                A + u0 * lda + u0, lda, 1, nullptr, EdgeSig(), rwait));
-                e_cu_prev = nullptr;
-                rest_edge_prev = EdgeSig();
-                if (rest_flag) {
-                    EdgeSig re;
-                    re.word = c->d_edge + 32;
-                    re.value = ++c->edge_seq;
-                    re = with_err(c, re);
-                    GPT_TRY(gemm_nt(c, S, n - u1, n - u1, w, -1.0, A + u1 * lda + c0, lda, A + u1 * lda + c0, lda, 1.0,
-                                    A + u1 * lda + u1, lda, 1, nullptr, re));
-                    rest_edge_prev = re;
-                    e_rest_prev = nullptr;
-                    c0 += w;
-                    continue;
-                }
-                hipEvent_t e_rest = get_event(c, 10 + 5 * widths.size() + k);
-                if (!e_rest) return GPT_E_HIP;
-                GPT_TRY(gemm_nt(c, S, n - u1, n - u1, w, -1.0, A + u1 * lda + c0, lda, A + u1 * lda + c0, lda, 1.0,
-                                A + u1 * lda + u1, lda, 1, e_rest));
-                e_rest_prev = e_rest;
-                c0 += w;
-                continue;
-            }
+            GPT_TRY(update(P, c0, w, u0, u1, nullptr, EdgeSig(), rwait));
             e_rest_prev = nullptr;
             rest_edge_prev = EdgeSig();
-            if (use_flags) {
-                EdgeSig cu_edge;
-                cu_edge.word = c->d_edge + 16;
-                cu_edge.value = ++c->edge_seq;
-                cu_edge = with_err(c, cu_edge);
-                // Urgent + rest as ONE launch (option merge_urgent) while the update is large enough for an order table: the
-                // tiles of the urgent columns come first on every XCD, write through and raise the flag when THEY are done;
-                // the rest follows in the same launch -- one drain and one ramp-up less per panel on the main stream, and
-                // the small urgent launch (30 TFLOP/s on its own) runs at the large launch's rate.
-                // (with a helper slice the merged launch is the lower trapezoid of the columns [u0, split))
-                const int64_t mtn = (split - u0 + 63) / 64, mtm = (n - u0 + 63) / 64;
-                const int64_t nt64m = mtn * (mtn + 1) / 2 + (mtm - mtn) * mtn;
-                if (c->merge_urgent && u1 < split && nt64m >= c->merge_min_tiles && (c->tile == 0 || c->tile == 64) && (u1 - u0) % 64 == 0) {
-                    if (e_help_prev && !waited) GPT_HIP_CHECK(hipStreamWaitEvent(S, e_help_prev, 0));
-                    e_help_prev = nullptr;
-                    GPT_TRY(gemm_nt(c, S, n - u0, split - u0, w, -1.0, A + u0 * lda + c0, lda, A + u0 * lda + c0, lda, 1.0,
-                                    A + u0 * lda + u0, lda, 1, nullptr, cu_edge, EdgeSig(), u1 - u0, tail));
-                    next_panel_edge = tail;
-                    cu_edge_prev = cu_edge;
-                    if (split < n) {
-                        s_prev = split;
-                        e_help_prev = e_help;
-                    }
-                    c0 += w;
-                    continue;
-                }
-                GPT_TRY(gemm_nt(c, S, n - u0, u1 - u0, w, -1.0, A + u0 * lda + c0, lda, A + u0 * lda + c0, lda, 1.0,
-                                A + u0 * lda + u0, lda, 1, nullptr, cu_edge));
-                cu_edge_prev = cu_edge;
+            if (rest_flag) {
+                rest_edge_prev = new_edge(c, 32);
+                GPT_TRY(update(S, c0, w, u1, n, nullptr, rest_edge_prev));
             } else {
-                GPT_TRY(gemm_nt(c, S, n - u0, u1 - u0, w, -1.0, A + u0 * lda + c0, lda, A + u0 * lda + c0, lda, 1.0,
-                                A + u0 * lda + u0, lda, 1, e_cu));
-                e_cu_prev = e_cu;
+                e_rest_prev = get_event(c, 10 + 5 * np + k);
+                if (!e_rest_prev) return GPT_E_HIP;
+                GPT_TRY(update(S, c0, w, u1, n, e_rest_prev));
             }
-            if (u1 < n) {
-                if (e_help_prev && !waited) GPT_HIP_CHECK(hipStreamWaitEvent(S, e_help_prev, 0));
-                e_help_prev = nullptr;
-                if (!H && c->defer_rows > 0 && n - c0 <= c->defer_rows && k + 1 < widths.size() && !c->use_graph) {
-                    pend = PendingRest{true, c0, w, u1, split, S};
-                } else {
-                    // (tail wait on the 64x64 / 32x32 kernels only; an event may not ride on the same launch)
-                    const bool tl = tail.word && (c->tile == 0 || c->tile == 64);
-                    GPT_TRY(gemm_nt(c, S, n - u1, split - u1, w, -1.0, A + u1 * lda + c0, lda, A + u1 * lda + c0, lda, 1.0,
-                                    A + u1 * lda + u1, lda, 1, nullptr, EdgeSig(), EdgeSig(), 0, tl ? tail : EdgeSig()));
-                    if (tl) next_panel_edge = tail;
-                }
+            continue;
+        }
+        e_rest_prev = nullptr;
+        rest_edge_prev = EdgeSig();
+        if (use_flags) {
+            cu_edge_prev = new_edge(c, 16);
+            // (2) urgent + rest as ONE launch (option merge_urgent) while the update is large enough for an order table: the
+            // tiles of the urgent columns come first on every XCD, write through and raise the flag when THEY are done;
+            // the rest follows in the same launch -- one drain and one ramp-up less per panel on the main stream, and
+            // the small urgent launch (30 TFLOP/s on its own) runs at the large launch's rate.
+            // (with a helper slice the merged launch is the lower trapezoid of the columns [u0, split))
+            const int64_t mtn = (split - u0 + 63) / 64, mtm = (n - u0 + 63) / 64;
+            const int64_t nt64m = mtn * (mtn + 1) / 2 + (mtm - mtn) * mtn;
+            if (c->merge_urgent && u1 < split && nt64m >= GPT_MERGE_MIN_TILES && (u1 - u0) % 64 == 0) {
+                GPT_TRY(wait_help_prev());
+                GPT_TRY(update(S, c0, w, u0, split, nullptr, cu_edge_prev, EdgeSig(), u1 - u0, tail));
+                next_panel_edge = tail;
                 if (split < n) {
                     s_prev = split;
                     e_help_prev = e_help;
                 }
+                continue;
+            }
+            GPT_TRY(update(S, c0, w, u0, u1, nullptr, cu_edge_prev));
+        } else {
+            GPT_TRY(update(S, c0, w, u0, u1, e_cu));
+            e_cu_prev = e_cu;
+        }
+        // (3) urgent, then the rest -- at once, or (defer_rows) behind the next panel's first update
+        if (u1 < n) {
+            GPT_TRY(wait_help_prev());
+            if (defer_rows > 0 && n - c0 <= defer_rows && k + 1 < np) {
+                pend = PendingRest{true, c0, w, u1, split};
+            } else {
+                // (an event may not ride on the launch that carries the tail wait)
+                GPT_TRY(update(S, c0, w, u1, split, nullptr, EdgeSig(), EdgeSig(), 0, tail));
+                next_panel_edge = tail;
+            }
+            if (split < n) {
+                s_prev = split;
+                e_help_prev = e_help;
             }
         }
-        c0 += w;
     }
-    if (pend.on) GPT_TRY(launch_rest(pend));
-    c->pad_now = 0;
+    if (pend.on) GPT_TRY(update(S, pend.c0, pend.w, pend.u1, pend.split));
     // Eager alpha: the inverses of the 512 x 512 diagonal blocks left of the last panel are built now, on the main stream, which has
     // nothing else to do while the panel stream factors the last panel (api_solve.inc; the blocks right of them follow behind the
-    // factorisation) -- as far as they are FINAL on S0, i.e. left of the last panel S0 has WAITED for.  That is usually the
+    // factorisation) -- as far as they are FINAL on S, i.e. left of the last panel S has WAITED for.  That is usually the
     // panel in front of the last one, but a panel whose update reaches no column (c0 + w + EXT >= n: the one in front of a
     // 128-wide last panel) is never waited for, and reading its columns would race the panel stream (ADVICE r6).
-    // (on the early stream, S0 has seen its waits only if the loop switched back to S0)
     // The last helper slice (e_help_prev, joined below) writes nothing left of `awaited` by then: every column there belongs to
     // a panel S has waited for, and a panel is factored only behind every update of its columns, the helper's included (S waits
     // for a helper slice before its next urgent update touches the slice's columns, and the panel stream waits for that update).
-    if (c->want_early_binv && A == c->dA && invd == c->d_invd && widths.size() >= 2)
-        GPT_TRY(enqueue_early_block_inverses(c, S0, n - widths.back(), S_cur == S0 ? awaited : 0));
-    if (c->pad_leaf_deferred) {
-        // The pad leaf (gpt_ctx defer_pad_leaf): behind the last real leaf, on the main stream -- the held-back rank-128 updates of
-        // the pad block in leaf order (the order the panel stream would have applied them in: same bits), then its pivot block.
-        hipEvent_t e_real = get_event(c, 12 + 6 * widths.size());
+    if (req.want_early_binv && A == c->dA && invd == c->d_invd && np >= 2)
+        GPT_TRY(enqueue_early_block_inverses(c, S, n - widths.back(), awaited));
+    if (ps.pad_leaf_deferred) {
+        // The pad leaf (PotrfRequest::defer_pad_leaf): behind the last real leaf, on the main stream -- the held-back rank-128 updates
+        // of the pad block in leaf order (the order the panel stream would have applied them in: same bits), then its pivot block.
+        hipEvent_t e_real = get_event(c, 12 + 6 * np);
         if (!e_real) return GPT_E_HIP;
         GPT_HIP_CHECK(hipEventRecord(e_real, P));
-        GPT_HIP_CHECK(hipStreamWaitEvent(S0, e_real, 0));
+        GPT_HIP_CHECK(hipStreamWaitEvent(S, e_real, 0));
         const int64_t pc = n - 128;
-        for (const int64_t lc : c->pad_upd_lc) {
-            GPT_TRY(gemm_nt(c, S0, 128, 128, 128, -1.0, A + pc * lda + lc, lda, A + pc * lda + lc, lda, 1.0, A + pc * lda + pc, lda, 1));
-        }
-        GPT_TRY(launch_potf2_diag(S0, A + pc * lda + pc, lda, invd + (pc / 128) * GPT_WS_BLOCK, info, pc));
+        for (const int64_t lc : ps.pad_upd_lc)
+            GPT_TRY(gemm_nt(c, S, 128, 128, 128, -1.0, A + pc * lda + lc, lda, A + pc * lda + lc, lda, 1.0, A + pc * lda + pc, lda, 1));
+        GPT_TRY(launch_potf2_diag(S, A + pc * lda + pc, lda, invd + (pc / 128) * GPT_WS_BLOCK, info, pc));
+        res->pad_leaf_deferred = true;
     }
     if (e_help_prev) GPT_HIP_CHECK(hipStreamWaitEvent(S, e_help_prev, 0));
-    if (use_early && S_cur != S0) {
-        hipEvent_t e_sw = get_event(c, 3 + 4 * widths.size());
-        if (!e_sw) return GPT_E_HIP;
-        GPT_HIP_CHECK(hipEventRecord(e_sw, S_cur));
-        GPT_HIP_CHECK(hipStreamWaitEvent(S0, e_sw, 0));
-    }
-    S = S0;
-    if (c->defer_join && !c->use_graph) {
+    if (req.defer_join && !graph) {
         // (the caller continues on the panel stream -- the last leaf runs there -- and joins the streams itself)
-        c->tail_stream = P;
+        res->tail_stream = P;
         return GPT_OK;
     }
     hipEvent_t e_end = get_event(c, 1);
@@ -759,9 +687,13 @@ static int potrf_enqueue(gpt_ctx *c, int64_t n, double *A, int64_t lda, double *
     return GPT_OK;
 }
 
-static int potrf_run(gpt_ctx *c, int64_t n, double *A, int64_t lda, double *invd, int32_t *info)
+static int potrf_run(gpt_ctx *c, int64_t n, double *A, int64_t lda, double *invd, int32_t *info,
+                     const PotrfRequest &req = PotrfRequest(), PotrfResult *res = nullptr)
 {
-    if (!c->use_graph) return potrf_enqueue(c, n, A, lda, invd, info);
+    PotrfResult unused;
+    if (!res) res = &unused;
+    *res = PotrfResult();
+    if (!c->use_graph) return potrf_enqueue(c, n, A, lda, invd, info, req, res);
     if (c->gexec && (c->g_n != n || c->g_nb != c->nb_outer || c->g_la != c->lookahead || c->g_A != A)) {
         hipGraphExecDestroy(c->gexec);
         c->gexec = nullptr;
@@ -769,7 +701,7 @@ static int potrf_run(gpt_ctx *c, int64_t n, double *A, int64_t lda, double *invd
     if (!c->gexec) {
         hipGraph_t graph = nullptr;
         GPT_HIP_CHECK(hipStreamBeginCapture(c->stream, hipStreamCaptureModeRelaxed));
-        int rc = potrf_enqueue(c, n, A, lda, invd, info);
+        int rc = potrf_enqueue(c, n, A, lda, invd, info, req, res);
         hipError_t e = hipStreamEndCapture(c->stream, &graph);
         if (rc != GPT_OK) {
             if (graph) hipGraphDestroy(graph);

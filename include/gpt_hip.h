@@ -94,8 +94,8 @@ int gpt_ctx_destroy(gpt_ctx *ctx);
  *   "lookahead"    0/1: factor panel k+1 on the high-priority panel stream while the main stream applies panel k
  *   "purg_rows"    while more rows than this remain the panel stream applies panel k to the columns of panel k+1 itself
  *                  (6144; 0 = the main stream always does)
- *   "panel_prio"   wave priority (0..3) of the panel stream's GEMM main loops (2); "gemm_prio" >= 0 forces one priority
- *                  for every GEMM of the context (the panel-side context of gptools_amd/dist.py)
+ *   "gemm_prio"    >= 0 forces one wave priority (0..3) for every GEMM main loop of the context (the panel-side context of
+ *                  gptools_amd/dist.py); -1 (default): 2 on the panel stream, 0 elsewhere
  *   "fuse_trsm"    panels with at most this many rows under a leaf use the fused diagonal-block + TRSM kernel (8192)
  *   "fuse_rows64"  fused leaves with at most this many rows under them run 64-row consumer workgroups, one substitution
  *                  strip per SIMD (2048 = what fits the CUs reserved for the panel stream; 0 = always 128-row workgroups)
@@ -103,16 +103,13 @@ int gpt_ctx_destroy(gpt_ctx *ctx);
  *                  waves per CU -- every strip wave requests the same fragments of the diagonal block and a CU turns out ~32 bytes of
  *                  vector-load requests per cycle (round 5, bit-identical: N = 4096 1.158 -> 1.152 ms, N = 8192 4.346 -> 4.31 ms)
  *   "merge_urgent" 1 (default, with edge_flags): the two trailing updates per panel are one launch with a partial edge flag
+ *                  (while it has at least 512 64x64 tiles: it needs an order table); "purg_rows" is then not applied
  *   "edge_flags"   1 (default): the per-panel dependencies of the look-ahead are flag words in device memory (last workgroup
  *                  of the producer raises it; a bounded in-kernel wait or a one-wave wait kernel on the consumer side)
  *                  instead of events; 0: events.  Used by an evaluation only while it is the only one in flight in the
  *                  process (idle contexts do not count; see gpt_concurrency_hint) on a context that owns its streams; off by
  *                  itself under rocprofv3 counter collection, for n > 12288, and for the rest of the process once a wait has
  *                  timed out (250 ms: the evaluation is then repeated on events)
- *   "head_wait_wgs" the first leaf of a factorisation waits for the K build's head columns inside its own kernel while its launch has
- *                  at most this many workgroups (33 = what fits the reserved CUs), else a one-wave wait kernel in front of it
- *   "merge_min_tiles" smallest merged trailing update, in 64x64 tiles (512: the launch needs an order table)
- *   "purg_rows_flags" "purg_rows" while flag edges and merged launches are in use (0: never -- measured)
  *   "tail_wait"    1 (default since round 6): the main stream's last launch of a panel awaits the NEXT panel's flag at its end instead of
  *                  a wait kernel in front of the next launch (C3 -19 us, C2 -15 us); not while "profile_gemm" times the launches (a
  *                  launch that waits at its end reports the wait as its duration); 0: always the wait kernel
@@ -144,11 +141,16 @@ int gpt_ctx_destroy(gpt_ctx *ctx);
  *   "debug_poison" 0/1 (test aid): gpt_ll_grad fills its scratch matrices with NaN before use
  *   "edge_test_stall" 1 (test aid): the next evaluation's first flag is withheld once, so that the bounded wait, the repeat on
  *                  event edges and the switch of the process to event edges can be tested
- *   measured and off by default: "ramp", "inner", "inner_rows", "defer_rows", "late_rows",
- *   "early_rows", "nb_early", "nb_switch_rows", "late_pad", "late_pad_rows".
+ *   measured and off by default: "ramp", "inner" (1: left-looking panels, 2: once at most 4608 rows
+ *   remain), "defer_rows", "nb_early", "nb_switch_rows".
  *   Removed in round 6 with the code behind them (each lost its A/B twice; NOTES_r04.md / NOTES_r05.md have the numbers, the
  *   history up to round 5's last commit the sources): "fuse_upd" / "fuse_upd_rows", "pair_rows", "leaf256", "tile" = 65 / 128 / 129,
- *   the environment switches GPT_GEMM_LOOP and GPT_GEMM_MIXED.  gpt_ctx_set_option refuses unknown keys.
+ *   the environment switches GPT_GEMM_LOOP and GPT_GEMM_MIXED.
+ *   Removed after round 6, frozen at their defaults because nothing set them (NOTES_r02.md, NOTES_r04.md, NOTES_r06.md and
+ *   DESIGN.md section 4 have the A/B numbers): "early_rows", "late_rows", "late_pad", "late_pad_rows" (off), "panel_prio" (2),
+ *   "head_wait_wgs" (33), "purg_rows_flags" (0), "merge_min_tiles" (512), "inner_rows" (4608), and the environment switches
+ *   GPT_LATE_STREAM, GPT_RESERVE_EARLY, GPT_EDGE_WAITVALUE and GPT_EDGE_UNBOUNDED (every flag wait is bounded, always).
+ *   gpt_ctx_set_option refuses unknown keys.
  * Environment: GPT_RESERVE_CUS (CUs the main stream leaves to the panel stream, default 32), GPT_TILE_ORDER
  * ("rows,cols,mode": supertile shape and deal of the GEMM's XCD-aware tile order, default 64,8,1), GPT_GRAD_TIMING,
  * GPT_EDGE_FLAGS=0 (event edges only: set it for jobs that share one GPU between several processes), GPT_GEMM_SMALL (64x64-tile count under which a GEMM launch uses 32x32 tiles, 512),

@@ -953,7 +953,8 @@ def test_schedule_options_agree_with_default(ctx, oracle):
             ctx.set_option(k_, d_)
         ctx.set_option("profile_gemm", 0)
     # options that were removed with the code behind them (round 6) are refused, not ignored
-    for gone in ("fuse_upd", "pair_rows", "leaf256"):
+    for gone in ("fuse_upd", "pair_rows", "leaf256", "early_rows", "late_rows", "late_pad", "late_pad_rows", "panel_prio",
+                 "head_wait_wgs", "purg_rows_flags", "merge_min_tiles", "inner_rows"):
         with pytest.raises(Exception):
             ctx.set_option(gone, 1)
     with pytest.raises(Exception):
