@@ -18,6 +18,7 @@ GPT_E_ARG, GPT_E_VALUE, GPT_E_NOTIMPL, GPT_E_HIP, GPT_E_NOMEM, GPT_E_STATE = -1,
 KERNEL_SE, KERNEL_M52, KERNEL_DIAGNOISE, KERNEL_ZERO, KERNEL_RQ, KERNEL_MATERN, KERNEL_PRODUCT = 0, 1, 2, 3, 4, 5, 6
 KERNEL_GIBBS_TANH, KERNEL_GIBBS_DTANH = 7, 8
 MAX_DIM = 16
+WARP_LINEAR, WARP_BETA, WARP_MAX_LAYERS = 1, 2, 4
 
 _dp = C.POINTER(C.c_double)
 _ip = C.POINTER(C.c_int32)
@@ -42,6 +43,8 @@ SIGNATURES = {
     "gpt_fit_terms": (C.c_int, [_vp, C.c_int, _ip, _ip, _dp, _ip, _ip, C.c_double, _dp, _dp, C.c_double, _dp, _dp]),
     "gpt_set_data": (C.c_int, [_vp, _dp, _ip, _i64, C.c_int]),
     "gpt_set_T": (C.c_int, [_vp, _dp, _i64]),
+    "gpt_set_warp": (C.c_int, [_vp, C.c_int, _ip, _dp]),
+    "gpt_set_warp_batch": (C.c_int, [_vp, C.c_int, C.c_int, _ip, _dp]),
     "gpt_fit": (C.c_int, [_vp, C.c_int, _dp, C.c_int, C.c_double, _dp, _dp, C.c_double, _dp, _dp]),
     "gpt_fit_sum": (C.c_int, [_vp, C.c_int, _ip, _dp, _ip, C.c_double, _dp, _dp, C.c_double, _dp, _dp]),
     "gpt_fit_batch": (C.c_int, [_vp, C.c_int, C.c_int, _dp, C.c_int, _dp, _dp, _dp, C.c_double, _dp, _dp, _ip]),
@@ -244,6 +247,7 @@ class Context(object):
         self._h = h
         self._lib = lib
         self.device = int(device)
+        self._warp_key = None               # the layers the library holds (set_warp); None: no warp
 
     def close(self):
         if getattr(self, "_h", None):
@@ -350,7 +354,45 @@ class Context(object):
     # ---- fit / state ---------------------------------------------------------------------------
     def set_data(self, X, n):
         X, n = f64(X), i32(n)
+        self._warp_key = None               # (gpt_set_data drops the layers)
+        self._num_dim = X.shape[1]
         check(self._lib.gpt_set_data(self.handle, dptr(X), iptr(n), X.shape[0], X.shape[1]))
+
+    def set_warp(self, layers):
+        """gpt_set_warp: ``layers`` is a list of ``(type, params)`` (``WARP_LINEAR`` / ``WARP_BETA``, 2 D parameters each), the
+        first applied first; an empty list (or ``None``) clears the warp.  Every call that changes the layers drops the resident
+        factorisation; a call with the layers the library already holds is a no-op, so that reading ``K`` or predicting after a
+        fit leaves the factor alone."""
+        layers = [(int(t), f64(p).ravel()) for t, p in (layers or [])]
+        key = tuple((t, p.tobytes()) for t, p in layers) or None
+        if key == self._warp_key:
+            return
+        self._warp_key = None
+        if not layers:
+            check(self._lib.gpt_set_warp(self.handle, 0, None, None))
+            return
+        types = i32(np.asarray([t for t, _ in layers]))
+        flat = f64(np.concatenate([p for _, p in layers]))
+        if any(p.size != 2 * getattr(self, "_num_dim", -1) for _, p in layers):
+            raise ValueError("set_warp needs set_data first, and every layer takes 2 * num_dim parameters")
+        check(self._lib.gpt_set_warp(self.handle, len(layers), iptr(types), dptr(flat)))
+        self._warp_key = key
+
+    def set_warp_batch(self, layers_list):
+        """gpt_set_warp_batch: element b's layers ``layers_list[b]`` (as :meth:`set_warp` takes them; the same types in every
+        element) for the next ``fit_batch*`` of ``len(layers_list)`` elements, which consumes them."""
+        types = [int(t) for t, _ in layers_list[0]]
+        D = getattr(self, "_num_dim", -1)
+        rows = []
+        for layers in layers_list:
+            if [int(t) for t, _ in layers] != types:
+                raise ValueError("set_warp_batch: every element takes the same layer types")
+            ps = [f64(p).ravel() for _, p in layers]
+            if any(p.size != 2 * D for p in ps):
+                raise ValueError("set_warp_batch needs set_data first, and every layer takes 2 * num_dim parameters")
+            rows.append(np.concatenate(ps) if ps else np.zeros(0))
+        flat = f64(np.array(rows))
+        check(self._lib.gpt_set_warp_batch(self.handle, len(layers_list), len(types), iptr(i32(np.asarray(types))), dptr(flat)))
 
     def set_T(self, T):
         """Resident linear transform (Ny, N) for the data set given to set_data; ``None`` removes it."""

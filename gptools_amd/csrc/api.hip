@@ -16,6 +16,7 @@
 #include <mutex>
 #include <vector>
 #include "common.hpp"
+#include "warp.hpp"
 
 // ------------------------------------------------------------------------------------------------
 static thread_local char g_err[512] = "";
@@ -47,7 +48,7 @@ struct DevBuf {
 enum { SLOT_XI = 0, SLOT_XJ, SLOT_NI, SLOT_NJ, SLOT_OUT, SLOT_KST, SLOT_KSS, SLOT_XS, SLOT_NS, SLOT_VEC, SLOT_VEC2,
        SLOT_RHS, SLOT_LOW, SLOT_KFULL, SLOT_TK, SLOT_ZERO, SLOT_UINV, SLOT_WINV, SLOT_GPART, SLOT_BINV, SLOT_BTMP,
        SLOT_BINV2, SLOT_BINV3, SLOT_BINV3U, SLOT_BINVU, SLOT_BATCH_A, SLOT_BATCH_WS, SLOT_BATCH_MISC, SLOT_SPLITK,
-       SLOT_PB_V, SLOT_PB_COV, SLOT_PB_MISC, SLOT_COUNT };
+       SLOT_PB_V, SLOT_PB_COV, SLOT_PB_MISC, SLOT_XSW, SLOT_SS, SLOT_SI, SLOT_SJ, SLOT_WB_X, SLOT_WB_S, SLOT_WB_P, SLOT_COUNT };
 
 struct gpt_ctx {
     int device = 0;
@@ -80,6 +81,7 @@ struct gpt_ctx {
     int lookahead = 1;
     int use_graph = 0;
     long n_maxsum = 0;                 // largest row sum of the training derivative orders (gpt_set_data)
+    long n_maxord = 0;                 // largest single derivative order of the training points (gpt_set_data)
     int timing = 0;
     int tile = 0;
     int gemm_pad = 1024;
@@ -106,6 +108,14 @@ struct gpt_ctx {
     int64_t Ny = 0, NxP = 0;
     double *dX = nullptr;
     int32_t *dn = nullptr;
+    // input warp (gpt_set_warp): while warp.nlayers > 0 the builders read dXw (Nx x D warped points) in place of dX and take
+    // the slope factors dS (Nx) on tiles with derivative orders
+    WarpLayers warp = WarpLayers();
+    double *dXw = nullptr, *dS = nullptr;
+    // a batch's warps (gpt_set_warp_batch): SLOT_WB_X / SLOT_WB_S hold warpb_nbatch x Nx x D warped points / warpb_nbatch x Nx slope
+    // factors for the next gpt_fit_batch* of that many elements, which consumes them (warpb_nbatch back to 0)
+    int warpb_nbatch = 0;
+    bool rb_warped = false;            // the resident batch was fitted with warps (gpt_predict_batch refuses it)
     // factorisation state
     int64_t NP = 0;            // padded order (multiple of 128, > N)
     double *dA = nullptr;      // NP x NP, row-major, lower triangle meaningful

@@ -56,6 +56,14 @@ static int fit_batch_impl(gpt_ctx *c, int nbatch, int nterms, const int *kernel_
                           double diag_add, double *ll_data_out, double *logdet_half_out, int32_t *info_out)
 {
     CTX_ENTER(c);
+    // warps: a batch's elements have their own (gpt_set_warp_batch, consumed here); the context's single layers are not a batch's
+    const int wb = c->warpb_nbatch;
+    c->warpb_nbatch = 0;
+    if (wb == 0) GPT_TRY(refuse_warp(c, "gpt_fit_batch without gpt_set_warp_batch"));
+    if (wb != 0 && wb != nbatch) {
+        gpt_set_error("gpt_fit_batch: %d elements, but gpt_set_warp_batch set the warps of %d", nbatch, wb);
+        return GPT_E_ARG;
+    }
     if (!c->dX) {
         gpt_set_error("gpt_fit_batch: call gpt_set_data first");
         return GPT_E_STATE;
@@ -140,6 +148,15 @@ static int fit_batch_impl(gpt_ctx *c, int nbatch, int nterms, const int *kernel_
     int32_t *dinfo = reinterpret_cast<int32_t *>(dmisc + d_off_info);
     const KParams *dkp = reinterpret_cast<const KParams *>(dmisc + d_off_kp);
     const KParams *dkp2 = any_prod ? dkp + (size_t)nterms * nbatch : nullptr;
+    // a warped batch: element b's points at bX + b * xstr, its slope factors at bS + b * sstr; else the shared resident points
+    const double *bX = c->dX, *bS = nullptr;
+    int64_t xstr = 0, sstr = 0;
+    if (wb) {
+        bX = (const double *)c->slots[SLOT_WB_X].p;
+        bS = (const double *)c->slots[SLOT_WB_S].p;
+        xstr = Nx * c->D;
+        sstr = Nx;
+    }
     EvalScope scope(c, true);                // (in flight like an evaluation for the flag-edge accounting; has no flag edges)
     // everything on the panel stream: unmasked (all 256 CUs), the main stream is idle here
     hipStream_t st = c->panel_stream;
@@ -159,8 +176,9 @@ static int fit_batch_impl(gpt_ctx *c, int nbatch, int nterms, const int *kernel_
         GPT_HIP_CHECK(hipMemsetAsync(dzero, 0, (size_t)Nx * sizeof(double), st));
         if (NxP > Nx) GPT_HIP_CHECK(hipMemsetAsync(dKf, 0, (size_t)nbatch * kfull * sizeof(double), st));
         for (int t = 0; t < nterms; t++)
-            GPT_TRY(launch_kbuild_batch(st, kernel_ids[t], c->D, dkp + (size_t)t * nbatch, dmisc + d_off_nv, nbatch, c->dX, c->dn, Nx,
-                                        t + 1 == nterms ? dzero : nullptr, 0.0, dKf, NxP, (int64_t)kfull, t > 0 ? 1 : 0, 1, term_kp2(t)));
+            GPT_TRY(launch_kbuild_batch(st, kernel_ids[t], c->D, dkp + (size_t)t * nbatch, dmisc + d_off_nv, nbatch, bX, c->dn, Nx,
+                                        t + 1 == nterms ? dzero : nullptr, 0.0, dKf, NxP, (int64_t)kfull, t > 0 ? 1 : 0, 1, term_kp2(t),
+                                        xstr, bS, sstr));
         GPT_TRY(launch_gemm_nt(st, NyP, NxP, NxP, 1.0, c->dT, NxP, dKf, NxP, 0.0, dTK, NxP, 0, 0, 0, nullptr, nullptr, 0, EdgeSig(),
                                EdgeSig(), 0, nbatch, 0, EdgeSig(), (int64_t)kfull, (int64_t)tk));
         GPT_TRY(launch_gemm_nt(st, NyP, NyP, NxP, 1.0, dTK, NxP, c->dT, NxP, 0.0, dA, NP, 1, 0, 0, nullptr, nullptr, 0, EdgeSig(),
@@ -171,8 +189,8 @@ static int fit_batch_impl(gpt_ctx *c, int nbatch, int nterms, const int *kernel_
         GPT_TRY(launch_batch_pad(st, h, nbatch, dA, NP, bs, N, NP, 1e300, dinfo));
         for (int t = 0; t < nterms; t++)                                    // (as kbuild_terms: later terms accumulate, the last
             GPT_TRY(launch_kbuild_batch(st, kernel_ids[t], c->D, dkp + (size_t)t * nbatch, dmisc + d_off_nv, nbatch,   //  one carries the
-                                        c->dX, c->dn, N, t + 1 == nterms ? dmisc : nullptr, diag_add, dA, NP, bs,     //  diagonal epilogue)
-                                        t > 0 ? 1 : 0, 0, term_kp2(t)));
+                                        bX, c->dn, N, t + 1 == nterms ? dmisc : nullptr, diag_add, dA, NP, bs,     //  diagonal epilogue)
+                                        t > 0 ? 1 : 0, 0, term_kp2(t), xstr, bS, sstr));
     }
     // LEFT-looking over the 128-column leaves: leaf j first receives the update of ALL leaves before it in one launch
     // (k = 128 j; element by element the same sums in the same order as the right-looking rank-128 updates of gpt_fit, whose
@@ -222,6 +240,7 @@ static int fit_batch_impl(gpt_ctx *c, int nbatch, int nterms, const int *kernel_
     c->rb_any_prod = any_prod;
     c->rb_N = N;
     c->rb_gen = c->batch_gen;
+    c->rb_warped = wb != 0;
     return GPT_OK;
 }
 
@@ -247,6 +266,11 @@ extern "C" int gpt_predict_batch(gpt_ctx *c, const double *Xstar, const int32_t 
                                  const int32_t *keep, double *mean_out, double *var_out, double *cov_out, double *cov_sum_out)
 {
     CTX_ENTER(c);
+    GPT_TRY(refuse_warp(c, "gpt_predict_batch"));
+    if (c->rb_warped && c->rb_nbatch > 0 && c->rb_gen == c->batch_gen) {
+        gpt_set_error("gpt_predict_batch is not available for a batch that was fitted with warps (gpt_set_warp_batch)");
+        return GPT_E_NOTIMPL;
+    }
     if (c->rb_nbatch <= 0 || c->rb_gen != c->batch_gen) {
         gpt_set_error("gpt_predict_batch: no batch resident (call gpt_fit_batch* first; gpt_set_data, gpt_set_T, gpt_cov_sample and "
                       "gpt_release_batch_scratch end its residency)");

@@ -99,6 +99,8 @@ extern "C" int gpt_ctx_destroy(gpt_ctx *c)
     free_factor(c);
     if (c->dX) hipFree(c->dX);
     if (c->dn) hipFree(c->dn);
+    if (c->dXw) hipFree(c->dXw);
+    if (c->dS) hipFree(c->dS);
     if (c->dT) hipFree(c->dT);
     for (auto &b : c->slots)
         if (b.p) hipFree(b.p);

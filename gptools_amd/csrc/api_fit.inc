@@ -15,6 +15,11 @@ extern "C" int gpt_set_data(gpt_ctx *c, const double *X, const int32_t *n, int64
     if (c->dn) hipFree(c->dn);
     c->dX = nullptr;
     c->dn = nullptr;
+    if (c->dXw) hipFree(c->dXw);       // warp layers belong to one data set
+    if (c->dS) hipFree(c->dS);
+    c->dXw = c->dS = nullptr;
+    c->warp.nlayers = 0;
+    c->warpb_nbatch = 0;
     GPT_HIP_CHECK(hipMalloc(&c->dX, (size_t)N * D * sizeof(double)));
     GPT_HIP_CHECK(hipMalloc(&c->dn, (size_t)N * D * sizeof(int32_t)));
     GPT_HIP_CHECK(hipMemcpyAsync(c->dX, X, (size_t)N * D * sizeof(double), hipMemcpyHostToDevice, c->stream));
@@ -23,10 +28,13 @@ extern "C" int gpt_set_data(gpt_ctx *c, const double *X, const int32_t *n, int64
     c->N = N;
     c->Nx = N;
     c->D = D;
-    c->n_maxsum = 0;
+    c->n_maxsum = c->n_maxord = 0;
     for (int64_t i = 0; i < N; i++) {
         long sn = 0;
-        for (int d = 0; d < D; d++) sn += n[i * D + d];
+        for (int d = 0; d < D; d++) {
+            sn += n[i * D + d];
+            if (n[i * D + d] > c->n_maxord) c->n_maxord = n[i * D + d];
+        }
         if (sn > c->n_maxsum) c->n_maxsum = sn;
     }
     c->factored = false;
@@ -66,6 +74,115 @@ extern "C" int gpt_set_T(gpt_ctx *c, const double *T, int64_t Ny)
     GPT_HIP_CHECK(hipStreamSynchronize(c->stream));
     c->Ny = Ny;
     c->NxP = NxP;
+    return GPT_OK;
+}
+
+// Input warp (include/gpt_hip.h): the layers by value in the context, the warped resident points and their slope factors next
+// to dX.  Recomputed by every call -- warp parameters are hyperparameters -- on the context's stream, in front of the next build.
+extern "C" int gpt_set_warp(gpt_ctx *c, int nlayers, const int *types, const double *params)
+{
+    CTX_ENTER(c);
+    if (nlayers == 0 && c->warp.nlayers == 0) return GPT_OK;      // nothing set, nothing to clear: the resident factor stays
+    c->factored = false;
+    c->h_alpha_valid = c->alpha_valid = c->binv_valid = c->binv2_valid = c->binv3_valid = false;
+    c->have_kernel = false;
+    c->cov_M = 0;
+    if (nlayers == 0) {
+        c->warp.nlayers = 0;
+        return GPT_OK;
+    }
+    if (!c->dX) {
+        gpt_set_error("gpt_set_warp: call gpt_set_data first");
+        return GPT_E_STATE;
+    }
+    if (nlayers < 0 || nlayers > GPT_WARP_MAX_LAYERS || !types || !params) {
+        gpt_set_error("gpt_set_warp: %d layers (at most %d)", nlayers, GPT_WARP_MAX_LAYERS);
+        return GPT_E_ARG;
+    }
+    WarpLayers wl = WarpLayers();
+    wl.nlayers = nlayers;
+    wl.D = c->D;
+    for (int l = 0; l < nlayers; l++) {
+        if (types[l] != GPT_WARP_LINEAR && types[l] != GPT_WARP_BETA) {
+            gpt_set_error("gpt_set_warp: unknown warp type %d", types[l]);
+            return GPT_E_ARG;
+        }
+        wl.type[l] = types[l];
+        memcpy(wl.p[l], params + (size_t)l * 2 * c->D, (size_t)2 * c->D * sizeof(double));
+    }
+    c->warp.nlayers = 0;                       // (nothing half set should an allocation or the launch fail)
+    if (c->n_maxord > 1) {
+        gpt_set_error("%s", WARP_ORDER_MSG);
+        return GPT_E_VALUE;
+    }
+    if (!c->dXw) GPT_HIP_CHECK(hipMalloc(&c->dXw, (size_t)c->Nx * c->D * sizeof(double)));
+    if (!c->dS) GPT_HIP_CHECK(hipMalloc(&c->dS, (size_t)c->Nx * sizeof(double)));
+    if (c->debug_poison) {                     // (test aid: whatever the warp kernel does not write shows up as NaN)
+        GPT_HIP_CHECK(hipMemsetAsync(c->dXw, 0xff, (size_t)c->Nx * c->D * sizeof(double), c->stream));
+        GPT_HIP_CHECK(hipMemsetAsync(c->dS, 0xff, (size_t)c->Nx * sizeof(double), c->stream));
+    }
+    GPT_TRY(launch_warp_points(c->stream, wl, c->dX, c->dn, c->Nx, c->dXw, c->dS));
+    c->warp = wl;
+    return GPT_OK;
+}
+
+// Per-element warps of a batch (include/gpt_hip.h): one launch fills nbatch x Nx x D warped points and nbatch x Nx slope factors;
+// the next gpt_fit_batch* of nbatch elements builds element b from its own.  The resident single factorisation is untouched.
+extern "C" int gpt_set_warp_batch(gpt_ctx *c, int nbatch, int nlayers, const int *types, const double *params)
+{
+    CTX_ENTER(c);
+    c->warpb_nbatch = 0;
+    if (nlayers == 0 || nbatch == 0) return GPT_OK;
+    if (!c->dX) {
+        gpt_set_error("gpt_set_warp_batch: call gpt_set_data first");
+        return GPT_E_STATE;
+    }
+    if (nbatch < 0 || nbatch > 65535 || nlayers < 0 || nlayers > GPT_WARP_MAX_LAYERS || !types || !params) {
+        gpt_set_error("gpt_set_warp_batch: %d elements, %d layers (at most %d)", nbatch, nlayers, GPT_WARP_MAX_LAYERS);
+        return GPT_E_ARG;
+    }
+    WarpLayers wl = WarpLayers();
+    wl.nlayers = nlayers;
+    wl.D = c->D;
+    for (int l = 0; l < nlayers; l++) {
+        if (types[l] != GPT_WARP_LINEAR && types[l] != GPT_WARP_BETA) {
+            gpt_set_error("gpt_set_warp_batch: unknown warp type %d", types[l]);
+            return GPT_E_ARG;
+        }
+        wl.type[l] = types[l];
+    }
+    if (c->n_maxord > 1) {
+        gpt_set_error("%s", WARP_ORDER_MSG);
+        return GPT_E_VALUE;
+    }
+    const size_t np = (size_t)nbatch * nlayers * 2 * c->D, nx = (size_t)nbatch * c->Nx * c->D, ns = (size_t)nbatch * c->Nx;
+    double *dP, *dXb, *dSb;
+    GPT_TRY(ensure(c, SLOT_WB_P, np * sizeof(double), (void **)&dP));
+    GPT_TRY(ensure(c, SLOT_WB_X, nx * sizeof(double), (void **)&dXb));
+    GPT_TRY(ensure(c, SLOT_WB_S, ns * sizeof(double), (void **)&dSb));
+    hipStream_t st = c->stream;
+    // (the caller's array is pageable: the copy has left it when the call returns)
+    GPT_HIP_CHECK(hipMemcpyAsync(dP, params, np * sizeof(double), hipMemcpyHostToDevice, st));
+    if (c->debug_poison) {
+        GPT_HIP_CHECK(hipMemsetAsync(dXb, 0xff, nx * sizeof(double), st));
+        GPT_HIP_CHECK(hipMemsetAsync(dSb, 0xff, ns * sizeof(double), st));
+    }
+    GPT_TRY(launch_warp_points_batch(st, wl, dP, nbatch, c->dX, c->dn, c->Nx, dXb, dSb));
+    GPT_HIP_CHECK(hipStreamSynchronize(st));
+    c->warpb_nbatch = nbatch;
+    return GPT_OK;
+}
+
+// the points / slope factors the builders take for the resident data: warped while layers are set
+static inline const double *model_X(const gpt_ctx *c) { return c->warp.nlayers > 0 ? c->dXw : c->dX; }
+static inline const double *model_S(const gpt_ctx *c) { return c->warp.nlayers > 0 ? c->dS : nullptr; }
+
+static int refuse_warp(const gpt_ctx *c, const char *what)
+{
+    if (c->warp.nlayers > 0) {
+        gpt_set_error("%s is not available while warp layers are set (gpt_set_warp)", what);
+        return GPT_E_NOTIMPL;
+    }
     return GPT_OK;
 }
 
@@ -203,7 +320,7 @@ static int factor_and_ll(gpt_ctx *c, int64_t N, double *ll_data_out, double *log
 static int kbuild_terms(gpt_ctx *c, hipStream_t st, const std::vector<KParams> &terms, int symmetric, const double *dXi,
                         const int32_t *dni, int64_t M, const double *dXj, const int32_t *dnj, int64_t P, int lower_only,
                         int64_t i0, int64_t j0, const double *d_err, double noise_var, double diag_add, double *dK,
-                        int64_t ldk)
+                        int64_t ldk, const double *dSi = nullptr, const double *dSj = nullptr)
 {
     for (size_t t = 0; t < terms.size(); t++) {
         KParams kp = terms[t];
@@ -213,18 +330,13 @@ static int kbuild_terms(gpt_ctx *c, hipStream_t st, const std::vector<KParams> &
         // (a product term brings its second factor: c->terms2 runs parallel to c->terms whenever `terms` IS c->terms)
         const KParams *kp2 = (&terms == &c->terms && t < c->terms2.size() && c->terms2[t].kernel_id >= 0) ? &c->terms2[t] : nullptr;
         GPT_TRY(launch_kbuild(st, kp, dXi, dni, M, dXj, dnj, P, lower_only, i0, j0, last ? d_err : nullptr, noise_var,
-                              diag_add, dK, ldk, t > 0 ? 1 : 0, kp2));
+                              diag_add, dK, ldk, t > 0 ? 1 : 0, kp2, dSi, dSj));
     }
     return GPT_OK;
 }
 
 static int fit_terms(gpt_ctx *c, const std::vector<KParams> &terms, double noise_var, const double *y,
                      const double *err_y, double diag_add, double *ll_data_out, double *logdet_half_out);
-
-static bool native_fit_kernel(int kid)
-{
-    return kid == GPT_KERNEL_SE || kid == GPT_KERNEL_M52 || kid == GPT_KERNEL_RQ || kid == GPT_KERNEL_MATERN || is_gibbs(kid);
-}
 
 // a Gibbs term over the resident points: derivative orders <= 1 (the points' largest order is c->n_maxsum in 1-D)
 static int check_gibbs_fit(const gpt_ctx *c, int kid)
@@ -355,6 +467,7 @@ static int fit_terms_once(gpt_ctx *c, const std::vector<KParams> &terms, double 
 {
     const int64_t Nx = c->Nx;
     const int64_t N = c->dT ? c->Ny : Nx;          // order of K_tot
+    const double *mX = model_X(c), *mS = model_S(c);      // (warp layers set: the warped points and their slope factors)
     c->N = N;
     GPT_TRY(ensure_factor_storage(c, N));
     hipStream_t st = c->stream;
@@ -383,7 +496,7 @@ static int fit_terms_once(gpt_ctx *c, const std::vector<KParams> &terms, double 
         GPT_HIP_CHECK(hipMemsetAsync(dzero, 0, (size_t)Nx * sizeof(double), st));
         if (NxP > Nx) GPT_HIP_CHECK(hipMemsetAsync(dK, 0, (size_t)NxP * NxP * sizeof(double), st));   // zero padding of k
         // (K + noise_K): the builder's diagonal epilogue with err = 0, diag_add = 0 adds exactly noise_var
-        GPT_TRY(kbuild_terms(c, st, c->terms, 1, c->dX, c->dn, Nx, c->dX, c->dn, Nx, 0, 0, 0, dzero, noise_var, 0.0, dK, NxP));
+        GPT_TRY(kbuild_terms(c, st, c->terms, 1, mX, c->dn, Nx, mX, c->dn, Nx, 0, 0, 0, dzero, noise_var, 0.0, dK, NxP, mS, mS));
         GPT_TRY(gemm_nt(c, st, NyP, NxP, NxP, 1.0, c->dT, NxP, dK, NxP, 0.0, dTK, NxP, 0));          // T K  (K = K^T)
         GPT_TRY(gemm_nt(c, st, NyP, NyP, NxP, 1.0, dTK, NxP, c->dT, NxP, 0.0, c->dA, NP, 1));        // (T K) T^T, lower
         GPT_TRY(launch_add_diag(st, c->dA, NP, N, c->d_erry, diag_add));
@@ -404,8 +517,8 @@ static int fit_terms_once(gpt_ctx *c, const std::vector<KParams> &terms, double 
     hipEvent_t e_head = nullptr;
     const bool head_flag = c->flags_now && c->edge_seq < 0xf0000000u;
     if (c->lookahead && !c->use_graph && head < N && (head_flag || (e_head = get_event(c, 0)) != nullptr)) {
-        GPT_TRY(kbuild_terms(c, st, c->terms, 1, c->dX, c->dn, N, c->dX, c->dn, head, 1, 0, 0, c->d_erry, noise_var, diag_add,
-                             c->dA, NP));
+        GPT_TRY(kbuild_terms(c, st, c->terms, 1, mX, c->dn, N, mX, c->dn, head, 1, 0, 0, c->d_erry, noise_var, diag_add,
+                             c->dA, NP, mS, mS));
         if (head_flag) {
             // "the head columns are built" as a flag word raised from this stream (a one-thread kernel behind the build);
             // the first diagonal-block kernel of the panel stream polls it itself: no event record here, no event wait there
@@ -418,12 +531,12 @@ static int fit_terms_once(gpt_ctx *c, const std::vector<KParams> &terms, double 
         } else {
             GPT_HIP_CHECK(hipEventRecord(e_head, st));
         }
-        GPT_TRY(kbuild_terms(c, st, c->terms, 1, c->dX + head * c->D, c->dn + head * c->D, N - head, c->dX + head * c->D,
+        GPT_TRY(kbuild_terms(c, st, c->terms, 1, mX + head * c->D, c->dn + head * c->D, N - head, mX + head * c->D,
                              c->dn + head * c->D, N - head, 1, head, head, c->d_erry, noise_var, diag_add,
-                             c->dA + head * NP + head, NP));
+                             c->dA + head * NP + head, NP, mS ? mS + head : nullptr, mS ? mS + head : nullptr));
     } else {
-        GPT_TRY(kbuild_terms(c, st, c->terms, 1, c->dX, c->dn, N, c->dX, c->dn, N, 1, 0, 0, c->d_erry, noise_var, diag_add,
-                             c->dA, NP));
+        GPT_TRY(kbuild_terms(c, st, c->terms, 1, mX, c->dn, N, mX, c->dn, N, 1, 0, 0, c->d_erry, noise_var, diag_add,
+                             c->dA, NP, mS, mS));
     }
     c->have_kernel = true;
     req.head_event = e_head;

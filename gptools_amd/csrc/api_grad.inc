@@ -177,6 +177,7 @@ static int trtri_u_gemm_b(gpt_ctx *c, hipStream_t st, int64_t lo, int64_t hi, co
 extern "C" int gpt_ll_grad(gpt_ctx *c, int nh, const int *term_idx, const int *local_idx, double *out)
 {
     CTX_ENTER(c);
+    GPT_TRY(refuse_warp(c, "gpt_ll_grad"));
     NEED_FACTOR(c);
     if (!c->have_kernel) {
         gpt_set_error("gpt_ll_grad needs a factorisation produced by gpt_fit / gpt_fit_sum");

@@ -40,6 +40,27 @@ extern "C" int gpt_kpairs(gpt_ctx *c, int kernel_id, const double *params, int n
     return GPT_OK;
 }
 
+// gpt_kbuild / gpt_kbuild2 with warp layers set (gpt_set_warp): the uploaded points are warped in place, their slope factors go to
+// two slots of their own; the builder then takes the WARP instantiation.
+static int warp_kbuild_check(const gpt_ctx *c, const int32_t *ni, int64_t M, const int32_t *nj, int64_t P, int D)
+{
+    if (D != c->warp.D) {
+        gpt_set_error("kbuild: the warp layers are set for num_dim %d, the points have %d", c->warp.D, D);
+        return GPT_E_ARG;
+    }
+    GPT_TRY(check_warp_orders(ni, M, D));
+    return check_warp_orders(nj, P, D);
+}
+
+static int warp_kbuild_points(gpt_ctx *c, hipStream_t st, double *dXi, const int32_t *dni, int64_t M, double *dXj,
+                              const int32_t *dnj, int64_t P, double **dSi, double **dSj)
+{
+    GPT_TRY(ensure(c, SLOT_SI, (size_t)M * sizeof(double), (void **)dSi));
+    GPT_TRY(ensure(c, SLOT_SJ, (size_t)P * sizeof(double), (void **)dSj));
+    GPT_TRY(launch_warp_points(st, c->warp, dXi, dni, M, dXi, *dSi));
+    return launch_warp_points(st, c->warp, dXj, dnj, P, dXj, *dSj);
+}
+
 extern "C" int gpt_kbuild(gpt_ctx *c, int kernel_id, const double *params, int nparams, const double *Xi,
                           const int32_t *ni, int64_t M, const double *Xj, const int32_t *nj, int64_t P, int D,
                           int hyper_deriv, const int32_t *noise_n, double *K_out)
@@ -66,7 +87,9 @@ extern "C" int gpt_kbuild(gpt_ctx *c, int kernel_id, const double *params, int n
     }
     if (M == 0 || P == 0) return GPT_OK;
     if (!Xi || !ni || !Xj || !nj || !K_out) return GPT_E_ARG;
-    double *dXi, *dXj, *dK;
+    const bool warp = c->warp.nlayers > 0 && native_fit_kernel(kernel_id);      // (the noise kernels are never warped)
+    if (warp) GPT_TRY(warp_kbuild_check(c, ni, M, nj, P, D));
+    double *dXi, *dXj, *dK, *dSi = nullptr, *dSj = nullptr;
     int32_t *dni, *dnj;
     GPT_TRY(ensure(c, SLOT_XI, (size_t)M * D * sizeof(double), (void **)&dXi));
     GPT_TRY(ensure(c, SLOT_NI, (size_t)M * D * sizeof(int32_t), (void **)&dni));
@@ -78,7 +101,8 @@ extern "C" int gpt_kbuild(gpt_ctx *c, int kernel_id, const double *params, int n
     GPT_HIP_CHECK(hipMemcpyAsync(dni, ni, (size_t)M * D * sizeof(int32_t), hipMemcpyHostToDevice, st));
     GPT_HIP_CHECK(hipMemcpyAsync(dXj, Xj, (size_t)P * D * sizeof(double), hipMemcpyHostToDevice, st));
     GPT_HIP_CHECK(hipMemcpyAsync(dnj, nj, (size_t)P * D * sizeof(int32_t), hipMemcpyHostToDevice, st));
-    GPT_TRY(launch_kbuild(st, kp, dXi, dni, M, dXj, dnj, P, 0, 0, 0, nullptr, 0.0, 0.0, dK, P));
+    if (warp) GPT_TRY(warp_kbuild_points(c, st, dXi, dni, M, dXj, dnj, P, &dSi, &dSj));
+    GPT_TRY(launch_kbuild(st, kp, dXi, dni, M, dXj, dnj, P, 0, 0, 0, nullptr, 0.0, 0.0, dK, P, 0, nullptr, dSi, dSj));
     GPT_HIP_CHECK(hipMemcpyAsync(K_out, dK, (size_t)M * P * sizeof(double), hipMemcpyDeviceToHost, st));
     GPT_HIP_CHECK(hipStreamSynchronize(st));
     return GPT_OK;
@@ -159,7 +183,9 @@ extern "C" int gpt_kbuild2(gpt_ctx *c, int kernel_id1, const double *params1, in
         GPT_TRY(check_gibbs_orders(ni, M, D));
         GPT_TRY(check_gibbs_orders(nj, P, D));
     }
-    double *dXi, *dXj, *dK;
+    const bool warp = c->warp.nlayers > 0;
+    if (warp) GPT_TRY(warp_kbuild_check(c, ni, M, nj, P, D));
+    double *dXi, *dXj, *dK, *dSi = nullptr, *dSj = nullptr;
     int32_t *dni, *dnj;
     GPT_TRY(ensure(c, SLOT_XI, (size_t)M * D * sizeof(double), (void **)&dXi));
     GPT_TRY(ensure(c, SLOT_NI, (size_t)M * D * sizeof(int32_t), (void **)&dni));
@@ -171,7 +197,8 @@ extern "C" int gpt_kbuild2(gpt_ctx *c, int kernel_id1, const double *params1, in
     GPT_HIP_CHECK(hipMemcpyAsync(dni, ni, (size_t)M * D * sizeof(int32_t), hipMemcpyHostToDevice, st));
     GPT_HIP_CHECK(hipMemcpyAsync(dXj, Xj, (size_t)P * D * sizeof(double), hipMemcpyHostToDevice, st));
     GPT_HIP_CHECK(hipMemcpyAsync(dnj, nj, (size_t)P * D * sizeof(int32_t), hipMemcpyHostToDevice, st));
-    GPT_TRY(launch_kbuild(st, k1, dXi, dni, M, dXj, dnj, P, 0, 0, 0, nullptr, 0.0, 0.0, dK, P, 0, &k2));
+    if (warp) GPT_TRY(warp_kbuild_points(c, st, dXi, dni, M, dXj, dnj, P, &dSi, &dSj));
+    GPT_TRY(launch_kbuild(st, k1, dXi, dni, M, dXj, dnj, P, 0, 0, 0, nullptr, 0.0, 0.0, dK, P, 0, &k2, dSi, dSj));
     GPT_HIP_CHECK(hipMemcpyAsync(K_out, dK, (size_t)M * P * sizeof(double), hipMemcpyDeviceToHost, st));
     GPT_HIP_CHECK(hipStreamSynchronize(st));
     return GPT_OK;

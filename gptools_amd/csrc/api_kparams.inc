@@ -211,3 +211,20 @@ static int check_gibbs_orders(const int32_t *n, int64_t M, int D)
         }
     return GPT_OK;
 }
+
+// warp layers set (gpt_set_warp): the chain rule w'(x) k'(w(x), .) covers orders 0 and 1 only (ref: kernel/warping.py:492-493)
+static const char *const WARP_ORDER_MSG = "Derivative orders greater than one are not supported!";
+static int check_warp_orders(const int32_t *n, int64_t M, int D)
+{
+    for (int64_t i = 0; i < M * D; i++)
+        if (n[i] > 1) {
+            gpt_set_error("%s", WARP_ORDER_MSG);
+            return GPT_E_VALUE;
+        }
+    return GPT_OK;
+}
+
+static bool native_fit_kernel(int kid)
+{
+    return kid == GPT_KERNEL_SE || kid == GPT_KERNEL_M52 || kid == GPT_KERNEL_RQ || kid == GPT_KERNEL_MATERN || is_gibbs(kid);
+}

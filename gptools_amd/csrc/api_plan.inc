@@ -127,8 +127,10 @@ extern "C" int gpt_plan_create(int nctx, gpt_ctx **ctxs, const int64_t *ops, int
                                int D, const void *d_err, gpt_plan **out)
 {
     if (nctx < 1 || nctx > 3 || !ctxs || !ops || nops < 0 || nevents < 0 || !out) return GPT_E_ARG;
-    for (int i = 0; i < nctx; i++)
+    for (int i = 0; i < nctx; i++) {
         if (!ctxs[i]) return GPT_E_ARG;
+        GPT_TRY(refuse_warp(ctxs[i], "gpt_plan_create"));      // (a plan builds from its own points: it would ignore the layers)
+    }
     for (int64_t i = 0; i < nops; i++) {
         const int64_t *o = ops + i * GPT_PLAN_W;
         const bool coll = o[0] == GPT_OP_BCAST || o[0] == GPT_OP_SCATTER || o[0] == GPT_OP_ALLGATHER;
@@ -207,6 +209,7 @@ static inline double plan_f64(int64_t bits)
 extern "C" int gpt_plan_run(gpt_plan *p, int kernel_id, const double *params, int nparams, double noise_var, double diag_add)
 {
     if (!p || !params) return GPT_E_ARG;
+    for (const gpt_ctx *pc : p->ctxs) GPT_TRY(refuse_warp(pc, "gpt_plan_run"));
     GPT_HIP_CHECK(hipSetDevice(p->device));
     const auto t0 = std::chrono::steady_clock::now();
     RcclApi *api = nullptr;

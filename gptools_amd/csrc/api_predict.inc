@@ -52,6 +52,8 @@ extern "C" int gpt_predict(gpt_ctx *c, const double *Xstar, const int32_t *nstar
             }
             break;
         }
+    const bool warp = c->warp.nlayers > 0;
+    if (warp) GPT_TRY(check_warp_orders(nstar, M, D));
     hipStream_t st = c->stream;
     double *dXs, *dKst, *dmean;
     int32_t *dns;
@@ -62,6 +64,17 @@ extern "C" int gpt_predict(gpt_ctx *c, const double *Xstar, const int32_t *nstar
     double *dvar = dmean + MP;
     GPT_HIP_CHECK(hipMemcpyAsync(dXs, Xstar, (size_t)M * D * sizeof(double), hipMemcpyHostToDevice, st));
     GPT_HIP_CHECK(hipMemcpyAsync(dns, nstar, (size_t)M * D * sizeof(int32_t), hipMemcpyHostToDevice, st));
+    // warp layers set (gpt_set_warp): the model kernel sees w(X*) and the slope factors of X*; the noise term below keeps X* itself
+    const double *mXs = dXs, *dSs = nullptr;
+    if (warp) {
+        double *w, *s;
+        GPT_TRY(ensure(c, SLOT_XSW, (size_t)M * D * sizeof(double), (void **)&w));
+        GPT_TRY(ensure(c, SLOT_SS, (size_t)M * sizeof(double), (void **)&s));
+        GPT_TRY(launch_warp_points(st, c->warp, dXs, dns, M, w, s));
+        mXs = w;
+        dSs = s;
+    }
+    const double *mX = model_X(c), *mS = model_S(c);
     // Kstar^T: row a = test point a, column i = training point i  (k is symmetric under swapping its
     // two (point, derivative-order) arguments, so this equals Kstar[i][a] of ref :966)
     GPT_TRY(launch_zero2d(st, MP, n128, dKst, n128));
@@ -70,10 +83,10 @@ extern "C" int gpt_predict(gpt_ctx *c, const double *Xstar, const int32_t *nstar
         double *dKx;
         GPT_TRY(ensure(c, SLOT_TK, (size_t)MP * c->NxP * sizeof(double), (void **)&dKx));
         GPT_TRY(launch_zero2d(st, MP, c->NxP, dKx, c->NxP));
-        GPT_TRY(kbuild_terms(c, st, c->terms, 0, dXs, dns, M, c->dX, c->dn, Nx, 0, 0, 0, nullptr, 0.0, 0.0, dKx, c->NxP));
+        GPT_TRY(kbuild_terms(c, st, c->terms, 0, mXs, dns, M, mX, c->dn, Nx, 0, 0, 0, nullptr, 0.0, 0.0, dKx, c->NxP, dSs, mS));
         GPT_TRY(gemm_nt(c, st, MP, round_up(N, 64), c->NxP, 1.0, dKx, c->NxP, c->dT, c->NxP, 0.0, dKst, n128, 0));
     } else
-    GPT_TRY(kbuild_terms(c, st, c->terms, 0, dXs, dns, M, c->dX, c->dn, N, 0, 0, 0, nullptr, 0.0, 0.0, dKst, n128));
+    GPT_TRY(kbuild_terms(c, st, c->terms, 0, mXs, dns, M, mX, c->dn, N, 0, 0, 0, nullptr, 0.0, 0.0, dKst, n128, dSs, mS));
     GPT_TRY(ensure_alpha(c));
     GPT_TRY(launch_gemv_n(st, M, N, dKst, n128, c->d_alpha, dmean));
     GPT_HIP_CHECK(hipMemcpyAsync(mean_out, dmean, (size_t)M * sizeof(double), hipMemcpyDeviceToHost, st));
@@ -90,9 +103,10 @@ extern "C" int gpt_predict(gpt_ctx *c, const double *Xstar, const int32_t *nstar
                 KParams ks = c->terms[t];
                 ks.symmetric = 1;
                 ks.hyper_deriv = -1;
-                GPT_TRY(launch_kpairs(st, ks, dXs, dXs, dns, dns, M, dkd, t > 0 ? 1 : 0,
+                GPT_TRY(launch_kpairs(st, ks, mXs, mXs, dns, dns, M, dkd, t > 0 ? 1 : 0,
                                       (t < c->terms2.size() && c->terms2[t].kernel_id >= 0) ? &c->terms2[t] : nullptr));
             }
+            if (warp) GPT_TRY(launch_warp_scale_diag(st, dkd, dSs, M));
             GPT_TRY(launch_rowsumsq_sub(st, M, n128, dV, n128, dkd, dvar));
             GPT_HIP_CHECK(hipMemcpyAsync(std_out, dvar, (size_t)M * sizeof(double), hipMemcpyDeviceToHost, st));
             GPT_HIP_CHECK(hipStreamSynchronize(st));
@@ -117,7 +131,7 @@ extern "C" int gpt_predict(gpt_ctx *c, const double *Xstar, const int32_t *nstar
         const int64_t LDC = round_up(M, 128);
         GPT_TRY(ensure(c, SLOT_KSS, (size_t)LDC * LDC * sizeof(double), (void **)&dcov));
         GPT_TRY(launch_zero2d(st, LDC, LDC, dcov, LDC));
-        GPT_TRY(kbuild_terms(c, st, c->terms, 1, dXs, dns, M, dXs, dns, M, 0, 0, 0, nullptr, 0.0, 0.0, dcov, LDC));
+        GPT_TRY(kbuild_terms(c, st, c->terms, 1, mXs, dns, M, mXs, dns, M, 0, 0, 0, nullptr, 0.0, 0.0, dcov, LDC, dSs, dSs));
         if (noise_params) GPT_TRY(launch_add_noise_sym(st, kn, dXs, dns, M, dcov, LDC));
         c->cov_M = 0;
         const int64_t CB = 512;

@@ -136,10 +136,12 @@ int launch_kpairs(hipStream_t st, const KParams &kp, const double *dXi, const do
 int launch_kbuild(hipStream_t st, const KParams &kp, const double *dXi, const int32_t *dni, int64_t M,
                   const double *dXj, const int32_t *dnj, int64_t P, int lower_only, int64_t i0, int64_t j0,
                   const double *d_err_y, double noise_var, double diag_add, double *dK, int64_t ldk,
-                  int accumulate = 0, const KParams *kp2 = nullptr);
+                  int accumulate = 0, const KParams *kp2 = nullptr, const double *dSi = nullptr, const double *dSj = nullptr);
+                  // dSi / dSj (both or neither): Xi / Xj are WARPED points, these their slope factors (warp.hpp; the fit kernels only)
 int launch_kbuild_prod(hipStream_t st, const KParams &kp1, const KParams &kp2, const double *dXi, const int32_t *dni, int64_t M,
                        const double *dXj, const int32_t *dnj, int64_t P, int lower_only, int64_t i0, int64_t j0,
-                       const double *d_err_y, double noise_var, double diag_add, double *dK, int64_t ldk, int accumulate);
+                       const double *d_err_y, double noise_var, double diag_add, double *dK, int64_t ldk, int accumulate,
+                       const double *dSi = nullptr, const double *dSj = nullptr);
 int launch_kpairs_prod(hipStream_t st, const KParams &kp1, const KParams &kp2, const double *dXi, const double *dXj,
                        const int32_t *dni, const int32_t *dnj, int64_t M, double *dout, int accumulate);
 int launch_check_orders(hipStream_t st, const int32_t *dn, int64_t M, int D, int32_t *d_flag);
@@ -169,7 +171,9 @@ int launch_trsm_panel(hipStream_t st, int64_t m, const double *L, int64_t ldl, c
 // batched small fits (gpt_fit_batch)
 int launch_kbuild_batch(hipStream_t st, int kernel_id, int D, const KParams *d_kps, const double *d_noise_var, int64_t nbatch,
                         const double *dX, const int32_t *dn, int64_t N, const double *d_err_y, double diag_add, double *dK,
-                        int64_t ldk, int64_t bstride, int accumulate = 0, int full = 0, const KParams *d_kps2 = nullptr);
+                        int64_t ldk, int64_t bstride, int accumulate = 0, int full = 0, const KParams *d_kps2 = nullptr,
+                        int64_t xstride = 0, const double *dS = nullptr, int64_t sstride = 0);
+                        // dS != NULL: a warped batch -- element z's (warped) points at dX + z * xstride, its slopes at dS + z * sstride
 int launch_batch_pad(hipStream_t st, const double *h_y, int64_t nbatch, double *A, int64_t lda, int64_t bstride, int64_t n_valid,
                      int64_t n_pad, double big, int32_t *info);
 // the predictive half of a resident batch (gpt_predict_batch)

@@ -36,7 +36,7 @@ template <int KID>
 static int kbuild_dispatch_d(hipStream_t st, const KParams &kp, const double *dXi, const int32_t *dni, int64_t M,
                              const double *dXj, const int32_t *dnj, int64_t P, int lower_only, int64_t i0,
                              int64_t j0, const double *d_err_y, double noise_var, double diag_add, double *dK,
-                             int64_t ldk, int accumulate)
+                             int64_t ldk, int accumulate, const double *dSi, const double *dSj)
 {
     dim3 grid((unsigned)((P + KB_COLS - 1) / KB_COLS), (unsigned)((M + KB_ROWS - 1) / KB_ROWS));
     dim3 block(KB_THREADS);
@@ -47,11 +47,25 @@ static int kbuild_dispatch_d(hipStream_t st, const KParams &kp, const double *dX
         grid = dim3((unsigned)ntile, 1);
         lower_only = 2;
     }
+    // (warp layers set: the WARP instantiation, which takes the slope factor on tiles with derivative orders -- the fit kernels only)
+    constexpr bool can_warp = KID != GPT_KERNEL_DIAGNOISE && KID != GPT_KERNEL_ZERO;
+    if (dSi != nullptr && (!can_warp || dSj == nullptr)) {
+        gpt_set_error("kbuild: warp slopes given for kernel_id %d", kp.kernel_id);
+        return GPT_E_ARG;
+    }
 #define KB_CASE(DD)                                                                                     \
     case DD:                                                                                            \
+        if constexpr (can_warp) if (dSi != nullptr) {                                                   \
+            hipLaunchKernelGGL((kbuild_kernel<KID, DD, false, true>), grid, block, 0, st, kp, dXi, dni, M, dXj, dnj, P,   \
+                               lower_only, i0, j0, d_err_y, noise_var, diag_add, dK, ldk, accumulate,           \
+                               (const KParams *)nullptr, (const double *)nullptr, (int64_t)0, KParams(), (const KParams *)nullptr, \
+                               dSi, dSj);                                                               \
+            break;                                                                                      \
+        }                                                                                               \
         hipLaunchKernelGGL((kbuild_kernel<KID, DD, false>), grid, block, 0, st, kp, dXi, dni, M, dXj, dnj, P,   \
                            lower_only, i0, j0, d_err_y, noise_var, diag_add, dK, ldk, accumulate,               \
-                           (const KParams *)nullptr, (const double *)nullptr, (int64_t)0, KParams(), (const KParams *)nullptr);  \
+                           (const KParams *)nullptr, (const double *)nullptr, (int64_t)0, KParams(), (const KParams *)nullptr,  \
+                           (const double *)nullptr, (const double *)nullptr);  \
         break;
     if constexpr (KID == GPT_KERNEL_GIBBS_TANH || KID == GPT_KERNEL_GIBBS_DTANH) {      // (1-D kernels: one instantiation)
         switch (kp.D) {
@@ -75,38 +89,38 @@ static int kbuild_dispatch_d(hipStream_t st, const KParams &kp, const double *dX
 int launch_kbuild(hipStream_t st, const KParams &kp, const double *dXi, const int32_t *dni, int64_t M,
                   const double *dXj, const int32_t *dnj, int64_t P, int lower_only, int64_t i0, int64_t j0,
                   const double *d_err_y, double noise_var, double diag_add, double *dK, int64_t ldk, int accumulate,
-                  const KParams *kp2)
+                  const KParams *kp2, const double *dSi, const double *dSj)
 {
     if (kp2 && kp2->kernel_id >= 0)
         return launch_kbuild_prod(st, kp, *kp2, dXi, dni, M, dXj, dnj, P, lower_only, i0, j0, d_err_y, noise_var, diag_add, dK, ldk,
-                                  accumulate);
+                                  accumulate, dSi, dSj);
     gpt_jitter(st);
     if (M <= 0 || P <= 0) return GPT_OK;
     switch (kp.kernel_id) {
     case GPT_KERNEL_SE:
         return kbuild_dispatch_d<GPT_KERNEL_SE>(st, kp, dXi, dni, M, dXj, dnj, P, lower_only, i0, j0, d_err_y,
-                                                noise_var, diag_add, dK, ldk, accumulate);
+                                                noise_var, diag_add, dK, ldk, accumulate, dSi, dSj);
     case GPT_KERNEL_M52:
         return kbuild_dispatch_d<GPT_KERNEL_M52>(st, kp, dXi, dni, M, dXj, dnj, P, lower_only, i0, j0, d_err_y,
-                                                 noise_var, diag_add, dK, ldk, accumulate);
+                                                 noise_var, diag_add, dK, ldk, accumulate, dSi, dSj);
     case GPT_KERNEL_DIAGNOISE:
         return kbuild_dispatch_d<GPT_KERNEL_DIAGNOISE>(st, kp, dXi, dni, M, dXj, dnj, P, lower_only, i0, j0,
-                                                       d_err_y, noise_var, diag_add, dK, ldk, accumulate);
+                                                       d_err_y, noise_var, diag_add, dK, ldk, accumulate, dSi, dSj);
     case GPT_KERNEL_ZERO:
         return kbuild_dispatch_d<GPT_KERNEL_ZERO>(st, kp, dXi, dni, M, dXj, dnj, P, lower_only, i0, j0, d_err_y,
-                                                  noise_var, diag_add, dK, ldk, accumulate);
+                                                  noise_var, diag_add, dK, ldk, accumulate, dSi, dSj);
     case GPT_KERNEL_RQ:
         return kbuild_dispatch_d<GPT_KERNEL_RQ>(st, kp, dXi, dni, M, dXj, dnj, P, lower_only, i0, j0, d_err_y,
-                                                noise_var, diag_add, dK, ldk, accumulate);
+                                                noise_var, diag_add, dK, ldk, accumulate, dSi, dSj);
     case GPT_KERNEL_MATERN:
         return kbuild_dispatch_d<GPT_KERNEL_MATERN>(st, kp, dXi, dni, M, dXj, dnj, P, lower_only, i0, j0, d_err_y,
-                                                    noise_var, diag_add, dK, ldk, accumulate);
+                                                    noise_var, diag_add, dK, ldk, accumulate, dSi, dSj);
     case GPT_KERNEL_GIBBS_TANH:
         return kbuild_dispatch_d<GPT_KERNEL_GIBBS_TANH>(st, kp, dXi, dni, M, dXj, dnj, P, lower_only, i0, j0, d_err_y,
-                                                        noise_var, diag_add, dK, ldk, accumulate);
+                                                        noise_var, diag_add, dK, ldk, accumulate, dSi, dSj);
     case GPT_KERNEL_GIBBS_DTANH:
         return kbuild_dispatch_d<GPT_KERNEL_GIBBS_DTANH>(st, kp, dXi, dni, M, dXj, dnj, P, lower_only, i0, j0, d_err_y,
-                                                         noise_var, diag_add, dK, ldk, accumulate);
+                                                         noise_var, diag_add, dK, ldk, accumulate, dSi, dSj);
     default:
         gpt_set_error("kbuild: unknown kernel_id %d", kp.kernel_id);
         return GPT_E_ARG;

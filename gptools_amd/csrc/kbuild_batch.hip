@@ -12,7 +12,8 @@
 template <int KID>
 static int kbuild_batch_d(hipStream_t st, int D, const KParams *d_kps, const double *d_nv, int64_t nbatch, const double *dX,
                           const int32_t *dn, int64_t N, const double *d_err_y, double diag_add, double *dK, int64_t ldk,
-                          int64_t bstride, int accumulate, int full, const KParams *d_kps2)
+                          int64_t bstride, int accumulate, int full, const KParams *d_kps2, int64_t xstride, const double *dS,
+                          int64_t sstride)
 {
     const int64_t nrt = (N + KB_ROWS - 1) / KB_ROWS;
     int64_t ntile = 0;
@@ -21,10 +22,18 @@ static int kbuild_batch_d(hipStream_t st, int D, const KParams *d_kps, const dou
     if (full) grid = dim3((unsigned)((N + KB_COLS - 1) / KB_COLS), (unsigned)nrt, (unsigned)nbatch);
     const int lower = full ? 0 : 2;
     KParams dummy = KParams();
+    // (dS != NULL: a warped batch -- element z's points at dX + z * xstride, its slope factors at dS + z * sstride, the WARP instantiation)
 #define KBB_CASE(DD)                                                                                              \
     case DD:                                                                                                      \
+        if (dS != nullptr) {                                                                                      \
+            hipLaunchKernelGGL((kbuild_kernel<KID, DD, true, true>), grid, block, 0, st, dummy, dX, dn, N, dX, dn, N, lower, \
+                               (int64_t)0, (int64_t)0, d_err_y, 0.0, diag_add, dK, ldk, accumulate, d_kps, d_nv, bstride, dummy, d_kps2, \
+                               dS, dS, xstride, sstride);                                                         \
+            break;                                                                                                \
+        }                                                                                                         \
         hipLaunchKernelGGL((kbuild_kernel<KID, DD, true>), grid, block, 0, st, dummy, dX, dn, N, dX, dn, N, lower, \
-                           (int64_t)0, (int64_t)0, d_err_y, 0.0, diag_add, dK, ldk, accumulate, d_kps, d_nv, bstride, dummy, d_kps2); \
+                           (int64_t)0, (int64_t)0, d_err_y, 0.0, diag_add, dK, ldk, accumulate, d_kps, d_nv, bstride, dummy, d_kps2, \
+                           (const double *)nullptr, (const double *)nullptr); \
         break;
     if constexpr (KID == GPT_KERNEL_GIBBS_TANH || KID == GPT_KERNEL_GIBBS_DTANH) {      // (1-D kernels: one instantiation)
         switch (D) {
@@ -47,19 +56,20 @@ static int kbuild_batch_d(hipStream_t st, int D, const KParams *d_kps, const dou
 
 int launch_kbuild_batch(hipStream_t st, int kernel_id, int D, const KParams *d_kps, const double *d_noise_var, int64_t nbatch,
                         const double *dX, const int32_t *dn, int64_t N, const double *d_err_y, double diag_add, double *dK,
-                        int64_t ldk, int64_t bstride, int accumulate, int full, const KParams *d_kps2)
+                        int64_t ldk, int64_t bstride, int accumulate, int full, const KParams *d_kps2, int64_t xstride,
+                        const double *dS, int64_t sstride)
 {
     if (N <= 0 || nbatch <= 0) return GPT_OK;
     if (d_kps2 != nullptr)           // a product term: the factors' kernel ids are read from the elements' KParams at run time
         return kbuild_batch_d<GPT_KERNEL_PRODUCT>(st, D, d_kps, d_noise_var, nbatch, dX, dn, N, d_err_y, diag_add, dK, ldk, bstride, accumulate,
-                                                  full, d_kps2);
+                                                  full, d_kps2, xstride, dS, sstride);
     switch (kernel_id) {
-    case GPT_KERNEL_SE: return kbuild_batch_d<GPT_KERNEL_SE>(st, D, d_kps, d_noise_var, nbatch, dX, dn, N, d_err_y, diag_add, dK, ldk, bstride, accumulate, full, nullptr);
-    case GPT_KERNEL_M52: return kbuild_batch_d<GPT_KERNEL_M52>(st, D, d_kps, d_noise_var, nbatch, dX, dn, N, d_err_y, diag_add, dK, ldk, bstride, accumulate, full, nullptr);
-    case GPT_KERNEL_RQ: return kbuild_batch_d<GPT_KERNEL_RQ>(st, D, d_kps, d_noise_var, nbatch, dX, dn, N, d_err_y, diag_add, dK, ldk, bstride, accumulate, full, nullptr);
-    case GPT_KERNEL_MATERN: return kbuild_batch_d<GPT_KERNEL_MATERN>(st, D, d_kps, d_noise_var, nbatch, dX, dn, N, d_err_y, diag_add, dK, ldk, bstride, accumulate, full, nullptr);
-    case GPT_KERNEL_GIBBS_TANH: return kbuild_batch_d<GPT_KERNEL_GIBBS_TANH>(st, D, d_kps, d_noise_var, nbatch, dX, dn, N, d_err_y, diag_add, dK, ldk, bstride, accumulate, full, nullptr);
-    case GPT_KERNEL_GIBBS_DTANH: return kbuild_batch_d<GPT_KERNEL_GIBBS_DTANH>(st, D, d_kps, d_noise_var, nbatch, dX, dn, N, d_err_y, diag_add, dK, ldk, bstride, accumulate, full, nullptr);
+    case GPT_KERNEL_SE: return kbuild_batch_d<GPT_KERNEL_SE>(st, D, d_kps, d_noise_var, nbatch, dX, dn, N, d_err_y, diag_add, dK, ldk, bstride, accumulate, full, nullptr, xstride, dS, sstride);
+    case GPT_KERNEL_M52: return kbuild_batch_d<GPT_KERNEL_M52>(st, D, d_kps, d_noise_var, nbatch, dX, dn, N, d_err_y, diag_add, dK, ldk, bstride, accumulate, full, nullptr, xstride, dS, sstride);
+    case GPT_KERNEL_RQ: return kbuild_batch_d<GPT_KERNEL_RQ>(st, D, d_kps, d_noise_var, nbatch, dX, dn, N, d_err_y, diag_add, dK, ldk, bstride, accumulate, full, nullptr, xstride, dS, sstride);
+    case GPT_KERNEL_MATERN: return kbuild_batch_d<GPT_KERNEL_MATERN>(st, D, d_kps, d_noise_var, nbatch, dX, dn, N, d_err_y, diag_add, dK, ldk, bstride, accumulate, full, nullptr, xstride, dS, sstride);
+    case GPT_KERNEL_GIBBS_TANH: return kbuild_batch_d<GPT_KERNEL_GIBBS_TANH>(st, D, d_kps, d_noise_var, nbatch, dX, dn, N, d_err_y, diag_add, dK, ldk, bstride, accumulate, full, nullptr, xstride, dS, sstride);
+    case GPT_KERNEL_GIBBS_DTANH: return kbuild_batch_d<GPT_KERNEL_GIBBS_DTANH>(st, D, d_kps, d_noise_var, nbatch, dX, dn, N, d_err_y, diag_add, dK, ldk, bstride, accumulate, full, nullptr, xstride, dS, sstride);
     default:
         gpt_set_error("kbuild_batch: kernel_id %d is not a fit kernel", kernel_id);
         return GPT_E_ARG;
@@ -81,7 +91,8 @@ static int kbuild_batch_cross_d(hipStream_t st, int D, const KParams *d_kps, con
 #define KBC_CASE(DD)                                                                                                         \
     case DD:                                                                                                                 \
         hipLaunchKernelGGL((kbuild_kernel<KID, DD, true>), grid, block, 0, st, dummy, dXi, dni, M, dXj, dnj, P, 0, (int64_t)0, \
-                           (int64_t)0, nullptr, 0.0, 0.0, dK, ldk, accumulate, d_kps, d_nv, bstride, dummy, d_kps2);          \
+                           (int64_t)0, nullptr, 0.0, 0.0, dK, ldk, accumulate, d_kps, d_nv, bstride, dummy, d_kps2,          \
+                           (const double *)nullptr, (const double *)nullptr);                                        \
         break;
     if constexpr (KID == GPT_KERNEL_GIBBS_TANH || KID == GPT_KERNEL_GIBBS_DTANH) {
         switch (D) {

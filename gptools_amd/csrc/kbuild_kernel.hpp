@@ -13,14 +13,25 @@
 
 // BATCH: element blockIdx.z of a batch of independent matrices over the same points -- its hyperparameters kps[z], its
 // noise variance nvs[z], its matrix K + z * bstride (gpt_fit_batch); `kp_one` / `noise_one` are unused then.
-template <int KID, int D, bool BATCH>
+// WARP (gpt_set_warp): Xi / Xj hold WARPED points and Si / Sj the points' chain-rule slopes (warp.hpp: exactly 1.0 for a value
+// point); every pair of a tile that carries a derivative order is multiplied by Si[i] Sj[j] before it is added to earlier terms
+// and before the diagonal epilogue.  PLAIN tiles have S = 1 throughout and skip the factor.  A template flag, not a run-time
+// test: the instantiations without a warp are the code they were.
+template <int KID, int D, bool BATCH, bool WARP = false>
 __global__ __launch_bounds__(KB_THREADS) void kbuild_kernel(
     KParams kp_one, const double *__restrict__ Xi, const int32_t *__restrict__ ni, int64_t M,
     const double *__restrict__ Xj, const int32_t *__restrict__ nj, int64_t P,
     int lower_only, int64_t i0, int64_t j0, const double *__restrict__ err_y, double noise_one,
     double diag_add, double *__restrict__ K, int64_t ldk, int accumulate, const KParams *__restrict__ kps,
-    const double *__restrict__ nvs, int64_t bstride, KParams kp_two_one, const KParams *__restrict__ kps2)
+    const double *__restrict__ nvs, int64_t bstride, KParams kp_two_one, const KParams *__restrict__ kps2,
+    const double *__restrict__ Si = nullptr, const double *__restrict__ Sj = nullptr, int64_t xstride = 0, int64_t sstride = 0)
 {
+    if constexpr (BATCH && WARP) {       // a warped batch: element z has its own warped points and slope factors (gpt_set_warp_batch)
+        Xi += (int64_t)blockIdx.z * xstride;
+        Xj += (int64_t)blockIdx.z * xstride;
+        Si += (int64_t)blockIdx.z * sstride;
+        Sj += (int64_t)blockIdx.z * sstride;
+    }
     const KParams &kp = BATCH ? kps[blockIdx.z] : kp_one;
     const KParams &kp_two = (BATCH && kps2 != nullptr) ? kps2[blockIdx.z] : kp_two_one;      // second factor of a product term
     const double noise_var = BATCH ? nvs[blockIdx.z] : noise_one;
@@ -58,6 +69,11 @@ __global__ __launch_bounds__(KB_THREADS) void kbuild_kernel(
             xj[c][d] = Xj[jc * D + d];
             njr[c][d] = nj[jc * D + d];
         }
+    }
+    double sj[KB_CPT];
+    if constexpr (WARP) {
+#pragma unroll
+        for (int c = 0; c < KB_CPT; c++) sj[c] = Sj[(jfirst + c < P) ? jfirst + c : (P - 1)];
     }
     // both columns in range and the pair 16-byte aligned -> one dwordx4 store per row
     const bool vec = (jfirst + KB_CPT <= P) && ((ldk & 1) == 0) && ((((uintptr_t)K >> 3) + (uint64_t)jfirst) & 1) == 0;
@@ -109,6 +125,7 @@ __global__ __launch_bounds__(KB_THREADS) void kbuild_kernel(
             const double A = readlane_f64(rp.A, q), ha = readlane_f64(rp.h, q);
             const double rb = gibbs_col_root(a, cp.rp, cp.rn);
             double v = gibbs_core(s2, xi, a, A, ha, ra, xj[0][0], cp.l, cp.A, cp.h, rb, nir, njr[0][0], col_d || nir != 0);
+            if constexpr (WARP) v *= Si[i] * sj[0];
             if (accumulate && jfirst < P) v += K[i * ldk + jfirst];
             if (err_y != nullptr && (i + i0 == jfirst + j0)) {
                 const double e = err_y[i + i0];
@@ -164,6 +181,7 @@ __global__ __launch_bounds__(KB_THREADS) void kbuild_kernel(
         for (int c = 0; c < KB_CPT; c++) {
             if constexpr (KID == GPT_KERNEL_PRODUCT) v[c] = prod_pair<D>(kp, kp_two, xi, xj[c], nir, njr[c]);
             else v[c] = any_pair<KID, D>(kp, xi, xj[c], nir, njr[c]);
+            if constexpr (WARP) v[c] *= Si[i] * sj[c];
             // SumKernel (ref: gptools/kernel/core.py:549-584): later terms add to what the earlier passes stored
             if (accumulate && jfirst + c < P) v[c] += K[i * ldk + jfirst + c];
             if (err_y != nullptr && (i + i0 == jfirst + c + j0)) {

@@ -5,9 +5,11 @@
 
 int launch_kbuild_prod(hipStream_t st, const KParams &kp1, const KParams &kp2, const double *dXi, const int32_t *dni, int64_t M,
                        const double *dXj, const int32_t *dnj, int64_t P, int lower_only, int64_t i0, int64_t j0,
-                       const double *d_err_y, double noise_var, double diag_add, double *dK, int64_t ldk, int accumulate)
+                       const double *d_err_y, double noise_var, double diag_add, double *dK, int64_t ldk, int accumulate,
+                       const double *dSi, const double *dSj)
 {
     gpt_jitter(st);
+    if (dSi != nullptr && dSj == nullptr) return GPT_E_ARG;
     if (M <= 0 || P <= 0) return GPT_OK;
     dim3 grid((unsigned)((P + KB_COLS - 1) / KB_COLS), (unsigned)((M + KB_ROWS - 1) / KB_ROWS));
     dim3 block(KB_THREADS);
@@ -20,9 +22,16 @@ int launch_kbuild_prod(hipStream_t st, const KParams &kp1, const KParams &kp2, c
     }
 #define KBP_CASE(DD)                                                                                                  \
     case DD:                                                                                                          \
+        if (dSi != nullptr) {      /* warp layers set: the WARP instantiation (kbuild_kernel.hpp) */                  \
+            hipLaunchKernelGGL((kbuild_kernel<GPT_KERNEL_PRODUCT, DD, false, true>), grid, block, 0, st, kp1, dXi, dni, M, dXj, \
+                               dnj, P, lower_only, i0, j0, d_err_y, noise_var, diag_add, dK, ldk, accumulate,          \
+                               (const KParams *)nullptr, (const double *)nullptr, (int64_t)0, kp2, (const KParams *)nullptr, dSi, dSj); \
+            break;                                                                                                    \
+        }                                                                                                             \
         hipLaunchKernelGGL((kbuild_kernel<GPT_KERNEL_PRODUCT, DD, false>), grid, block, 0, st, kp1, dXi, dni, M, dXj,  \
                            dnj, P, lower_only, i0, j0, d_err_y, noise_var, diag_add, dK, ldk, accumulate,              \
-                           (const KParams *)nullptr, (const double *)nullptr, (int64_t)0, kp2, (const KParams *)nullptr);  \
+                           (const KParams *)nullptr, (const double *)nullptr, (int64_t)0, kp2, (const KParams *)nullptr,  \
+                           (const double *)nullptr, (const double *)nullptr);                                          \
         break;
     switch (kp1.D) {
         KBP_CASE(1) KBP_CASE(2) KBP_CASE(3) KBP_CASE(4) KBP_CASE(5) KBP_CASE(6) KBP_CASE(7) KBP_CASE(8)

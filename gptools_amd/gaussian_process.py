@@ -29,6 +29,7 @@ from . import _lib, _ingest
 from . import replicas
 from .error_handling import GPArgumentError, GPImpossibleParamsError
 from .kernel import Kernel, ZeroKernel, DiagonalNoiseKernel, SumKernel, ProductKernel
+from .kernel.warping import WarpedKernel, beta_cdf_warp, linear_warp
 from .utils import CombinedBounds
 
 __all__ = ["GaussianProcess"]
@@ -36,6 +37,7 @@ __all__ = ["GaussianProcess"]
 _NATIVE_FIT = (_lib.KERNEL_SE, _lib.KERNEL_M52, _lib.KERNEL_RQ, _lib.KERNEL_MATERN, _lib.KERNEL_GIBBS_TANH,
                _lib.KERNEL_GIBBS_DTANH)
 _GIBBS = (_lib.KERNEL_GIBBS_TANH, _lib.KERNEL_GIBBS_DTANH)
+_DEVICE_WARPS = {linear_warp: _lib.WARP_LINEAR, beta_cdf_warp: _lib.WARP_BETA}
 
 
 def _uniform_to_normal(u):
@@ -280,19 +282,36 @@ class GaussianProcess(object):
             k = self.noise_k if noise else self.k
         Xi = np.atleast_2d(np.asarray(Xi, dtype=float))
         ni = np.atleast_2d(np.asarray(ni, dtype=int))
+        if k is self.k and isinstance(k, WarpedKernel) and hyper_deriv is None and self.X is not None:
+            model = self._device_model()
+            if model is not None:
+                # the GP's own warped model: the builder on the warped points (gpt_set_warp needs the resident data for num_dim)
+                ctx = self._ctx
+                if not self._data_on_device:
+                    self._upload_data(ctx)
+                    self._data_on_device = True
+                ctx.set_warp(model[1])
+                Xj_ = None if Xj is None else np.atleast_2d(np.asarray(Xj, dtype=float))
+                nj_ = None if Xj is None else np.atleast_2d(np.asarray(nj, dtype=int))
+                out = None
+                for t in model[0]:
+                    Kt = (ctx.kbuild2(t[0], t[1], t[2], t[3], Xi, ni, Xj_, nj_) if len(t) == 4
+                          else ctx.kbuild(t[0], t[1], Xi, ni, Xj_, nj_))
+                    out = Kt if out is None else out + Kt
+                return out
         kid = getattr(k, "_gpt_kernel_id", None)
         if kid is not None and type(k).__call__ in (Kernel.__call__, _M52_CALL, _ZERO_CALL):
             if kid == _lib.KERNEL_M52 and hyper_deriv is not None:
                 raise NotImplementedError("Hyperparameter derivatives have not been implemented!")
             Xj_ = None if Xj is None else np.atleast_2d(np.asarray(Xj, dtype=float))
             nj_ = None if Xj is None else np.atleast_2d(np.asarray(nj, dtype=int))
-            return self._ctx.kbuild(kid, k.params, Xi, ni, Xj_, nj_, hyper_deriv=hyper_deriv,
-                                    noise_n=getattr(k, "n", None))
+            return self._plain_ctx().kbuild(kid, k.params, Xi, ni, Xj_, nj_, hyper_deriv=hyper_deriv,
+                                            noise_n=getattr(k, "n", None))
         if type(k) is ProductKernel and hyper_deriv is None and k._native_factors() is not None:
             nat = k._native_factors()
             Xj_ = None if Xj is None else np.atleast_2d(np.asarray(Xj, dtype=float))
             nj_ = None if Xj is None else np.atleast_2d(np.asarray(nj, dtype=int))
-            return self._ctx.kbuild2(nat[0], nat[1], nat[2], nat[3], Xi, ni, Xj_, nj_)
+            return self._plain_ctx().kbuild2(nat[0], nat[1], nat[2], nat[3], Xi, ni, Xj_, nj_)
         symmetric = Xj is None
         if symmetric:
             Xj, nj = Xi, ni
@@ -371,8 +390,32 @@ class GaussianProcess(object):
             return None if nat is None else [nat]
         return None
 
+    def _device_model(self):
+        """``(terms, layers)`` when the library evaluates the whole covariance kernel itself, else ``None``: ``terms`` as
+        :meth:`_native_terms` gives them for the kernel under the outer ``WarpedKernel`` layers, ``layers`` those layers as
+        ``gpt_set_warp`` takes them -- ``(type, params)``, the outermost (applied first) first; empty without a warp.  Only
+        layers whose warp function is exactly ``beta_cdf_warp`` or ``linear_warp`` (and whose ``__call__`` is the class's own)
+        peel off, at most ``GPT_WARP_MAX_LAYERS``; a warped kernel anywhere else in the tree keeps the host class."""
+        k, layers = self.k, []
+        while isinstance(k, WarpedKernel):
+            kind = _DEVICE_WARPS.get(getattr(k.w, "fun", None))
+            if kind is None or type(k).__call__ is not WarpedKernel.__call__ or len(k.w.params) != 2 * k.num_dim:
+                return None
+            layers.append((kind, np.array(k.w.params, dtype=float)))
+            k = k.k
+        if len(layers) > _lib.WARP_MAX_LAYERS:
+            return None
+        terms = self._native_terms(k)
+        return None if terms is None else (terms, layers)
+
+    def _plain_ctx(self):
+        """The context for a kernel that is not the GP's model (``compute_Kij(k=...)``): the instance's own, unless that
+        holds the model's warp layers -- they would warp this kernel's points too."""
+        ctx = self._ctx
+        return ctx if ctx._warp_key is None else _lib.default_context(self.device)
+
     def _fast_fit_possible(self):
-        return (self._native_terms() is not None and
+        return (self._device_model() is not None and
                 isinstance(self.noise_k, (ZeroKernel, DiagonalNoiseKernel)))
 
     def _device_fit(self, ctx, terms, noise_var, y_alph, diag_add):
@@ -420,7 +463,9 @@ class GaussianProcess(object):
                 noise_var = 0.0
             else:
                 noise_var = self.noise_k.params[0] ** 2.0
-            ll_data, _ = self._device_fit(ctx, self._native_terms(), noise_var, y_alph, diag_add)
+            terms, layers = self._device_model()
+            ctx.set_warp(layers)                 # (no-op unless the layers or their parameters changed)
+            ll_data, _ = self._device_fit(ctx, terms, noise_var, y_alph, diag_add)
             self._fit_mode = "kernel"
         else:
             # T (linear transform) or a Python-defined kernel: K is still built by the GPU builder
@@ -621,13 +666,17 @@ class GaussianProcess(object):
             if exit_on_bounds and np.isinf(prior):
                 continue                                            # impossible parameters: stays -inf
             noise_var = 0.0 if isinstance(self.noise_k, ZeroKernel) else self.noise_k.params[0] ** 2.0
-            jobs.append((i, self._native_terms(), None, noise_var,
+            terms, layers = self._device_model()
+            jobs.append((i, terms, layers, noise_var,
                          np.array(self._y_alph(), dtype=float), prior))
         if not self._data_on_device:
             self._upload_data(self._ctx)
             self._data_on_device = True
         version = getattr(self, "_data_version", 0)
+        # (a warped model: the elements' warp parameters differ, set_warp_batch gives every element its own warped points; the
+        # layer types are the model's, the same in every element)
         if (max(len(self.y), self.X.shape[0]) <= self.batch_grid_max_n and int(self.batch_grid) > 1 and jobs
+                and all([t for t, _ in j[2]] == [t for t, _ in jobs[0][2]] for j in jobs)
                 and all([(t[0], t[2] if len(t) == 4 else -1) for t in j[1]] == [(t[0], t[2] if len(t) == 4 else -1) for t in jobs[0][1]]
                         for j in jobs)):
             # small N: the whole batch in ONE launch sequence (gpt_fit_batch_terms: every kernel of the factorisation carries the
@@ -641,7 +690,7 @@ class GaussianProcess(object):
             # (other ranks / processes may share the GPU) -- and should the allocation still fail, half as many, down to the
             # one-context-per-thread path below (a MemoryError used to abort ll_batch / compute_ll_matrix)
             budget = min(int(self.batch_grid_bytes), self._ctx.mem_info()[0] // 2)
-            per = 8 * NP * NP + 8 * 9216 * (NP // 128)
+            per = 8 * NP * NP + 8 * 9216 * (NP // 128) + (8 * self.X.shape[0] * (self.num_dim + 1) if jobs[0][2] else 0)
             if self.T is not None:                               # + every element's K over the latent points and T K
                 NxP = -(-self.X.shape[0] // 16) * 16
                 per += 8 * NxP * NxP + 8 * (-(-len(self.y) // 64) * 64) * NxP
@@ -650,6 +699,10 @@ class GaussianProcess(object):
             while s0 < len(jobs) and G >= 1:
                 chunk = jobs[s0:s0 + G]
                 try:
+                    if chunk[0][2]:
+                        self._ctx.set_warp_batch([j[2] for j in chunk])
+                    else:
+                        self._ctx.set_warp(None)             # (layers an earlier warped model left on the context)
                     ll, _, info = self._ctx.fit_batch_terms([j[1] for j in chunk], np.array([j[3] for j in chunk]),
                                                             np.array([j[4] for j in chunk]), err_y, diag_add)
                 except MemoryError:
@@ -662,6 +715,7 @@ class GaussianProcess(object):
                     ll, info = np.zeros(len(chunk)), np.ones(len(chunk), dtype=int)
                     for q, j in enumerate(chunk):
                         try:
+                            self._ctx.set_warp(j[2])
                             ll[q], info[q] = self._device_fit(self._ctx, j[1], j[3], j[4], diag_add)[0], 0
                         except (np.linalg.LinAlgError, ValueError, ArithmeticError):
                             pass
@@ -691,8 +745,9 @@ class GaussianProcess(object):
                     job = next(it, None)
                 if job is None:
                     return
-                i, terms, _, noise_var, y_alph, prior = job
+                i, terms, layers, noise_var, y_alph, prior = job
                 try:
+                    ctx.set_warp(layers)
                     ll_data, _ = self._device_fit(ctx, terms, noise_var, y_alph, diag_add)
                     out[i] = ll_data + prior
                 except (np.linalg.LinAlgError, ValueError, ArithmeticError):
@@ -1038,7 +1093,8 @@ class GaussianProcess(object):
         rows it evaluates and returns the rows left to the loop route."""
         N = len(self.y)
         if (not rows or len(rows) < int(self.mcmc_batch_min_rows) or not self._fast_fit_possible() or self.T is not None
-                or max(N, self.X.shape[0]) > self.batch_grid_max_n or int(self.batch_grid) < 1):
+                or max(N, self.X.shape[0]) > self.batch_grid_max_n or int(self.batch_grid) < 1
+                or self._device_model()[1]):                 # (a warped model: the loop route, each row a device fit + predict)
             return rows
         jobs = []
         for i in rows:
@@ -1167,6 +1223,35 @@ class GaussianProcess(object):
                     warnings.warn("Encountered exception during evaluation of MCMC samples. Exception is:\n%s\nParams are:\n%s"
                                   % (traceback.format_exc(), str(list(t))))
                 rows.append(None)
+        shape = next((np.shape(r) for r in rows if r is not None), np.shape(X))
+        return np.array([np.full(shape, np.nan) if r is None else np.broadcast_to(r, shape) for r in rows], dtype=float)
+
+    def compute_w_from_MCMC(self, X, n=0, sampler=None, flat_trace=None, burn=0, thin=1, **kwargs):
+        """The warping function ``k.w_func`` of dimension 0 of a :class:`WarpedKernel` (its slope for ``n = 1``) at ``X`` for
+        each row of a trace of the free hyperparameters (ref: gaussian_process.py:2067-2142, _ComputeWWrapper :2379-2420): an
+        ``(S, M)`` array where the reference returns a list (or a lazy ``map``).  A row whose evaluation fails, or that holds
+        a NaN parameter, is NaN.  Trace handling as :meth:`compute_l_from_MCMC`; the kernel's hyperparameters are unchanged
+        afterwards.  Host numpy (O(M S)); ``num_proc`` is accepted and ignored."""
+        trace = self._mcmc_trace(sampler, flat_trace, burn, thin)
+        X = np.asarray(X, dtype=float)
+        p = np.array(self.k.params, dtype=float)
+        free = ~np.asarray(self.k.fixed_params, dtype=bool)
+        nk = len(self.k.free_params)
+        rows = []
+        try:
+            for t in trace:
+                try:
+                    q = p.copy()
+                    q[free] = t[:nk]
+                    self.k.params = q
+                    rows.append(np.asarray(self.k.w_func(X, 0, n), dtype=float))
+                except Exception:
+                    if self.verbose:
+                        warnings.warn("Encountered exception during evaluation of MCMC samples. Exception is:\n%s\nParams "
+                                      "are:\n%s" % (traceback.format_exc(), str(list(t))))
+                    rows.append(None)
+        finally:
+            self.k.params = p
         shape = next((np.shape(r) for r in rows if r is not None), np.shape(X))
         return np.array([np.full(shape, np.nan) if r is None else np.broadcast_to(r, shape) for r in rows], dtype=float)
 

@@ -5,3 +5,4 @@ from .matern import *          # noqa: F401,F403
 from .noise import *           # noqa: F401,F403
 from .rational_quadratic import *   # noqa: F401,F403
 from .gibbs import *           # noqa: F401,F403
+from .warping import *         # noqa: F401,F403

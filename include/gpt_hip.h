@@ -75,6 +75,9 @@ extern "C" {
                                   * a = (l_m - l_c)/2, b = (l_e - l_m)/2, c = (l_c + l_e)/2 */
 
 #define GPT_MAX_DIM 16      /* largest supported num_dim */
+#define GPT_WARP_LINEAR 1    /* input warp layer w = (x - a)/(b - a) per dimension (ref: kernel/warping.py:367-402) */
+#define GPT_WARP_BETA 2      /* input warp layer w = I_x(alpha, beta), the beta CDF, per dimension (ref: kernel/warping.py:315-365) */
+#define GPT_WARP_MAX_LAYERS 4
 #define GPT_WS_BLOCK 9216    /* doubles of factorisation workspace per 128 columns (d_invd arguments) */
 
 typedef struct gpt_ctx gpt_ctx;
@@ -218,6 +221,30 @@ int gpt_set_data(gpt_ctx *ctx, const double *X, const int32_t *n, int64_t N, int
  * (Ny x Ny; the products are fp64-MFMA GEMMs on the device), and gpt_predict applies T to the training side of
  * Kstar.  gpt_set_data drops the transform; T == NULL removes it. */
 int gpt_set_T(gpt_ctx *ctx, const double *T, int64_t Ny);
+
+/* Input warp of the model kernel (ref: kernel/warping.py:464-531, WarpedKernel around a native model): k(w(x), w(x')) with an
+ * elementwise warp w made of `nlayers` layers (1 .. GPT_WARP_MAX_LAYERS, layer 0 applied first), `types[l]` one of GPT_WARP_*,
+ * `params` nlayers x 2 D doubles -- layer l, dimension d: (a_d, b_d) of the linear warp, (alpha_d, beta_d) of the beta warp.
+ * While layers are set, gpt_kbuild / gpt_kbuild2 (for the kernels gpt_fit takes; the noise kernels are never warped), gpt_fit /
+ * gpt_fit_sum / gpt_fit_terms (with and without T) and gpt_predict (hence gpt_cov_sample) evaluate the kernel on w(X), and an
+ * entry whose row (column) point carries derivative order 1 in dimension d is multiplied by w_d'(x_d): the chain rule.  Only
+ * orders 0 and 1 have that form: an order above 1 in the resident data, in X* or in gpt_kbuild's points is GPT_E_VALUE
+ * ("Derivative orders greater than one are not supported!"), found on the host before anything is launched.
+ * The beta warp wants its input in [0, 1]: NaN outside (and for alpha <= 0 or beta <= 0), exactly 0 / 1 at the ends.
+ * The call warps the resident points (O(N D) on the device: warp_points_kernel) and drops the resident factorisation; the
+ * layers hold until gpt_set_data or gpt_set_warp(ctx, 0, NULL, NULL).  Needs gpt_set_data first (GPT_E_STATE).
+ * gpt_set_warp(ctx, 0, ...) with no layers set changes nothing (the resident factorisation stays).
+ * Not available while layers are set (GPT_E_NOTIMPL, gpt_last_error says so): gpt_ll_grad, gpt_predict_batch, gpt_plan_create /
+ * gpt_plan_run over this context, and gpt_fit_batch* unless gpt_set_warp_batch gave the batch its own warps. */
+int gpt_set_warp(gpt_ctx *ctx, int nlayers, const int *types, const double *params);
+
+/* The warps of a BATCH: warp parameters are hyperparameters and differ from element to element.  `params` holds nbatch x nlayers x
+ * 2 D doubles (element-major, then as gpt_set_warp); the layer types are shared.  One launch fills nbatch x N x D warped points and
+ * nbatch x N slope factors; the next gpt_fit_batch* -- which must have the same nbatch (GPT_E_ARG otherwise) -- builds element b
+ * from its own and consumes them: element b carries the bits gpt_set_warp + gpt_fit_terms give for that element alone.  The
+ * context's single layers and resident factorisation are untouched.  nlayers == 0 or nbatch == 0 drops a pending set.
+ * gpt_predict_batch answers GPT_E_NOTIMPL for a batch that was fitted with warps.  Orders above 1 in the data: GPT_E_VALUE. */
+int gpt_set_warp_batch(gpt_ctx *ctx, int nbatch, int nlayers, const int *types, const double *params);
 
 /* ---- GaussianProcess.compute_K_L_alpha_ll ------------------------------------------------- */
 /* Replaces the T-free body of GaussianProcess.compute_K_L_alpha_ll   ref: gaussian_process.py:1428-1467
