@@ -283,67 +283,78 @@ class Context(object):
         return int(self._lib.gpt_ctx_edge_count(self.handle))
 
     # ---- Kernel.__call__ / compute_Kij -------------------------------------------------------
-    def kpairs(self, kernel_id, params, Xi, Xj, ni, nj, hyper_deriv=None, symmetric=False, noise_n=None):
-        params, Xi, Xj, ni, nj = f64(params), f64(Xi), f64(Xj), i32(ni), i32(nj)
+    @staticmethod
+    def _pair_args(Xi, Xj, ni, nj):
+        """Points and orders of a pair list -> ``(argument tuple of gpt_kpairs*, D, out, keep)``; ``keep`` holds the contiguous
+        copies the pointers point into: the caller keeps it alive across the C call."""
+        Xi, Xj, ni, nj = f64(Xi), f64(Xj), i32(ni), i32(nj)
         if Xi.ndim != 2 or Xi.shape != Xj.shape or ni.shape != Xi.shape or nj.shape != Xi.shape:
             raise ValueError("Lengths/widths of Xi, Xj, ni, nj don't match")
         M, D = Xi.shape
-        out = np.empty(M, dtype=np.float64)
-        nn = None if noise_n is None else i32(noise_n)
-        check(self._lib.gpt_kpairs(self.handle, kernel_id, dptr(params), len(params), dptr(Xi), dptr(Xj), iptr(ni),
-                                   iptr(nj), M, D, -1 if hyper_deriv is None else int(hyper_deriv),
-                                   int(bool(symmetric)), iptr(nn), dptr(out)))
-        return out
+        return (dptr(Xi), dptr(Xj), iptr(ni), iptr(nj), M), D, np.empty(M, dtype=np.float64), (Xi, Xj, ni, nj)
 
-    def kbuild(self, kernel_id, params, Xi, ni, Xj=None, nj=None, hyper_deriv=None, noise_n=None):
-        params, Xi, ni = f64(params), f64(Xi), i32(ni)
+    @staticmethod
+    def _block_args(Xi, ni, Xj, nj):
+        """Points and orders of a Gram block (``Xj`` None: of ``Xi`` with itself) -> ``(argument tuple of gpt_kbuild*, D, out,
+        keep)``; ``keep`` as in :meth:`_pair_args`."""
+        Xi, ni = f64(Xi), i32(ni)
         M, D = Xi.shape
         if Xj is None:
             Xj_, nj_, P = None, None, M
         else:
             Xj_, nj_ = f64(Xj), i32(nj)
             P = Xj_.shape[0]
-        out = np.empty((M, P), dtype=np.float64)
+        return (dptr(Xi), iptr(ni), M, dptr(Xj_), iptr(nj_), P), D, np.empty((M, P), dtype=np.float64), (Xi, ni, Xj_, nj_)
+
+    def kpairs(self, kernel_id, params, Xi, Xj, ni, nj, hyper_deriv=None, symmetric=False, noise_n=None):
+        params = f64(params)
+        pts, D, out, keep = self._pair_args(Xi, Xj, ni, nj)
         nn = None if noise_n is None else i32(noise_n)
-        check(self._lib.gpt_kbuild(self.handle, kernel_id, dptr(params), len(params), dptr(Xi), iptr(ni), M,
-                                   dptr(Xj_), iptr(nj_), P, D, -1 if hyper_deriv is None else int(hyper_deriv),
-                                   iptr(nn), dptr(out)))
+        check(self._lib.gpt_kpairs(self.handle, kernel_id, dptr(params), len(params), *pts, D,
+                                   -1 if hyper_deriv is None else int(hyper_deriv), int(bool(symmetric)), iptr(nn), dptr(out)))
+        return out
+
+    def kbuild(self, kernel_id, params, Xi, ni, Xj=None, nj=None, hyper_deriv=None, noise_n=None):
+        params = f64(params)
+        pts, D, out, keep = self._block_args(Xi, ni, Xj, nj)
+        nn = None if noise_n is None else i32(noise_n)
+        check(self._lib.gpt_kbuild(self.handle, kernel_id, dptr(params), len(params), *pts, D,
+                                   -1 if hyper_deriv is None else int(hyper_deriv), iptr(nn), dptr(out)))
         return out
 
     def kpairs2(self, kid1, params1, kid2, params2, Xi, Xj, ni, nj):
         """Pair list of the product of two native kernels (gpt_kpairs2)."""
-        p1, p2, Xi, Xj, ni, nj = f64(params1), f64(params2), f64(Xi), f64(Xj), i32(ni), i32(nj)
-        if Xi.ndim != 2 or Xi.shape != Xj.shape or ni.shape != Xi.shape or nj.shape != Xi.shape:
-            raise ValueError("Lengths/widths of Xi, Xj, ni, nj don't match")
-        M, D = Xi.shape
-        out = np.empty(M, dtype=np.float64)
-        check(self._lib.gpt_kpairs2(self.handle, kid1, dptr(p1), len(p1), kid2, dptr(p2), len(p2), dptr(Xi), dptr(Xj),
-                                    iptr(ni), iptr(nj), M, D, dptr(out)))
+        p1, p2 = f64(params1), f64(params2)
+        pts, D, out, keep = self._pair_args(Xi, Xj, ni, nj)
+        check(self._lib.gpt_kpairs2(self.handle, kid1, dptr(p1), len(p1), kid2, dptr(p2), len(p2), *pts, D, dptr(out)))
         return out
 
     def kbuild2(self, kid1, params1, kid2, params2, Xi, ni, Xj=None, nj=None):
         """Covariance matrix of the product of two native kernels (gpt_kbuild2)."""
-        p1, p2, Xi, ni = f64(params1), f64(params2), f64(Xi), i32(ni)
-        M, D = Xi.shape
-        if Xj is None:
-            Xj_, nj_, P = None, None, M
-        else:
-            Xj_, nj_ = f64(Xj), i32(nj)
-            P = Xj_.shape[0]
-        out = np.empty((M, P), dtype=np.float64)
-        check(self._lib.gpt_kbuild2(self.handle, kid1, dptr(p1), len(p1), kid2, dptr(p2), len(p2), dptr(Xi), iptr(ni), M,
-                                    dptr(Xj_), iptr(nj_), P, D, dptr(out)))
+        p1, p2 = f64(params1), f64(params2)
+        pts, D, out, keep = self._block_args(Xi, ni, Xj, nj)
+        check(self._lib.gpt_kbuild2(self.handle, kid1, dptr(p1), len(p1), kid2, dptr(p2), len(p2), *pts, D, dptr(out)))
         return out
 
-    def fit_terms(self, terms, noise_var, y, err_y, diag_add):
-        """gpt_fit_terms: ``terms`` is a list of ``(kernel_id, params)`` or ``(kernel_id1, params1, kernel_id2, params2)``
-        (a product term)."""
+    @staticmethod
+    def _flat_params(terms):
+        """The parameters of a model (see :meth:`_pack_terms`) concatenated, both factors of a product term."""
+        return np.concatenate([np.asarray(p, dtype=float) for t in terms for p in t[1::2]])
+
+    @staticmethod
+    def _pack_terms(terms):
+        """A model as a list of ``(kernel_id, params)`` or ``(kernel_id1, params1, kernel_id2, params2)`` (a product term) ->
+        ``(ids, ids2, nparams, nparams1, flat parameters)`` as gpt_fit_terms / gpt_fit_batch_terms take them."""
         ids = i32(np.asarray([t[0] for t in terms]))
         ids2 = i32(np.asarray([t[2] if len(t) == 4 else -1 for t in terms]))
         npar1 = i32(np.asarray([len(t[1]) for t in terms]))
         npar = i32(np.asarray([len(t[1]) + (len(t[3]) if len(t) == 4 else 0) for t in terms]))
-        flat = f64(np.concatenate([np.concatenate([np.asarray(t[1], dtype=float)] +
-                                                  ([np.asarray(t[3], dtype=float)] if len(t) == 4 else [])) for t in terms]))
+        return ids, ids2, npar, npar1, f64(Context._flat_params(terms))
+
+    def fit_terms(self, terms, noise_var, y, err_y, diag_add):
+        """gpt_fit_terms: ``terms`` is a list of ``(kernel_id, params)`` or ``(kernel_id1, params1, kernel_id2, params2)``
+        (a product term)."""
+        ids, ids2, npar, npar1, flat = self._pack_terms(terms)
         y, err_y = f64(y), f64(err_y)
         ll = C.c_double()
         ld = C.c_double()
@@ -453,14 +464,8 @@ class Context(object):
     def fit_batch_terms(self, terms_list, noise_var, y, err_y, diag_add):
         """gpt_fit_batch_terms: ``terms_list[b]`` is element b's model in the form :meth:`fit_terms` takes (the same kernels in
         every element, only the parameters differ); ``y`` (B, Ny); with a transform set (:meth:`set_T`) K_tot is T (K + noise) T^T."""
-        first = terms_list[0]
-        ids = i32(np.asarray([t[0] for t in first]))
-        ids2 = i32(np.asarray([t[2] if len(t) == 4 else -1 for t in first]))
-        npar1 = i32(np.asarray([len(t[1]) for t in first]))
-        npar = i32(np.asarray([len(t[1]) + (len(t[3]) if len(t) == 4 else 0) for t in first]))
-        params = f64(np.array([np.concatenate([np.concatenate([np.asarray(t[1], dtype=float)] +
-                                                              ([np.asarray(t[3], dtype=float)] if len(t) == 4 else []))
-                                               for t in terms]) for terms in terms_list]))
+        ids, ids2, npar, npar1, _ = self._pack_terms(terms_list[0])
+        params = f64(np.array([self._flat_params(terms) for terms in terms_list]))
         noise_var, y, err_y = f64(noise_var), f64(np.atleast_2d(y)), f64(err_y)
         B = params.shape[0]
         if noise_var.shape != (B,) or y.shape[0] != B or y.shape[1] != err_y.shape[0] or params.shape[1] != int(npar.sum()):

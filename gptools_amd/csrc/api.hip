@@ -1,7 +1,9 @@
 // api.hip -- C ABI (include/gpt_hip.h) and host-side orchestration for libgpt_hip.so.
 // One translation unit, kept in parts by entry-point family (api_*.inc, included at the end of this file in dependency order):
 // this file holds the error channel and struct gpt_ctx.  What belongs to ONE factorisation (not to the context) travels as
-// arguments: PotrfRequest / PotrfResult / PanelShared, api_schedule.inc.
+// arguments: PotrfRequest / PotrfResult / PanelShared, api_schedule.inc.  The model kernel is ONE value (ModelKernel,
+// api_kparams.inc): parse_model is the only place that reads the ABI's id / parameter-count arrays, and the derivative-order
+// rules live there too, one function per family (training points, test points, free-standing pair lists / Gram blocks).
 //
 // Host logic restated here (not kernels): the blocked right-looking Cholesky with a recursive
 // panel and one-panel look-ahead on a second, high-priority HIP stream; the padded / augmented
@@ -39,6 +41,8 @@ extern "C" int gpt_version(void) { return 100; }
     } while (0)
 
 static inline int64_t round_up(int64_t x, int64_t m) { return (x + m - 1) / m * m; }
+
+#include "api_kparams.inc"      // the model kernel (KParams marshalling, ModelKernel, parse_model) and the derivative-order checks of every entry point
 
 struct DevBuf {
     void *p = nullptr;
@@ -153,15 +157,13 @@ struct gpt_ctx {
     // everything that frees, reuses or outdates those slots (gpt_set_data, gpt_set_T, gpt_release_batch_scratch, gpt_cov_sample,
     // the next gpt_fit_batch* until it succeeds) advances batch_gen.
     uint64_t batch_gen = 1, rb_gen = 0;
-    int rb_nbatch = 0, rb_nterms = 0;
+    int rb_nbatch = 0;
     int64_t rb_N = 0;
-    bool rb_any_prod = false;
-    std::vector<KParams> rb_kp, rb_kp2;   // term-major [t][b]; rb_kp2 (product terms, kernel_id -1 elsewhere) only with rb_any_prod
+    ModelKernel rb_model;                 // the first element's model: ids, nterms and the product pattern are every element's
+    std::vector<KParams> rb_kp, rb_kp2;   // term-major [t][b], the device layout; rb_kp2 (kernel_id -1 where term t is no product) only with rb_model.any_prod
     std::vector<double> rb_nv;            // element noise variances
     int64_t cov_M = 0;                 // > 0: SLOT_KSS holds the lower triangle of the predictive covariance of the last gpt_predict(want = 2, cov_out = NULL)
-    KParams kp;                      // first term (single-kernel paths)
-    std::vector<KParams> terms;      // the model kernel as a sum of native kernels (gpt_fit_sum)
-    std::vector<KParams> terms2;     // ... term t is the PRODUCT terms[t] * terms2[t] where terms2[t].kernel_id >= 0 (gpt_fit_terms)
+    ModelKernel model;               // the model kernel of the resident factorisation (gpt_fit, gpt_fit_sum, gpt_fit_terms)
     double timings[5] = {0, 0, 0, 0, 0};
     // per-launch HIP-event timing of the dominant (large) GEMM/SYRK launches, for the roofline line
     int prof_gemm = 0;
@@ -205,7 +207,23 @@ static hipEvent_t get_event(gpt_ctx *c, size_t idx)
     return c->events[idx];
 }
 
-#include "api_kparams.inc"      // kernel-parameter marshalling and argument checks shared by the entry points (make_kparams, order limits)
+// what the resident factor was good for is gone: alpha (device and host copy) and the three sets of block inverses
+static void invalidate_factor(gpt_ctx *c)
+{
+    c->factored = false;
+    c->h_alpha_valid = c->alpha_valid = c->binv_valid = c->binv2_valid = c->binv3_valid = false;
+}
+
+// stream `to` continues behind everything enqueued on `from` so far (one record / wait pair on the context's event `idx`)
+static int stream_follows(gpt_ctx *c, hipStream_t from, hipStream_t to, size_t idx)
+{
+    hipEvent_t e = get_event(c, idx);
+    if (!e) return GPT_E_HIP;
+    GPT_HIP_CHECK(hipEventRecord(e, from));
+    GPT_HIP_CHECK(hipStreamWaitEvent(to, e, 0));
+    return GPT_OK;
+}
+
 #include "api_schedule.inc"      // the factorisation: GEMM driver, flag-edge policy (EvalScope), panels, the look-ahead schedule potrf_enqueue / potrf_run
 #include "api_context.inc"      // gpt_ctx_create / destroy / set_option / synchronize, workspace slots
 #include "api_kernels.inc"      // Kernel.__call__ and compute_Kij: gpt_kpairs, gpt_kbuild, gpt_kpairs2, gpt_kbuild2

@@ -68,35 +68,16 @@ static int fit_batch_impl(gpt_ctx *c, int nbatch, int nterms, const int *kernel_
         gpt_set_error("gpt_fit_batch: call gpt_set_data first");
         return GPT_E_STATE;
     }
-    if (nbatch < 1 || nbatch > 65535 || nterms < 1 || nterms > 8 || !kernel_ids || !nparams_t || !params || !noise_var || !y ||
-        !err_y || !ll_data_out || !info_out || (kernel_ids2 && !nparams1_t))
-        return GPT_E_ARG;
+    if (nbatch < 1 || nbatch > 65535 || !noise_var || !y || !err_y || !ll_data_out || !info_out) return GPT_E_ARG;
     const int64_t Nx = c->Nx, N = c->dT ? c->Ny : Nx;                   // latent points / order of K_tot
     if (Nx > GPT_BATCH_MAX_N || N > GPT_BATCH_MAX_N) {
         gpt_set_error("gpt_fit_batch: needs N <= %d (N = %lld)", GPT_BATCH_MAX_N, (long long)(Nx > N ? Nx : N));
         return GPT_E_ARG;
     }
-    int ptot = 0;
-    bool any_prod = false;
-    for (int t = 0; t < nterms; t++) {
-        const bool prod = kernel_ids2 && kernel_ids2[t] >= 0;
-        any_prod = any_prod || prod;
-        if (!native_fit_kernel(kernel_ids[t]) || (prod && !native_fit_kernel(kernel_ids2[t]))) {
-            gpt_set_error("gpt_fit_batch: kernel ids must be SE, Matern52, RationalQuadratic, Matern or Gibbs");
-            return GPT_E_ARG;
-        }
-        GPT_TRY(check_gibbs_fit(c, kernel_ids[t]));
-        if (prod) GPT_TRY(check_gibbs_fit(c, kernel_ids2[t]));
-        const bool any_chain = kernel_ids[t] == GPT_KERNEL_RQ || kernel_ids[t] == GPT_KERNEL_MATERN ||
-                               (prod && (kernel_ids2[t] == GPT_KERNEL_RQ || kernel_ids2[t] == GPT_KERNEL_MATERN));
-        if ((any_chain || prod) && 2 * c->n_maxsum > GPT_RQ_MAXORD) {
-            gpt_set_error("derivative orders of a pair sum to %ld, the device builder supports %d for products and the "
-                          "RationalQuadratic / Matern kernels", 2 * c->n_maxsum, GPT_RQ_MAXORD);
-            return GPT_E_VALUE;
-        }
-        if (nparams_t[t] < 1 || (prod && (nparams1_t[t] < 1 || nparams1_t[t] >= nparams_t[t]))) return GPT_E_ARG;
-        ptot += nparams_t[t];
-    }
+    // every element has the first one's kernels: its parse decides the layout (and refuses what any element's would)
+    ModelKernel m0, mb;
+    GPT_TRY(parse_model(c->D, c->n_maxsum, nterms, kernel_ids, kernel_ids2, params, nparams_t, nparams1_t, &m0));
+    const bool any_prod = m0.any_prod;
     const int64_t NP = round_up(N + 1, 128), nleaf = NP / 128, bs = NP * NP, bws = nleaf * GPT_WS_BLOCK;
     // pinned staging: [y: nbatch N | err: N | noise: nbatch | KParams: nterms x nbatch (| second factors: the same) | results: 4
     // nbatch]; err .. KParams go to the device in one copy
@@ -118,19 +99,11 @@ static int fit_batch_impl(gpt_ctx *c, int nbatch, int nterms, const int *kernel_
     memcpy(h + off_nv, noise_var, (size_t)nbatch * sizeof(double));
     char *hkp = reinterpret_cast<char *>(h + off_kp), *hkp2 = hkp + (size_t)nterms * nbatch * kp_doubles * 8;
     for (int b = 0; b < nbatch; b++) {
-        const double *pb = params + (size_t)b * ptot;
+        if (b > 0) GPT_TRY(parse_model(c->D, c->n_maxsum, nterms, kernel_ids, kernel_ids2, params + (size_t)b * m0.nparams, nparams_t, nparams1_t, &mb));
+        const ModelKernel &m = b > 0 ? mb : m0;
         for (int t = 0; t < nterms; t++) {                                  // term-major on the device: [t][b]
-            const bool prod = kernel_ids2 && kernel_ids2[t] >= 0;
-            const int n1 = prod ? nparams1_t[t] : nparams_t[t];
-            KParams kp, kp2 = KParams();
-            GPT_TRY(make_kparams(kernel_ids[t], pb, n1, c->D, -1, 1, nullptr, &kp));
-            memcpy(hkp + ((size_t)t * nbatch + (size_t)b) * kp_doubles * 8, &kp, sizeof(KParams));
-            if (any_prod) {
-                kp2.kernel_id = -1;
-                if (prod) GPT_TRY(make_kparams(kernel_ids2[t], pb + n1, nparams_t[t] - n1, c->D, -1, 1, nullptr, &kp2));
-                memcpy(hkp2 + ((size_t)t * nbatch + (size_t)b) * kp_doubles * 8, &kp2, sizeof(KParams));
-            }
-            pb += nparams_t[t];
+            memcpy(hkp + ((size_t)t * nbatch + (size_t)b) * kp_doubles * 8, &m.f1[t], sizeof(KParams));
+            if (any_prod) memcpy(hkp2 + ((size_t)t * nbatch + (size_t)b) * kp_doubles * 8, &m.f2[t], sizeof(KParams));
         }
     }
     c->batch_gen++;                          // (the resident batch is overwritten: valid again once this call has succeeded)
@@ -160,23 +133,16 @@ static int fit_batch_impl(gpt_ctx *c, int nbatch, int nterms, const int *kernel_
     EvalScope scope(c, true);                // (in flight like an evaluation for the flag-edge accounting; has no flag edges)
     // everything on the panel stream: unmasked (all 256 CUs), the main stream is idle here
     hipStream_t st = c->panel_stream;
-    {
-        hipEvent_t e = get_event(c, 0);
-        if (!e) return GPT_E_HIP;
-        GPT_HIP_CHECK(hipEventRecord(e, c->stream));
-        GPT_HIP_CHECK(hipStreamWaitEvent(st, e, 0));
-    }
+    GPT_TRY(stream_follows(c, c->stream, st, 0));
     GPT_HIP_CHECK(hipMemcpyAsync(dmisc, h + off_err, ((size_t)N + (size_t)nbatch + nkp) * sizeof(double), hipMemcpyHostToDevice, st));
-    auto term_kp2 = [&](int t) -> const KParams * {
-        return (kernel_ids2 && kernel_ids2[t] >= 0) ? dkp2 + (size_t)t * nbatch : nullptr;
-    };
+    auto term_kp2 = [&](int t) -> const KParams * { return m0.second(t) ? dkp2 + (size_t)t * nbatch : nullptr; };
     if (c->dT) {
         // K_tot = T (K + noise_var I) T^T + diag(err_y^2) + diag_add I per element (ref :1443-1451), as fit_terms_once does for one
         double *dzero = dmisc + d_off_zero;
         GPT_HIP_CHECK(hipMemsetAsync(dzero, 0, (size_t)Nx * sizeof(double), st));
         if (NxP > Nx) GPT_HIP_CHECK(hipMemsetAsync(dKf, 0, (size_t)nbatch * kfull * sizeof(double), st));
         for (int t = 0; t < nterms; t++)
-            GPT_TRY(launch_kbuild_batch(st, kernel_ids[t], c->D, dkp + (size_t)t * nbatch, dmisc + d_off_nv, nbatch, bX, c->dn, Nx,
+            GPT_TRY(launch_kbuild_batch(st, m0.f1[t].kernel_id, c->D, dkp + (size_t)t * nbatch, dmisc + d_off_nv, nbatch, bX, c->dn, Nx,
                                         t + 1 == nterms ? dzero : nullptr, 0.0, dKf, NxP, (int64_t)kfull, t > 0 ? 1 : 0, 1, term_kp2(t),
                                         xstr, bS, sstr));
         GPT_TRY(launch_gemm_nt(st, NyP, NxP, NxP, 1.0, c->dT, NxP, dKf, NxP, 0.0, dTK, NxP, 0, 0, 0, nullptr, nullptr, 0, EdgeSig(),
@@ -188,7 +154,7 @@ static int fit_batch_impl(gpt_ctx *c, int nbatch, int nterms, const int *kernel_
     } else {
         GPT_TRY(launch_batch_pad(st, h, nbatch, dA, NP, bs, N, NP, 1e300, dinfo));
         for (int t = 0; t < nterms; t++)                                    // (as kbuild_terms: later terms accumulate, the last
-            GPT_TRY(launch_kbuild_batch(st, kernel_ids[t], c->D, dkp + (size_t)t * nbatch, dmisc + d_off_nv, nbatch,   //  one carries the
+            GPT_TRY(launch_kbuild_batch(st, m0.f1[t].kernel_id, c->D, dkp + (size_t)t * nbatch, dmisc + d_off_nv, nbatch,   //  one carries the
                                         bX, c->dn, N, t + 1 == nterms ? dmisc : nullptr, diag_add, dA, NP, bs,     //  diagonal epilogue)
                                         t > 0 ? 1 : 0, 0, term_kp2(t), xstr, bS, sstr));
     }
@@ -236,8 +202,7 @@ static int fit_batch_impl(gpt_ctx *c, int nbatch, int nterms, const int *kernel_
     else c->rb_kp2.clear();
     c->rb_nv.assign(noise_var, noise_var + nbatch);
     c->rb_nbatch = nbatch;
-    c->rb_nterms = nterms;
-    c->rb_any_prod = any_prod;
+    c->rb_model = m0;
     c->rb_N = N;
     c->rb_gen = c->batch_gen;
     c->rb_warped = wb != 0;
@@ -284,34 +249,11 @@ extern "C" int gpt_predict_batch(gpt_ctx *c, const double *Xstar, const int32_t 
         gpt_set_error("gpt_predict_batch: bad arguments");
         return GPT_E_ARG;
     }
-    const int D = c->D, nbatch = c->rb_nbatch, nterms = c->rb_nterms;
+    const ModelKernel &model = c->rb_model;
+    const int D = c->D, nbatch = c->rb_nbatch, nterms = model.nterms;
     const int64_t N = c->rb_N, NP = round_up(N + 1, 128), nleaf = NP / 128, bs = NP * NP, bws = nleaf * GPT_WS_BLOCK;
     const int64_t MP = round_up(M, 64), ldv = (int64_t)nbatch * NP;
-    // derivative orders of the test points: the checks of gpt_predict, for the first element's kernels (all elements share them)
-    {
-        bool m52 = false, chain = c->rb_any_prod, gibbs = false;
-        for (int t = 0; t < nterms; t++) {
-            const int k1 = c->rb_kp[(size_t)t * nbatch].kernel_id;
-            const int k2 = c->rb_any_prod ? c->rb_kp2[(size_t)t * nbatch].kernel_id : -1;
-            m52 = m52 || k1 == GPT_KERNEL_M52 || k2 == GPT_KERNEL_M52;
-            chain = chain || k1 == GPT_KERNEL_RQ || k1 == GPT_KERNEL_MATERN;
-            gibbs = gibbs || is_gibbs(k1) || is_gibbs(k2);
-        }
-        if (m52) GPT_TRY(check_m52_orders(nstar, M, D));
-        if (gibbs) GPT_TRY(check_gibbs_orders(nstar, M, D));
-        if (chain) {
-            long ms = 0;
-            for (int64_t i = 0; i < M; i++) {
-                long sn = 0;
-                for (int d = 0; d < D; d++) sn += nstar[i * D + d];
-                if (sn > ms) ms = sn;
-            }
-            if (ms + (ms > c->n_maxsum ? ms : c->n_maxsum) > GPT_RQ_MAXORD) {
-                gpt_set_error("RationalQuadraticKernel: derivative orders of a pair sum to more than %d", GPT_RQ_MAXORD);
-                return GPT_E_VALUE;
-            }
-        }
-    }
+    GPT_TRY(check_test_orders(model, c->n_maxsum, false, nstar, M, D));
     double noise_sum = 0.0;
     for (int b = 0; b < nbatch; b++)
         if (keep[b]) noise_sum += c->rb_nv[b];
@@ -324,7 +266,7 @@ extern "C" int gpt_predict_batch(gpt_ctx *c, const double *Xstar, const int32_t 
         }
     // device inputs in one slot: [KParams (| second factors) | noise variances: nbatch | keep: nbatch | hit: M | X*: M D | n*: M D],
     // then [mean | var]
-    const size_t nkp = (size_t)nterms * nbatch * (c->rb_any_prod ? 2 : 1);
+    const size_t nkp = (size_t)nterms * nbatch * (model.any_prod ? 2 : 1);
     const size_t b_kp = nkp * sizeof(KParams) + (size_t)nbatch * 8, b_keep = round_up(nbatch, 2) * 4, b_hit = round_up(M, 2) * 4,
                  b_xs = (size_t)M * D * 8, b_ns = round_up(M * D, 2) * 4;
     const size_t o_keep = b_kp, o_hit = o_keep + b_keep, o_xs = o_hit + b_hit, o_ns = o_xs + b_xs, o_mv = o_ns + b_ns;
@@ -333,14 +275,14 @@ extern "C" int gpt_predict_batch(gpt_ctx *c, const double *Xstar, const int32_t 
     GPT_TRY(ensure(c, SLOT_PB_MISC, o_mv + b_mv, (void **)&dmisc));
     std::vector<char> hin(o_mv);
     memcpy(hin.data(), c->rb_kp.data(), (size_t)nterms * nbatch * sizeof(KParams));
-    if (c->rb_any_prod) memcpy(hin.data() + (size_t)nterms * nbatch * sizeof(KParams), c->rb_kp2.data(), (size_t)nterms * nbatch * sizeof(KParams));
+    if (model.any_prod) memcpy(hin.data() + (size_t)nterms * nbatch * sizeof(KParams), c->rb_kp2.data(), (size_t)nterms * nbatch * sizeof(KParams));
     memcpy(hin.data() + nkp * sizeof(KParams), c->rb_nv.data(), (size_t)nbatch * 8);
     memcpy(hin.data() + o_keep, keep, (size_t)nbatch * 4);
     memcpy(hin.data() + o_hit, hit.data(), (size_t)M * 4);
     memcpy(hin.data() + o_xs, Xstar, b_xs);
     memcpy(hin.data() + o_ns, nstar, (size_t)M * D * 4);
     const KParams *dkp = reinterpret_cast<const KParams *>(dmisc);
-    const KParams *dkp2 = c->rb_any_prod ? dkp + (size_t)nterms * nbatch : nullptr;
+    const KParams *dkp2 = model.any_prod ? dkp + (size_t)nterms * nbatch : nullptr;
     const double *dnv = reinterpret_cast<const double *>(dmisc + nkp * sizeof(KParams));
     const int32_t *dkeep = reinterpret_cast<const int32_t *>(dmisc + o_keep), *dhit = reinterpret_cast<const int32_t *>(dmisc + o_hit);
     const double *dXs = reinterpret_cast<const double *>(dmisc + o_xs);
@@ -354,20 +296,13 @@ extern "C" int gpt_predict_batch(gpt_ctx *c, const double *Xstar, const int32_t 
     const double *dA = (const double *)c->slots[SLOT_BATCH_A].p, *dws = (const double *)c->slots[SLOT_BATCH_WS].p;
     EvalScope scope(c, true);
     hipStream_t st = c->panel_stream;                      // (unmasked, as the fit)
-    {
-        hipEvent_t e = get_event(c, 0);
-        if (!e) return GPT_E_HIP;
-        GPT_HIP_CHECK(hipEventRecord(e, c->stream));
-        GPT_HIP_CHECK(hipStreamWaitEvent(st, e, 0));
-    }
+    GPT_TRY(stream_follows(c, c->stream, st, 0));
     GPT_HIP_CHECK(hipMemcpyAsync(dmisc, hin.data(), o_mv, hipMemcpyHostToDevice, st));
-    auto term_kp2 = [&](int t) -> const KParams * {
-        return (c->rb_any_prod && c->rb_kp2[(size_t)t * nbatch].kernel_id >= 0) ? dkp2 + (size_t)t * nbatch : nullptr;
-    };
+    auto term_kp2 = [&](int t) -> const KParams * { return model.second(t) ? dkp2 + (size_t)t * nbatch : nullptr; };
     // K*_b^T (M x N per element) into V, zeros elsewhere
     GPT_TRY(launch_zero2d(st, MP, ldv, dV, ldv));
     for (int t = 0; t < nterms; t++)
-        GPT_TRY(launch_kbuild_batch_cross(st, c->rb_kp[(size_t)t * nbatch].kernel_id, D, dkp + (size_t)t * nbatch, dnv, nbatch, dXs, dns,
+        GPT_TRY(launch_kbuild_batch_cross(st, model.f1[t].kernel_id, D, dkp + (size_t)t * nbatch, dnv, nbatch, dXs, dns,
                                           M, c->dX, c->dn, N, dV, ldv, NP, t > 0 ? 1 : 0, term_kp2(t)));
     // V_b = K*_b^T L_b^-T, left-looking over the leaves: leaf j first receives the update of all leaves before it
     for (int64_t lc = 0; lc < NP; lc += 128) {
@@ -395,7 +330,7 @@ extern "C" int gpt_predict_batch(gpt_ctx *c, const double *Xstar, const int32_t 
         const int64_t cs = MP * MP;
         GPT_TRY(launch_zero2d(st, (int64_t)nbatch * MP, MP, dC, MP));
         for (int t = 0; t < nterms; t++)
-            GPT_TRY(launch_kbuild_batch_cross(st, c->rb_kp[(size_t)t * nbatch].kernel_id, D, dkp + (size_t)t * nbatch, dnv, nbatch, dXs,
+            GPT_TRY(launch_kbuild_batch_cross(st, model.f1[t].kernel_id, D, dkp + (size_t)t * nbatch, dnv, nbatch, dXs,
                                               dns, M, dXs, dns, M, dC, MP, cs, t > 0 ? 1 : 0, term_kp2(t)));
         GPT_TRY(launch_gemm_nt(st, MP, MP, NP, -1.0, dV, ldv, dV, ldv, 1.0, dC, MP, 0, 0, 0, nullptr, nullptr, 0, EdgeSig(), EdgeSig(), 0,
                                nbatch, NP, EdgeSig(), NP, cs));

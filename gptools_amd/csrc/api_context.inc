@@ -87,7 +87,7 @@ static void free_factor(gpt_ctx *c)
     if (c->d_alpha) hipFree(c->d_alpha);
     c->dA = c->d_invd = c->d_y = c->d_erry = c->d_alpha = nullptr;
     c->NP = 0;
-    c->factored = c->h_alpha_valid = c->alpha_valid = c->binv_valid = c->binv2_valid = c->binv3_valid = false;
+    invalidate_factor(c);
 }
 
 extern "C" int gpt_ctx_destroy(gpt_ctx *c)

@@ -37,8 +37,7 @@ extern "C" int gpt_set_data(gpt_ctx *c, const double *X, const int32_t *n, int64
         }
         if (sn > c->n_maxsum) c->n_maxsum = sn;
     }
-    c->factored = false;
-    c->h_alpha_valid = c->alpha_valid = c->binv_valid = c->binv2_valid = c->binv3_valid = false;
+    invalidate_factor(c);
     c->have_kernel = false;
     c->batch_gen++;                     // (the resident batch was fitted to the old data)
     if (c->dT) hipFree(c->dT);          // a transform belongs to one data set
@@ -61,8 +60,7 @@ extern "C" int gpt_set_T(gpt_ctx *c, const double *T, int64_t Ny)
     if (c->dT) hipFree(c->dT);
     c->dT = nullptr;
     c->Ny = 0;
-    c->factored = false;
-    c->h_alpha_valid = c->alpha_valid = c->binv_valid = c->binv2_valid = c->binv3_valid = false;
+    invalidate_factor(c);
     c->have_kernel = false;
     c->batch_gen++;
     if (!T || Ny <= 0) return GPT_OK;
@@ -83,8 +81,7 @@ extern "C" int gpt_set_warp(gpt_ctx *c, int nlayers, const int *types, const dou
 {
     CTX_ENTER(c);
     if (nlayers == 0 && c->warp.nlayers == 0) return GPT_OK;      // nothing set, nothing to clear: the resident factor stays
-    c->factored = false;
-    c->h_alpha_valid = c->alpha_valid = c->binv_valid = c->binv2_valid = c->binv3_valid = false;
+    invalidate_factor(c);
     c->have_kernel = false;
     c->cov_M = 0;
     if (nlayers == 0) {
@@ -244,16 +241,13 @@ static int factor_and_ll(gpt_ctx *c, int64_t N, double *ll_data_out, double *log
         red_st = st;
         joined = true;
     } else if (c->eager_alpha && tl != st) {
-        hipEvent_t e_end = get_event(c, 1);
-        if (!e_end) return GPT_E_HIP;
-        GPT_HIP_CHECK(hipEventRecord(e_end, tl));
-        GPT_HIP_CHECK(hipStreamWaitEvent(st, e_end, 0));
+        GPT_TRY(stream_follows(c, tl, st, 1));
         red_st = st;
         joined = true;
     }
     GPT_TRY(launch_logdet_dot(red_st, c->dA, NP, N, c->d_info, c->d_scal, c->h_scal, nullptr, c->timing ? c->tev[4] : nullptr,
                               c->flags_now ? c->d_edge + 60 : nullptr));
-    c->h_alpha_valid = c->alpha_valid = c->binv_valid = c->binv2_valid = c->binv3_valid = false;
+    invalidate_factor(c);                  // (c->factored is false already: every caller drops it in front of its build)
     // option eager_alpha (the reference computes alpha in every evaluation, gaussian_process.py:1462): the substitution goes behind
     // the factorisation at once, ON THE STREAM THE FACTORISATION ENDS ON (no event edge in front of its first kernel; the block
     // inverses left of the last panel were built under that panel, enqueue_early_block_inverses);
@@ -263,17 +257,11 @@ static int factor_and_ll(gpt_ctx *c, int64_t N, double *ll_data_out, double *log
     // The device timings of gpt_last_timings end at the reduction kernel: an eager evaluation's alpha is not in them, see bench.py.)
     int rc_alpha = c->eager_alpha ? alpha_to_host(c, tl) : GPT_OK;
     c->binv_early = 0;                     // (whatever was built early has been taken up by now, or is not going to be)
-    if (tl != st && !joined) {
-        hipEvent_t e_end = get_event(c, 1);
-        if (!e_end) return GPT_E_HIP;
-        GPT_HIP_CHECK(hipEventRecord(e_end, tl));
-        GPT_HIP_CHECK(hipStreamWaitEvent(st, e_end, 0));
-    }
+    if (tl != st && !joined) GPT_TRY(stream_follows(c, tl, st, 1));
     if (rc_alpha != GPT_OK) {
-        c->h_alpha_valid = c->alpha_valid = c->binv_valid = c->binv2_valid = c->binv3_valid = false;
+        invalidate_factor(c);
         if (tl != st) (void)hipStreamSynchronize(tl);
         (void)hipStreamSynchronize(st);
-        c->factored = false;
         return rc_alpha;
     }
     if (tl != st) GPT_HIP_CHECK(hipStreamSynchronize(tl));
@@ -292,15 +280,13 @@ static int factor_and_ll(gpt_ctx *c, int64_t N, double *ll_data_out, double *log
         c->timings[4] = ms;
     }
     if (c->flags_now && c->h_scal[3] != 0.0) {
-        c->h_alpha_valid = c->alpha_valid = c->binv_valid = c->binv2_valid = c->binv3_valid = false;
         // a flag wait of this evaluation timed out (common.hpp): its numbers mean nothing; the caller repeats it on events
-        c->factored = false;
+        invalidate_factor(c);
         return GPT_I_EDGE_TIMEOUT;
     }
     const int32_t info = (int32_t)c->h_scal[2];
     if (info != 0) {
-        c->factored = false;
-        c->h_alpha_valid = c->alpha_valid = c->binv_valid = c->binv2_valid = c->binv3_valid = false;
+        invalidate_factor(c);
         if (info > N) {          // only the augmented / padding pivots failed: z.z overflowed
             gpt_set_error("factorisation failed in the augmented row (non-finite data?)");
             return (int)N;
@@ -315,38 +301,27 @@ static int factor_and_ll(gpt_ctx *c, int64_t N, double *ll_data_out, double *log
     return GPT_OK;
 }
 
-// K block of the model kernel = sum of c->terms (SumKernel, ref: gptools/kernel/core.py:549-584): one builder pass per
-// term, later passes accumulate; the diagonal epilogue (err != nullptr) rides on the last pass, after the sum.
-static int kbuild_terms(gpt_ctx *c, hipStream_t st, const std::vector<KParams> &terms, int symmetric, const double *dXi,
-                        const int32_t *dni, int64_t M, const double *dXj, const int32_t *dnj, int64_t P, int lower_only,
-                        int64_t i0, int64_t j0, const double *d_err, double noise_var, double diag_add, double *dK,
-                        int64_t ldk, const double *dSi = nullptr, const double *dSj = nullptr)
+// K block of the model kernel = the sum of its terms (SumKernel, ref: gptools/kernel/core.py:549-584): one builder pass per
+// term (a product term brings its second factor), later passes accumulate; the diagonal epilogue (err != nullptr) rides on the
+// last pass, after the sum.
+static int kbuild_terms(hipStream_t st, const ModelKernel &m, int symmetric, const double *dXi, const int32_t *dni, int64_t M,
+                        const double *dXj, const int32_t *dnj, int64_t P, int lower_only, int64_t i0, int64_t j0,
+                        const double *d_err, double noise_var, double diag_add, double *dK, int64_t ldk,
+                        const double *dSi = nullptr, const double *dSj = nullptr)
 {
-    for (size_t t = 0; t < terms.size(); t++) {
-        KParams kp = terms[t];
+    for (int t = 0; t < m.nterms; t++) {
+        KParams kp = m.f1[t];
         kp.symmetric = symmetric;
         kp.hyper_deriv = -1;
-        const bool last = t + 1 == terms.size();
-        // (a product term brings its second factor: c->terms2 runs parallel to c->terms whenever `terms` IS c->terms)
-        const KParams *kp2 = (&terms == &c->terms && t < c->terms2.size() && c->terms2[t].kernel_id >= 0) ? &c->terms2[t] : nullptr;
+        const bool last = t + 1 == m.nterms;
         GPT_TRY(launch_kbuild(st, kp, dXi, dni, M, dXj, dnj, P, lower_only, i0, j0, last ? d_err : nullptr, noise_var,
-                              diag_add, dK, ldk, t > 0 ? 1 : 0, kp2, dSi, dSj));
+                              diag_add, dK, ldk, t > 0 ? 1 : 0, m.second(t), dSi, dSj));
     }
     return GPT_OK;
 }
 
-static int fit_terms(gpt_ctx *c, const std::vector<KParams> &terms, double noise_var, const double *y,
-                     const double *err_y, double diag_add, double *ll_data_out, double *logdet_half_out);
-
-// a Gibbs term over the resident points: derivative orders <= 1 (the points' largest order is c->n_maxsum in 1-D)
-static int check_gibbs_fit(const gpt_ctx *c, int kid)
-{
-    if (is_gibbs(kid) && c->n_maxsum > 1) {
-        gpt_set_error("Derivatives greater than [1, 1] are not supported!");
-        return GPT_E_NOTIMPL;
-    }
-    return GPT_OK;
-}
+static int fit_terms(gpt_ctx *c, const ModelKernel &model, double noise_var, const double *y, const double *err_y,
+                     double diag_add, double *ll_data_out, double *logdet_half_out);
 
 extern "C" int gpt_fit(gpt_ctx *c, int kernel_id, const double *params, int nparams, double noise_var,
                        const double *y, const double *err_y, double diag_add, double *ll_data_out,
@@ -355,80 +330,41 @@ extern "C" int gpt_fit(gpt_ctx *c, int kernel_id, const double *params, int npar
     return gpt_fit_sum(c, 1, &kernel_id, params, &nparams, noise_var, y, err_y, diag_add, ll_data_out, logdet_half_out);
 }
 
+// gpt_fit_sum (no product terms: kernel_ids2 == NULL) and gpt_fit_terms (need_ids2: both product arrays are part of its contract)
+static int fit_model(gpt_ctx *c, int nterms, const int *kernel_ids, const int *kernel_ids2, bool need_ids2, const double *params,
+                     const int *nparams, const int *nparams1, double noise_var, const double *y, const double *err_y, double diag_add,
+                     double *ll_data_out, double *logdet_half_out)
+{
+    if (!c->dX) {
+        gpt_set_error("gpt_fit: call gpt_set_data first");
+        return GPT_E_STATE;
+    }
+    if (!y || !err_y || (need_ids2 && (!kernel_ids2 || !nparams1))) return GPT_E_ARG;
+    ModelKernel model;
+    GPT_TRY(parse_model(c->D, c->n_maxsum, nterms, kernel_ids, kernel_ids2, params, nparams, nparams1, &model));
+    return fit_terms(c, model, noise_var, y, err_y, diag_add, ll_data_out, logdet_half_out);
+}
+
 extern "C" int gpt_fit_sum(gpt_ctx *c, int nterms, const int *kernel_ids, const double *params, const int *nparams,
                            double noise_var, const double *y, const double *err_y, double diag_add,
                            double *ll_data_out, double *logdet_half_out)
 {
     CTX_ENTER(c);
-    if (!c->dX) {
-        gpt_set_error("gpt_fit: call gpt_set_data first");
-        return GPT_E_STATE;
-    }
-    if (nterms < 1 || nterms > 8 || !kernel_ids || !params || !nparams || !y || !err_y) return GPT_E_ARG;
-    std::vector<KParams> terms((size_t)nterms);
-    const double *p = params;
-    for (int t = 0; t < nterms; t++) {
-        if (!native_fit_kernel(kernel_ids[t])) {
-            gpt_set_error("gpt_fit: kernel_id must be SE, Matern52, RationalQuadratic, Matern or Gibbs");
-            return GPT_E_ARG;
-        }
-        GPT_TRY(check_gibbs_fit(c, kernel_ids[t]));
-        if ((kernel_ids[t] == GPT_KERNEL_RQ || kernel_ids[t] == GPT_KERNEL_MATERN) && 2 * c->n_maxsum > GPT_RQ_MAXORD) {
-            gpt_set_error("RationalQuadratic / Matern kernel: derivative orders of a pair sum to %ld, the device builder supports %d",
-                          2 * c->n_maxsum, GPT_RQ_MAXORD);
-            return GPT_E_VALUE;
-        }
-        GPT_TRY(make_kparams(kernel_ids[t], p, nparams[t], c->D, -1, 1, nullptr, &terms[(size_t)t]));
-        p += nparams[t];
-    }
-    c->terms2.assign(terms.size(), KParams());
-    for (auto &k2 : c->terms2) k2.kernel_id = -1;
-    return fit_terms(c, terms, noise_var, y, err_y, diag_add, ll_data_out, logdet_half_out);
+    return fit_model(c, nterms, kernel_ids, nullptr, false, params, nparams, nullptr, noise_var, y, err_y, diag_add, ll_data_out,
+                     logdet_half_out);
 }
 
 // The same with product terms (include/gpt_hip.h)
-
 extern "C" int gpt_fit_terms(gpt_ctx *c, int nterms, const int *kernel_ids, const int *kernel_ids2, const double *params,
                              const int *nparams, const int *nparams1, double noise_var, const double *y, const double *err_y,
                              double diag_add, double *ll_data_out, double *logdet_half_out)
 {
     CTX_ENTER(c);
-    if (!c->dX) {
-        gpt_set_error("gpt_fit_terms: call gpt_set_data first");
-        return GPT_E_STATE;
-    }
-    if (nterms < 1 || nterms > 8 || !kernel_ids || !kernel_ids2 || !params || !nparams || !nparams1 || !y || !err_y) return GPT_E_ARG;
-    std::vector<KParams> terms((size_t)nterms), terms2((size_t)nterms);
-    const double *p = params;
-    for (int t = 0; t < nterms; t++) {
-        const bool prod = kernel_ids2[t] >= 0;
-        if (!native_fit_kernel(kernel_ids[t]) || (prod && !native_fit_kernel(kernel_ids2[t]))) {
-            gpt_set_error("gpt_fit_terms: kernel ids must be SE, Matern52, RationalQuadratic, Matern or Gibbs");
-            return GPT_E_ARG;
-        }
-        GPT_TRY(check_gibbs_fit(c, kernel_ids[t]));
-        if (prod) GPT_TRY(check_gibbs_fit(c, kernel_ids2[t]));
-        const int n1 = prod ? nparams1[t] : nparams[t];
-        if (n1 < 1 || n1 > nparams[t]) return GPT_E_ARG;
-        // derivative orders: a product meets the SUM of both points' orders in either factor
-        const bool any_chain = kernel_ids[t] == GPT_KERNEL_RQ || kernel_ids[t] == GPT_KERNEL_MATERN ||
-                               (prod && (kernel_ids2[t] == GPT_KERNEL_RQ || kernel_ids2[t] == GPT_KERNEL_MATERN));
-        if ((any_chain || prod) && 2 * c->n_maxsum > GPT_RQ_MAXORD) {
-            gpt_set_error("derivative orders of a pair sum to %ld, the device builder supports %d for products and the "
-                          "RationalQuadratic / Matern kernels", 2 * c->n_maxsum, GPT_RQ_MAXORD);
-            return GPT_E_VALUE;
-        }
-        GPT_TRY(make_kparams(kernel_ids[t], p, n1, c->D, -1, 1, nullptr, &terms[(size_t)t]));
-        terms2[(size_t)t] = KParams();
-        terms2[(size_t)t].kernel_id = -1;
-        if (prod) GPT_TRY(make_kparams(kernel_ids2[t], p + n1, nparams[t] - n1, c->D, -1, 1, nullptr, &terms2[(size_t)t]));
-        p += nparams[t];
-    }
-    c->terms2 = terms2;
-    return fit_terms(c, terms, noise_var, y, err_y, diag_add, ll_data_out, logdet_half_out);
+    return fit_model(c, nterms, kernel_ids, kernel_ids2, true, params, nparams, nparams1, noise_var, y, err_y, diag_add, ll_data_out,
+                     logdet_half_out);
 }
 
-static int fit_terms_once(gpt_ctx *c, const std::vector<KParams> &terms, double noise_var, const double *y,
+static int fit_terms_once(gpt_ctx *c, const ModelKernel &model, double noise_var, const double *y,
                           const double *err_y, double diag_add, double *ll_data_out, double *logdet_half_out);
 
 // An evaluation whose flag wait timed out: the process goes to event edges for good and the evaluation runs again.
@@ -446,23 +382,23 @@ static int edge_timeout_fallback(gpt_ctx *c)
     return GPT_OK;
 }
 
-static int fit_terms(gpt_ctx *c, const std::vector<KParams> &terms, double noise_var, const double *y,
-                     const double *err_y, double diag_add, double *ll_data_out, double *logdet_half_out)
+static int fit_terms(gpt_ctx *c, const ModelKernel &model, double noise_var, const double *y, const double *err_y,
+                     double diag_add, double *ll_data_out, double *logdet_half_out)
 {
     int rc;
     {
         EvalScope scope(c);
-        rc = fit_terms_once(c, terms, noise_var, y, err_y, diag_add, ll_data_out, logdet_half_out);
+        rc = fit_terms_once(c, model, noise_var, y, err_y, diag_add, ll_data_out, logdet_half_out);
     }
     if (rc == GPT_I_EDGE_TIMEOUT) {
         edge_timeout_fallback(c);
         EvalScope scope(c);
-        rc = fit_terms_once(c, terms, noise_var, y, err_y, diag_add, ll_data_out, logdet_half_out);
+        rc = fit_terms_once(c, model, noise_var, y, err_y, diag_add, ll_data_out, logdet_half_out);
     }
     return rc;
 }
 
-static int fit_terms_once(gpt_ctx *c, const std::vector<KParams> &terms, double noise_var, const double *y,
+static int fit_terms_once(gpt_ctx *c, const ModelKernel &model, double noise_var, const double *y,
                           const double *err_y, double diag_add, double *ll_data_out, double *logdet_half_out)
 {
     const int64_t Nx = c->Nx;
@@ -483,8 +419,7 @@ static int fit_terms_once(gpt_ctx *c, const std::vector<KParams> &terms, double 
         if (c->timing) GPT_HIP_CHECK(hipEventRecord(c->tev[1], st));
         GPT_HIP_CHECK(hipMemsetAsync(c->d_info, 0, sizeof(int32_t), st));
     }
-    c->terms = terms;
-    c->kp = terms[0];
+    c->model = model;
     if (c->dT) {
         // ---- T path: K_tot = T (K + noise_var I) T^T + diag(err_y^2) + diag_add I, assembled on the device by the
         // K-builder (full symmetric K over the Nx latent points) and two fp64-MFMA GEMMs (ref :1443-1451)
@@ -496,7 +431,7 @@ static int fit_terms_once(gpt_ctx *c, const std::vector<KParams> &terms, double 
         GPT_HIP_CHECK(hipMemsetAsync(dzero, 0, (size_t)Nx * sizeof(double), st));
         if (NxP > Nx) GPT_HIP_CHECK(hipMemsetAsync(dK, 0, (size_t)NxP * NxP * sizeof(double), st));   // zero padding of k
         // (K + noise_K): the builder's diagonal epilogue with err = 0, diag_add = 0 adds exactly noise_var
-        GPT_TRY(kbuild_terms(c, st, c->terms, 1, mX, c->dn, Nx, mX, c->dn, Nx, 0, 0, 0, dzero, noise_var, 0.0, dK, NxP, mS, mS));
+        GPT_TRY(kbuild_terms(st, c->model, 1, mX, c->dn, Nx, mX, c->dn, Nx, 0, 0, 0, dzero, noise_var, 0.0, dK, NxP, mS, mS));
         GPT_TRY(gemm_nt(c, st, NyP, NxP, NxP, 1.0, c->dT, NxP, dK, NxP, 0.0, dTK, NxP, 0));          // T K  (K = K^T)
         GPT_TRY(gemm_nt(c, st, NyP, NyP, NxP, 1.0, dTK, NxP, c->dT, NxP, 0.0, c->dA, NP, 1));        // (T K) T^T, lower
         GPT_TRY(launch_add_diag(st, c->dA, NP, N, c->d_erry, diag_add));
@@ -517,7 +452,7 @@ static int fit_terms_once(gpt_ctx *c, const std::vector<KParams> &terms, double 
     hipEvent_t e_head = nullptr;
     const bool head_flag = c->flags_now && c->edge_seq < 0xf0000000u;
     if (c->lookahead && !c->use_graph && head < N && (head_flag || (e_head = get_event(c, 0)) != nullptr)) {
-        GPT_TRY(kbuild_terms(c, st, c->terms, 1, mX, c->dn, N, mX, c->dn, head, 1, 0, 0, c->d_erry, noise_var, diag_add,
+        GPT_TRY(kbuild_terms(st, c->model, 1, mX, c->dn, N, mX, c->dn, head, 1, 0, 0, c->d_erry, noise_var, diag_add,
                              c->dA, NP, mS, mS));
         if (head_flag) {
             // "the head columns are built" as a flag word raised from this stream (a one-thread kernel behind the build);
@@ -531,11 +466,11 @@ static int fit_terms_once(gpt_ctx *c, const std::vector<KParams> &terms, double 
         } else {
             GPT_HIP_CHECK(hipEventRecord(e_head, st));
         }
-        GPT_TRY(kbuild_terms(c, st, c->terms, 1, mX + head * c->D, c->dn + head * c->D, N - head, mX + head * c->D,
+        GPT_TRY(kbuild_terms(st, c->model, 1, mX + head * c->D, c->dn + head * c->D, N - head, mX + head * c->D,
                              c->dn + head * c->D, N - head, 1, head, head, c->d_erry, noise_var, diag_add,
                              c->dA + head * NP + head, NP, mS ? mS + head : nullptr, mS ? mS + head : nullptr));
     } else {
-        GPT_TRY(kbuild_terms(c, st, c->terms, 1, mX, c->dn, N, mX, c->dn, N, 1, 0, 0, c->d_erry, noise_var, diag_add,
+        GPT_TRY(kbuild_terms(st, c->model, 1, mX, c->dn, N, mX, c->dn, N, 1, 0, 0, c->d_erry, noise_var, diag_add,
                              c->dA, NP, mS, mS));
     }
     c->have_kernel = true;

@@ -185,10 +185,8 @@ extern "C" int gpt_ll_grad(gpt_ctx *c, int nh, const int *term_idx, const int *l
     }
     if (nh < 0 || (nh > 0 && (!term_idx || !local_idx)) || !out) return GPT_E_ARG;
     for (int h = 0; h < nh; h++) {
-        if (term_idx[h] < 0 || term_idx[h] >= (int)c->terms.size()) return GPT_E_ARG;
-        const KParams &t = c->terms[(size_t)term_idx[h]];
-        const bool is_prod = (size_t)term_idx[h] < c->terms2.size() && c->terms2[(size_t)term_idx[h]].kernel_id >= 0;
-        if (t.kernel_id != GPT_KERNEL_SE || is_prod) {
+        if (term_idx[h] < 0 || term_idx[h] >= c->model.nterms) return GPT_E_ARG;
+        if (c->model.f1[term_idx[h]].kernel_id != GPT_KERNEL_SE || c->model.second(term_idx[h])) {
             gpt_set_error("hyper-parameter derivatives exist for the squared-exponential kernel only "
                           "(ref: matern.py:543-544)");
             return GPT_E_NOTIMPL;
@@ -199,12 +197,7 @@ extern "C" int gpt_ll_grad(gpt_ctx *c, int nh, const int *term_idx, const int *l
     // Everything here runs on the panel stream: it is not CU-masked (the main stream leaves 32 of the 256 CUs to it), and
     // nothing else is in flight.
     hipStream_t st = c->panel_stream;
-    {
-        hipEvent_t e = get_event(c, 0);
-        if (!e) return GPT_E_HIP;
-        GPT_HIP_CHECK(hipEventRecord(e, c->stream));
-        GPT_HIP_CHECK(hipStreamWaitEvent(st, e, 0));
-    }
+    GPT_TRY(stream_follows(c, c->stream, st, 0));
     double *U, *W, *dpart;
     // K_tot^-1 = L^-T L^-1 = U U^T: triangular inverse (N^3/3 flop), then the lower half of U U^T block row by block row
     // with k starting at the diagonal (N^3/3) -- all on the fp64-MFMA GEMM
@@ -221,10 +214,7 @@ extern "C" int gpt_ll_grad(gpt_ctx *c, int nh, const int *term_idx, const int *l
     if (nfull >= 2 * GPT_BINV_NB) {
         // (the block inverses are built on the main stream with the head of SLOT_UINV as their scratch: before U is touched)
         GPT_TRY(ensure_block_inverses(c, GPT_BINV_NB, nfull, &Wb));
-        hipEvent_t e = get_event(c, 1);
-        if (!e) return GPT_E_HIP;
-        GPT_HIP_CHECK(hipEventRecord(e, c->stream));
-        GPT_HIP_CHECK(hipStreamWaitEvent(st, e, 0));
+        GPT_TRY(stream_follows(c, c->stream, st, 1));
     }
     GPT_TRY(ensure_alpha(c));                                  // (main stream; joined below before the pair pass)
     if (c->debug_poison)                                       // test aid: every byte 0xff = NaN in whatever is not written below
@@ -267,11 +257,7 @@ extern "C" int gpt_ll_grad(gpt_ctx *c, int nh, const int *term_idx, const int *l
         GPT_TRY(gemm_nt(c, st, rows, rows, NP - r0, 1.0, U + r0 * NP + r0, NP, U + r0 * NP + r0, NP, 0.0, W + r0 * NP + r0, NP, 1));
     }
     if (gt) GPT_HIP_CHECK(hipEventRecord(ge[2], st));
-    {   // alpha (main stream) is needed from here on
-        hipEvent_t e = get_event(c, 0);
-        GPT_HIP_CHECK(hipEventRecord(e, c->stream));
-        GPT_HIP_CHECK(hipStreamWaitEvent(st, e, 0));
-    }
+    GPT_TRY(stream_follows(c, c->stream, st, 0));              // alpha (main stream) is needed from here on
     // With a linear transform (ref :1499-1500, dK_tot = T dK T^T):  tr(K_tot^-1 T dK T^T) = tr((T^T K_tot^-1 T) dK) and
     // alpha^T T dK T^T alpha = (T^T alpha)^T dK (T^T alpha): the pair pass runs over the Nx LATENT points with
     // W' = T^T W T (two GEMMs with the resident T) and alpha' = T^T alpha.  The noise entry (out[nh]) is taken from the
@@ -309,16 +295,17 @@ extern "C" int gpt_ll_grad(gpt_ctx *c, int nh, const int *term_idx, const int *l
     GPT_TRY(ensure(c, SLOT_GPART, (size_t)nblk * (GPT_GRAD_MAXH + 1) * sizeof(double), (void **)&dpart));
     std::vector<double> hpart((size_t)nblk * (GPT_GRAD_MAXH + 1));
     bool have_trace = false;
-    for (size_t t = 0; t < c->terms.size() || !have_trace; t++) {
+    const int nterms = c->model.nterms;
+    for (int t = 0; t < nterms || !have_trace; t++) {
         std::vector<int> hs, where;
-        if (t < c->terms.size())
+        if (t < nterms)
             for (int h = 0; h < nh; h++)
-                if ((size_t)term_idx[h] == t) {
+                if (term_idx[h] == t) {
                     hs.push_back(local_idx[h]);
                     where.push_back(h);
                 }
         if (hs.empty() && have_trace) continue;
-        const KParams &kp = c->terms[t < c->terms.size() ? t : 0];
+        const KParams &kp = c->model.f1[t < nterms ? t : 0];
         for (size_t b0 = 0; b0 < hs.size() || !have_trace; b0 += GPT_GRAD_MAXH) {
             const int cnt = (int)((hs.size() - b0 < (size_t)GPT_GRAD_MAXH) ? hs.size() - b0 : (size_t)GPT_GRAD_MAXH);
             KParams ks = kp;
@@ -361,10 +348,5 @@ extern "C" int gpt_ll_grad(gpt_ctx *c, int nh, const int *term_idx, const int *l
         fprintf(stderr, "gpt_ll_grad N=%lld: triangular inverse %.2f ms, U U^T %.2f ms, pair pass %.2f ms\n", (long long)N, a, b, d);
         for (auto &e : ge) hipEventDestroy(e);
     }
-    {   // the main stream continues behind this (the block inverses stay valid for predict)
-        hipEvent_t e = get_event(c, 1);
-        GPT_HIP_CHECK(hipEventRecord(e, st));
-        GPT_HIP_CHECK(hipStreamWaitEvent(c->stream, e, 0));
-    }
-    return GPT_OK;
+    return stream_follows(c, st, c->stream, 1);     // the main stream continues behind this (the block inverses stay valid for predict)
 }

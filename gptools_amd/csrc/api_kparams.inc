@@ -1,5 +1,9 @@
-// api_kparams.inc -- part of api.hip (ONE translation unit: included from there, in this order; the parts share struct gpt_ctx and
-// static helpers).  Kernel-parameter marshalling and argument checks shared by the entry points (make_kparams, order limits).
+// api_kparams.inc -- part of api.hip (ONE translation unit: included from there, in front of struct gpt_ctx, which holds a
+// ModelKernel by value; nothing here reads the context).  The model kernel and what the entry points check about it:
+// make_kparams (one native kernel's parameters -> KParams), ModelKernel + parse_model (a sum of native kernels and products of
+// two, from the id / parameter-count arrays of the ABI), and the derivative-order rules -- the primitives check_m52_orders,
+// check_rq_orders, check_gibbs_orders, check_warp_orders and, built on them, ONE function per family of entry points:
+// check_train_orders (the fits), check_test_orders (the predictions), check_pair_orders (gpt_kpairs* / gpt_kbuild*).
 // ------------------------------------------------------------------------------------------------
 static int make_kparams(int kernel_id, const double *params, int nparams, int D, int hyper_deriv, int symmetric,
                         const int32_t *noise_n, KParams *kp)
@@ -201,12 +205,19 @@ static bool is_gibbs(int kid)
     return kid == GPT_KERNEL_GIBBS_TANH || kid == GPT_KERNEL_GIBBS_DTANH;
 }
 
+// RationalQuadratic / Matern: derivatives by the chain rule with GPT_RQ_MAXORD + 1 Faa di Bruno coefficients (check_rq_orders)
+static bool is_chain(int kid)
+{
+    return kid == GPT_KERNEL_RQ || kid == GPT_KERNEL_MATERN;
+}
+
 // The Gibbs kernels evaluate derivative orders 0 and 1 per point (ref: gibbs.py:417-420 raises NotImplementedError beyond)
+static const char *const GIBBS_ORDER_MSG = "Derivatives greater than [1, 1] are not supported!";
 static int check_gibbs_orders(const int32_t *n, int64_t M, int D)
 {
     for (int64_t i = 0; i < M * D; i++)
         if (n[i] > 1) {
-            gpt_set_error("Derivatives greater than [1, 1] are not supported!");
+            gpt_set_error("%s", GIBBS_ORDER_MSG);
             return GPT_E_NOTIMPL;
         }
     return GPT_OK;
@@ -226,5 +237,118 @@ static int check_warp_orders(const int32_t *n, int64_t M, int D)
 
 static bool native_fit_kernel(int kid)
 {
-    return kid == GPT_KERNEL_SE || kid == GPT_KERNEL_M52 || kid == GPT_KERNEL_RQ || kid == GPT_KERNEL_MATERN || is_gibbs(kid);
+    return kid == GPT_KERNEL_SE || kid == GPT_KERNEL_M52 || is_chain(kid) || is_gibbs(kid);
+}
+
+// ------------------------------------------------------------------------------------------------
+// the model kernel
+// ------------------------------------------------------------------------------------------------
+// A sum of up to GPT_MAX_TERMS terms (SumKernel, ref: kernel/core.py:549-584), each one native kernel or the product of two
+// (ProductKernel, ref: kernel/core.py:587-671).  The context holds the resident factorisation's by value (gpt_ctx::model), the
+// resident batch its first element's (gpt_ctx::rb_model: ids, nterms and the product pattern are the same in every element).
+#define GPT_MAX_TERMS 8
+struct ModelKernel {
+    int nterms = 0;
+    int nparams = 0;                               // doubles one parameter set takes in the ABI's flat array (all terms, both factors)
+    KParams f1[GPT_MAX_TERMS] = {}, f2[GPT_MAX_TERMS] = {};      // f2[t].kernel_id < 0: term t is not a product; zero beyond nterms
+    bool any_prod = false, has_m52 = false, has_chain = false, has_gibbs = false;      // over all factors of all terms
+    const KParams *second(int t) const { return f2[t].kernel_id >= 0 ? &f2[t] : nullptr; }
+};
+
+// Training points against ONE term k1 (* k2 where k2 >= 0); n_maxsum: the largest row sum of their derivative orders
+// (gpt_set_data).  A Gibbs factor takes orders <= 1 (1-D: the largest order IS n_maxsum); a pair of training points meets
+// 2 n_maxsum in a RationalQuadratic / Matern factor, and in EITHER factor of a product (the SUM of both points' orders).  A lone
+// SE or Matern52 term has no limit here (Matern52's own rule is the Python host's).
+static int check_train_orders(int k1, int k2, long n_maxsum)
+{
+    if ((is_gibbs(k1) || is_gibbs(k2)) && n_maxsum > 1) {
+        gpt_set_error("%s", GIBBS_ORDER_MSG);
+        return GPT_E_NOTIMPL;
+    }
+    if ((is_chain(k1) || k2 >= 0) && 2 * n_maxsum > GPT_RQ_MAXORD) {
+        gpt_set_error("derivative orders of a pair sum to %ld, the device builder supports %d for products and the "
+                      "RationalQuadratic / Matern kernels", 2 * n_maxsum, GPT_RQ_MAXORD);
+        return GPT_E_VALUE;
+    }
+    return GPT_OK;
+}
+
+// The ONE reader of the ABI's model arrays: term t is ids[t] with nparams[t] parameters, or -- ids2 given and ids2[t] >= 0 --
+// the product ids[t] * ids2[t], the first nparams1[t] of its nparams[t] parameters the first factor's.  Term by term: ids, the
+// training points' orders (check_train_orders), the parameter split, the parameters (make_kparams) -- the first refusal in that
+// order is the call's status.  *m is overwritten whether or not the call succeeds: callers that keep a model parse into a local.
+static int parse_model(int D, long n_maxsum, int nterms, const int *ids, const int *ids2, const double *params, const int *nparams,
+                       const int *nparams1, ModelKernel *m)
+{
+    if (nterms < 1 || nterms > GPT_MAX_TERMS || !ids || !params || !nparams || (ids2 && !nparams1)) return GPT_E_ARG;
+    m->nterms = nterms;
+    m->any_prod = m->has_m52 = m->has_chain = m->has_gibbs = false;      // (the factors beyond nterms stay as they are: never read, zero in a fresh model)
+    const double *p = params;
+    for (int t = 0; t < nterms; t++) {
+        const int k1 = ids[t], k2 = (ids2 && ids2[t] >= 0) ? ids2[t] : -1;
+        const bool prod = k2 >= 0;
+        if (!native_fit_kernel(k1) || (prod && !native_fit_kernel(k2))) {
+            gpt_set_error("gpt_fit: kernel ids must be SE, Matern52, RationalQuadratic, Matern or Gibbs");
+            return GPT_E_ARG;
+        }
+        GPT_TRY(check_train_orders(k1, k2, n_maxsum));
+        const int n1 = prod ? nparams1[t] : nparams[t];
+        if (n1 < 1 || (prod && n1 >= nparams[t])) {
+            gpt_set_error("gpt_fit: term %d: %d parameters, %d of them the first factor's", t, nparams[t], n1);
+            return GPT_E_ARG;
+        }
+        GPT_TRY(make_kparams(k1, p, n1, D, -1, 1, nullptr, &m->f1[t]));
+        m->f2[t] = KParams();
+        m->f2[t].kernel_id = -1;
+        if (prod) GPT_TRY(make_kparams(k2, p + n1, nparams[t] - n1, D, -1, 1, nullptr, &m->f2[t]));
+        m->any_prod = m->any_prod || prod;
+        m->has_m52 = m->has_m52 || k1 == GPT_KERNEL_M52 || k2 == GPT_KERNEL_M52;
+        m->has_chain = m->has_chain || is_chain(k1) || is_chain(k2);
+        m->has_gibbs = m->has_gibbs || is_gibbs(k1) || is_gibbs(k2);
+        p += nparams[t];
+    }
+    m->nparams = (int)(p - params);
+    return GPT_OK;
+}
+
+// Test points against the model and the resident training points: Matern52 and Gibbs factors limit the test points' own orders,
+// a RationalQuadratic / Matern factor or a product the orders of a (test, test) and of a (test, training) pair; `warp`: layers
+// are set (gpt_set_warp).
+static int check_test_orders(const ModelKernel &m, long n_maxsum, bool warp, const int32_t *nstar, int64_t M, int D)
+{
+    if (m.has_m52) GPT_TRY(check_m52_orders(nstar, M, D));
+    if (m.has_gibbs) GPT_TRY(check_gibbs_orders(nstar, M, D));
+    if (m.has_chain || m.any_prod) {
+        long ms = 0;
+        for (int64_t i = 0; i < M; i++) {
+            long sn = 0;
+            for (int d = 0; d < D; d++) sn += nstar[i * D + d];
+            if (sn > ms) ms = sn;
+        }
+        if (ms + (ms > n_maxsum ? ms : n_maxsum) > GPT_RQ_MAXORD) {
+            gpt_set_error("RationalQuadraticKernel: derivative orders of a pair sum to more than %d", GPT_RQ_MAXORD);
+            return GPT_E_VALUE;
+        }
+    }
+    if (warp) GPT_TRY(check_warp_orders(nstar, M, D));
+    return GPT_OK;
+}
+
+// A free-standing pair list (`pairwise`: row i of ni meets row i of nj, M == P) or Gram block (every row meets every column) of
+// k1, or of the product k1 * k2 where k2 != NULL: in a product either factor meets the combined order of a pair, and Leibniz
+// hands a Gibbs / Matern52 factor at most the points' own orders.
+static int check_pair_orders(const KParams &k1, const KParams *k2, const int32_t *ni, int64_t M, const int32_t *nj, int64_t P, int D,
+                             bool pairwise)
+{
+    const int id1 = k1.kernel_id, id2 = k2 ? k2->kernel_id : -1;
+    if (id1 == GPT_KERNEL_M52 || id2 == GPT_KERNEL_M52) {
+        GPT_TRY(check_m52_orders(ni, M, D));
+        GPT_TRY(check_m52_orders(nj, P, D));
+    }
+    if (is_chain(id1) || k2) GPT_TRY(check_rq_orders(ni, M, nj, P, D, pairwise));
+    if (is_gibbs(id1) || is_gibbs(id2)) {
+        GPT_TRY(check_gibbs_orders(ni, M, D));
+        GPT_TRY(check_gibbs_orders(nj, P, D));
+    }
+    return GPT_OK;
 }

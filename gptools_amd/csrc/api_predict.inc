@@ -21,39 +21,9 @@ extern "C" int gpt_predict(gpt_ctx *c, const double *Xstar, const int32_t *nstar
     const int D = c->D;
     const int64_t N = c->N, n128 = round_up(N, 128), MP = round_up(M, 64);
     const int64_t Nx = c->Nx;
-    std::vector<KParams> all_factors(c->terms);
-    bool any_product = false;
-    for (const auto &t2 : c->terms2)
-        if (t2.kernel_id >= 0) {
-            all_factors.push_back(t2);
-            any_product = true;
-        }
-    for (const auto &t : all_factors)
-        if (t.kernel_id == GPT_KERNEL_M52) {
-            GPT_TRY(check_m52_orders(nstar, M, D));
-            break;
-        }
-    for (const auto &t : all_factors)
-        if (is_gibbs(t.kernel_id)) {
-            GPT_TRY(check_gibbs_orders(nstar, M, D));
-            break;
-        }
-    for (const auto &t : all_factors)
-        if (t.kernel_id == GPT_KERNEL_RQ || t.kernel_id == GPT_KERNEL_MATERN || any_product) {
-            long ms = 0;
-            for (int64_t i = 0; i < M; i++) {
-                long sn = 0;
-                for (int d = 0; d < D; d++) sn += nstar[i * D + d];
-                if (sn > ms) ms = sn;
-            }
-            if (ms + (ms > c->n_maxsum ? ms : c->n_maxsum) > GPT_RQ_MAXORD) {
-                gpt_set_error("RationalQuadraticKernel: derivative orders of a pair sum to more than %d", GPT_RQ_MAXORD);
-                return GPT_E_VALUE;
-            }
-            break;
-        }
+    const ModelKernel &model = c->model;
     const bool warp = c->warp.nlayers > 0;
-    if (warp) GPT_TRY(check_warp_orders(nstar, M, D));
+    GPT_TRY(check_test_orders(model, c->n_maxsum, warp, nstar, M, D));
     hipStream_t st = c->stream;
     double *dXs, *dKst, *dmean;
     int32_t *dns;
@@ -83,10 +53,10 @@ extern "C" int gpt_predict(gpt_ctx *c, const double *Xstar, const int32_t *nstar
         double *dKx;
         GPT_TRY(ensure(c, SLOT_TK, (size_t)MP * c->NxP * sizeof(double), (void **)&dKx));
         GPT_TRY(launch_zero2d(st, MP, c->NxP, dKx, c->NxP));
-        GPT_TRY(kbuild_terms(c, st, c->terms, 0, mXs, dns, M, mX, c->dn, Nx, 0, 0, 0, nullptr, 0.0, 0.0, dKx, c->NxP, dSs, mS));
+        GPT_TRY(kbuild_terms(st, model, 0, mXs, dns, M, mX, c->dn, Nx, 0, 0, 0, nullptr, 0.0, 0.0, dKx, c->NxP, dSs, mS));
         GPT_TRY(gemm_nt(c, st, MP, round_up(N, 64), c->NxP, 1.0, dKx, c->NxP, c->dT, c->NxP, 0.0, dKst, n128, 0));
     } else
-    GPT_TRY(kbuild_terms(c, st, c->terms, 0, mXs, dns, M, mX, c->dn, N, 0, 0, 0, nullptr, 0.0, 0.0, dKst, n128, dSs, mS));
+    GPT_TRY(kbuild_terms(st, model, 0, mXs, dns, M, mX, c->dn, N, 0, 0, 0, nullptr, 0.0, 0.0, dKst, n128, dSs, mS));
     GPT_TRY(ensure_alpha(c));
     GPT_TRY(launch_gemv_n(st, M, N, dKst, n128, c->d_alpha, dmean));
     GPT_HIP_CHECK(hipMemcpyAsync(mean_out, dmean, (size_t)M * sizeof(double), hipMemcpyDeviceToHost, st));
@@ -99,12 +69,11 @@ extern "C" int gpt_predict(gpt_ctx *c, const double *Xstar, const int32_t *nstar
         if (want == 1) {
             double *dkd;
             GPT_TRY(ensure(c, SLOT_VEC2, (size_t)M * sizeof(double), (void **)&dkd));
-            for (size_t t = 0; t < c->terms.size(); t++) {
-                KParams ks = c->terms[t];
+            for (int t = 0; t < model.nterms; t++) {
+                KParams ks = model.f1[t];
                 ks.symmetric = 1;
                 ks.hyper_deriv = -1;
-                GPT_TRY(launch_kpairs(st, ks, mXs, mXs, dns, dns, M, dkd, t > 0 ? 1 : 0,
-                                      (t < c->terms2.size() && c->terms2[t].kernel_id >= 0) ? &c->terms2[t] : nullptr));
+                GPT_TRY(launch_kpairs(st, ks, mXs, mXs, dns, dns, M, dkd, t > 0 ? 1 : 0, model.second(t)));
             }
             if (warp) GPT_TRY(launch_warp_scale_diag(st, dkd, dSs, M));
             GPT_TRY(launch_rowsumsq_sub(st, M, n128, dV, n128, dkd, dvar));
@@ -131,7 +100,7 @@ extern "C" int gpt_predict(gpt_ctx *c, const double *Xstar, const int32_t *nstar
         const int64_t LDC = round_up(M, 128);
         GPT_TRY(ensure(c, SLOT_KSS, (size_t)LDC * LDC * sizeof(double), (void **)&dcov));
         GPT_TRY(launch_zero2d(st, LDC, LDC, dcov, LDC));
-        GPT_TRY(kbuild_terms(c, st, c->terms, 1, mXs, dns, M, mXs, dns, M, 0, 0, 0, nullptr, 0.0, 0.0, dcov, LDC, dSs, dSs));
+        GPT_TRY(kbuild_terms(st, model, 1, mXs, dns, M, mXs, dns, M, 0, 0, 0, nullptr, 0.0, 0.0, dcov, LDC, dSs, dSs));
         if (noise_params) GPT_TRY(launch_add_noise_sym(st, kn, dXs, dns, M, dcov, LDC));
         c->cov_M = 0;
         const int64_t CB = 512;

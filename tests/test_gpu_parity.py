@@ -2639,3 +2639,234 @@ def test_g12_draw_sample_and_predict_samples_against_the_reference(g, golden, ke
     close(o["mean"], G[key + "mc_mean"], 1e-10, "full_MC mean")
     close(o["cov"], G[key + "mc_cov"], 1e-10, "full_MC cov")
     close(o["std"], np.sqrt(np.diag(G[key + "mc_cov"])), 1e-10, "full_MC std")
+
+
+# ---------------------------------------------------------------- refusals of the C ABI, entry point by entry point ----
+# One rule, every entry point that carries it, through _lib.Context (the C status decides the exception class: GPT_E_ARG /
+# GPT_E_VALUE -> ValueError, GPT_E_NOTIMPL -> NotImplementedError).  Everything here is refused on the host in front of any launch,
+# or is a valid call.
+_SE, _M52, _NOISE, _RQ, _MAT, _GIBBS = 0, 1, 2, 4, 5, 7
+_P = {_SE: [1.0, 2.0], _M52: [1.0, 2.0], _RQ: [1.0, 1.5, 2.0], _MAT: [1.0, 10.5, 2.0], _GIBBS: [1.1, 0.8, 0.6, 0.3, 0.5], _NOISE: [0.1]}
+_NFIT = 24
+
+
+def _fit_routes(c, product):
+    """name -> callable(terms) for the fit entry points that can carry `terms` (as Context.fit_terms takes them)."""
+    rs = np.random.RandomState(11)
+    y, err = rs.randn(_NFIT), np.full(_NFIT, 0.1)
+    Y, nv = np.tile(y, (2, 1)), np.zeros(2)
+
+    def flat(terms):
+        return [np.asarray(t[1], dtype=float) for t in terms]
+    routes = {
+        "fit_terms": lambda terms: c.fit_terms(terms, 0.0, y, err, 0.0),
+        "fit_batch_terms": lambda terms: c.fit_batch_terms([terms, terms], nv, Y, err, 0.0),
+    }
+    if not product:
+        routes["fit_sum"] = lambda terms: c.fit_sum([t[0] for t in terms], flat(terms), 0.0, y, err, 0.0)
+        routes["fit_batch_sum"] = lambda terms: c.fit_batch_sum(
+            [t[0] for t in terms], np.tile(np.concatenate(flat(terms)), (2, 1)), [len(t[1]) for t in terms], nv, Y, err, 0.0)
+    return routes
+
+
+def _single_routes(c):
+    rs = np.random.RandomState(11)
+    y, err = rs.randn(_NFIT), np.full(_NFIT, 0.1)
+    return {
+        "fit": lambda kid, p: c.fit(kid, p, 0.0, y, err, 0.0),
+        "fit_batch": lambda kid, p: c.fit_batch(kid, np.tile(np.asarray(p, dtype=float), (2, 1)), np.zeros(2), np.tile(y, (2, 1)), err, 0.0),
+    }
+
+
+def _refused(exc, terms, c, tag):
+    """`terms` is refused with `exc` by every fit entry point that can carry it (a single non-product term: all six)."""
+    product = any(len(t) == 4 for t in terms)
+    for name, call in _fit_routes(c, product).items():
+        with pytest.raises(exc):
+            call(terms)
+            pytest.fail("%s: %s accepted %r" % (tag, name, [t[0::2] for t in terms]))
+    if len(terms) == 1 and not product:
+        for name, call in _single_routes(c).items():
+            with pytest.raises(exc):
+                call(terms[0][0], terms[0][1])
+                pytest.fail("%s: %s accepted kernel %d" % (tag, name, terms[0][0]))
+
+
+def _fits(terms, c, tag):
+    product = any(len(t) == 4 for t in terms)
+    for name, call in _fit_routes(c, product).items():
+        out = call(terms)
+        assert np.all(np.isfinite(out[0])), (tag, name, out)
+    if len(terms) == 1 and not product:
+        for name, call in _single_routes(c).items():
+            out = call(terms[0][0], terms[0][1])
+            assert np.all(np.isfinite(out[0])), (tag, name, out)
+
+
+def _points_1d(top_order, N=_NFIT):
+    """N points in [0, 1], 1-D: mostly values, two first derivatives and ONE row of order `top_order` (the last)."""
+    X = np.linspace(0.0, 1.0, N)[:, None]
+    n = np.zeros((N, 1), dtype=int)
+    n[3] = n[N // 2] = 1
+    n[-1] = top_order
+    return X, n
+
+
+def test_fit_refusals_agree_across_the_six_fit_entry_points():
+    from gptools_amd import _lib
+    c = _lib.Context(0)
+    try:
+        t = lambda kid: (kid, _P[kid])
+        prod = lambda k1, k2: (k1, _P[k1], k2, _P[k2])
+        # --- orders <= 1: ids and parameter counts
+        c.set_data(*_points_1d(1))
+        _fits([t(_SE)], c, "plain")
+        _fits([t(_RQ), prod(_SE, _GIBBS)], c, "plain sum with a product")
+        _refused(ValueError, [t(_NOISE)], c, "not a native fit kernel")
+        _refused(ValueError, [t(_SE), t(_NOISE)], c, "not a native fit kernel, second term")
+        _refused(ValueError, [prod(_SE, _NOISE)], c, "not a native fit kernel as second factor")
+        _refused(ValueError, [(_SE, [1.0, 2.0, 3.0])], c, "parameter count")
+        _refused(ValueError, [(_RQ, [1.0, 2.0])], c, "parameter count")
+        _refused(ValueError, [t(_SE), (_GIBBS, _P[_GIBBS][:4])], c, "parameter count, second term")
+        _refused(ValueError, [(_SE, _P[_SE], _SE, [1.0])], c, "parameter count of a second factor")
+        _refused(ValueError, [(_SE, [], _SE, _P[_SE])], c, "product split nparams1 = 0")
+        # --- a training row of order 2: Gibbs terms
+        c.set_data(*_points_1d(2))
+        _fits([t(_RQ)], c, "order 2 without Gibbs")
+        _refused(NotImplementedError, [t(_GIBBS)], c, "Gibbs, order 2")
+        _refused(NotImplementedError, [t(_SE), t(_GIBBS)], c, "Gibbs second term, order 2")
+        _refused(NotImplementedError, [prod(_SE, _GIBBS)], c, "Gibbs as second factor, order 2")
+        # --- a training row of order 9: 2 * n_maxsum = 18 > GPT_RQ_MAXORD = 16
+        c.set_data(*_points_1d(9))
+        _refused(ValueError, [t(_RQ)], c, "RQ, order 9")
+        _refused(ValueError, [t(_MAT)], c, "Matern, order 9")
+        _refused(ValueError, [t(_SE), t(_RQ)], c, "RQ second term, order 9")
+        _refused(ValueError, [prod(_SE, _SE)], c, "SE * SE, order 9")
+        _fits([t(_SE)], c, "a lone SE term is not subject to the limit")
+        # which refusal wins is decided term by term
+        _refused(ValueError, [t(_RQ), t(_GIBBS)], c, "[RQ, Gibbs], order 9")
+        _refused(NotImplementedError, [t(_GIBBS), t(_RQ)], c, "[Gibbs, RQ], order 9")
+        # --- order 8: 16 is within the limit
+        c.set_data(*_points_1d(8))
+        _fits([t(_RQ)], c, "RQ, order 8")
+    finally:
+        c.close()
+
+
+def test_test_point_refusals_agree_between_predict_and_predict_batch():
+    from gptools_amd import _lib
+    c = _lib.Context(0)
+    rs = np.random.RandomState(12)
+    y, err = rs.randn(_NFIT), np.full(_NFIT, 0.1)
+    Xs = np.array([[0.21], [0.47], [0.83]])
+
+    def ns(order):
+        return np.array([[0], [order], [1]])
+
+    def routes(terms):
+        """the same model resident for gpt_predict (after gpt_fit_terms) and for gpt_predict_batch (after gpt_fit_batch_terms)"""
+        c.fit_terms(terms, 0.0, y, err, 0.0)
+        c.fit_batch_terms([terms, terms], np.zeros(2), np.tile(y, (2, 1)), err, 0.0)
+        return {"predict": lambda n: c.predict(Xs, n, 0)[0],
+                "predict_batch": lambda n: c.predict_batch(Xs, n, [1, 1], want_var=False)[0]}
+    try:
+        t = lambda kid: (kid, _P[kid])
+        prod = lambda k1, k2: (k1, _P[k1], k2, _P[k2])
+        c.set_data(*_points_1d(1))
+        for terms, exc, tag in (([t(_M52)], ValueError, "M52"), ([t(_SE), prod(_SE, _M52)], ValueError, "M52 second factor"),
+                                ([t(_GIBBS)], NotImplementedError, "Gibbs"),
+                                ([t(_SE), prod(_SE, _GIBBS)], NotImplementedError, "Gibbs second factor")):
+            for name, call in routes(terms).items():
+                assert np.all(np.isfinite(call(ns(1)))), (tag, name)
+                with pytest.raises(exc):
+                    call(ns(2))
+                    pytest.fail("%s: %s accepted a test row of order 2" % (tag, name))
+        # training orders up to 7: a test row of order 9 meets 9 + max(9, 7) = 18 > 16, one of order 8 exactly 16
+        c.set_data(*_points_1d(7))
+        for terms, tag in (([t(_RQ)], "RQ"), ([t(_MAT)], "Matern"), ([t(_SE), prod(_SE, _SE)], "product"),
+                           ([prod(_SE, _RQ)], "RQ second factor")):
+            for name, call in routes(terms).items():
+                assert np.all(np.isfinite(call(ns(8)))), (tag, name)
+                with pytest.raises(ValueError):
+                    call(ns(9))
+                    pytest.fail("%s: %s accepted a test row of order 9" % (tag, name))
+        c.fit_terms([t(_SE)], 0.0, y, err, 0.0)
+        assert np.all(np.isfinite(c.predict(Xs, ns(9), 0)[0]))            # (a sum of lone SE terms has no such limit)
+    finally:
+        c.close()
+
+
+def test_pair_list_and_gram_block_refusals_agree_across_kpairs_and_kbuild():
+    from gptools_amd import _lib
+    c = _lib.Context(0)
+    M = 5
+    X, Xo = np.linspace(0.0, 1.0, M)[:, None], np.linspace(0.1, 0.9, M)[:, None]
+
+    def orders(**rows):
+        n = np.zeros((M, 1), dtype=int)
+        for r, o in rows.items():
+            n[int(r[1:])] = o
+        return n
+    z = orders()
+
+    def calls(k1, k2):
+        """name -> callable(ni, nj) for the one-kernel (k2 None) or product entry points; `pairs`: rows matched one to one"""
+        if k2 is None:
+            return {"kpairs": lambda ni, nj: c.kpairs(k1, _P[k1], X, Xo, ni, nj),
+                    "kbuild": lambda ni, nj: c.kbuild(k1, _P[k1], X, ni, Xo, nj),
+                    "kbuild sym": lambda ni, nj: c.kbuild(k1, _P[k1], X, ni)}
+        return {"kpairs": lambda ni, nj: c.kpairs2(k1, _P[k1], k2, _P[k2], X, Xo, ni, nj),
+                "kbuild": lambda ni, nj: c.kbuild2(k1, _P[k1], k2, _P[k2], X, ni, Xo, nj),
+                "kbuild sym": lambda ni, nj: c.kbuild2(k1, _P[k1], k2, _P[k2], X, ni)}
+
+    def check(k1, k2, ni, nj, exc, only=None):
+        for name, call in calls(k1, k2).items():
+            if only and name not in only:
+                continue
+            if exc is None:
+                assert np.all(np.isfinite(call(ni, nj))), (k1, k2, name)
+            else:
+                with pytest.raises(exc):
+                    call(ni, nj)
+                    pytest.fail("kernels (%s, %s): %s accepted the orders" % (k1, k2, name))
+    try:
+        for k1, k2 in ((_M52, None), (_SE, _M52), (_M52, _SE)):                      # M52: a row summing to 2
+            check(k1, k2, orders(r1=1), orders(r2=1), None)
+            check(k1, k2, orders(r1=2), z, ValueError)
+            check(k1, k2, z, orders(r1=2), ValueError, only=("kpairs", "kbuild"))
+        for k1, k2 in ((_GIBBS, None), (_SE, _GIBBS), (_GIBBS, _RQ)):                # Gibbs: an order of 2
+            check(k1, k2, orders(r1=1), orders(r2=1), None)
+            check(k1, k2, orders(r1=2), z, NotImplementedError)
+            check(k1, k2, z, orders(r1=2), NotImplementedError, only=("kpairs", "kbuild"))
+        for k1, k2 in ((_RQ, None), (_MAT, None), (_SE, _SE), (_SE, _RQ)):           # GPT_RQ_MAXORD = 16
+            # a pair list meets row i with row i, a Gram block the worst row with the worst column
+            check(k1, k2, orders(r1=9), orders(r1=8), ValueError, only=("kpairs", "kbuild"))          # 17 either way
+            check(k1, k2, orders(r1=9), orders(r2=8), None, only=("kpairs",))                          # pairs: 9 and 8
+            check(k1, k2, orders(r1=9), orders(r2=8), ValueError, only=("kbuild",))                    # block: 9 + 8
+            check(k1, k2, orders(r1=8), orders(r1=8), None, only=("kpairs", "kbuild"))                 # 16
+            check(k1, k2, orders(r1=9), z, ValueError, only=("kbuild sym",))                           # 18
+            check(k1, k2, orders(r1=8), z, None, only=("kbuild sym",))                                 # 16
+        # no points: valid parameters give an empty result, a wrong parameter count is still refused
+        e, ez = np.zeros((0, 1)), np.zeros((0, 1), dtype=int)
+        good, bad = _P[_RQ], _P[_RQ][:2]
+        assert c.kpairs(_RQ, good, e, e, ez, ez).shape == (0,)
+        assert c.kpairs2(_SE, _P[_SE], _RQ, good, e, e, ez, ez).shape == (0,)
+        assert c.kbuild(_RQ, good, e, ez).shape == (0, 0)
+        assert c.kbuild(_RQ, good, e, ez, X, z).shape == (0, M)
+        assert c.kbuild(_RQ, good, X, z, e, ez).shape == (M, 0)
+        assert c.kbuild2(_SE, _P[_SE], _RQ, good, e, ez).shape == (0, 0)
+        assert c.kbuild2(_SE, _P[_SE], _RQ, good, e, ez, X, z).shape == (0, M)
+        assert c.kbuild2(_SE, _P[_SE], _RQ, good, X, z, e, ez).shape == (M, 0)
+        # ... and the points of an empty block are not looked at: no pair could break an order rule
+        assert c.kbuild(_RQ, good, X, orders(r1=9), e, ez).shape == (M, 0)
+        assert c.kbuild(_GIBBS, _P[_GIBBS], e, ez, X, orders(r1=2)).shape == (0, M)
+        assert c.kbuild2(_SE, _P[_SE], _M52, _P[_M52], X, orders(r1=2), e, ez).shape == (M, 0)
+        assert c.kbuild2(_GIBBS, _P[_GIBBS], _RQ, good, e, ez, X, orders(r1=9)).shape == (0, M)
+        for call in (lambda: c.kpairs(_RQ, bad, e, e, ez, ez), lambda: c.kpairs2(_SE, _P[_SE], _RQ, bad, e, e, ez, ez),
+                     lambda: c.kpairs2(_SE, [1.0], _RQ, good, e, e, ez, ez), lambda: c.kbuild(_RQ, bad, e, ez),
+                     lambda: c.kbuild(_RQ, bad, e, ez, X, z), lambda: c.kbuild2(_SE, _P[_SE], _RQ, bad, e, ez),
+                     lambda: c.kbuild2(_SE, _P[_SE], _RQ, bad, X, z, e, ez)):
+            with pytest.raises(ValueError):
+                call()
+    finally:
+        c.close()
