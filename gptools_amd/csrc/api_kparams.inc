@@ -138,6 +138,36 @@ static int make_kparams(int kernel_id, const double *params, int nparams, int D,
             kp->g_x0[0] = params[6];
             kp->g_x0[1] = params[7];
         }
+    } else if (kernel_id == GPT_KERNEL_GIBBS_CUBIC || kernel_id == GPT_KERNEL_GIBBS_QUINTIC || kernel_id == GPT_KERNEL_GIBBS_EXPGAUSS) {
+        // GibbsKernel1dCubicBucket / GibbsKernel1dQuinticBucket [sigma_f, l_1, l_2, l_3, x_0, w_1, w_2, w_3] (ref: gibbs.py:603-801);
+        // GibbsKernel1dExpGauss [sigma_f, l_0, mu_1..G, sigma_1..G, beta_1..G] (ref: gibbs.py:804-902).  The parameters after
+        // sigma_f go to the device as they are (gibbs_lfunc.hpp forms l and l' from them in the reference's order of operations)
+        const bool eg = kernel_id == GPT_KERNEL_GIBBS_EXPGAUSS;
+        if (D != 1) {
+            gpt_set_error("Gibbs kernel only supports 1d data.");
+            return GPT_E_ARG;
+        }
+        if (eg) {
+            if (nparams < 5 || (nparams - 2) % 3 != 0) {
+                gpt_set_error("kernel %d expects 3 G + 2 params (G >= 1 Gaussians), got %d", kernel_id, nparams);
+                return GPT_E_ARG;
+            }
+            if ((nparams - 2) / 3 > GPT_GIBBS_MAX_GAUSS) {
+                gpt_set_error("kernel %d: %d Gaussians, the device kernel takes GPT_GIBBS_MAX_GAUSS = %d at most", kernel_id,
+                              (nparams - 2) / 3, GPT_GIBBS_MAX_GAUSS);
+                return GPT_E_ARG;
+            }
+        } else if (nparams != 8) {
+            gpt_set_error("kernel %d expects %d params, got %d", kernel_id, 8, nparams);
+            return GPT_E_ARG;
+        }
+        if (hyper_deriv >= 0) {
+            gpt_set_error("Hyperparameter derivatives have not been implemented!");      // ref: gibbs.py:319-322
+            return GPT_E_NOTIMPL;
+        }
+        kp->sigma = params[0];
+        kp->g_nt = eg ? (nparams - 2) / 3 : 0;
+        for (int q = 1; q < nparams; q++) kp->g_raw[q - 1] = params[q];
     } else if (kernel_id == GPT_KERNEL_DIAGNOISE || kernel_id == GPT_KERNEL_ZERO) {
         if (nparams != 1) {
             gpt_set_error("noise kernels expect 1 param, got %d", nparams);
@@ -200,11 +230,6 @@ static int check_rq_orders(const int32_t *ni, int64_t M, const int32_t *nj, int6
     return GPT_OK;
 }
 
-static bool is_gibbs(int kid)
-{
-    return kid == GPT_KERNEL_GIBBS_TANH || kid == GPT_KERNEL_GIBBS_DTANH;
-}
-
 // RationalQuadratic / Matern: derivatives by the chain rule with GPT_RQ_MAXORD + 1 Faa di Bruno coefficients (check_rq_orders)
 static bool is_chain(int kid)
 {
@@ -237,7 +262,7 @@ static int check_warp_orders(const int32_t *n, int64_t M, int D)
 
 static bool native_fit_kernel(int kid)
 {
-    return kid == GPT_KERNEL_SE || kid == GPT_KERNEL_M52 || is_chain(kid) || is_gibbs(kid);
+    return kid == GPT_KERNEL_SE || kid == GPT_KERNEL_M52 || is_chain(kid) || gibbs_kid(kid);
 }
 
 // ------------------------------------------------------------------------------------------------
@@ -261,7 +286,7 @@ struct ModelKernel {
 // SE or Matern52 term has no limit here (Matern52's own rule is the Python host's).
 static int check_train_orders(int k1, int k2, long n_maxsum)
 {
-    if ((is_gibbs(k1) || is_gibbs(k2)) && n_maxsum > 1) {
+    if ((gibbs_kid(k1) || gibbs_kid(k2)) && n_maxsum > 1) {
         gpt_set_error("%s", GIBBS_ORDER_MSG);
         return GPT_E_NOTIMPL;
     }
@@ -304,7 +329,7 @@ static int parse_model(int D, long n_maxsum, int nterms, const int *ids, const i
         m->any_prod = m->any_prod || prod;
         m->has_m52 = m->has_m52 || k1 == GPT_KERNEL_M52 || k2 == GPT_KERNEL_M52;
         m->has_chain = m->has_chain || is_chain(k1) || is_chain(k2);
-        m->has_gibbs = m->has_gibbs || is_gibbs(k1) || is_gibbs(k2);
+        m->has_gibbs = m->has_gibbs || gibbs_kid(k1) || gibbs_kid(k2);
         p += nparams[t];
     }
     m->nparams = (int)(p - params);
@@ -346,7 +371,7 @@ static int check_pair_orders(const KParams &k1, const KParams *k2, const int32_t
         GPT_TRY(check_m52_orders(nj, P, D));
     }
     if (is_chain(id1) || k2) GPT_TRY(check_rq_orders(ni, M, nj, P, D, pairwise));
-    if (is_gibbs(id1) || is_gibbs(id2)) {
+    if (gibbs_kid(id1) || gibbs_kid(id2)) {
         GPT_TRY(check_gibbs_orders(ni, M, D));
         GPT_TRY(check_gibbs_orders(nj, P, D));
     }

@@ -46,9 +46,17 @@ struct KParams {
     int symmetric;        // DiagonalNoiseKernel only fires for symmetric calls
     double sigma;         // params[0]
     double alpha;         // RationalQuadraticKernel: params[1]
-    double l[GPT_MAX_DIM];      // length scales (SE / M52)
-    double inv_l[GPT_MAX_DIM];  // 1 / l
-    double inv_var[GPT_MAX_DIM];// 1 / l^2
+    union {
+        struct {
+            double l[GPT_MAX_DIM];      // length scales (SE / M52)
+            double inv_l[GPT_MAX_DIM];  // 1 / l
+            double inv_var[GPT_MAX_DIM];// 1 / l^2
+        };
+        // bucket and exp-Gauss Gibbs kernels (1-D, no length scales of the kind above): the parameters after sigma_f as the ABI
+        // hands them over (gibbs_lfunc.hpp reads them raw).  In the place of the three arrays, so that sizeof(KParams) is what it
+        // was: the product kernels keep both factors' KParams on the stack and pay for every byte in scratch
+        double g_raw[3 * GPT_GIBBS_MAX_GAUSS + 1];
+    };
     int noise_n[GPT_MAX_DIM];   // DiagonalNoiseKernel.n
     // MaternKernel (general nu): nu = alpha; constants of make_kparams (api.hip)
     double m_cnu;             // 2^(1-nu) / Gamma(nu)
@@ -61,8 +69,30 @@ struct KParams {
     double m_g[2], m_gm[2], m_nus[2];             // Gamma(nu_s), Gamma(-nu_s), nu_s for the small-y series (nu_s = nu, or nu -+ 0.001)
     // Gibbs kernels (1-D): l(x) = g_c + sum_q g_amp[q] tanh((x - g_x0[q]) / g_w[q]) over g_nt terms (1: tanh warp, 2: double tanh)
     double g_amp[2], g_w[2], g_x0[2], g_c;
-    int g_nt, g_pad_;
+    int g_nt, g_pad_;      // (exp-Gauss: g_nt = the number of Gaussians)
 };
+
+static_assert(3 * GPT_GIBBS_MAX_GAUSS + 1 <= 3 * GPT_MAX_DIM, "g_raw must fit the arrays it shares its place with");
+static_assert(sizeof(KParams) == 656, "KParams travels by value in the kernel arguments (two per product term)");
+
+// the Gibbs kernels (1-D, derivative orders <= 1): the tanh warps, the buckets, the exponential of Gaussians
+__host__ __device__ constexpr bool gibbs_kid(int kid)
+{
+    return kid == GPT_KERNEL_GIBBS_TANH || kid == GPT_KERNEL_GIBBS_DTANH || kid == GPT_KERNEL_GIBBS_CUBIC ||
+           kid == GPT_KERNEL_GIBBS_QUINTIC || kid == GPT_KERNEL_GIBBS_EXPGAUSS;
+}
+
+// ... those of them added after the tanh warps (kernel ids 9-11), and the builder's INTERNAL id of a product with such a factor
+// (never in the ABI): the single-matrix product kernels at num_dim 1 were already out of registers, and carrying the three
+// extra length-scale branches cost them ~350 bytes more scratch per lane whatever the model.  So a product kernel
+// compiles those branches only as GPT_KID_PRODUCT_GM, which the launchers choose when a factor needs them (kbuild_prod.hip);
+// GPT_KERNEL_PRODUCT is the code it was.  The batched kernels (kbuild_batch.hip), whose registers had room, take
+// GPT_KID_PRODUCT_GM for every 1-D product: same registers, same scratch as before.
+__host__ __device__ constexpr bool gibbs_more_kid(int kid)
+{
+    return kid == GPT_KERNEL_GIBBS_CUBIC || kid == GPT_KERNEL_GIBBS_QUINTIC || kid == GPT_KERNEL_GIBBS_EXPGAUSS;
+}
+#define GPT_KID_PRODUCT_GM 106
 
 // A cross-stream edge without an event: the kernel that completes a piece of work raises a 32-bit word in device
 // memory when its LAST workgroup is through (its results written with write-through stores and drained first) and the

@@ -1,0 +1,89 @@
+// gibbs_lfunc.hpp -- the closed-form length-scale functions l(x), l'(x) of the bucket and exp-Gauss Gibbs kernels
+// (GPT_KERNEL_GIBBS_CUBIC / _QUINTIC / _EXPGAUSS, include/gpt_hip.h; ref: gptools/kernel/gibbs.py:603-651, :695-760, :804-855),
+// from the raw parameters after sigma_f.  The functions are __host__ __device__ and need nothing of HIP, so that the ordinary
+// host compiler can build them into a test aid (test_aids/gibbs_host.cpp) and a CPU-only test can compare them with the numpy
+// functions of gptools_amd/kernel/gibbs.py.  kpair.hpp (gibbs_point) calls them once per point, never per pair.
+//
+// The buckets are the reference's arithmetic LITERALLY: the section ends in its order of operations, every section value
+// formed everywhere and multiplied by its 0/1 mask, the products summed left to right.  The reference is DEFINED by that sum: a
+// point exactly at a section end belongs to exactly one mask; a non-finite section polynomial times a zero mask is NaN (w_1 = 0:
+// NaN everywhere; a width so small that the quintic's fifth power overflows: NaN outside that section); negative widths make
+// the masks overlap or leave gaps.  A branch that picked one section would give other numbers in each of these cases.  Integer
+// powers are repeated multiplication (within 2 ulp of the reference's pow, and not the ~100 instructions of a device pow).
+#pragma once
+#include <math.h>
+#include "../../include/gpt_hip.h"
+
+#ifndef GPT_HD
+#ifdef __HIPCC__
+#define GPT_HD __host__ __device__
+#else
+#define GPT_HD
+#endif
+#endif
+
+// the five 0/1 masks of a bucket with section ends e0 < e1 <= e2 < e3 (for positive widths), gibbs.py:633-639
+struct GibbsBucketMasks {
+    double left, join1, mid, join2, right;
+};
+
+GPT_HD static inline GibbsBucketMasks gpt_gibbs_bucket_masks(double x, double x1, double x2, double w1, double w3)
+{
+    GibbsBucketMasks m;
+    m.left = (x <= (x1 - w1 / 2.0)) ? 1.0 : 0.0;
+    m.join1 = ((x > (x1 - w1 / 2.0)) && (x < (x1 + w1 / 2.0))) ? 1.0 : 0.0;
+    m.mid = ((x >= (x1 + w1 / 2.0)) && (x <= x2 - w3 / 2.0)) ? 1.0 : 0.0;
+    m.join2 = ((x > (x2 - w3 / 2.0)) && (x < (x2 + w3 / 2.0))) ? 1.0 : 0.0;
+    m.right = (x >= (x2 + w3 / 2.0)) ? 1.0 : 0.0;
+    return m;
+}
+
+// p = [l_1, l_2, l_3, x_0, w_1, w_2, w_3]
+GPT_HD static inline void gpt_gibbs_cubic_bucket(const double *p, double x, double *l, double *dl)
+{
+    const double l1 = p[0], l2 = p[1], l3 = p[2], x0 = p[3], w1 = p[4], w2 = p[5], w3 = p[6];
+    const double x1 = x0 - w2 / 2.0 - w1 / 2.0;
+    const double x2 = x0 + w2 / 2.0 + w3 / 2.0;
+    const double s1 = (x - x1 + w1 / 2.0) / w1;
+    const double s2 = (x - x2 + w3 / 2.0) / w3;
+    const GibbsBucketMasks m = gpt_gibbs_bucket_masks(x, x1, x2, w1, w3);
+    const double s1q = s1 * s1, s2q = s2 * s2;
+    *l = l1 * m.left + (-2.0 * (l2 - l1) * (s1q * s1 - 3.0 / 2.0 * s1q) + l1) * m.join1 + l2 * m.mid +
+         (-2.0 * (l3 - l2) * (s2q * s2 - 3.0 / 2.0 * s2q) + l2) * m.join2 + l3 * m.right;
+    *dl = (-2.0 * (l2 - l1) * (3.0 * s1q - 3.0 * s1) / w1) * m.join1 + (-2.0 * (l3 - l2) * (3.0 * s2q - 3.0 * s2) / w3) * m.join2;
+}
+
+// p as for the cubic bucket
+GPT_HD static inline void gpt_gibbs_quintic_bucket(const double *p, double x, double *l, double *dl)
+{
+    const double l1 = p[0], l2 = p[1], l3 = p[2], x0 = p[3], w1 = p[4], w2 = p[5], w3 = p[6];
+    const double x1 = x0 - w2 / 2.0 - w1 / 2.0;
+    const double x2 = x0 + w2 / 2.0 + w3 / 2.0;
+    const double s1 = 2.0 * (x - x1) / w1;
+    const double s3 = 2.0 * (x - x2) / w3;
+    const GibbsBucketMasks m = gpt_gibbs_bucket_masks(x, x1, x2, w1, w3);
+    const double s1q = s1 * s1, s1c = s1q * s1, s1f = s1q * s1q, s1v = s1f * s1;
+    const double s3q = s3 * s3, s3c = s3q * s3, s3f = s3q * s3q, s3v = s3f * s3;
+    *l = l1 * m.left + (0.5 * (l2 - l1) * (3.0 / 8.0 * s1v - 5.0 / 4.0 * s1c + 15.0 / 8.0 * s1) + (l1 + l2) / 2.0) * m.join1 +
+         l2 * m.mid + (0.5 * (l3 - l2) * (3.0 / 8.0 * s3v - 5.0 / 4.0 * s3c + 15.0 / 8.0 * s3) + (l2 + l3) / 2.0) * m.join2 +
+         l3 * m.right;
+    *dl = (0.5 * (l2 - l1) * (5.0 * 3.0 / 8.0 * s1f - 3.0 * 5.0 / 4.0 * s1q + 15.0 / 8.0) / w1) * m.join1 +
+          (0.5 * (l3 - l2) * (5.0 * 3.0 / 8.0 * s3f - 3.0 * 5.0 / 4.0 * s3q + 15.0 / 8.0) / w3) * m.join2;
+}
+
+// p = [l_0, mu_1 .. mu_G, sigma_1 .. sigma_G, beta_1 .. beta_G]:  S1 = sum_i beta_i exp(-(x - mu_i)^2 / (2 sigma_i^2)),
+// S2 = sum_i beta_i exp(..) (x - mu_i) / sigma_i^2 in the reference's loop order;  l = l_0 exp(S1),  l' = -l_0 exp(S1) S2
+GPT_HD static inline void gpt_gibbs_exp_gauss(const double *p, int G, double x, double *l, double *dl)
+{
+    const double l0 = p[0];
+    double S1 = 0.0, S2 = 0.0;
+    for (int i = 0; i < G; i++) {
+        const double d = x - p[1 + i], s = p[1 + G + i], b = p[1 + 2 * G + i];
+        const double term = b * exp(-(d * d) / (2.0 * (s * s)));
+        S1 += term;
+        S2 += term * d / (s * s);
+    }
+    const double e = exp(S1);
+    *l = l0 * e;
+    *dl = -l0 * e * S2;
+}

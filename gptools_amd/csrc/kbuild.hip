@@ -67,7 +67,7 @@ static int kbuild_dispatch_d(hipStream_t st, const KParams &kp, const double *dX
                            (const KParams *)nullptr, (const double *)nullptr, (int64_t)0, KParams(), (const KParams *)nullptr,  \
                            (const double *)nullptr, (const double *)nullptr);  \
         break;
-    if constexpr (KID == GPT_KERNEL_GIBBS_TANH || KID == GPT_KERNEL_GIBBS_DTANH) {      // (1-D kernels: one instantiation)
+    if constexpr (gibbs_kid(KID)) {      // (1-D kernels: one instantiation)
         switch (kp.D) {
             KB_CASE(1)
         default:
@@ -121,6 +121,15 @@ int launch_kbuild(hipStream_t st, const KParams &kp, const double *dXi, const in
     case GPT_KERNEL_GIBBS_DTANH:
         return kbuild_dispatch_d<GPT_KERNEL_GIBBS_DTANH>(st, kp, dXi, dni, M, dXj, dnj, P, lower_only, i0, j0, d_err_y,
                                                          noise_var, diag_add, dK, ldk, accumulate, dSi, dSj);
+    case GPT_KERNEL_GIBBS_CUBIC:
+        return kbuild_dispatch_d<GPT_KERNEL_GIBBS_CUBIC>(st, kp, dXi, dni, M, dXj, dnj, P, lower_only, i0, j0, d_err_y,
+                                                         noise_var, diag_add, dK, ldk, accumulate, dSi, dSj);
+    case GPT_KERNEL_GIBBS_QUINTIC:
+        return kbuild_dispatch_d<GPT_KERNEL_GIBBS_QUINTIC>(st, kp, dXi, dni, M, dXj, dnj, P, lower_only, i0, j0, d_err_y,
+                                                           noise_var, diag_add, dK, ldk, accumulate, dSi, dSj);
+    case GPT_KERNEL_GIBBS_EXPGAUSS:
+        return kbuild_dispatch_d<GPT_KERNEL_GIBBS_EXPGAUSS>(st, kp, dXi, dni, M, dXj, dnj, P, lower_only, i0, j0, d_err_y,
+                                                            noise_var, diag_add, dK, ldk, accumulate, dSi, dSj);
     default:
         gpt_set_error("kbuild: unknown kernel_id %d", kp.kernel_id);
         return GPT_E_ARG;
@@ -136,7 +145,7 @@ static int kpairs_dispatch_d(hipStream_t st, const KParams &kp, const double *dX
     case DD:                                                                                          \
         hipLaunchKernelGGL((kpairs_kernel<KID, DD>), grid, block, 0, st, kp, dXi, dXj, dni, dnj, M, dout, accumulate, KParams()); \
         break;
-    if constexpr (KID == GPT_KERNEL_GIBBS_TANH || KID == GPT_KERNEL_GIBBS_DTANH) {
+    if constexpr (gibbs_kid(KID)) {
         switch (kp.D) {
             KP_CASE(1)
         default:
@@ -169,6 +178,9 @@ int launch_kpairs(hipStream_t st, const KParams &kp, const double *dXi, const do
     case GPT_KERNEL_MATERN: return kpairs_dispatch_d<GPT_KERNEL_MATERN>(st, kp, dXi, dXj, dni, dnj, M, dout, accumulate);
     case GPT_KERNEL_GIBBS_TANH: return kpairs_dispatch_d<GPT_KERNEL_GIBBS_TANH>(st, kp, dXi, dXj, dni, dnj, M, dout, accumulate);
     case GPT_KERNEL_GIBBS_DTANH: return kpairs_dispatch_d<GPT_KERNEL_GIBBS_DTANH>(st, kp, dXi, dXj, dni, dnj, M, dout, accumulate);
+    case GPT_KERNEL_GIBBS_CUBIC: return kpairs_dispatch_d<GPT_KERNEL_GIBBS_CUBIC>(st, kp, dXi, dXj, dni, dnj, M, dout, accumulate);
+    case GPT_KERNEL_GIBBS_QUINTIC: return kpairs_dispatch_d<GPT_KERNEL_GIBBS_QUINTIC>(st, kp, dXi, dXj, dni, dnj, M, dout, accumulate);
+    case GPT_KERNEL_GIBBS_EXPGAUSS: return kpairs_dispatch_d<GPT_KERNEL_GIBBS_EXPGAUSS>(st, kp, dXi, dXj, dni, dnj, M, dout, accumulate);
     default:
         gpt_set_error("kpairs: unknown kernel_id %d", kp.kernel_id);
         return GPT_E_ARG;

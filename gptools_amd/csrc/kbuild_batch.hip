@@ -35,7 +35,7 @@ static int kbuild_batch_d(hipStream_t st, int D, const KParams *d_kps, const dou
                            (int64_t)0, (int64_t)0, d_err_y, 0.0, diag_add, dK, ldk, accumulate, d_kps, d_nv, bstride, dummy, d_kps2, \
                            (const double *)nullptr, (const double *)nullptr); \
         break;
-    if constexpr (KID == GPT_KERNEL_GIBBS_TANH || KID == GPT_KERNEL_GIBBS_DTANH) {      // (1-D kernels: one instantiation)
+    if constexpr (gibbs_kid(KID) || KID == GPT_KID_PRODUCT_GM) {      // (1-D kernels: one instantiation)
         switch (D) {
             KBB_CASE(1)
         default:
@@ -61,8 +61,10 @@ int launch_kbuild_batch(hipStream_t st, int kernel_id, int D, const KParams *d_k
 {
     if (N <= 0 || nbatch <= 0) return GPT_OK;
     if (d_kps2 != nullptr)           // a product term: the factors' kernel ids are read from the elements' KParams at run time
-        return kbuild_batch_d<GPT_KERNEL_PRODUCT>(st, D, d_kps, d_noise_var, nbatch, dX, dn, N, d_err_y, diag_add, dK, ldk, bstride, accumulate,
-                                                  full, d_kps2, xstride, dS, sstride);
+        return D == 1 ? kbuild_batch_d<GPT_KID_PRODUCT_GM>(st, D, d_kps, d_noise_var, nbatch, dX, dn, N, d_err_y, diag_add, dK, ldk, bstride,
+                                                           accumulate, full, d_kps2, xstride, dS, sstride)
+                      : kbuild_batch_d<GPT_KERNEL_PRODUCT>(st, D, d_kps, d_noise_var, nbatch, dX, dn, N, d_err_y, diag_add, dK, ldk, bstride,
+                                                           accumulate, full, d_kps2, xstride, dS, sstride);
     switch (kernel_id) {
     case GPT_KERNEL_SE: return kbuild_batch_d<GPT_KERNEL_SE>(st, D, d_kps, d_noise_var, nbatch, dX, dn, N, d_err_y, diag_add, dK, ldk, bstride, accumulate, full, nullptr, xstride, dS, sstride);
     case GPT_KERNEL_M52: return kbuild_batch_d<GPT_KERNEL_M52>(st, D, d_kps, d_noise_var, nbatch, dX, dn, N, d_err_y, diag_add, dK, ldk, bstride, accumulate, full, nullptr, xstride, dS, sstride);
@@ -70,6 +72,9 @@ int launch_kbuild_batch(hipStream_t st, int kernel_id, int D, const KParams *d_k
     case GPT_KERNEL_MATERN: return kbuild_batch_d<GPT_KERNEL_MATERN>(st, D, d_kps, d_noise_var, nbatch, dX, dn, N, d_err_y, diag_add, dK, ldk, bstride, accumulate, full, nullptr, xstride, dS, sstride);
     case GPT_KERNEL_GIBBS_TANH: return kbuild_batch_d<GPT_KERNEL_GIBBS_TANH>(st, D, d_kps, d_noise_var, nbatch, dX, dn, N, d_err_y, diag_add, dK, ldk, bstride, accumulate, full, nullptr, xstride, dS, sstride);
     case GPT_KERNEL_GIBBS_DTANH: return kbuild_batch_d<GPT_KERNEL_GIBBS_DTANH>(st, D, d_kps, d_noise_var, nbatch, dX, dn, N, d_err_y, diag_add, dK, ldk, bstride, accumulate, full, nullptr, xstride, dS, sstride);
+    case GPT_KERNEL_GIBBS_CUBIC: return kbuild_batch_d<GPT_KERNEL_GIBBS_CUBIC>(st, D, d_kps, d_noise_var, nbatch, dX, dn, N, d_err_y, diag_add, dK, ldk, bstride, accumulate, full, nullptr, xstride, dS, sstride);
+    case GPT_KERNEL_GIBBS_QUINTIC: return kbuild_batch_d<GPT_KERNEL_GIBBS_QUINTIC>(st, D, d_kps, d_noise_var, nbatch, dX, dn, N, d_err_y, diag_add, dK, ldk, bstride, accumulate, full, nullptr, xstride, dS, sstride);
+    case GPT_KERNEL_GIBBS_EXPGAUSS: return kbuild_batch_d<GPT_KERNEL_GIBBS_EXPGAUSS>(st, D, d_kps, d_noise_var, nbatch, dX, dn, N, d_err_y, diag_add, dK, ldk, bstride, accumulate, full, nullptr, xstride, dS, sstride);
     default:
         gpt_set_error("kbuild_batch: kernel_id %d is not a fit kernel", kernel_id);
         return GPT_E_ARG;
@@ -94,7 +99,7 @@ static int kbuild_batch_cross_d(hipStream_t st, int D, const KParams *d_kps, con
                            (int64_t)0, nullptr, 0.0, 0.0, dK, ldk, accumulate, d_kps, d_nv, bstride, dummy, d_kps2,          \
                            (const double *)nullptr, (const double *)nullptr);                                        \
         break;
-    if constexpr (KID == GPT_KERNEL_GIBBS_TANH || KID == GPT_KERNEL_GIBBS_DTANH) {
+    if constexpr (gibbs_kid(KID) || KID == GPT_KID_PRODUCT_GM) {
         switch (D) {
             KBC_CASE(1)
         default:
@@ -123,7 +128,8 @@ int launch_kbuild_batch_cross(hipStream_t st, int kernel_id, int D, const KParam
         return GPT_E_ARG;
     }
     if (d_kps2 != nullptr)
-        return kbuild_batch_cross_d<GPT_KERNEL_PRODUCT>(st, D, d_kps, d_nv, nbatch, dXi, dni, M, dXj, dnj, P, dK, ldk, bstride, accumulate, d_kps2);
+        return D == 1 ? kbuild_batch_cross_d<GPT_KID_PRODUCT_GM>(st, D, d_kps, d_nv, nbatch, dXi, dni, M, dXj, dnj, P, dK, ldk, bstride, accumulate, d_kps2)
+                      : kbuild_batch_cross_d<GPT_KERNEL_PRODUCT>(st, D, d_kps, d_nv, nbatch, dXi, dni, M, dXj, dnj, P, dK, ldk, bstride, accumulate, d_kps2);
     switch (kernel_id) {
     case GPT_KERNEL_SE: return kbuild_batch_cross_d<GPT_KERNEL_SE>(st, D, d_kps, d_nv, nbatch, dXi, dni, M, dXj, dnj, P, dK, ldk, bstride, accumulate, nullptr);
     case GPT_KERNEL_M52: return kbuild_batch_cross_d<GPT_KERNEL_M52>(st, D, d_kps, d_nv, nbatch, dXi, dni, M, dXj, dnj, P, dK, ldk, bstride, accumulate, nullptr);
@@ -131,6 +137,9 @@ int launch_kbuild_batch_cross(hipStream_t st, int kernel_id, int D, const KParam
     case GPT_KERNEL_MATERN: return kbuild_batch_cross_d<GPT_KERNEL_MATERN>(st, D, d_kps, d_nv, nbatch, dXi, dni, M, dXj, dnj, P, dK, ldk, bstride, accumulate, nullptr);
     case GPT_KERNEL_GIBBS_TANH: return kbuild_batch_cross_d<GPT_KERNEL_GIBBS_TANH>(st, D, d_kps, d_nv, nbatch, dXi, dni, M, dXj, dnj, P, dK, ldk, bstride, accumulate, nullptr);
     case GPT_KERNEL_GIBBS_DTANH: return kbuild_batch_cross_d<GPT_KERNEL_GIBBS_DTANH>(st, D, d_kps, d_nv, nbatch, dXi, dni, M, dXj, dnj, P, dK, ldk, bstride, accumulate, nullptr);
+    case GPT_KERNEL_GIBBS_CUBIC: return kbuild_batch_cross_d<GPT_KERNEL_GIBBS_CUBIC>(st, D, d_kps, d_nv, nbatch, dXi, dni, M, dXj, dnj, P, dK, ldk, bstride, accumulate, nullptr);
+    case GPT_KERNEL_GIBBS_QUINTIC: return kbuild_batch_cross_d<GPT_KERNEL_GIBBS_QUINTIC>(st, D, d_kps, d_nv, nbatch, dXi, dni, M, dXj, dnj, P, dK, ldk, bstride, accumulate, nullptr);
+    case GPT_KERNEL_GIBBS_EXPGAUSS: return kbuild_batch_cross_d<GPT_KERNEL_GIBBS_EXPGAUSS>(st, D, d_kps, d_nv, nbatch, dXi, dni, M, dXj, dnj, P, dK, ldk, bstride, accumulate, nullptr);
     default:
         gpt_set_error("kbuild_batch_cross: kernel_id %d is not a fit kernel", kernel_id);
         return GPT_E_ARG;
@@ -143,8 +152,9 @@ template <int D>
 __device__ __forceinline__ double batch_term_pair(const KParams *__restrict__ kps, const KParams *__restrict__ kps2, int64_t idx,
                                                   const double *xi, const double *xj, const int *ni, const int *nj)
 {
-    if (kps2 != nullptr && kps2[idx].kernel_id >= 0) return prod_pair<D>(kps[idx], kps2[idx], xi, xj, ni, nj);
-    return factor_pair<D>(kps[idx], xi, xj, ni, nj);
+    // (D == 1: with the bucket / exp-Gauss Gibbs branches, GPT_KID_PRODUCT_GM's form; otherwise the functions the builders share)
+    if (kps2 != nullptr && kps2[idx].kernel_id >= 0) return prod_pair<D, D == 1>(kps[idx], kps2[idx], xi, xj, ni, nj);
+    return factor_pair<D, D == 1>(kps[idx], xi, xj, ni, nj);
 }
 
 // diag K**_b: out[b * ldo + a] = k_b((x_a, n_a), (x_a, n_a)), terms summed in order (as gpt_predict's pair launches do)

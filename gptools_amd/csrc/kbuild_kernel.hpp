@@ -83,15 +83,15 @@ __global__ __launch_bounds__(KB_THREADS) void kbuild_kernel(
     // derivative-order loads, no index selection (the ~25 scalar and ~6 vector instructions per row the general loop spends on
     // choosing among four formulas).  The test is once per tile and wave: the orders of the rows in one or two vector loads
     // and a ballot.  C3 (last quarter derivative rows): 56 % of the lower triangle's pairs.
-    if constexpr ((KID == GPT_KERNEL_GIBBS_TANH || KID == GPT_KERNEL_GIBBS_DTANH) && KB_CPT == 1) {
+    if constexpr (gibbs_kid(KID) && KB_CPT == 1) {
         static_assert(D == 1, "the Gibbs kernels are one-dimensional");
         // The warps are hoisted out of the row loop (kpair.hpp, GibbsPt): this lane's column point once, and the tile's
         // 32 row points once per wave -- lane q (and q + 32) forms row rbase + q, the row loop reads it back with
         // v_readlane into scalar registers.  Per pair: one v_rsq_f64 + Newton step, one exponential, a few FMAs.
-        const GibbsPt cp = gibbs_point(kp, xj[0][0]);
+        const GibbsPt cp = gibbs_point<KID>(kp, xj[0][0]);
         const int lane = (int)(threadIdx.x & 63);
         const int64_t ir = (rbase + (lane & 31) < M) ? rbase + (lane & 31) : M - 1;
-        const GibbsPt rp = gibbs_point(kp, Xi[ir]);
+        const GibbsPt rp = gibbs_point<KID>(kp, Xi[ir]);
         const double s2 = kp.sigma * kp.sigma;
         const bool col_d = __builtin_amdgcn_ballot_w64(njr[0][0] != 0) != 0;
         bool row_d = false;
@@ -180,6 +180,7 @@ __global__ __launch_bounds__(KB_THREADS) void kbuild_kernel(
 #pragma unroll
         for (int c = 0; c < KB_CPT; c++) {
             if constexpr (KID == GPT_KERNEL_PRODUCT) v[c] = prod_pair<D>(kp, kp_two, xi, xj[c], nir, njr[c]);
+            else if constexpr (KID == GPT_KID_PRODUCT_GM) v[c] = prod_pair<D, true>(kp, kp_two, xi, xj[c], nir, njr[c]);
             else v[c] = any_pair<KID, D>(kp, xi, xj[c], nir, njr[c]);
             if constexpr (WARP) v[c] *= Si[i] * sj[c];
             // SumKernel (ref: gptools/kernel/core.py:549-584): later terms add to what the earlier passes stored
@@ -226,6 +227,7 @@ __global__ __launch_bounds__(256) void kpairs_kernel(KParams kp, const double *_
     }
     double v;
     if constexpr (KID == GPT_KERNEL_PRODUCT) v = prod_pair<D>(kp, kp_two, xi, xj, nir, njr);
+    else if constexpr (KID == GPT_KID_PRODUCT_GM) v = prod_pair<D, true>(kp, kp_two, xi, xj, nir, njr);
     else v = any_pair<KID, D>(kp, xi, xj, nir, njr);
     out[m] = accumulate ? out[m] + v : v;
 }

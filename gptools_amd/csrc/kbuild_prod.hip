@@ -20,6 +20,20 @@ int launch_kbuild_prod(hipStream_t st, const KParams &kp1, const KParams &kp2, c
         grid = dim3((unsigned)ntile, 1);
         lower_only = 2;
     }
+    // a bucket / exp-Gauss Gibbs factor (1-D): the instantiation that carries those branches (GPT_KID_PRODUCT_GM, common.hpp)
+    if (kp1.D == 1 && (gibbs_more_kid(kp1.kernel_id) || gibbs_more_kid(kp2.kernel_id))) {
+        if (dSi != nullptr)
+            hipLaunchKernelGGL((kbuild_kernel<GPT_KID_PRODUCT_GM, 1, false, true>), grid, block, 0, st, kp1, dXi, dni, M, dXj, dnj, P,
+                               lower_only, i0, j0, d_err_y, noise_var, diag_add, dK, ldk, accumulate, (const KParams *)nullptr,
+                               (const double *)nullptr, (int64_t)0, kp2, (const KParams *)nullptr, dSi, dSj);
+        else
+            hipLaunchKernelGGL((kbuild_kernel<GPT_KID_PRODUCT_GM, 1, false>), grid, block, 0, st, kp1, dXi, dni, M, dXj, dnj, P,
+                               lower_only, i0, j0, d_err_y, noise_var, diag_add, dK, ldk, accumulate, (const KParams *)nullptr,
+                               (const double *)nullptr, (int64_t)0, kp2, (const KParams *)nullptr, (const double *)nullptr,
+                               (const double *)nullptr);
+        GPT_LAUNCH_CHECK();
+        return GPT_OK;
+    }
 #define KBP_CASE(DD)                                                                                                  \
     case DD:                                                                                                          \
         if (dSi != nullptr) {      /* warp layers set: the WARP instantiation (kbuild_kernel.hpp) */                  \
@@ -50,6 +64,11 @@ int launch_kpairs_prod(hipStream_t st, const KParams &kp1, const KParams &kp2, c
 {
     if (M <= 0) return GPT_OK;
     dim3 grid((unsigned)((M + 255) / 256)), block(256);
+    if (kp1.D == 1 && (gibbs_more_kid(kp1.kernel_id) || gibbs_more_kid(kp2.kernel_id))) {
+        hipLaunchKernelGGL((kpairs_kernel<GPT_KID_PRODUCT_GM, 1>), grid, block, 0, st, kp1, dXi, dXj, dni, dnj, M, dout, accumulate, kp2);
+        GPT_LAUNCH_CHECK();
+        return GPT_OK;
+    }
 #define KPP_CASE(DD)                                                                                                  \
     case DD:                                                                                                          \
         hipLaunchKernelGGL((kpairs_kernel<GPT_KERNEL_PRODUCT, DD>), grid, block, 0, st, kp1, dXi, dXj, dni, dnj, M,    \

@@ -21,6 +21,7 @@
 //     accumulated here as a product of per-dimension polynomials in a marker for the number of blocks.
 #pragma once
 #include "common.hpp"
+#include "gibbs_lfunc.hpp"
 
 #define GPT_SQRT5 2.2360679774997898
 #define GPT_FIVE_THIRDS 1.6666666666666667
@@ -573,7 +574,7 @@ __device__ __forceinline__ double plain_pair(const KParams &kp, const double *xi
     }
 }
 
-// ---- Gibbs kernels in 1-D (ref: gptools/kernel/gibbs.py:229-466, :508-558) ---------------------------------------------
+// ---- Gibbs kernels in 1-D (ref: gptools/kernel/gibbs.py:229-466, :508-558, :603-902) -----------------------------------
 // k = sigma^2 sqrt(2ab/s) exp(-d^2/s),  a = l(x_i), b = l(x_j), s = a^2 + b^2, d = x_i - x_j.  The reference's derivative
 // classes (Mathematica polynomials up to l^8, gibbs.py:336-416) are k times a short factor; with u = 1/s, du = d u,
 // w = 2 du^2 - u, A = a a', B = b b':
@@ -600,19 +601,11 @@ struct GibbsPt {
     double rp, rn;      // sqrt(|l|), NaN where l < 0 / where l > 0   (column side)
 };
 
-// l(x) = c + sum_q amp_q tanh((x - x0_q) / w_q) and l'(x) = sum_q amp_q / w_q cosh((x - x0_q) / w_q)^-2 in the reference's
-// order of operations (gibbs.py:459-464, :552-556); cosh overflows to inf beyond |u| = 710 and the slope is then 0, as there
-__device__ __forceinline__ GibbsPt gibbs_point(const KParams &kp, double x)
+// what a pair needs of one point, from l(x) and l'(x)
+__device__ __forceinline__ GibbsPt gibbs_pt(double l, double dl)
 {
-    double l = 0.0, dl = 0.0;
-    for (int q = 0; q < kp.g_nt; q++) {
-        const double u = (x - kp.g_x0[q]) / kp.g_w[q];
-        const double ch = cosh(u);
-        l = fma(kp.g_amp[q], tanh(u), l);
-        dl += kp.g_amp[q] / kp.g_w[q] * (1.0 / (ch * ch));
-    }
     GibbsPt p;
-    p.l = l + kp.g_c;
+    p.l = l;
     p.dl = dl;
     p.A = p.l * dl;
     p.h = dl / (2.0 * p.l);
@@ -621,6 +614,38 @@ __device__ __forceinline__ GibbsPt gibbs_point(const KParams &kp, double x)
     p.rp = (p.l < 0.0) ? (double)NAN : al;
     p.rn = (p.l > 0.0) ? (double)NAN : al;
     return p;
+}
+
+// One branch per length-scale function; KID: the kernel id where the caller's instantiation fixes it (the builders and pair
+// lists of one kernel: the other branches fold away, the function is inlined into the per-point hoist and the tanh
+// instantiations are the code they were), -1 where only kp carries it (product factors, the batched pair kernels: per pair,
+// as for the tanh warps there).  The tanh warps: l(x) = c + sum_q amp_q tanh((x - x0_q) / w_q) and l'(x) = sum_q amp_q / w_q
+// cosh((x - x0_q) / w_q)^-2 in the reference's order of operations (gibbs.py:459-464, :552-556); cosh overflows to inf beyond
+// |u| = 710 and the slope is then 0, as there.  The buckets and the exponential of Gaussians: gibbs_lfunc.hpp.
+template <int KID = -1>
+__device__ __forceinline__ GibbsPt gibbs_point(const KParams &kp, double x)
+{
+    const int kid = (KID < 0) ? kp.kernel_id : KID;
+    double l = 0.0, dl = 0.0;
+    if (kid == GPT_KERNEL_GIBBS_CUBIC) {
+        gpt_gibbs_cubic_bucket(kp.g_raw, x, &l, &dl);
+        return gibbs_pt(l, dl);
+    }
+    if (kid == GPT_KERNEL_GIBBS_QUINTIC) {
+        gpt_gibbs_quintic_bucket(kp.g_raw, x, &l, &dl);
+        return gibbs_pt(l, dl);
+    }
+    if (kid == GPT_KERNEL_GIBBS_EXPGAUSS) {
+        gpt_gibbs_exp_gauss(kp.g_raw, kp.g_nt, x, &l, &dl);
+        return gibbs_pt(l, dl);
+    }
+    for (int q = 0; q < kp.g_nt; q++) {
+        const double u = (x - kp.g_x0[q]) / kp.g_w[q];
+        const double ch = cosh(u);
+        l = fma(kp.g_amp[q], tanh(u), l);
+        dl += kp.g_amp[q] / kp.g_w[q] * (1.0 / (ch * ch));
+    }
+    return gibbs_pt(l + kp.g_c, dl);
 }
 
 // the column factor sqrt(|b|) that belongs to a row of length scale a (see above; a == 0: the unmasked root)
@@ -654,9 +679,10 @@ __device__ __forceinline__ double gibbs_core(double s2, double xi, double a, dou
     return v;
 }
 
+template <int KID = -1>
 __device__ __forceinline__ double gibbs_pair(const KParams &kp, const double *xi, const double *xj, const int *ni, const int *nj)
 {
-    const GibbsPt p = gibbs_point(kp, xi[0]), q = gibbs_point(kp, xj[0]);
+    const GibbsPt p = gibbs_point<KID>(kp, xi[0]), q = gibbs_point<KID>(kp, xj[0]);
     return gibbs_core(kp.sigma * kp.sigma, xi[0], p.l, p.A, p.h, p.r2, xj[0], q.l, q.A, q.h, gibbs_col_root(p.l, q.rp, q.rn),
                       ni[0], nj[0], (ni[0] | nj[0]) != 0);
 }
@@ -670,7 +696,7 @@ __device__ __forceinline__ double any_pair(const KParams &kp, const double *xi, 
     if (KID == GPT_KERNEL_DIAGNOISE) return noise_pair<D>(kp, xi, xj, ni, nj);
     if (KID == GPT_KERNEL_RQ) return rq_pair<D>(kp, xi, xj, ni, nj);
     if (KID == GPT_KERNEL_MATERN) return matern_pair<D>(kp, xi, xj, ni, nj);
-    if (KID == GPT_KERNEL_GIBBS_TANH || KID == GPT_KERNEL_GIBBS_DTANH) return gibbs_pair(kp, xi, xj, ni, nj);
+    if constexpr (gibbs_kid(KID)) return gibbs_pair<KID>(kp, xi, xj, ni, nj);
     return 0.0;
 }
 
@@ -678,7 +704,8 @@ __device__ __forceinline__ double any_pair(const KParams &kp, const double *xi, 
 // The reference walks the power set of the derivative multiset of a pair and multiplies k1 with the subset's orders by k2
 // with the complement's; equal subsets recur, so grouped by how many of the r_s derivatives of slot s (the D orders of ni, then
 // the D of nj) go to k1 that is the general Leibniz rule  sum_a prod_s C(r_s, a_s) k1^(a) k2^(r - a).  Factors by run-time id.
-template <int D>
+// GM: the bucket / exp-Gauss Gibbs ids are compiled in (GPT_KID_PRODUCT_GM, common.hpp; 1-D only)
+template <int D, bool GM = false>
 __device__ __forceinline__ double factor_pair(const KParams &kp, const double *xi, const double *xj, const int *ni, const int *nj)
 {
     switch (kp.kernel_id) {
@@ -688,11 +715,16 @@ __device__ __forceinline__ double factor_pair(const KParams &kp, const double *x
     case GPT_KERNEL_MATERN: return matern_pair<D>(kp, xi, xj, ni, nj);
     case GPT_KERNEL_GIBBS_TANH:
     case GPT_KERNEL_GIBBS_DTANH: return gibbs_pair(kp, xi, xj, ni, nj);      // (1-D: the host admits no other D, and orders <= 1)
+    case GPT_KERNEL_GIBBS_CUBIC:
+    case GPT_KERNEL_GIBBS_QUINTIC:
+    case GPT_KERNEL_GIBBS_EXPGAUSS:
+        if constexpr (GM && D == 1) return gibbs_pair(kp, xi, xj, ni, nj);
+        return 0.0;
     default: return 0.0;
     }
 }
 
-template <int D>
+template <int D, bool GM = false>
 __device__ double prod_pair(const KParams &k1, const KParams &k2, const double *xi, const double *xj, const int *ni, const int *nj)
 {
     int r[2 * D], a[2 * D];
@@ -719,7 +751,7 @@ __device__ double prod_pair(const KParams &k1, const KParams &k2, const double *
                 n2j[s - D] = r[s] - a[s];
             }
         }
-        sum += w * (factor_pair<D>(k1, xi, xj, n1i, n1j) * factor_pair<D>(k2, xi, xj, n2i, n2j));
+        sum += w * (factor_pair<D, GM>(k1, xi, xj, n1i, n1j) * factor_pair<D, GM>(k2, xi, xj, n2i, n2j));
         int s = 0;
         while (s < 2 * D) {
             if (a[s] < r[s]) {

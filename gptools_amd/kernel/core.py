@@ -155,7 +155,7 @@ class ProductKernel(BinaryKernel):
     The reference walks the power set of the derivative multiset of every pair (positions distinct, so equal subsets
     recur); grouped by how many of the ``n`` derivatives of each of the 2 D slots (``ni`` then ``nj``) go to ``k1`` that
     is the general Leibniz rule, ``sum_a prod_slots C(n, a) * k1^(a) * k2^(n - a)`` -- the same sum with each distinct
-    term evaluated once.  With two native factors (SE, Matern52, RationalQuadratic, Matern, the tanh Gibbs kernels) that sum
+    term evaluated once.  With two native factors (SE, Matern52, RationalQuadratic, Matern, the native Gibbs kernels) that sum
     runs per pair on the device (``GPT_KERNEL_PRODUCT``: ``gpt_kpairs2`` here, the fused builder in ``GaussianProcess``); otherwise both
     factors are evaluated through their own ``__call__`` and combined on the host."""
 
@@ -165,7 +165,7 @@ class ProductKernel(BinaryKernel):
         from .. import _lib
         from .matern import Matern52Kernel
         ok = (_lib.KERNEL_SE, _lib.KERNEL_M52, _lib.KERNEL_RQ, _lib.KERNEL_MATERN, _lib.KERNEL_GIBBS_TANH,
-              _lib.KERNEL_GIBBS_DTANH)
+              _lib.KERNEL_GIBBS_DTANH, _lib.KERNEL_GIBBS_CUBIC, _lib.KERNEL_GIBBS_QUINTIC, _lib.KERNEL_GIBBS_EXPGAUSS)
         f = []
         for k in (self.k1, self.k2):
             kid = getattr(k, "_gpt_kernel_id", None)

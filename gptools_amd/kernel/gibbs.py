@@ -1,7 +1,8 @@
 r"""Gibbs non-stationary squared-exponential kernels in one dimension.
 
 ref: gptools/kernel/gibbs.py:229-424 (GibbsKernel1d), :426-466 (tanh_warp, GibbsKernel1dTanh), :508-558 (double_tanh_warp,
-GibbsKernel1dDoubleTanh).  With a point-dependent length scale ``l(x)``, ``a = l(x_i)``, ``b = l(x_j)``, ``s = a^2 + b^2``
+GibbsKernel1dDoubleTanh), :603-801 (cubic_bucket_warp, quintic_bucket_warp and their kernels), :804-902 (exp_gauss_warp,
+GibbsKernel1dExpGauss).  With a point-dependent length scale ``l(x)``, ``a = l(x_i)``, ``b = l(x_j)``, ``s = a^2 + b^2``
 and ``d = x_i - x_j``:
 
 .. math::  k = \sigma_f^2 \sqrt{2ab/s}\, \exp(-d^2/s).
@@ -15,9 +16,11 @@ The reference hard-codes the derivative classes as expanded polynomials (terms u
                                                            d2 k / dx_i dx_j   = k (P Q + R)
 
 ``GibbsKernel1d(l_func)`` evaluates that on the host in numpy for any warp (the Python-kernel route of
-``GaussianProcess``: pair list, then ``fit_matrix`` on the GPU).  ``GibbsKernel1dTanh`` and ``GibbsKernel1dDoubleTanh`` are
-native: the HIP library evaluates them (``GPT_KERNEL_GIBBS_TANH`` / ``GPT_KERNEL_GIBBS_DTANH``, gptools_amd/csrc/kpair.hpp)
-with the warps hoisted out of the builder's pair loop.  A subclass that overrides ``__call__`` is a Python kernel again.
+``GaussianProcess``: pair list, then ``fit_matrix`` on the GPU).  ``GibbsKernel1dTanh``, ``GibbsKernel1dDoubleTanh``,
+``GibbsKernel1dCubicBucket``, ``GibbsKernel1dQuinticBucket`` and ``GibbsKernel1dExpGauss`` are native: the HIP library evaluates
+them (``GPT_KERNEL_GIBBS_*``, gptools_amd/csrc/kpair.hpp and gibbs_lfunc.hpp) with the length-scale functions hoisted out of
+the builder's pair loop.  A subclass that overrides ``__call__`` is a Python kernel again; so is a ``GibbsKernel1dExpGauss``
+with more Gaussians than the device kernel carries (``_lib.GIBBS_MAX_GAUSS``).
 Derivative orders above ``[1, 1]`` and hyperparameter derivatives raise ``NotImplementedError`` like the reference.
 """
 import inspect
@@ -27,7 +30,9 @@ import numpy as np
 from .core import Kernel
 from .. import _lib
 
-__all__ = ["GibbsKernel1d", "GibbsKernel1dTanh", "GibbsKernel1dDoubleTanh", "tanh_warp", "double_tanh_warp"]
+__all__ = ["GibbsKernel1d", "GibbsKernel1dTanh", "GibbsKernel1dDoubleTanh", "GibbsKernel1dCubicBucket",
+           "GibbsKernel1dQuinticBucket", "GibbsKernel1dExpGauss", "tanh_warp", "double_tanh_warp", "cubic_bucket_warp",
+           "quintic_bucket_warp", "exp_gauss_warp"]
 
 
 def gibbs_1d(x, y, ni, nj, lx, ly, lx1, ly1):
@@ -132,3 +137,133 @@ class GibbsKernel1dDoubleTanh(GibbsKernel1d):
     def __init__(self, **kwargs):
         super(GibbsKernel1dDoubleTanh, self).__init__(
             double_tanh_warp, param_names=[r"\sigma_f", "l_c", "l_m", "l_e", "l_a", "l_b", "x_a", "x_b"], **kwargs)
+
+
+def _bucket_sections(x, x0, w1, w2, w3):
+    """Centres of the two joins and the five 0/1 masks of a bucket, in the reference's order of operations (gibbs.py:627-639)."""
+    x1 = x0 - w2 / 2.0 - w1 / 2.0
+    x2 = x0 + w2 / 2.0 + w3 / 2.0
+    masks = (x <= (x1 - w1 / 2.0),
+             (x > (x1 - w1 / 2.0)) & (x < (x1 + w1 / 2.0)),
+             (x >= (x1 + w1 / 2.0)) & (x <= x2 - w3 / 2.0),
+             (x > (x2 - w3 / 2.0)) & (x < (x2 + w3 / 2.0)),
+             x >= (x2 + w3 / 2.0))
+    return x1, x2, masks
+
+
+def cubic_bucket_warp(x, n, l1, l2, l3, x0, w1, w2, w3):
+    r"""Piecewise cubic "bucket": ``l_1`` left of the bucket, ``l_2`` inside it (centre ``x_0``, width ``w_2``), ``l_3`` right of
+    it, joined by cubic sections of widths ``w_1`` and ``w_3``; its slope for ``n = 1`` (ref: gibbs.py:603-651).
+
+    Written as the reference writes it -- every section's value times its 0/1 mask, summed -- because that sum defines the
+    function: a non-finite section value times a zero mask is NaN (``w_1 = 0``: NaN everywhere), negative widths make the masks
+    overlap or leave gaps."""
+    x = np.asarray(x, dtype=float)
+    x1, x2, (m0, m1, m2, m3, m4) = _bucket_sections(x, x0, w1, w2, w3)
+    with np.errstate(all="ignore"):
+        s1 = (x - x1 + w1 / 2.0) / w1
+        s2 = (x - x2 + w3 / 2.0) / w3
+        if n == 0:
+            return (l1 * m0 + (-2.0 * (l2 - l1) * (s1 ** 3 - 3.0 / 2.0 * s1 ** 2) + l1) * m1 + l2 * m2 +
+                    (-2.0 * (l3 - l2) * (s2 ** 3 - 3.0 / 2.0 * s2 ** 2) + l2) * m3 + l3 * m4)
+        elif n == 1:
+            return ((-2.0 * (l2 - l1) * (3 * s1 ** 2 - 3.0 * s1) / w1) * m1 +
+                    (-2.0 * (l3 - l2) * (3 * s2 ** 2 - 3.0 * s2) / w3) * m3)
+    raise NotImplementedError("Only up to first derivatives are supported!")
+
+
+def quintic_bucket_warp(x, n, l1, l2, l3, x0, w1, w2, w3):
+    r"""The bucket of :func:`cubic_bucket_warp` with quintic joins (continuous second derivative) (ref: gibbs.py:695-760); the
+    same masked-sum form."""
+    x = np.asarray(x, dtype=float)
+    x1, x2, (m0, m1, m2, m3, m4) = _bucket_sections(x, x0, w1, w2, w3)
+    with np.errstate(all="ignore"):
+        s1 = 2.0 * (x - x1) / w1
+        s3 = 2.0 * (x - x2) / w3
+        if n == 0:
+            return (l1 * m0 +
+                    (0.5 * (l2 - l1) * (3.0 / 8.0 * s1 ** 5 - 5.0 / 4.0 * s1 ** 3 + 15.0 / 8.0 * s1) + (l1 + l2) / 2.0) * m1 +
+                    l2 * m2 +
+                    (0.5 * (l3 - l2) * (3.0 / 8.0 * s3 ** 5 - 5.0 / 4.0 * s3 ** 3 + 15.0 / 8.0 * s3) + (l2 + l3) / 2.0) * m3 +
+                    l3 * m4)
+        elif n == 1:
+            return ((0.5 * (l2 - l1) * (5.0 * 3.0 / 8.0 * s1 ** 4 - 3.0 * 5.0 / 4.0 * s1 ** 2 + 15.0 / 8.0) / w1) * m1 +
+                    (0.5 * (l3 - l2) * (5.0 * 3.0 / 8.0 * s3 ** 4 - 3.0 * 5.0 / 4.0 * s3 ** 2 + 15.0 / 8.0) / w3) * m3)
+    raise NotImplementedError("Only up to first derivatives are supported!")
+
+
+def exp_gauss_warp(X, n, l0, *msb):
+    r"""``l = l_0 \exp(\sum_i \beta_i \exp(-(x - \mu_i)^2 / (2 \sigma_i^2)))`` (``n = 0``) or its slope (``n = 1``); ``msb``: the
+    means, then the standard deviations, then the weights (ref: gibbs.py:804-855).  The thirds of ``msb`` are split with integer
+    division (the reference's ``len(msb) / 3`` is a float under Python 3 and cannot index)."""
+    X = np.asarray(X, dtype=float)
+    msb = np.asarray(msb, dtype=float)
+    G = len(msb) // 3
+    mm, ss, bb = msb[:G], msb[G:2 * G], msb[2 * G:]
+    with np.errstate(all="ignore"):
+        if n == 0:
+            l = np.zeros_like(X)
+            for m, s, b in zip(mm, ss, bb):
+                l += b * np.exp(-(X - m) ** 2.0 / (2.0 * s ** 2.0))
+            return l0 * np.exp(l)
+        elif n == 1:
+            l1 = np.zeros_like(X)
+            l2 = np.zeros_like(X)
+            for m, s, b in zip(mm, ss, bb):
+                term = b * np.exp(-(X - m) ** 2.0 / (2.0 * s ** 2.0))
+                l1 += term
+                l2 += term * (X - m) / s ** 2.0
+            return -l0 * np.exp(l1) * l2
+    raise NotImplementedError("Only n <= 1 is supported!")
+
+
+_BUCKET_NAMES = [r"\sigma_f", "l_1", "l_2", "l_3", "x_0", "w_1", "w_2", "w_3"]
+
+
+class GibbsKernel1dCubicBucket(GibbsKernel1d):
+    r"""Gibbs kernel with the cubic bucket, evaluated on the GPU.  Parameters ``[sigma_f, l_1, l_2, l_3, x_0, w_1, w_2, w_3]``."""
+    _gpt_kernel_id = _lib.KERNEL_GIBBS_CUBIC
+    __call__ = Kernel.__call__
+
+    def __init__(self, **kwargs):
+        super(GibbsKernel1dCubicBucket, self).__init__(cubic_bucket_warp, param_names=list(_BUCKET_NAMES), **kwargs)
+
+
+class GibbsKernel1dQuinticBucket(GibbsKernel1d):
+    r"""Gibbs kernel with the quintic bucket, evaluated on the GPU.  Parameters as :class:`GibbsKernel1dCubicBucket`."""
+    _gpt_kernel_id = _lib.KERNEL_GIBBS_QUINTIC
+    __call__ = Kernel.__call__
+
+    def __init__(self, **kwargs):
+        super(GibbsKernel1dQuinticBucket, self).__init__(quintic_bucket_warp, param_names=list(_BUCKET_NAMES), **kwargs)
+
+
+class GibbsKernel1dExpGauss(GibbsKernel1d):
+    r"""Gibbs kernel whose length scale is an exponential of ``n_gaussians`` Gaussians, evaluated on the GPU.  Parameters
+    ``[sigma_f, l_0, mu_1 .., sigma_1 .., beta_1 ..]`` (ref: gibbs.py:858-902).
+
+    The device kernel carries up to ``_lib.GIBBS_MAX_GAUSS`` Gaussians.  With more, the constructor returns an instance of a
+    subclass whose ``__call__`` is the host ``GibbsKernel1d``'s -- a Python kernel by the rule above, with the same numbers.
+    That switch is made for this class only: a user subclass that keeps the native ``__call__`` and asks for more Gaussians
+    than the cap stays a native kernel and gets the library's ``ValueError`` (``GPT_GIBBS_MAX_GAUSS``) at its first evaluation;
+    it takes the host route by overriding ``__call__`` (``__call__ = GibbsKernel1d.__call__``), like any Python kernel."""
+    _gpt_kernel_id = _lib.KERNEL_GIBBS_EXPGAUSS
+    __call__ = Kernel.__call__
+
+    def __new__(cls, n_gaussians=None, **kwargs):
+        if cls is GibbsKernel1dExpGauss and n_gaussians is not None and n_gaussians > _lib.GIBBS_MAX_GAUSS:
+            cls = _GibbsKernel1dExpGaussHost
+        return super(GibbsKernel1dExpGauss, cls).__new__(cls)
+
+    def __init__(self, n_gaussians, **kwargs):
+        super(GibbsKernel1dExpGauss, self).__init__(
+            exp_gauss_warp, num_params=3 * n_gaussians + 2,
+            param_names=([r"\sigma_f", "l_0"] + [r"\mu_{{{:d}}}".format(i + 1) for i in range(n_gaussians)] +
+                         [r"\sigma_{{{:d}}}".format(i + 1) for i in range(n_gaussians)] +
+                         [r"\beta_{{{:d}}}".format(i + 1) for i in range(n_gaussians)]),
+            **kwargs)
+
+
+class _GibbsKernel1dExpGaussHost(GibbsKernel1dExpGauss):
+    """``GibbsKernel1dExpGauss`` beyond the device kernel's cap: evaluated on the host."""
+    __call__ = GibbsKernel1d.__call__

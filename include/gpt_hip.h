@@ -73,6 +73,18 @@ extern "C" {
 #define GPT_KERNEL_GIBBS_DTANH 8 /* GibbsKernel1dDoubleTanh, the same with params [sigma_f, l_c, l_m, l_e, l_a, l_b, x_a, x_b]
                                   * (ref: kernel/gibbs.py:508-558): l(x) = a tanh((x - x_a)/l_a) + b tanh((x - x_b)/l_b) + c,
                                   * a = (l_m - l_c)/2, b = (l_e - l_m)/2, c = (l_c + l_e)/2 */
+#define GPT_KERNEL_GIBBS_CUBIC 9 /* GibbsKernel1dCubicBucket, the same with params [sigma_f, l_1, l_2, l_3, x_0, w_1, w_2, w_3]
+                                  * (ref: kernel/gibbs.py:603-692): l(x) is l_1 left of the bucket, l_2 inside it (centre x_0, width
+                                  * w_2), l_3 right of it, joined by cubic sections of widths w_1 and w_3.  Evaluated as the reference
+                                  * writes it: the five section values (two for l') each times its 0/1 mask, summed -- so w_1 = 0 or
+                                  * w_3 = 0 is NaN everywhere, negative widths overlap or leave gaps exactly as there */
+#define GPT_KERNEL_GIBBS_QUINTIC 10 /* GibbsKernel1dQuinticBucket, the same 8 params with quintic joins (ref: kernel/gibbs.py:695-801) */
+#define GPT_KERNEL_GIBBS_EXPGAUSS 11 /* GibbsKernel1dExpGauss with G Gaussians, 3 G + 2 params [sigma_f, l_0, mu_1 .. mu_G,
+                                  * sigma_1 .. sigma_G, beta_1 .. beta_G] (ref: kernel/gibbs.py:804-902):
+                                  * l(x) = l_0 exp(sum_i beta_i exp(-(x - mu_i)^2 / (2 sigma_i^2))).  1 <= G <= GPT_GIBBS_MAX_GAUSS
+                                  * (the parameters travel by value in the kernel arguments); a parameter count that is not 3 G + 2
+                                  * or a G beyond the cap is GPT_E_ARG */
+#define GPT_GIBBS_MAX_GAUSS 8    /* most Gaussians of GPT_KERNEL_GIBBS_EXPGAUSS */
 
 #define GPT_MAX_DIM 16      /* largest supported num_dim */
 #define GPT_WARP_LINEAR 1    /* input warp layer w = (x - a)/(b - a) per dimension (ref: kernel/warping.py:367-402) */
