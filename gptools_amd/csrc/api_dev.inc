@@ -12,8 +12,7 @@ extern "C" int gpt_dev_kbuild(gpt_ctx *c, int kernel_id, const double *params_ho
     CTX_ENTER(c);
     KParams kp;
     GPT_TRY(make_kparams(kernel_id, params_host, nparams, D, hyper_deriv, symmetric, noise_n_host, &kp));
-    return launch_kbuild(c->stream, kp, dXi, dni, M, dXj, dnj, P, lower_only, i0, j0, d_err_y, noise_var, diag_add,
-                         dK, ldk);
+    return launch_kbuild(c->stream, kp, nullptr, {dXi, dni, M, dXj, dnj, P, lower_only, i0, j0, d_err_y, noise_var, diag_add, dK, ldk});
 }
 
 extern "C" int gpt_dev_gemm_nt(gpt_ctx *c, int64_t m, int64_t n, int64_t k, double alpha, const double *dA,

@@ -314,8 +314,8 @@ static int kbuild_terms(hipStream_t st, const ModelKernel &m, int symmetric, con
         kp.symmetric = symmetric;
         kp.hyper_deriv = -1;
         const bool last = t + 1 == m.nterms;
-        GPT_TRY(launch_kbuild(st, kp, dXi, dni, M, dXj, dnj, P, lower_only, i0, j0, last ? d_err : nullptr, noise_var,
-                              diag_add, dK, ldk, t > 0 ? 1 : 0, m.second(t), dSi, dSj));
+        GPT_TRY(launch_kbuild(st, kp, m.second(t), {dXi, dni, M, dXj, dnj, P, lower_only, i0, j0, last ? d_err : nullptr, noise_var,
+                                                    diag_add, dK, ldk, t > 0 ? 1 : 0, dSi, dSj}));
     }
     return GPT_OK;
 }

@@ -82,7 +82,7 @@ static int kbuild_run(gpt_ctx *c, const KParams &k1, const KParams *k2, const do
     GPT_HIP_CHECK(hipMemcpyAsync(dXj, Xj, (size_t)P * D * sizeof(double), hipMemcpyHostToDevice, st));
     GPT_HIP_CHECK(hipMemcpyAsync(dnj, nj, (size_t)P * D * sizeof(int32_t), hipMemcpyHostToDevice, st));
     if (warp) GPT_TRY(warp_kbuild_points(c, st, dXi, dni, M, dXj, dnj, P, &dSi, &dSj));
-    GPT_TRY(launch_kbuild(st, k1, dXi, dni, M, dXj, dnj, P, 0, 0, 0, nullptr, 0.0, 0.0, dK, P, 0, k2, dSi, dSj));
+    GPT_TRY(launch_kbuild(st, k1, k2, {dXi, dni, M, dXj, dnj, P, 0, 0, 0, nullptr, 0.0, 0.0, dK, P, 0, dSi, dSj}));
     GPT_HIP_CHECK(hipMemcpyAsync(K_out, dK, (size_t)M * P * sizeof(double), hipMemcpyDeviceToHost, st));
     GPT_HIP_CHECK(hipStreamSynchronize(st));
     return GPT_OK;

@@ -163,17 +163,27 @@ __device__ __forceinline__ void edge_poll(const unsigned *word, unsigned value, 
 int launch_kpairs(hipStream_t st, const KParams &kp, const double *dXi, const double *dXj,
                   const int32_t *dni, const int32_t *dnj, int64_t M, double *dout, int accumulate = 0,
                   const KParams *kp2 = nullptr);      // kp2 (kernel_id >= 0): the pair list of the product kp * kp2
-int launch_kbuild(hipStream_t st, const KParams &kp, const double *dXi, const int32_t *dni, int64_t M,
-                  const double *dXj, const int32_t *dnj, int64_t P, int lower_only, int64_t i0, int64_t j0,
-                  const double *d_err_y, double noise_var, double diag_add, double *dK, int64_t ldk,
-                  int accumulate = 0, const KParams *kp2 = nullptr, const double *dSi = nullptr, const double *dSj = nullptr);
-                  // dSi / dSj (both or neither): Xi / Xj are WARPED points, these their slope factors (warp.hpp; the fit kernels only)
-int launch_kbuild_prod(hipStream_t st, const KParams &kp1, const KParams &kp2, const double *dXi, const int32_t *dni, int64_t M,
-                       const double *dXj, const int32_t *dnj, int64_t P, int lower_only, int64_t i0, int64_t j0,
-                       const double *d_err_y, double noise_var, double diag_add, double *dK, int64_t ldk, int accumulate,
-                       const double *dSi = nullptr, const double *dSj = nullptr);
-int launch_kpairs_prod(hipStream_t st, const KParams &kp1, const KParams &kp2, const double *dXi, const double *dXj,
-                       const int32_t *dni, const int32_t *dnj, int64_t M, double *dout, int accumulate);
+// One block of the covariance builder: rows Xi / ni (M points), columns Xj / nj (P points), written to K (row stride ldk).
+// lower_only: skip the tiles strictly above the diagonal of the whole matrix, in which this block starts at (i0, j0); err_y != NULL:
+// the diagonal epilogue ((K + noise_var) + err_y^2) + diag_add; accumulate: add to what K holds (a later term of a sum).
+// Si / Sj (both or neither): Xi / Xj are WARPED points, these their slope factors (warp.hpp; the fit kernels only).
+struct KBuildArgs {
+    const double *Xi;
+    const int32_t *ni;
+    int64_t M;
+    const double *Xj;
+    const int32_t *nj;
+    int64_t P;
+    int lower_only;
+    int64_t i0, j0;
+    const double *err_y;
+    double noise_var, diag_add;
+    double *K;
+    int64_t ldk;
+    int accumulate = 0;
+    const double *Si = nullptr, *Sj = nullptr;
+};
+int launch_kbuild(hipStream_t st, const KParams &kp, const KParams *kp2, const KBuildArgs &a);      // kp2 (kernel_id >= 0): kp * kp2
 int launch_check_orders(hipStream_t st, const int32_t *dn, int64_t M, int D, int32_t *d_flag);
 int launch_gemm_nt(hipStream_t st, int64_t m, int64_t n, int64_t k, double alpha, const double *A, int64_t lda,
                    const double *B, int64_t ldb, double beta, double *C, int64_t ldc, int tri, int force_tile, int lds_pad,

@@ -8,6 +8,9 @@
 // (pure write pattern, 4.6-5.0 TB/s): SE runs at that ceiling (4.65-4.7 TB/s), Matern-5/2 is bound by its
 // sqrt + exp + divide arithmetic (2.7-3.1 TB/s).  For the fit only the tiles of the lower triangle are launched.
 // Fused epilogue: the diagonal loading of ref :1447-1451 ((K + noise_var) + err_y^2) + diag_add.
+// This file: the launchers of the single-matrix builder and the pair list for the ids of AllKids (the products: kbuild_prod.hip),
+// the noise term of a prediction and the gradient pass with their kernels.  From (kernel_id, num_dim) to an instantiation:
+// dispatch_kid / dispatch_dim, kbuild_kernel.hpp.
 #include "kbuild_kernel.hpp"
 
 // C[a][b] += noise_k(X[a], X[b], n[a], n[b]) for the symmetric predict(noise=True) term
@@ -32,180 +35,33 @@ __global__ __launch_bounds__(256) void add_noise_sym_kernel(KParams kp, const do
     C[a * ldc + b] += noise_pair<D>(kp, xa, xb, na, nb);
 }
 
-template <int KID>
-static int kbuild_dispatch_d(hipStream_t st, const KParams &kp, const double *dXi, const int32_t *dni, int64_t M,
-                             const double *dXj, const int32_t *dnj, int64_t P, int lower_only, int64_t i0,
-                             int64_t j0, const double *d_err_y, double noise_var, double diag_add, double *dK,
-                             int64_t ldk, int accumulate, const double *dSi, const double *dSj)
+int launch_kbuild(hipStream_t st, const KParams &kp, const KParams *kp2, const KBuildArgs &a)
 {
-    dim3 grid((unsigned)((P + KB_COLS - 1) / KB_COLS), (unsigned)((M + KB_ROWS - 1) / KB_ROWS));
-    dim3 block(KB_THREADS);
-    if (lower_only && i0 == j0 && M == P) {        // square lower triangle: launch only the tiles that exist
-        const int64_t nrt = (M + KB_ROWS - 1) / KB_ROWS;
-        int64_t ntile = 0;
-        for (int64_t rt = 0; rt < nrt; rt++) ntile += rt / KB_RATIO + 1;
-        grid = dim3((unsigned)ntile, 1);
-        lower_only = 2;
-    }
-    // (warp layers set: the WARP instantiation, which takes the slope factor on tiles with derivative orders -- the fit kernels only)
-    constexpr bool can_warp = KID != GPT_KERNEL_DIAGNOISE && KID != GPT_KERNEL_ZERO;
-    if (dSi != nullptr && (!can_warp || dSj == nullptr)) {
-        gpt_set_error("kbuild: warp slopes given for kernel_id %d", kp.kernel_id);
-        return GPT_E_ARG;
-    }
-#define KB_CASE(DD)                                                                                     \
-    case DD:                                                                                            \
-        if constexpr (can_warp) if (dSi != nullptr) {                                                   \
-            hipLaunchKernelGGL((kbuild_kernel<KID, DD, false, true>), grid, block, 0, st, kp, dXi, dni, M, dXj, dnj, P,   \
-                               lower_only, i0, j0, d_err_y, noise_var, diag_add, dK, ldk, accumulate,           \
-                               (const KParams *)nullptr, (const double *)nullptr, (int64_t)0, KParams(), (const KParams *)nullptr, \
-                               dSi, dSj);                                                               \
-            break;                                                                                      \
-        }                                                                                               \
-        hipLaunchKernelGGL((kbuild_kernel<KID, DD, false>), grid, block, 0, st, kp, dXi, dni, M, dXj, dnj, P,   \
-                           lower_only, i0, j0, d_err_y, noise_var, diag_add, dK, ldk, accumulate,               \
-                           (const KParams *)nullptr, (const double *)nullptr, (int64_t)0, KParams(), (const KParams *)nullptr,  \
-                           (const double *)nullptr, (const double *)nullptr);  \
-        break;
-    if constexpr (gibbs_kid(KID)) {      // (1-D kernels: one instantiation)
-        switch (kp.D) {
-            KB_CASE(1)
-        default:
-            gpt_set_error("kbuild: the Gibbs kernels need num_dim 1, got %d", kp.D);
-            return GPT_E_ARG;
-        }
-    } else switch (kp.D) {
-        KB_CASE(1) KB_CASE(2) KB_CASE(3) KB_CASE(4) KB_CASE(5) KB_CASE(6) KB_CASE(7) KB_CASE(8)
-        KB_CASE(9) KB_CASE(10) KB_CASE(11) KB_CASE(12) KB_CASE(13) KB_CASE(14) KB_CASE(15) KB_CASE(16)
-    default:
-        gpt_set_error("kbuild: unsupported num_dim %d (max %d)", kp.D, GPT_MAX_DIM);
-        return GPT_E_ARG;
-    }
-#undef KB_CASE
-    GPT_LAUNCH_CHECK();
-    return GPT_OK;
-}
-
-int launch_kbuild(hipStream_t st, const KParams &kp, const double *dXi, const int32_t *dni, int64_t M,
-                  const double *dXj, const int32_t *dnj, int64_t P, int lower_only, int64_t i0, int64_t j0,
-                  const double *d_err_y, double noise_var, double diag_add, double *dK, int64_t ldk, int accumulate,
-                  const KParams *kp2, const double *dSi, const double *dSj)
-{
-    if (kp2 && kp2->kernel_id >= 0)
-        return launch_kbuild_prod(st, kp, *kp2, dXi, dni, M, dXj, dnj, P, lower_only, i0, j0, d_err_y, noise_var, diag_add, dK, ldk,
-                                  accumulate, dSi, dSj);
     gpt_jitter(st);
-    if (M <= 0 || P <= 0) return GPT_OK;
-    switch (kp.kernel_id) {
-    case GPT_KERNEL_SE:
-        return kbuild_dispatch_d<GPT_KERNEL_SE>(st, kp, dXi, dni, M, dXj, dnj, P, lower_only, i0, j0, d_err_y,
-                                                noise_var, diag_add, dK, ldk, accumulate, dSi, dSj);
-    case GPT_KERNEL_M52:
-        return kbuild_dispatch_d<GPT_KERNEL_M52>(st, kp, dXi, dni, M, dXj, dnj, P, lower_only, i0, j0, d_err_y,
-                                                 noise_var, diag_add, dK, ldk, accumulate, dSi, dSj);
-    case GPT_KERNEL_DIAGNOISE:
-        return kbuild_dispatch_d<GPT_KERNEL_DIAGNOISE>(st, kp, dXi, dni, M, dXj, dnj, P, lower_only, i0, j0,
-                                                       d_err_y, noise_var, diag_add, dK, ldk, accumulate, dSi, dSj);
-    case GPT_KERNEL_ZERO:
-        return kbuild_dispatch_d<GPT_KERNEL_ZERO>(st, kp, dXi, dni, M, dXj, dnj, P, lower_only, i0, j0, d_err_y,
-                                                  noise_var, diag_add, dK, ldk, accumulate, dSi, dSj);
-    case GPT_KERNEL_RQ:
-        return kbuild_dispatch_d<GPT_KERNEL_RQ>(st, kp, dXi, dni, M, dXj, dnj, P, lower_only, i0, j0, d_err_y,
-                                                noise_var, diag_add, dK, ldk, accumulate, dSi, dSj);
-    case GPT_KERNEL_MATERN:
-        return kbuild_dispatch_d<GPT_KERNEL_MATERN>(st, kp, dXi, dni, M, dXj, dnj, P, lower_only, i0, j0, d_err_y,
-                                                    noise_var, diag_add, dK, ldk, accumulate, dSi, dSj);
-    case GPT_KERNEL_GIBBS_TANH:
-        return kbuild_dispatch_d<GPT_KERNEL_GIBBS_TANH>(st, kp, dXi, dni, M, dXj, dnj, P, lower_only, i0, j0, d_err_y,
-                                                        noise_var, diag_add, dK, ldk, accumulate, dSi, dSj);
-    case GPT_KERNEL_GIBBS_DTANH:
-        return kbuild_dispatch_d<GPT_KERNEL_GIBBS_DTANH>(st, kp, dXi, dni, M, dXj, dnj, P, lower_only, i0, j0, d_err_y,
-                                                         noise_var, diag_add, dK, ldk, accumulate, dSi, dSj);
-    case GPT_KERNEL_GIBBS_CUBIC:
-        return kbuild_dispatch_d<GPT_KERNEL_GIBBS_CUBIC>(st, kp, dXi, dni, M, dXj, dnj, P, lower_only, i0, j0, d_err_y,
-                                                         noise_var, diag_add, dK, ldk, accumulate, dSi, dSj);
-    case GPT_KERNEL_GIBBS_QUINTIC:
-        return kbuild_dispatch_d<GPT_KERNEL_GIBBS_QUINTIC>(st, kp, dXi, dni, M, dXj, dnj, P, lower_only, i0, j0, d_err_y,
-                                                           noise_var, diag_add, dK, ldk, accumulate, dSi, dSj);
-    case GPT_KERNEL_GIBBS_EXPGAUSS:
-        return kbuild_dispatch_d<GPT_KERNEL_GIBBS_EXPGAUSS>(st, kp, dXi, dni, M, dXj, dnj, P, lower_only, i0, j0, d_err_y,
-                                                            noise_var, diag_add, dK, ldk, accumulate, dSi, dSj);
-    default:
-        gpt_set_error("kbuild: unknown kernel_id %d", kp.kernel_id);
-        return GPT_E_ARG;
-    }
-}
-
-template <int KID>
-static int kpairs_dispatch_d(hipStream_t st, const KParams &kp, const double *dXi, const double *dXj,
-                             const int32_t *dni, const int32_t *dnj, int64_t M, double *dout, int accumulate)
-{
-    dim3 grid((unsigned)((M + 255) / 256)), block(256);
-#define KP_CASE(DD)                                                                                   \
-    case DD:                                                                                          \
-        hipLaunchKernelGGL((kpairs_kernel<KID, DD>), grid, block, 0, st, kp, dXi, dXj, dni, dnj, M, dout, accumulate, KParams()); \
-        break;
-    if constexpr (gibbs_kid(KID)) {
-        switch (kp.D) {
-            KP_CASE(1)
-        default:
-            gpt_set_error("kpairs: the Gibbs kernels need num_dim 1, got %d", kp.D);
-            return GPT_E_ARG;
-        }
-    } else switch (kp.D) {
-        KP_CASE(1) KP_CASE(2) KP_CASE(3) KP_CASE(4) KP_CASE(5) KP_CASE(6) KP_CASE(7) KP_CASE(8)
-        KP_CASE(9) KP_CASE(10) KP_CASE(11) KP_CASE(12) KP_CASE(13) KP_CASE(14) KP_CASE(15) KP_CASE(16)
-    default:
-        gpt_set_error("kpairs: unsupported num_dim %d (max %d)", kp.D, GPT_MAX_DIM);
-        return GPT_E_ARG;
-    }
-#undef KP_CASE
-    GPT_LAUNCH_CHECK();
-    return GPT_OK;
+    if (a.M <= 0 || a.P <= 0) return GPT_OK;
+    if (kp2 && kp2->kernel_id >= 0) return kbuild_prod(st, kp, *kp2, a);
+    return kbuild_dispatch(AllKids(), kp.kernel_id, st, kp, KParams(), a);
 }
 
 int launch_kpairs(hipStream_t st, const KParams &kp, const double *dXi, const double *dXj,
                   const int32_t *dni, const int32_t *dnj, int64_t M, double *dout, int accumulate, const KParams *kp2)
 {
     if (M <= 0) return GPT_OK;
-    if (kp2 && kp2->kernel_id >= 0) return launch_kpairs_prod(st, kp, *kp2, dXi, dXj, dni, dnj, M, dout, accumulate);
-    switch (kp.kernel_id) {
-    case GPT_KERNEL_SE: return kpairs_dispatch_d<GPT_KERNEL_SE>(st, kp, dXi, dXj, dni, dnj, M, dout, accumulate);
-    case GPT_KERNEL_M52: return kpairs_dispatch_d<GPT_KERNEL_M52>(st, kp, dXi, dXj, dni, dnj, M, dout, accumulate);
-    case GPT_KERNEL_DIAGNOISE: return kpairs_dispatch_d<GPT_KERNEL_DIAGNOISE>(st, kp, dXi, dXj, dni, dnj, M, dout, accumulate);
-    case GPT_KERNEL_ZERO: return kpairs_dispatch_d<GPT_KERNEL_ZERO>(st, kp, dXi, dXj, dni, dnj, M, dout, accumulate);
-    case GPT_KERNEL_RQ: return kpairs_dispatch_d<GPT_KERNEL_RQ>(st, kp, dXi, dXj, dni, dnj, M, dout, accumulate);
-    case GPT_KERNEL_MATERN: return kpairs_dispatch_d<GPT_KERNEL_MATERN>(st, kp, dXi, dXj, dni, dnj, M, dout, accumulate);
-    case GPT_KERNEL_GIBBS_TANH: return kpairs_dispatch_d<GPT_KERNEL_GIBBS_TANH>(st, kp, dXi, dXj, dni, dnj, M, dout, accumulate);
-    case GPT_KERNEL_GIBBS_DTANH: return kpairs_dispatch_d<GPT_KERNEL_GIBBS_DTANH>(st, kp, dXi, dXj, dni, dnj, M, dout, accumulate);
-    case GPT_KERNEL_GIBBS_CUBIC: return kpairs_dispatch_d<GPT_KERNEL_GIBBS_CUBIC>(st, kp, dXi, dXj, dni, dnj, M, dout, accumulate);
-    case GPT_KERNEL_GIBBS_QUINTIC: return kpairs_dispatch_d<GPT_KERNEL_GIBBS_QUINTIC>(st, kp, dXi, dXj, dni, dnj, M, dout, accumulate);
-    case GPT_KERNEL_GIBBS_EXPGAUSS: return kpairs_dispatch_d<GPT_KERNEL_GIBBS_EXPGAUSS>(st, kp, dXi, dXj, dni, dnj, M, dout, accumulate);
-    default:
-        gpt_set_error("kpairs: unknown kernel_id %d", kp.kernel_id);
-        return GPT_E_ARG;
-    }
+    const KPairsArgs a = {dXi, dXj, dni, dnj, M, dout, accumulate};
+    if (kp2 && kp2->kernel_id >= 0) return kpairs_prod(st, kp, *kp2, a);
+    return kpairs_dispatch(AllKids(), kp.kernel_id, st, kp, KParams(), a);
 }
 
 int launch_add_noise_sym(hipStream_t st, const KParams &kp, const double *dX, const int32_t *dn, int64_t M,
                          double *C, int64_t ldc)
 {
     if (M <= 0) return GPT_OK;
-    dim3 grid((unsigned)((M + 255) / 256), (unsigned)M), block(256);
-#define AN_CASE(DD)                                                                                  \
-    case DD:                                                                                         \
-        hipLaunchKernelGGL((add_noise_sym_kernel<DD>), grid, block, 0, st, kp, dX, dn, M, C, ldc);   \
-        break;
-    switch (kp.D) {
-        AN_CASE(1) AN_CASE(2) AN_CASE(3) AN_CASE(4) AN_CASE(5) AN_CASE(6) AN_CASE(7) AN_CASE(8)
-        AN_CASE(9) AN_CASE(10) AN_CASE(11) AN_CASE(12) AN_CASE(13) AN_CASE(14) AN_CASE(15) AN_CASE(16)
-    default:
-        gpt_set_error("add_noise: unsupported num_dim %d", kp.D);
-        return GPT_E_ARG;
-    }
-#undef AN_CASE
-    GPT_LAUNCH_CHECK();
-    return GPT_OK;
+    return dispatch_dim<GPT_MAX_DIM>("add_noise", kp.D, [&](auto d) {
+        hipLaunchKernelGGL((add_noise_sym_kernel<decltype(d)::value>), dim3((unsigned)((M + 255) / 256), (unsigned)M), dim3(256), 0, st, kp,
+                           dX, dn, M, C, ldc);
+        GPT_LAUNCH_CHECK();
+        return GPT_OK;
+    });
 }
 
 // ------------------------------------------------------------------------------------------------
@@ -283,45 +139,25 @@ __global__ __launch_bounds__(KB_THREADS) void grad_reduce_kernel(
     }
 }
 
-int grad_reduce_blocks(int64_t N)
-{
-    const int64_t nrt = (N + KB_ROWS - 1) / KB_ROWS;
-    int64_t ntile = 0;
-    for (int64_t rt = 0; rt < nrt; rt++) ntile += rt / KB_RATIO + 1;
-    return (int)ntile;
-}
-
-template <int KID>
-static int grad_dispatch_d(hipStream_t st, const KParams &kp, int nh, const int *hl, const double *dX, const int32_t *dn,
-                           int64_t N, const double *dalpha, const double *dW, int64_t ldw, double *dpartial)
-{
-    dim3 grid((unsigned)grad_reduce_blocks(N)), block(KB_THREADS);
-    int h[GR_MAXH];
-    for (int i = 0; i < GR_MAXH; i++) h[i] = i < nh ? hl[i] : -1;
-#define GR_CASE(DD)                                                                                                  \
-    case DD:                                                                                                         \
-        hipLaunchKernelGGL((grad_reduce_kernel<KID, DD>), grid, block, 0, st, kp, nh, (const int *)nullptr, h[0], h[1], \
-                           h[2], h[3], h[4], h[5], h[6], h[7], dX, dn, N, dalpha, dW, ldw, dpartial);                 \
-        break;
-    switch (kp.D) {
-        GR_CASE(1) GR_CASE(2) GR_CASE(3) GR_CASE(4) GR_CASE(5) GR_CASE(6) GR_CASE(7) GR_CASE(8)
-        GR_CASE(9) GR_CASE(10) GR_CASE(11) GR_CASE(12) GR_CASE(13) GR_CASE(14) GR_CASE(15) GR_CASE(16)
-    default:
-        gpt_set_error("grad_reduce: unsupported num_dim %d", kp.D);
-        return GPT_E_ARG;
-    }
-#undef GR_CASE
-    GPT_LAUNCH_CHECK();
-    return GPT_OK;
-}
+int grad_reduce_blocks(int64_t N) { return (int)lower_tile_count(N); }
 
 // up to GR_MAXH hyper-derivative indices hl[] of ONE kernel term; partial: grad_reduce_blocks(N) x (GR_MAXH + 1)
 int launch_grad_reduce(hipStream_t st, const KParams &kp, int nh, const int *hl, const double *dX, const int32_t *dn,
                        int64_t N, const double *dalpha, const double *dW, int64_t ldw, double *dpartial)
 {
     if (nh < 0 || nh > GR_MAXH) return GPT_E_ARG;
-    if (kp.kernel_id == GPT_KERNEL_SE)
-        return grad_dispatch_d<GPT_KERNEL_SE>(st, kp, nh, hl, dX, dn, N, dalpha, dW, ldw, dpartial);
-    gpt_set_error("hyper-parameter derivatives exist for the squared-exponential kernel only (ref: matern.py:543-544)");
-    return GPT_E_NOTIMPL;
+    int h[GR_MAXH];
+    for (int i = 0; i < GR_MAXH; i++) h[i] = i < nh ? hl[i] : -1;
+    return dispatch_kid(KidList<GPT_KERNEL_SE>(), kp.kernel_id, [&](auto k) {
+        return dispatch_dim<GPT_MAX_DIM>("grad_reduce", kp.D, [&](auto d) {
+            hipLaunchKernelGGL((grad_reduce_kernel<decltype(k)::value, decltype(d)::value>), dim3((unsigned)grad_reduce_blocks(N)),
+                               dim3(KB_THREADS), 0, st, kp, nh, (const int *)nullptr, h[0], h[1], h[2], h[3], h[4], h[5], h[6], h[7], dX, dn,
+                               N, dalpha, dW, ldw, dpartial);
+            GPT_LAUNCH_CHECK();
+            return GPT_OK;
+        });
+    }, [] {
+        gpt_set_error("hyper-parameter derivatives exist for the squared-exponential kernel only (ref: matern.py:543-544)");
+        return GPT_E_NOTIMPL;
+    });
 }

@@ -4,81 +4,38 @@
 // (kbuild_kernel.hpp), so an element of a batch holds the very numbers gpt_fit would build alone.
 // ref: gptools/gaussian_process.py:1607-1692 (compute_ll_matrix) and :723-735 (random starts) evaluate the LML at many
 // hyperparameter vectors one after another; this is their builder.
-#include <string.h>
+// The launchers fill KBuildArgs / KBatchArgs and go through the dispatch of kbuild_kernel.hpp (FitKids; a product term:
+// ProductKids by product_kid); the two kernels of the predictive half that loop over terms and elements are defined here.
 #include "kbuild_kernel.hpp"
+
+// One term of every element: kernel_id, or (d_kps2 != NULL) a product term, whose factors' ids the kernel reads from the elements'
+// KParams at run time.  `who` names the launcher in a refusal.
+static int kbuild_batch_dispatch(const char *who, hipStream_t st, int kernel_id, int D, const KBuildArgs &a, const KBatchArgs &b)
+{
+    const KParams dummy = KParams();
+    auto for_kid = [&](auto k) {
+        constexpr int KID = decltype(k)::value;
+        return dispatch_dim<kid_max_dim(KID)>(who, D, [&](auto d) { return kbuild_launch<KID, decltype(d)::value, true>(st, dummy, dummy, a, b); });
+    };
+    if (b.kps2 != nullptr) return dispatch_kid(ProductKids(), product_kid(D, -1, -1, true), for_kid, [] { return GPT_E_ARG; });
+    return dispatch_kid(FitKids(), kernel_id, for_kid, [&] {
+        gpt_set_error("%s: kernel_id %d is not a fit kernel", who, kernel_id);
+        return GPT_E_ARG;
+    });
+}
 
 // full != 0: the whole symmetric N x N matrix of every element (the transform path multiplies it by T from both sides), else
 // the tiles of its lower triangle.  d_kps2 (product terms): element z's second factor.
-template <int KID>
-static int kbuild_batch_d(hipStream_t st, int D, const KParams *d_kps, const double *d_nv, int64_t nbatch, const double *dX,
-                          const int32_t *dn, int64_t N, const double *d_err_y, double diag_add, double *dK, int64_t ldk,
-                          int64_t bstride, int accumulate, int full, const KParams *d_kps2, int64_t xstride, const double *dS,
-                          int64_t sstride)
-{
-    const int64_t nrt = (N + KB_ROWS - 1) / KB_ROWS;
-    int64_t ntile = 0;
-    for (int64_t rt = 0; rt < nrt; rt++) ntile += rt / KB_RATIO + 1;
-    dim3 grid((unsigned)ntile, 1, (unsigned)nbatch), block(KB_THREADS);
-    if (full) grid = dim3((unsigned)((N + KB_COLS - 1) / KB_COLS), (unsigned)nrt, (unsigned)nbatch);
-    const int lower = full ? 0 : 2;
-    KParams dummy = KParams();
-    // (dS != NULL: a warped batch -- element z's points at dX + z * xstride, its slope factors at dS + z * sstride, the WARP instantiation)
-#define KBB_CASE(DD)                                                                                              \
-    case DD:                                                                                                      \
-        if (dS != nullptr) {                                                                                      \
-            hipLaunchKernelGGL((kbuild_kernel<KID, DD, true, true>), grid, block, 0, st, dummy, dX, dn, N, dX, dn, N, lower, \
-                               (int64_t)0, (int64_t)0, d_err_y, 0.0, diag_add, dK, ldk, accumulate, d_kps, d_nv, bstride, dummy, d_kps2, \
-                               dS, dS, xstride, sstride);                                                         \
-            break;                                                                                                \
-        }                                                                                                         \
-        hipLaunchKernelGGL((kbuild_kernel<KID, DD, true>), grid, block, 0, st, dummy, dX, dn, N, dX, dn, N, lower, \
-                           (int64_t)0, (int64_t)0, d_err_y, 0.0, diag_add, dK, ldk, accumulate, d_kps, d_nv, bstride, dummy, d_kps2, \
-                           (const double *)nullptr, (const double *)nullptr); \
-        break;
-    if constexpr (gibbs_kid(KID) || KID == GPT_KID_PRODUCT_GM) {      // (1-D kernels: one instantiation)
-        switch (D) {
-            KBB_CASE(1)
-        default:
-            gpt_set_error("kbuild_batch: the Gibbs kernels need num_dim 1, got %d", D);
-            return GPT_E_ARG;
-        }
-    } else switch (D) {
-        KBB_CASE(1) KBB_CASE(2) KBB_CASE(3) KBB_CASE(4) KBB_CASE(5) KBB_CASE(6) KBB_CASE(7) KBB_CASE(8)
-        KBB_CASE(9) KBB_CASE(10) KBB_CASE(11) KBB_CASE(12) KBB_CASE(13) KBB_CASE(14) KBB_CASE(15) KBB_CASE(16)
-    default:
-        gpt_set_error("kbuild_batch: unsupported num_dim %d (max %d)", D, GPT_MAX_DIM);
-        return GPT_E_ARG;
-    }
-#undef KBB_CASE
-    GPT_LAUNCH_CHECK();
-    return GPT_OK;
-}
-
+// (dS != NULL: a warped batch -- element z's points at dX + z * xstride, its slope factors at dS + z * sstride, the WARP instantiation)
 int launch_kbuild_batch(hipStream_t st, int kernel_id, int D, const KParams *d_kps, const double *d_noise_var, int64_t nbatch,
                         const double *dX, const int32_t *dn, int64_t N, const double *d_err_y, double diag_add, double *dK,
                         int64_t ldk, int64_t bstride, int accumulate, int full, const KParams *d_kps2, int64_t xstride,
                         const double *dS, int64_t sstride)
 {
     if (N <= 0 || nbatch <= 0) return GPT_OK;
-    if (d_kps2 != nullptr)           // a product term: the factors' kernel ids are read from the elements' KParams at run time
-        return D == 1 ? kbuild_batch_d<GPT_KID_PRODUCT_GM>(st, D, d_kps, d_noise_var, nbatch, dX, dn, N, d_err_y, diag_add, dK, ldk, bstride,
-                                                           accumulate, full, d_kps2, xstride, dS, sstride)
-                      : kbuild_batch_d<GPT_KERNEL_PRODUCT>(st, D, d_kps, d_noise_var, nbatch, dX, dn, N, d_err_y, diag_add, dK, ldk, bstride,
-                                                           accumulate, full, d_kps2, xstride, dS, sstride);
-    switch (kernel_id) {
-    case GPT_KERNEL_SE: return kbuild_batch_d<GPT_KERNEL_SE>(st, D, d_kps, d_noise_var, nbatch, dX, dn, N, d_err_y, diag_add, dK, ldk, bstride, accumulate, full, nullptr, xstride, dS, sstride);
-    case GPT_KERNEL_M52: return kbuild_batch_d<GPT_KERNEL_M52>(st, D, d_kps, d_noise_var, nbatch, dX, dn, N, d_err_y, diag_add, dK, ldk, bstride, accumulate, full, nullptr, xstride, dS, sstride);
-    case GPT_KERNEL_RQ: return kbuild_batch_d<GPT_KERNEL_RQ>(st, D, d_kps, d_noise_var, nbatch, dX, dn, N, d_err_y, diag_add, dK, ldk, bstride, accumulate, full, nullptr, xstride, dS, sstride);
-    case GPT_KERNEL_MATERN: return kbuild_batch_d<GPT_KERNEL_MATERN>(st, D, d_kps, d_noise_var, nbatch, dX, dn, N, d_err_y, diag_add, dK, ldk, bstride, accumulate, full, nullptr, xstride, dS, sstride);
-    case GPT_KERNEL_GIBBS_TANH: return kbuild_batch_d<GPT_KERNEL_GIBBS_TANH>(st, D, d_kps, d_noise_var, nbatch, dX, dn, N, d_err_y, diag_add, dK, ldk, bstride, accumulate, full, nullptr, xstride, dS, sstride);
-    case GPT_KERNEL_GIBBS_DTANH: return kbuild_batch_d<GPT_KERNEL_GIBBS_DTANH>(st, D, d_kps, d_noise_var, nbatch, dX, dn, N, d_err_y, diag_add, dK, ldk, bstride, accumulate, full, nullptr, xstride, dS, sstride);
-    case GPT_KERNEL_GIBBS_CUBIC: return kbuild_batch_d<GPT_KERNEL_GIBBS_CUBIC>(st, D, d_kps, d_noise_var, nbatch, dX, dn, N, d_err_y, diag_add, dK, ldk, bstride, accumulate, full, nullptr, xstride, dS, sstride);
-    case GPT_KERNEL_GIBBS_QUINTIC: return kbuild_batch_d<GPT_KERNEL_GIBBS_QUINTIC>(st, D, d_kps, d_noise_var, nbatch, dX, dn, N, d_err_y, diag_add, dK, ldk, bstride, accumulate, full, nullptr, xstride, dS, sstride);
-    case GPT_KERNEL_GIBBS_EXPGAUSS: return kbuild_batch_d<GPT_KERNEL_GIBBS_EXPGAUSS>(st, D, d_kps, d_noise_var, nbatch, dX, dn, N, d_err_y, diag_add, dK, ldk, bstride, accumulate, full, nullptr, xstride, dS, sstride);
-    default:
-        gpt_set_error("kbuild_batch: kernel_id %d is not a fit kernel", kernel_id);
-        return GPT_E_ARG;
-    }
+    const KBuildArgs a = {dX, dn, N, dX, dn, N, full ? 0 : 1, 0, 0, d_err_y, 0.0, diag_add, dK, ldk, accumulate, dS, dS};
+    const KBatchArgs b = {d_kps, d_noise_var, nbatch, bstride, d_kps2, xstride, sstride};
+    return kbuild_batch_dispatch("kbuild_batch", st, kernel_id, D, a, b);
 }
 
 // ---- the predictive half of a resident batch (gpt_predict_batch, api_batch.inc) ----------------------------------------
@@ -86,38 +43,6 @@ int launch_kbuild_batch(hipStream_t st, int kernel_id, int D, const KParams *d_k
 // (K*_b^T, or K**_b with Xi = Xj), element z at dK + z * bstride.  Sums and products as launch_kbuild_batch: later terms
 // accumulate, a product term reads its factors' ids from the elements' KParams.
 // (d_nv: the elements' noise variances -- the batched kernel reads its element's entry, though without err_y nothing uses it)
-template <int KID>
-static int kbuild_batch_cross_d(hipStream_t st, int D, const KParams *d_kps, const double *d_nv, int64_t nbatch, const double *dXi,
-                                const int32_t *dni, int64_t M, const double *dXj, const int32_t *dnj, int64_t P, double *dK, int64_t ldk,
-                                int64_t bstride, int accumulate, const KParams *d_kps2)
-{
-    dim3 grid((unsigned)((P + KB_COLS - 1) / KB_COLS), (unsigned)((M + KB_ROWS - 1) / KB_ROWS), (unsigned)nbatch), block(KB_THREADS);
-    KParams dummy = KParams();
-#define KBC_CASE(DD)                                                                                                         \
-    case DD:                                                                                                                 \
-        hipLaunchKernelGGL((kbuild_kernel<KID, DD, true>), grid, block, 0, st, dummy, dXi, dni, M, dXj, dnj, P, 0, (int64_t)0, \
-                           (int64_t)0, nullptr, 0.0, 0.0, dK, ldk, accumulate, d_kps, d_nv, bstride, dummy, d_kps2,          \
-                           (const double *)nullptr, (const double *)nullptr);                                        \
-        break;
-    if constexpr (gibbs_kid(KID) || KID == GPT_KID_PRODUCT_GM) {
-        switch (D) {
-            KBC_CASE(1)
-        default:
-            gpt_set_error("kbuild_batch_cross: the Gibbs kernels need num_dim 1, got %d", D);
-            return GPT_E_ARG;
-        }
-    } else switch (D) {
-        KBC_CASE(1) KBC_CASE(2) KBC_CASE(3) KBC_CASE(4) KBC_CASE(5) KBC_CASE(6) KBC_CASE(7) KBC_CASE(8)
-        KBC_CASE(9) KBC_CASE(10) KBC_CASE(11) KBC_CASE(12) KBC_CASE(13) KBC_CASE(14) KBC_CASE(15) KBC_CASE(16)
-    default:
-        gpt_set_error("kbuild_batch_cross: unsupported num_dim %d (max %d)", D, GPT_MAX_DIM);
-        return GPT_E_ARG;
-    }
-#undef KBC_CASE
-    GPT_LAUNCH_CHECK();
-    return GPT_OK;
-}
-
 int launch_kbuild_batch_cross(hipStream_t st, int kernel_id, int D, const KParams *d_kps, const double *d_nv, int64_t nbatch,
                               const double *dXi, const int32_t *dni, int64_t M, const double *dXj, const int32_t *dnj, int64_t P, double *dK,
                               int64_t ldk, int64_t bstride, int accumulate, const KParams *d_kps2)
@@ -127,23 +52,9 @@ int launch_kbuild_batch_cross(hipStream_t st, int kernel_id, int D, const KParam
         gpt_set_error("kbuild_batch_cross: the elements' KParams and noise variances must be device arrays");
         return GPT_E_ARG;
     }
-    if (d_kps2 != nullptr)
-        return D == 1 ? kbuild_batch_cross_d<GPT_KID_PRODUCT_GM>(st, D, d_kps, d_nv, nbatch, dXi, dni, M, dXj, dnj, P, dK, ldk, bstride, accumulate, d_kps2)
-                      : kbuild_batch_cross_d<GPT_KERNEL_PRODUCT>(st, D, d_kps, d_nv, nbatch, dXi, dni, M, dXj, dnj, P, dK, ldk, bstride, accumulate, d_kps2);
-    switch (kernel_id) {
-    case GPT_KERNEL_SE: return kbuild_batch_cross_d<GPT_KERNEL_SE>(st, D, d_kps, d_nv, nbatch, dXi, dni, M, dXj, dnj, P, dK, ldk, bstride, accumulate, nullptr);
-    case GPT_KERNEL_M52: return kbuild_batch_cross_d<GPT_KERNEL_M52>(st, D, d_kps, d_nv, nbatch, dXi, dni, M, dXj, dnj, P, dK, ldk, bstride, accumulate, nullptr);
-    case GPT_KERNEL_RQ: return kbuild_batch_cross_d<GPT_KERNEL_RQ>(st, D, d_kps, d_nv, nbatch, dXi, dni, M, dXj, dnj, P, dK, ldk, bstride, accumulate, nullptr);
-    case GPT_KERNEL_MATERN: return kbuild_batch_cross_d<GPT_KERNEL_MATERN>(st, D, d_kps, d_nv, nbatch, dXi, dni, M, dXj, dnj, P, dK, ldk, bstride, accumulate, nullptr);
-    case GPT_KERNEL_GIBBS_TANH: return kbuild_batch_cross_d<GPT_KERNEL_GIBBS_TANH>(st, D, d_kps, d_nv, nbatch, dXi, dni, M, dXj, dnj, P, dK, ldk, bstride, accumulate, nullptr);
-    case GPT_KERNEL_GIBBS_DTANH: return kbuild_batch_cross_d<GPT_KERNEL_GIBBS_DTANH>(st, D, d_kps, d_nv, nbatch, dXi, dni, M, dXj, dnj, P, dK, ldk, bstride, accumulate, nullptr);
-    case GPT_KERNEL_GIBBS_CUBIC: return kbuild_batch_cross_d<GPT_KERNEL_GIBBS_CUBIC>(st, D, d_kps, d_nv, nbatch, dXi, dni, M, dXj, dnj, P, dK, ldk, bstride, accumulate, nullptr);
-    case GPT_KERNEL_GIBBS_QUINTIC: return kbuild_batch_cross_d<GPT_KERNEL_GIBBS_QUINTIC>(st, D, d_kps, d_nv, nbatch, dXi, dni, M, dXj, dnj, P, dK, ldk, bstride, accumulate, nullptr);
-    case GPT_KERNEL_GIBBS_EXPGAUSS: return kbuild_batch_cross_d<GPT_KERNEL_GIBBS_EXPGAUSS>(st, D, d_kps, d_nv, nbatch, dXi, dni, M, dXj, dnj, P, dK, ldk, bstride, accumulate, nullptr);
-    default:
-        gpt_set_error("kbuild_batch_cross: kernel_id %d is not a fit kernel", kernel_id);
-        return GPT_E_ARG;
-    }
+    const KBuildArgs a = {dXi, dni, M, dXj, dnj, P, 0, 0, 0, nullptr, 0.0, 0.0, dK, ldk, accumulate};
+    const KBatchArgs b = {d_kps, d_nv, nbatch, bstride, d_kps2};
+    return kbuild_batch_dispatch("kbuild_batch_cross", st, kernel_id, D, a, b);
 }
 
 // One term of element b's kernel at a pair, kernels chosen at run time (the two kernels below loop over terms AND elements,
@@ -220,21 +131,12 @@ int launch_kdiag_batch(hipStream_t st, int D, int nterms, const KParams *d_kps, 
                        const int32_t *dn, int64_t M, double *dout, int64_t ldo)
 {
     if (M <= 0 || nbatch <= 0) return GPT_OK;
-    dim3 grid((unsigned)((M + 255) / 256), (unsigned)nbatch);
-#define KD_CASE(DD)                                                                                                               \
-    case DD:                                                                                                                      \
-        hipLaunchKernelGGL(kdiag_batch_kernel<DD>, grid, dim3(256), 0, st, nterms, d_kps, d_kps2, nbatch, dX, dn, M, dout, ldo); \
-        break;
-    switch (D) {
-        KD_CASE(1) KD_CASE(2) KD_CASE(3) KD_CASE(4) KD_CASE(5) KD_CASE(6) KD_CASE(7) KD_CASE(8)
-        KD_CASE(9) KD_CASE(10) KD_CASE(11) KD_CASE(12) KD_CASE(13) KD_CASE(14) KD_CASE(15) KD_CASE(16)
-    default:
-        gpt_set_error("kdiag_batch: unsupported num_dim %d (max %d)", D, GPT_MAX_DIM);
-        return GPT_E_ARG;
-    }
-#undef KD_CASE
-    GPT_LAUNCH_CHECK();
-    return GPT_OK;
+    return dispatch_dim<GPT_MAX_DIM>("kdiag_batch", D, [&](auto d) {
+        hipLaunchKernelGGL(kdiag_batch_kernel<decltype(d)::value>, dim3((unsigned)((M + 255) / 256), (unsigned)nbatch), dim3(256), 0, st,
+                           nterms, d_kps, d_kps2, nbatch, dX, dn, M, dout, ldo);
+        GPT_LAUNCH_CHECK();
+        return GPT_OK;
+    });
 }
 
 int launch_kss_sum(hipStream_t st, int D, int nterms, const KParams *d_kps, const KParams *d_kps2, int64_t nbatch, const int32_t *d_keep,
@@ -243,20 +145,10 @@ int launch_kss_sum(hipStream_t st, int D, int nterms, const KParams *d_kps, cons
 {
     if (MP <= 0) return GPT_OK;
     const unsigned nt = (unsigned)((MP + 15) / 16);
-    dim3 grid(nt, nt);
-#define KS_CASE(DD)                                                                                                                  \
-    case DD:                                                                                                                         \
-        hipLaunchKernelGGL(kss_sum_kernel<DD>, grid, dim3(256), 0, st, nterms, d_kps, d_kps2, nbatch, d_keep, dX, dn, M, MP, d_hit, \
-                           noise_sum, dC, ldc);                                                                                      \
-        break;
-    switch (D) {
-        KS_CASE(1) KS_CASE(2) KS_CASE(3) KS_CASE(4) KS_CASE(5) KS_CASE(6) KS_CASE(7) KS_CASE(8)
-        KS_CASE(9) KS_CASE(10) KS_CASE(11) KS_CASE(12) KS_CASE(13) KS_CASE(14) KS_CASE(15) KS_CASE(16)
-    default:
-        gpt_set_error("kss_sum: unsupported num_dim %d (max %d)", D, GPT_MAX_DIM);
-        return GPT_E_ARG;
-    }
-#undef KS_CASE
-    GPT_LAUNCH_CHECK();
-    return GPT_OK;
+    return dispatch_dim<GPT_MAX_DIM>("kss_sum", D, [&](auto d) {
+        hipLaunchKernelGGL(kss_sum_kernel<decltype(d)::value>, dim3(nt, nt), dim3(256), 0, st, nterms, d_kps, d_kps2, nbatch, d_keep, dX, dn,
+                           M, MP, d_hit, noise_sum, dC, ldc);
+        GPT_LAUNCH_CHECK();
+        return GPT_OK;
+    });
 }

@@ -1,5 +1,6 @@
 // kbuild_kernel.hpp -- the fused covariance-builder kernel (see kbuild.hip), shared by the single-matrix launcher
-// (kbuild.hip) and the batched one (kbuild_batch.hip: gpt_fit_batch, one matrix per blockIdx.z).
+// (kbuild.hip) and the batched one (kbuild_batch.hip: gpt_fit_batch, one matrix per blockIdx.z); below the kernels, the host
+// side all the launchers share: kernel-id and num_dim dispatch, the tile grid, the one launch of kbuild_kernel.
 #pragma once
 #include "kpair.hpp"
 
@@ -231,3 +232,165 @@ __global__ __launch_bounds__(256) void kpairs_kernel(KParams kp, const double *_
     else v = any_pair<KID, D>(kp, xi, xj, nir, njr);
     out[m] = accumulate ? out[m] + v : v;
 }
+
+// ================================================================================================
+// Host side: from the run-time (kernel_id, num_dim) to ONE instantiation of the templates above.  Every launcher of kbuild.hip,
+// kbuild_prod.hip and kbuild_batch.hip goes through dispatch_kid and dispatch_dim; a new kernel id is one entry of FitKids.
+// ================================================================================================
+#include <type_traits>
+#include <utility>
+
+// the ids a launcher accepts, as a type
+template <int... KIDS>
+struct KidList {
+    template <int... MORE>
+    using plus = KidList<KIDS..., MORE...>;
+};
+// the kernels a model term can be (native_fit_kernel, api_kparams.inc): what the batched builders take
+using FitKids = KidList<GPT_KERNEL_SE, GPT_KERNEL_M52, GPT_KERNEL_RQ, GPT_KERNEL_MATERN, GPT_KERNEL_GIBBS_TANH, GPT_KERNEL_GIBBS_DTANH,
+                        GPT_KERNEL_GIBBS_CUBIC, GPT_KERNEL_GIBBS_QUINTIC, GPT_KERNEL_GIBBS_EXPGAUSS>;
+// ... and the noise kernels: the single-matrix builder and the pair list
+using AllKids = FitKids::plus<GPT_KERNEL_DIAGNOISE, GPT_KERNEL_ZERO>;
+// the builders' two product instantiations (product_kid chooses)
+using ProductKids = KidList<GPT_KERNEL_PRODUCT, GPT_KID_PRODUCT_GM>;
+
+// The product of the factors id1 * id2 at num_dim D: GPT_KID_PRODUCT_GM carries the bucket / exp-Gauss Gibbs branches and exists
+// at num_dim 1 only.  The single-matrix kernels take it only when a factor needs those branches (GPT_KERNEL_PRODUCT at num_dim 1
+// stays the code it was, for the products of the older kernels); the batched ones, whose factor ids only the device sees, take it
+// for every 1-D product.  Why: common.hpp, at GPT_KID_PRODUCT_GM.
+inline int product_kid(int D, int id1, int id2, bool batched)
+{
+    return D == 1 && (batched || gibbs_more_kid(id1) || gibbs_more_kid(id2)) ? GPT_KID_PRODUCT_GM : GPT_KERNEL_PRODUCT;
+}
+
+constexpr int kid_max_dim(int kid) { return gibbs_kid(kid) || kid == GPT_KID_PRODUCT_GM ? 1 : GPT_MAX_DIM; }
+// (the WARP instantiations exist for these only: the noise kernels are never warped)
+constexpr bool kid_can_warp(int kid) { return kid != GPT_KERNEL_DIAGNOISE && kid != GPT_KERNEL_ZERO; }
+
+// f(std::integral_constant<int, KID>()) for the entry of the list that equals `kid`, else refuse() -- the launcher's own message
+// and status
+template <int... KIDS, class F, class R>
+int dispatch_kid(KidList<KIDS...>, int kid, F &&f, R &&refuse)
+{
+    int rc = GPT_OK;
+    const bool hit = ((kid == KIDS && (rc = f(std::integral_constant<int, KIDS>()), true)) || ...);
+    return hit ? rc : refuse();
+}
+
+template <class F, int... I>
+bool dispatch_dim_fold(int D, F &f, int &rc, std::integer_sequence<int, I...>)
+{
+    return ((D == I + 1 && (rc = f(std::integral_constant<int, I + 1>()), true)) || ...);
+}
+
+// f(std::integral_constant<int, D>()) for D in 1 .. MAXD (kid_max_dim); `who` names the launcher in the refusal
+template <int MAXD, class F>
+int dispatch_dim(const char *who, int D, F &&f)
+{
+    int rc = GPT_OK;
+    if (dispatch_dim_fold(D, f, rc, std::make_integer_sequence<int, MAXD>())) return rc;
+    if (MAXD == 1) gpt_set_error("%s: the Gibbs kernels need num_dim 1, got %d", who, D);
+    else gpt_set_error("%s: unsupported num_dim %d (max %d)", who, D, MAXD);
+    return GPT_E_ARG;
+}
+
+// Tiles of the lower triangle of an N x N matrix: row tile rt (KB_ROWS rows) needs column tiles 0 .. rt / KB_RATIO
+inline int64_t lower_tile_count(int64_t N)
+{
+    const int64_t nrt = (N + KB_ROWS - 1) / KB_ROWS;
+    int64_t ntile = 0;
+    for (int64_t rt = 0; rt < nrt; rt++) ntile += rt / KB_RATIO + 1;
+    return ntile;
+}
+
+// The builder's grid and the lower_only it is launched with.  A square block on the diagonal with lower_only set (the batched fit
+// without a transform asks for exactly that; `full` = lower_only 0) launches only the tiles that exist, in the kernel's mode 2;
+// everything else is the whole rectangle.  nbatch: one matrix per blockIdx.z.
+struct TileGrid {
+    dim3 grid;
+    int lower_only;
+};
+inline TileGrid tile_grid(int64_t M, int64_t P, int lower_only, int64_t i0, int64_t j0, int64_t nbatch = 1)
+{
+    if (lower_only && i0 == j0 && M == P) return {dim3((unsigned)lower_tile_count(M), 1, (unsigned)nbatch), 2};
+    return {dim3((unsigned)((P + KB_COLS - 1) / KB_COLS), (unsigned)((M + KB_ROWS - 1) / KB_ROWS), (unsigned)nbatch), lower_only};
+}
+
+// What a batched launch adds to KBuildArgs (common.hpp): element z's hyperparameters kps[z] (kps2[z]: the second factor of a product
+// term), its noise variance nvs[z], its matrix at K + z * bstride; warped: its points at X + z * xstride, its slopes at S + z * sstride
+struct KBatchArgs {
+    const KParams *kps = nullptr;
+    const double *nvs = nullptr;
+    int64_t nbatch = 1, bstride = 0;
+    const KParams *kps2 = nullptr;
+    int64_t xstride = 0, sstride = 0;
+};
+
+// THE launch of kbuild_kernel: the parameters a mode does not use are padded here, and the WARP instantiation is chosen here (slopes
+// given; for the kernels that can warp only).  kp / kp2: the single matrix's hyperparameters (dummies for a batch).
+template <int KID, int D, bool BATCH>
+int kbuild_launch(hipStream_t st, const KParams &kp, const KParams &kp2, const KBuildArgs &a, const KBatchArgs &b = KBatchArgs())
+{
+    const TileGrid tg = tile_grid(a.M, a.P, a.lower_only, a.i0, a.j0, b.nbatch);
+    const dim3 block(KB_THREADS);
+    if constexpr (kid_can_warp(KID)) {
+        if (a.Si != nullptr) {
+            hipLaunchKernelGGL((kbuild_kernel<KID, D, BATCH, true>), tg.grid, block, 0, st, kp, a.Xi, a.ni, a.M, a.Xj, a.nj, a.P,
+                               tg.lower_only, a.i0, a.j0, a.err_y, a.noise_var, a.diag_add, a.K, a.ldk, a.accumulate, b.kps, b.nvs,
+                               b.bstride, kp2, b.kps2, a.Si, a.Sj, b.xstride, b.sstride);
+            GPT_LAUNCH_CHECK();
+            return GPT_OK;
+        }
+    }
+    hipLaunchKernelGGL((kbuild_kernel<KID, D, BATCH, false>), tg.grid, block, 0, st, kp, a.Xi, a.ni, a.M, a.Xj, a.nj, a.P, tg.lower_only,
+                       a.i0, a.j0, a.err_y, a.noise_var, a.diag_add, a.K, a.ldk, a.accumulate, b.kps, b.nvs, b.bstride, kp2, b.kps2,
+                       (const double *)nullptr, (const double *)nullptr, (int64_t)0, (int64_t)0);
+    GPT_LAUNCH_CHECK();
+    return GPT_OK;
+}
+
+// The single-matrix builder / pair list for the ids of one list: AllKids in kbuild.hip, ProductKids (kid from product_kid) in
+// kbuild_prod.hip -- each translation unit compiles the instantiations of its list.
+template <class LIST>
+int kbuild_dispatch(LIST list, int kid, hipStream_t st, const KParams &kp, const KParams &kp2, const KBuildArgs &a)
+{
+    return dispatch_kid(list, kid, [&](auto k) {
+        constexpr int KID = decltype(k)::value;
+        if (a.Si != nullptr && (!kid_can_warp(KID) || a.Sj == nullptr)) {
+            gpt_set_error("kbuild: warp slopes given for kernel_id %d", kp.kernel_id);
+            return GPT_E_ARG;
+        }
+        return dispatch_dim<kid_max_dim(KID)>("kbuild", kp.D, [&](auto d) { return kbuild_launch<KID, decltype(d)::value, false>(st, kp, kp2, a); });
+    }, [&] {
+        gpt_set_error("kbuild: unknown kernel_id %d", kid);
+        return GPT_E_ARG;
+    });
+}
+
+struct KPairsArgs {
+    const double *Xi, *Xj;
+    const int32_t *ni, *nj;
+    int64_t M;
+    double *out;
+    int accumulate;
+};
+template <class LIST>
+int kpairs_dispatch(LIST list, int kid, hipStream_t st, const KParams &kp, const KParams &kp2, const KPairsArgs &a)
+{
+    return dispatch_kid(list, kid, [&](auto k) {
+        constexpr int KID = decltype(k)::value;
+        return dispatch_dim<kid_max_dim(KID)>("kpairs", kp.D, [&](auto d) {
+            hipLaunchKernelGGL((kpairs_kernel<KID, decltype(d)::value>), dim3((unsigned)((a.M + 255) / 256)), dim3(256), 0, st, kp, a.Xi, a.Xj,
+                               a.ni, a.nj, a.M, a.out, a.accumulate, kp2);
+            GPT_LAUNCH_CHECK();
+            return GPT_OK;
+        });
+    }, [&] {
+        gpt_set_error("kpairs: unknown kernel_id %d", kid);
+        return GPT_E_ARG;
+    });
+}
+
+// the product halves of launch_kbuild / launch_kpairs (kbuild_prod.hip)
+int kbuild_prod(hipStream_t st, const KParams &kp1, const KParams &kp2, const KBuildArgs &a);
+int kpairs_prod(hipStream_t st, const KParams &kp1, const KParams &kp2, const KPairsArgs &a);
