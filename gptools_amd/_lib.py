@@ -17,7 +17,9 @@ GPT_OK = 0
 GPT_E_ARG, GPT_E_VALUE, GPT_E_NOTIMPL, GPT_E_HIP, GPT_E_NOMEM, GPT_E_STATE = -1, -2, -3, -4, -5, -6
 KERNEL_SE, KERNEL_M52, KERNEL_DIAGNOISE, KERNEL_ZERO, KERNEL_RQ, KERNEL_MATERN, KERNEL_PRODUCT = 0, 1, 2, 3, 4, 5, 6
 KERNEL_GIBBS_TANH, KERNEL_GIBBS_DTANH, KERNEL_GIBBS_CUBIC, KERNEL_GIBBS_QUINTIC, KERNEL_GIBBS_EXPGAUSS = 7, 8, 9, 10, 11
+KERNEL_GIBBS_BSPLINE = 12
 GIBBS_MAX_GAUSS = 8      # GPT_GIBBS_MAX_GAUSS: most Gaussians of KERNEL_GIBBS_EXPGAUSS
+GIBBS_MAX_KNOTS = 11     # GPT_GIBBS_MAX_KNOTS: most knots of KERNEL_GIBBS_BSPLINE
 MAX_DIM = 16
 WARP_LINEAR, WARP_BETA, WARP_MAX_LAYERS = 1, 2, 4
 

@@ -168,6 +168,32 @@ static int make_kparams(int kernel_id, const double *params, int nparams, int D,
         kp->sigma = params[0];
         kp->g_nt = eg ? (nparams - 2) / 3 : 0;
         for (int q = 1; q < nparams; q++) kp->g_raw[q - 1] = params[q];
+    } else if (kernel_id == GPT_KERNEL_GIBBS_BSPLINE) {
+        // GibbsKernel1dBSpline, cubic [sigma_f, t_1 .. t_nt, C_1 .. C_{nt+2}] (ref: gibbs.py:905-992); the ABI carries no integer
+        // besides nparams, so nt = (nparams - 3) / 2.  Knots and coefficients go to the device as they are (gibbs_lfunc.hpp)
+        if (D != 1) {
+            gpt_set_error("Gibbs kernel only supports 1d data.");
+            return GPT_E_ARG;
+        }
+        const int nt = (nparams - 3) / 2;
+        if (nparams < 3 || (nparams - 3) % 2 != 0 || nt < 2 || nt > GPT_GIBBS_MAX_KNOTS) {
+            gpt_set_error("kernel %d expects 2 nt + 3 params (cubic, 2 <= nt <= GPT_GIBBS_MAX_KNOTS = %d knots), got %d", kernel_id,
+                          GPT_GIBBS_MAX_KNOTS, nparams);
+            return GPT_E_ARG;
+        }
+        if (hyper_deriv >= 0) {
+            gpt_set_error("Hyperparameter derivatives have not been implemented!");      // ref: gibbs.py:319-322
+            return GPT_E_NOTIMPL;
+        }
+        // (ref: splines.py:54-55 compares the knots with their sorted copy, which also refuses a NaN among them)
+        for (int q = 1; q < nt; q++)
+            if (!(params[q] <= params[q + 1])) {
+                gpt_set_error("Knots must be in increasing order!");
+                return GPT_E_VALUE;
+            }
+        kp->sigma = params[0];
+        kp->g_nt = nt;
+        for (int q = 1; q < nparams; q++) kp->g_raw[q - 1] = params[q];
     } else if (kernel_id == GPT_KERNEL_DIAGNOISE || kernel_id == GPT_KERNEL_ZERO) {
         if (nparams != 1) {
             gpt_set_error("noise kernels expect 1 param, got %d", nparams);
@@ -277,6 +303,7 @@ struct ModelKernel {
     int nparams = 0;                               // doubles one parameter set takes in the ABI's flat array (all terms, both factors)
     KParams f1[GPT_MAX_TERMS] = {}, f2[GPT_MAX_TERMS] = {};      // f2[t].kernel_id < 0: term t is not a product; zero beyond nterms
     bool any_prod = false, has_m52 = false, has_chain = false, has_gibbs = false;      // over all factors of all terms
+    bool has_bspline = false;      // ... a B-spline Gibbs kernel among them: the batched launchers take the kernels with that branch
     const KParams *second(int t) const { return f2[t].kernel_id >= 0 ? &f2[t] : nullptr; }
 };
 
@@ -307,7 +334,7 @@ static int parse_model(int D, long n_maxsum, int nterms, const int *ids, const i
 {
     if (nterms < 1 || nterms > GPT_MAX_TERMS || !ids || !params || !nparams || (ids2 && !nparams1)) return GPT_E_ARG;
     m->nterms = nterms;
-    m->any_prod = m->has_m52 = m->has_chain = m->has_gibbs = false;      // (the factors beyond nterms stay as they are: never read, zero in a fresh model)
+    m->any_prod = m->has_m52 = m->has_chain = m->has_gibbs = m->has_bspline = false;      // (the factors beyond nterms stay as they are: never read, zero in a fresh model)
     const double *p = params;
     for (int t = 0; t < nterms; t++) {
         const int k1 = ids[t], k2 = (ids2 && ids2[t] >= 0) ? ids2[t] : -1;
@@ -330,6 +357,7 @@ static int parse_model(int D, long n_maxsum, int nterms, const int *ids, const i
         m->has_m52 = m->has_m52 || k1 == GPT_KERNEL_M52 || k2 == GPT_KERNEL_M52;
         m->has_chain = m->has_chain || is_chain(k1) || is_chain(k2);
         m->has_gibbs = m->has_gibbs || gibbs_kid(k1) || gibbs_kid(k2);
+        m->has_bspline = m->has_bspline || k1 == GPT_KERNEL_GIBBS_BSPLINE || k2 == GPT_KERNEL_GIBBS_BSPLINE;
         p += nparams[t];
     }
     m->nparams = (int)(p - params);

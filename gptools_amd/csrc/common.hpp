@@ -52,7 +52,7 @@ struct KParams {
             double inv_l[GPT_MAX_DIM];  // 1 / l
             double inv_var[GPT_MAX_DIM];// 1 / l^2
         };
-        // bucket and exp-Gauss Gibbs kernels (1-D, no length scales of the kind above): the parameters after sigma_f as the ABI
+        // bucket, exp-Gauss and B-spline Gibbs kernels (1-D, no length scales of the kind above): the parameters after sigma_f as the ABI
         // hands them over (gibbs_lfunc.hpp reads them raw).  In the place of the three arrays, so that sizeof(KParams) is what it
         // was: the product kernels keep both factors' KParams on the stack and pay for every byte in scratch
         double g_raw[3 * GPT_GIBBS_MAX_GAUSS + 1];
@@ -69,17 +69,18 @@ struct KParams {
     double m_g[2], m_gm[2], m_nus[2];             // Gamma(nu_s), Gamma(-nu_s), nu_s for the small-y series (nu_s = nu, or nu -+ 0.001)
     // Gibbs kernels (1-D): l(x) = g_c + sum_q g_amp[q] tanh((x - g_x0[q]) / g_w[q]) over g_nt terms (1: tanh warp, 2: double tanh)
     double g_amp[2], g_w[2], g_x0[2], g_c;
-    int g_nt, g_pad_;      // (exp-Gauss: g_nt = the number of Gaussians)
+    int g_nt, g_pad_;      // (exp-Gauss: g_nt = the number of Gaussians; B-spline: the number of knots)
 };
 
 static_assert(3 * GPT_GIBBS_MAX_GAUSS + 1 <= 3 * GPT_MAX_DIM, "g_raw must fit the arrays it shares its place with");
+static_assert(2 * GPT_GIBBS_MAX_KNOTS + 2 <= 3 * GPT_GIBBS_MAX_GAUSS + 1, "the B-spline's knots and coefficients must fit g_raw");
 static_assert(sizeof(KParams) == 656, "KParams travels by value in the kernel arguments (two per product term)");
 
-// the Gibbs kernels (1-D, derivative orders <= 1): the tanh warps, the buckets, the exponential of Gaussians
+// the Gibbs kernels (1-D, derivative orders <= 1): the tanh warps, the buckets, the exponential of Gaussians, the B-spline
 __host__ __device__ constexpr bool gibbs_kid(int kid)
 {
     return kid == GPT_KERNEL_GIBBS_TANH || kid == GPT_KERNEL_GIBBS_DTANH || kid == GPT_KERNEL_GIBBS_CUBIC ||
-           kid == GPT_KERNEL_GIBBS_QUINTIC || kid == GPT_KERNEL_GIBBS_EXPGAUSS;
+           kid == GPT_KERNEL_GIBBS_QUINTIC || kid == GPT_KERNEL_GIBBS_EXPGAUSS || kid == GPT_KERNEL_GIBBS_BSPLINE;
 }
 
 // ... those of them added after the tanh warps (kernel ids 9-11), and the builder's INTERNAL id of a product with such a factor
@@ -93,6 +94,11 @@ __host__ __device__ constexpr bool gibbs_more_kid(int kid)
     return kid == GPT_KERNEL_GIBBS_CUBIC || kid == GPT_KERNEL_GIBBS_QUINTIC || kid == GPT_KERNEL_GIBBS_EXPGAUSS;
 }
 #define GPT_KID_PRODUCT_GM 106
+// ... and a product with a B-spline factor (id 12): the spline costs registers again, in the batched kernels too, so it has an
+// instantiation of its own everywhere -- the builders' GPT_KID_PRODUCT_GB, the B-spline forms of kdiag_batch / kss_sum
+// (kbuild_batch.hip) -- which the launchers take only for a model that holds a B-spline (ModelKernel::has_bspline); GPT_KERNEL_PRODUCT,
+// GPT_KID_PRODUCT_GM and the batched kernels of every other model are the code they were
+#define GPT_KID_PRODUCT_GB 107
 
 // A cross-stream edge without an event: the kernel that completes a piece of work raises a 32-bit word in device
 // memory when its LAST workgroup is through (its results written with write-through stores and drained first) and the
@@ -212,19 +218,20 @@ int launch_trsm_panel(hipStream_t st, int64_t m, const double *L, int64_t ldl, c
 int launch_kbuild_batch(hipStream_t st, int kernel_id, int D, const KParams *d_kps, const double *d_noise_var, int64_t nbatch,
                         const double *dX, const int32_t *dn, int64_t N, const double *d_err_y, double diag_add, double *dK,
                         int64_t ldk, int64_t bstride, int accumulate = 0, int full = 0, const KParams *d_kps2 = nullptr,
-                        int64_t xstride = 0, const double *dS = nullptr, int64_t sstride = 0);
+                        int64_t xstride = 0, const double *dS = nullptr, int64_t sstride = 0, int bspline = 0);
                         // dS != NULL: a warped batch -- element z's (warped) points at dX + z * xstride, its slopes at dS + z * sstride
 int launch_batch_pad(hipStream_t st, const double *h_y, int64_t nbatch, double *A, int64_t lda, int64_t bstride, int64_t n_valid,
                      int64_t n_pad, double big, int32_t *info);
 // the predictive half of a resident batch (gpt_predict_batch)
 int launch_kbuild_batch_cross(hipStream_t st, int kernel_id, int D, const KParams *d_kps, const double *d_nv, int64_t nbatch,
                               const double *dXi, const int32_t *dni, int64_t M, const double *dXj, const int32_t *dnj, int64_t P, double *dK,
-                              int64_t ldk, int64_t bstride, int accumulate = 0, const KParams *d_kps2 = nullptr);
+                              int64_t ldk, int64_t bstride, int accumulate = 0, const KParams *d_kps2 = nullptr, int bspline = 0);
+                              // bspline (here and below): the model holds a B-spline Gibbs kernel -- the kernels with that branch
 int launch_kdiag_batch(hipStream_t st, int D, int nterms, const KParams *d_kps, const KParams *d_kps2, int64_t nbatch, const double *dX,
-                       const int32_t *dn, int64_t M, double *dout, int64_t ldo);
+                       const int32_t *dn, int64_t M, double *dout, int64_t ldo, int bspline = 0);
 int launch_kss_sum(hipStream_t st, int D, int nterms, const KParams *d_kps, const KParams *d_kps2, int64_t nbatch, const int32_t *d_keep,
                    const double *dX, const int32_t *dn, int64_t M, int64_t MP, const int32_t *d_hit, double noise_sum, double *dC,
-                   int64_t ldc);
+                   int64_t ldc, int bspline = 0);
 int launch_batch_meanvar(hipStream_t st, int64_t M, int64_t MP, int64_t N, int64_t NP, int64_t nbatch, double *V, int64_t ldv,
                          const double *A, int64_t bs, const int32_t *keep, double *mean, double *var, int64_t ld);
 int launch_batch_logdet_dot(hipStream_t st, const double *A, int64_t lda, int64_t bstride, int64_t n, int64_t nbatch,

@@ -1,5 +1,6 @@
-// gibbs_lfunc.hpp -- the closed-form length-scale functions l(x), l'(x) of the bucket and exp-Gauss Gibbs kernels
-// (GPT_KERNEL_GIBBS_CUBIC / _QUINTIC / _EXPGAUSS, include/gpt_hip.h; ref: gptools/kernel/gibbs.py:603-651, :695-760, :804-855),
+// gibbs_lfunc.hpp -- the closed-form length-scale functions l(x), l'(x) of the bucket, exp-Gauss and B-spline Gibbs kernels
+// (GPT_KERNEL_GIBBS_CUBIC / _QUINTIC / _EXPGAUSS / _BSPLINE, include/gpt_hip.h; ref: gptools/kernel/gibbs.py:603-651, :695-760,
+// :804-855, :905-992),
 // from the raw parameters after sigma_f.  The functions are __host__ __device__ and need nothing of HIP, so that the ordinary
 // host compiler can build them into a test aid (test_aids/gibbs_host.cpp) and a CPU-only test can compare them with the numpy
 // functions of gptools_amd/kernel/gibbs.py.  kpair.hpp (gibbs_point) calls them once per point, never per pair.
@@ -86,4 +87,84 @@ GPT_HD static inline void gpt_gibbs_exp_gauss(const double *p, int G, double x, 
     const double e = exp(S1);
     *l = l0 * e;
     *dl = -l0 * e * S2;
+}
+
+// B-spline length scale (GPT_KERNEL_GIBBS_BSPLINE; ref: gptools/kernel/gibbs.py:905-992 through gptools/splines.py:5-146; the
+// numpy statement is gptools_amd/splines.py).  p = [t_1 .. t_nt, C_1 .. C_{nt+2}], cubic, knots in increasing order (the parser
+// refuses anything else), 2 <= nt <= GPT_GIBBS_MAX_KNOTS.  l = sum_i C_i B_{i,3}(x) over the knots padded with three copies of
+// t_1 and t_nt; l' = sum_i (C_{i+1} - C_i) M_{i,2}(x) over the knots padded with two -- the reference's coefficient differencing.
+//
+// The reference fills the whole Cox-de Boor table, (nt + 5) x 4 entries per point.  Of those only the triangle above the span
+// that holds x is non-zero, four cubic B-splines and three quadratic M-splines, and the rest are exact zeros that it adds; so
+// the triangle alone gives its numbers, in its order of operations: each term (x - t_i) B / (t_{i+d} - t_i) as product then
+// quotient, a term whose knot difference is zero left out, the first term added before the second, the M-spline level scaled by
+// (d + 1) / (d (t_{i+d+1} - t_i)).  The span rule is the reference's: t_s <= x < t_{s+1}, the last span closed on the right;
+// an empty span (repeated knot) holds no point.  No span (x outside [t_1, t_nt]): l = l' = 0, NaN for a non-finite x (the
+// reference's 0 * x).
+//
+// How the span's operands are found: a UNIFORM loop over the at most GPT_GIBBS_MAX_KNOTS - 1 spans that keeps, under the span's
+// 0/1 mask, the six knots and four coefficients of the triangle in registers.  Every index into p is then the same in all
+// lanes (scalar loads from the kernel arguments) and nothing depends on how a compiler lowers a lane-varying index into the
+// by-value KParams of the single-matrix builders; a per-lane span search measured the same (both forms'
+// registers, scratch and times).
+GPT_HD static inline void gpt_gibbs_bspline(const double *p, int nt, double x, double *l, double *dl)
+{
+    const double *t = p, *C = p + nt;
+    const double tlast = t[nt - 1];
+    // k[m]: padded knot mu - 2 + m of the span mu that holds x, i.e. t[s - 2 + m] with the index held inside [0, nt - 1];
+    // c[r]: coefficient s + r (the B-splines mu - 3 .. mu)
+    double k[6] = {0.0, 0.0, 0.0, 0.0, 0.0, 0.0}, c[4] = {0.0, 0.0, 0.0, 0.0};
+    bool hit = false;
+#pragma unroll
+    for (int s = 0; s < GPT_GIBBS_MAX_KNOTS - 1; s++) {
+        if (s < nt - 1) {
+            const bool in = (t[s] <= x) && ((x < t[s + 1]) || ((s == nt - 2) && (x == tlast)));
+            if (in) {
+#pragma unroll
+                for (int m = 0; m < 6; m++) {
+                    const int q = s - 2 + m;
+                    k[m] = t[q < 0 ? 0 : (q > nt - 1 ? nt - 1 : q)];
+                }
+#pragma unroll
+                for (int r = 0; r < 4; r++) c[r] = C[s + r];
+                hit = true;
+            }
+        }
+    }
+    if (!hit) {
+        *l = *dl = x - x;
+        return;
+    }
+    // level d holds the functions mu - d .. mu as N[0 .. d]; function mu - d + r needs, of the padded knots, i -> k[2 - d + r],
+    // i + d -> k[2 + r], i + d + 1 -> k[3 + r], i + 1 -> k[3 - d + r]
+    double N[4] = {1.0, 0.0, 0.0, 0.0}, M[3] = {1.0 / (k[3] - k[2]), 0.0, 0.0};
+#pragma unroll
+    for (int d = 1; d <= 3; d++) {
+        double Nn[4] = {0.0, 0.0, 0.0, 0.0}, Mn[3] = {0.0, 0.0, 0.0};
+#pragma unroll
+        for (int r = 0; r <= d; r++) {
+            double v = 0.0, w = 0.0;
+            if (r >= 1 && k[2 + r] != k[2 - d + r]) {
+                v += ((x - k[2 - d + r]) * N[r - 1]) / (k[2 + r] - k[2 - d + r]);
+                if (d <= 2) w += (x - k[2 - d + r]) * M[r - 1];
+            }
+            if (r <= d - 1 && k[3 + r] != k[3 - d + r]) {
+                v += ((k[3 + r] - x) * N[r]) / (k[3 + r] - k[3 - d + r]);
+                if (d <= 2) w += (k[3 + r] - x) * M[r];
+            }
+            Nn[r] = v;
+            if (d <= 2) {
+                if (k[3 + r] != k[2 - d + r]) w *= (double)(d + 1) / ((double)d * (k[3 + r] - k[2 - d + r]));
+                Mn[r] = w;
+            }
+        }
+#pragma unroll
+        for (int r = 0; r <= d; r++) N[r] = Nn[r];
+        if (d <= 2) {
+#pragma unroll
+            for (int r = 0; r <= d; r++) M[r] = Mn[r];
+        }
+    }
+    *l = ((N[0] * c[0] + N[1] * c[1]) + N[2] * c[2]) + N[3] * c[3];
+    *dl = (M[0] * (c[1] - c[0]) + M[1] * (c[2] - c[1])) + M[2] * (c[3] - c[2]);
 }

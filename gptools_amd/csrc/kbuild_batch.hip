@@ -10,14 +10,15 @@
 
 // One term of every element: kernel_id, or (d_kps2 != NULL) a product term, whose factors' ids the kernel reads from the elements'
 // KParams at run time.  `who` names the launcher in a refusal.
-static int kbuild_batch_dispatch(const char *who, hipStream_t st, int kernel_id, int D, const KBuildArgs &a, const KBatchArgs &b)
+// bspline: the model holds a B-spline Gibbs kernel (ModelKernel::has_bspline) -- a product term then takes GPT_KID_PRODUCT_GB.
+static int kbuild_batch_dispatch(const char *who, hipStream_t st, int kernel_id, int D, const KBuildArgs &a, const KBatchArgs &b, int bspline)
 {
     const KParams dummy = KParams();
     auto for_kid = [&](auto k) {
         constexpr int KID = decltype(k)::value;
         return dispatch_dim<kid_max_dim(KID)>(who, D, [&](auto d) { return kbuild_launch<KID, decltype(d)::value, true>(st, dummy, dummy, a, b); });
     };
-    if (b.kps2 != nullptr) return dispatch_kid(ProductKids(), product_kid(D, -1, -1, true), for_kid, [] { return GPT_E_ARG; });
+    if (b.kps2 != nullptr) return dispatch_kid(ProductKids(), product_kid(D, bspline ? GPT_KERNEL_GIBBS_BSPLINE : -1, -1, true), for_kid, [] { return GPT_E_ARG; });
     return dispatch_kid(FitKids(), kernel_id, for_kid, [&] {
         gpt_set_error("%s: kernel_id %d is not a fit kernel", who, kernel_id);
         return GPT_E_ARG;
@@ -30,12 +31,12 @@ static int kbuild_batch_dispatch(const char *who, hipStream_t st, int kernel_id,
 int launch_kbuild_batch(hipStream_t st, int kernel_id, int D, const KParams *d_kps, const double *d_noise_var, int64_t nbatch,
                         const double *dX, const int32_t *dn, int64_t N, const double *d_err_y, double diag_add, double *dK,
                         int64_t ldk, int64_t bstride, int accumulate, int full, const KParams *d_kps2, int64_t xstride,
-                        const double *dS, int64_t sstride)
+                        const double *dS, int64_t sstride, int bspline)
 {
     if (N <= 0 || nbatch <= 0) return GPT_OK;
     const KBuildArgs a = {dX, dn, N, dX, dn, N, full ? 0 : 1, 0, 0, d_err_y, 0.0, diag_add, dK, ldk, accumulate, dS, dS};
     const KBatchArgs b = {d_kps, d_noise_var, nbatch, bstride, d_kps2, xstride, sstride};
-    return kbuild_batch_dispatch("kbuild_batch", st, kernel_id, D, a, b);
+    return kbuild_batch_dispatch("kbuild_batch", st, kernel_id, D, a, b, bspline);
 }
 
 // ---- the predictive half of a resident batch (gpt_predict_batch, api_batch.inc) ----------------------------------------
@@ -45,7 +46,7 @@ int launch_kbuild_batch(hipStream_t st, int kernel_id, int D, const KParams *d_k
 // (d_nv: the elements' noise variances -- the batched kernel reads its element's entry, though without err_y nothing uses it)
 int launch_kbuild_batch_cross(hipStream_t st, int kernel_id, int D, const KParams *d_kps, const double *d_nv, int64_t nbatch,
                               const double *dXi, const int32_t *dni, int64_t M, const double *dXj, const int32_t *dnj, int64_t P, double *dK,
-                              int64_t ldk, int64_t bstride, int accumulate, const KParams *d_kps2)
+                              int64_t ldk, int64_t bstride, int accumulate, const KParams *d_kps2, int bspline)
 {
     if (M <= 0 || P <= 0 || nbatch <= 0) return GPT_OK;
     if (!d_kps || !d_nv) {
@@ -54,22 +55,25 @@ int launch_kbuild_batch_cross(hipStream_t st, int kernel_id, int D, const KParam
     }
     const KBuildArgs a = {dXi, dni, M, dXj, dnj, P, 0, 0, 0, nullptr, 0.0, 0.0, dK, ldk, accumulate};
     const KBatchArgs b = {d_kps, d_nv, nbatch, bstride, d_kps2};
-    return kbuild_batch_dispatch("kbuild_batch_cross", st, kernel_id, D, a, b);
+    return kbuild_batch_dispatch("kbuild_batch_cross", st, kernel_id, D, a, b, bspline);
 }
 
 // One term of element b's kernel at a pair, kernels chosen at run time (the two kernels below loop over terms AND elements,
 // whose ids only the KParams carry): the same pair functions as the builder, so the same numbers.
-template <int D>
+// GB: with the B-spline branch (GPT_KID_PRODUCT_GB's form; 1-D models that hold a B-spline kernel only)
+template <int D, bool GB = false>
 __device__ __forceinline__ double batch_term_pair(const KParams *__restrict__ kps, const KParams *__restrict__ kps2, int64_t idx,
                                                   const double *xi, const double *xj, const int *ni, const int *nj)
 {
     // (D == 1: with the bucket / exp-Gauss Gibbs branches, GPT_KID_PRODUCT_GM's form; otherwise the functions the builders share)
-    if (kps2 != nullptr && kps2[idx].kernel_id >= 0) return prod_pair<D, D == 1>(kps[idx], kps2[idx], xi, xj, ni, nj);
-    return factor_pair<D, D == 1>(kps[idx], xi, xj, ni, nj);
+    if (kps2 != nullptr && kps2[idx].kernel_id >= 0) return prod_pair<D, D == 1, GB>(kps[idx], kps2[idx], xi, xj, ni, nj);
+    return factor_pair<D, D == 1, GB>(kps[idx], xi, xj, ni, nj);
 }
 
 // diag K**_b: out[b * ldo + a] = k_b((x_a, n_a), (x_a, n_a)), terms summed in order (as gpt_predict's pair launches do)
-template <int D>
+// (GB, here and in kss_sum_kernel: the form for a 1-D model that holds a B-spline kernel; a flag of the kernel itself, not a shared
+// body behind two kernels -- through a wrapper the pointers lose __restrict__ and the code of every num_dim changes)
+template <int D, bool GB = false>
 __global__ __launch_bounds__(256) void kdiag_batch_kernel(int nterms, const KParams *__restrict__ kps, const KParams *__restrict__ kps2,
                                                           int64_t nbatch, const double *__restrict__ X, const int32_t *__restrict__ n,
                                                           int64_t M, double *__restrict__ out, int64_t ldo)
@@ -85,7 +89,7 @@ __global__ __launch_bounds__(256) void kdiag_batch_kernel(int nterms, const KPar
     }
     double v = 0.0;
     for (int t = 0; t < nterms; t++) {
-        const double p = batch_term_pair<D>(kps, kps2, (int64_t)t * nbatch + b, x, x, na, na);
+        const double p = batch_term_pair<D, GB>(kps, kps2, (int64_t)t * nbatch + b, x, x, na, na);
         v = t > 0 ? v + p : p;
     }
     out[b * ldo + a] = v;
@@ -93,7 +97,7 @@ __global__ __launch_bounds__(256) void kdiag_batch_kernel(int nterms, const KPar
 
 // Lower triangle of  C = sum over kept elements b of K**_b  (+ noise_sum on the diagonal of the rows hit[a] != 0): ONE pass over
 // the M x M triangle with the elements' KParams looped inside, 16 x 16 entries per workgroup; rows / columns in [M, MP) get 0.
-template <int D>
+template <int D, bool GB = false>
 __global__ __launch_bounds__(256) void kss_sum_kernel(int nterms, const KParams *__restrict__ kps, const KParams *__restrict__ kps2,
                                                       int64_t nbatch, const int32_t *__restrict__ keep, const double *__restrict__ X,
                                                       const int32_t *__restrict__ n, int64_t M, int64_t MP, const int32_t *__restrict__ hit,
@@ -117,7 +121,7 @@ __global__ __launch_bounds__(256) void kss_sum_kernel(int nterms, const KParams 
             if (!keep[b]) continue;
             double kb = 0.0;
             for (int t = 0; t < nterms; t++) {
-                const double p = batch_term_pair<D>(kps, kps2, (int64_t)t * nbatch + b, xa, xc, na, nc);
+                const double p = batch_term_pair<D, GB>(kps, kps2, (int64_t)t * nbatch + b, xa, xc, na, nc);
                 kb = t > 0 ? kb + p : p;
             }
             v += kb;
@@ -127,12 +131,19 @@ __global__ __launch_bounds__(256) void kss_sum_kernel(int nterms, const KParams 
     C[a * ldc + cc] = v;
 }
 
+// bspline: the model holds a B-spline Gibbs kernel (1-D by the parser's rule): the kernel with that branch
 int launch_kdiag_batch(hipStream_t st, int D, int nterms, const KParams *d_kps, const KParams *d_kps2, int64_t nbatch, const double *dX,
-                       const int32_t *dn, int64_t M, double *dout, int64_t ldo)
+                       const int32_t *dn, int64_t M, double *dout, int64_t ldo, int bspline)
 {
     if (M <= 0 || nbatch <= 0) return GPT_OK;
+    if (bspline && D == 1) {
+        hipLaunchKernelGGL((kdiag_batch_kernel<1, true>), dim3((unsigned)((M + 255) / 256), (unsigned)nbatch), dim3(256), 0, st, nterms, d_kps,
+                           d_kps2, nbatch, dX, dn, M, dout, ldo);
+        GPT_LAUNCH_CHECK();
+        return GPT_OK;
+    }
     return dispatch_dim<GPT_MAX_DIM>("kdiag_batch", D, [&](auto d) {
-        hipLaunchKernelGGL(kdiag_batch_kernel<decltype(d)::value>, dim3((unsigned)((M + 255) / 256), (unsigned)nbatch), dim3(256), 0, st,
+        hipLaunchKernelGGL((kdiag_batch_kernel<decltype(d)::value, false>), dim3((unsigned)((M + 255) / 256), (unsigned)nbatch), dim3(256), 0, st,
                            nterms, d_kps, d_kps2, nbatch, dX, dn, M, dout, ldo);
         GPT_LAUNCH_CHECK();
         return GPT_OK;
@@ -141,12 +152,18 @@ int launch_kdiag_batch(hipStream_t st, int D, int nterms, const KParams *d_kps, 
 
 int launch_kss_sum(hipStream_t st, int D, int nterms, const KParams *d_kps, const KParams *d_kps2, int64_t nbatch, const int32_t *d_keep,
                    const double *dX, const int32_t *dn, int64_t M, int64_t MP, const int32_t *d_hit, double noise_sum, double *dC,
-                   int64_t ldc)
+                   int64_t ldc, int bspline)
 {
     if (MP <= 0) return GPT_OK;
     const unsigned nt = (unsigned)((MP + 15) / 16);
+    if (bspline && D == 1) {
+        hipLaunchKernelGGL((kss_sum_kernel<1, true>), dim3(nt, nt), dim3(256), 0, st, nterms, d_kps, d_kps2, nbatch, d_keep, dX, dn, M, MP,
+                           d_hit, noise_sum, dC, ldc);
+        GPT_LAUNCH_CHECK();
+        return GPT_OK;
+    }
     return dispatch_dim<GPT_MAX_DIM>("kss_sum", D, [&](auto d) {
-        hipLaunchKernelGGL(kss_sum_kernel<decltype(d)::value>, dim3(nt, nt), dim3(256), 0, st, nterms, d_kps, d_kps2, nbatch, d_keep, dX, dn,
+        hipLaunchKernelGGL((kss_sum_kernel<decltype(d)::value, false>), dim3(nt, nt), dim3(256), 0, st, nterms, d_kps, d_kps2, nbatch, d_keep, dX, dn,
                            M, MP, d_hit, noise_sum, dC, ldc);
         GPT_LAUNCH_CHECK();
         return GPT_OK;

@@ -123,9 +123,10 @@ __global__ __launch_bounds__(KB_THREADS) void kbuild_kernel(
             const double xi = Xi[i];
             const int nir = ni[i];
             const double a = readlane_f64(rp.l, q), ra = readlane_f64(rp.r2, q);
-            const double A = readlane_f64(rp.A, q), ha = readlane_f64(rp.h, q);
+            const double A = readlane_f64(rp.A, q), ha = gibbs_h_other<KID>(readlane_f64(rp.h, q), cp.l);
             const double rb = gibbs_col_root(a, cp.rp, cp.rn);
-            double v = gibbs_core(s2, xi, a, A, ha, ra, xj[0][0], cp.l, cp.A, cp.h, rb, nir, njr[0][0], col_d || nir != 0);
+            double v = gibbs_core(s2, xi, a, A, ha, ra, xj[0][0], cp.l, cp.A, gibbs_h_other<KID>(cp.h, a), rb, nir, njr[0][0],
+                                  col_d || nir != 0);
             if constexpr (WARP) v *= Si[i] * sj[0];
             if (accumulate && jfirst < P) v += K[i * ldk + jfirst];
             if (err_y != nullptr && (i + i0 == jfirst + j0)) {
@@ -182,6 +183,7 @@ __global__ __launch_bounds__(KB_THREADS) void kbuild_kernel(
         for (int c = 0; c < KB_CPT; c++) {
             if constexpr (KID == GPT_KERNEL_PRODUCT) v[c] = prod_pair<D>(kp, kp_two, xi, xj[c], nir, njr[c]);
             else if constexpr (KID == GPT_KID_PRODUCT_GM) v[c] = prod_pair<D, true>(kp, kp_two, xi, xj[c], nir, njr[c]);
+            else if constexpr (KID == GPT_KID_PRODUCT_GB) v[c] = prod_pair<D, true, true>(kp, kp_two, xi, xj[c], nir, njr[c]);
             else v[c] = any_pair<KID, D>(kp, xi, xj[c], nir, njr[c]);
             if constexpr (WARP) v[c] *= Si[i] * sj[c];
             // SumKernel (ref: gptools/kernel/core.py:549-584): later terms add to what the earlier passes stored
@@ -229,6 +231,7 @@ __global__ __launch_bounds__(256) void kpairs_kernel(KParams kp, const double *_
     double v;
     if constexpr (KID == GPT_KERNEL_PRODUCT) v = prod_pair<D>(kp, kp_two, xi, xj, nir, njr);
     else if constexpr (KID == GPT_KID_PRODUCT_GM) v = prod_pair<D, true>(kp, kp_two, xi, xj, nir, njr);
+    else if constexpr (KID == GPT_KID_PRODUCT_GB) v = prod_pair<D, true, true>(kp, kp_two, xi, xj, nir, njr);
     else v = any_pair<KID, D>(kp, xi, xj, nir, njr);
     out[m] = accumulate ? out[m] + v : v;
 }
@@ -248,22 +251,24 @@ struct KidList {
 };
 // the kernels a model term can be (native_fit_kernel, api_kparams.inc): what the batched builders take
 using FitKids = KidList<GPT_KERNEL_SE, GPT_KERNEL_M52, GPT_KERNEL_RQ, GPT_KERNEL_MATERN, GPT_KERNEL_GIBBS_TANH, GPT_KERNEL_GIBBS_DTANH,
-                        GPT_KERNEL_GIBBS_CUBIC, GPT_KERNEL_GIBBS_QUINTIC, GPT_KERNEL_GIBBS_EXPGAUSS>;
+                        GPT_KERNEL_GIBBS_CUBIC, GPT_KERNEL_GIBBS_QUINTIC, GPT_KERNEL_GIBBS_EXPGAUSS, GPT_KERNEL_GIBBS_BSPLINE>;
 // ... and the noise kernels: the single-matrix builder and the pair list
 using AllKids = FitKids::plus<GPT_KERNEL_DIAGNOISE, GPT_KERNEL_ZERO>;
-// the builders' two product instantiations (product_kid chooses)
-using ProductKids = KidList<GPT_KERNEL_PRODUCT, GPT_KID_PRODUCT_GM>;
+// the builders' product instantiations (product_kid chooses)
+using ProductKids = KidList<GPT_KERNEL_PRODUCT, GPT_KID_PRODUCT_GM, GPT_KID_PRODUCT_GB>;
 
 // The product of the factors id1 * id2 at num_dim D: GPT_KID_PRODUCT_GM carries the bucket / exp-Gauss Gibbs branches and exists
 // at num_dim 1 only.  The single-matrix kernels take it only when a factor needs those branches (GPT_KERNEL_PRODUCT at num_dim 1
 // stays the code it was, for the products of the older kernels); the batched ones, whose factor ids only the device sees, take it
-// for every 1-D product.  Why: common.hpp, at GPT_KID_PRODUCT_GM.
+// for every 1-D product.  GPT_KID_PRODUCT_GB adds the B-spline branch and is taken, single-matrix or batched, only when a factor
+// is a B-spline (batched: the caller says so, `id1` = GPT_KERNEL_GIBBS_BSPLINE).  Why: common.hpp, at GPT_KID_PRODUCT_GM.
 inline int product_kid(int D, int id1, int id2, bool batched)
 {
+    if (D == 1 && (id1 == GPT_KERNEL_GIBBS_BSPLINE || id2 == GPT_KERNEL_GIBBS_BSPLINE)) return GPT_KID_PRODUCT_GB;
     return D == 1 && (batched || gibbs_more_kid(id1) || gibbs_more_kid(id2)) ? GPT_KID_PRODUCT_GM : GPT_KERNEL_PRODUCT;
 }
 
-constexpr int kid_max_dim(int kid) { return gibbs_kid(kid) || kid == GPT_KID_PRODUCT_GM ? 1 : GPT_MAX_DIM; }
+constexpr int kid_max_dim(int kid) { return gibbs_kid(kid) || kid == GPT_KID_PRODUCT_GM || kid == GPT_KID_PRODUCT_GB ? 1 : GPT_MAX_DIM; }
 // (the WARP instantiations exist for these only: the noise kernels are never warped)
 constexpr bool kid_can_warp(int kid) { return kid != GPT_KERNEL_DIAGNOISE && kid != GPT_KERNEL_ZERO; }
 

@@ -621,7 +621,7 @@ __device__ __forceinline__ GibbsPt gibbs_pt(double l, double dl)
 // instantiations are the code they were), -1 where only kp carries it (product factors, the batched pair kernels: per pair,
 // as for the tanh warps there).  The tanh warps: l(x) = c + sum_q amp_q tanh((x - x0_q) / w_q) and l'(x) = sum_q amp_q / w_q
 // cosh((x - x0_q) / w_q)^-2 in the reference's order of operations (gibbs.py:459-464, :552-556); cosh overflows to inf beyond
-// |u| = 710 and the slope is then 0, as there.  The buckets and the exponential of Gaussians: gibbs_lfunc.hpp.
+// |u| = 710 and the slope is then 0, as there.  The buckets, the exponential of Gaussians and the B-spline: gibbs_lfunc.hpp.
 template <int KID = -1>
 __device__ __forceinline__ GibbsPt gibbs_point(const KParams &kp, double x)
 {
@@ -637,6 +637,10 @@ __device__ __forceinline__ GibbsPt gibbs_point(const KParams &kp, double x)
     }
     if (kid == GPT_KERNEL_GIBBS_EXPGAUSS) {
         gpt_gibbs_exp_gauss(kp.g_raw, kp.g_nt, x, &l, &dl);
+        return gibbs_pt(l, dl);
+    }
+    if (kid == GPT_KERNEL_GIBBS_BSPLINE) {
+        gpt_gibbs_bspline(kp.g_raw, kp.g_nt, x, &l, &dl);
         return gibbs_pt(l, dl);
     }
     for (int q = 0; q < kp.g_nt; q++) {
@@ -679,12 +683,33 @@ __device__ __forceinline__ double gibbs_core(double s2, double xi, double a, dou
     return v;
 }
 
+// A length scale of exactly zero.  The reference divides every derivative class by sqrt(2 l(x_i) l(x_j)) (gibbs.py:358, :371,
+// :415): with l = 0 at EITHER point the three of them are 0/0 = NaN, the value class 0.  Above, the class that differentiates at
+// the OTHER point is k Q (k P) = 0 * finite = 0.  The B-spline is the one length scale that is zero over whole intervals -- outside
+// its knots, where l' = 0 too -- so its instantiations hand over the other point's h = l'/(2l) as NaN when this point's l is
+// zero: P, Q and with them every derivative class are NaN, the value class does not read h.  (KID fixed by the caller; the other
+// kernels reach l = 0 at single points at most and are the code they were.)
+template <int KID>
+__device__ __forceinline__ double gibbs_h_other(double h, double l_this)
+{
+    if constexpr (KID == GPT_KERNEL_GIBBS_BSPLINE) return (l_this == 0.0) ? (double)NAN : h;
+    return h;
+}
+
 template <int KID = -1>
 __device__ __forceinline__ double gibbs_pair(const KParams &kp, const double *xi, const double *xj, const int *ni, const int *nj)
 {
     const GibbsPt p = gibbs_point<KID>(kp, xi[0]), q = gibbs_point<KID>(kp, xj[0]);
-    return gibbs_core(kp.sigma * kp.sigma, xi[0], p.l, p.A, p.h, p.r2, xj[0], q.l, q.A, q.h, gibbs_col_root(p.l, q.rp, q.rn),
-                      ni[0], nj[0], (ni[0] | nj[0]) != 0);
+    return gibbs_core(kp.sigma * kp.sigma, xi[0], p.l, p.A, gibbs_h_other<KID>(p.h, q.l), p.r2, xj[0], q.l, q.A,
+                      gibbs_h_other<KID>(q.h, p.l), gibbs_col_root(p.l, q.rp, q.rn), ni[0], nj[0], (ni[0] | nj[0]) != 0);
+}
+
+// The B-spline kernel as a product factor (run-time ids: the GB product kernels, the B-spline forms of kdiag_batch / kss_sum):
+// OUT OF LINE.  Inlined, its two spline evaluations per factor evaluation (some forty divisions) take the kernel to 256 VGPRs and
+// twice the scratch; as a call the caller keeps the registers of the kernel without it.
+static __device__ __noinline__ double gibbs_pair_bspline(const KParams *kp, double xi, double xj, int ni, int nj)
+{
+    return gibbs_pair<GPT_KERNEL_GIBBS_BSPLINE>(*kp, &xi, &xj, &ni, &nj);
 }
 
 template <int KID, int D>
@@ -704,10 +729,17 @@ __device__ __forceinline__ double any_pair(const KParams &kp, const double *xi, 
 // The reference walks the power set of the derivative multiset of a pair and multiplies k1 with the subset's orders by k2
 // with the complement's; equal subsets recur, so grouped by how many of the r_s derivatives of slot s (the D orders of ni, then
 // the D of nj) go to k1 that is the general Leibniz rule  sum_a prod_s C(r_s, a_s) k1^(a) k2^(r - a).  Factors by run-time id.
-// GM: the bucket / exp-Gauss Gibbs ids are compiled in (GPT_KID_PRODUCT_GM, common.hpp; 1-D only)
-template <int D, bool GM = false>
+// GM: the bucket / exp-Gauss Gibbs ids are compiled in (GPT_KID_PRODUCT_GM, common.hpp; 1-D only); GB: the B-spline id as well
+// (GPT_KID_PRODUCT_GB: only the kernels the launchers choose for a model WITH a B-spline factor; every other instantiation is
+// the code it was)
+template <int D, bool GM = false, bool GB = false>
 __device__ __forceinline__ double factor_pair(const KParams &kp, const double *xi, const double *xj, const int *ni, const int *nj)
 {
+    // (in front of the switch, not a case of it: without GB the switch is the parent's, jump table and all; with its id: the
+    // zero-length-scale rule, gibbs_h_other)
+    if constexpr (GB && D == 1) {
+        if (kp.kernel_id == GPT_KERNEL_GIBBS_BSPLINE) return gibbs_pair_bspline(&kp, xi[0], xj[0], ni[0], nj[0]);
+    }
     switch (kp.kernel_id) {
     case GPT_KERNEL_SE: return se_pair<D>(kp, xi, xj, ni, nj);
     case GPT_KERNEL_M52: return m52_pair<D>(kp, xi, xj, ni, nj);
@@ -724,7 +756,7 @@ __device__ __forceinline__ double factor_pair(const KParams &kp, const double *x
     }
 }
 
-template <int D, bool GM = false>
+template <int D, bool GM = false, bool GB = false>
 __device__ double prod_pair(const KParams &k1, const KParams &k2, const double *xi, const double *xj, const int *ni, const int *nj)
 {
     int r[2 * D], a[2 * D];
@@ -751,7 +783,7 @@ __device__ double prod_pair(const KParams &k1, const KParams &k2, const double *
                 n2j[s - D] = r[s] - a[s];
             }
         }
-        sum += w * (factor_pair<D, GM>(k1, xi, xj, n1i, n1j) * factor_pair<D, GM>(k2, xi, xj, n2i, n2j));
+        sum += w * (factor_pair<D, GM, GB>(k1, xi, xj, n1i, n1j) * factor_pair<D, GM, GB>(k2, xi, xj, n2i, n2j));
         int s = 0;
         while (s < 2 * D) {
             if (a[s] < r[s]) {

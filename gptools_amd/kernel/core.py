@@ -165,7 +165,8 @@ class ProductKernel(BinaryKernel):
         from .. import _lib
         from .matern import Matern52Kernel
         ok = (_lib.KERNEL_SE, _lib.KERNEL_M52, _lib.KERNEL_RQ, _lib.KERNEL_MATERN, _lib.KERNEL_GIBBS_TANH,
-              _lib.KERNEL_GIBBS_DTANH, _lib.KERNEL_GIBBS_CUBIC, _lib.KERNEL_GIBBS_QUINTIC, _lib.KERNEL_GIBBS_EXPGAUSS)
+              _lib.KERNEL_GIBBS_DTANH, _lib.KERNEL_GIBBS_CUBIC, _lib.KERNEL_GIBBS_QUINTIC, _lib.KERNEL_GIBBS_EXPGAUSS,
+              _lib.KERNEL_GIBBS_BSPLINE)
         f = []
         for k in (self.k1, self.k2):
             kid = getattr(k, "_gpt_kernel_id", None)

@@ -2,7 +2,7 @@ r"""Gibbs non-stationary squared-exponential kernels in one dimension.
 
 ref: gptools/kernel/gibbs.py:229-424 (GibbsKernel1d), :426-466 (tanh_warp, GibbsKernel1dTanh), :508-558 (double_tanh_warp,
 GibbsKernel1dDoubleTanh), :603-801 (cubic_bucket_warp, quintic_bucket_warp and their kernels), :804-902 (exp_gauss_warp,
-GibbsKernel1dExpGauss).  With a point-dependent length scale ``l(x)``, ``a = l(x_i)``, ``b = l(x_j)``, ``s = a^2 + b^2``
+GibbsKernel1dExpGauss), :905-992 (BSplineWarp, GibbsKernel1dBSpline).  With a point-dependent length scale ``l(x)``, ``a = l(x_i)``, ``b = l(x_j)``, ``s = a^2 + b^2``
 and ``d = x_i - x_j``:
 
 .. math::  k = \sigma_f^2 \sqrt{2ab/s}\, \exp(-d^2/s).
@@ -17,10 +17,11 @@ The reference hard-codes the derivative classes as expanded polynomials (terms u
 
 ``GibbsKernel1d(l_func)`` evaluates that on the host in numpy for any warp (the Python-kernel route of
 ``GaussianProcess``: pair list, then ``fit_matrix`` on the GPU).  ``GibbsKernel1dTanh``, ``GibbsKernel1dDoubleTanh``,
-``GibbsKernel1dCubicBucket``, ``GibbsKernel1dQuinticBucket`` and ``GibbsKernel1dExpGauss`` are native: the HIP library evaluates
-them (``GPT_KERNEL_GIBBS_*``, gptools_amd/csrc/kpair.hpp and gibbs_lfunc.hpp) with the length-scale functions hoisted out of
-the builder's pair loop.  A subclass that overrides ``__call__`` is a Python kernel again; so is a ``GibbsKernel1dExpGauss``
-with more Gaussians than the device kernel carries (``_lib.GIBBS_MAX_GAUSS``).
+``GibbsKernel1dCubicBucket``, ``GibbsKernel1dQuinticBucket``, ``GibbsKernel1dExpGauss`` and the cubic ``GibbsKernel1dBSpline``
+are native: the HIP library evaluates them (``GPT_KERNEL_GIBBS_*``, gptools_amd/csrc/kpair.hpp and gibbs_lfunc.hpp) with the
+length-scale functions hoisted out of the builder's pair loop.  A subclass that overrides ``__call__`` is a Python kernel again;
+so is a ``GibbsKernel1dExpGauss`` with more Gaussians than the device kernel carries (``_lib.GIBBS_MAX_GAUSS``) and a
+``GibbsKernel1dBSpline`` of another degree than 3 or with more knots than ``_lib.GIBBS_MAX_KNOTS``.
 Derivative orders above ``[1, 1]`` and hyperparameter derivatives raise ``NotImplementedError`` like the reference.
 """
 import inspect
@@ -29,15 +30,17 @@ import numpy as np
 
 from .core import Kernel
 from .. import _lib
+from ..splines import spev
 
 __all__ = ["GibbsKernel1d", "GibbsKernel1dTanh", "GibbsKernel1dDoubleTanh", "GibbsKernel1dCubicBucket",
-           "GibbsKernel1dQuinticBucket", "GibbsKernel1dExpGauss", "tanh_warp", "double_tanh_warp", "cubic_bucket_warp",
-           "quintic_bucket_warp", "exp_gauss_warp"]
+           "GibbsKernel1dQuinticBucket", "GibbsKernel1dExpGauss", "BSplineWarp", "GibbsKernel1dBSpline", "tanh_warp",
+           "double_tanh_warp", "cubic_bucket_warp", "quintic_bucket_warp", "exp_gauss_warp"]
 
 
-def gibbs_1d(x, y, ni, nj, lx, ly, lx1, ly1):
+def gibbs_1d(x, y, ni, nj, lx, ly, lx1, ly1, zero_nan=False):
     """``k / sigma_f^2`` of the pairs ``(x[m], y[m])`` with orders ``ni[m], nj[m]`` in {0, 1}, from the warp values ``l``
-    and slopes ``l'`` at both points."""
+    and slopes ``l'`` at both points.  ``zero_nan``: a length scale of exactly zero at either point makes every derivative
+    class NaN (the B-spline warp, which is zero over whole intervals)."""
     with np.errstate(all="ignore"):
         d = x - y
         s = lx * lx + ly * ly
@@ -49,6 +52,11 @@ def gibbs_1d(x, y, ni, nj, lx, ly, lx1, ly1):
         Q = ly1 / (2.0 * ly) - B * u + 2.0 * d * u + 2.0 * d * d * B * u * u
         R = 2.0 * A * B * u * u + 2.0 * u + 4.0 * d * B * u * u - 4.0 * d * A * u * u - 8.0 * d * d * A * B * u * u * u
         out = np.where(ni == 1, np.where(nj == 1, k * (P * Q + R), k * P), np.where(nj == 1, k * Q, k))
+        if zero_nan:
+            # a length scale of exactly zero at either point: the reference divides its derivative classes by sqrt(2 l l') -> 0/0
+            # (gibbs.py:358, :371, :415); k Q above is 0 * finite where only the OTHER point's l is zero.  Applied for the
+            # B-spline warp alone, as on the device (kpair.hpp, gibbs_h_other): the other warps keep the numbers they had
+            out = np.where(((ni == 1) | (nj == 1)) & ((lx == 0.0) | (ly == 0.0)), np.nan, out)
     return out
 
 
@@ -86,7 +94,8 @@ class GibbsKernel1d(Kernel):
         with np.errstate(all="ignore"):
             lx, ly = self.l_func(x, 0, *p), self.l_func(y, 0, *p)
             lx1, ly1 = self.l_func(x, 1, *p), self.l_func(y, 1, *p)
-        return self.params[0] ** 2 * gibbs_1d(x, y, ni[:, 0], nj[:, 0], lx, ly, lx1, ly1)
+        return self.params[0] ** 2 * gibbs_1d(x, y, ni[:, 0], nj[:, 0], lx, ly, lx1, ly1,
+                                              zero_nan=isinstance(self.l_func, BSplineWarp))
 
 
 def tanh_warp(x, n, l1, l2, lw, x0):
@@ -266,4 +275,54 @@ class GibbsKernel1dExpGauss(GibbsKernel1d):
 
 class _GibbsKernel1dExpGaussHost(GibbsKernel1dExpGauss):
     """``GibbsKernel1dExpGauss`` beyond the device kernel's cap: evaluated on the host."""
+    __call__ = GibbsKernel1d.__call__
+
+
+class BSplineWarp(object):
+    r"""Length-scale function that is a B-spline of fixed degree ``k`` (default 3) with free knots and coefficients
+    (ref: gibbs.py:905-941).  ``warp(X, n, t_1 .. t_nt, C_1 .. C_{nt+k-1})`` is the spline (``n = 0``) or its ``n``-th
+    derivative at ``X`` (the first column of a 2-D ``X``), in the shape of ``X``; ``nt = (len(tC) - k + 1) // 2``.  Outside
+    ``[t_1, t_nt]`` the spline, and with it the length scale, is zero: keep the boundary knots at or beyond the data."""
+
+    def __init__(self, k=3):
+        self.k = k
+
+    def __call__(self, X, n, *tC):
+        X = np.asarray(X, dtype=float)
+        shape = X.shape
+        if X.ndim == 2:
+            X = X[:, 0]
+        tC = np.asarray(tC, dtype=float)
+        nt = (len(tC) - self.k + 1) // 2
+        return np.reshape(spev(tC[:nt], tC[nt:], self.k, X, n=n), shape)
+
+
+class GibbsKernel1dBSpline(GibbsKernel1d):
+    r"""Gibbs kernel whose length scale is a B-spline of degree ``k`` on ``nt`` free knots.  Parameters
+    ``[sigma_f, t_1 .. t_nt, C_1 .. C_{nt+k-1}]`` (ref: gibbs.py:944-992).  Put the two outer knots at or beyond the edges of
+    the data (the length scale is zero outside them) and keep the coefficients positive (the spline lies in their hull).
+    Knots out of increasing order raise ``ValueError("Knots must be in increasing order!")`` at evaluation.
+
+    The cubic kernel with ``2 <= nt <= _lib.GIBBS_MAX_KNOTS`` is evaluated on the GPU.  For another degree or knot count the
+    constructor returns an instance of a subclass whose ``__call__`` is the host ``GibbsKernel1d``'s -- a Python kernel, with
+    the same numbers.  As for :class:`GibbsKernel1dExpGauss` that switch is made for this class only: a user subclass that keeps
+    the native ``__call__`` stays native and gets the library's ``ValueError`` beyond the cap."""
+    _gpt_kernel_id = _lib.KERNEL_GIBBS_BSPLINE
+    __call__ = Kernel.__call__
+
+    def __new__(cls, nt=None, k=3, **kwargs):
+        if cls is GibbsKernel1dBSpline and nt is not None and (k != 3 or not 2 <= nt <= _lib.GIBBS_MAX_KNOTS):
+            cls = _GibbsKernel1dBSplineHost
+        return super(GibbsKernel1dBSpline, cls).__new__(cls)
+
+    def __init__(self, nt, k=3, **kwargs):
+        super(GibbsKernel1dBSpline, self).__init__(
+            BSplineWarp(k=k), num_params=2 * nt + k,
+            param_names=([r"\sigma_f"] + [r"t_{{{:d}}}".format(i + 1) for i in range(nt)] +
+                         [r"C_{{{:d}}}".format(i + 1) for i in range(nt + k - 1)]),
+            **kwargs)
+
+
+class _GibbsKernel1dBSplineHost(GibbsKernel1dBSpline):
+    """``GibbsKernel1dBSpline`` of a degree or knot count the device kernel does not carry: evaluated on the host."""
     __call__ = GibbsKernel1d.__call__

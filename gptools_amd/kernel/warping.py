@@ -1,7 +1,7 @@
 r"""Input-warped kernels: ``k(w(x), w(x'))`` with an elementwise, per-dimension warp ``w``.
 
-ref: gptools/kernel/warping.py:63-313 (WarpingFunction), :315-402 (beta_cdf_warp, linear_warp), :464-631 (WarpedKernel),
-:633-716 (BetaWarpedKernel, LinearWarpedKernel); Snoek et al., "Input Warping for Bayesian Optimization of Non-stationary
+ref: gptools/kernel/warping.py:63-313 (WarpingFunction), :315-402 (beta_cdf_warp, linear_warp), :404-462 (ISplineWarp),
+:464-631 (WarpedKernel), :633-758 (BetaWarpedKernel, LinearWarpedKernel, ISplineWarpedKernel); Snoek et al., "Input Warping for Bayesian Optimization of Non-stationary
 Functions", ICML 2014.  With ``w_d`` acting on dimension ``d`` alone,
 
 .. math::  \tilde k(x, x') = k(w(x), w(x')), \qquad
@@ -14,11 +14,14 @@ every dimension in which the row point carries order 1, and likewise for the col
 * beta warp: ``w = I_x(alpha, beta)`` (regularised incomplete beta function), ``w' = x^(alpha-1) (1-x)^(beta-1) / B(alpha, beta)``;
   inputs must lie in [0, 1] (NaN outside, exactly 0 / 1 at the ends).
 * linear warp: ``w = (x - a)/(b - a)``, ``w' = 1/(b - a)``: maps data onto the unit cube in front of a beta warp.
+* I-spline warp: ``w = sum_i C_i I_{i,k}(x | t)`` on a knot grid per dimension (``splines.spev``), monotone for positive
+  coefficients, ``w(t_1) = 0``; ``w'`` is the M-spline of degree ``k - 1``.
 
 ``WarpedKernel.__call__`` runs on the host (numpy / scipy) around the inner kernel's pair-list route and works for any
 inner kernel, any placement (a warped term of a sum) and any user warp function.  ``GaussianProcess`` peels beta / linear
 layers off the *outside* of a native model and evaluates that on the GPU instead (``gpt_set_warp``).
-The I-spline warp of the reference needs its spline module and is not provided.
+The I-spline warp is not among those layers: a kernel warped by it is a Python kernel (pair list on the host, the matrix fit on
+the GPU).
 """
 import inspect
 
@@ -27,9 +30,11 @@ import scipy.special
 
 from .core import Kernel
 from .._hyper import HyperparameterSet
+from ..splines import spev
 from ..utils import CombinedBounds, LogNormalJointPrior
 
-__all__ = ["WarpingFunction", "beta_cdf_warp", "linear_warp", "WarpedKernel", "BetaWarpedKernel", "LinearWarpedKernel"]
+__all__ = ["WarpingFunction", "beta_cdf_warp", "linear_warp", "ISplineWarp", "WarpedKernel", "BetaWarpedKernel",
+           "LinearWarpedKernel", "ISplineWarpedKernel"]
 
 
 class WarpingFunction(HyperparameterSet):
@@ -100,6 +105,30 @@ def linear_warp(X, d, n, *args):
     if n == 1:
         return 1.0 / (b - a) * np.ones_like(X)
     return np.zeros_like(X)
+
+
+class ISplineWarp(object):
+    r"""I-spline warp ``w(x) = \sum_{i=1}^{nt+k-2} C_i I_{i,k}(x | t)`` per dimension (ref: warping.py:404-462).
+
+    ``nt``: the number of knots, one int for every dimension or one per dimension; ``k``: the degree, the same in every
+    dimension.  Called as ``warp(X, d, n, *args)`` with ALL dimensions' parameters in ``args``: per dimension the ``nt_d`` knots,
+    then the ``nt_d + k - 2`` coefficients.  The constant I-spline gets the coefficient 0, so ``w(t_1) = 0``."""
+
+    def __init__(self, nt, k=3):
+        self.nt = nt
+        self.k = k
+
+    def __call__(self, X, d, n, *args):
+        X = np.asarray(X, dtype=float)
+        args = np.asarray(args, dtype=float)
+        nt = np.asarray(self.nt, dtype=int)
+        if nt.ndim == 0:
+            nt = np.full(d + 1, int(nt), dtype=int)
+        i = int(sum(2 * nt[j] + self.k - 2 for j in range(d)))
+        ntd = int(nt[d])
+        t = args[i:i + ntd]
+        C = np.concatenate(([0.0], args[i + ntd:i + 2 * ntd + self.k - 2]))
+        return spev(t, C, self.k, X, n=n, I_spline=True)
 
 
 class WarpedKernel(Kernel):
@@ -266,3 +295,26 @@ class LinearWarpedKernel(WarpedKernel):
         super(LinearWarpedKernel, self).__init__(
             k, WarpingFunction(linear_warp, num_dim=k.num_dim, initial_params=values, param_bounds=bounds,
                                fixed_params=np.ones(len(values), dtype=bool), param_names=names))
+
+
+class ISplineWarpedKernel(WarpedKernel):
+    """``k`` warped by an I-spline of degree ``k_deg`` per dimension (:class:`ISplineWarp`); ``nt`` is the number of knots, an int
+    or one per dimension.  Parameters of the warp: per dimension ``t_{d,1} ..`` then ``C_{d,1} .. C_{d,nt+k_deg-2}``.  Other
+    keywords go to :class:`WarpingFunction` (ref: warping.py:718-758).  Evaluated on the host around the inner kernel."""
+
+    def __init__(self, k, nt, k_deg=3, **w_kwargs):
+        try:
+            iter(nt)
+        except TypeError:
+            nt = nt * np.ones(k.num_dim, dtype=int)
+        else:
+            nt = np.asarray(nt, dtype=int)
+            if len(nt) != k.num_dim:
+                raise ValueError("nt must have length equal to k.num_dim!")
+        names = []
+        for d, ntv in enumerate(nt):
+            names += ["t_{{{:d},{:d}}}".format(d, i + 1) for i in range(ntv)]
+            names += ["C_{{{:d},{:d}}}".format(d, i + 1) for i in range(ntv + k_deg - 2)]
+        super(ISplineWarpedKernel, self).__init__(
+            k, WarpingFunction(ISplineWarp(nt, k=k_deg), num_dim=k.num_dim, param_names=names, num_params=len(names),
+                               **w_kwargs))

@@ -85,6 +85,15 @@ extern "C" {
                                   * (the parameters travel by value in the kernel arguments); a parameter count that is not 3 G + 2
                                   * or a G beyond the cap is GPT_E_ARG */
 #define GPT_GIBBS_MAX_GAUSS 8    /* most Gaussians of GPT_KERNEL_GIBBS_EXPGAUSS */
+#define GPT_KERNEL_GIBBS_BSPLINE 12 /* GibbsKernel1dBSpline, cubic, with nt knots: 2 nt + 3 params [sigma_f, t_1 .. t_nt,
+                                  * C_1 .. C_{nt+2}] (ref: kernel/gibbs.py:905-992, splines.py:5-146): l(x) = sum_i C_i B_{i,3}(x),
+                                  * the cubic B-spline on the knots with three copies of t_1 and t_nt appended; l = l' = 0 outside
+                                  * [t_1, t_nt] (the kernel is then NaN or 0 as in the reference), the last span closed on the
+                                  * right, repeated knots allowed.  nt = (nparams - 3) / 2: an even parameter count, nt < 2 or
+                                  * nt > GPT_GIBBS_MAX_KNOTS (the parameters travel by value in the kernel arguments) is GPT_E_ARG;
+                                  * knots that are not in increasing order (a NaN knot among them) GPT_E_VALUE, "Knots must be in
+                                  * increasing order!", before anything is launched */
+#define GPT_GIBBS_MAX_KNOTS 11   /* most knots of GPT_KERNEL_GIBBS_BSPLINE */
 
 #define GPT_MAX_DIM 16      /* largest supported num_dim */
 #define GPT_WARP_LINEAR 1    /* input warp layer w = (x - a)/(b - a) per dimension (ref: kernel/warping.py:367-402) */
