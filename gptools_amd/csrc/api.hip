@@ -69,6 +69,8 @@ struct gpt_ctx {
                                            //    the launches that DO wait (1-6 GFLOP: only-large or only-small launches gain nothing); not while launches are timed.
     int64_t merge_urgent = 1;              // 1: with flag edges, urgent + rest of a panel are ONE launch (urgent tiles first, partial flag)
                                            //    while the merged launch has at least GPT_MERGE_MIN_TILES 64x64 tiles
+    int64_t skip_pad_rows = 1;             // 1: the trailing updates of a fit leave out the padding rows of the augmented factor (PotrfRequest::live_rows);
+                                           //    0: they cover all NP rows, as they did before (same bits in every row <= N; A/B and the tests' reference)
     int64_t edge_flags = 1;                // 1: those two edges of the look-ahead may be flag words instead of events (see EvalScope)
     bool flags_now = false;                // ... and ARE, in the evaluation in progress (set by EvalScope)
     int reserve_cus = 0;                   // CUs the main stream's mask leaves to the panel stream (0: unmasked)

@@ -148,6 +148,7 @@ extern "C" int gpt_ctx_set_option(gpt_ctx *c, const char *key, int64_t value)
     else if (!strcmp(key, "edge_flags")) c->edge_flags = value;
     else if (!strcmp(key, "merge_urgent")) c->merge_urgent = value;
     else if (!strcmp(key, "tail_wait")) c->tail_wait = value;
+    else if (!strcmp(key, "skip_pad_rows")) c->skip_pad_rows = value ? 1 : 0;
     else if (!strcmp(key, "gemm_prio")) c->gemm_prio = value;
     else if (!strcmp(key, "nb_early")) c->nb_early = value;
     else if (!strcmp(key, "nb_switch_rows")) c->nb_switch_rows = value;

@@ -223,6 +223,7 @@ static int factor_and_ll(gpt_ctx *c, int64_t N, double *ll_data_out, double *log
     req.want_early_binv = c->eager_alpha != 0 && !c->use_graph;
     // (the eager substitution's fast path -- ensure_alpha: N a multiple of 512, at least 1024 -- reads nothing of the last leaf then)
     req.defer_pad_leaf = req.want_early_binv && c->defer_pad && N % 512 == 0 && N >= 1024 && NP == N + 128;
+    req.live_rows = N + 1;                 // the data rows and the augmented row; rows N+1 ... NP-1 are padding (fill_pad_kernel)
     PotrfResult fac;
     GPT_TRY(potrf_run(c, NP, c->dA, NP, c->d_invd, c->d_info, req, &fac));
     const bool pad_on_main = fac.pad_leaf_deferred;

@@ -7,10 +7,15 @@
 static int gemm_nt(gpt_ctx *c, hipStream_t st, int64_t m, int64_t n, int64_t k, double alpha, const double *A,
                    int64_t lda, const double *B, int64_t ldb, double beta, double *C, int64_t ldc, int tri,
                    hipEvent_t done = nullptr, EdgeSig edge = EdgeSig(), EdgeSig wait = EdgeSig(), int64_t edge_cols = 0,
-                   EdgeSig tail = EdgeSig())
+                   EdgeSig tail = EdgeSig(), int64_t m_live = -1)
 {
     // algorithmic flop count: 2k per computed element of C (lower trapezoid when tri)
-    const double elems = tri ? 0.5 * (double)n * (double)(n + 1) + (double)(m - n) * (double)n : (double)m * (double)n;
+    // (m_live, launch_gemm_nt: the rows the result needs -- the padding rows of a fit's factor are not computed and not counted;
+    // with fewer live rows than columns the trapezoid ends inside its triangle)
+    const int64_t ml = (tri && m_live >= 0 && m_live < m) ? m_live : m;
+    const double elems = !tri ? (double)m * (double)n
+                         : ml >= n ? 0.5 * (double)n * (double)(n + 1) + (double)(ml - n) * (double)n
+                                   : 0.5 * (double)ml * (double)(ml + 1);
     const double flops = 2.0 * (double)k * elems;
     // (the roofline line of bench.py: the trailing updates on the MAIN stream only -- at large N the panel and helper
     // streams also launch >= 1 GFLOP updates, on the few CUs reserved for them and concurrently with these; summing their
@@ -31,7 +36,7 @@ static int gemm_nt(gpt_ctx *c, hipStream_t st, int64_t m, int64_t n, int64_t k, 
         gp->flops = flops;
         // algorithmic bytes of the launch: C read and written once (16 B per computed element) + the operand panel once (the B rows
         // of a trailing update are a subset of its A rows: 8 k max(m, n) bytes) -- SURVEY 8d's per-unit figure for this kernel
-        gp->bytes = 16.0 * elems + 8.0 * (double)k * (double)(m > n ? m : n);
+        gp->bytes = 16.0 * elems + 8.0 * (double)k * (double)(tri ? ml : (m > n ? m : n));
     }
     // trailing updates on the main stream leave room on every CU for the panel stream (see gemm.hip)
     const int lds_pad = on_main ? (c->lookahead ? c->gemm_pad : (int)c->dev_gemm_pad) : 0;
@@ -56,7 +61,7 @@ static int gemm_nt(gpt_ctx *c, hipStream_t st, int64_t m, int64_t n, int64_t k, 
         if (glog && flops >= 1.0e9 && on_main) {
             const int64_t nt64 = ((m + 63) / 64) * ((n + 63) / 64);
             const int k64 = (c->tile == 64) || !(c->tile == 0 && nt64 < gemm_small_threshold() && !e0 && edge_cols == 0);
-            fprintf(glog, "%lld %lld %lld %d %.6e %d\n", (long long)m, (long long)n, (long long)k, tri, flops, k64);
+            fprintf(glog, "%lld %lld %lld %d %.6e %d\n", (long long)ml, (long long)n, (long long)k, tri, flops, k64);
             fflush(glog);
         }
     }
@@ -64,7 +69,8 @@ static int gemm_nt(gpt_ctx *c, hipStream_t st, int64_t m, int64_t n, int64_t k, 
     // (option gemm_prio >= 0: every GEMM of this context -- the panel-side context of the block-cyclic engine, whose
     // launches all sit on the chain)
     const int prio = (c->gemm_prio >= 0) ? (int)c->gemm_prio : (!on_main && c->lookahead) ? GPT_PANEL_PRIO : 0;
-    int rc = launch_gemm_nt(st, m, n, k, alpha, A, lda, B, ldb, beta, C, ldc, tri, c->tile, lds_pad, e0, e1, prio, edge, wait, edge_cols, 1, 0, tail);
+    int rc = launch_gemm_nt(st, m, n, k, alpha, A, lda, B, ldb, beta, C, ldc, tri, c->tile, lds_pad, e0, e1, prio, edge, wait, edge_cols, 1, 0, tail,
+                            -1, -1, ml < m ? ml : -1);
     if (!ext) {
         if (prof) GPT_HIP_CHECK(hipEventRecord(gp->e1, st));
         if (done) GPT_HIP_CHECK(hipEventRecord(done, st));
@@ -270,6 +276,10 @@ struct PotrfRequest {
     // nothing of that leaf, so its pivot block (and the rank-128 updates that reach it) leave the panel stream: the substitution
     // follows the last REAL leaf at once, the pad leaf and the reduction run beside it on the main stream (potrf_enqueue).
     bool defer_pad_leaf = false;
+    // The matrix is a fit's augmented factor: only its first live_rows rows (the data rows and the augmented one) carry anything, the
+    // rest is padding -- zero left of a unit diagonal, and stays so.  The trailing updates then leave those rows out (potrf_enqueue's
+    // `update`; option "skip_pad_rows").  0: every row is live.
+    int64_t live_rows = 0;
 };
 struct PotrfResult {
     hipStream_t tail_stream = nullptr;   // defer_join: the stream the factorisation ended on (nullptr: the main stream, joined)
@@ -403,11 +413,16 @@ static int potrf_enqueue(gpt_ctx *c, int64_t n, double *A, int64_t lda, double *
     const int64_t nblk = (n + nbo - 1) / nbo;
     const hipStream_t S = c->stream, P = c->panel_stream;
     const bool la = c->lookahead && nblk > 1;
-    // the rank-pw update by the block column [pc0, pc0 + pw): the lower trapezoid of the columns [a, b), rows [a, n)
+    // the rank-pw update by the block column [pc0, pc0 + pw): the lower trapezoid of the columns [a, b), rows [a, n) -- of which the
+    // rows [a, live) are computed (PotrfRequest::live_rows: for a padding row r every L[r, k] is 0 and stays 0, its update is
+    // C[r, :] -= 0 * B^T and nothing reads it; a < live always, the last block column holds the augmented row).  On every stream
+    // the look-ahead uses it on, and in the one-stream loop below.
+    // (not under option graph: a captured factorisation is replayed for every N of the same padded order)
+    const int64_t live = (req.live_rows > 0 && req.live_rows < n && c->skip_pad_rows && !c->use_graph) ? req.live_rows : n;
     auto update = [&](hipStream_t st, int64_t pc0, int64_t pw, int64_t a, int64_t b, hipEvent_t done = nullptr, EdgeSig edge = EdgeSig(),
                       EdgeSig wait = EdgeSig(), int64_t edge_cols = 0, EdgeSig tail = EdgeSig()) -> int {
         return gemm_nt(c, st, n - a, b - a, pw, -1.0, A + a * lda + pc0, lda, A + a * lda + pc0, lda, 1.0, A + a * lda + a, lda, 1,
-                       done, edge, wait, edge_cols, tail);
+                       done, edge, wait, edge_cols, tail, live > a ? live - a : -1);
     };
     if (!la) {
         for (int64_t k = 0; k < nblk; k++) {

@@ -335,21 +335,15 @@ __global__ __launch_bounds__(256, WPS) void gemm_nt_kernel(
 }
 
 // ---- XCD-aware tile order ------------------------------------------------------------------------------------
-// Workgroup b runs on XCD b % 8 and the workgroups of one XCD start in the order of b / 8.  The needed tiles are put
-// in ONE sequence -- supertiles of 64 x 8 tiles (rows x columns) in row-major order, each walked row by row -- and the
-// sequence is cut into eight contiguous pieces of equal length, one per XCD.  The ~110 workgroups resident on an XCD then
-// share 8 B-panels (kept in its L2 for 64 tile rows) and each A-panel eight times, and every XCD gets the same number of
-// tiles to within one.  Measured on a 7168-row rank-384 update (scratch/pmc_order.sh, scratch/gemm_time.py): 8 x 8
-// supertiles dealt round robin (round 1) 637 MB fetched / 412-417 us, the same cut evenly 674 MB / 402 us (the XCDs'
-// lists differed by up to one supertile = 8 % of a small launch: 4096 rows 157 -> 145 us), 64 x 8 cut evenly 503 MB /
-// 404 us, 16 x 16 846 MB (the streamed C tiles leave the panels well under the L2's 4 MB).  GPT_TILE_ORDER="rows,cols,mode"
-// overrides (mode 0 = round-robin deal).  Tables are built once per (ntm, ntn, tri) and cached on the device; slots past
-// an XCD's list hold (-1, -1).
+// The list itself is built by tile_order.hpp (no HIP calls there: it is also built and checked on the CPU).  Tables are built
+// once per (ntm, ntn, tri, live tile rows, ...) and cached on the device.
 #include <algorithm>
 #include <cstdio>
 #include <cstdlib>
 #include <mutex>
 #include <vector>
+#include "tile_order.hpp"
+static_assert(sizeof(TileIJ) == sizeof(int2), "the order table is uploaded as int2 entries");
 struct TileOrder {
     int64_t ntm, ntn;
     int tri, dev;
@@ -358,6 +352,7 @@ struct TileOrder {
     int2 *d_tab;
     int64_t grid;
     int64_t ntiles;                // entries of the table that hold a tile (the rest are (-1, -1) padding)
+    int64_t live_tm;               // tile rows enumerated (tile_needed): < ntm when the launch skips the padding rows of a fit's factor
     int64_t edge_cols, nedge;      // partial edge flag: the tiles of the first edge_cols columns come first; their number
     uint64_t last_use;             // tick of the last look-up (eviction takes the least recently used tables)
     bool pinned;                   // looked up during a stream capture: a captured graph holds d_tab, never evicted
@@ -366,35 +361,11 @@ static std::vector<TileOrder> g_orders;
 static std::mutex g_orders_mu;
 static uint64_t g_orders_tick = 0;
 
-// tri == 2: staircase.  Column segment q = j / seg_t starts (its diagonal block) at tile row q * rss_t; tile (i, j) is
-// needed iff i >= q * rss_t + (j - q * seg_t).
-// tri == 3: grid staircase (2-D block-cyclic layout, gptools_amd/dist.py GridLML).  Column segment q is local block column q of
-// the update, global block column J = J0 + q * num; the local block rows hold the global block rows I = pr + li * den.  Its
-// first needed block row is the first I >= J:  rs(q) = ceil((off + q * num) / den) - base  with off = J0 - pr and base = the
-// local index of the update's first block row.  Below that row the segment is a full rectangle; the first block itself is a
-// DIAGONAL block of the matrix iff (off + q * num) is a multiple of den, and then only its lower tiles are needed.
-struct GridStair { int64_t off = 0, num = 0, den = 1, base = 0; };
-static inline bool tile_needed(int tri, int64_t i, int64_t j, int64_t seg_t, int64_t rss_t, const GridStair &g = GridStair())
-{
-    if (tri == 1) return j <= i;
-    if (tri == 2) {
-        const int64_t q = j / seg_t;
-        return i >= q * rss_t + (j - q * seg_t);
-    }
-    if (tri == 3) {
-        const int64_t q = j / seg_t, v = g.off + q * g.num;
-        const int64_t i0 = ((v + g.den - 1) / g.den - g.base) * seg_t;
-        if (i < i0) return false;
-        if (v % g.den == 0 && i < i0 + seg_t) return (i - i0) >= (j - q * seg_t);
-        return true;
-    }
-    return true;
-}
-
 static int tile_order(int64_t ntm, int64_t ntn, int tri, const int2 **tab, int64_t *grid, int64_t seg_t = 0,
                       int64_t rss_t = 0, int64_t *ntiles = nullptr, int64_t edge_cols = 0, int64_t *nedge = nullptr,
-                      const GridStair &gs = GridStair(), hipStream_t st = nullptr)
+                      const GridStair &gs = GridStair(), hipStream_t st = nullptr, int64_t live_tm = -1)
 {
+    if (live_tm < 0 || live_tm > ntm) live_tm = ntm;
     static int sgm = 0, sgn = 0, mode = 0;
     if (sgm == 0) {
         sgm = 64, sgn = 8, mode = 1;
@@ -414,7 +385,7 @@ static int tile_order(int64_t ntm, int64_t ntn, int tri, const int2 **tab, int64
     }
     std::lock_guard<std::mutex> lk(g_orders_mu);
     for (auto &o : g_orders)
-        if (o.ntm == ntm && o.ntn == ntn && o.tri == tri && o.dev == dev && o.seg_t == seg_t && o.rss_t == rss_t && o.edge_cols == edge_cols &&
+        if (o.ntm == ntm && o.ntn == ntn && o.tri == tri && o.dev == dev && o.seg_t == seg_t && o.rss_t == rss_t && o.edge_cols == edge_cols && o.live_tm == live_tm &&
             o.g_off == gs.off && o.g_num == gs.num && o.g_den == gs.den && o.g_base == gs.base) {
             o.last_use = ++g_orders_tick;
             o.pinned = o.pinned || capturing;
@@ -447,38 +418,8 @@ static int tile_order(int64_t ntm, int64_t ntn, int tri, const int2 **tab, int64
             (void)hipGetLastError();
         }
     }
-    std::vector<std::vector<int2>> per(8);
-    std::vector<int2> seq, sequ;          // sequ: the tiles of the first edge_cols columns (they go first on every XCD)
-    const int64_t sm = (ntm + sgm - 1) / sgm, sn = (ntn + sgn - 1) / sgn;
-    int64_t sidx = 0;
-    for (int64_t si = 0; si < sm; si++)
-        for (int64_t sj = 0; sj < sn; sj++) {
-            std::vector<int2> &dst = (mode || edge_cols > 0) ? seq : per[sidx % 8];
-            bool any = false;
-            for (int64_t i = si * sgm; i < (si + 1) * sgm && i < ntm; i++)
-                for (int64_t j = sj * sgn; j < (sj + 1) * sgn && j < ntn; j++) {
-                    if (!tile_needed(tri, i, j, seg_t, rss_t, gs)) continue;
-                    (j < edge_cols ? sequ : dst).push_back(make_int2((int)i, (int)j));
-                    any = true;
-                }
-            if (any) sidx++;
-        }
-    if (mode || edge_cols > 0) {
-        for (const std::vector<int2> *sq : {&sequ, &seq}) {
-            const size_t T = sq->size(), q = T / 8, r = T % 8;
-            size_t at = 0;
-            for (int x = 0; x < 8; x++) {
-                const size_t len = q + ((size_t)x < r ? 1 : 0);
-                per[x].insert(per[x].end(), sq->begin() + at, sq->begin() + at + len);
-                at += len;
-            }
-        }
-    }
-    size_t mx = 0;
-    for (auto &v : per) mx = v.size() > mx ? v.size() : mx;
-    std::vector<int2> flat(mx * 8, make_int2(-1, -1));
-    for (int x = 0; x < 8; x++)
-        for (size_t l = 0; l < per[x].size(); l++) flat[l * 8 + x] = per[x][l];
+    const TileTable t = build_tile_table(ntm, ntn, tri, seg_t, rss_t, edge_cols, gs, live_tm, sgm, sgn, mode);
+    const std::vector<TileIJ> &flat = t.flat;
     TileOrder o;
     o.ntm = ntm;
     o.ntn = ntn;
@@ -491,10 +432,10 @@ static int tile_order(int64_t ntm, int64_t ntn, int tri, const int2 **tab, int64
     o.g_den = gs.den;
     o.g_base = gs.base;
     o.edge_cols = edge_cols;
-    o.nedge = (int64_t)sequ.size();
+    o.live_tm = live_tm;
+    o.nedge = t.nedge;
     o.grid = (int64_t)flat.size();
-    o.ntiles = 0;
-    for (auto &v : per) o.ntiles += (int64_t)v.size();
+    o.ntiles = t.ntiles;
     o.d_tab = nullptr;
     GPT_HIP_CHECK(hipMalloc(&o.d_tab, flat.size() * sizeof(int2)));
     {   // upload on a private non-blocking stream: the caller may be inside a stream capture (hipGraph option), where
@@ -524,12 +465,20 @@ static int gemm_launch_t(hipStream_t st, int64_t m, int64_t n, int64_t k, double
                          int lds_pad, hipEvent_t ev0 = nullptr, hipEvent_t ev1 = nullptr, int64_t seg_cols = 0,
                          int64_t bskip = 0, int64_t row_step = 0, int prio = 0, EdgeSig edge = EdgeSig(),
                          EdgeSig wait = EdgeSig(), int64_t edge_cols_elems = 0, int64_t nbatch = 1, int64_t bstride = 0,
-                         EdgeSig tail = EdgeSig(), int64_t bstride_b = -1, int64_t bstride_c = -1, const GridStair &gs = GridStair())
+                         EdgeSig tail = EdgeSig(), int64_t bstride_b = -1, int64_t bstride_c = -1, const GridStair &gs = GridStair(),
+                         int64_t m_live = -1)
 {
     if (bstride_b < 0) bstride_b = bstride;
     if (bstride_c < 0) bstride_c = bstride;
     const int64_t ntm = (m + BM - 1) / BM, ntn = (n + BN - 1) / BN;
-    int64_t nwg = (tri == 1) ? ntn * (ntn + 1) / 2 + (ntm - ntn) * ntn : ntm * ntn;
+    // Live rows of a tri launch (launch_gemm_nt): the rows from m_live on are not computed.  The kernel takes the live count as its
+    // row limit, and the tiles that start at or beyond it are not enumerated -- neither by the table (tile_needed) nor by the closed
+    // form, whose triangle is walked row by row and simply ends earlier.  What kind of launch this is (table or closed form, and the
+    // callers' tile choice) still follows the FULL shape, so that a limit never changes the path a launch takes.
+    const int64_t nwg_full = (tri == 1) ? ntn * (ntn + 1) / 2 + (ntm - ntn) * ntn : ntm * ntn;
+    if (tri == 1 && m_live >= 0 && m_live < m) m = m_live;
+    const int64_t ltm = (m + BM - 1) / BM;
+    int64_t nwg = (tri == 1) ? (ltm >= ntn ? ntn * (ntn + 1) / 2 + (ltm - ntn) * ntn : ltm * (ltm + 1) / 2) : ntm * ntn;
     int64_t nreal = nwg;                   // workgroups that compute a tile (and count towards an edge flag)
     int64_t nedge = 0;                     // ... of which in the first edge_cols columns (partial edge flag)
     const int2 *order = nullptr;
@@ -541,9 +490,9 @@ static int gemm_launch_t(hipStream_t st, int64_t m, int64_t n, int64_t k, double
         int64_t grid = 0;
         GPT_TRY_RC(tile_order(ntm, ntn, 3, &order, &grid, seg_cols / BN, 0, &nreal, 0, nullptr, gs, st));
         nwg = grid;
-    } else if (nwg >= 512) {               // large launches only: small ones live in L2 anyway
+    } else if (nwg_full >= 512) {          // large launches only: small ones live in L2 anyway
         int64_t grid = 0;
-        GPT_TRY_RC(tile_order(ntm, ntn, tri, &order, &grid, 0, 0, &nreal, edge_cols_elems / BN, &nedge, GridStair(), st));
+        GPT_TRY_RC(tile_order(ntm, ntn, tri, &order, &grid, 0, 0, &nreal, edge_cols_elems / BN, &nedge, GridStair(), st, ltm));
         nwg = grid;
     }
     if (edge_cols_elems > 0 && (order == nullptr || !edge.word || nedge <= 0)) {
@@ -586,7 +535,7 @@ int gemm_small_threshold()
 int launch_gemm_nt(hipStream_t st, int64_t m, int64_t n, int64_t k, double alpha, const double *A, int64_t lda,
                    const double *B, int64_t ldb, double beta, double *C, int64_t ldc, int tri, int force_tile, int lds_pad,
                    hipEvent_t ev0, hipEvent_t ev1, int prio, EdgeSig edge, EdgeSig wait, int64_t edge_cols, int64_t nbatch,
-                   int64_t bstride, EdgeSig tail, int64_t bstride_b, int64_t bstride_c)
+                   int64_t bstride, EdgeSig tail, int64_t bstride_b, int64_t bstride_c, int64_t m_live)
 {
     gpt_jitter(st);
     if (m <= 0 || n <= 0) {
@@ -610,6 +559,14 @@ int launch_gemm_nt(hipStream_t st, int64_t m, int64_t n, int64_t k, double alpha
     }
     if (tri && m < n) {
         gpt_set_error("gemm_nt: tri requires m >= n");
+        return GPT_E_ARG;
+    }
+    // m_live (tri launches; < 0: all rows): only the first m_live of the m rows are computed -- the trailing updates of a fit's
+    // augmented factor, whose rows past the augmented one are padding (zero left of a unit diagonal: their update is -0 * B^T and
+    // nothing reads it).  A row count of its own and not a smaller m: the column extent n may exceed it (the launch then ends inside
+    // its triangle), and the tile choice below follows the full shape.
+    if (m_live >= 0 && (!tri || m_live == 0 || nbatch > 1)) {
+        gpt_set_error("gemm_nt: a live row count needs a tri launch with at least one live row, not batched");
         return GPT_E_ARG;
     }
     if (nbatch > 1 && (force_tile != 0 || edge.word || wait.word || edge_cols || ev0 || ev1)) {
@@ -642,8 +599,10 @@ int launch_gemm_nt(hipStream_t st, int64_t m, int64_t n, int64_t k, double alpha
             if (const char *e = getenv("GPT_GEMM_SMALL_STAGES")) stages = atoi(e);
         }
         if ((stages == 4 && k >= 64) || (stages == 0 && k >= 256))
-            return gemm_launch_t<32, 32, 2, 4>(st, m, n, k, alpha, A, lda, B, ldb, beta, C, ldc, tri, 0, ev0, ev1, 0, 0, 0, prio, edge, wait, 0, nbatch, bstride, tail, bstride_b, bstride_c);
-        return gemm_launch_t<32, 32, 2, 2>(st, m, n, k, alpha, A, lda, B, ldb, beta, C, ldc, tri, 0, ev0, ev1, 0, 0, 0, prio, edge, wait, 0, nbatch, bstride, tail, bstride_b, bstride_c);
+            return gemm_launch_t<32, 32, 2, 4>(st, m, n, k, alpha, A, lda, B, ldb, beta, C, ldc, tri, 0, ev0, ev1, 0, 0, 0, prio, edge, wait, 0, nbatch, bstride, tail, bstride_b, bstride_c,
+                                               GridStair(), m_live);
+        return gemm_launch_t<32, 32, 2, 2>(st, m, n, k, alpha, A, lda, B, ldb, beta, C, ldc, tri, 0, ev0, ev1, 0, 0, 0, prio, edge, wait, 0, nbatch, bstride, tail, bstride_b, bstride_c,
+                                               GridStair(), m_live);
     }
     if ((edge.word || wait.word || edge_cols || tail.word) && tile != 64) {
         gpt_set_error("gemm_nt: edge flags exist for the 64x64 / 32x32 kernels only");
@@ -657,7 +616,7 @@ int launch_gemm_nt(hipStream_t st, int64_t m, int64_t n, int64_t k, double alpha
         return GPT_E_ARG;
     }
     return gemm_launch_t<64, 64, 2, 2>(st, m, n, k, alpha, A, lda, B, ldb, beta, C, ldc, tri, lds_pad, ev0, ev1, 0, 0, 0, prio, edge, wait, edge_cols,
-                                       nbatch, bstride, tail, bstride_b, bstride_c);
+                                       nbatch, bstride, tail, bstride_b, bstride_c, GridStair(), m_live);
 }
 
 // Staircase update: C (m x nseg*seg_cols) += alpha * A B_q^T per column segment q, where segment q (seg_cols

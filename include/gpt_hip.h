@@ -137,6 +137,12 @@ int gpt_ctx_destroy(gpt_ctx *ctx);
  *   "tail_wait"    1 (default since round 6): the main stream's last launch of a panel awaits the NEXT panel's flag at its end instead of
  *                  a wait kernel in front of the next launch (C3 -19 us, C2 -15 us); not while "profile_gemm" times the launches (a
  *                  launch that waits at its end reports the wait as its duration); 0: always the wait kernel
+ *   "skip_pad_rows" 1 (default): the trailing updates of a fit (gpt_fit*, gpt_fit_matrix) compute only the rows 0 ... N of the padded
+ *                  factor of order NP = round_up(N + 1, 128) -- the data rows and the augmented row.  The up to 127 padding rows below are
+ *                  zero left of a unit diagonal and stay so: the tiles that start below row N are not launched, and the tile row that
+ *                  holds row N stores nothing below it (N = 8192: one 64-row tile row in 122 ... 2 per launch, C3 -0.06 ms).  Rows <= N,
+ *                  ll, alpha, predictions and gradients are bit-identical to 0, which updates all NP rows; the padding entries can
+ *                  differ in the sign of zero.  Not under "graph" (a captured factorisation is replayed for every N of one NP)
  *   "alpha_invalidate" (measurement aid) the next gpt_get_alpha recomputes alpha
  *   "eager_alpha"  1: every gpt_fit* also enqueues alpha = K_tot^-1 y behind its factorisation (the reference computes alpha in every
  *                  evaluation, gaussian_process.py:1462) and lands it in pinned memory under the call's own synchronisation;
