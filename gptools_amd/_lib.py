@@ -20,6 +20,14 @@ KERNEL_GIBBS_TANH, KERNEL_GIBBS_DTANH, KERNEL_GIBBS_CUBIC, KERNEL_GIBBS_QUINTIC,
 KERNEL_GIBBS_BSPLINE = 12
 GIBBS_MAX_GAUSS = 8      # GPT_GIBBS_MAX_GAUSS: most Gaussians of KERNEL_GIBBS_EXPGAUSS
 GIBBS_MAX_KNOTS = 11     # GPT_GIBBS_MAX_KNOTS: most knots of KERNEL_GIBBS_BSPLINE
+GIBBS_ON_DIM_MAX_D = 3   # GPT_GIBBS_ON_DIM_MAX_D: largest num_dim at which a Gibbs kernel id may carry the dimension it acts on
+KERNEL_ON_DIM_STRIDE = 256
+
+
+def kernel_on_dim(kernel_id, d):
+    """GPT_KERNEL_ON_DIM(id, d): the 1-D Gibbs kernel ``kernel_id`` on dimension ``d`` of a model with more dimensions (a product
+    factor, include/gpt_hip.h)."""
+    return int(kernel_id) + KERNEL_ON_DIM_STRIDE * (int(d) + 1)
 MAX_DIM = 16
 WARP_LINEAR, WARP_BETA, WARP_MAX_LAYERS = 1, 2, 4
 

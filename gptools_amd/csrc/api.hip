@@ -87,6 +87,7 @@ struct gpt_ctx {
     int lookahead = 1;
     int use_graph = 0;
     long n_maxsum = 0;                 // largest row sum of the training derivative orders (gpt_set_data)
+    long n_colmax[GPT_MAX_DIM] = {};   // largest training order of each coordinate (gpt_set_data): a Gibbs factor's own rule
     long n_maxord = 0;                 // largest single derivative order of the training points (gpt_set_data)
     int timing = 0;
     int tile = 0;

@@ -76,7 +76,7 @@ static int fit_batch_impl(gpt_ctx *c, int nbatch, int nterms, const int *kernel_
     }
     // every element has the first one's kernels: its parse decides the layout (and refuses what any element's would)
     ModelKernel m0, mb;
-    GPT_TRY(parse_model(c->D, c->n_maxsum, nterms, kernel_ids, kernel_ids2, params, nparams_t, nparams1_t, &m0));
+    GPT_TRY(parse_model(c->D, c->n_maxsum, c->n_colmax, nterms, kernel_ids, kernel_ids2, params, nparams_t, nparams1_t, &m0));
     const bool any_prod = m0.any_prod;
     const int64_t NP = round_up(N + 1, 128), nleaf = NP / 128, bs = NP * NP, bws = nleaf * GPT_WS_BLOCK;
     // pinned staging: [y: nbatch N | err: N | noise: nbatch | KParams: nterms x nbatch (| second factors: the same) | results: 4
@@ -99,7 +99,7 @@ static int fit_batch_impl(gpt_ctx *c, int nbatch, int nterms, const int *kernel_
     memcpy(h + off_nv, noise_var, (size_t)nbatch * sizeof(double));
     char *hkp = reinterpret_cast<char *>(h + off_kp), *hkp2 = hkp + (size_t)nterms * nbatch * kp_doubles * 8;
     for (int b = 0; b < nbatch; b++) {
-        if (b > 0) GPT_TRY(parse_model(c->D, c->n_maxsum, nterms, kernel_ids, kernel_ids2, params + (size_t)b * m0.nparams, nparams_t, nparams1_t, &mb));
+        if (b > 0) GPT_TRY(parse_model(c->D, c->n_maxsum, c->n_colmax, nterms, kernel_ids, kernel_ids2, params + (size_t)b * m0.nparams, nparams_t, nparams1_t, &mb));
         const ModelKernel &m = b > 0 ? mb : m0;
         for (int t = 0; t < nterms; t++) {                                  // term-major on the device: [t][b]
             memcpy(hkp + ((size_t)t * nbatch + (size_t)b) * kp_doubles * 8, &m.f1[t], sizeof(KParams));
@@ -144,7 +144,7 @@ static int fit_batch_impl(gpt_ctx *c, int nbatch, int nterms, const int *kernel_
         for (int t = 0; t < nterms; t++)
             GPT_TRY(launch_kbuild_batch(st, m0.f1[t].kernel_id, c->D, dkp + (size_t)t * nbatch, dmisc + d_off_nv, nbatch, bX, c->dn, Nx,
                                         t + 1 == nterms ? dzero : nullptr, 0.0, dKf, NxP, (int64_t)kfull, t > 0 ? 1 : 0, 1, term_kp2(t),
-                                        xstr, bS, sstr, m0.has_bspline));
+                                        xstr, bS, sstr, m0.gibbs_form()));
         GPT_TRY(launch_gemm_nt(st, NyP, NxP, NxP, 1.0, c->dT, NxP, dKf, NxP, 0.0, dTK, NxP, 0, 0, 0, nullptr, nullptr, 0, EdgeSig(),
                                EdgeSig(), 0, nbatch, 0, EdgeSig(), (int64_t)kfull, (int64_t)tk));
         GPT_TRY(launch_gemm_nt(st, NyP, NyP, NxP, 1.0, dTK, NxP, c->dT, NxP, 0.0, dA, NP, 1, 0, 0, nullptr, nullptr, 0, EdgeSig(),
@@ -156,7 +156,7 @@ static int fit_batch_impl(gpt_ctx *c, int nbatch, int nterms, const int *kernel_
         for (int t = 0; t < nterms; t++)                                    // (as kbuild_terms: later terms accumulate, the last
             GPT_TRY(launch_kbuild_batch(st, m0.f1[t].kernel_id, c->D, dkp + (size_t)t * nbatch, dmisc + d_off_nv, nbatch,   //  one carries the
                                         bX, c->dn, N, t + 1 == nterms ? dmisc : nullptr, diag_add, dA, NP, bs,     //  diagonal epilogue)
-                                        t > 0 ? 1 : 0, 0, term_kp2(t), xstr, bS, sstr, m0.has_bspline));
+                                        t > 0 ? 1 : 0, 0, term_kp2(t), xstr, bS, sstr, m0.gibbs_form()));
     }
     // LEFT-looking over the 128-column leaves: leaf j first receives the update of ALL leaves before it in one launch
     // (k = 128 j; element by element the same sums in the same order as the right-looking rank-128 updates of gpt_fit, whose
@@ -303,7 +303,7 @@ extern "C" int gpt_predict_batch(gpt_ctx *c, const double *Xstar, const int32_t 
     GPT_TRY(launch_zero2d(st, MP, ldv, dV, ldv));
     for (int t = 0; t < nterms; t++)
         GPT_TRY(launch_kbuild_batch_cross(st, model.f1[t].kernel_id, D, dkp + (size_t)t * nbatch, dnv, nbatch, dXs, dns,
-                                          M, c->dX, c->dn, N, dV, ldv, NP, t > 0 ? 1 : 0, term_kp2(t), model.has_bspline));
+                                          M, c->dX, c->dn, N, dV, ldv, NP, t > 0 ? 1 : 0, term_kp2(t), model.gibbs_form()));
     // V_b = K*_b^T L_b^-T, left-looking over the leaves: leaf j first receives the update of all leaves before it
     for (int64_t lc = 0; lc < NP; lc += 128) {
         if (lc > 0)
@@ -311,13 +311,13 @@ extern "C" int gpt_predict_batch(gpt_ctx *c, const double *Xstar, const int32_t 
                                    EdgeSig(), EdgeSig(), 0, nbatch, NP, EdgeSig(), bs, NP));
         GPT_TRY(launch_trsm_panel(st, MP, nullptr, 0, dws + (lc / 128) * GPT_WS_BLOCK, dV + lc, ldv, nullptr, EdgeSig(), nbatch, NP, bws));
     }
-    GPT_TRY(launch_kdiag_batch(st, D, nterms, dkp, dkp2, nbatch, dXs, dns, M, dvar, MP, model.has_bspline));
+    GPT_TRY(launch_kdiag_batch(st, D, nterms, dkp, dkp2, nbatch, dXs, dns, M, dvar, MP, model.gibbs_form()));
     GPT_TRY(launch_batch_meanvar(st, M, MP, N, NP, nbatch, dV, ldv, dA, bs, dkeep, dmean, dvar, MP));
     std::vector<double> hmv(2 * (size_t)nbatch * MP);
     GPT_HIP_CHECK(hipMemcpyAsync(hmv.data(), dmean, hmv.size() * sizeof(double), hipMemcpyDeviceToHost, st));
     if (want_sum) {
         GPT_TRY(launch_zero2d(st, MP, MP, dC, MP));
-        GPT_TRY(launch_kss_sum(st, D, nterms, dkp, dkp2, nbatch, dkeep, dXs, dns, M, MP, noise_n ? dhit : nullptr, noise_sum, dC, MP, model.has_bspline));
+        GPT_TRY(launch_kss_sum(st, D, nterms, dkp, dkp2, nbatch, dkeep, dXs, dns, M, MP, noise_n ? dhit : nullptr, noise_sum, dC, MP, model.gibbs_form()));
         // (k = nbatch NP against few output tiles: split along k where that pays, as the few-rows solves do)
         GPT_TRY(gemm_nt_few(c, st, MP, MP, ldv, -1.0, dV, ldv, dV, ldv, 1.0, dC, MP, 1));
         GPT_TRY(launch_mirror_rows(st, dC, MP, 0, MP, MP));
@@ -331,7 +331,7 @@ extern "C" int gpt_predict_batch(gpt_ctx *c, const double *Xstar, const int32_t 
         GPT_TRY(launch_zero2d(st, (int64_t)nbatch * MP, MP, dC, MP));
         for (int t = 0; t < nterms; t++)
             GPT_TRY(launch_kbuild_batch_cross(st, model.f1[t].kernel_id, D, dkp + (size_t)t * nbatch, dnv, nbatch, dXs,
-                                              dns, M, dXs, dns, M, dC, MP, cs, t > 0 ? 1 : 0, term_kp2(t), model.has_bspline));
+                                              dns, M, dXs, dns, M, dC, MP, cs, t > 0 ? 1 : 0, term_kp2(t), model.gibbs_form()));
         GPT_TRY(launch_gemm_nt(st, MP, MP, NP, -1.0, dV, ldv, dV, ldv, 1.0, dC, MP, 0, 0, 0, nullptr, nullptr, 0, EdgeSig(), EdgeSig(), 0,
                                nbatch, NP, EdgeSig(), NP, cs));
         for (int b = 0; b < nbatch; b++)

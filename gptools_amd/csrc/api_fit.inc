@@ -29,11 +29,13 @@ extern "C" int gpt_set_data(gpt_ctx *c, const double *X, const int32_t *n, int64
     c->Nx = N;
     c->D = D;
     c->n_maxsum = c->n_maxord = 0;
+    for (int d = 0; d < GPT_MAX_DIM; d++) c->n_colmax[d] = 0;
     for (int64_t i = 0; i < N; i++) {
         long sn = 0;
         for (int d = 0; d < D; d++) {
             sn += n[i * D + d];
             if (n[i * D + d] > c->n_maxord) c->n_maxord = n[i * D + d];
+            if (n[i * D + d] > c->n_colmax[d]) c->n_colmax[d] = n[i * D + d];
         }
         if (sn > c->n_maxsum) c->n_maxsum = sn;
     }
@@ -342,7 +344,7 @@ static int fit_model(gpt_ctx *c, int nterms, const int *kernel_ids, const int *k
     }
     if (!y || !err_y || (need_ids2 && (!kernel_ids2 || !nparams1))) return GPT_E_ARG;
     ModelKernel model;
-    GPT_TRY(parse_model(c->D, c->n_maxsum, nterms, kernel_ids, kernel_ids2, params, nparams, nparams1, &model));
+    GPT_TRY(parse_model(c->D, c->n_maxsum, c->n_colmax, nterms, kernel_ids, kernel_ids2, params, nparams, nparams1, &model));
     return fit_terms(c, model, noise_var, y, err_y, diag_add, ll_data_out, logdet_half_out);
 }
 

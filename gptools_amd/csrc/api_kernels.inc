@@ -114,12 +114,12 @@ extern "C" int gpt_kbuild(gpt_ctx *c, int kernel_id, const double *params, int n
 static int make_product(int kid1, const double *p1, int n1, int kid2, const double *p2, int n2, int D, KParams *k1, KParams *k2)
 {
     if (!p1 || !p2) return GPT_E_ARG;
-    if (!native_fit_kernel(kid1) || !native_fit_kernel(kid2)) {
+    if (!native_fit_kernel(GPT_KERNEL_BASE_ID(kid1)) || !native_fit_kernel(GPT_KERNEL_BASE_ID(kid2))) {
         gpt_set_error("product factors must be SE, Matern52, RationalQuadratic, Matern or Gibbs kernels");
         return GPT_E_ARG;
     }
-    GPT_TRY(make_kparams(kid1, p1, n1, D, -1, 0, nullptr, k1));
-    return make_kparams(kid2, p2, n2, D, -1, 0, nullptr, k2);
+    GPT_TRY(make_kparams(kid1, p1, n1, D, -1, 0, nullptr, k1, true));
+    return make_kparams(kid2, p2, n2, D, -1, 0, nullptr, k2, true);
 }
 
 extern "C" int gpt_kpairs2(gpt_ctx *c, int kernel_id1, const double *params1, int nparams1, int kernel_id2,

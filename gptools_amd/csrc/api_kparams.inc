@@ -5,15 +5,40 @@
 // check_rq_orders, check_gibbs_orders, check_warp_orders and, built on them, ONE function per family of entry points:
 // check_train_orders (the fits), check_test_orders (the predictions), check_pair_orders (gpt_kpairs* / gpt_kbuild*).
 // ------------------------------------------------------------------------------------------------
+// factor: the kernel is a factor of a product -- the only place of a GPT_KERNEL_ON_DIM id
 static int make_kparams(int kernel_id, const double *params, int nparams, int D, int hyper_deriv, int symmetric,
-                        const int32_t *noise_n, KParams *kp)
+                        const int32_t *noise_n, KParams *kp, bool factor = false)
 {
     if (D < 1 || D > GPT_MAX_DIM) {
         gpt_set_error("num_dim %d out of range [1, %d]", D, GPT_MAX_DIM);
         return GPT_E_ARG;
     }
+    // GPT_KERNEL_ON_DIM(id, d): a 1-D Gibbs kernel on coordinate d of num_dim <= GPT_GIBBS_ON_DIM_MAX_D (a product factor: the
+    // builders have that form only as GPT_KID_PRODUCT_GM / _GB, kbuild_kernel.hpp).  From here on kernel_id is the plain id
+    const int on_dim = GPT_KERNEL_DIM_OF(kernel_id);
+    if (on_dim >= 0) {
+        kernel_id = GPT_KERNEL_BASE_ID(kernel_id);
+        if (!factor) {
+            gpt_set_error("kernel %d on coordinate %d: a Gibbs kernel on one coordinate is a product factor (on its own: times SE [1, inf ..])",
+                          kernel_id, on_dim);
+            return GPT_E_ARG;
+        }
+        if (!gibbs_kid(kernel_id)) {
+            gpt_set_error("kernel %d: only a Gibbs kernel id carries a coordinate (GPT_KERNEL_ON_DIM)", kernel_id);
+            return GPT_E_ARG;
+        }
+        if (D > GPT_GIBBS_ON_DIM_MAX_D) {
+            gpt_set_error("a Gibbs kernel on one coordinate needs num_dim <= %d, got %d", GPT_GIBBS_ON_DIM_MAX_D, D);
+            return GPT_E_ARG;
+        }
+        if (on_dim >= D) {
+            gpt_set_error("kernel %d on coordinate %d of num_dim %d", kernel_id, on_dim, D);
+            return GPT_E_ARG;
+        }
+    }
     memset(kp, 0, sizeof(*kp));
     kp->kernel_id = kernel_id;
+    kp->g_dim = on_dim >= 0 ? on_dim : 0;
     kp->D = D;
     kp->hyper_deriv = hyper_deriv < 0 ? -1 : hyper_deriv;
     kp->symmetric = symmetric ? 1 : 0;
@@ -81,6 +106,7 @@ static int make_kparams(int kernel_id, const double *params, int nparams, int D,
             kp->l[d] = l;
             kp->inv_l[d] = 1.0 / l;
             kp->inv_var[d] = 1.0 / (l * l);
+            if (std::isinf(l)) kp->inf_l = 1;      // (matern_pair's guard for an order in a masked-out dimension, kpair.hpp)
         }
         kp->m_cnu = pow(2.0, 1.0 - nu) / tgamma(nu);
         kp->m_nint = (int)floor(nu + 0.5);
@@ -106,7 +132,7 @@ static int make_kparams(int kernel_id, const double *params, int nparams, int D,
         // GibbsKernel1dTanh [sigma_f, l_1, l_2, l_w, x_0] (ref: gibbs.py:426-498); GibbsKernel1dDoubleTanh [sigma_f, l_c, l_m,
         // l_e, l_a, l_b, x_a, x_b] (ref: gibbs.py:508-590).  Both as l(x) = g_c + sum_q g_amp[q] tanh((x - g_x0[q]) / g_w[q])
         const bool dbl = kernel_id == GPT_KERNEL_GIBBS_DTANH;
-        if (D != 1) {
+        if (D != 1 && on_dim < 0) {
             gpt_set_error("Gibbs kernel only supports 1d data.");
             return GPT_E_ARG;
         }
@@ -143,7 +169,7 @@ static int make_kparams(int kernel_id, const double *params, int nparams, int D,
         // GibbsKernel1dExpGauss [sigma_f, l_0, mu_1..G, sigma_1..G, beta_1..G] (ref: gibbs.py:804-902).  The parameters after
         // sigma_f go to the device as they are (gibbs_lfunc.hpp forms l and l' from them in the reference's order of operations)
         const bool eg = kernel_id == GPT_KERNEL_GIBBS_EXPGAUSS;
-        if (D != 1) {
+        if (D != 1 && on_dim < 0) {
             gpt_set_error("Gibbs kernel only supports 1d data.");
             return GPT_E_ARG;
         }
@@ -171,7 +197,7 @@ static int make_kparams(int kernel_id, const double *params, int nparams, int D,
     } else if (kernel_id == GPT_KERNEL_GIBBS_BSPLINE) {
         // GibbsKernel1dBSpline, cubic [sigma_f, t_1 .. t_nt, C_1 .. C_{nt+2}] (ref: gibbs.py:905-992); the ABI carries no integer
         // besides nparams, so nt = (nparams - 3) / 2.  Knots and coefficients go to the device as they are (gibbs_lfunc.hpp)
-        if (D != 1) {
+        if (D != 1 && on_dim < 0) {
             gpt_set_error("Gibbs kernel only supports 1d data.");
             return GPT_E_ARG;
         }
@@ -262,12 +288,14 @@ static bool is_chain(int kid)
     return kid == GPT_KERNEL_RQ || kid == GPT_KERNEL_MATERN;
 }
 
-// The Gibbs kernels evaluate derivative orders 0 and 1 per point (ref: gibbs.py:417-420 raises NotImplementedError beyond)
+// The Gibbs kernels evaluate derivative orders 0 and 1 per point (ref: gibbs.py:417-420 raises NotImplementedError beyond) -- in
+// the coordinate `col` the kernel acts on (KParams::g_dim: 0 at num_dim 1, the coordinate of a GPT_KERNEL_ON_DIM factor).  The
+// orders of the other coordinates belong to the other factor of the product and to its rules.
 static const char *const GIBBS_ORDER_MSG = "Derivatives greater than [1, 1] are not supported!";
-static int check_gibbs_orders(const int32_t *n, int64_t M, int D)
+static int check_gibbs_orders(const int32_t *n, int64_t M, int D, int col)
 {
-    for (int64_t i = 0; i < M * D; i++)
-        if (n[i] > 1) {
+    for (int64_t i = 0; i < M; i++)
+        if (n[i * D + col] > 1) {
             gpt_set_error("%s", GIBBS_ORDER_MSG);
             return GPT_E_NOTIMPL;
         }
@@ -304,16 +332,19 @@ struct ModelKernel {
     KParams f1[GPT_MAX_TERMS] = {}, f2[GPT_MAX_TERMS] = {};      // f2[t].kernel_id < 0: term t is not a product; zero beyond nterms
     bool any_prod = false, has_m52 = false, has_chain = false, has_gibbs = false;      // over all factors of all terms
     bool has_bspline = false;      // ... a B-spline Gibbs kernel among them: the batched launchers take the kernels with that branch
+    bool has_on_dim = false;       // ... a Gibbs factor on one coordinate of num_dim > 1 (GPT_KERNEL_ON_DIM): likewise
+    int gibbs_form() const { return (has_bspline ? GPT_GFORM_BSPLINE : 0) | (has_on_dim ? GPT_GFORM_ON_DIM : 0); }      // what those launchers take
     const KParams *second(int t) const { return f2[t].kernel_id >= 0 ? &f2[t] : nullptr; }
 };
 
 // Training points against ONE term k1 (* k2 where k2 >= 0); n_maxsum: the largest row sum of their derivative orders
-// (gpt_set_data).  A Gibbs factor takes orders <= 1 (1-D: the largest order IS n_maxsum); a pair of training points meets
+// (gpt_set_data), gibbs_max1 / gibbs_max2: the largest order in the coordinate a Gibbs factor acts on (train_gibbs_max).  A Gibbs
+// factor takes orders <= 1 there (1-D: the largest order IS n_maxsum); a pair of training points meets
 // 2 n_maxsum in a RationalQuadratic / Matern factor, and in EITHER factor of a product (the SUM of both points' orders).  A lone
 // SE or Matern52 term has no limit here (Matern52's own rule is the Python host's).
-static int check_train_orders(int k1, int k2, long n_maxsum)
+static int check_train_orders(int k1, int k2, long n_maxsum, long gibbs_max1, long gibbs_max2)
 {
-    if ((gibbs_kid(k1) || gibbs_kid(k2)) && n_maxsum > 1) {
+    if ((gibbs_kid(k1) && gibbs_max1 > 1) || (gibbs_kid(k2) && gibbs_max2 > 1)) {
         gpt_set_error("%s", GIBBS_ORDER_MSG);
         return GPT_E_NOTIMPL;
     }
@@ -329,35 +360,51 @@ static int check_train_orders(int k1, int k2, long n_maxsum)
 // the product ids[t] * ids2[t], the first nparams1[t] of its nparams[t] parameters the first factor's.  Term by term: ids, the
 // training points' orders (check_train_orders), the parameter split, the parameters (make_kparams) -- the first refusal in that
 // order is the call's status.  *m is overwritten whether or not the call succeeds: callers that keep a model parse into a local.
-static int parse_model(int D, long n_maxsum, int nterms, const int *ids, const int *ids2, const double *params, const int *nparams,
+// the largest training order a Gibbs id meets: of its coordinate for a GPT_KERNEL_ON_DIM id inside num_dim, else of any row sum (num_dim 1:
+// the same number; a plain Gibbs id at num_dim > 1 is refused by make_kparams after the order check, as it always was)
+static long train_gibbs_max(int abi_id, int D, long n_maxsum, const long *n_colmax)
+{
+    const int d = GPT_KERNEL_DIM_OF(abi_id);
+    return (d >= 0 && d < D) ? n_colmax[d] : n_maxsum;
+}
+
+// n_colmax[d]: the largest training order of coordinate d (gpt_set_data)
+static int parse_model(int D, long n_maxsum, const long *n_colmax, int nterms, const int *ids, const int *ids2, const double *params, const int *nparams,
                        const int *nparams1, ModelKernel *m)
 {
     if (nterms < 1 || nterms > GPT_MAX_TERMS || !ids || !params || !nparams || (ids2 && !nparams1)) return GPT_E_ARG;
     m->nterms = nterms;
-    m->any_prod = m->has_m52 = m->has_chain = m->has_gibbs = m->has_bspline = false;      // (the factors beyond nterms stay as they are: never read, zero in a fresh model)
+    m->any_prod = m->has_m52 = m->has_chain = m->has_gibbs = m->has_bspline = m->has_on_dim = false;      // (the factors beyond nterms stay as they are: never read, zero in a fresh model)
     const double *p = params;
     for (int t = 0; t < nterms; t++) {
-        const int k1 = ids[t], k2 = (ids2 && ids2[t] >= 0) ? ids2[t] : -1;
+        // (plain ids from here on; the coordinate of a GPT_KERNEL_ON_DIM id goes to make_kparams with the id as the ABI gave it)
+        const int k1 = GPT_KERNEL_BASE_ID(ids[t]), k2 = (ids2 && ids2[t] >= 0) ? GPT_KERNEL_BASE_ID(ids2[t]) : -1;
         const bool prod = k2 >= 0;
+        if (!prod && GPT_KERNEL_DIM_OF(ids[t]) >= 0) {
+            gpt_set_error("gpt_fit: term %d: a Gibbs kernel on one coordinate is a product factor (its own term: times SE [1, inf ..])", t);
+            return GPT_E_ARG;
+        }
         if (!native_fit_kernel(k1) || (prod && !native_fit_kernel(k2))) {
             gpt_set_error("gpt_fit: kernel ids must be SE, Matern52, RationalQuadratic, Matern or Gibbs");
             return GPT_E_ARG;
         }
-        GPT_TRY(check_train_orders(k1, k2, n_maxsum));
+        GPT_TRY(check_train_orders(k1, k2, n_maxsum, train_gibbs_max(ids[t], D, n_maxsum, n_colmax),
+                                   prod ? train_gibbs_max(ids2[t], D, n_maxsum, n_colmax) : 0));
         const int n1 = prod ? nparams1[t] : nparams[t];
         if (n1 < 1 || (prod && n1 >= nparams[t])) {
             gpt_set_error("gpt_fit: term %d: %d parameters, %d of them the first factor's", t, nparams[t], n1);
             return GPT_E_ARG;
         }
-        GPT_TRY(make_kparams(k1, p, n1, D, -1, 1, nullptr, &m->f1[t]));
+        GPT_TRY(make_kparams(ids[t], p, n1, D, -1, 1, nullptr, &m->f1[t], prod));
         m->f2[t] = KParams();
         m->f2[t].kernel_id = -1;
-        if (prod) GPT_TRY(make_kparams(k2, p + n1, nparams[t] - n1, D, -1, 1, nullptr, &m->f2[t]));
+        if (prod) GPT_TRY(make_kparams(ids2[t], p + n1, nparams[t] - n1, D, -1, 1, nullptr, &m->f2[t], true));
         m->any_prod = m->any_prod || prod;
         m->has_m52 = m->has_m52 || k1 == GPT_KERNEL_M52 || k2 == GPT_KERNEL_M52;
         m->has_chain = m->has_chain || is_chain(k1) || is_chain(k2);
         m->has_gibbs = m->has_gibbs || gibbs_kid(k1) || gibbs_kid(k2);
         m->has_bspline = m->has_bspline || k1 == GPT_KERNEL_GIBBS_BSPLINE || k2 == GPT_KERNEL_GIBBS_BSPLINE;
+        m->has_on_dim = m->has_on_dim || (D > 1 && (gibbs_kid(k1) || gibbs_kid(k2)));
         p += nparams[t];
     }
     m->nparams = (int)(p - params);
@@ -370,7 +417,11 @@ static int parse_model(int D, long n_maxsum, int nterms, const int *ids, const i
 static int check_test_orders(const ModelKernel &m, long n_maxsum, bool warp, const int32_t *nstar, int64_t M, int D)
 {
     if (m.has_m52) GPT_TRY(check_m52_orders(nstar, M, D));
-    if (m.has_gibbs) GPT_TRY(check_gibbs_orders(nstar, M, D));
+    if (m.has_gibbs)
+        for (int t = 0; t < m.nterms; t++) {
+            if (gibbs_kid(m.f1[t].kernel_id)) GPT_TRY(check_gibbs_orders(nstar, M, D, m.f1[t].g_dim));
+            if (m.second(t) && gibbs_kid(m.f2[t].kernel_id)) GPT_TRY(check_gibbs_orders(nstar, M, D, m.f2[t].g_dim));
+        }
     if (m.has_chain || m.any_prod) {
         long ms = 0;
         for (int64_t i = 0; i < M; i++) {
@@ -389,7 +440,7 @@ static int check_test_orders(const ModelKernel &m, long n_maxsum, bool warp, con
 
 // A free-standing pair list (`pairwise`: row i of ni meets row i of nj, M == P) or Gram block (every row meets every column) of
 // k1, or of the product k1 * k2 where k2 != NULL: in a product either factor meets the combined order of a pair, and Leibniz
-// hands a Gibbs / Matern52 factor at most the points' own orders.
+// hands a Gibbs / Matern52 factor at most the points' own orders (a Gibbs factor: those of its own coordinate).
 static int check_pair_orders(const KParams &k1, const KParams *k2, const int32_t *ni, int64_t M, const int32_t *nj, int64_t P, int D,
                              bool pairwise)
 {
@@ -399,9 +450,10 @@ static int check_pair_orders(const KParams &k1, const KParams *k2, const int32_t
         GPT_TRY(check_m52_orders(nj, P, D));
     }
     if (is_chain(id1) || k2) GPT_TRY(check_rq_orders(ni, M, nj, P, D, pairwise));
-    if (gibbs_kid(id1) || gibbs_kid(id2)) {
-        GPT_TRY(check_gibbs_orders(ni, M, D));
-        GPT_TRY(check_gibbs_orders(nj, P, D));
-    }
+    for (const KParams *k : {&k1, k2})
+        if (k && gibbs_kid(k->kernel_id)) {
+            GPT_TRY(check_gibbs_orders(ni, M, D, k->g_dim));
+            GPT_TRY(check_gibbs_orders(nj, P, D, k->g_dim));
+        }
     return GPT_OK;
 }

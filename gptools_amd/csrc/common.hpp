@@ -64,12 +64,15 @@ struct KParams {
     int m_nint;               // round(nu)
     int m_isint;              // nu is an integer (the reference then averages nu -+ 0.001 near the origin)
     int zero_l;               // some length scale is exactly 0 (1 / l = inf): the squared-exponential pair function then applies the
-    int pad_;                 //   reference's 0/0 -> 0 rule per dimension (core.py:416); otherwise it is one multiply
+    int inf_l;                //   reference's 0/0 -> 0 rule per dimension (core.py:416); otherwise it is one multiply
+                              // inf_l (MaternKernel only: set and read for no other kernel): some length scale is +inf (1 / l = 0: a
+                              //   masked-out dimension, gpt_hip.h) -- the Matern pair function then returns 0.0 for an order in such a dimension in front of its r = 0 classes
     double m_gampl, m_gammi, m_gam1, m_gam2;      // Temme's 1/Gamma(1 +- mu) and their combinations
     double m_g[2], m_gm[2], m_nus[2];             // Gamma(nu_s), Gamma(-nu_s), nu_s for the small-y series (nu_s = nu, or nu -+ 0.001)
     // Gibbs kernels (1-D): l(x) = g_c + sum_q g_amp[q] tanh((x - g_x0[q]) / g_w[q]) over g_nt terms (1: tanh warp, 2: double tanh)
     double g_amp[2], g_w[2], g_x0[2], g_c;
-    int g_nt, g_pad_;      // (exp-Gauss: g_nt = the number of Gaussians; B-spline: the number of knots)
+    int g_nt, g_dim;       // (exp-Gauss: g_nt = the number of Gaussians; B-spline: the number of knots); g_dim: the coordinate the
+                           // kernel acts on (GPT_KERNEL_ON_DIM, num_dim 2 .. GPT_GIBBS_ON_DIM_MAX_D; 0 for a plain id)
 };
 
 static_assert(3 * GPT_GIBBS_MAX_GAUSS + 1 <= 3 * GPT_MAX_DIM, "g_raw must fit the arrays it shares its place with");
@@ -99,6 +102,11 @@ __host__ __device__ constexpr bool gibbs_more_kid(int kid)
 // (kbuild_batch.hip) -- which the launchers take only for a model that holds a B-spline (ModelKernel::has_bspline); GPT_KERNEL_PRODUCT,
 // GPT_KID_PRODUCT_GM and the batched kernels of every other model are the code they were
 #define GPT_KID_PRODUCT_GB 107
+// what the launchers are told about the Gibbs kernels of a model or a product (their `gform` argument; ModelKernel::gibbs_form(),
+// gibbs_form_of): GPT_GFORM_BSPLINE, a B-spline among them; GPT_GFORM_ON_DIM, a Gibbs factor on one coordinate of num_dim > 1
+// (GPT_KERNEL_ON_DIM, gpt_hip.h)
+#define GPT_GFORM_BSPLINE 1
+#define GPT_GFORM_ON_DIM 2
 
 // A cross-stream edge without an event: the kernel that completes a piece of work raises a 32-bit word in device
 // memory when its LAST workgroup is through (its results written with write-through stores and drained first) and the
@@ -219,20 +227,20 @@ int launch_trsm_panel(hipStream_t st, int64_t m, const double *L, int64_t ldl, c
 int launch_kbuild_batch(hipStream_t st, int kernel_id, int D, const KParams *d_kps, const double *d_noise_var, int64_t nbatch,
                         const double *dX, const int32_t *dn, int64_t N, const double *d_err_y, double diag_add, double *dK,
                         int64_t ldk, int64_t bstride, int accumulate = 0, int full = 0, const KParams *d_kps2 = nullptr,
-                        int64_t xstride = 0, const double *dS = nullptr, int64_t sstride = 0, int bspline = 0);
+                        int64_t xstride = 0, const double *dS = nullptr, int64_t sstride = 0, int gform = 0);
                         // dS != NULL: a warped batch -- element z's (warped) points at dX + z * xstride, its slopes at dS + z * sstride
 int launch_batch_pad(hipStream_t st, const double *h_y, int64_t nbatch, double *A, int64_t lda, int64_t bstride, int64_t n_valid,
                      int64_t n_pad, double big, int32_t *info);
 // the predictive half of a resident batch (gpt_predict_batch)
 int launch_kbuild_batch_cross(hipStream_t st, int kernel_id, int D, const KParams *d_kps, const double *d_nv, int64_t nbatch,
                               const double *dXi, const int32_t *dni, int64_t M, const double *dXj, const int32_t *dnj, int64_t P, double *dK,
-                              int64_t ldk, int64_t bstride, int accumulate = 0, const KParams *d_kps2 = nullptr, int bspline = 0);
-                              // bspline (here and below): the model holds a B-spline Gibbs kernel -- the kernels with that branch
+                              int64_t ldk, int64_t bstride, int accumulate = 0, const KParams *d_kps2 = nullptr, int gform = 0);
+                              // gform (here and below): ModelKernel::gibbs_form(), GPT_GFORM_* bits -- the kernels with those branches
 int launch_kdiag_batch(hipStream_t st, int D, int nterms, const KParams *d_kps, const KParams *d_kps2, int64_t nbatch, const double *dX,
-                       const int32_t *dn, int64_t M, double *dout, int64_t ldo, int bspline = 0);
+                       const int32_t *dn, int64_t M, double *dout, int64_t ldo, int gform = 0);
 int launch_kss_sum(hipStream_t st, int D, int nterms, const KParams *d_kps, const KParams *d_kps2, int64_t nbatch, const int32_t *d_keep,
                    const double *dX, const int32_t *dn, int64_t M, int64_t MP, const int32_t *d_hit, double noise_sum, double *dC,
-                   int64_t ldc, int bspline = 0);
+                   int64_t ldc, int gform = 0);
 int launch_batch_meanvar(hipStream_t st, int64_t M, int64_t MP, int64_t N, int64_t NP, int64_t nbatch, double *V, int64_t ldv,
                          const double *A, int64_t bs, const int32_t *keep, double *mean, double *var, int64_t ld);
 int launch_batch_logdet_dot(hipStream_t st, const double *A, int64_t lda, int64_t bstride, int64_t n, int64_t nbatch,

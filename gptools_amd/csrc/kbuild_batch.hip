@@ -10,15 +10,17 @@
 
 // One term of every element: kernel_id, or (d_kps2 != NULL) a product term, whose factors' ids the kernel reads from the elements'
 // KParams at run time.  `who` names the launcher in a refusal.
-// bspline: the model holds a B-spline Gibbs kernel (ModelKernel::has_bspline) -- a product term then takes GPT_KID_PRODUCT_GB.
-static int kbuild_batch_dispatch(const char *who, hipStream_t st, int kernel_id, int D, const KBuildArgs &a, const KBatchArgs &b, int bspline)
+// gform: ModelKernel::gibbs_form() -- GPT_GFORM_BSPLINE: the model holds a B-spline Gibbs kernel, a product term then takes GPT_KID_PRODUCT_GB;
+// GPT_GFORM_ON_DIM: it holds a Gibbs factor on one coordinate of num_dim > 1, a product term then takes the GM / GB form
+// of that num_dim (product_kid).
+static int kbuild_batch_dispatch(const char *who, hipStream_t st, int kernel_id, int D, const KBuildArgs &a, const KBatchArgs &b, int gform)
 {
     const KParams dummy = KParams();
     auto for_kid = [&](auto k) {
         constexpr int KID = decltype(k)::value;
-        return dispatch_dim<kid_max_dim(KID)>(who, D, [&](auto d) { return kbuild_launch<KID, decltype(d)::value, true>(st, dummy, dummy, a, b); });
+        return dispatch_dim<kid_max_dim(KID)>(who, D, [&](auto d) { return kbuild_launch<KID, decltype(d)::value, true>(st, dummy, dummy, a, b); }, kid_dim_rule(KID));
     };
-    if (b.kps2 != nullptr) return dispatch_kid(ProductKids(), product_kid(D, bspline ? GPT_KERNEL_GIBBS_BSPLINE : -1, -1, true), for_kid, [] { return GPT_E_ARG; });
+    if (b.kps2 != nullptr) return dispatch_kid(ProductKids(), product_kid(D, gform, false, true), for_kid, [] { return GPT_E_ARG; });
     return dispatch_kid(FitKids(), kernel_id, for_kid, [&] {
         gpt_set_error("%s: kernel_id %d is not a fit kernel", who, kernel_id);
         return GPT_E_ARG;
@@ -31,12 +33,12 @@ static int kbuild_batch_dispatch(const char *who, hipStream_t st, int kernel_id,
 int launch_kbuild_batch(hipStream_t st, int kernel_id, int D, const KParams *d_kps, const double *d_noise_var, int64_t nbatch,
                         const double *dX, const int32_t *dn, int64_t N, const double *d_err_y, double diag_add, double *dK,
                         int64_t ldk, int64_t bstride, int accumulate, int full, const KParams *d_kps2, int64_t xstride,
-                        const double *dS, int64_t sstride, int bspline)
+                        const double *dS, int64_t sstride, int gform)
 {
     if (N <= 0 || nbatch <= 0) return GPT_OK;
     const KBuildArgs a = {dX, dn, N, dX, dn, N, full ? 0 : 1, 0, 0, d_err_y, 0.0, diag_add, dK, ldk, accumulate, dS, dS};
     const KBatchArgs b = {d_kps, d_noise_var, nbatch, bstride, d_kps2, xstride, sstride};
-    return kbuild_batch_dispatch("kbuild_batch", st, kernel_id, D, a, b, bspline);
+    return kbuild_batch_dispatch("kbuild_batch", st, kernel_id, D, a, b, gform);
 }
 
 // ---- the predictive half of a resident batch (gpt_predict_batch, api_batch.inc) ----------------------------------------
@@ -46,7 +48,7 @@ int launch_kbuild_batch(hipStream_t st, int kernel_id, int D, const KParams *d_k
 // (d_nv: the elements' noise variances -- the batched kernel reads its element's entry, though without err_y nothing uses it)
 int launch_kbuild_batch_cross(hipStream_t st, int kernel_id, int D, const KParams *d_kps, const double *d_nv, int64_t nbatch,
                               const double *dXi, const int32_t *dni, int64_t M, const double *dXj, const int32_t *dnj, int64_t P, double *dK,
-                              int64_t ldk, int64_t bstride, int accumulate, const KParams *d_kps2, int bspline)
+                              int64_t ldk, int64_t bstride, int accumulate, const KParams *d_kps2, int gform)
 {
     if (M <= 0 || P <= 0 || nbatch <= 0) return GPT_OK;
     if (!d_kps || !d_nv) {
@@ -55,25 +57,27 @@ int launch_kbuild_batch_cross(hipStream_t st, int kernel_id, int D, const KParam
     }
     const KBuildArgs a = {dXi, dni, M, dXj, dnj, P, 0, 0, 0, nullptr, 0.0, 0.0, dK, ldk, accumulate};
     const KBatchArgs b = {d_kps, d_nv, nbatch, bstride, d_kps2};
-    return kbuild_batch_dispatch("kbuild_batch_cross", st, kernel_id, D, a, b, bspline);
+    return kbuild_batch_dispatch("kbuild_batch_cross", st, kernel_id, D, a, b, gform);
 }
 
 // One term of element b's kernel at a pair, kernels chosen at run time (the two kernels below loop over terms AND elements,
 // whose ids only the KParams carry): the same pair functions as the builder, so the same numbers.
-// GB: with the B-spline branch (GPT_KID_PRODUCT_GB's form; 1-D models that hold a B-spline kernel only)
-template <int D, bool GB = false>
+// GB: with the B-spline branch (GPT_KID_PRODUCT_GB's form; models that hold a B-spline kernel only)
+// GM: with the Gibbs branches of GPT_KID_PRODUCT_GM -- every 1-D model, and at num_dim 2 .. GPT_GIBBS_ON_DIM_MAX_D the models with a
+// Gibbs factor on one coordinate (instantiations of their own: the kernels of every other model at those num_dim are the code they were)
+template <int D, bool GB = false, bool GM = (D == 1)>
 __device__ __forceinline__ double batch_term_pair(const KParams *__restrict__ kps, const KParams *__restrict__ kps2, int64_t idx,
                                                   const double *xi, const double *xj, const int *ni, const int *nj)
 {
     // (D == 1: with the bucket / exp-Gauss Gibbs branches, GPT_KID_PRODUCT_GM's form; otherwise the functions the builders share)
-    if (kps2 != nullptr && kps2[idx].kernel_id >= 0) return prod_pair<D, D == 1, GB>(kps[idx], kps2[idx], xi, xj, ni, nj);
-    return factor_pair<D, D == 1, GB>(kps[idx], xi, xj, ni, nj);
+    if (kps2 != nullptr && kps2[idx].kernel_id >= 0) return prod_pair<D, GM, GB>(kps[idx], kps2[idx], xi, xj, ni, nj);
+    return factor_pair<D, GM, GB>(kps[idx], xi, xj, ni, nj);
 }
 
 // diag K**_b: out[b * ldo + a] = k_b((x_a, n_a), (x_a, n_a)), terms summed in order (as gpt_predict's pair launches do)
 // (GB, here and in kss_sum_kernel: the form for a 1-D model that holds a B-spline kernel; a flag of the kernel itself, not a shared
 // body behind two kernels -- through a wrapper the pointers lose __restrict__ and the code of every num_dim changes)
-template <int D, bool GB = false>
+template <int D, bool GB = false, bool GM = (D == 1)>
 __global__ __launch_bounds__(256) void kdiag_batch_kernel(int nterms, const KParams *__restrict__ kps, const KParams *__restrict__ kps2,
                                                           int64_t nbatch, const double *__restrict__ X, const int32_t *__restrict__ n,
                                                           int64_t M, double *__restrict__ out, int64_t ldo)
@@ -89,7 +93,7 @@ __global__ __launch_bounds__(256) void kdiag_batch_kernel(int nterms, const KPar
     }
     double v = 0.0;
     for (int t = 0; t < nterms; t++) {
-        const double p = batch_term_pair<D, GB>(kps, kps2, (int64_t)t * nbatch + b, x, x, na, na);
+        const double p = batch_term_pair<D, GB, GM>(kps, kps2, (int64_t)t * nbatch + b, x, x, na, na);
         v = t > 0 ? v + p : p;
     }
     out[b * ldo + a] = v;
@@ -97,7 +101,7 @@ __global__ __launch_bounds__(256) void kdiag_batch_kernel(int nterms, const KPar
 
 // Lower triangle of  C = sum over kept elements b of K**_b  (+ noise_sum on the diagonal of the rows hit[a] != 0): ONE pass over
 // the M x M triangle with the elements' KParams looped inside, 16 x 16 entries per workgroup; rows / columns in [M, MP) get 0.
-template <int D, bool GB = false>
+template <int D, bool GB = false, bool GM = (D == 1)>
 __global__ __launch_bounds__(256) void kss_sum_kernel(int nterms, const KParams *__restrict__ kps, const KParams *__restrict__ kps2,
                                                       int64_t nbatch, const int32_t *__restrict__ keep, const double *__restrict__ X,
                                                       const int32_t *__restrict__ n, int64_t M, int64_t MP, const int32_t *__restrict__ hit,
@@ -121,7 +125,7 @@ __global__ __launch_bounds__(256) void kss_sum_kernel(int nterms, const KParams 
             if (!keep[b]) continue;
             double kb = 0.0;
             for (int t = 0; t < nterms; t++) {
-                const double p = batch_term_pair<D, GB>(kps, kps2, (int64_t)t * nbatch + b, xa, xc, na, nc);
+                const double p = batch_term_pair<D, GB, GM>(kps, kps2, (int64_t)t * nbatch + b, xa, xc, na, nc);
                 kb = t > 0 ? kb + p : p;
             }
             v += kb;
@@ -131,12 +135,31 @@ __global__ __launch_bounds__(256) void kss_sum_kernel(int nterms, const KParams 
     C[a * ldc + cc] = v;
 }
 
-// bspline: the model holds a B-spline Gibbs kernel (1-D by the parser's rule): the kernel with that branch
+// gform: ModelKernel::gibbs_form() (see kbuild_batch_dispatch): the kernel with the B-spline branch at num_dim 1, the kernels
+// with the on-coordinate Gibbs branches at num_dim 2 .. GPT_GIBBS_ON_DIM_MAX_D
+// f(D, GB) for the on-coordinate forms
+template <class F>
+static int dispatch_on_dim(const char *who, int D, int gform, F &&f)
+{
+    return dispatch_dim<GPT_GIBBS_ON_DIM_MAX_D>(who, D, [&](auto d) {
+        constexpr int DD = decltype(d)::value;
+        if constexpr (DD == 1) return GPT_E_ARG;      // (never: the callers come here with num_dim > 1)
+        else return (gform & GPT_GFORM_BSPLINE) ? f(d, std::true_type()) : f(d, std::false_type());
+    }, kid_dim_rule(GPT_KID_PRODUCT_GM));
+}
+
 int launch_kdiag_batch(hipStream_t st, int D, int nterms, const KParams *d_kps, const KParams *d_kps2, int64_t nbatch, const double *dX,
-                       const int32_t *dn, int64_t M, double *dout, int64_t ldo, int bspline)
+                       const int32_t *dn, int64_t M, double *dout, int64_t ldo, int gform)
 {
     if (M <= 0 || nbatch <= 0) return GPT_OK;
-    if (bspline && D == 1) {
+    if ((gform & GPT_GFORM_ON_DIM) && D > 1)
+        return dispatch_on_dim("kdiag_batch", D, gform, [&](auto d, auto gb) {
+            hipLaunchKernelGGL((kdiag_batch_kernel<decltype(d)::value, decltype(gb)::value, true>), dim3((unsigned)((M + 255) / 256), (unsigned)nbatch),
+                               dim3(256), 0, st, nterms, d_kps, d_kps2, nbatch, dX, dn, M, dout, ldo);
+            GPT_LAUNCH_CHECK();
+            return GPT_OK;
+        });
+    if ((gform & GPT_GFORM_BSPLINE) && D == 1) {
         hipLaunchKernelGGL((kdiag_batch_kernel<1, true>), dim3((unsigned)((M + 255) / 256), (unsigned)nbatch), dim3(256), 0, st, nterms, d_kps,
                            d_kps2, nbatch, dX, dn, M, dout, ldo);
         GPT_LAUNCH_CHECK();
@@ -152,11 +175,18 @@ int launch_kdiag_batch(hipStream_t st, int D, int nterms, const KParams *d_kps, 
 
 int launch_kss_sum(hipStream_t st, int D, int nterms, const KParams *d_kps, const KParams *d_kps2, int64_t nbatch, const int32_t *d_keep,
                    const double *dX, const int32_t *dn, int64_t M, int64_t MP, const int32_t *d_hit, double noise_sum, double *dC,
-                   int64_t ldc, int bspline)
+                   int64_t ldc, int gform)
 {
     if (MP <= 0) return GPT_OK;
     const unsigned nt = (unsigned)((MP + 15) / 16);
-    if (bspline && D == 1) {
+    if ((gform & GPT_GFORM_ON_DIM) && D > 1)
+        return dispatch_on_dim("kss_sum", D, gform, [&](auto d, auto gb) {
+            hipLaunchKernelGGL((kss_sum_kernel<decltype(d)::value, decltype(gb)::value, true>), dim3(nt, nt), dim3(256), 0, st, nterms, d_kps,
+                               d_kps2, nbatch, d_keep, dX, dn, M, MP, d_hit, noise_sum, dC, ldc);
+            GPT_LAUNCH_CHECK();
+            return GPT_OK;
+        });
+    if ((gform & GPT_GFORM_BSPLINE) && D == 1) {
         hipLaunchKernelGGL((kss_sum_kernel<1, true>), dim3(nt, nt), dim3(256), 0, st, nterms, d_kps, d_kps2, nbatch, d_keep, dX, dn, M, MP,
                            d_hit, noise_sum, dC, ldc);
         GPT_LAUNCH_CHECK();

@@ -262,14 +262,36 @@ using ProductKids = KidList<GPT_KERNEL_PRODUCT, GPT_KID_PRODUCT_GM, GPT_KID_PROD
 // stays the code it was, for the products of the older kernels); the batched ones, whose factor ids only the device sees, take it
 // for every 1-D product.  GPT_KID_PRODUCT_GB adds the B-spline branch and is taken, single-matrix or batched, only when a factor
 // is a B-spline (batched: the caller says so, `id1` = GPT_KERNEL_GIBBS_BSPLINE).  Why: common.hpp, at GPT_KID_PRODUCT_GM.
-inline int product_kid(int D, int id1, int id2, bool batched)
+// At num_dim 2 .. GPT_GIBBS_ON_DIM_MAX_D a Gibbs factor acts on ONE coordinate (GPT_KERNEL_ON_DIM; make_kparams admits no other
+// Gibbs factor there): GPT_KID_PRODUCT_GM, the tanh warps included, or GPT_KID_PRODUCT_GB with a B-spline -- instantiations of their
+// own, so GPT_KERNEL_PRODUCT at those num_dim stays the code it was for every product without a Gibbs factor.
+// gform: the GPT_GFORM_* bits of the factors (gibbs_form_of; batched: of the whole model, ModelKernel::gibbs_form());
+// gibbs_more: a factor is a bucket / exp-Gauss kernel (single-matrix launchers at num_dim 1 only).
+inline int gibbs_form_of(int D, int id1, int id2)
 {
-    if (D == 1 && (id1 == GPT_KERNEL_GIBBS_BSPLINE || id2 == GPT_KERNEL_GIBBS_BSPLINE)) return GPT_KID_PRODUCT_GB;
-    return D == 1 && (batched || gibbs_more_kid(id1) || gibbs_more_kid(id2)) ? GPT_KID_PRODUCT_GM : GPT_KERNEL_PRODUCT;
+    return ((id1 == GPT_KERNEL_GIBBS_BSPLINE || id2 == GPT_KERNEL_GIBBS_BSPLINE) ? GPT_GFORM_BSPLINE : 0) |
+           ((D > 1 && (gibbs_kid(id1) || gibbs_kid(id2))) ? GPT_GFORM_ON_DIM : 0);
+}
+inline int product_kid(int D, int gform, bool gibbs_more, bool batched)
+{
+    const bool bs = (gform & GPT_GFORM_BSPLINE) != 0;
+    if (D > 1) return !(gform & GPT_GFORM_ON_DIM) ? GPT_KERNEL_PRODUCT : bs ? GPT_KID_PRODUCT_GB : GPT_KID_PRODUCT_GM;
+    if (bs) return GPT_KID_PRODUCT_GB;
+    return batched || gibbs_more ? GPT_KID_PRODUCT_GM : GPT_KERNEL_PRODUCT;
 }
 
-constexpr int kid_max_dim(int kid) { return gibbs_kid(kid) || kid == GPT_KID_PRODUCT_GM || kid == GPT_KID_PRODUCT_GB ? 1 : GPT_MAX_DIM; }
+constexpr int kid_max_dim(int kid)
+{
+    return gibbs_kid(kid) ? 1 : kid == GPT_KID_PRODUCT_GM || kid == GPT_KID_PRODUCT_GB ? GPT_GIBBS_ON_DIM_MAX_D : GPT_MAX_DIM;
+}
 // (the WARP instantiations exist for these only: the noise kernels are never warped)
+// what dispatch_dim says when num_dim is beyond kid_max_dim(kid) (NULL: its general message)
+static_assert(GPT_GIBBS_ON_DIM_MAX_D == 3, "the message below names the number");
+constexpr const char *kid_dim_rule(int kid)
+{
+    return gibbs_kid(kid) ? "the Gibbs kernels need num_dim 1"
+                          : kid == GPT_KID_PRODUCT_GM || kid == GPT_KID_PRODUCT_GB ? "a Gibbs factor needs num_dim <= 3" : nullptr;
+}
 constexpr bool kid_can_warp(int kid) { return kid != GPT_KERNEL_DIAGNOISE && kid != GPT_KERNEL_ZERO; }
 
 // f(std::integral_constant<int, KID>()) for the entry of the list that equals `kid`, else refuse() -- the launcher's own message
@@ -288,13 +310,14 @@ bool dispatch_dim_fold(int D, F &f, int &rc, std::integer_sequence<int, I...>)
     return ((D == I + 1 && (rc = f(std::integral_constant<int, I + 1>()), true)) || ...);
 }
 
-// f(std::integral_constant<int, D>()) for D in 1 .. MAXD (kid_max_dim); `who` names the launcher in the refusal
+// f(std::integral_constant<int, D>()) for D in 1 .. MAXD (kid_max_dim); `who` names the launcher in the refusal, `rule` (the
+// caller's, kid_dim_rule) says why MAXD is what it is
 template <int MAXD, class F>
-int dispatch_dim(const char *who, int D, F &&f)
+int dispatch_dim(const char *who, int D, F &&f, const char *rule = nullptr)
 {
     int rc = GPT_OK;
     if (dispatch_dim_fold(D, f, rc, std::make_integer_sequence<int, MAXD>())) return rc;
-    if (MAXD == 1) gpt_set_error("%s: the Gibbs kernels need num_dim 1, got %d", who, D);
+    if (rule) gpt_set_error("%s: %s, got %d", who, rule, D);
     else gpt_set_error("%s: unsupported num_dim %d (max %d)", who, D, MAXD);
     return GPT_E_ARG;
 }
@@ -365,7 +388,7 @@ int kbuild_dispatch(LIST list, int kid, hipStream_t st, const KParams &kp, const
             gpt_set_error("kbuild: warp slopes given for kernel_id %d", kp.kernel_id);
             return GPT_E_ARG;
         }
-        return dispatch_dim<kid_max_dim(KID)>("kbuild", kp.D, [&](auto d) { return kbuild_launch<KID, decltype(d)::value, false>(st, kp, kp2, a); });
+        return dispatch_dim<kid_max_dim(KID)>("kbuild", kp.D, [&](auto d) { return kbuild_launch<KID, decltype(d)::value, false>(st, kp, kp2, a); }, kid_dim_rule(KID));
     }, [&] {
         gpt_set_error("kbuild: unknown kernel_id %d", kid);
         return GPT_E_ARG;
@@ -389,7 +412,7 @@ int kpairs_dispatch(LIST list, int kid, hipStream_t st, const KParams &kp, const
                                a.ni, a.nj, a.M, a.out, a.accumulate, kp2);
             GPT_LAUNCH_CHECK();
             return GPT_OK;
-        });
+        }, kid_dim_rule(KID));
     }, [&] {
         gpt_set_error("kpairs: unknown kernel_id %d", kid);
         return GPT_E_ARG;

@@ -6,10 +6,10 @@
 
 int kbuild_prod(hipStream_t st, const KParams &kp1, const KParams &kp2, const KBuildArgs &a)
 {
-    return kbuild_dispatch(ProductKids(), product_kid(kp1.D, kp1.kernel_id, kp2.kernel_id, false), st, kp1, kp2, a);
+    return kbuild_dispatch(ProductKids(), product_kid(kp1.D, gibbs_form_of(kp1.D, kp1.kernel_id, kp2.kernel_id), gibbs_more_kid(kp1.kernel_id) || gibbs_more_kid(kp2.kernel_id), false), st, kp1, kp2, a);
 }
 
 int kpairs_prod(hipStream_t st, const KParams &kp1, const KParams &kp2, const KPairsArgs &a)
 {
-    return kpairs_dispatch(ProductKids(), product_kid(kp1.D, kp1.kernel_id, kp2.kernel_id, false), st, kp1, kp2, a);
+    return kpairs_dispatch(ProductKids(), product_kid(kp1.D, gibbs_form_of(kp1.D, kp1.kernel_id, kp2.kernel_id), gibbs_more_kid(kp1.kernel_id) || gibbs_more_kid(kp2.kernel_id), false), st, kp1, kp2, a);
 }

@@ -453,6 +453,15 @@ __device__ __forceinline__ double matern_pair(const KParams &kp, const double *x
         njtot += nj[d];
     }
     const double y = 2.0 * nu * r2;
+    // A masked-out dimension (1 / l = 0, gpt_hip.h): an order there makes the pair exactly 0.0.  Away from r = 0 the chain rule below
+    // gets there by itself (y1 = y2 = 0); the r = 0 classes would answer NaN (the term-by-term masking) or 0 * inf for small nu.
+    // Wave-uniform flag from the host (make_kparams), as zero_l is for the squared exponential.
+    if (kp.inf_l && ntot != 0) {
+        bool out = false;
+#pragma unroll
+        for (int d = 0; d < D; d++) out = out || (kp.inv_l[d] == 0.0 && (ni[d] | nj[d]) != 0);
+        if (out) return 0.0;
+    }
     if (ntot == 0) {                                          // matern.py:322-325
         if (r2 == 0.0) return s2;
         const double z = sqrt(y);
@@ -732,13 +741,44 @@ __device__ __forceinline__ double any_pair(const KParams &kp, const double *xi, 
 // GM: the bucket / exp-Gauss Gibbs ids are compiled in (GPT_KID_PRODUCT_GM, common.hpp; 1-D only); GB: the B-spline id as well
 // (GPT_KID_PRODUCT_GB: only the kernels the launchers choose for a model WITH a B-spline factor; every other instantiation is
 // the code it was)
+// A 1-D Gibbs kernel on coordinate kp.g_dim of D = 2 .. GPT_GIBBS_ON_DIM_MAX_D (GPT_KERNEL_ON_DIM, gpt_hip.h; MaskedKernel, ref:
+// kernel/core.py:1128-1147): the factor from that coordinate of the two points and its orders, exactly 0.0 when any other coordinate
+// carries an order.  The coordinate is chosen by compares over the unrolled dimensions (the points stay in registers); g_dim is the
+// same for every lane.  BS: the factor is the B-spline kernel (the out-of-line call, as at num_dim 1).
+template <int D, bool BS>
+__device__ __forceinline__ double gibbs_pair_on_dim(const KParams &kp, const double *xi, const double *xj, const int *ni, const int *nj)
+{
+    double a = 0.0, b = 0.0;
+    int na = 0, nb = 0, other = 0;
+#pragma unroll
+    for (int d = 0; d < D; d++) {
+        if (d == kp.g_dim) {
+            a = xi[d];
+            b = xj[d];
+            na = ni[d];
+            nb = nj[d];
+        } else {
+            other |= ni[d] | nj[d];
+        }
+    }
+    if (other != 0) return 0.0;
+    if constexpr (BS) return gibbs_pair_bspline(&kp, a, b, na, nb);
+    return gibbs_pair(kp, &a, &b, &na, &nb);
+}
+
+// (GM / GB at D = 2 .. GPT_GIBBS_ON_DIM_MAX_D: the products with a Gibbs factor ON ONE COORDINATE, every Gibbs id of the form's set
+// through gibbs_pair_on_dim -- instantiations that did not exist before; without GM the switch at D > 1 is the code it was)
 template <int D, bool GM = false, bool GB = false>
 __device__ __forceinline__ double factor_pair(const KParams &kp, const double *xi, const double *xj, const int *ni, const int *nj)
 {
+    constexpr bool ON_DIM = GM && D > 1 && D <= GPT_GIBBS_ON_DIM_MAX_D;
     // (in front of the switch, not a case of it: without GB the switch is the parent's, jump table and all; with its id: the
     // zero-length-scale rule, gibbs_h_other)
     if constexpr (GB && D == 1) {
         if (kp.kernel_id == GPT_KERNEL_GIBBS_BSPLINE) return gibbs_pair_bspline(&kp, xi[0], xj[0], ni[0], nj[0]);
+    }
+    if constexpr (GB && ON_DIM) {
+        if (kp.kernel_id == GPT_KERNEL_GIBBS_BSPLINE) return gibbs_pair_on_dim<D, true>(kp, xi, xj, ni, nj);
     }
     switch (kp.kernel_id) {
     case GPT_KERNEL_SE: return se_pair<D>(kp, xi, xj, ni, nj);
@@ -746,10 +786,13 @@ __device__ __forceinline__ double factor_pair(const KParams &kp, const double *x
     case GPT_KERNEL_RQ: return rq_pair<D>(kp, xi, xj, ni, nj);
     case GPT_KERNEL_MATERN: return matern_pair<D>(kp, xi, xj, ni, nj);
     case GPT_KERNEL_GIBBS_TANH:
-    case GPT_KERNEL_GIBBS_DTANH: return gibbs_pair(kp, xi, xj, ni, nj);      // (1-D: the host admits no other D, and orders <= 1)
+    case GPT_KERNEL_GIBBS_DTANH:
+        if constexpr (ON_DIM) return gibbs_pair_on_dim<D, false>(kp, xi, xj, ni, nj);
+        return gibbs_pair(kp, xi, xj, ni, nj);      // (1-D: the host admits no other D without a coordinate, and orders <= 1)
     case GPT_KERNEL_GIBBS_CUBIC:
     case GPT_KERNEL_GIBBS_QUINTIC:
     case GPT_KERNEL_GIBBS_EXPGAUSS:
+        if constexpr (ON_DIM) return gibbs_pair_on_dim<D, false>(kp, xi, xj, ni, nj);
         if constexpr (GM && D == 1) return gibbs_pair(kp, xi, xj, ni, nj);
         return 0.0;
     default: return 0.0;

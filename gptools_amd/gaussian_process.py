@@ -28,7 +28,8 @@ import scipy.optimize
 from . import _lib, _ingest
 from . import replicas
 from .error_handling import GPArgumentError, GPImpossibleParamsError
-from .kernel import Kernel, ZeroKernel, DiagonalNoiseKernel, SumKernel, ProductKernel
+from .kernel import Kernel, ZeroKernel, DiagonalNoiseKernel, BinaryKernel, SumKernel, ProductKernel
+from .kernel.masked import MaskedKernel
 from .kernel.warping import WarpedKernel, beta_cdf_warp, linear_warp
 from .utils import CombinedBounds
 
@@ -132,6 +133,8 @@ class GaussianProcess(object):
             return False
         terms = self._native_terms()
         if terms is None or len(terms) != 1 or terms[0][0] in _GIBBS:     # (the multi-GPU engines have no Gibbs builder)
+            return False
+        if self._has_masked():                # (... and know nothing of the masked encoding: a masked model is not partitioned)
             return False
         import torch.distributed as dist
         return dist.is_available() and dist.is_initialized()
@@ -312,6 +315,14 @@ class GaussianProcess(object):
             Xj_ = None if Xj is None else np.atleast_2d(np.asarray(Xj, dtype=float))
             nj_ = None if Xj is None else np.atleast_2d(np.asarray(nj, dtype=int))
             return self._plain_ctx().kbuild2(nat[0], nat[1], nat[2], nat[3], Xi, ni, Xj_, nj_)
+        if type(k) is MaskedKernel and hyper_deriv is None and k._native_term() is not None:
+            # a masked kernel on its device route (kernel/masked.py): the builder, like the native kernel it is encoded as
+            nat = k._native_term()
+            Xj_ = None if Xj is None else np.atleast_2d(np.asarray(Xj, dtype=float))
+            nj_ = None if Xj is None else np.atleast_2d(np.asarray(nj, dtype=int))
+            if len(nat) == 4:
+                return self._plain_ctx().kbuild2(nat[0], nat[1], nat[2], nat[3], Xi, ni, Xj_, nj_)
+            return self._plain_ctx().kbuild(nat[0], nat[1], Xi, ni, Xj_, nj_)
         symmetric = Xj is None
         if symmetric:
             Xj, nj = Xi, ni
@@ -388,7 +399,21 @@ class GaussianProcess(object):
             # k1 * k2 of two native kernels: one PRODUCT term of the fused builder (ref: gptools/kernel/core.py:587-671)
             nat = k._native_factors()
             return None if nat is None else [nat]
+        if type(k) is MaskedKernel:
+            # (by type, never through a forwarded attribute) a stationary kernel with infinite length scales outside its mask, or
+            # a Gibbs kernel on one dimension times the unit factor (kernel/masked.py); None: the host route
+            nat = k._native_term()
+            return None if nat is None else [nat]
         return None
+
+    def _has_masked(self, k=None):
+        """A ``MaskedKernel`` anywhere in the covariance kernel's tree."""
+        k = self.k if k is None else k
+        if isinstance(k, MaskedKernel):
+            return True
+        if isinstance(k, BinaryKernel):
+            return self._has_masked(k.k1) or self._has_masked(k.k2)
+        return isinstance(k, WarpedKernel) and self._has_masked(k.k)
 
     def _device_model(self):
         """``(terms, layers)`` when the library evaluates the whole covariance kernel itself, else ``None``: ``terms`` as
@@ -506,7 +531,9 @@ class GaussianProcess(object):
             return 0.5 * (alpha.dot(dK.dot(alpha)) - np.trace(W2))
 
         ll_deriv = np.zeros(len(self.free_params))
-        terms = self._native_terms() if self._fit_mode == "kernel" else None
+        # (a masked term: gpt_ll_grad indexes the DEVICE parameter arrays, which the masked encoding expands -- the
+        # per-parameter host branch below, every dK through compute_Kij)
+        terms = self._native_terms() if self._fit_mode == "kernel" and not self._has_masked() else None
         knk = self.k
         free_idx = np.arange(0, len(knk.params), dtype=int)[~np.asarray(knk.fixed_params, dtype=bool)]
         tix = lix = None

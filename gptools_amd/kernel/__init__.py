@@ -6,3 +6,4 @@ from .noise import *           # noqa: F401,F403
 from .rational_quadratic import *   # noqa: F401,F403
 from .gibbs import *           # noqa: F401,F403
 from .warping import *         # noqa: F401,F403
+from .masked import *          # noqa: F401,F403

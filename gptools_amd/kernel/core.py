@@ -157,7 +157,8 @@ class ProductKernel(BinaryKernel):
     is the general Leibniz rule, ``sum_a prod_slots C(n, a) * k1^(a) * k2^(n - a)`` -- the same sum with each distinct
     term evaluated once.  With two native factors (SE, Matern52, RationalQuadratic, Matern, the native Gibbs kernels) that sum
     runs per pair on the device (``GPT_KERNEL_PRODUCT``: ``gpt_kpairs2`` here, the fused builder in ``GaussianProcess``); otherwise both
-    factors are evaluated through their own ``__call__`` and combined on the host."""
+    factors are evaluated through their own ``__call__`` and combined on the host.  A ``MaskedKernel`` factor on its device route
+    (masked.py) is a native factor."""
 
     def _native_factors(self):
         """``(kernel_id1, params1, kernel_id2, params2)`` when both factors are kernels the HIP library evaluates itself
@@ -167,8 +168,17 @@ class ProductKernel(BinaryKernel):
         ok = (_lib.KERNEL_SE, _lib.KERNEL_M52, _lib.KERNEL_RQ, _lib.KERNEL_MATERN, _lib.KERNEL_GIBBS_TANH,
               _lib.KERNEL_GIBBS_DTANH, _lib.KERNEL_GIBBS_CUBIC, _lib.KERNEL_GIBBS_QUINTIC, _lib.KERNEL_GIBBS_EXPGAUSS,
               _lib.KERNEL_GIBBS_BSPLINE)
+        from .masked import MaskedKernel
         f = []
         for k in (self.k1, self.k2):
+            if type(k) is MaskedKernel:
+                # (by type: a stationary kernel with infinite length scales outside its mask, or a Gibbs id that carries its
+                # dimension -- masked.py; None: the masked kernel is evaluated on the host)
+                nat = k._native_factor()
+                if nat is None:
+                    return None
+                f += list(nat)
+                continue
             kid = getattr(k, "_gpt_kernel_id", None)
             # (a subclass that overrides __call__ is a Python-defined kernel, whatever id it inherited)
             if kid not in ok or type(k).__call__ not in (Kernel.__call__, Matern52Kernel.__call__):

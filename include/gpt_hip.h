@@ -95,6 +95,29 @@ extern "C" {
                                   * increasing order!", before anything is launched */
 #define GPT_GIBBS_MAX_KNOTS 11   /* most knots of GPT_KERNEL_GIBBS_BSPLINE */
 
+/* MaskedKernel (ref: kernel/core.py:1011-1149): a kernel that acts on a subset of the num_dim coordinates and is exactly 0.0 for a
+ * pair with a derivative order in any other coordinate.
+ *   - A masked SE / Matern52 / RationalQuadratic / Matern kernel has no id of its own.  It IS the kernel at num_dim whose
+ *     masked-out coordinates have the length scale +infinity in the parameter array (1/l = 1/l^2 = 0 exactly): the distance ignores
+ *     those coordinates and every derivative order in them multiplies the pair by zero -- 0.0, never NaN or inf, coincident points
+ *     included (the Matern pair function guards its r = 0 classes behind a flag make_kparams raises for an infinite length scale).
+ *     The hyper-parameter indices of such an array are the expanded array's, not the base kernel's: gpt_ll_grad is not offered.
+ *   - A 1-D Gibbs kernel on coordinate d of a num_dim <= GPT_GIBBS_ON_DIM_MAX_D model: kernel id GPT_KERNEL_ON_DIM(id, d) with the
+ *     parameters of the plain id.  Accepted wherever a PRODUCT FACTOR is (gpt_kpairs2, gpt_kbuild2, kernel_ids / kernel_ids2 of
+ *     gpt_fit_terms and gpt_fit_batch_terms): the factor is evaluated from coordinate d of the two points and that coordinate's
+ *     orders, and is 0.0 when any other coordinate carries an order.  A masked Gibbs kernel on its own is its product with the
+ *     constant unit factor SE [1, inf .. inf].  The plain ids keep their meaning: num_dim 1, and a Gibbs id WITHOUT a coordinate
+ *     at num_dim > 1 is refused as before; d >= num_dim, a non-Gibbs id, num_dim > GPT_GIBBS_ON_DIM_MAX_D or a use outside a product
+ *     (gpt_kpairs, gpt_kbuild, gpt_fit, gpt_fit_sum, a term of gpt_fit_terms without a second factor; at num_dim 1 too) is
+ *     GPT_E_ARG.  The Gibbs order rule (orders <= 1, GPT_E_NOTIMPL beyond) applies to coordinate d alone -- training points, test
+ *     points and pair lists alike: n = [1, 1] or [0, 2] with the Gibbs factor on coordinate 0 is a first / no derivative for it,
+ *     the rest belongs to the other factor and to that factor's own rules; the cap on the summed orders of a pair in a product
+ *     (GPT_RQ_MAXORD) and the Matern52 rule (a point's orders sum to <= 1) keep looking at whole rows. */
+#define GPT_GIBBS_ON_DIM_MAX_D 3
+#define GPT_KERNEL_ON_DIM(id, d) ((id) + 256 * ((d) + 1))
+#define GPT_KERNEL_BASE_ID(kid) ((kid) >= 256 ? (kid) % 256 : (kid))      /* the plain id of either form */
+#define GPT_KERNEL_DIM_OF(kid) ((kid) >= 256 ? (kid) / 256 - 1 : -1)      /* the coordinate, -1 for a plain id */
+
 #define GPT_MAX_DIM 16      /* largest supported num_dim */
 #define GPT_WARP_LINEAR 1    /* input warp layer w = (x - a)/(b - a) per dimension (ref: kernel/warping.py:367-402) */
 #define GPT_WARP_BETA 2      /* input warp layer w = I_x(alpha, beta), the beta CDF, per dimension (ref: kernel/warping.py:315-365) */
