@@ -20,6 +20,8 @@ KERNEL_GIBBS_TANH, KERNEL_GIBBS_DTANH, KERNEL_GIBBS_CUBIC, KERNEL_GIBBS_QUINTIC,
 KERNEL_GIBBS_BSPLINE = 12
 GIBBS_MAX_GAUSS = 8      # GPT_GIBBS_MAX_GAUSS: most Gaussians of KERNEL_GIBBS_EXPGAUSS
 GIBBS_MAX_KNOTS = 11     # GPT_GIBBS_MAX_KNOTS: most knots of KERNEL_GIBBS_BSPLINE
+KERNEL_GIBBS_GP = 13
+GIBBS_MAX_GP_POINTS = 12 # GPT_GIBBS_MAX_GP_POINTS: most points of KERNEL_GIBBS_GP
 GIBBS_ON_DIM_MAX_D = 3   # GPT_GIBBS_ON_DIM_MAX_D: largest num_dim at which a Gibbs kernel id may carry the dimension it acts on
 KERNEL_ON_DIM_STRIDE = 256
 

@@ -220,6 +220,31 @@ static int make_kparams(int kernel_id, const double *params, int nparams, int D,
         kp->sigma = params[0];
         kp->g_nt = nt;
         for (int q = 1; q < nparams; q++) kp->g_raw[q - 1] = params[q];
+    } else if (kernel_id == GPT_KERNEL_GIBBS_GP) {
+        // GibbsKernel1dGP with a nested 1-D squared-exponential kernel, [sigma_f, l, x_1 .. x_m, c_1 .. c_m] (ref: gibbs.py:995-1095): the
+        // c_j are the nested GP's weights, solved for by the caller (gpt_hip.h); m = (nparams - 2) / 2.  As they are to the device
+        if (D != 1 && on_dim < 0) {
+            gpt_set_error("Gibbs kernel only supports 1d data.");
+            return GPT_E_ARG;
+        }
+        const int m = (nparams - 2) / 2;
+        if (nparams < 4 || (nparams - 2) % 2 != 0) {
+            gpt_set_error("kernel %d expects 2 m + 2 params (1 <= m <= GPT_GIBBS_MAX_GP_POINTS = %d points), got %d", kernel_id,
+                          GPT_GIBBS_MAX_GP_POINTS, nparams);
+            return GPT_E_ARG;
+        }
+        if (m > GPT_GIBBS_MAX_GP_POINTS) {
+            gpt_set_error("kernel %d: %d points, the device kernel takes GPT_GIBBS_MAX_GP_POINTS = %d at most", kernel_id, m,
+                          GPT_GIBBS_MAX_GP_POINTS);
+            return GPT_E_ARG;
+        }
+        if (hyper_deriv >= 0) {
+            gpt_set_error("Hyperparameter derivatives have not been implemented!");      // ref: gibbs.py:319-322
+            return GPT_E_NOTIMPL;
+        }
+        kp->sigma = params[0];
+        kp->g_nt = m;
+        for (int q = 1; q < nparams; q++) kp->g_raw[q - 1] = params[q];
     } else if (kernel_id == GPT_KERNEL_DIAGNOISE || kernel_id == GPT_KERNEL_ZERO) {
         if (nparams != 1) {
             gpt_set_error("noise kernels expect 1 param, got %d", nparams);
@@ -331,9 +356,9 @@ struct ModelKernel {
     int nparams = 0;                               // doubles one parameter set takes in the ABI's flat array (all terms, both factors)
     KParams f1[GPT_MAX_TERMS] = {}, f2[GPT_MAX_TERMS] = {};      // f2[t].kernel_id < 0: term t is not a product; zero beyond nterms
     bool any_prod = false, has_m52 = false, has_chain = false, has_gibbs = false;      // over all factors of all terms
-    bool has_bspline = false;      // ... a B-spline Gibbs kernel among them: the batched launchers take the kernels with that branch
+    bool has_gb = false;      // ... a B-spline or nested-GP Gibbs kernel among them (gibbs_gb_kid): the batched launchers take the kernels with those branches
     bool has_on_dim = false;       // ... a Gibbs factor on one coordinate of num_dim > 1 (GPT_KERNEL_ON_DIM): likewise
-    int gibbs_form() const { return (has_bspline ? GPT_GFORM_BSPLINE : 0) | (has_on_dim ? GPT_GFORM_ON_DIM : 0); }      // what those launchers take
+    int gibbs_form() const { return (has_gb ? GPT_GFORM_GB : 0) | (has_on_dim ? GPT_GFORM_ON_DIM : 0); }      // what those launchers take
     const KParams *second(int t) const { return f2[t].kernel_id >= 0 ? &f2[t] : nullptr; }
 };
 
@@ -374,7 +399,7 @@ static int parse_model(int D, long n_maxsum, const long *n_colmax, int nterms, c
 {
     if (nterms < 1 || nterms > GPT_MAX_TERMS || !ids || !params || !nparams || (ids2 && !nparams1)) return GPT_E_ARG;
     m->nterms = nterms;
-    m->any_prod = m->has_m52 = m->has_chain = m->has_gibbs = m->has_bspline = m->has_on_dim = false;      // (the factors beyond nterms stay as they are: never read, zero in a fresh model)
+    m->any_prod = m->has_m52 = m->has_chain = m->has_gibbs = m->has_gb = m->has_on_dim = false;      // (the factors beyond nterms stay as they are: never read, zero in a fresh model)
     const double *p = params;
     for (int t = 0; t < nterms; t++) {
         // (plain ids from here on; the coordinate of a GPT_KERNEL_ON_DIM id goes to make_kparams with the id as the ABI gave it)
@@ -403,7 +428,7 @@ static int parse_model(int D, long n_maxsum, const long *n_colmax, int nterms, c
         m->has_m52 = m->has_m52 || k1 == GPT_KERNEL_M52 || k2 == GPT_KERNEL_M52;
         m->has_chain = m->has_chain || is_chain(k1) || is_chain(k2);
         m->has_gibbs = m->has_gibbs || gibbs_kid(k1) || gibbs_kid(k2);
-        m->has_bspline = m->has_bspline || k1 == GPT_KERNEL_GIBBS_BSPLINE || k2 == GPT_KERNEL_GIBBS_BSPLINE;
+        m->has_gb = m->has_gb || gibbs_gb_kid(k1) || gibbs_gb_kid(k2);
         m->has_on_dim = m->has_on_dim || (D > 1 && (gibbs_kid(k1) || gibbs_kid(k2)));
         p += nparams[t];
     }

@@ -52,7 +52,7 @@ struct KParams {
             double inv_l[GPT_MAX_DIM];  // 1 / l
             double inv_var[GPT_MAX_DIM];// 1 / l^2
         };
-        // bucket, exp-Gauss and B-spline Gibbs kernels (1-D, no length scales of the kind above): the parameters after sigma_f as the ABI
+        // bucket, exp-Gauss, B-spline and nested-GP Gibbs kernels (1-D, no length scales of the kind above): the parameters after sigma_f as the ABI
         // hands them over (gibbs_lfunc.hpp reads them raw).  In the place of the three arrays, so that sizeof(KParams) is what it
         // was: the product kernels keep both factors' KParams on the stack and pay for every byte in scratch
         double g_raw[3 * GPT_GIBBS_MAX_GAUSS + 1];
@@ -71,19 +71,21 @@ struct KParams {
     double m_g[2], m_gm[2], m_nus[2];             // Gamma(nu_s), Gamma(-nu_s), nu_s for the small-y series (nu_s = nu, or nu -+ 0.001)
     // Gibbs kernels (1-D): l(x) = g_c + sum_q g_amp[q] tanh((x - g_x0[q]) / g_w[q]) over g_nt terms (1: tanh warp, 2: double tanh)
     double g_amp[2], g_w[2], g_x0[2], g_c;
-    int g_nt, g_dim;       // (exp-Gauss: g_nt = the number of Gaussians; B-spline: the number of knots); g_dim: the coordinate the
+    int g_nt, g_dim;       // (exp-Gauss: g_nt = the number of Gaussians; B-spline: the number of knots; nested GP: of points); g_dim: the coordinate the
                            // kernel acts on (GPT_KERNEL_ON_DIM, num_dim 2 .. GPT_GIBBS_ON_DIM_MAX_D; 0 for a plain id)
 };
 
 static_assert(3 * GPT_GIBBS_MAX_GAUSS + 1 <= 3 * GPT_MAX_DIM, "g_raw must fit the arrays it shares its place with");
 static_assert(2 * GPT_GIBBS_MAX_KNOTS + 2 <= 3 * GPT_GIBBS_MAX_GAUSS + 1, "the B-spline's knots and coefficients must fit g_raw");
+static_assert(2 * GPT_GIBBS_MAX_GP_POINTS + 1 <= 3 * GPT_GIBBS_MAX_GAUSS + 1, "the nested GP's length scale, points and weights must fit g_raw");
 static_assert(sizeof(KParams) == 656, "KParams travels by value in the kernel arguments (two per product term)");
 
-// the Gibbs kernels (1-D, derivative orders <= 1): the tanh warps, the buckets, the exponential of Gaussians, the B-spline
+// the Gibbs kernels (1-D, derivative orders <= 1): the tanh warps, the buckets, the exponential of Gaussians, the B-spline, the nested GP
 __host__ __device__ constexpr bool gibbs_kid(int kid)
 {
     return kid == GPT_KERNEL_GIBBS_TANH || kid == GPT_KERNEL_GIBBS_DTANH || kid == GPT_KERNEL_GIBBS_CUBIC ||
-           kid == GPT_KERNEL_GIBBS_QUINTIC || kid == GPT_KERNEL_GIBBS_EXPGAUSS || kid == GPT_KERNEL_GIBBS_BSPLINE;
+           kid == GPT_KERNEL_GIBBS_QUINTIC || kid == GPT_KERNEL_GIBBS_EXPGAUSS || kid == GPT_KERNEL_GIBBS_BSPLINE ||
+           kid == GPT_KERNEL_GIBBS_GP;
 }
 
 // ... those of them added after the tanh warps (kernel ids 9-11), and the builder's INTERNAL id of a product with such a factor
@@ -99,13 +101,21 @@ __host__ __device__ constexpr bool gibbs_more_kid(int kid)
 #define GPT_KID_PRODUCT_GM 106
 // ... and a product with a B-spline factor (id 12): the spline costs registers again, in the batched kernels too, so it has an
 // instantiation of its own everywhere -- the builders' GPT_KID_PRODUCT_GB, the B-spline forms of kdiag_batch / kss_sum
-// (kbuild_batch.hip) -- which the launchers take only for a model that holds a B-spline (ModelKernel::has_bspline); GPT_KERNEL_PRODUCT,
+// (kbuild_batch.hip) -- which the launchers take only for a model that holds a kernel of these forms (ModelKernel::has_gb, gibbs_gb_kid below); GPT_KERNEL_PRODUCT,
 // GPT_KID_PRODUCT_GM and the batched kernels of every other model are the code they were
 #define GPT_KID_PRODUCT_GB 107
+// The nested-GP kernel (id 13) rides with the B-spline: compiled into GPT_KID_PRODUCT_GM and kss_sum / kdiag_batch<1> it took their
+// scratch from 736 to 1488 bytes and the single-matrix GM product from 512 to 256 VGPRs at 2080 bytes (profiles/gibbs_gp_resource_usage.txt),
+// in kernels every 1-D model runs; as a second out-of-line call in front of the GB forms' switch every kernel keeps its record.
+// GPT_GFORM_GB says "a kernel of the GB forms among them".
+__host__ __device__ constexpr bool gibbs_gb_kid(int kid)
+{
+    return kid == GPT_KERNEL_GIBBS_BSPLINE || kid == GPT_KERNEL_GIBBS_GP;
+}
 // what the launchers are told about the Gibbs kernels of a model or a product (their `gform` argument; ModelKernel::gibbs_form(),
-// gibbs_form_of): GPT_GFORM_BSPLINE, a B-spline among them; GPT_GFORM_ON_DIM, a Gibbs factor on one coordinate of num_dim > 1
+// gibbs_form_of): GPT_GFORM_GB, a kernel of the GB forms -- a B-spline or a nested GP, gibbs_gb_kid -- among them; GPT_GFORM_ON_DIM, a Gibbs factor on one coordinate of num_dim > 1
 // (GPT_KERNEL_ON_DIM, gpt_hip.h)
-#define GPT_GFORM_BSPLINE 1
+#define GPT_GFORM_GB 1
 #define GPT_GFORM_ON_DIM 2
 
 // A cross-stream edge without an event: the kernel that completes a piece of work raises a 32-bit word in device

@@ -1,6 +1,6 @@
-// gibbs_lfunc.hpp -- the closed-form length-scale functions l(x), l'(x) of the bucket, exp-Gauss and B-spline Gibbs kernels
-// (GPT_KERNEL_GIBBS_CUBIC / _QUINTIC / _EXPGAUSS / _BSPLINE, include/gpt_hip.h; ref: gptools/kernel/gibbs.py:603-651, :695-760,
-// :804-855, :905-992),
+// gibbs_lfunc.hpp -- the closed-form length-scale functions l(x), l'(x) of the bucket, exp-Gauss, B-spline and nested-GP Gibbs kernels
+// (GPT_KERNEL_GIBBS_CUBIC / _QUINTIC / _EXPGAUSS / _BSPLINE / _GP, include/gpt_hip.h; ref: gptools/kernel/gibbs.py:603-651, :695-760,
+// :804-855, :905-992, :995-1095),
 // from the raw parameters after sigma_f.  The functions are __host__ __device__ and need nothing of HIP, so that the ordinary
 // host compiler can build them into a test aid (test_aids/gibbs_host.cpp) and a CPU-only test can compare them with the numpy
 // functions of gptools_amd/kernel/gibbs.py.  kpair.hpp (gibbs_point) calls them once per point, never per pair.
@@ -167,4 +167,24 @@ GPT_HD static inline void gpt_gibbs_bspline(const double *p, int nt, double x, d
     }
     *l = ((N[0] * c[0] + N[1] * c[1]) + N[2] * c[2]) + N[3] * c[3];
     *dl = (M[0] * (c[1] - c[0]) + M[1] * (c[2] - c[1])) + M[2] * (c[3] - c[2]);
+}
+
+// Nested-GP length scale (GPT_KERNEL_GIBBS_GP; ref: gptools/kernel/gibbs.py:995-1095; the numpy statement is GPWarp in
+// gptools_amd/kernel/gibbs.py).  p = [l, x_1 .. x_m, c_1 .. c_m], 1 <= m <= GPT_GIBBS_MAX_GP_POINTS: the mean of a noiseless GP with a
+// squared-exponential kernel of length scale l through the points, whose weights c the host has solved for (gpt_hip.h) --
+// S1 = sum_j c_j exp(-(x - x_j)^2 / (2 l^2)), S2 = sum_j c_j exp(..) (x - x_j) / l^2, terms added in index order as the numpy
+// statement adds them;  l(x) = S1,  l'(x) = -S2.  One exponential per term serves both.  ONE uniform loop over m: every index
+// into p is the same in all lanes (the rule of the B-spline above), so the by-value KParams stays on scalar loads.
+GPT_HD static inline void gpt_gibbs_gp(const double *p, int m, double x, double *l, double *dl)
+{
+    const double s = p[0];
+    double S1 = 0.0, S2 = 0.0;
+    for (int j = 0; j < m; j++) {
+        const double d = x - p[1 + j], c = p[1 + m + j];
+        const double term = c * exp(-(d * d) / (2.0 * (s * s)));
+        S1 += term;
+        S2 += term * d / (s * s);
+    }
+    *l = S1;
+    *dl = -S2;
 }

@@ -10,7 +10,7 @@
 
 // One term of every element: kernel_id, or (d_kps2 != NULL) a product term, whose factors' ids the kernel reads from the elements'
 // KParams at run time.  `who` names the launcher in a refusal.
-// gform: ModelKernel::gibbs_form() -- GPT_GFORM_BSPLINE: the model holds a B-spline Gibbs kernel, a product term then takes GPT_KID_PRODUCT_GB;
+// gform: ModelKernel::gibbs_form() -- GPT_GFORM_GB: the model holds a B-spline or nested-GP Gibbs kernel, a product term then takes GPT_KID_PRODUCT_GB;
 // GPT_GFORM_ON_DIM: it holds a Gibbs factor on one coordinate of num_dim > 1, a product term then takes the GM / GB form
 // of that num_dim (product_kid).
 static int kbuild_batch_dispatch(const char *who, hipStream_t st, int kernel_id, int D, const KBuildArgs &a, const KBatchArgs &b, int gform)
@@ -62,7 +62,7 @@ int launch_kbuild_batch_cross(hipStream_t st, int kernel_id, int D, const KParam
 
 // One term of element b's kernel at a pair, kernels chosen at run time (the two kernels below loop over terms AND elements,
 // whose ids only the KParams carry): the same pair functions as the builder, so the same numbers.
-// GB: with the B-spline branch (GPT_KID_PRODUCT_GB's form; models that hold a B-spline kernel only)
+// GB: with the B-spline and nested-GP branches (GPT_KID_PRODUCT_GB's form; models that hold such a kernel only)
 // GM: with the Gibbs branches of GPT_KID_PRODUCT_GM -- every 1-D model, and at num_dim 2 .. GPT_GIBBS_ON_DIM_MAX_D the models with a
 // Gibbs factor on one coordinate (instantiations of their own: the kernels of every other model at those num_dim are the code they were)
 template <int D, bool GB = false, bool GM = (D == 1)>
@@ -75,7 +75,7 @@ __device__ __forceinline__ double batch_term_pair(const KParams *__restrict__ kp
 }
 
 // diag K**_b: out[b * ldo + a] = k_b((x_a, n_a), (x_a, n_a)), terms summed in order (as gpt_predict's pair launches do)
-// (GB, here and in kss_sum_kernel: the form for a 1-D model that holds a B-spline kernel; a flag of the kernel itself, not a shared
+// (GB, here and in kss_sum_kernel: the form for a 1-D model that holds a B-spline or nested-GP kernel; a flag of the kernel itself, not a shared
 // body behind two kernels -- through a wrapper the pointers lose __restrict__ and the code of every num_dim changes)
 template <int D, bool GB = false, bool GM = (D == 1)>
 __global__ __launch_bounds__(256) void kdiag_batch_kernel(int nterms, const KParams *__restrict__ kps, const KParams *__restrict__ kps2,
@@ -144,7 +144,7 @@ static int dispatch_on_dim(const char *who, int D, int gform, F &&f)
     return dispatch_dim<GPT_GIBBS_ON_DIM_MAX_D>(who, D, [&](auto d) {
         constexpr int DD = decltype(d)::value;
         if constexpr (DD == 1) return GPT_E_ARG;      // (never: the callers come here with num_dim > 1)
-        else return (gform & GPT_GFORM_BSPLINE) ? f(d, std::true_type()) : f(d, std::false_type());
+        else return (gform & GPT_GFORM_GB) ? f(d, std::true_type()) : f(d, std::false_type());
     }, kid_dim_rule(GPT_KID_PRODUCT_GM));
 }
 
@@ -159,7 +159,7 @@ int launch_kdiag_batch(hipStream_t st, int D, int nterms, const KParams *d_kps, 
             GPT_LAUNCH_CHECK();
             return GPT_OK;
         });
-    if ((gform & GPT_GFORM_BSPLINE) && D == 1) {
+    if ((gform & GPT_GFORM_GB) && D == 1) {
         hipLaunchKernelGGL((kdiag_batch_kernel<1, true>), dim3((unsigned)((M + 255) / 256), (unsigned)nbatch), dim3(256), 0, st, nterms, d_kps,
                            d_kps2, nbatch, dX, dn, M, dout, ldo);
         GPT_LAUNCH_CHECK();
@@ -186,7 +186,7 @@ int launch_kss_sum(hipStream_t st, int D, int nterms, const KParams *d_kps, cons
             GPT_LAUNCH_CHECK();
             return GPT_OK;
         });
-    if ((gform & GPT_GFORM_BSPLINE) && D == 1) {
+    if ((gform & GPT_GFORM_GB) && D == 1) {
         hipLaunchKernelGGL((kss_sum_kernel<1, true>), dim3(nt, nt), dim3(256), 0, st, nterms, d_kps, d_kps2, nbatch, d_keep, dX, dn, M, MP,
                            d_hit, noise_sum, dC, ldc);
         GPT_LAUNCH_CHECK();

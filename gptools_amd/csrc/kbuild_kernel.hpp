@@ -251,7 +251,7 @@ struct KidList {
 };
 // the kernels a model term can be (native_fit_kernel, api_kparams.inc): what the batched builders take
 using FitKids = KidList<GPT_KERNEL_SE, GPT_KERNEL_M52, GPT_KERNEL_RQ, GPT_KERNEL_MATERN, GPT_KERNEL_GIBBS_TANH, GPT_KERNEL_GIBBS_DTANH,
-                        GPT_KERNEL_GIBBS_CUBIC, GPT_KERNEL_GIBBS_QUINTIC, GPT_KERNEL_GIBBS_EXPGAUSS, GPT_KERNEL_GIBBS_BSPLINE>;
+                        GPT_KERNEL_GIBBS_CUBIC, GPT_KERNEL_GIBBS_QUINTIC, GPT_KERNEL_GIBBS_EXPGAUSS, GPT_KERNEL_GIBBS_BSPLINE, GPT_KERNEL_GIBBS_GP>;
 // ... and the noise kernels: the single-matrix builder and the pair list
 using AllKids = FitKids::plus<GPT_KERNEL_DIAGNOISE, GPT_KERNEL_ZERO>;
 // the builders' product instantiations (product_kid chooses)
@@ -260,23 +260,23 @@ using ProductKids = KidList<GPT_KERNEL_PRODUCT, GPT_KID_PRODUCT_GM, GPT_KID_PROD
 // The product of the factors id1 * id2 at num_dim D: GPT_KID_PRODUCT_GM carries the bucket / exp-Gauss Gibbs branches and exists
 // at num_dim 1 only.  The single-matrix kernels take it only when a factor needs those branches (GPT_KERNEL_PRODUCT at num_dim 1
 // stays the code it was, for the products of the older kernels); the batched ones, whose factor ids only the device sees, take it
-// for every 1-D product.  GPT_KID_PRODUCT_GB adds the B-spline branch and is taken, single-matrix or batched, only when a factor
-// is a B-spline (batched: the caller says so, `id1` = GPT_KERNEL_GIBBS_BSPLINE).  Why: common.hpp, at GPT_KID_PRODUCT_GM.
+// for every 1-D product.  GPT_KID_PRODUCT_GB adds the B-spline and nested-GP branches and is taken, single-matrix or batched, only when a factor
+// is one of those two (gibbs_gb_kid; batched: the caller says so, GPT_GFORM_GB).  Why: common.hpp, at GPT_KID_PRODUCT_GM.
 // At num_dim 2 .. GPT_GIBBS_ON_DIM_MAX_D a Gibbs factor acts on ONE coordinate (GPT_KERNEL_ON_DIM; make_kparams admits no other
-// Gibbs factor there): GPT_KID_PRODUCT_GM, the tanh warps included, or GPT_KID_PRODUCT_GB with a B-spline -- instantiations of their
+// Gibbs factor there): GPT_KID_PRODUCT_GM, the tanh warps included, or GPT_KID_PRODUCT_GB with a B-spline or nested GP -- instantiations of their
 // own, so GPT_KERNEL_PRODUCT at those num_dim stays the code it was for every product without a Gibbs factor.
 // gform: the GPT_GFORM_* bits of the factors (gibbs_form_of; batched: of the whole model, ModelKernel::gibbs_form());
 // gibbs_more: a factor is a bucket / exp-Gauss kernel (single-matrix launchers at num_dim 1 only).
 inline int gibbs_form_of(int D, int id1, int id2)
 {
-    return ((id1 == GPT_KERNEL_GIBBS_BSPLINE || id2 == GPT_KERNEL_GIBBS_BSPLINE) ? GPT_GFORM_BSPLINE : 0) |
+    return ((gibbs_gb_kid(id1) || gibbs_gb_kid(id2)) ? GPT_GFORM_GB : 0) |
            ((D > 1 && (gibbs_kid(id1) || gibbs_kid(id2))) ? GPT_GFORM_ON_DIM : 0);
 }
 inline int product_kid(int D, int gform, bool gibbs_more, bool batched)
 {
-    const bool bs = (gform & GPT_GFORM_BSPLINE) != 0;
-    if (D > 1) return !(gform & GPT_GFORM_ON_DIM) ? GPT_KERNEL_PRODUCT : bs ? GPT_KID_PRODUCT_GB : GPT_KID_PRODUCT_GM;
-    if (bs) return GPT_KID_PRODUCT_GB;
+    const bool gb = (gform & GPT_GFORM_GB) != 0;
+    if (D > 1) return !(gform & GPT_GFORM_ON_DIM) ? GPT_KERNEL_PRODUCT : gb ? GPT_KID_PRODUCT_GB : GPT_KID_PRODUCT_GM;
+    if (gb) return GPT_KID_PRODUCT_GB;
     return batched || gibbs_more ? GPT_KID_PRODUCT_GM : GPT_KERNEL_PRODUCT;
 }
 

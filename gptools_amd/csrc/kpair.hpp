@@ -630,7 +630,7 @@ __device__ __forceinline__ GibbsPt gibbs_pt(double l, double dl)
 // instantiations are the code they were), -1 where only kp carries it (product factors, the batched pair kernels: per pair,
 // as for the tanh warps there).  The tanh warps: l(x) = c + sum_q amp_q tanh((x - x0_q) / w_q) and l'(x) = sum_q amp_q / w_q
 // cosh((x - x0_q) / w_q)^-2 in the reference's order of operations (gibbs.py:459-464, :552-556); cosh overflows to inf beyond
-// |u| = 710 and the slope is then 0, as there.  The buckets, the exponential of Gaussians and the B-spline: gibbs_lfunc.hpp.
+// |u| = 710 and the slope is then 0, as there.  The buckets, the exponential of Gaussians, the B-spline and the nested GP: gibbs_lfunc.hpp.
 template <int KID = -1>
 __device__ __forceinline__ GibbsPt gibbs_point(const KParams &kp, double x)
 {
@@ -650,6 +650,10 @@ __device__ __forceinline__ GibbsPt gibbs_point(const KParams &kp, double x)
     }
     if (kid == GPT_KERNEL_GIBBS_BSPLINE) {
         gpt_gibbs_bspline(kp.g_raw, kp.g_nt, x, &l, &dl);
+        return gibbs_pt(l, dl);
+    }
+    if (kid == GPT_KERNEL_GIBBS_GP) {
+        gpt_gibbs_gp(kp.g_raw, kp.g_nt, x, &l, &dl);
         return gibbs_pt(l, dl);
     }
     for (int q = 0; q < kp.g_nt; q++) {
@@ -721,6 +725,12 @@ static __device__ __noinline__ double gibbs_pair_bspline(const KParams *kp, doub
     return gibbs_pair<GPT_KERNEL_GIBBS_BSPLINE>(*kp, &xi, &xj, &ni, &nj);
 }
 
+// ... and the nested-GP kernel likewise (the same GB forms carry it: common.hpp, gibbs_gb_kid)
+static __device__ __noinline__ double gibbs_pair_gp(const KParams *kp, double xi, double xj, int ni, int nj)
+{
+    return gibbs_pair<GPT_KERNEL_GIBBS_GP>(*kp, &xi, &xj, &ni, &nj);
+}
+
 template <int KID, int D>
 __device__ __forceinline__ double any_pair(const KParams &kp, const double *xi, const double *xj,
                                            const int *ni, const int *nj)
@@ -738,14 +748,14 @@ __device__ __forceinline__ double any_pair(const KParams &kp, const double *xi, 
 // The reference walks the power set of the derivative multiset of a pair and multiplies k1 with the subset's orders by k2
 // with the complement's; equal subsets recur, so grouped by how many of the r_s derivatives of slot s (the D orders of ni, then
 // the D of nj) go to k1 that is the general Leibniz rule  sum_a prod_s C(r_s, a_s) k1^(a) k2^(r - a).  Factors by run-time id.
-// GM: the bucket / exp-Gauss Gibbs ids are compiled in (GPT_KID_PRODUCT_GM, common.hpp; 1-D only); GB: the B-spline id as well
-// (GPT_KID_PRODUCT_GB: only the kernels the launchers choose for a model WITH a B-spline factor; every other instantiation is
+// GM: the bucket / exp-Gauss Gibbs ids are compiled in (GPT_KID_PRODUCT_GM, common.hpp; 1-D only); GB: the B-spline and nested-GP ids as well
+// (GPT_KID_PRODUCT_GB: only the kernels the launchers choose for a model WITH a B-spline or nested-GP factor; every other instantiation is
 // the code it was)
 // A 1-D Gibbs kernel on coordinate kp.g_dim of D = 2 .. GPT_GIBBS_ON_DIM_MAX_D (GPT_KERNEL_ON_DIM, gpt_hip.h; MaskedKernel, ref:
 // kernel/core.py:1128-1147): the factor from that coordinate of the two points and its orders, exactly 0.0 when any other coordinate
 // carries an order.  The coordinate is chosen by compares over the unrolled dimensions (the points stay in registers); g_dim is the
-// same for every lane.  BS: the factor is the B-spline kernel (the out-of-line call, as at num_dim 1).
-template <int D, bool BS>
+// same for every lane.  KIDF: the factor's id where the caller has tested it -- the B-spline or the nested-GP kernel, the out-of-line calls as at num_dim 1 -- or -1, by run-time id.
+template <int D, int KIDF>
 __device__ __forceinline__ double gibbs_pair_on_dim(const KParams &kp, const double *xi, const double *xj, const int *ni, const int *nj)
 {
     double a = 0.0, b = 0.0;
@@ -762,7 +772,8 @@ __device__ __forceinline__ double gibbs_pair_on_dim(const KParams &kp, const dou
         }
     }
     if (other != 0) return 0.0;
-    if constexpr (BS) return gibbs_pair_bspline(&kp, a, b, na, nb);
+    if constexpr (KIDF == GPT_KERNEL_GIBBS_BSPLINE) return gibbs_pair_bspline(&kp, a, b, na, nb);
+    if constexpr (KIDF == GPT_KERNEL_GIBBS_GP) return gibbs_pair_gp(&kp, a, b, na, nb);
     return gibbs_pair(kp, &a, &b, &na, &nb);
 }
 
@@ -776,9 +787,11 @@ __device__ __forceinline__ double factor_pair(const KParams &kp, const double *x
     // zero-length-scale rule, gibbs_h_other)
     if constexpr (GB && D == 1) {
         if (kp.kernel_id == GPT_KERNEL_GIBBS_BSPLINE) return gibbs_pair_bspline(&kp, xi[0], xj[0], ni[0], nj[0]);
+        if (kp.kernel_id == GPT_KERNEL_GIBBS_GP) return gibbs_pair_gp(&kp, xi[0], xj[0], ni[0], nj[0]);
     }
     if constexpr (GB && ON_DIM) {
-        if (kp.kernel_id == GPT_KERNEL_GIBBS_BSPLINE) return gibbs_pair_on_dim<D, true>(kp, xi, xj, ni, nj);
+        if (kp.kernel_id == GPT_KERNEL_GIBBS_BSPLINE) return gibbs_pair_on_dim<D, GPT_KERNEL_GIBBS_BSPLINE>(kp, xi, xj, ni, nj);
+        if (kp.kernel_id == GPT_KERNEL_GIBBS_GP) return gibbs_pair_on_dim<D, GPT_KERNEL_GIBBS_GP>(kp, xi, xj, ni, nj);
     }
     switch (kp.kernel_id) {
     case GPT_KERNEL_SE: return se_pair<D>(kp, xi, xj, ni, nj);
@@ -787,12 +800,12 @@ __device__ __forceinline__ double factor_pair(const KParams &kp, const double *x
     case GPT_KERNEL_MATERN: return matern_pair<D>(kp, xi, xj, ni, nj);
     case GPT_KERNEL_GIBBS_TANH:
     case GPT_KERNEL_GIBBS_DTANH:
-        if constexpr (ON_DIM) return gibbs_pair_on_dim<D, false>(kp, xi, xj, ni, nj);
+        if constexpr (ON_DIM) return gibbs_pair_on_dim<D, -1>(kp, xi, xj, ni, nj);
         return gibbs_pair(kp, xi, xj, ni, nj);      // (1-D: the host admits no other D without a coordinate, and orders <= 1)
     case GPT_KERNEL_GIBBS_CUBIC:
     case GPT_KERNEL_GIBBS_QUINTIC:
     case GPT_KERNEL_GIBBS_EXPGAUSS:
-        if constexpr (ON_DIM) return gibbs_pair_on_dim<D, false>(kp, xi, xj, ni, nj);
+        if constexpr (ON_DIM) return gibbs_pair_on_dim<D, -1>(kp, xi, xj, ni, nj);
         if constexpr (GM && D == 1) return gibbs_pair(kp, xi, xj, ni, nj);
         return 0.0;
     default: return 0.0;

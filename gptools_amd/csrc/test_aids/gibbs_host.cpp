@@ -22,3 +22,11 @@ extern "C" int gpt_host_gibbs_bspline(const double *p, int nt, const double *x, 
     for (long m = 0; m < M; m++) gpt_gibbs_bspline(p, nt, x[m], l + m, dl + m);
     return 0;
 }
+
+// the nested GP (p: the length scale, the m points, the m weights)
+extern "C" int gpt_host_gibbs_gp(const double *p, int m, const double *x, long M, double *l, double *dl)
+{
+    if (m < 1 || m > GPT_GIBBS_MAX_GP_POINTS) return -1;
+    for (long q = 0; q < M; q++) gpt_gibbs_gp(p, m, x[q], l + q, dl + q);
+    return 0;
+}

@@ -36,7 +36,7 @@ from .utils import CombinedBounds
 __all__ = ["GaussianProcess"]
 
 _GIBBS = (_lib.KERNEL_GIBBS_TANH, _lib.KERNEL_GIBBS_DTANH, _lib.KERNEL_GIBBS_CUBIC, _lib.KERNEL_GIBBS_QUINTIC,
-          _lib.KERNEL_GIBBS_EXPGAUSS, _lib.KERNEL_GIBBS_BSPLINE)
+          _lib.KERNEL_GIBBS_EXPGAUSS, _lib.KERNEL_GIBBS_BSPLINE, _lib.KERNEL_GIBBS_GP)
 _NATIVE_FIT = (_lib.KERNEL_SE, _lib.KERNEL_M52, _lib.KERNEL_RQ, _lib.KERNEL_MATERN) + _GIBBS
 _DEVICE_WARPS = {linear_warp: _lib.WARP_LINEAR, beta_cdf_warp: _lib.WARP_BETA}
 
@@ -308,7 +308,7 @@ class GaussianProcess(object):
                 raise NotImplementedError("Hyperparameter derivatives have not been implemented!")
             Xj_ = None if Xj is None else np.atleast_2d(np.asarray(Xj, dtype=float))
             nj_ = None if Xj is None else np.atleast_2d(np.asarray(nj, dtype=int))
-            return self._plain_ctx().kbuild(kid, k.params, Xi, ni, Xj_, nj_, hyper_deriv=hyper_deriv,
+            return self._plain_ctx().kbuild(kid, k._native_params(), Xi, ni, Xj_, nj_, hyper_deriv=hyper_deriv,
                                             noise_n=getattr(k, "n", None))
         if type(k) is ProductKernel and hyper_deriv is None and k._native_factors() is not None:
             nat = k._native_factors()
@@ -394,7 +394,7 @@ class GaussianProcess(object):
             a, b = self._native_terms(k.k1), self._native_terms(k.k2)
             return None if a is None or b is None or len(a) + len(b) > 8 else a + b
         if (getattr(k, "_gpt_kernel_id", None) in _NATIVE_FIT and type(k).__call__ in (Kernel.__call__, _M52_CALL)):
-            return [(k._gpt_kernel_id, np.array(k.params, dtype=float))]
+            return [(k._gpt_kernel_id, k._native_params())]
         if type(k) is ProductKernel:
             # k1 * k2 of two native kernels: one PRODUCT term of the fused builder (ref: gptools/kernel/core.py:587-671)
             nat = k._native_factors()
@@ -693,7 +693,10 @@ class GaussianProcess(object):
             if exit_on_bounds and np.isinf(prior):
                 continue                                            # impossible parameters: stays -inf
             noise_var = 0.0 if isinstance(self.noise_k, ZeroKernel) else self.noise_k.params[0] ** 2.0
-            terms, layers = self._device_model()
+            try:
+                terms, layers = self._device_model()
+            except np.linalg.LinAlgError:
+                continue                                            # (a kernel whose device parameters need a solve that failed: -inf)
             jobs.append((i, terms, layers, noise_var,
                          np.array(self._y_alph(), dtype=float), prior))
         if not self._data_on_device:
@@ -1126,7 +1129,10 @@ class GaussianProcess(object):
         jobs = []
         for i in rows:
             self._assign_free(trace[i])
-            terms = self._native_terms()
+            try:
+                terms = self._native_terms()
+            except np.linalg.LinAlgError:
+                continue                                     # (as a fit that fails: the row is dropped)
             noise_var = 0.0 if isinstance(self.noise_k, ZeroKernel) else self.noise_k.params[0] ** 2.0
             mu_star = None if self.mu is None else np.asarray(self.mu(Xs, ns), dtype=float)
             jobs.append((i, terms, noise_var, np.array(self._y_alph(), dtype=float), mu_star))

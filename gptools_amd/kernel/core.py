@@ -49,8 +49,13 @@ class Kernel(HyperparameterSet):
         if self._gpt_kernel_id is None:
             raise NotImplementedError("This is an abstract method -- please use one of the implementing subclasses!")
         return _lib.default_context().kpairs(
-            self._gpt_kernel_id, self.params, np.atleast_2d(Xi), np.atleast_2d(Xj), np.atleast_2d(ni),
+            self._gpt_kernel_id, self._native_params(), np.atleast_2d(Xi), np.atleast_2d(Xj), np.atleast_2d(ni),
             np.atleast_2d(nj), hyper_deriv=hyper_deriv, symmetric=symmetric, noise_n=getattr(self, "n", None))
+
+    def _native_params(self):
+        """The parameter array the HIP library gets for this kernel's ``_gpt_kernel_id``: the hyperparameters themselves, unless a
+        class overrides it (``GibbsKernel1dGP`` hands over the nested GP's weights in the place of its values)."""
+        return np.array(self.params, dtype=float)
 
     def _compute_r2l2(self, tau, return_l=False):
         """Anisotropic ``sum_d tau_d^2 / l_d^2`` with the 0/0 -> 0 rule; a host helper for Python
@@ -167,7 +172,7 @@ class ProductKernel(BinaryKernel):
         from .matern import Matern52Kernel
         ok = (_lib.KERNEL_SE, _lib.KERNEL_M52, _lib.KERNEL_RQ, _lib.KERNEL_MATERN, _lib.KERNEL_GIBBS_TANH,
               _lib.KERNEL_GIBBS_DTANH, _lib.KERNEL_GIBBS_CUBIC, _lib.KERNEL_GIBBS_QUINTIC, _lib.KERNEL_GIBBS_EXPGAUSS,
-              _lib.KERNEL_GIBBS_BSPLINE)
+              _lib.KERNEL_GIBBS_BSPLINE, _lib.KERNEL_GIBBS_GP)
         from .masked import MaskedKernel
         f = []
         for k in (self.k1, self.k2):
@@ -183,7 +188,7 @@ class ProductKernel(BinaryKernel):
             # (a subclass that overrides __call__ is a Python-defined kernel, whatever id it inherited)
             if kid not in ok or type(k).__call__ not in (Kernel.__call__, Matern52Kernel.__call__):
                 return None
-            f += [kid, np.array(k.params, dtype=float)]
+            f += [kid, k._native_params()]
         return tuple(f)
 
     def __call__(self, Xi, Xj, ni, nj, hyper_deriv=None, symmetric=False):

@@ -2,7 +2,7 @@ r"""Gibbs non-stationary squared-exponential kernels in one dimension.
 
 ref: gptools/kernel/gibbs.py:229-424 (GibbsKernel1d), :426-466 (tanh_warp, GibbsKernel1dTanh), :508-558 (double_tanh_warp,
 GibbsKernel1dDoubleTanh), :603-801 (cubic_bucket_warp, quintic_bucket_warp and their kernels), :804-902 (exp_gauss_warp,
-GibbsKernel1dExpGauss), :905-992 (BSplineWarp, GibbsKernel1dBSpline).  With a point-dependent length scale ``l(x)``, ``a = l(x_i)``, ``b = l(x_j)``, ``s = a^2 + b^2``
+GibbsKernel1dExpGauss), :905-992 (BSplineWarp, GibbsKernel1dBSpline), :995-1095 (GPWarp, GibbsKernel1dGP).  With a point-dependent length scale ``l(x)``, ``a = l(x_i)``, ``b = l(x_j)``, ``s = a^2 + b^2``
 and ``d = x_i - x_j``:
 
 .. math::  k = \sigma_f^2 \sqrt{2ab/s}\, \exp(-d^2/s).
@@ -17,23 +17,26 @@ The reference hard-codes the derivative classes as expanded polynomials (terms u
 
 ``GibbsKernel1d(l_func)`` evaluates that on the host in numpy for any warp (the Python-kernel route of
 ``GaussianProcess``: pair list, then ``fit_matrix`` on the GPU).  ``GibbsKernel1dTanh``, ``GibbsKernel1dDoubleTanh``,
-``GibbsKernel1dCubicBucket``, ``GibbsKernel1dQuinticBucket``, ``GibbsKernel1dExpGauss`` and the cubic ``GibbsKernel1dBSpline``
-are native: the HIP library evaluates them (``GPT_KERNEL_GIBBS_*``, gptools_amd/csrc/kpair.hpp and gibbs_lfunc.hpp) with the
+``GibbsKernel1dCubicBucket``, ``GibbsKernel1dQuinticBucket``, ``GibbsKernel1dExpGauss``, the cubic ``GibbsKernel1dBSpline`` and
+``GibbsKernel1dGP`` with a nested 1-D squared-exponential kernel are native: the HIP library evaluates them (``GPT_KERNEL_GIBBS_*``, gptools_amd/csrc/kpair.hpp and gibbs_lfunc.hpp) with the
 length-scale functions hoisted out of the builder's pair loop.  A subclass that overrides ``__call__`` is a Python kernel again;
 so is a ``GibbsKernel1dExpGauss`` with more Gaussians than the device kernel carries (``_lib.GIBBS_MAX_GAUSS``) and a
-``GibbsKernel1dBSpline`` of another degree than 3 or with more knots than ``_lib.GIBBS_MAX_KNOTS``.
+``GibbsKernel1dBSpline`` of another degree than 3 or with more knots than ``_lib.GIBBS_MAX_KNOTS`` and a ``GibbsKernel1dGP`` with
+another nested kernel, a free nested amplitude or more points than ``_lib.GIBBS_MAX_GP_POINTS``.
 Derivative orders above ``[1, 1]`` and hyperparameter derivatives raise ``NotImplementedError`` like the reference.
 """
 import inspect
+import sys
 
 import numpy as np
+import scipy.linalg
 
 from .core import Kernel
 from .. import _lib
 from ..splines import spev
 
 __all__ = ["GibbsKernel1d", "GibbsKernel1dTanh", "GibbsKernel1dDoubleTanh", "GibbsKernel1dCubicBucket",
-           "GibbsKernel1dQuinticBucket", "GibbsKernel1dExpGauss", "BSplineWarp", "GibbsKernel1dBSpline", "tanh_warp",
+           "GibbsKernel1dQuinticBucket", "GibbsKernel1dExpGauss", "BSplineWarp", "GibbsKernel1dBSpline", "GPWarp", "GibbsKernel1dGP", "tanh_warp",
            "double_tanh_warp", "cubic_bucket_warp", "quintic_bucket_warp", "exp_gauss_warp"]
 
 
@@ -325,4 +328,178 @@ class GibbsKernel1dBSpline(GibbsKernel1d):
 
 class _GibbsKernel1dBSplineHost(GibbsKernel1dBSpline):
     """``GibbsKernel1dBSpline`` of a degree or knot count the device kernel does not carry: evaluated on the host."""
+    __call__ = GibbsKernel1d.__call__
+
+
+class GPWarp(object):
+    r"""Length-scale function that is the mean of a small noiseless Gaussian process through ``npts`` free values at free
+    locations (ref: gibbs.py:995-1036).  ``warp(X, n, *hpXy)`` is that mean (``n = 0``) or its slope (``n = 1``) at ``X``, in the
+    shape of ``X``; ``hpXy`` holds the free hyperparameters of the nested kernel ``k``, then ``x_1 .. x_npts``, then
+    ``y_1 .. y_npts``.  With ``K`` the nested kernel over the ``x_j``, ``K_tot = K + 1e2 eps I`` (the reference's nested
+    ``GaussianProcess``: no noise, ``diag_factor = 1e2``) and ``alpha = K_tot^-1 y`` (``cho_factor(lower=True)`` /
+    ``cho_solve``), the mean is ``K_*(X) alpha``.
+
+    For a nested kernel whose type is exactly ``SquaredExponentialKernel`` with ``num_dim == 1``, parameters ``[sigma_n, l]``,
+    that is a closed form evaluated here in numpy, and the statement the device kernel ``GPT_KERNEL_GIBBS_GP`` is compared with::
+
+        l(x)  =  sum_j c_j exp(-(x - x_j)^2 / (2 l^2))
+        l'(x) = -sum_j c_j exp(-(x - x_j)^2 / (2 l^2)) (x - x_j) / l^2
+        c     = sigma_n^2 (sigma_n^2 E + 1e2 eps I)^-1 y,       E_ij = exp(-(x_i - x_j)^2 / (2 l^2))
+
+    (terms added in index order).  Any other nested kernel is evaluated through its own ``__call__``, with the same solve.
+
+    Deliberate differences from the reference:
+
+    * ``k=None`` builds the default the reference documents -- a squared-exponential kernel with ``sigma_f = 1`` fixed and
+      ``l_1 = 1`` free, the class's default bounds.  The reference cannot construct it: its ``GPWarp(npts)`` raises
+      ``GPArgumentError("Must pass explicit parameter values if fixing parameters!")`` and only works with a kernel passed in.
+    * The warp is a pure function of its arguments: the weights are recomputed at every call and the nested kernel's own
+      hyperparameters are left as they were.  The reference routes through a nested ``GaussianProcess`` whose
+      ``update_hyperparameters`` can decline to refit (bounds, a swallowed ``LinAlgError``) and then predicts from stale state.
+    * A nested matrix that does not factor raises ``numpy.linalg.LinAlgError`` -- and so does one that factors only by the
+      ``1e2 eps`` on its diagonal: a squared pivot of the Cholesky factor at or below ``pivot_factor`` (10) times that jitter.  Two
+      ``x_j`` that coincide (to about ``1e-6 l``) with values that differ are the case: the reference's nested fit succeeds
+      there, with weights of the order ``1e12`` whose sum leaves a length scale of two digits; here the evaluation fails and
+      ``update_hyperparameters`` counts it as ``+inf``.  The condition numbers an optimiser meets otherwise (the fixture's: up to
+      344) are ten orders of magnitude away from that threshold."""
+
+    diag_factor = 1e2
+    pivot_factor = 10.0
+
+    def __init__(self, npts, k=None):
+        if isinstance(npts, bool) or not isinstance(npts, (int, np.integer)) or npts < 1:
+            raise ValueError("npts must be an integer > 0!")
+        self.npts = int(npts)
+        if k is None:
+            from .squared_exponential import SquaredExponentialKernel
+            k = SquaredExponentialKernel(initial_params=[1.0, 1.0], fixed_params=[True, False],
+                                         param_bounds=[(0.0, 1e16), (0.0, 1e16)])
+        if not isinstance(k, Kernel):
+            raise TypeError("k must be an instance of type Kernel!")
+        if k.num_dim != 1:
+            raise ValueError("Gibbs kernel only supports 1d data.")
+        self.k = k
+
+    def _closed_form(self):
+        """The nested kernel is exactly a 1-D ``SquaredExponentialKernel``: the closed form applies."""
+        from .squared_exponential import SquaredExponentialKernel
+        return type(self.k) is SquaredExponentialKernel and self.k.num_dim == 1
+
+    def split(self, hpXy):
+        """``(p, x, y)``: the nested kernel's full parameter array with its free entries taken from ``hpXy``, the points, the
+        values."""
+        hpXy = np.asarray(hpXy, dtype=float).ravel()
+        nf = self.k.num_free_params
+        if len(hpXy) != nf + 2 * self.npts:
+            raise ValueError("%d values given for %d nested hyperparameters and 2 x %d points" % (len(hpXy), nf, self.npts))
+        p = np.array(self.k.params, dtype=float)
+        p[self.k.free_param_idxs] = hpXy[:nf]
+        return p, hpXy[nf:nf + self.npts], hpXy[nf + self.npts:]
+
+    def _solve(self, K, y):
+        K_tot = K + self.diag_factor * sys.float_info.epsilon * np.eye(self.npts)
+        if not np.isfinite(K_tot).all():
+            raise np.linalg.LinAlgError("the nested covariance matrix of GPWarp is not finite")
+        c, low = scipy.linalg.cho_factor(K_tot, lower=True)
+        if (np.diagonal(c) ** 2.0).min() <= self.pivot_factor * self.diag_factor * sys.float_info.epsilon:
+            raise np.linalg.LinAlgError("the nested covariance matrix of GPWarp factors only by the jitter on its diagonal "
+                                        "(coincident points?)")
+        return scipy.linalg.cho_solve((c, low), y)
+
+    def weights(self, *hpXy):
+        """``(l, x, c)`` of the closed form above: what the device kernel takes.  ``ValueError`` for a nested kernel that is not
+        exactly a 1-D ``SquaredExponentialKernel`` (its parameters are not ``[sigma_n, l]``)."""
+        if not self._closed_form():
+            raise ValueError("GPWarp.weights: the closed form needs a nested 1-D SquaredExponentialKernel, got %s"
+                             % type(self.k).__name__)
+        p, x, y = self.split(hpXy)
+        with np.errstate(all="ignore"):
+            d = x[:, None] - x[None, :]
+            E = np.exp(-d ** 2.0 / (2.0 * p[1] ** 2.0))
+            s2 = p[0] ** 2.0
+            return p[1], x, s2 * self._solve(s2 * E, y)
+
+    def __call__(self, X, n, *hpXy):
+        if n not in (0, 1):
+            raise NotImplementedError("Only derivatives up to order 1 are supported!")
+        X = np.asarray(X, dtype=float)
+        shape = X.shape
+        xs = X[:, 0] if X.ndim == 2 else X.ravel()
+        if self._closed_form():
+            l, x, c = self.weights(*hpXy)
+            out = np.zeros_like(xs)
+            with np.errstate(all="ignore"):
+                for xj, cj in zip(x, c):
+                    term = cj * np.exp(-(xs - xj) ** 2.0 / (2.0 * l ** 2.0))
+                    out += term if n == 0 else term * (xs - xj) / l ** 2.0
+            return np.reshape(out if n == 0 else -out, shape)
+        p, x, y = self.split(hpXy)
+        k, keep = self.k, np.array(self.k.params, dtype=float)
+        m, M = self.npts, len(xs)
+        zm = np.zeros((m * m, 1), dtype=int)
+        try:
+            k.params = p
+            K = np.reshape(k(np.repeat(x, m)[:, None], np.tile(x, m)[:, None], zm, zm, symmetric=True), (m, m))
+            alpha = self._solve(np.asarray(K, dtype=float), y)
+            Ks = np.reshape(k(np.repeat(xs, m)[:, None], np.tile(x, M)[:, None], np.full((M * m, 1), n, dtype=int),
+                              np.zeros((M * m, 1), dtype=int)), (M, m))
+        finally:
+            k.params = keep
+        return np.reshape(np.asarray(Ks, dtype=float).dot(alpha), shape)
+
+
+class GibbsKernel1dGP(GibbsKernel1d):
+    r"""Gibbs kernel whose length scale interpolates ``npts`` free values ``y_j`` at free locations ``x_j`` with a small nested
+    Gaussian process (:class:`GPWarp`; ref: gibbs.py:1039-1095).  Parameters ``[sigma_f, (free nested hyperparameters), x_1 ..
+    x_npts, y_1 .. y_npts]``.  Keep the outer points near the edges of the data (the nested GP goes to zero away from its points)
+    and the values positive.  ``k=None``: see :class:`GPWarp` (the reference fails there).
+
+    With a nested kernel that is exactly a 1-D ``SquaredExponentialKernel`` whose ``l_1`` is free and ``sigma_f`` fixed and with
+    ``npts <= _lib.GIBBS_MAX_GP_POINTS`` the kernel is evaluated on the GPU: the library gets ``[sigma_f, l, x_1 .., c_1 ..]``
+    with the nested GP's weights ``c`` (:meth:`_native_params`; an ``npts x npts`` solve on the host per hyperparameter vector).
+    For another nested kernel, a free nested ``sigma_f`` or more points the constructor returns an instance of a subclass whose
+    ``__call__`` is the host ``GibbsKernel1d``'s -- a Python kernel, with the same numbers.  As for :class:`GibbsKernel1dBSpline`
+    that switch is made for this class only: a user subclass that keeps the native ``__call__`` with such a nested kernel or point
+    count stays native and gets a ``ValueError`` at its first evaluation (from :meth:`_native_params`, or the library's beyond the
+    cap); it takes the host route by overriding ``__call__``, like any Python kernel.  Coincident ``x_j``: see :class:`GPWarp`."""
+    _gpt_kernel_id = _lib.KERNEL_GIBBS_GP
+    __call__ = Kernel.__call__
+
+    @staticmethod
+    def _device_form(npts, k):
+        from .squared_exponential import SquaredExponentialKernel
+        if npts is None or not 1 <= npts <= _lib.GIBBS_MAX_GP_POINTS:
+            return False
+        if k is None or not isinstance(k, Kernel):
+            return True                                     # (not a Kernel: GPWarp's constructor raises the TypeError)
+        fixed = np.asarray(k.fixed_params, dtype=bool)
+        return type(k) is SquaredExponentialKernel and k.num_dim == 1 and bool(fixed[0]) and not bool(fixed[1])
+
+    def __new__(cls, npts=None, k=None, **kwargs):
+        if cls is GibbsKernel1dGP and npts is not None and not cls._device_form(npts, k):
+            cls = _GibbsKernel1dGPHost
+        return super(GibbsKernel1dGP, cls).__new__(cls)
+
+    def __init__(self, npts, k=None, **kwargs):
+        w = GPWarp(npts, k=k)
+        super(GibbsKernel1dGP, self).__init__(
+            w, num_params=w.k.num_free_params + 2 * npts + 1,
+            param_names=([r"\sigma_f"] + [str(s) for s in w.k.free_param_names[:]] +
+                         [r"x_{{{:d}}}".format(i + 1) for i in range(npts)] +
+                         [r"y_{{{:d}}}".format(i + 1) for i in range(npts)]),
+            **kwargs)
+
+    def _native_params(self):
+        """``[sigma_f, l, x_1 .. x_m, c_1 .. c_m]``: what ``GPT_KERNEL_GIBBS_GP`` takes (the weights, not the values)."""
+        w = self.l_func
+        if not w._closed_form() or w.k.num_free_params != 1 or bool(np.asarray(w.k.fixed_params, dtype=bool)[1]):
+            raise ValueError("GibbsKernel1dGP: the device kernel takes a nested 1-D SquaredExponentialKernel with sigma_f fixed and "
+                             "l_1 free; override __call__ (GibbsKernel1d.__call__) for the host route")
+        p = np.array(self.params, dtype=float)
+        l, x, c = w.weights(*p[1:])
+        return np.concatenate(([p[0], l], x, c))
+
+
+class _GibbsKernel1dGPHost(GibbsKernel1dGP):
+    """``GibbsKernel1dGP`` with a nested kernel or a number of points the device kernel does not carry: evaluated on the host."""
     __call__ = GibbsKernel1d.__call__

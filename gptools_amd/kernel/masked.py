@@ -40,7 +40,7 @@ __all__ = ["MaskedKernel"]
 
 _STATIONARY = (_lib.KERNEL_SE, _lib.KERNEL_M52, _lib.KERNEL_RQ, _lib.KERNEL_MATERN)
 _GIBBS = (_lib.KERNEL_GIBBS_TANH, _lib.KERNEL_GIBBS_DTANH, _lib.KERNEL_GIBBS_CUBIC, _lib.KERNEL_GIBBS_QUINTIC,
-          _lib.KERNEL_GIBBS_EXPGAUSS, _lib.KERNEL_GIBBS_BSPLINE)
+          _lib.KERNEL_GIBBS_EXPGAUSS, _lib.KERNEL_GIBBS_BSPLINE, _lib.KERNEL_GIBBS_GP)
 
 
 def unit_factor(num_dim):
@@ -122,7 +122,7 @@ class MaskedKernel(Kernel):
             ls[self.mask] = p[lead:]
             return kid, np.concatenate((p[:lead], ls))
         if kid in _GIBBS and self.num_dim <= _lib.GIBBS_ON_DIM_MAX_D:
-            return _lib.kernel_on_dim(kid, self.mask[0]), np.array(base.params, dtype=float)
+            return _lib.kernel_on_dim(kid, self.mask[0]), base._native_params()
         return None
 
     def _native_term(self):

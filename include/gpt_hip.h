@@ -94,6 +94,15 @@ extern "C" {
                                   * knots that are not in increasing order (a NaN knot among them) GPT_E_VALUE, "Knots must be in
                                   * increasing order!", before anything is launched */
 #define GPT_GIBBS_MAX_KNOTS 11   /* most knots of GPT_KERNEL_GIBBS_BSPLINE */
+#define GPT_KERNEL_GIBBS_GP 13   /* GibbsKernel1dGP with m points and a nested 1-D squared-exponential kernel (ref: kernel/gibbs.py:995-1095),
+                                  * 2 m + 2 params [sigma_f, l, x_1 .. x_m, c_1 .. c_m]: l(x) = sum_j c_j exp(-(x - x_j)^2 / (2 l^2)),
+                                  * the mean of the nested noiseless GP in closed form.  The c_j are its WEIGHTS, not the class's
+                                  * hyperparameters y_j: c = sigma_n^2 (sigma_n^2 E + 1e2 eps I)^-1 y with E_ij = exp(-(x_i - x_j)^2 /
+                                  * (2 l^2)), an m x m solve the caller does once per hyperparameter vector (gptools_amd/kernel/gibbs.py,
+                                  * GPWarp.weights).  m = (nparams - 2) / 2: an odd parameter count, m < 1 or m > GPT_GIBBS_MAX_GP_POINTS
+                                  * (the parameters travel by value in the kernel arguments) is GPT_E_ARG.  A non-finite or non-positive
+                                  * l is not refused: it gives NaN (or what the arithmetic gives) like the other length scales */
+#define GPT_GIBBS_MAX_GP_POINTS 12 /* most points of GPT_KERNEL_GIBBS_GP */
 
 /* MaskedKernel (ref: kernel/core.py:1011-1149): a kernel that acts on a subset of the num_dim coordinates and is exactly 0.0 for a
  * pair with a derivative order in any other coordinate.
