@@ -70,6 +70,7 @@ SIGNATURES = {
     "gpt_get_L": (C.c_int, [_vp, _dp]),
     "gpt_get_alpha": (C.c_int, [_vp, _dp]),
     "gpt_ll_grad": (C.c_int, [_vp, C.c_int, _ip, _ip, _dp]),
+    "gpt_ll_grad_diff": (C.c_int, [_vp, C.c_int, _ip, _dp, _dp, _dp, _dp]),
     "gpt_predict": (C.c_int, [_vp, _dp, _ip, _i64, C.c_int, _dp, _ip, _dp, _dp, _dp]),
     "gpt_host_alloc": (C.c_int, [_i64, C.POINTER(_vp)]),
     "gpt_host_free": (C.c_int, [_vp]),
@@ -261,6 +262,7 @@ class Context(object):
         self._lib = lib
         self.device = int(device)
         self._warp_key = None               # the layers the library holds (set_warp); None: no warp
+        self._term_nparams = None           # parameter counts of the terms of the last successful fit / fit_sum / fit_terms
 
     def close(self):
         if getattr(self, "_h", None):
@@ -371,8 +373,10 @@ class Context(object):
         y, err_y = f64(y), f64(err_y)
         ll = C.c_double()
         ld = C.c_double()
+        self._term_nparams = None
         check(self._lib.gpt_fit_terms(self.handle, len(ids), iptr(ids), iptr(ids2), dptr(flat), iptr(npar), iptr(npar1),
                                       float(noise_var), dptr(y), dptr(err_y), float(diag_add), C.byref(ll), C.byref(ld)))
+        self._term_nparams = [int(v) for v in npar]
         return ll.value, ld.value
 
     # ---- fit / state ---------------------------------------------------------------------------
@@ -432,8 +436,10 @@ class Context(object):
         params, y, err_y = f64(params), f64(y), f64(err_y)
         ll = C.c_double()
         ld = C.c_double()
+        self._term_nparams = None
         check(self._lib.gpt_fit(self.handle, kernel_id, dptr(params), len(params), float(noise_var), dptr(y),
                                 dptr(err_y), float(diag_add), C.byref(ll), C.byref(ld)))
+        self._term_nparams = [len(params)]
         return ll.value, ld.value
 
     def fit_sum(self, kernel_ids, params_list, noise_var, y, err_y, diag_add):
@@ -444,8 +450,10 @@ class Context(object):
         y, err_y = f64(y), f64(err_y)
         ll = C.c_double()
         ld = C.c_double()
+        self._term_nparams = None
         check(self._lib.gpt_fit_sum(self.handle, len(ids), iptr(ids), dptr(flat), iptr(npar), float(noise_var), dptr(y),
                                     dptr(err_y), float(diag_add), C.byref(ll), C.byref(ld)))
+        self._term_nparams = [int(v) for v in npar]
         return ll.value, ld.value
 
     def fit_batch(self, kernel_id, params, noise_var, y, err_y, diag_add):
@@ -520,10 +528,38 @@ class Context(object):
         check(self._lib.gpt_ll_grad(self.handle, len(ti), iptr(ti), iptr(li), dptr(out)))
         return out
 
+    def ll_grad_diff(self, term_idx, params_a, params_b, denom):
+        """gpt_ll_grad_diff: the data-term gradient by per-pair central differences.  For every entry h the resident model's
+        term ``term_idx[h]`` with its complete parameter vector (both factors of a product) at the two stencil points,
+        ``params_a[h]`` and ``params_b[h]``, and ``denom[h]`` = theta_b - theta_a; returns the gradient entries followed by the
+        noise trace term, as :meth:`ll_grad`."""
+        ti, dn = i32(np.asarray(term_idx)), f64(np.asarray(denom, dtype=float))
+        if not (len(ti) == len(params_a) == len(params_b) == len(dn)):
+            raise ValueError("ll_grad_diff: %d terms, %d / %d stencil points, %d steps"
+                             % (len(ti), len(params_a), len(params_b), len(dn)))
+        # The library reads, per entry, as many doubles as the resident term has parameters (the export carries no lengths): the
+        # counts are those of this context's last successful fit, and every vector is checked against them here
+        counts = self._term_nparams
+        if len(ti) and counts is None:
+            raise GPTBackendError("ll_grad_diff needs a factorisation made by fit / fit_sum / fit_terms on this context")
+        for h, t in enumerate(ti):
+            if not 0 <= t < len(counts):
+                raise ValueError("ll_grad_diff: term_idx[%d] = %d, the resident model has %d terms" % (h, t, len(counts)))
+            for p in (params_a[h], params_b[h]):
+                if np.size(p) != counts[t]:
+                    raise ValueError("ll_grad_diff: entry %d holds %d parameters, term %d of the resident model has %d"
+                                     % (h, np.size(p), t, counts[t]))
+        pa = f64(np.concatenate([np.asarray(p, dtype=float).ravel() for p in params_a])) if len(ti) else f64(np.zeros(1))
+        pb = f64(np.concatenate([np.asarray(p, dtype=float).ravel() for p in params_b])) if len(ti) else f64(np.zeros(1))
+        out = np.empty(len(ti) + 1)
+        check(self._lib.gpt_ll_grad_diff(self.handle, len(ti), iptr(ti), dptr(pa), dptr(pb), dptr(dn), dptr(out)))
+        return out
+
     def fit_matrix(self, K_tot, y):
         K_tot, y = f64(K_tot), f64(y)
         ll = C.c_double()
         ld = C.c_double()
+        self._term_nparams = None
         check(self._lib.gpt_fit_matrix(self.handle, dptr(K_tot), K_tot.shape[0], dptr(y), C.byref(ll), C.byref(ld)))
         return ll.value, ld.value
 

@@ -52,7 +52,7 @@ struct DevBuf {
 enum { SLOT_XI = 0, SLOT_XJ, SLOT_NI, SLOT_NJ, SLOT_OUT, SLOT_KST, SLOT_KSS, SLOT_XS, SLOT_NS, SLOT_VEC, SLOT_VEC2,
        SLOT_RHS, SLOT_LOW, SLOT_KFULL, SLOT_TK, SLOT_ZERO, SLOT_UINV, SLOT_WINV, SLOT_GPART, SLOT_BINV, SLOT_BTMP,
        SLOT_BINV2, SLOT_BINV3, SLOT_BINV3U, SLOT_BINVU, SLOT_BATCH_A, SLOT_BATCH_WS, SLOT_BATCH_MISC, SLOT_SPLITK,
-       SLOT_PB_V, SLOT_PB_COV, SLOT_PB_MISC, SLOT_XSW, SLOT_SS, SLOT_SI, SLOT_SJ, SLOT_WB_X, SLOT_WB_S, SLOT_WB_P, SLOT_COUNT };
+       SLOT_PB_V, SLOT_PB_COV, SLOT_PB_MISC, SLOT_XSW, SLOT_SS, SLOT_SI, SLOT_SJ, SLOT_WB_X, SLOT_WB_S, SLOT_WB_P, SLOT_GKP, SLOT_COUNT };
 
 struct gpt_ctx {
     int device = 0;

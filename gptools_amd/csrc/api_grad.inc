@@ -1,5 +1,6 @@
 // api_grad.inc -- part of api.hip (ONE translation unit: included from there, in this order; the parts share struct gpt_ctx and
-// static helpers).  Triangular inverses (gpt_dev_trinv) and the analytic LML gradient gpt_ll_grad.
+// static helpers).  Triangular inverses (gpt_dev_trinv), the analytic LML gradient gpt_ll_grad and the per-pair differenced one,
+// gpt_ll_grad_diff; grad_weights is the half the two share.
 // ------------------------------------------------------------------------------------------------
 // analytic gradient of the LML data term (ref: gptools/gaussian_process.py:1471-1520; SURVEY.md 8f-1)
 // ------------------------------------------------------------------------------------------------
@@ -174,39 +175,28 @@ static int trtri_u_gemm_b(gpt_ctx *c, hipStream_t st, int64_t lo, int64_t hi, co
     return trsm_rlt_binv_b(c, st, h, nb, mid, hi, Wb, T + lo * ldt, ldt, U + lo * ldu, ldu, wb);
 }
 
-extern "C" int gpt_ll_grad(gpt_ctx *c, int nh, const int *term_idx, const int *local_idx, double *out)
+// The weights of a gradient's pair pass, G = alpha' alpha'^T - W' over Np points: W' (lower triangle, row stride ldwp) and alpha'.
+// Without a transform W' = W = K_tot^-1 and alpha' = alpha over the N training points; with T, W' = T^T W T and alpha' = T^T alpha
+// over the Nx latent points.  W: K_tot^-1 itself (NP x NP), which the noise entry of a transformed model reads (grad_noise_trace_T).
+struct GradWeights {
+    const double *Wp = nullptr, *ap = nullptr;
+    int64_t Np = 0, ldwp = 0;
+    double *W = nullptr;
+};
+
+// The half that gpt_ll_grad and gpt_ll_grad_diff share: the triangular inverse, U U^T and the T branch, enqueued on the panel
+// stream `st` behind the main stream; the pair pass of either caller follows on `st`.  ge (GPT_GRAD_TIMING; else NULL): four
+// events, [0] .. [2] recorded here -- before the inverse, after it, after U U^T.
+static int grad_weights(gpt_ctx *c, hipStream_t st, hipEvent_t *ge, GradWeights *gw)
 {
-    CTX_ENTER(c);
-    GPT_TRY(refuse_warp(c, "gpt_ll_grad"));
-    NEED_FACTOR(c);
-    if (!c->have_kernel) {
-        gpt_set_error("gpt_ll_grad needs a factorisation produced by gpt_fit / gpt_fit_sum");
-        return GPT_E_STATE;
-    }
-    if (nh < 0 || (nh > 0 && (!term_idx || !local_idx)) || !out) return GPT_E_ARG;
-    for (int h = 0; h < nh; h++) {
-        if (term_idx[h] < 0 || term_idx[h] >= c->model.nterms) return GPT_E_ARG;
-        if (c->model.f1[term_idx[h]].kernel_id != GPT_KERNEL_SE || c->model.second(term_idx[h])) {
-            gpt_set_error("hyper-parameter derivatives exist for the squared-exponential kernel only "
-                          "(ref: matern.py:543-544)");
-            return GPT_E_NOTIMPL;
-        }
-        if (local_idx[h] < 0 || local_idx[h] > c->D) return GPT_E_ARG;
-    }
     const int64_t N = c->N, NP = c->NP;
     // Everything here runs on the panel stream: it is not CU-masked (the main stream leaves 32 of the 256 CUs to it), and
     // nothing else is in flight.
-    hipStream_t st = c->panel_stream;
     GPT_TRY(stream_follows(c, c->stream, st, 0));
-    double *U, *W, *dpart;
+    double *U, *W;
     // K_tot^-1 = L^-T L^-1 = U U^T: triangular inverse (N^3/3 flop), then the lower half of U U^T block row by block row
     // with k starting at the diagonal (N^3/3) -- all on the fp64-MFMA GEMM
-    const bool gt = getenv("GPT_GRAD_TIMING") != nullptr;
-    hipEvent_t ge[4] = {nullptr, nullptr, nullptr, nullptr};
-    if (gt) {
-        for (auto &e : ge) GPT_HIP_CHECK(hipEventCreate(&e));
-        GPT_HIP_CHECK(hipEventRecord(ge[0], st));
-    }
+    if (ge) GPT_HIP_CHECK(hipEventRecord(ge[0], st));
     const int64_t nfull = (NP / GPT_BINV_NB) * GPT_BINV_NB;
     double *Wb = nullptr;
     GPT_TRY(ensure(c, SLOT_UINV, (size_t)NP * NP * sizeof(double), (void **)&U));
@@ -244,7 +234,7 @@ extern "C" int gpt_ll_grad(gpt_ctx *c, int nh, const int *term_idx, const int *l
         GPT_TRY(trtri_u(c, st, 0, NP, c->dA, NP, c->d_invd, U, NP));
     }
     // (block rows of about NP/8: skinnier launches exploit more of U's zeros but run the GEMM far below its rate)
-    if (gt) GPT_HIP_CHECK(hipEventRecord(ge[1], st));
+    if (ge) GPT_HIP_CHECK(hipEventRecord(ge[1], st));
     int64_t nbdiv = 8;
     if (const char *e = getenv("GPT_GRAD_ROWS_DIV")) nbdiv = atoi(e) > 0 ? atoi(e) : 8;
     const int64_t nb = (NP / nbdiv >= 512) ? (NP / nbdiv) / 128 * 128 : 512;
@@ -256,8 +246,8 @@ extern "C" int gpt_ll_grad(gpt_ctx *c, int nh, const int *term_idx, const int *l
             GPT_TRY(gemm_nt(c, st, rows, r0, NP - r0, 1.0, U + r0 * NP + r0, NP, U + r0, NP, 0.0, W + r0 * NP, NP, 0));
         GPT_TRY(gemm_nt(c, st, rows, rows, NP - r0, 1.0, U + r0 * NP + r0, NP, U + r0 * NP + r0, NP, 0.0, W + r0 * NP + r0, NP, 1));
     }
-    if (gt) GPT_HIP_CHECK(hipEventRecord(ge[2], st));
-    GPT_TRY(stream_follows(c, c->stream, st, 0));              // alpha (main stream) is needed from here on
+    if (ge) GPT_HIP_CHECK(hipEventRecord(ge[2], st));
+    GPT_TRY(stream_follows(c, c->stream, st, 0));             // alpha (main stream) is needed from here on
     // With a linear transform (ref :1499-1500, dK_tot = T dK T^T):  tr(K_tot^-1 T dK T^T) = tr((T^T K_tot^-1 T) dK) and
     // alpha^T T dK T^T alpha = (T^T alpha)^T dK (T^T alpha): the pair pass runs over the Nx LATENT points with
     // W' = T^T W T (two GEMMs with the resident T) and alpha' = T^T alpha.  The noise entry (out[nh]) is taken from the
@@ -290,6 +280,87 @@ extern "C" int gpt_ll_grad(gpt_ctx *c, int nh, const int *term_idx, const int *l
         Np = Nx;
         ldwp = NxQ;
     }
+    gw->Wp = Wp;
+    gw->ap = ap;
+    gw->Np = Np;
+    gw->ldwp = ldwp;
+    gw->W = W;
+    return GPT_OK;
+}
+
+// The noise entry with a transform: the reference differentiates the DiagonalNoiseKernel as 2 sigma_n I over the
+// OBSERVATIONS, not transformed by T (ref :1482-1488, dK = 2 sigma_n eye(len(y))): 1/2 sum_i (alpha_i^2 - (K_tot^-1)_ii) from the
+// untransformed pair, replacing what the pass over the latent points left in its place.
+static int grad_noise_trace_T(gpt_ctx *c, hipStream_t st, const double *W, double *dpart, double *out)
+{
+    GPT_TRY(launch_alpha_trace(st, c->d_alpha, W, c->NP, c->N, dpart));
+    double tr = 0.0;
+    GPT_HIP_CHECK(hipMemcpyAsync(&tr, dpart, sizeof(double), hipMemcpyDeviceToHost, st));
+    GPT_HIP_CHECK(hipStreamSynchronize(st));
+    *out = 0.5 * tr;
+    return GPT_OK;
+}
+
+// GPT_GRAD_TIMING: the four events of a gradient's three phases, owned by the entry point -- destroyed on every way out of it, an
+// early error return included
+struct GradTimer {
+    hipEvent_t ge[4] = {nullptr, nullptr, nullptr, nullptr};
+    bool on = false;
+    int init()
+    {
+        on = getenv("GPT_GRAD_TIMING") != nullptr;
+        if (on)
+            for (auto &e : ge) GPT_HIP_CHECK(hipEventCreate(&e));
+        return GPT_OK;
+    }
+    hipEvent_t *events() { return on ? ge : nullptr; }
+    ~GradTimer()
+    {
+        for (auto &e : ge)
+            if (e) hipEventDestroy(e);
+    }
+};
+
+// ... and the phases on stderr (ge as grad_weights took it; [3] recorded here)
+static int grad_timing_report(const char *who, int64_t N, hipStream_t st, hipEvent_t *ge)
+{
+    GPT_HIP_CHECK(hipEventRecord(ge[3], st));
+    GPT_HIP_CHECK(hipStreamSynchronize(st));
+    float a = 0, b = 0, d = 0;
+    hipEventElapsedTime(&a, ge[0], ge[1]);
+    hipEventElapsedTime(&b, ge[1], ge[2]);
+    hipEventElapsedTime(&d, ge[2], ge[3]);
+    fprintf(stderr, "%s N=%lld: triangular inverse %.2f ms, U U^T %.2f ms, pair pass %.2f ms\n", who, (long long)N, a, b, d);
+    return GPT_OK;
+}
+
+extern "C" int gpt_ll_grad(gpt_ctx *c, int nh, const int *term_idx, const int *local_idx, double *out)
+{
+    CTX_ENTER(c);
+    GPT_TRY(refuse_warp(c, "gpt_ll_grad"));
+    NEED_FACTOR(c);
+    if (!c->have_kernel) {
+        gpt_set_error("gpt_ll_grad needs a factorisation produced by gpt_fit / gpt_fit_sum");
+        return GPT_E_STATE;
+    }
+    if (nh < 0 || (nh > 0 && (!term_idx || !local_idx)) || !out) return GPT_E_ARG;
+    for (int h = 0; h < nh; h++) {
+        if (term_idx[h] < 0 || term_idx[h] >= c->model.nterms) return GPT_E_ARG;
+        if (c->model.f1[term_idx[h]].kernel_id != GPT_KERNEL_SE || c->model.second(term_idx[h])) {
+            gpt_set_error("hyper-parameter derivatives exist for the squared-exponential kernel only "
+                          "(ref: matern.py:543-544)");
+            return GPT_E_NOTIMPL;
+        }
+        if (local_idx[h] < 0 || local_idx[h] > c->D) return GPT_E_ARG;
+    }
+    hipStream_t st = c->panel_stream;
+    GradTimer timer;
+    GPT_TRY(timer.init());
+    GradWeights gw;
+    GPT_TRY(grad_weights(c, st, timer.events(), &gw));
+    const double *Wp = gw.Wp, *ap = gw.ap;
+    const int64_t Np = gw.Np, ldwp = gw.ldwp;
+    double *dpart;
     // sum_ab (alpha_a alpha_b - W_ab) dK_h[a][b], per kernel term, GPT_GRAD_MAXH parameters per launch
     const int nblk = grad_reduce_blocks(Np);
     GPT_TRY(ensure(c, SLOT_GPART, (size_t)nblk * (GPT_GRAD_MAXH + 1) * sizeof(double), (void **)&dpart));
@@ -328,25 +399,97 @@ extern "C" int gpt_ll_grad(gpt_ctx *c, int nh, const int *term_idx, const int *l
             if (cnt <= 0) break;
         }
     }
-    if (c->dT) {
-        // The noise entry with a transform: the reference differentiates the DiagonalNoiseKernel as 2 sigma_n I over the
-        // OBSERVATIONS, not transformed by T (ref :1482-1488, dK = 2 sigma_n eye(len(y))): out[nh] = 1/2 sum_i (alpha_i^2 -
-        // (K_tot^-1)_ii) from the untransformed pair, replacing what the pass over the latent points left there.
-        GPT_TRY(launch_alpha_trace(st, c->d_alpha, W, NP, N, dpart));
-        double tr = 0.0;
-        GPT_HIP_CHECK(hipMemcpyAsync(&tr, dpart, sizeof(double), hipMemcpyDeviceToHost, st));
-        GPT_HIP_CHECK(hipStreamSynchronize(st));
-        out[nh] = 0.5 * tr;
-    }
-    if (gt) {
-        GPT_HIP_CHECK(hipEventRecord(ge[3], st));
-        GPT_HIP_CHECK(hipStreamSynchronize(st));
-        float a = 0, b = 0, d = 0;
-        hipEventElapsedTime(&a, ge[0], ge[1]);
-        hipEventElapsedTime(&b, ge[1], ge[2]);
-        hipEventElapsedTime(&d, ge[2], ge[3]);
-        fprintf(stderr, "gpt_ll_grad N=%lld: triangular inverse %.2f ms, U U^T %.2f ms, pair pass %.2f ms\n", (long long)N, a, b, d);
-        for (auto &e : ge) hipEventDestroy(e);
-    }
+    if (c->dT) GPT_TRY(grad_noise_trace_T(c, st, gw.W, dpart, &out[nh]));
+    if (timer.on) GPT_TRY(grad_timing_report("gpt_ll_grad", c->N, st, timer.ge));
     return stream_follows(c, st, c->stream, 1);     // the main stream continues behind this (the block inverses stay valid for predict)
+}
+
+// The same gradient for ANY term of the resident model, by central differences of the pair function taken per pair (kgrad.hip):
+// parameter h is given as its term's complete parameter vector at the two stencil points, and every stencil point goes through
+// parse_model as a one-term model with the ids and parameter counts the fit was given -- whatever that refuses is refused here,
+// before anything is launched.  After K_tot^-1 a parameter costs two O(N^2) evaluations of its term instead of a factorisation.
+extern "C" int gpt_ll_grad_diff(gpt_ctx *c, int nh, const int *term_idx, const double *params_a, const double *params_b,
+                                const double *denom, double *out)
+{
+    CTX_ENTER(c);
+    GPT_TRY(refuse_warp(c, "gpt_ll_grad_diff"));
+    NEED_FACTOR(c);
+    if (!c->have_kernel) {
+        gpt_set_error("gpt_ll_grad_diff needs a factorisation produced by gpt_fit / gpt_fit_sum / gpt_fit_terms");
+        return GPT_E_STATE;
+    }
+    if (nh < 0 || (nh > 0 && (!term_idx || !params_a || !params_b || !denom)) || !out) return GPT_E_ARG;
+    const ModelKernel &m = c->model;
+    // the stencil points, term by term (the parameters of one launch belong to one term): kp1 / kp2 hold [a, b] per parameter in
+    // launch order, where[] the caller's index of each
+    std::vector<KParams> kp1, kp2;
+    std::vector<int> where, term_of;
+    std::vector<size_t> off((size_t)nh + 1, 0);
+    for (int h = 0; h < nh; h++) {
+        if (term_idx[h] < 0 || term_idx[h] >= m.nterms) return GPT_E_ARG;
+        if (!(denom[h] != 0.0) || std::isinf(denom[h])) {
+            gpt_set_error("gpt_ll_grad_diff: denom[%d] = %g", h, denom[h]);
+            return GPT_E_ARG;
+        }
+        off[h + 1] = off[h] + (size_t)m.np[term_idx[h]];
+    }
+    for (int t = 0; t < m.nterms; t++)
+        for (int h = 0; h < nh; h++) {
+            if (term_idx[h] != t) continue;
+            const bool prod = m.abi_id2[t] >= 0;
+            for (const double *p : {params_a + off[h], params_b + off[h]}) {
+                ModelKernel one;
+                GPT_TRY(parse_model(c->D, c->n_maxsum, c->n_colmax, 1, &m.abi_id1[t], prod ? &m.abi_id2[t] : nullptr, p, &m.np[t],
+                                    prod ? &m.np1[t] : nullptr, &one));
+                kp1.push_back(one.f1[0]);
+                kp2.push_back(one.f2[0]);
+            }
+            where.push_back(h);
+            term_of.push_back(t);
+        }
+    hipStream_t st = c->panel_stream;
+    GradTimer timer;
+    GPT_TRY(timer.init());
+    GradWeights gw;
+    GPT_TRY(grad_weights(c, st, timer.events(), &gw));
+    const int nblk = grad_reduce_blocks(gw.Np);
+    double *dpart;
+    KParams *dkp;
+    GPT_TRY(ensure(c, SLOT_GPART, (size_t)nblk * (GPT_GRAD_MAXH + 1) * sizeof(double), (void **)&dpart));
+    const size_t nk = kp1.size() > 0 ? kp1.size() : 1;      // (nh == 0: one launch for the trace, which reads no KParams)
+    GPT_TRY(ensure(c, SLOT_GKP, 2 * nk * sizeof(KParams), (void **)&dkp));
+    if (!kp1.empty()) {
+        GPT_HIP_CHECK(hipMemcpyAsync(dkp, kp1.data(), kp1.size() * sizeof(KParams), hipMemcpyHostToDevice, st));
+        GPT_HIP_CHECK(hipMemcpyAsync(dkp + nk, kp2.data(), kp2.size() * sizeof(KParams), hipMemcpyHostToDevice, st));
+        GPT_HIP_CHECK(hipStreamSynchronize(st));      // (pageable sources: the vectors may not change before the copies are through)
+    }
+    std::vector<double> hpart((size_t)nblk * (GPT_GRAD_MAXH + 1));
+    bool have_trace = false;
+    const int total = (int)where.size();
+    for (int b0 = 0; b0 < total || !have_trace;) {
+        // the parameters [b0, b0 + cnt): one term, GPT_GRAD_MAXH at most
+        const int t = b0 < total ? term_of[b0] : 0;
+        int cnt = 0;
+        while (b0 + cnt < total && cnt < GPT_GRAD_MAXH && term_of[b0 + cnt] == t) cnt++;
+        GPT_TRY(launch_kgrad_diff(st, m.f1[t].kernel_id, m.second(t) ? m.f2[t].kernel_id : -1, c->D, dkp + 2 * b0, dkp + nk + 2 * b0, cnt,
+                                  c->dX, c->dn, gw.Np, gw.ap, gw.Wp, gw.ldwp, dpart));
+        GPT_HIP_CHECK(hipMemcpyAsync(hpart.data(), dpart, hpart.size() * sizeof(double), hipMemcpyDeviceToHost, st));
+        GPT_HIP_CHECK(hipStreamSynchronize(st));
+        for (int q = 0; q < cnt; q++) {
+            double sum = 0.0;
+            for (int b = 0; b < nblk; b++) sum += hpart[(size_t)b * (GPT_GRAD_MAXH + 1) + q];
+            out[where[b0 + q]] = 0.5 * sum / denom[where[b0 + q]];
+        }
+        if (!have_trace) {
+            double sum = 0.0;
+            for (int b = 0; b < nblk; b++) sum += hpart[(size_t)b * (GPT_GRAD_MAXH + 1) + GPT_GRAD_MAXH];
+            out[nh] = 0.5 * sum;
+            have_trace = true;
+        }
+        b0 += cnt;
+        if (cnt <= 0) break;
+    }
+    if (c->dT) GPT_TRY(grad_noise_trace_T(c, st, gw.W, dpart, &out[nh]));
+    if (timer.on) GPT_TRY(grad_timing_report("gpt_ll_grad_diff", c->N, st, timer.ge));
+    return stream_follows(c, st, c->stream, 1);
 }

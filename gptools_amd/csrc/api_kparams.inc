@@ -358,6 +358,9 @@ struct ModelKernel {
     bool any_prod = false, has_m52 = false, has_chain = false, has_gibbs = false;      // over all factors of all terms
     bool has_gb = false;      // ... a B-spline or nested-GP Gibbs kernel among them (gibbs_gb_kid): the batched launchers take the kernels with those branches
     bool has_on_dim = false;       // ... a Gibbs factor on one coordinate of num_dim > 1 (GPT_KERNEL_ON_DIM): likewise
+    // the terms as the ABI named them (ids with their GPT_KERNEL_ON_DIM coordinate; abi_id2 < 0: no product) and their parameter counts
+    // (np: the whole term, np1: its first factor): what gpt_ll_grad_diff needs to send a stencil point of ONE term through parse_model again
+    int abi_id1[GPT_MAX_TERMS] = {}, abi_id2[GPT_MAX_TERMS] = {}, np[GPT_MAX_TERMS] = {}, np1[GPT_MAX_TERMS] = {};
     int gibbs_form() const { return (has_gb ? GPT_GFORM_GB : 0) | (has_on_dim ? GPT_GFORM_ON_DIM : 0); }      // what those launchers take
     const KParams *second(int t) const { return f2[t].kernel_id >= 0 ? &f2[t] : nullptr; }
 };
@@ -424,6 +427,10 @@ static int parse_model(int D, long n_maxsum, const long *n_colmax, int nterms, c
         m->f2[t] = KParams();
         m->f2[t].kernel_id = -1;
         if (prod) GPT_TRY(make_kparams(ids2[t], p + n1, nparams[t] - n1, D, -1, 1, nullptr, &m->f2[t], true));
+        m->abi_id1[t] = ids[t];
+        m->abi_id2[t] = prod ? ids2[t] : -1;
+        m->np[t] = nparams[t];
+        m->np1[t] = n1;
         m->any_prod = m->any_prod || prod;
         m->has_m52 = m->has_m52 || k1 == GPT_KERNEL_M52 || k2 == GPT_KERNEL_M52;
         m->has_chain = m->has_chain || is_chain(k1) || is_chain(k2);

@@ -259,6 +259,10 @@ int launch_batch_logdet_dot(hipStream_t st, const double *A, int64_t lda, int64_
 int grad_reduce_blocks(int64_t N);
 int launch_grad_reduce(hipStream_t st, const KParams &kp, int nh, const int *hl, const double *dX, const int32_t *dn,
                        int64_t N, const double *dalpha, const double *dW, int64_t ldw, double *dpartial);
+// the pair pass of gpt_ll_grad_diff (kgrad.hip): nh <= GPT_GRAD_MAXH parameters of one term id1 (* id2 where id2 >= 0), 2 nh KParams in
+// device memory per factor (the term at the stencil points a, b of every parameter); dpartial as launch_grad_reduce
+int launch_kgrad_diff(hipStream_t st, int id1, int id2, int D, const KParams *d_kps, const KParams *d_kps2, int nh, const double *dX,
+                      const int32_t *dn, int64_t N, const double *dalpha, const double *dW, int64_t ldw, double *dpartial);
 int launch_add_diag(hipStream_t st, double *A, int64_t lda, int64_t n, const double *err, double diag_add, int64_t nbatch = 1,
                     int64_t bstride = 0);
 // Test aid (GPT_JITTER=<max microseconds> in the environment): a delay kernel of random length on `st`, called in front of

@@ -1,0 +1,156 @@
+// kgrad.hip -- the pair pass of gpt_ll_grad_diff (api_grad.inc): the LML gradient of ANY model term by per-pair central
+// differences of its pair function,
+//     d ll / d theta_h ~= 1/2 sum_ab (alpha_a alpha_b - W_ab) (k_b - k_a)[a][b] / (theta_b - theta_a),   W = K_tot^-1 resident,
+// where k_a / k_b are the term at the two stencil points of parameter h.  The difference is taken PER PAIR, before the weight
+// (differencing the two weighted sums instead loses a digit: the sums are large and nearly equal), and the division by the
+// step is the host's, once per parameter.  Geometry and reduction are grad_reduce_kernel's (kbuild.hip): the tiles of the lower
+// triangle, a workgroup owns 32 x 256 pairs, each lane keeps its column's point, the rows arrive through wave-uniform loads,
+// the strictly lower part counts twice; per-workgroup partial sums that the host adds in index order (deterministic); slot
+// GR_MAXH of a partial row carries sum_i (alpha_i^2 - W_ii), the same bits grad_reduce_kernel leaves there.
+// The stencil points' KParams (two per parameter, four for a product term: 656 bytes each) do not fit the kernel arguments: they
+// live in device memory and are read BY REFERENCE with wave-uniform indices, as the batched builder reads kps[z] -- never copied
+// per lane.  The parameters of a launch are walked by an outer loop that is not unrolled, so an instantiation holds the pair
+// function twice (a and b), whatever the number of parameters.  That trades bandwidth for registers: every parameter reads the
+// tile's weights again (W, alpha, the rows' points: N^2 / 2 doubles of W per parameter, 1 GB at N = 16384), where
+// grad_reduce_kernel forms a pair's weight once for its eight parameters but holds eight accumulators and its pair function
+// eight times.  For the cheap pair functions the pass is then bound by that traffic (Matern-5/2, N = 16384: 0.47 ms per
+// parameter); next to K_tot^-1 (57 ms there) it does not show.  The 1-D Gibbs kernels hoist their length scales out of the pair
+// loop as the builder does.
+// Instantiated through the dispatch the builders share (kbuild_kernel.hpp): FitKids for a plain term, ProductKids by product_kid
+// for a product term -- the form its factors' gform asks for.  A translation unit of its own: the builders' code objects stay
+// what they were.
+#include "kbuild_kernel.hpp"
+
+#define GR_MAXH GPT_GRAD_MAXH
+
+// the term KID at one pair: a native kernel, or the product k1 * k2 in the form KID names
+template <int KID, int D>
+__device__ __forceinline__ double kgrad_term_pair(const KParams &k1, const KParams *__restrict__ k2, const double *xi, const double *xj,
+                                                  const int *ni, const int *nj)
+{
+    if constexpr (KID == GPT_KERNEL_PRODUCT) return prod_pair<D>(k1, *k2, xi, xj, ni, nj);
+    else if constexpr (KID == GPT_KID_PRODUCT_GM) return prod_pair<D, true>(k1, *k2, xi, xj, ni, nj);
+    else if constexpr (KID == GPT_KID_PRODUCT_GB) return prod_pair<D, true, true>(k1, *k2, xi, xj, ni, nj);
+    else return any_pair<KID, D>(k1, xi, xj, ni, nj);
+}
+
+// kps[2 h], kps[2 h + 1]: the term at the stencil points a, b of parameter h < nh <= GR_MAXH (kps2: the second factors of a product
+// term, else unused); partial: grad_reduce_blocks(N) x (GR_MAXH + 1), every entry written
+template <int KID, int D>
+__global__ __launch_bounds__(KB_THREADS) void kgrad_diff_kernel(
+    const KParams *__restrict__ kps, const KParams *__restrict__ kps2, int nh, const double *__restrict__ X,
+    const int32_t *__restrict__ nn, int64_t N, const double *__restrict__ alpha, const double *__restrict__ W, int64_t ldw,
+    double *__restrict__ partial)
+{
+    constexpr int64_t R = KB_RATIO;
+    const int64_t b = blockIdx.x;
+    int64_t g = (int64_t)((sqrt(1.0 + 8.0 * (double)b / (double)R) - 1.0) * 0.5);
+    while (g > 0 && R * g * (g + 1) / 2 > b) g--;
+    while (R * (g + 1) * (g + 2) / 2 <= b) g++;
+    const int64_t rem = b - R * g * (g + 1) / 2;
+    const int64_t rt = R * g + rem / (g + 1), ct = rem % (g + 1);
+    const int64_t rbase = rt * KB_ROWS, j = ct * KB_COLS + threadIdx.x;
+    const bool live = rbase < N && j < N;
+    const int64_t jc = live ? j : 0;                                // (a lane without a column reads point 0 and adds nothing)
+    const int64_t rend = (rbase + KB_ROWS < N) ? rbase + KB_ROWS : N;
+    double xj[D];
+    int njr[D];
+#pragma unroll
+    for (int d = 0; d < D; d++) {
+        xj[d] = X[jc * D + d];
+        njr[d] = nn[jc * D + d];
+    }
+    const double aj = alpha[jc];
+    __shared__ double red[KB_THREADS / 64][GR_MAXH + 1];
+    const int lane = threadIdx.x & 63, wave = threadIdx.x >> 6;
+#pragma unroll 1
+    for (int h = 0; h <= GR_MAXH; h++) {
+        double acc = 0.0;
+        if constexpr (gibbs_kid(KID)) {
+            // The 1-D Gibbs kernels with the builder's hoist (kbuild_kernel.hpp): the length scale is formed once per point and
+            // stencil -- this lane's column, and the tile's 32 rows once per wave, lane q (and q + 32) row rbase + q, read back
+            // with v_readlane before the lanes part ways -- so a pair costs two gibbs_core, not eight length-scale evaluations
+            // (measured, DoubleTanh at N = 16384: 10.0 -> 0.82 ms per parameter).  EVERY lane takes part in the hoist, the ones
+            // without a column too: a row's point may sit in such a lane.
+            static_assert(D == 1, "the Gibbs kernels are one-dimensional");
+            if (h < nh) {
+                const KParams &ka = kps[2 * h], &kb = kps[2 * h + 1];
+                const GibbsPt ca = gibbs_point<KID>(ka, xj[0]), cb = gibbs_point<KID>(kb, xj[0]);
+                const int64_t ir = (rbase + (lane & 31) < N) ? rbase + (lane & 31) : N - 1;
+                const double xr = X[ir];
+                const GibbsPt ra = gibbs_point<KID>(ka, xr), rb = gibbs_point<KID>(kb, xr);
+                const double s2a = ka.sigma * ka.sigma, s2b = kb.sigma * kb.sigma;
+                for (int64_t i = rbase; i < rend; i++) {
+                    const int q = (int)(i - rbase);
+                    const double xi = X[i];
+                    const int nir = nn[i];
+                    const double la = readlane_f64(ra.l, q), Aa = readlane_f64(ra.A, q), ha = readlane_f64(ra.h, q), qa = readlane_f64(ra.r2, q);
+                    const double lb = readlane_f64(rb.l, q), Ab = readlane_f64(rb.A, q), hb = readlane_f64(rb.h, q), qb = readlane_f64(rb.r2, q);
+                    if (!live || j > i) continue;                   // lower triangle (wave-uniform row, per-lane column)
+                    const bool need_d = (nir | njr[0]) != 0;
+                    const double va = gibbs_core(s2a, xi, la, Aa, gibbs_h_other<KID>(ha, ca.l), qa, xj[0], ca.l, ca.A, gibbs_h_other<KID>(ca.h, la),
+                                                 gibbs_col_root(la, ca.rp, ca.rn), nir, njr[0], need_d);
+                    const double vb = gibbs_core(s2b, xi, lb, Ab, gibbs_h_other<KID>(hb, cb.l), qb, xj[0], cb.l, cb.A, gibbs_h_other<KID>(cb.h, lb),
+                                                 gibbs_col_root(lb, cb.rp, cb.rn), nir, njr[0], need_d);
+                    const double w = alpha[i] * aj - W[i * ldw + j];
+                    acc = fma((i == j) ? w : 2.0 * w, vb - va, acc);
+                }
+            }
+        } else if (live && h < nh) {
+            const KParams &ka = kps[2 * h], &kb = kps[2 * h + 1];
+            const KParams *ka2 = nullptr, *kb2 = nullptr;
+            if constexpr (KID == GPT_KERNEL_PRODUCT || KID == GPT_KID_PRODUCT_GM || KID == GPT_KID_PRODUCT_GB) {
+                ka2 = kps2 + 2 * h;
+                kb2 = kps2 + 2 * h + 1;
+            }
+            for (int64_t i = rbase; i < rend; i++) {
+                if (j > i) continue;                                // lower triangle (wave-uniform row, per-lane column)
+                double xi[D];
+                int nir[D];
+#pragma unroll
+                for (int d = 0; d < D; d++) {
+                    xi[d] = X[i * D + d];
+                    nir[d] = nn[i * D + d];
+                }
+                const double w = alpha[i] * aj - W[i * ldw + j];
+                const double w2 = (i == j) ? w : 2.0 * w;
+                const double dk = kgrad_term_pair<KID, D>(kb, kb2, xi, xj, nir, njr) - kgrad_term_pair<KID, D>(ka, ka2, xi, xj, nir, njr);
+                acc = fma(w2, dk, acc);
+            }
+        }
+        // the noise trace: this lane's diagonal entry, if the tile holds it
+        if (live && h == GR_MAXH && j >= rbase && j < rend) acc += alpha[j] * aj - W[j * ldw + j];
+        for (int off = 32; off > 0; off >>= 1) acc += __shfl_down(acc, off);
+        if (lane == 0) red[wave][h] = acc;
+    }
+    __syncthreads();
+    if (threadIdx.x <= GR_MAXH) {
+        double v = 0.0;
+        for (int wv = 0; wv < KB_THREADS / 64; wv++) v += red[wv][threadIdx.x];
+        partial[(int64_t)blockIdx.x * (GR_MAXH + 1) + threadIdx.x] = v;
+    }
+}
+
+// One launch: nh <= GPT_GRAD_MAXH parameters of ONE term, kernel id1 (* id2 where id2 >= 0) at num_dim D; d_kps / d_kps2: 2 nh
+// KParams each in device memory (d_kps2 only for a product).  The N points dX / dn against the weights alpha alpha^T - W.
+int launch_kgrad_diff(hipStream_t st, int id1, int id2, int D, const KParams *d_kps, const KParams *d_kps2, int nh, const double *dX,
+                      const int32_t *dn, int64_t N, const double *dalpha, const double *dW, int64_t ldw, double *dpartial)
+{
+    if (nh < 0 || nh > GR_MAXH || N <= 0 || !d_kps || (id2 >= 0 && !d_kps2)) return GPT_E_ARG;
+    auto for_kid = [&](auto k) {
+        constexpr int KID = decltype(k)::value;
+        return dispatch_dim<kid_max_dim(KID)>("ll_grad_diff", D, [&](auto d) {
+            hipLaunchKernelGGL((kgrad_diff_kernel<KID, decltype(d)::value>), dim3((unsigned)grad_reduce_blocks(N)), dim3(KB_THREADS), 0, st,
+                               d_kps, d_kps2, nh, dX, dn, N, dalpha, dW, ldw, dpartial);
+            GPT_LAUNCH_CHECK();
+            return GPT_OK;
+        }, kid_dim_rule(KID));
+    };
+    if (id2 >= 0)
+        return dispatch_kid(ProductKids(), product_kid(D, gibbs_form_of(D, id1, id2), gibbs_more_kid(id1) || gibbs_more_kid(id2), false), for_kid,
+                            [] { return GPT_E_ARG; });
+    return dispatch_kid(FitKids(), id1, for_kid, [&] {
+        gpt_set_error("ll_grad_diff: kernel_id %d is not a fit kernel", id1);
+        return GPT_E_ARG;
+    });
+}

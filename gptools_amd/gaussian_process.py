@@ -578,6 +578,133 @@ class GaussianProcess(object):
             ll_deriv[i] += self.hyperprior(self.params[:], hyper_deriv=int(pi))
         self.ll_deriv = ll_deriv
 
+    # ---- device gradient for every native kernel (gpt_ll_grad_diff) ------------
+    def _ll_gradient_refusal(self):
+        """Why ``gpt_ll_grad_diff`` cannot serve this model, or ``None``."""
+        model = self._device_model()
+        if model is not None and model[1]:
+            return "a warped model (WarpedKernel layers evaluated on the device)"
+        if not self._fast_fit_possible():
+            return ("the matrix route (a covariance or noise kernel the library does not evaluate itself: K_tot is assembled "
+                    "on the host)")
+        if self._partitioned_possible():
+            return "a partitioned fit (the factor is spread over the ranks of the job)"
+        return None
+
+    def _ll_gradient_stencil(self, rel_step):
+        """The central stencils of the free KERNEL parameters at the current hyperparameters, as ``Context.ll_grad_diff``
+        takes them: ``(slot, term_idx, params_a, params_b, denom)``, entry ``h`` a term of the device model whose parameters
+        change along free parameter ``slot[h]``, with that term's complete device parameters at theta - eps and theta + eps
+        (eps = ``rel_step`` max(1, abs(theta)); a point that would leave the parameter's bounds stays on the bound) and ``denom[h]``
+        the floating-point difference of the two values of the parameter.
+        The device parameters are :meth:`_native_terms` after :meth:`_assign_free` at each point -- a masked term's expanded
+        array and the nested GP's weights are what a fit there would send.  The hyperparameters are restored; host only."""
+        theta = np.array(self.free_params[:], dtype=float)
+        box = np.array(self.free_param_bounds[:], dtype=float).reshape(-1, 2)
+        up_to_date = self.K_up_to_date
+        slot, tix, pa, pb, denom = [], [], [], [], []
+
+        def flat(t):
+            return np.concatenate([np.asarray(p, dtype=float).ravel() for p in t[1::2]])
+        try:
+            for i in range(len(self.k.free_params)):
+                eps = rel_step * max(1.0, abs(theta[i]))
+                ta, tb = theta.copy(), theta.copy()
+                # (an optimiser puts parameters ON their bounds, and beyond one the library may refuse the point -- Matern's nu,
+                # a B-spline's knot order: a stencil point that would leave the bounds stays on the bound, the difference then
+                # one-sided, first order in eps)
+                ta[i] = theta[i] - eps
+                tb[i] = theta[i] + eps
+                if box[i, 0] <= theta[i] <= box[i, 1]:      # (NaN bounds, or a value already outside them: the plain stencil)
+                    ta[i] = max(ta[i], box[i, 0])
+                    tb[i] = min(tb[i], box[i, 1])
+                if not tb[i] > ta[i]:
+                    continue                                # (bounds that pin the parameter: no derivative to take)
+                self._assign_free(ta)
+                terms_a = self._native_terms()
+                self._assign_free(tb)
+                terms_b = self._native_terms()
+                if terms_a is None or terms_b is None or len(terms_a) != len(terms_b):
+                    raise NotImplementedError("ll_gradient: the covariance kernel is not a model the library evaluates itself")
+                for t, (a, b) in enumerate(zip(terms_a, terms_b)):
+                    if a[0::2] != b[0::2]:
+                        raise NotImplementedError("ll_gradient: term %d changes its kernel along free parameter %d" % (t, i))
+                    fa, fb = flat(a), flat(b)
+                    if fa.shape != fb.shape or not np.array_equal(fa, fb):
+                        slot.append(i)
+                        tix.append(t)
+                        pa.append(fa)
+                        pb.append(fb)
+                        denom.append(tb[i] - ta[i])
+        finally:
+            self._assign_free(theta)
+            self.K_up_to_date = up_to_date          # (the very values the fit was made at)
+        return slot, tix, pa, pb, np.asarray(denom, dtype=float)
+
+    def ll_gradient(self, rel_step=6e-6):
+        """Gradient of the log-posterior with respect to the free hyperparameters at their current values, for every model of
+        native kernels (``gpt_ll_grad_diff``): ``K_tot^-1`` once on the device, then per free kernel parameter two passes over
+        the pairs with the term's central difference taken per pair -- eps = ``rel_step`` max(1, abs(theta)) -- instead of a
+        factorisation per parameter.  Fits first if the hyperparameters changed.  The noise parameter, the mean function's
+        parameters and the hyperprior's derivative as in the analytic gradient (``use_hyper_deriv``), which this leaves as it
+        is -- with a transform ``T`` that includes the reference's form of the noise entry, 2 sigma_n I over the observations (ref
+        :1482-1488), which is not the derivative of the fitted likelihood (the fit transforms the noise term): fix the noise
+        parameter when optimising such a model with this gradient.  ``NotImplementedError`` for a warped model, the matrix route and a partitioned fit."""
+        why = self._ll_gradient_refusal()
+        if why is not None:
+            raise NotImplementedError("ll_gradient is not available for %s" % why)
+        self.compute_K_L_alpha_ll()
+        if self._fit_mode != "kernel":
+            raise NotImplementedError("ll_gradient is not available for a fit by the %s route" % self._fit_mode)
+        ctx = self._ctx
+        grad = np.zeros(len(self.free_params))
+        slot, tix, pa, pb, denom = self._ll_gradient_stencil(rel_step)
+        g_dev = ctx.ll_grad_diff(tix, pa, pb, denom)
+        for s, v in zip(slot, g_dev[:-1]):
+            grad[s] += v
+        nk = len(self.k.free_params)
+        if isinstance(self.noise_k, DiagonalNoiseKernel) and not isinstance(self.noise_k, ZeroKernel) \
+                and not self.noise_k.fixed_params[0]:
+            grad[nk] = 2.0 * self.noise_k.params[0] * g_dev[-1]
+        if self.mu is not None:
+            alpha = ctx.get_alpha(len(self.y))
+            free_idx = np.arange(0, len(self.mu.params), dtype=int)[~self.mu.fixed_params]
+            for i, pi in enumerate(free_idx):
+                dmu = self.mu(self.X, self.n, hyper_deriv=int(pi))
+                if self.T is not None:
+                    dmu = self.T.dot(dmu)
+                grad[i + nk + len(self.noise_k.free_params)] = dmu.dot(alpha)
+        free_idx = np.arange(0, len(self.params), dtype=int)[~np.asarray(self.fixed_params[:], dtype=bool)]
+        for i, pi in enumerate(free_idx):
+            grad[i] += self.hyperprior(self.params[:], hyper_deriv=int(pi))
+        return grad
+
+    def _device_grad_objective(self):
+        """``(fun, jac)`` for scipy.optimize.minimize: ``fun`` is ``update_hyperparameters``, ``jac`` minus :meth:`ll_gradient`
+        at the same point (zeros where the value is ``+inf``)."""
+        last = {}
+
+        def fun(x):
+            x = np.array(x, dtype=float)
+            v = self.update_hyperparameters(x, hyper_deriv_handling="value")
+            last["x"], last["f"] = x, v
+            return v
+
+        def jac(x):
+            x = np.array(x, dtype=float)
+            f0 = last["f"] if ("x" in last and np.array_equal(last["x"], x)) else fun(x)
+            if not np.isfinite(f0):
+                return np.zeros(len(x))
+            try:
+                return -1.0 * self.ll_gradient()
+            except Exception:
+                # (the optimiser's caller drops a start whose run raised and says so only when verbose: a gradient that fails at a
+                # point whose VALUE was finite is reported whatever the setting)
+                warnings.warn("the device gradient failed at free hyperparameters %s, where the log-posterior is %.6g:\n%s"
+                              % (x, -f0, traceback.format_exc()), RuntimeWarning)
+                raise
+        return fun, jac
+
     # ---- hyperparameter update (ref: gptools/gaussian_process.py:1332-1416) -------------------
     def _assign_free(self, values):
         """Distribute a vector of FREE hyperparameters over the kernel, the noise kernel and the mean function, in the
@@ -848,13 +975,27 @@ class GaussianProcess(object):
 
     # ---- MAP estimate (ref: gptools/gaussian_process.py:623-783, :2443-2486) ------------------
     def optimize_hyperparameters(self, method="SLSQP", opt_kwargs={}, verbose=False, random_starts=None,
-                                 num_proc=None, max_tries=1, batch_fd=None):
+                                 num_proc=None, max_tries=1, batch_fd=None, gradient=None):
         """Maximise the log-posterior with ``scipy.optimize.minimize`` from ``random_starts`` draws
         of the hyperprior (0: start from the current values).  Every objective evaluation is one GPU
         fit.  ``num_proc`` is accepted for compatibility: a HIP context must not be shared across forked
         workers, so inside one process the starts run one after another; under a ``torch.distributed`` job
         (one process per GPU) they are spread over the ranks instead (``gptools_amd.replicas``) and every
-        rank returns the same best result."""
+        rank returns the same best result.
+
+        ``gradient="device"``: the optimiser is given ``jac`` = minus :meth:`ll_gradient` -- one fit, ``K_tot^-1`` and two passes
+        over the pairs per free kernel parameter, for every model of native kernels -- instead of finite differences of the
+        objective at one fit per free parameter (``None``, the default).  Independent of ``use_hyper_deriv`` (the analytic
+        gradient of squared-exponential models), with which it cannot be combined."""
+        if gradient not in (None, "device"):
+            raise ValueError("gradient must be None or 'device', got %r" % (gradient,))
+        if gradient == "device":
+            if self.use_hyper_deriv or "jac" in (opt_kwargs or {}):
+                raise ValueError("gradient='device' cannot be combined with use_hyper_deriv or a jac of the caller's")
+            why = self._ll_gradient_refusal()
+            if why is not None:
+                raise NotImplementedError("gradient='device' is not available for %s" % why)
+            self._ctx                          # (no device: GPTBackendError here, not a +inf objective at every start)
         opt_kwargs = dict(opt_kwargs or {})
         if "method" in opt_kwargs:
             method = opt_kwargs["method"]
@@ -887,7 +1028,9 @@ class GaussianProcess(object):
         # and the difference formula are scipy's own (approx_derivative is replayed), so the iterates are the same.
         fd_eps = {"L-BFGS-B": 1e-8, "TNC": 1e-8, "SLSQP": 1.4901161193847656e-08}
         partitioned = self._partitioned_possible()       # every evaluation is a collective: no local batching,
-        if (batch_fd is not False and int(self.batch_concurrency) > 1 and not self.use_hyper_deriv and not partitioned
+        if gradient == "device":
+            objective, opt_kwargs["jac"] = self._device_grad_objective()
+        elif (batch_fd is not False and int(self.batch_concurrency) > 1 and not self.use_hyper_deriv and not partitioned
                 and "jac" not in opt_kwargs and method in fd_eps and self._fast_fit_possible()):
             eps = (opt_kwargs.get("options") or {}).get("eps", fd_eps[method])
             objective, opt_kwargs["jac"] = self._batched_fd(eps, np.asarray(opt_kwargs["bounds"], dtype=float))

@@ -21,6 +21,10 @@
  *   (2) device API (gpt_dev_*), raw device pointers + the context's stream -- used by callers
  *       that own device memory themselves (the one-process-per-GPU block-cyclic Cholesky in
  *       gptools_amd/dist.py passes torch.Tensor.data_ptr() values).
+ *
+ * Gradients of the log marginal likelihood come in two forms, both after a fit and both at the cost of K_tot^-1 plus passes over
+ * the pairs: gpt_ll_grad, analytic, for squared-exponential terms (what the reference differentiates), and gpt_ll_grad_diff, for
+ * every kernel and product the fits take, by central differences of the pair function taken per pair.
  */
 #ifndef GPT_HIP_H_
 #define GPT_HIP_H_
@@ -293,7 +297,7 @@ int gpt_set_T(gpt_ctx *ctx, const double *T, int64_t Ny);
  * The call warps the resident points (O(N D) on the device: warp_points_kernel) and drops the resident factorisation; the
  * layers hold until gpt_set_data or gpt_set_warp(ctx, 0, NULL, NULL).  Needs gpt_set_data first (GPT_E_STATE).
  * gpt_set_warp(ctx, 0, ...) with no layers set changes nothing (the resident factorisation stays).
- * Not available while layers are set (GPT_E_NOTIMPL, gpt_last_error says so): gpt_ll_grad, gpt_predict_batch, gpt_plan_create /
+ * Not available while layers are set (GPT_E_NOTIMPL, gpt_last_error says so): gpt_ll_grad, gpt_ll_grad_diff, gpt_predict_batch, gpt_plan_create /
  * gpt_plan_run over this context, and gpt_fit_batch* unless gpt_set_warp_batch gave the batch its own warps. */
 int gpt_set_warp(gpt_ctx *ctx, int nlayers, const int *types, const double *params);
 
@@ -403,6 +407,25 @@ int gpt_get_alpha(gpt_ctx *ctx, double *alpha_out);
  * whatever nh is -- the reference spends 2 N^3 per parameter in cho_solve); dK is never materialised.
  * Squared-exponential terms only (GPT_E_NOTIMPL otherwise, like matern.py:543-544). */
 int gpt_ll_grad(gpt_ctx *ctx, int nh, const int *term_idx, const int *local_idx, double *out);
+
+/* The same gradient for EVERY kernel the fits take -- Matern52, Matern, RationalQuadratic, the Gibbs families, products,
+ * GPT_KERNEL_ON_DIM factors -- by central differences of the pair function, taken PER PAIR before the weight:
+ *   out[h]  = 1/2 * sum_ab (alpha_a alpha_b - (K_tot^-1)_ab) * (k_b - k_a)[a][b] / denom[h]      for h < nh,
+ *   out[nh] = the noise trace term, the value gpt_ll_grad returns there (with a transform T: over the observations).
+ * term_idx[h] names a term of the resident model (gpt_fit / gpt_fit_sum / gpt_fit_terms); k_a and k_b are that term with the
+ * parameters the caller gives for the two stencil points of parameter h: params_a and params_b hold, concatenated over h, the
+ * term's COMPLETE parameter vector in the layout gpt_fit_terms took (a product's two factors together), so entry h starts where
+ * the vectors of the entries before it end.  denom[h] = theta_b - theta_a as the caller formed it in floating point (0, NaN or
+ * an infinity: GPT_E_ARG).  The other terms of the sum cancel exactly and are not evaluated.
+ * Cost: K_tot^-1 as gpt_ll_grad (~N^3 flop whatever nh is), then two O(N^2) evaluations of ONE term per entry -- against a whole
+ * factorisation per parameter when the likelihood itself is differenced.  GPT_GRAD_MAXH entries of one term share a launch.
+ * Deterministic: repeated calls return the same bits.  Accuracy: with a relative step of 6e-6 the truncation and rounding errors
+ * meet near 1e-7 of the largest gradient entry.
+ * Errors: GPT_E_STATE without a factorisation made by a fit of kernels (gpt_fit_matrix leaves none); GPT_E_NOTIMPL while warp
+ * layers are set; every stencil point is checked as the parameters of a fit are (parameter domains, derivative orders) and the
+ * first refusal is the call's status, before anything is launched. */
+int gpt_ll_grad_diff(gpt_ctx *ctx, int nh, const int *term_idx, const double *params_a, const double *params_b,
+                     const double *denom, double *out);
 
 /* Replaces  ref: gaussian_process.py:965-1006 for the T-free, untransformed case:
  *   Kstar = K(X, Xstar) ; mean = Kstar^T alpha ; v = L^-1 Kstar ; cov = K(Xstar,Xstar) - v^T v ;
