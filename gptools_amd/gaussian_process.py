@@ -17,6 +17,7 @@ State attributes follow the reference: ``X n y err_y T K noise_K L alpha ll ll_d
 K_up_to_date``.  ``K``, ``noise_K``, ``L`` and ``alpha`` are fetched lazily from the device the
 first time they are read after a fit, so the MAP loop moves only ``params`` and a scalar.
 """
+import collections
 import sys
 import traceback
 import warnings
@@ -59,6 +60,27 @@ _SIGN_FEATURES = {
 def _combine(a, b, c=None):
     out = CombinedBounds(a, b)
     return CombinedBounds(out, c) if c is not None else out
+
+
+_UNRESOLVED = object()          # "resolve the device model yourself" (None is a resolved model: the library does not evaluate it)
+
+#: one element of a batched fit: the row of the caller's list it answers, its device model (``_device_model``), noise variance and
+#: ``y - mu``, and what the route carries along -- the log-prior (ll_batch) or the mean function at the test points (MCMC)
+_BatchJob = collections.namedtuple("_BatchJob", "row terms layers noise_var y_alph extra")
+
+
+def _terms_shape(terms):
+    """What a batch needs equal in all its elements: the kernel id(s) of every term."""
+    return [(t[0], t[2] if len(t) == 4 else -1) for t in terms]
+
+
+def _gram(ctx, terms, Xi, ni, Xj, nj):
+    """Gram block of a list of terms on a context: one builder call per term (a product term: ``kbuild2``), summed."""
+    out = None
+    for t in terms:
+        Kt = ctx.kbuild2(t[0], t[1], t[2], t[3], Xi, ni, Xj, nj) if len(t) == 4 else ctx.kbuild(t[0], t[1], Xi, ni, Xj, nj)
+        out = Kt if out is None else out + Kt
+    return out
 
 
 class GaussianProcess(object):
@@ -111,14 +133,10 @@ class GaussianProcess(object):
             self.K_up_to_date = False
 
     # ---- device plumbing -------------------------------------------------------------------
-    def _reset_device_state(self):
-        self._ctx_obj = None
-        self._scratch_ctx = None
-        self._ctx_pool = None
-        self._data_on_device = False
-        self._cache = {}
-        self._fit_mode = None
-        self._dist_plan = None
+    def _reset_device_state(self, state=None):
+        """Device handles and what depends on them, as before the first use (``state``: in that dict instead of the instance)."""
+        (self.__dict__ if state is None else state).update(_ctx_obj=None, _scratch_ctx=None, _ctx_pool=None, _data_on_device=False,
+                                                           _cache={}, _fit_mode=None, _dist_plan=None)
 
     partitioned = False
     partition_block = 512
@@ -128,13 +146,13 @@ class GaussianProcess(object):
     #: gradient); the MAP loop never reads it.  Cost at N = 8192: ~0.3 ms per evaluation (bench.py ``with_alpha``).
     eager_alpha = False
 
-    def _partitioned_possible(self):
-        if not self.partitioned or self.use_hyper_deriv or self.T is not None or not self._fast_fit_possible():
+    def _partitioned_possible(self, model=_UNRESOLVED):
+        if not self.partitioned or self.use_hyper_deriv or self.T is not None:
             return False
-        terms = self._native_terms()
-        if terms is None or len(terms) != 1 or terms[0][0] in _GIBBS:     # (the multi-GPU engines have no Gibbs builder)
-            return False
-        if self._has_masked():                # (... and know nothing of the masked encoding: a masked model is not partitioned)
+        model = self._device_model() if model is _UNRESOLVED else model
+        # (one native term without warp layers; the multi-GPU engines have no Gibbs builder and know nothing of the masked encoding)
+        if (not self._fast_fit_possible(model) or model[1] or len(model[0]) != 1 or model[0][0][0] in _GIBBS
+                or self._has_masked()):
             return False
         import torch.distributed as dist
         return dist.is_available() and dist.is_initialized()
@@ -155,13 +173,7 @@ class GaussianProcess(object):
         # The reference keeps the GP picklable for its process pools (gaussian_process.py:1701-1703);
         # device handles never cross a pickle: they are re-created lazily in the new process.
         st = dict(self.__dict__)
-        st["_ctx_obj"] = None
-        st["_scratch_ctx"] = None
-        st["_ctx_pool"] = None
-        st["_data_on_device"] = False
-        st["_cache"] = {}
-        st["_fit_mode"] = None
-        st["_dist_plan"] = None
+        self._reset_device_state(st)
         st["K_up_to_date"] = False
         return st
 
@@ -285,49 +297,30 @@ class GaussianProcess(object):
             k = self.noise_k if noise else self.k
         Xi = np.atleast_2d(np.asarray(Xi, dtype=float))
         ni = np.atleast_2d(np.asarray(ni, dtype=int))
+        symmetric = Xj is None
+        Xj = None if symmetric else np.atleast_2d(np.asarray(Xj, dtype=float))
+        nj = None if symmetric else np.atleast_2d(np.asarray(nj, dtype=int))
         if k is self.k and isinstance(k, WarpedKernel) and hyper_deriv is None and self.X is not None:
             model = self._device_model()
             if model is not None:
                 # the GP's own warped model: the builder on the warped points (gpt_set_warp needs the resident data for num_dim)
-                ctx = self._ctx
-                if not self._data_on_device:
-                    self._upload_data(ctx)
-                    self._data_on_device = True
+                ctx = self._resident_ctx()
                 ctx.set_warp(model[1])
-                Xj_ = None if Xj is None else np.atleast_2d(np.asarray(Xj, dtype=float))
-                nj_ = None if Xj is None else np.atleast_2d(np.asarray(nj, dtype=int))
-                out = None
-                for t in model[0]:
-                    Kt = (ctx.kbuild2(t[0], t[1], t[2], t[3], Xi, ni, Xj_, nj_) if len(t) == 4
-                          else ctx.kbuild(t[0], t[1], Xi, ni, Xj_, nj_))
-                    out = Kt if out is None else out + Kt
-                return out
+                return _gram(ctx, model[0], Xi, ni, Xj, nj)
         kid = getattr(k, "_gpt_kernel_id", None)
         if kid is not None and type(k).__call__ in (Kernel.__call__, _M52_CALL, _ZERO_CALL):
             if kid == _lib.KERNEL_M52 and hyper_deriv is not None:
                 raise NotImplementedError("Hyperparameter derivatives have not been implemented!")
-            Xj_ = None if Xj is None else np.atleast_2d(np.asarray(Xj, dtype=float))
-            nj_ = None if Xj is None else np.atleast_2d(np.asarray(nj, dtype=int))
-            return self._plain_ctx().kbuild(kid, k._native_params(), Xi, ni, Xj_, nj_, hyper_deriv=hyper_deriv,
+            return self._plain_ctx().kbuild(kid, k._native_params(), Xi, ni, Xj, nj, hyper_deriv=hyper_deriv,
                                             noise_n=getattr(k, "n", None))
-        if type(k) is ProductKernel and hyper_deriv is None and k._native_factors() is not None:
-            nat = k._native_factors()
-            Xj_ = None if Xj is None else np.atleast_2d(np.asarray(Xj, dtype=float))
-            nj_ = None if Xj is None else np.atleast_2d(np.asarray(nj, dtype=int))
-            return self._plain_ctx().kbuild2(nat[0], nat[1], nat[2], nat[3], Xi, ni, Xj_, nj_)
-        if type(k) is MaskedKernel and hyper_deriv is None and k._native_term() is not None:
-            # a masked kernel on its device route (kernel/masked.py): the builder, like the native kernel it is encoded as
-            nat = k._native_term()
-            Xj_ = None if Xj is None else np.atleast_2d(np.asarray(Xj, dtype=float))
-            nj_ = None if Xj is None else np.atleast_2d(np.asarray(nj, dtype=int))
-            if len(nat) == 4:
-                return self._plain_ctx().kbuild2(nat[0], nat[1], nat[2], nat[3], Xi, ni, Xj_, nj_)
-            return self._plain_ctx().kbuild(nat[0], nat[1], Xi, ni, Xj_, nj_)
-        symmetric = Xj is None
+        # a product of native kernels, or a masked kernel on its device route (kernel/masked.py): the builder, as one term
+        nat = None
+        if hyper_deriv is None and type(k) in (ProductKernel, MaskedKernel):
+            nat = k._native_factors() if type(k) is ProductKernel else k._native_term()
+        if nat is not None:
+            return _gram(self._plain_ctx(), [nat], Xi, ni, Xj, nj)
         if symmetric:
             Xj, nj = Xi, ni
-        Xj = np.atleast_2d(np.asarray(Xj, dtype=float))
-        nj = np.atleast_2d(np.asarray(nj, dtype=int))
         M, P = Xi.shape[0], Xj.shape[0]
         Kij = k(np.repeat(Xi, P, axis=0), np.tile(Xj, (M, 1)), np.repeat(ni, P, axis=0), np.tile(nj, (M, 1)),
                 hyper_deriv=hyper_deriv, symmetric=symmetric)
@@ -353,10 +346,8 @@ class GaussianProcess(object):
 
     def _noise_K(self):
         N = self.X.shape[0]
-        if isinstance(self.noise_k, ZeroKernel):
-            return np.zeros((N, N))
         if isinstance(self.noise_k, DiagonalNoiseKernel):
-            return self.noise_k.params[0] ** 2.0 * np.eye(N)
+            return self._noise_var() * np.eye(N)
         return self.compute_Kij(self.X, None, self.n, None, noise=True)
 
     @property
@@ -385,6 +376,28 @@ class GaussianProcess(object):
         ctx.set_data(self.X, self.n)
         if self.T is not None:
             ctx.set_T(self.T)
+
+    def _resident_ctx(self):
+        """The instance's context with the data on it: uploaded unless resident."""
+        ctx = self._ctx
+        if not self._data_on_device:
+            self._upload_data(ctx)
+            self._data_on_device = True
+        return ctx
+
+    # ---- the noise kernel as the device takes it: a variance in the fit, (parameters, orders) in a noisy prediction -------------
+    def _noise_var(self):
+        return 0.0 if isinstance(self.noise_k, ZeroKernel) else self.noise_k.params[0] ** 2.0
+
+    def _diagonal_noise(self):
+        return isinstance(self.noise_k, DiagonalNoiseKernel) and not isinstance(self.noise_k, ZeroKernel)
+
+    def _noise_is_free(self):
+        return self._diagonal_noise() and not self.noise_k.fixed_params[0]
+
+    def _prediction_noise(self, noise):
+        """``(noise_params, noise_n)`` of a prediction on the kernel route, ``(None, None)`` for a noise-free one."""
+        return (self.noise_k.params, self.noise_k.n) if noise and self._diagonal_noise() else (None, None)
 
     def _native_terms(self, k=None):
         """The covariance kernel as a list of ``(kernel_id, params)`` terms the HIP library evaluates itself -- a native
@@ -439,9 +452,11 @@ class GaussianProcess(object):
         ctx = self._ctx
         return ctx if ctx._warp_key is None else _lib.default_context(self.device)
 
-    def _fast_fit_possible(self):
-        return (self._device_model() is not None and
-                isinstance(self.noise_k, (ZeroKernel, DiagonalNoiseKernel)))
+    def _fast_fit_possible(self, model=_UNRESOLVED):
+        """The kernel route: the library evaluates the covariance kernel (``model``: what :meth:`_device_model` gave, where the
+        caller has resolved it already) and the noise is a variance on the diagonal."""
+        model = self._device_model() if model is _UNRESOLVED else model
+        return model is not None and isinstance(self.noise_k, (ZeroKernel, DiagonalNoiseKernel))
 
     def _device_fit(self, ctx, terms, noise_var, y_alph, diag_add):
         if any(len(t) == 4 for t in terms):
@@ -465,13 +480,13 @@ class GaussianProcess(object):
         self._cache = {}
         y_alph = self._y_alph()
         diag_add = self.diag_factor * sys.float_info.epsilon
-        if not need_factor and self._partitioned_possible():
+        model = self._device_model()                 # resolved once per evaluation: for GibbsKernel1dGP a host solve
+        if not need_factor and self._partitioned_possible(model):
             from .dist import DistributedLML
             if self._dist_plan is None:
                 self._dist_plan = DistributedLML(self.X, self.n, nb=self.partition_block, device=self.device)
-            kid, kparams = self._native_terms()[0]
-            noise_var = 0.0 if isinstance(self.noise_k, ZeroKernel) else self.noise_k.params[0] ** 2.0
-            ll_data, _ = self._dist_plan.fit(kid, kparams, y_alph, self.err_y, noise_var=noise_var,
+            kid, kparams = model[0][0]
+            ll_data, _ = self._dist_plan.fit(kid, kparams, y_alph, self.err_y, noise_var=self._noise_var(),
                                              diag_factor=self.diag_factor)
             self._fit_mode = "partitioned"
             self.ll = ll_data + self.hyperprior(self.params)
@@ -480,17 +495,11 @@ class GaussianProcess(object):
         ctx = self._ctx
         # (eager: the device enqueues alpha behind the factorisation of the same call; get_alpha below is then a copy)
         ctx.set_option("eager_alpha", 1 if self.eager_alpha else 0)
-        if self._fast_fit_possible():
-            if not self._data_on_device:
-                self._upload_data(ctx)
-                self._data_on_device = True
-            if isinstance(self.noise_k, ZeroKernel):
-                noise_var = 0.0
-            else:
-                noise_var = self.noise_k.params[0] ** 2.0
-            terms, layers = self._device_model()
+        if self._fast_fit_possible(model):
+            self._resident_ctx()
+            terms, layers = model
             ctx.set_warp(layers)                 # (no-op unless the layers or their parameters changed)
-            ll_data, _ = self._device_fit(ctx, terms, noise_var, y_alph, diag_add)
+            ll_data, _ = self._device_fit(ctx, terms, self._noise_var(), y_alph, diag_add)
             self._fit_mode = "kernel"
         else:
             # T (linear transform) or a Python-defined kernel: K is still built by the GPU builder
@@ -550,19 +559,14 @@ class GaussianProcess(object):
             # transform T the pass runs over the latent points against T^T K_tot^-1 T (two more GEMMs on the device).
             g_dev = ctx.ll_grad(tix, lix)
             ll_deriv[:len(free_idx)] = g_dev[:-1]
-            if isinstance(self.noise_k, DiagonalNoiseKernel) and not isinstance(self.noise_k, ZeroKernel) \
-                    and not self.noise_k.fixed_params[0]:
+            if self._noise_is_free():
                 ll_deriv[len(self.k.free_params)] = 2.0 * self.noise_k.params[0] * g_dev[-1]
         else:
-            if isinstance(self.noise_k, ZeroKernel):
-                knk = self.k
-            elif isinstance(self.noise_k, DiagonalNoiseKernel):
-                knk = self.k
-                if not self.noise_k.fixed_params[0]:
-                    # (the reference does not transform this term: 2 sigma_n eye(len(y)), ref :1482-1488)
-                    ll_deriv[len(self.k.free_params)] = term(2.0 * self.noise_k.params[0] * np.eye(Ny), transform=False)
-            else:
+            if not isinstance(self.noise_k, DiagonalNoiseKernel):
                 knk = self.k + self.noise_k
+            elif self._noise_is_free():
+                # (the reference does not transform this term: 2 sigma_n eye(len(y)), ref :1482-1488)
+                ll_deriv[len(self.k.free_params)] = term(2.0 * self.noise_k.params[0] * np.eye(Ny), transform=False)
             free_idx = np.arange(0, len(knk.params), dtype=int)[~np.asarray(knk.fixed_params, dtype=bool)]
             for i, pi in enumerate(free_idx):
                 ll_deriv[i] = term(self.compute_Kij(self.X, None, self.n, None, k=knk, hyper_deriv=int(pi)))
@@ -573,10 +577,15 @@ class GaussianProcess(object):
                 if self.T is not None:
                     dmu = self.T.dot(dmu)
                 ll_deriv[i + len(knk.free_params)] = dmu.dot(alpha)
+        self.ll_deriv = ll_deriv + self._hyperprior_gradient()
+
+    def _hyperprior_gradient(self):
+        """The log-prior's derivative with respect to every free hyperparameter (ref :1517-1520)."""
         free_idx = np.arange(0, len(self.params), dtype=int)[~np.asarray(self.fixed_params[:], dtype=bool)]
+        grad = np.zeros(len(free_idx))
         for i, pi in enumerate(free_idx):
-            ll_deriv[i] += self.hyperprior(self.params[:], hyper_deriv=int(pi))
-        self.ll_deriv = ll_deriv
+            grad[i] = self.hyperprior(self.params[:], hyper_deriv=int(pi))
+        return grad
 
     # ---- device gradient for every native kernel (gpt_ll_grad_diff; DESIGN.md 7.1) ------------
     def _ll_gradient_refusal(self):
@@ -584,10 +593,10 @@ class GaussianProcess(object):
         model = self._device_model()
         if model is not None and model[1]:
             return "a warped model (WarpedKernel layers evaluated on the device)"
-        if not self._fast_fit_possible():
+        if not self._fast_fit_possible(model):
             return ("the matrix route (a covariance or noise kernel the library does not evaluate itself: K_tot is assembled "
                     "on the host)")
-        if self._partitioned_possible():
+        if self._partitioned_possible(model):
             return "a partitioned fit (the factor is spread over the ranks of the job)"
         return None
 
@@ -663,8 +672,7 @@ class GaussianProcess(object):
         for s, v in zip(slot, g_dev[:-1]):
             grad[s] += v
         nk = len(self.k.free_params)
-        if isinstance(self.noise_k, DiagonalNoiseKernel) and not isinstance(self.noise_k, ZeroKernel) \
-                and not self.noise_k.fixed_params[0]:
+        if self._noise_is_free():
             grad[nk] = 2.0 * self.noise_k.params[0] * g_dev[-1]
         if self.mu is not None:
             alpha = ctx.get_alpha(len(self.y))
@@ -674,10 +682,7 @@ class GaussianProcess(object):
                 if self.T is not None:
                     dmu = self.T.dot(dmu)
                 grad[i + nk + len(self.noise_k.free_params)] = dmu.dot(alpha)
-        free_idx = np.arange(0, len(self.params), dtype=int)[~np.asarray(self.fixed_params[:], dtype=bool)]
-        for i, pi in enumerate(free_idx):
-            grad[i] += self.hyperprior(self.params[:], hyper_deriv=int(pi))
-        return grad
+        return grad + self._hyperprior_gradient()
 
     def _device_grad_objective(self):
         """``(fun, jac)`` for scipy.optimize.minimize: ``fun`` is ``update_hyperparameters``, ``jac`` minus :meth:`ll_gradient`
@@ -798,6 +803,56 @@ class GaussianProcess(object):
             self._assign_free(keep)
             self.partitioned = keep_partitioned
 
+    def _batch_job(self, row, extra):
+        """The current hyperparameters as one element of a batched fit; ``None`` for a kernel whose device parameters need a solve
+        that failed (the evaluation fails: the caller drops the row)."""
+        try:
+            terms, layers = self._device_model()
+        except np.linalg.LinAlgError:
+            return None
+        return _BatchJob(row, terms, layers, self._noise_var(), np.array(self._y_alph(), dtype=float), extra)
+
+    def _fit_batched(self, jobs, per, release_per, done, rejected):
+        """The chunk loop of the batched routes (ll_batch, compute_from_MCMC): ``jobs`` through ``gpt_fit_batch_terms``,
+        ``batch_grid`` per launch sequence or as many as fit ``batch_grid_bytes`` and HALF of the device memory free right now (other
+        ranks / processes may share the GPU) at ``per`` bytes an element -- and should the allocation still fail, half as many.
+        ``done(chunk, ll, info)`` takes a fitted chunk while it is resident; ``rejected(chunk)`` one the library refused (an argument
+        of ONE element, e.g. a kernel parameter out of its domain, fails the whole call).  A scratch above 2 GiB (``release_per`` bytes
+        an element) goes back at the end.  Returns the jobs NOT evaluated: all when they are not one model shape, the remainder
+        when not even one element fits."""
+        if not jobs:
+            return []
+        ctx, first = self._resident_ctx(), jobs[0]
+        if any(_terms_shape(j.terms) != _terms_shape(first.terms) or [t for t, _ in j.layers] != [t for t, _ in first.layers]
+               for j in jobs):
+            return jobs
+        self._cache = {}
+        err_y = np.asarray(self.err_y, dtype=float)
+        diag_add = self.diag_factor * sys.float_info.epsilon
+        budget = min(int(self.batch_grid_bytes), ctx.mem_info()[0] // 2)
+        G = max(1, min(int(self.batch_grid), budget // per))
+        s0 = 0
+        while s0 < len(jobs) and G >= 1:
+            chunk = jobs[s0:s0 + G]
+            try:
+                if first.layers:
+                    ctx.set_warp_batch([j.layers for j in chunk])
+                else:
+                    ctx.set_warp(None)                       # (layers an earlier warped model left on the context)
+                ll, _, info = ctx.fit_batch_terms([j.terms for j in chunk], np.array([j.noise_var for j in chunk]),
+                                                  np.array([j.y_alph for j in chunk]), err_y, diag_add)
+                done(chunk, ll, info)
+            except MemoryError:
+                ctx.release_batch_scratch()
+                G //= 2
+                continue
+            except (ValueError, ArithmeticError):
+                rejected(chunk)
+            s0 += len(chunk)
+        if release_per * min(G, len(jobs)) > (2 << 30):
+            ctx.release_batch_scratch()                      # a large scratch goes back to the device once the list is done
+        return jobs[s0:]
+
     def _ll_batch_local(self, param_list, exit_on_bounds):
         out = np.full(len(param_list), -np.inf)
         if not param_list:
@@ -819,79 +874,47 @@ class GaussianProcess(object):
             prior = self.hyperprior(self.params)
             if exit_on_bounds and np.isinf(prior):
                 continue                                            # impossible parameters: stays -inf
-            noise_var = 0.0 if isinstance(self.noise_k, ZeroKernel) else self.noise_k.params[0] ** 2.0
+            job = self._batch_job(i, prior)
+            if job is not None:
+                jobs.append(job)
+        if not jobs:
+            return out
+
+        def fit_one(ctx, j):
             try:
-                terms, layers = self._device_model()
-            except np.linalg.LinAlgError:
-                continue                                            # (a kernel whose device parameters need a solve that failed: -inf)
-            jobs.append((i, terms, layers, noise_var,
-                         np.array(self._y_alph(), dtype=float), prior))
-        if not self._data_on_device:
-            self._upload_data(self._ctx)
-            self._data_on_device = True
-        version = getattr(self, "_data_version", 0)
-        # (a warped model: the elements' warp parameters differ, set_warp_batch gives every element its own warped points; the
-        # layer types are the model's, the same in every element)
-        if (max(len(self.y), self.X.shape[0]) <= self.batch_grid_max_n and int(self.batch_grid) > 1 and jobs
-                and all([t for t, _ in j[2]] == [t for t, _ in jobs[0][2]] for j in jobs)
-                and all([(t[0], t[2] if len(t) == 4 else -1) for t in j[1]] == [(t[0], t[2] if len(t) == 4 else -1) for t in jobs[0][1]]
-                        for j in jobs)):
+                ctx.set_warp(j.layers)
+                out[j.row] = self._device_fit(ctx, j.terms, j.noise_var, j.y_alph, diag_add)[0] + j.extra
+            except (np.linalg.LinAlgError, ValueError, ArithmeticError):
+                pass                                                # the +inf policy of update_hyperparameters
+
+        if max(len(self.y), self.X.shape[0]) <= self.batch_grid_max_n and int(self.batch_grid) > 1:
             # small N: the whole batch in ONE launch sequence (gpt_fit_batch_terms: every kernel of the factorisation carries the
             # batch in a grid dimension), batch_grid evaluations at a time; bit-identical to one gpt_fit_terms per vector.  Any
             # model of native kernels -- sums, products, with or without the linear transform T (the reference's
-            # grids take any model: ref gaussian_process.py:1607-1692)
-            err_y = np.asarray(self.err_y, dtype=float)
-            self._cache = {}
+            # grids take any model: ref gaussian_process.py:1607-1692).  A warped model: the elements' warp parameters differ,
+            # set_warp_batch gives every element its own warped points
             NP = -(-(len(self.y) + 1) // 128) * 128
-            # chunk size: batch_grid, or what fits batch_grid_bytes, or what fits HALF of the device memory that is free right now
-            # (other ranks / processes may share the GPU) -- and should the allocation still fail, half as many, down to the
-            # one-context-per-thread path below (a MemoryError used to abort ll_batch / compute_ll_matrix)
-            budget = min(int(self.batch_grid_bytes), self._ctx.mem_info()[0] // 2)
-            per = 8 * NP * NP + 8 * 9216 * (NP // 128) + (8 * self.X.shape[0] * (self.num_dim + 1) if jobs[0][2] else 0)
+            per = 8 * NP * NP + 8 * 9216 * (NP // 128) + (8 * self.X.shape[0] * (self.num_dim + 1) if jobs[0].layers else 0)
             if self.T is not None:                               # + every element's K over the latent points and T K
                 NxP = -(-self.X.shape[0] // 16) * 16
                 per += 8 * NxP * NxP + 8 * (-(-len(self.y) // 64) * 64) * NxP
-            G = max(1, min(int(self.batch_grid), budget // per))
-            s0 = 0
-            while s0 < len(jobs) and G >= 1:
-                chunk = jobs[s0:s0 + G]
-                try:
-                    if chunk[0][2]:
-                        self._ctx.set_warp_batch([j[2] for j in chunk])
-                    else:
-                        self._ctx.set_warp(None)             # (layers an earlier warped model left on the context)
-                    ll, _, info = self._ctx.fit_batch_terms([j[1] for j in chunk], np.array([j[3] for j in chunk]),
-                                                            np.array([j[4] for j in chunk]), err_y, diag_add)
-                except MemoryError:
-                    self._ctx.release_batch_scratch()
-                    G //= 2
-                    continue
-                except (ValueError, ArithmeticError):
-                    # an argument the library rejects for one element (e.g. a kernel parameter out of its domain) fails the
-                    # whole call: that chunk one vector at a time, with the +inf policy of update_hyperparameters
-                    ll, info = np.zeros(len(chunk)), np.ones(len(chunk), dtype=int)
-                    for q, j in enumerate(chunk):
-                        try:
-                            self._ctx.set_warp(j[2])
-                            ll[q], info[q] = self._device_fit(self._ctx, j[1], j[3], j[4], diag_add)[0], 0
-                        except (np.linalg.LinAlgError, ValueError, ArithmeticError):
-                            pass
+
+            def store(chunk, ll, info):
                 for j, l, bad in zip(chunk, ll, info):
                     if bad == 0:
-                        out[j[0]] = l + j[5]
-                s0 += len(chunk)
-            if 8 * NP * NP * min(G, len(jobs)) > (2 << 30):
-                self._ctx.release_batch_scratch()            # a large scratch goes back to the device once the list is done
-            if s0 >= len(jobs):
-                return out
-            jobs = jobs[s0:]                                  # (no chunk size fits: the rest one context per thread)
-        ctxs = [[self._ctx, version]] + self._batch_contexts(B)
+                        out[j.row] = l + j.extra
+
+            # (a chunk the library rejects: one vector at a time)
+            jobs = self._fit_batched(jobs, per, 8 * NP * NP, store, lambda chunk: [fit_one(self._ctx, j) for j in chunk])
+            if not jobs:
+                return out                                       # (else no chunk size fits: the rest one context per thread)
+        version = getattr(self, "_data_version", 0)
+        ctxs = [[self._resident_ctx(), version]] + self._batch_contexts(B)
         for c in ctxs[1:]:
             if c[1] != version:                                      # data added since this context last saw it
                 self._upload_data(c[0])
                 c[1] = version
         self._cache = {}
-        err_y = np.asarray(self.err_y, dtype=float)
         import threading
         lock = threading.Lock()
         it = iter(jobs)
@@ -902,13 +925,7 @@ class GaussianProcess(object):
                     job = next(it, None)
                 if job is None:
                     return
-                i, terms, layers, noise_var, y_alph, prior = job
-                try:
-                    ctx.set_warp(layers)
-                    ll_data, _ = self._device_fit(ctx, terms, noise_var, y_alph, diag_add)
-                    out[i] = ll_data + prior
-                except (np.linalg.LinAlgError, ValueError, ArithmeticError):
-                    pass                                            # the +inf policy of update_hyperparameters
+                fit_one(ctx, job)
         threads = [threading.Thread(target=worker, args=(c[0],)) for c in ctxs[:B]]
         with _lib.concurrent_evaluations():          # several chains at once: event edges (include/gpt_hip.h)
             for t in threads:
@@ -1124,10 +1141,7 @@ class GaussianProcess(object):
         need_std = return_std or need_cov
         if self._fit_mode == "kernel":
             want = 2 if need_cov else (1 if need_std else 0)
-            noise_params = noise_n = None
-            if noise and isinstance(self.noise_k, DiagonalNoiseKernel) and not isinstance(self.noise_k, ZeroKernel):
-                noise_params, noise_n = self.noise_k.params, self.noise_k.n
-            mean, std, covariance = self._ctx.predict(Xstar, n, want, noise_params, noise_n)
+            mean, std, covariance = self._ctx.predict(Xstar, n, want, *self._prediction_noise(noise))
         else:
             mean, std, covariance = self._predict_general(Xstar, n, noise, need_std)
         mean_func = None
@@ -1207,9 +1221,9 @@ class GaussianProcess(object):
                "cov": np.full((S, M, M), np.nan) if want_cov else None,
                "cov_sum": np.zeros((M, M)) if want_cov_sum else None}
         ok = np.zeros(S, dtype=bool)
-        noise_n = None
-        if noise and isinstance(self.noise_k, DiagonalNoiseKernel) and not isinstance(self.noise_k, ZeroKernel):
-            noise_n = np.broadcast_to(np.asarray(self.noise_k.n, dtype=np.int32), (self.num_dim,))
+        noise_n = self._prediction_noise(noise)[1]      # (the batch's noise variances are those of its fits)
+        if noise_n is not None:
+            noise_n = np.broadcast_to(np.asarray(noise_n, dtype=np.int32), (self.num_dim,))
         saved = np.array(self.free_params[:], dtype=float)
         keep_partitioned = self.partitioned
         self.partitioned = False
@@ -1265,75 +1279,47 @@ class GaussianProcess(object):
         """The batched route: chunks of rows through gpt_fit_batch_terms + gpt_predict_batch.  Fills ``res`` / ``ok`` for the
         rows it evaluates and returns the rows left to the loop route."""
         N = len(self.y)
-        if (not rows or len(rows) < int(self.mcmc_batch_min_rows) or not self._fast_fit_possible() or self.T is not None
-                or max(N, self.X.shape[0]) > self.batch_grid_max_n or int(self.batch_grid) < 1
-                or self._device_model()[1]):                 # (a warped model: the loop route, each row a device fit + predict)
+        if not rows or len(rows) < int(self.mcmc_batch_min_rows):
+            return rows
+        model = self._device_model()
+        if (not self._fast_fit_possible(model) or self.T is not None or max(N, self.X.shape[0]) > self.batch_grid_max_n
+                or int(self.batch_grid) < 1 or model[1]):    # (a warped model: the loop route, each row a device fit + predict)
             return rows
         jobs = []
         for i in rows:
             self._assign_free(trace[i])
-            try:
-                terms = self._native_terms()
-            except np.linalg.LinAlgError:
-                continue                                     # (as a fit that fails: the row is dropped)
-            noise_var = 0.0 if isinstance(self.noise_k, ZeroKernel) else self.noise_k.params[0] ** 2.0
-            mu_star = None if self.mu is None else np.asarray(self.mu(Xs, ns), dtype=float)
-            jobs.append((i, terms, noise_var, np.array(self._y_alph(), dtype=float), mu_star))
-        shape = [(t[0], t[2] if len(t) == 4 else -1) for t in jobs[0][1]]
-        if any([(t[0], t[2] if len(t) == 4 else -1) for t in j[1]] != shape for j in jobs):
-            return rows
-        ctx = self._ctx
-        if not self._data_on_device:
-            self._upload_data(ctx)
-            self._data_on_device = True
-        self._cache = {}
+            job = self._batch_job(i, None if self.mu is None else np.asarray(self.mu(Xs, ns), dtype=float))
+            if job is not None:                              # (else as a fit that fails: the row is dropped)
+                jobs.append(job)
         want_var, want_cov, want_sum = res["var"] is not None, res["cov"] is not None, res["cov_sum"] is not None
         M = Xs.shape[0]
         NP, MP = -(-(N + 1) // 128) * 128, -(-M // 64) * 64
         per = 8 * (NP * NP + 9216 * (NP // 128) + MP * NP + (MP * MP if want_cov else 0))
-        budget = min(int(self.batch_grid_bytes), ctx.mem_info()[0] // 2)
-        G = max(1, min(int(self.batch_grid), budget // per))
-        err_y = np.asarray(self.err_y, dtype=float)
-        diag_add = self.diag_factor * sys.float_info.epsilon
-        rest, s0 = [], 0
-        while s0 < len(jobs):
-            chunk = jobs[s0:s0 + G]
-            try:
-                _, _, info = ctx.fit_batch_terms([j[1] for j in chunk], np.array([j[2] for j in chunk]),
-                                                 np.array([j[3] for j in chunk]), err_y, diag_add)
-                keep = info == 0
-                if keep.any():
-                    mean, var, cov, cov_sum = ctx.predict_batch(Xs, ns, keep, noise_n, want_var, want_cov, want_sum)
-            except MemoryError:
-                ctx.release_batch_scratch()
-                if G == 1:
-                    rest.extend(j[0] for j in jobs[s0:])
-                    break
-                G //= 2
-                continue
-            except (ValueError, ArithmeticError):
-                # a parameter the library rejects fails the whole chunk: its rows one at a time on the loop route
-                rest.extend(j[0] for j in chunk)
-                s0 += len(chunk)
-                continue
+        rest = []
+
+        def predict(chunk, _, info):
+            keep = info == 0
+            if not keep.any():
+                return
+            mean, var, cov, cov_sum = self._ctx.predict_batch(Xs, ns, keep, noise_n, want_var, want_cov, want_sum)
             for q, j in enumerate(chunk):
                 if not keep[q]:
                     continue                                 # not positive definite: the evaluation fails, the row is dropped
-                i = j[0]
-                res["mean"][i] = mean[q] if j[4] is None else mean[q] + j[4]
-                if j[4] is not None:
-                    res["mean_func"][i] = j[4]
+                res["mean"][j.row] = mean[q] if j.extra is None else mean[q] + j.extra
+                if j.extra is not None:
+                    res["mean_func"][j.row] = j.extra
                 if want_var:
-                    res["var"][i] = var[q]
+                    res["var"][j.row] = var[q]
                 if want_cov:
-                    res["cov"][i] = cov[q]
-                ok[i] = True
-            if want_sum and keep.any():
+                    res["cov"][j.row] = cov[q]
+                ok[j.row] = True
+            if want_sum:
                 res["cov_sum"] += cov_sum
-            s0 += len(chunk)
-        if 8 * (NP * NP + MP * NP) * min(G, len(jobs)) > (2 << 30):
-            ctx.release_batch_scratch()                      # a large scratch goes back to the device once the trace is done
-        return sorted(rest)
+
+        # (a parameter the library rejects fails the whole chunk: its rows, like the rows left when not even one element fits, one
+        # at a time on the loop route)
+        left = self._fit_batched(jobs, per, 8 * (NP * NP + MP * NP), predict, lambda chunk: rest.extend(j.row for j in chunk))
+        return sorted(rest + [j.row for j in left])
 
     def compute_from_MCMC(self, X, n=0, return_mean=True, return_std=True, return_cov=False, return_samples=False,
                           return_mean_func=False, num_samples=1, noise=False, samp_kwargs={}, sampler=None, flat_trace=None,
@@ -1515,10 +1501,7 @@ class GaussianProcess(object):
             self.compute_K_L_alpha_ll()
             if self._fit_mode == "kernel":
                 Xs, ns, _ = self._check_predict_args(Xstar, n)
-                noise = bool(kwargs.get("noise", False))
-                noise_params = noise_n = None
-                if noise and isinstance(self.noise_k, DiagonalNoiseKernel) and not isinstance(self.noise_k, ZeroKernel):
-                    noise_params, noise_n = self.noise_k.params, self.noise_k.n
+                noise_params, noise_n = self._prediction_noise(kwargs.get("noise", False))
                 M = Xs.shape[0]
                 ne = M if (num_eig is None or num_eig > M) else max(int(num_eig), 1)
                 rv = np.atleast_2d(np.asarray(rand_vars, dtype=float))[:ne, :]
