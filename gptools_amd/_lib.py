@@ -66,6 +66,8 @@ SIGNATURES = {
     "gpt_release_batch_scratch": (C.c_int, [_vp]),
     "gpt_fit_batch_terms": (C.c_int, [_vp, C.c_int, C.c_int, _ip, _ip, _dp, _ip, _ip, _dp, _dp, _dp, C.c_double, _dp, _dp, _ip]),
     "gpt_predict_batch": (C.c_int, [_vp, _dp, _ip, _i64, _ip, _ip, _dp, _dp, _dp, _dp]),
+    "gpt_ensemble_run": (C.c_int, [_vp, C.c_int, _ip, _ip, _ip, _ip, _dp, C.c_int, _ip, _dp, _dp, C.c_double, _dp, _dp, C.c_double,
+                                   C.c_double, C.c_int, C.c_int, C.c_double, _dp, _ip, _dp, C.c_int, _dp, _dp, _dp, _dp, _ip]),
     "gpt_fit_matrix": (C.c_int, [_vp, _dp, _i64, _dp, _dp, _dp]),
     "gpt_get_L": (C.c_int, [_vp, _dp]),
     "gpt_get_alpha": (C.c_int, [_vp, _dp]),
@@ -495,6 +497,32 @@ class Context(object):
         check(self._lib.gpt_fit_batch_terms(self.handle, B, len(ids), iptr(ids), iptr(ids2), dptr(params), iptr(npar), iptr(npar1),
                                             dptr(noise_var), dptr(y), dptr(err_y), float(diag_add), dptr(ll), dptr(ld), iptr(info)))
         return ll, ld, info
+
+    def ensemble_run(self, terms, free_idx, lo, hi, log_prior, noise_var, y, err_y, diag_add, a, u_stretch, partner, u_accept,
+                     pos, lnp, max_chunk):
+        """gpt_ensemble_run: ``u_stretch.shape[0]`` steps of the ensemble sampler's loop inside the library.  ``terms``: the model
+        as :meth:`fit_terms` takes it, at the values of the parameters that are not free; ``free_idx[f]``: the place of free
+        parameter f in the concatenated term parameters, or their count for the noise sigma; ``lo`` / ``hi``: the prior's box,
+        ``log_prior`` its constant log-density; the variates ``(nsteps, nwalkers)`` as ``sampler.draw_variates`` gives them;
+        ``pos`` (nwalkers, nfree) and ``lnp`` (nwalkers,) the start.  Returns ``(chain (nsteps, nwalkers, nfree), lnp_chain
+        (nsteps, nwalkers), naccept (nwalkers,))``; the walkers' last state is the chain's last step."""
+        ids, ids2, npar, npar1, base = self._pack_terms(terms)
+        free_idx, lo, hi = i32(free_idx), f64(lo), f64(hi)
+        u_stretch, partner, u_accept = f64(u_stretch), i32(partner), f64(u_accept)
+        pos, lnp, y, err_y = np.array(pos, dtype=np.float64, order="C"), np.array(lnp, dtype=np.float64), f64(y), f64(err_y)
+        nsteps, K = u_stretch.shape
+        nfree = free_idx.shape[0]
+        if (pos.shape != (K, nfree) or lnp.shape != (K,) or partner.shape != (nsteps, K) or u_accept.shape != (nsteps, K)
+                or lo.shape != (nfree,) or hi.shape != (nfree,) or y.shape != err_y.shape or y.ndim != 1):
+            raise ValueError("ensemble_run: variates (nsteps, nwalkers), pos (nwalkers, nfree), lnp (nwalkers,), lo / hi (nfree,), "
+                             "y and err_y (N,) expected")
+        chain, lnp_chain = np.empty((nsteps, K, nfree)), np.empty((nsteps, K))
+        naccept = np.zeros(K, dtype=np.int32)
+        check(self._lib.gpt_ensemble_run(self.handle, len(ids), iptr(ids), iptr(ids2), iptr(npar), iptr(npar1), dptr(base), nfree,
+                                         iptr(free_idx), dptr(lo), dptr(hi), float(log_prior), dptr(y), dptr(err_y), float(diag_add),
+                                         float(noise_var), K, nsteps, float(a), dptr(u_stretch), iptr(partner), dptr(u_accept),
+                                         int(max_chunk), dptr(pos), dptr(lnp), dptr(chain), dptr(lnp_chain), iptr(naccept)))
+        return chain, lnp_chain, naccept
 
     def predict_batch(self, Xstar, nstar, keep, noise_n=None, want_var=True, want_cov=False, want_cov_sum=False):
         """gpt_predict_batch: prediction at ``Xstar`` (M, D) from every element of the resident batch (the last

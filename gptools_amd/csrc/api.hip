@@ -237,3 +237,4 @@ static int stream_follows(gpt_ctx *c, hipStream_t from, hipStream_t to, size_t i
 #include "api_predict.inc"      // gpt_predict, gpt_cov_sample, gpt_solve_L / gpt_cho_solve, gpt_potrf_host / gpt_gemm_nt_host
 #include "api_dev.inc"      // device API (gpt_dev_*): raw device pointers on the context's streams, for the one-process-per-GPU engines
 #include "api_plan.inc"      // compiled schedules of the partitioned engines: gpt_plan_* (op list replay, RCCL called directly)
+#include "api_ensemble.inc"      // gpt_ensemble_run: the ensemble sampler's loop (ensemble.hpp) around the batched fit

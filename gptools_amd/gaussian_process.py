@@ -32,7 +32,7 @@ from .error_handling import GPArgumentError, GPImpossibleParamsError
 from .kernel import Kernel, ZeroKernel, DiagonalNoiseKernel, BinaryKernel, SumKernel, ProductKernel
 from .kernel.masked import MaskedKernel
 from .kernel.warping import WarpedKernel, beta_cdf_warp, linear_warp
-from .utils import CombinedBounds
+from .utils import CombinedBounds, ProductJointPrior, UniformJointPrior
 
 __all__ = ["GaussianProcess"]
 
@@ -812,6 +812,19 @@ class GaussianProcess(object):
             return None
         return _BatchJob(row, terms, layers, self._noise_var(), np.array(self._y_alph(), dtype=float), extra)
 
+    def _batch_element_bytes(self, warped):
+        """``(NP, bytes)``: the padded order of one element of a batched fit and the device memory it takes."""
+        NP = -(-(len(self.y) + 1) // 128) * 128
+        per = 8 * NP * NP + 8 * 9216 * (NP // 128) + (8 * self.X.shape[0] * (self.num_dim + 1) if warped else 0)
+        if self.T is not None:                               # + every element's K over the latent points and T K
+            NxP = -(-self.X.shape[0] // 16) * 16
+            per += 8 * NxP * NxP + 8 * (-(-len(self.y) // 64) * 64) * NxP
+        return NP, per
+
+    def _batch_chunk(self, ctx, per):
+        """Elements of one launch sequence: ``batch_grid``, or as many as fit ``batch_grid_bytes`` and half of the free memory."""
+        return max(1, min(int(self.batch_grid), min(int(self.batch_grid_bytes), ctx.mem_info()[0] // 2) // per))
+
     def _fit_batched(self, jobs, per, release_per, done, rejected):
         """The chunk loop of the batched routes (ll_batch, compute_from_MCMC): ``jobs`` through ``gpt_fit_batch_terms``,
         ``batch_grid`` per launch sequence or as many as fit ``batch_grid_bytes`` and HALF of the device memory free right now (other
@@ -829,8 +842,7 @@ class GaussianProcess(object):
         self._cache = {}
         err_y = np.asarray(self.err_y, dtype=float)
         diag_add = self.diag_factor * sys.float_info.epsilon
-        budget = min(int(self.batch_grid_bytes), ctx.mem_info()[0] // 2)
-        G = max(1, min(int(self.batch_grid), budget // per))
+        G = self._batch_chunk(ctx, per)
         s0 = 0
         while s0 < len(jobs) and G >= 1:
             chunk = jobs[s0:s0 + G]
@@ -893,11 +905,7 @@ class GaussianProcess(object):
             # model of native kernels -- sums, products, with or without the linear transform T (the reference's
             # grids take any model: ref gaussian_process.py:1607-1692).  A warped model: the elements' warp parameters differ,
             # set_warp_batch gives every element its own warped points
-            NP = -(-(len(self.y) + 1) // 128) * 128
-            per = 8 * NP * NP + 8 * 9216 * (NP // 128) + (8 * self.X.shape[0] * (self.num_dim + 1) if jobs[0].layers else 0)
-            if self.T is not None:                               # + every element's K over the latent points and T K
-                NxP = -(-self.X.shape[0] // 16) * 16
-                per += 8 * NxP * NxP + 8 * (-(-len(self.y) // 64) * 64) * NxP
+            NP, per = self._batch_element_bytes(bool(jobs[0].layers))
 
             def store(chunk, ll, info):
                 for j, l, bad in zip(chunk, ll, info):
@@ -989,6 +997,152 @@ class GaussianProcess(object):
         ll_vals = self.ll_batch(list(points)).reshape([int(c) for c in counts[:nfree]])
         self.update_hyperparameters(here)
         return (ll_vals, axes)
+
+    # ---- samples of the hyperparameter posterior (ref: gptools/gaussian_process.py:1694-1838) --
+    def _library_stepping(self):
+        """What ``gpt_ensemble_run`` needs to step an ensemble over this GP's free hyperparameters: ``(None, plan)`` with the
+        plan a dict of :meth:`_lib.Context.ensemble_run`'s model arguments -- or ``(refusal, None)``, the refusal a sentence
+        that names what keeps the model on the host route.  No device call."""
+        try:
+            model = self._device_model()
+        except np.linalg.LinAlgError:
+            return "the kernel's device parameters need a host solve, which failed at the current hyperparameters", None
+        if model is None:
+            return ("the covariance kernel is not one the library evaluates itself (a Python-defined kernel, or a tree of kernels "
+                    "it does not take)"), None
+        terms, layers = model
+        if layers:
+            return "the kernel has input-warp layers (WarpedKernel): the library route steps plain models only", None
+        if not isinstance(self.noise_k, (ZeroKernel, DiagonalNoiseKernel)) or len(self.noise_k.params) != 1:
+            return "the noise kernel is neither ZeroKernel nor DiagonalNoiseKernel", None
+        if self.mu is not None:
+            return "the GP has a mean function (mu): its parameters change the targets of every walker", None
+        if self.X is None:
+            return "no data have been added to the GaussianProcess", None
+        if max(len(self.y), self.X.shape[0]) > self.batch_grid_max_n:
+            return "more than batch_grid_max_n = %d points: the batched evaluator does not take them" % self.batch_grid_max_n, None
+        flat, own = _lib.Context._flat_params(terms), np.array(self.k.params, dtype=float)
+        if flat.shape != own.shape or not np.array_equal(flat, own):
+            return ("the parameters the library takes for this kernel are not the kernel's hyperparameters element for element (a "
+                    "MaskedKernel's expansion, a nested GP's weights): only the host can form them"), None
+
+        def leaves(p):
+            return leaves(p.p1) + leaves(p.p2) if type(p) is ProductJointPrior else [p]
+        others = sorted(set(type(p).__name__ for p in leaves(self.hyperprior) if type(p) is not UniformJointPrior))
+        if others:
+            return "the hyperprior is not a product of UniformJointPrior boxes (it holds %s)" % ", ".join(others), None
+        fixed = np.asarray(self.fixed_params[:], dtype=bool)
+        box = np.array([tuple(b) for b in self.hyperprior.bounds[:]], dtype=float).reshape(-1, 2)[~fixed]
+        inside = np.array(self.params[:], dtype=float)
+        inside[~fixed] = box[:, 0]
+        log_prior = self.hyperprior(inside)                  # (the same sum at every point of the box: one term per bound)
+        if not np.isfinite(log_prior):
+            return "the box prior has no finite density (an unbounded side, or a fixed hyperparameter outside its bounds)", None
+        free_idx = np.flatnonzero(~fixed)                    # (the noise sigma follows the kernel's parameters: index len(flat))
+        return None, dict(terms=terms, free_idx=free_idx, lo=box[:, 0], hi=box[:, 1], log_prior=log_prior)
+
+    def _library_stepping_refusal(self):
+        """``None`` when ``sample_hyperparameter_posterior(stepping="library")`` can run this model, else the reason."""
+        return self._library_stepping()[0]
+
+    #: what ``stepping="auto"`` selects for a model the library route can run (DESIGN.md section 13 has the measurements)
+    sampler_auto_route = "library"
+
+    def sample_hyperparameter_posterior(self, nwalkers=200, nsamp=500, burn=0, thin=1, num_proc=None, sampler=None,
+                                        plot_posterior=False, plot_chains=False, sampler_type='ensemble', ntemps=20,
+                                        sampler_a=2.0, theta0=None, random_state=None, stepping="auto"):
+        """Samples of the free hyperparameters from their posterior by an affine-invariant ensemble sampler
+        (:class:`gptools_amd.sampler.EnsembleSampler`; ref: gptools/gaussian_process.py:1694-1838, which drives emcee).  Returns
+        the sampler: pass it to ``predict_MCMC`` / ``compute_from_MCMC`` (``sampler=``), or back in here to add ``nsamp`` steps.
+
+        ``nwalkers`` walkers take ``nsamp`` steps from ``theta0`` (nwalkers, free parameters) -- default: draws of the hyperprior
+        -- or from where ``sampler``'s chain ends.  The log-probability of a row is what :meth:`ll_batch` returns for it.
+        ``sampler``: an ``EnsembleSampler`` of this package, or any object with ``run_mcmc`` and ``chain`` (then
+        ``run_mcmc(theta0, nsamp)`` is all that is called).  ``random_state``: a ``numpy.random.RandomState`` or a seed for the
+        sampler's moves.  ``burn`` only enters the summary printed when the GP is ``verbose``; ``thin``, ``num_proc`` and
+        ``ntemps`` are accepted for compatibility.  Plots and ``sampler_type='pt'`` are not implemented.
+
+        ``stepping``: ``"host"`` -- the loop runs in Python, every half-ensemble through :meth:`ll_batch` (any model);
+        ``"library"`` -- the whole loop runs inside the HIP library (``gpt_ensemble_run``) for a plain model: native kernels
+        without warp, ``ZeroKernel`` / ``DiagonalNoiseKernel`` noise, no mean function, a prior that is a product of
+        ``UniformJointPrior`` boxes (``ValueError`` names what is in the way otherwise); ``"auto"``: ``sampler_auto_route`` where
+        the model allows it, else the host loop.  Both give the same chain bit for bit.  Unlike the reference, the GP keeps its
+        own hyperparameters."""
+        from .sampler import EnsembleSampler
+        from .utils import summarize_sampler
+        if sampler_type != 'ensemble':
+            raise NotImplementedError("Sampler type {} not supported!".format(sampler_type))
+        if plot_posterior or plot_chains:
+            raise NotImplementedError("plots are not part of this package: plot sampler.chain yourself")
+        if stepping not in ("auto", "host", "library"):
+            raise ValueError("stepping must be 'auto', 'host' or 'library'")
+        ours = sampler is None or isinstance(sampler, EnsembleSampler)
+        plan = None
+        if ours and stepping != "host":
+            refusal, plan = self._library_stepping()
+            if stepping == "library" and refusal is not None:
+                raise ValueError("stepping='library': " + refusal)
+            if stepping == "auto" and self.sampler_auto_route != "library":
+                plan = None
+        elif stepping == "library":
+            raise ValueError("stepping='library' needs this package's EnsembleSampler, not a foreign sampler")
+        if self.X is None:
+            raise GPArgumentError("No data have been added to the GaussianProcess!")
+        ctx = self._resident_ctx()                           # (no device: GPTBackendError here, not a chain of -inf)
+        ndim = len(self.free_params)
+
+        def lnprob(P):
+            return self.ll_batch(list(np.atleast_2d(P)))
+        if sampler is None:
+            sampler = EnsembleSampler(nwalkers, ndim, lnprob, a=sampler_a, random_state=random_state)
+        else:
+            sampler.a = sampler_a
+            if ours:
+                sampler.lnprob_batch = lnprob
+                if random_state is not None:
+                    sampler.random_state = (random_state if isinstance(random_state, np.random.RandomState)
+                                            else np.random.RandomState(random_state))
+        lnprob0 = None
+        if np.asarray(sampler.chain).size == 0:
+            if theta0 is None:
+                fixed = np.asarray(self.fixed_params[:], dtype=bool)
+                theta0 = self.hyperprior.random_draw(size=sampler.k if ours else nwalkers).T[:, ~fixed]
+        else:
+            theta0 = sampler.chain[:, -1, :]                 # from where the chain ends (ref :1784-1785)
+            lnprob0 = sampler._last_lnprob if ours else None
+        saved = np.array(self.free_params[:], dtype=float)
+        was_current, fit_mode = self.K_up_to_date, self._fit_mode
+        try:
+            if not ours:
+                sampler.run_mcmc(theta0, nsamp)
+            else:
+                if plan is not None:
+                    _, per = self._batch_element_bytes(False)
+                    diag_add = self.diag_factor * sys.float_info.epsilon
+
+                    def stepper(pos, lnp, a, u_stretch, partner, u_accept):
+                        ctx.set_warp(None)                   # (layers an earlier warped model left on the context)
+                        self._cache = {}
+                        return ctx.ensemble_run(plan["terms"], plan["free_idx"], plan["lo"], plan["hi"], plan["log_prior"],
+                                                self._noise_var(), self.y, self.err_y, diag_add, a, u_stretch, partner, u_accept,
+                                                pos, lnp, self._batch_chunk(ctx, per))
+                    stepper.route = "library"
+                    sampler.stepper = stepper
+                try:
+                    sampler.run_mcmc(theta0, nsamp, lnprob0=lnprob0)
+                finally:
+                    sampler.stepper = None
+        finally:
+            # the GP as it was: its hyperparameters, and the factor of K_tot at them where it had one
+            self._assign_free(saved)
+            if was_current:
+                self.compute_K_L_alpha_ll(need_factor=fit_mode != "partitioned")
+        if self.verbose:
+            print("MCMC parameter summary:")
+            print("param\tmean\t95% posterior interval")
+            for name, m, lo, hi in zip(self.free_param_names[:], *summarize_sampler(sampler, burn=burn)):
+                print("{:s}\t{:4.4g}\t[{:4.4g}, {:4.4g}]".format(str(name), m, lo, hi))
+        return sampler
 
     # ---- MAP estimate (ref: gptools/gaussian_process.py:623-783, :2443-2486) ------------------
     def optimize_hyperparameters(self, method="SLSQP", opt_kwargs={}, verbose=False, random_starts=None,
@@ -1196,9 +1350,9 @@ class GaussianProcess(object):
         """The rows of free hyperparameters to marginalise over, burned and thinned as the reference does (:1935-1940)."""
         if flat_trace is None:
             if sampler is None:
-                raise NotImplementedError("drawing the hyperparameter posterior (emcee) is not part of this package: pass "
-                                          "flat_trace (samples of the free hyperparameters, one per row) or a sampler that "
-                                          "has already been run")
+                raise NotImplementedError("no sampling run is started here: pass flat_trace (samples of the free hyperparameters, "
+                                          "one per row) or a sampler that has already been run -- "
+                                          "sample_hyperparameter_posterior returns one")
             chain = np.asarray(sampler.chain, dtype=float)[:, burn::thin, :]
             return chain.reshape((-1, chain.shape[2]))
         return np.atleast_2d(np.asarray(flat_trace, dtype=float))[burn::thin, :]
@@ -1328,7 +1482,7 @@ class GaussianProcess(object):
         a dict of per-row lists -- ``mean`` (M,), ``std`` (M,), ``cov`` (M, M), ``samp`` (M, num_samples) and, with
         ``return_mean_func`` and a mean function, the ``*_func`` / ``*_without_func`` entries -- over the rows whose
         evaluation succeeded, in trace order.  ``flat_trace[burn::thin]`` or, duck-typed, ``sampler.chain[:, burn::thin, :]``
-        flattened; drawing the posterior itself (emcee) is not part of this package.  ``num_proc`` is accepted and ignored:
+        flattened (:meth:`sample_hyperparameter_posterior` draws one; no run is started here).  ``num_proc`` is accepted and ignored:
         the rows are evaluated in batches on the GPU (gpt_fit_batch_terms + gpt_predict_batch) where the model allows it,
         else one after another.  Samples are drawn on the host per row, in row order (numpy.random.multivariate_normal).
         The GP's hyperparameters are unchanged afterwards."""
@@ -1367,7 +1521,7 @@ class GaussianProcess(object):
         row of a trace of the free hyperparameters (ref: gaussian_process.py:1989-2065, _ComputeLWrapper :2341-2377): an
         ``(S, M)`` array, one row per trace row, where the reference returns a list (or a lazy ``map``).  A row whose
         evaluation fails is NaN.  ``flat_trace[burn::thin]`` or, duck-typed, ``sampler.chain[:, burn::thin, :]`` flattened;
-        drawing the posterior itself (emcee) is not part of this package.  ``X`` and ``n`` go to ``l_func`` unchanged.
+        :meth:`sample_hyperparameter_posterior` draws one (no run is started here).  ``X`` and ``n`` go to ``l_func`` unchanged.
         Host numpy (O(M S)); ``num_proc`` is accepted and ignored."""
         trace = self._mcmc_trace(sampler, flat_trace, burn, thin)
         X = np.asarray(X, dtype=float)

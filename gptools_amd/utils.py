@@ -13,7 +13,7 @@ import scipy.stats
 __all__ = [
     "JointPrior", "ProductJointPrior", "UniformJointPrior", "IndependentJointPrior",
     "NormalJointPrior", "LogNormalJointPrior", "GammaJointPrior", "GammaJointPriorAlt",
-    "CombinedBounds", "MaskedBounds", "unique_rows",
+    "CombinedBounds", "MaskedBounds", "unique_rows", "summarize_sampler",
 ]
 
 
@@ -301,3 +301,46 @@ class GammaJointPriorAlt(GammaJointPrior):
     @property
     def b(self):
         return (self.m + np.sqrt(self.m ** 2 + 4.0 * self.s ** 2)) / (2.0 * self.s ** 2)
+
+
+def summarize_sampler(sampler, weights=None, burn=0, ci=0.95, chain_mask=None):
+    """Mean and central ``ci`` interval of every parameter of a chain (ref: gptools/utils.py:1938-2030): ``(mean, ci_l, ci_u)``,
+    each ``(num_params,)``.
+
+    ``sampler``: an object with ``chain`` (walkers, steps, params) -- :class:`gptools_amd.sampler.EnsembleSampler`, an emcee
+    ensemble sampler -- or an array of that shape, or of shape (steps, params).  The first ``burn`` steps are dropped and, for a
+    3-D chain, the walkers ``chain_mask`` (index array or mask) kept; the rest is flattened.  ``weights`` (walkers, steps) or
+    (steps,): one weight per sample; the mean is then the weighted mean and the interval's ends come from the weighted
+    percentiles ``p_n = 100 / S_N (S_n - w_n / 2)`` of the sorted samples (``S_n`` the running sum of their weights), linearly
+    interpolated.  Without weights: ``numpy.mean`` and ``numpy.percentile`` at ``100 (1 - ci) / 2`` and ``100 - 100 (1 - ci) / 2``.
+    Parallel-tempering chains (4-D) are not supported."""
+    chain = np.asarray(sampler.chain if hasattr(sampler, "chain") else sampler, dtype=float)
+    if weights is not None:
+        weights = np.asarray(weights, dtype=float)
+    if chain.ndim == 3:
+        keep = np.ones(chain.shape[0], dtype=bool) if chain_mask is None else chain_mask
+        flat = chain[keep, burn:, :].reshape((-1, chain.shape[-1]))
+        if weights is not None:
+            weights = weights[keep, burn:].ravel()
+    elif chain.ndim == 2:
+        flat = chain[burn:, :]
+        if weights is not None:
+            weights = weights[burn:].ravel()
+    else:
+        raise ValueError("summarize_sampler takes a chain (walkers, steps, params) or (steps, params), not %d dimensions"
+                         % chain.ndim)
+    edge = 100.0 * (1.0 - ci) / 2.0
+    if weights is None:
+        ci_l, ci_u = np.percentile(flat, [edge, 100.0 - edge], axis=0)
+        return (np.mean(flat, axis=0), ci_l, ci_u)
+    if weights.shape != (flat.shape[0],):
+        raise ValueError("one weight per sample expected")
+    mean = weights.dot(flat) / weights.sum()
+    ends = np.empty((2, flat.shape[1]))
+    for i in range(flat.shape[1]):
+        order = np.argsort(flat[:, i], kind="stable")
+        x, w = flat[order, i], weights[order]
+        Sn = np.cumsum(w)
+        pn = 100.0 / Sn[-1] * (Sn - w / 2.0)
+        ends[:, i] = np.interp([edge, 100.0 - edge], pn, x)      # (outside [p_1, p_N]: the extreme samples)
+    return (mean, ends[0], ends[1])

@@ -387,6 +387,34 @@ int gpt_release_batch_scratch(gpt_ctx *ctx);
 int gpt_predict_batch(gpt_ctx *ctx, const double *Xstar, const int32_t *nstar, int64_t M, const int32_t *noise_n,
                       const int32_t *keep, double *mean_out, double *var_out, double *cov_out, double *cov_sum_out);
 
+/* The loop of an affine-invariant ENSEMBLE SAMPLER (Goodman & Weare's stretch move; what the reference drives emcee for, ref:
+ * gaussian_process.py:1694-1838) over nfree free hyperparameters of the resident data set's model, inside the library: one step is
+ * two dependent batches of nwalkers / 2 evaluations, each ONE launch sequence of the batched fit above, and no caller code runs
+ * between them.  For a model without mean function and warp whose prior is a box:
+ *   the model as gpt_fit_batch_terms takes it (kernel_ids, kernel_ids2, nparams, nparams1) and base_params, its complete parameter
+ *   vector (sum of nparams doubles): the values of the parameters that are not free;
+ *   free_idx[f]: the place of free parameter f in that vector, or its LENGTH for the noise sigma (squared for the fit; at most one);
+ *   noise_var is the noise variance when the sigma is not free;
+ *   lo / hi (nfree): the box, both ends inside; log_prior: the constant log-density inside it; y, err_y, diag_add as gpt_fit_batch_terms
+ *   takes them for ONE element (the targets are every element's);
+ *   u_stretch, partner, u_accept (nsteps, nwalkers): the variates, drawn beforehand.  Walkers [0, nwalkers / 2) are the first
+ *   half.  Per step the first half moves against the second, then the second against the first; walker w of the moving half S
+ *   against the other half C:  t = (a - 1) u_stretch[w] + 1, z = t t / a, q = C[partner[w]] - z (C[partner[w]] - S[w]) (partner
+ *   indexes INTO C), accepted where (nfree - 1) log z + lnp(q) - lnp(S[w]) > log u_accept[w];
+ *   lnp(q) = -inf outside the box (not evaluated), for parameters the model refuses (as gpt_fit_terms would, e.g. a length scale
+ *   that is not positive), for a matrix that is not positive definite and for a NaN; else ll_data + log_prior;
+ *   max_chunk: most elements of one launch sequence (the caller's memory budget); a chunk that answers GPT_E_NOMEM is halved.
+ * pos (nwalkers, nfree) and lnp (nwalkers): the walkers and their log-probabilities, in and out.  Outputs: chain (nsteps, nwalkers,
+ * nfree) and lnp_chain (nsteps, nwalkers), the state after every step; naccept (nwalkers), the accepted moves of this run.
+ * The same variates give the chain of gptools_amd.sampler.EnsembleSampler's Python loop over GaussianProcess.ll_batch bit for bit.
+ * Leaves the context as gpt_fit_batch_terms does (the last chunk is the resident batch; the resident factorisation is untouched);
+ * any error of a launch sequence other than GPT_E_NOMEM ends the run with that status. */
+int gpt_ensemble_run(gpt_ctx *ctx, int nterms, const int *kernel_ids, const int *kernel_ids2, const int *nparams, const int *nparams1,
+                     const double *base_params, int nfree, const int32_t *free_idx, const double *lo, const double *hi,
+                     double log_prior, const double *y, const double *err_y, double diag_add, double noise_var, int nwalkers,
+                     int nsteps, double a, const double *u_stretch, const int32_t *partner, const double *u_accept, int max_chunk,
+                     double *pos, double *lnp, double *chain, double *lnp_chain, int32_t *naccept);
+
 /* Same as gpt_fit but for an explicit, caller-assembled symmetric K_tot (host, (N, N) row-major;
  * only the lower triangle is read): used for the `T` (linear transform) branch,
  * ref: gaussian_process.py:1443-1446, where K_tot = T (K + noise_K) T^T + ... is (N_y, N_y). */
