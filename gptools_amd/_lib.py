@@ -73,6 +73,7 @@ SIGNATURES = {
     "gpt_get_alpha": (C.c_int, [_vp, _dp]),
     "gpt_ll_grad": (C.c_int, [_vp, C.c_int, _ip, _ip, _dp]),
     "gpt_ll_grad_diff": (C.c_int, [_vp, C.c_int, _ip, _dp, _dp, _dp, _dp]),
+    "gpt_ll_grad_diff_batch": (C.c_int, [_vp, C.c_int, _ip, _dp, _dp, _dp, _ip, _dp, _dp]),
     "gpt_predict": (C.c_int, [_vp, _dp, _ip, _i64, C.c_int, _dp, _ip, _dp, _dp, _dp]),
     "gpt_host_alloc": (C.c_int, [_i64, C.POINTER(_vp)]),
     "gpt_host_free": (C.c_int, [_vp]),
@@ -265,6 +266,7 @@ class Context(object):
         self.device = int(device)
         self._warp_key = None               # the layers the library holds (set_warp); None: no warp
         self._term_nparams = None           # parameter counts of the terms of the last successful fit / fit_sum / fit_terms
+        self._batch_shape = None            # (elements, N, parameter counts of the terms) of the last successful fit_batch*
 
     def close(self):
         if getattr(self, "_h", None):
@@ -466,8 +468,10 @@ class Context(object):
         if noise_var.shape != (B,) or y.shape[0] != B or y.shape[1] != err_y.shape[0]:
             raise ValueError("fit_batch: params (B, p), noise_var (B,), y (B, N), err_y (N,) expected")
         ll, ld, info = np.empty(B), np.empty(B), np.zeros(B, dtype=np.int32)
+        self._batch_shape = None
         check(self._lib.gpt_fit_batch(self.handle, B, kernel_id, dptr(params), params.shape[1], dptr(noise_var), dptr(y),
                                       dptr(err_y), float(diag_add), dptr(ll), dptr(ld), iptr(info)))
+        self._batch_shape = (B, y.shape[1], [params.shape[1]])
         return ll, ld, info
 
     def fit_batch_sum(self, kernel_ids, params, nparams, noise_var, y, err_y, diag_add):
@@ -480,8 +484,10 @@ class Context(object):
                 or params.shape[1] != int(npar.sum())):
             raise ValueError("fit_batch_sum: params (B, sum(nparams)), noise_var (B,), y (B, N), err_y (N,) expected")
         ll, ld, info = np.empty(B), np.empty(B), np.zeros(B, dtype=np.int32)
+        self._batch_shape = None
         check(self._lib.gpt_fit_batch_sum(self.handle, B, len(ids), iptr(ids), dptr(params), iptr(npar), dptr(noise_var),
                                           dptr(y), dptr(err_y), float(diag_add), dptr(ll), dptr(ld), iptr(info)))
+        self._batch_shape = (B, y.shape[1], [int(v) for v in npar])
         return ll, ld, info
 
     def fit_batch_terms(self, terms_list, noise_var, y, err_y, diag_add):
@@ -494,8 +500,10 @@ class Context(object):
         if noise_var.shape != (B,) or y.shape[0] != B or y.shape[1] != err_y.shape[0] or params.shape[1] != int(npar.sum()):
             raise ValueError("fit_batch_terms: one parameter set per element, noise_var (B,), y (B, N), err_y (N,) expected")
         ll, ld, info = np.empty(B), np.empty(B), np.zeros(B, dtype=np.int32)
+        self._batch_shape = None
         check(self._lib.gpt_fit_batch_terms(self.handle, B, len(ids), iptr(ids), iptr(ids2), dptr(params), iptr(npar), iptr(npar1),
                                             dptr(noise_var), dptr(y), dptr(err_y), float(diag_add), dptr(ll), dptr(ld), iptr(info)))
+        self._batch_shape = (B, y.shape[1], [int(v) for v in npar])
         return ll, ld, info
 
     def ensemble_run(self, terms, free_idx, lo, hi, log_prior, noise_var, y, err_y, diag_add, a, u_stretch, partner, u_accept,
@@ -518,6 +526,7 @@ class Context(object):
                              "y and err_y (N,) expected")
         chain, lnp_chain = np.empty((nsteps, K, nfree)), np.empty((nsteps, K))
         naccept = np.zeros(K, dtype=np.int32)
+        self._batch_shape = None            # (the run's last chunk becomes the resident batch: not one ll_grad_diff_batch may size)
         check(self._lib.gpt_ensemble_run(self.handle, len(ids), iptr(ids), iptr(ids2), iptr(npar), iptr(npar1), dptr(base), nfree,
                                          iptr(free_idx), dptr(lo), dptr(hi), float(log_prior), dptr(y), dptr(err_y), float(diag_add),
                                          float(noise_var), K, nsteps, float(a), dptr(u_stretch), iptr(partner), dptr(u_accept),
@@ -582,6 +591,49 @@ class Context(object):
         out = np.empty(len(ti) + 1)
         check(self._lib.gpt_ll_grad_diff(self.handle, len(ti), iptr(ti), dptr(pa), dptr(pb), dptr(dn), dptr(out)))
         return out
+
+    def ll_grad_diff_batch(self, term_idx, params_a, params_b, denom, keep, want_alpha=False):
+        """gpt_ll_grad_diff_batch: :meth:`ll_grad_diff` for every element of the resident batch (the last :meth:`fit_batch_terms`
+        and its kin) in one launch sequence.  ``term_idx`` (nh,) is shared; ``params_a[b][h]`` / ``params_b[b][h]`` are element
+        b's stencil points of entry h (the term's complete parameter vector), ``denom`` (B, nh) its steps; ``keep`` (B,) -- 0
+        skips an element, whose rows come back as NaN (pass ``info == 0``).  Returns ``(out (B, nh + 1), alpha (B, N) or None)``,
+        row b of ``out`` what :meth:`ll_grad_diff` returns for element b alone."""
+        ti, keep = i32(np.asarray(term_idx)).reshape(-1), i32(np.asarray(keep) != 0).reshape(-1)
+        nh = len(ti)
+        dn = f64(np.asarray(denom, dtype=float)).reshape(-1, nh) if nh else f64(np.zeros((len(keep), 0)))
+        # The library reads, per element and entry, as many doubles as the batch's term has parameters (the export carries no
+        # lengths): the counts are those of this context's last successful fit_batch*, and every vector is checked against them
+        if self._batch_shape is None:
+            raise GPTBackendError("ll_grad_diff_batch needs a batch fitted by fit_batch / fit_batch_sum / fit_batch_terms on this context")
+        B, N, counts = self._batch_shape
+        if not (len(keep) == len(params_a) == len(params_b) == dn.shape[0] == B):
+            raise ValueError("ll_grad_diff_batch: the resident batch has %d elements; %d / %d stencil rows, %d rows of steps, %d keep flags"
+                             % (B, len(params_a), len(params_b), dn.shape[0], len(keep)))
+        for h, t in enumerate(ti):
+            if not 0 <= t < len(counts):
+                raise ValueError("ll_grad_diff_batch: term_idx[%d] = %d, the resident batch's model has %d terms" % (h, t, len(counts)))
+        for b in range(B):
+            if not (len(params_a[b]) == len(params_b[b]) == nh):
+                raise ValueError("ll_grad_diff_batch: element %d holds %d / %d stencil points for %d entries"
+                                 % (b, len(params_a[b]), len(params_b[b]), nh))
+            for h, t in enumerate(ti):
+                for p in (params_a[b][h], params_b[b][h]):
+                    if np.size(p) != counts[t]:
+                        raise ValueError("ll_grad_diff_batch: element %d, entry %d holds %d parameters, term %d of the resident batch's "
+                                         "model has %d" % (b, h, np.size(p), t, counts[t]))
+
+        def flat(rows):
+            if not nh:
+                return f64(np.zeros(1))
+            return f64(np.concatenate([np.asarray(p, dtype=float).ravel() for row in rows for p in row]))
+        pa, pb = flat(params_a), flat(params_b)
+        out = np.empty((B, nh + 1))
+        alpha = np.empty((B, N)) if want_alpha else None
+        if not nh:
+            dn = f64(np.zeros(1))
+        check(self._lib.gpt_ll_grad_diff_batch(self.handle, nh, iptr(ti), dptr(pa), dptr(pb), dptr(dn), iptr(keep), dptr(out),
+                                               dptr(alpha)))
+        return out, alpha
 
     def fit_matrix(self, K_tot, y):
         K_tot, y = f64(K_tot), f64(y)

@@ -27,10 +27,10 @@ static int trtri_u(gpt_ctx *c, hipStream_t st, int64_t lo, int64_t hi, const dou
     return trsm_rlt(c, st, h, hi - mid, L + mid * ldl + mid, ldl, ws + (mid / 128) * GPT_WS_BLOCK, U12, ldu);
 }
 
-__global__ void eye_blocks_kernel(double *__restrict__ U, int64_t ldu, int64_t n)
+__global__ void eye_blocks_kernel(double *__restrict__ U, int64_t ldu, int64_t n, int64_t bstride = 0)
 {
     const int64_t i = (int64_t)blockIdx.x * blockDim.x + threadIdx.x;
-    if (i < n) U[i * ldu + i] = 1.0;
+    if (i < n) U[(int64_t)blockIdx.y * bstride + i * ldu + i] = 1.0;      // (blockIdx.y: a batch of equal matrices)
 }
 
 // W (n x n, row-major) = U^T through a 32x33 LDS tile

@@ -19,6 +19,13 @@
 // Instantiated through the dispatch the builders share (kbuild_kernel.hpp): FitKids for a plain term, ProductKids by product_kid
 // for a product term -- the form its factors' gform asks for.  A translation unit of its own: the builders' code objects stay
 // what they were.
+// A BATCH (gpt_ll_grad_diff_batch, the gradient half of a resident batch): the element is the grid's second dimension.  Element e
+// reads its own stencil points kps[2 nh e ..], its own alpha + e ldw and W + e ldw^2 and writes its own partial rows behind those
+// of the elements before it -- the strides follow from nh, ldw and the grid, so the kernel takes no further argument, and e is
+// wave-uniform: the element costs scalar registers only.  The single route is element 0 of a batch of one: the same instructions
+// on the same addresses, the same bits.  Tile geometry and summation order do not know the batch, so an element's partial sums
+// are the same whatever the batch around it is.  kgrad_batch_finish_kernel adds the partial sums of every element and launch
+// group in index order, as the host does for the single route, and alpha of a batch comes from kgrad_batch_alpha_kernel.
 #include "kbuild_kernel.hpp"
 
 #define GR_MAXH GPT_GRAD_MAXH
@@ -35,14 +42,21 @@ __device__ __forceinline__ double kgrad_term_pair(const KParams &k1, const KPara
 }
 
 // kps[2 h], kps[2 h + 1]: the term at the stencil points a, b of parameter h < nh <= GR_MAXH (kps2: the second factors of a product
-// term, else unused); partial: grad_reduce_blocks(N) x (GR_MAXH + 1), every entry written
+// term, else unused); partial: grad_reduce_blocks(N) x (GR_MAXH + 1), every entry written.  blockIdx.y: the element of a batch (see
+// the head of this file), 0 on the single route
 template <int KID, int D>
 __global__ __launch_bounds__(KB_THREADS) void kgrad_diff_kernel(
-    const KParams *__restrict__ kps, const KParams *__restrict__ kps2, int nh, const double *__restrict__ X,
-    const int32_t *__restrict__ nn, int64_t N, const double *__restrict__ alpha, const double *__restrict__ W, int64_t ldw,
-    double *__restrict__ partial)
+    const KParams *__restrict__ kps_, const KParams *__restrict__ kps2_, int nh, const double *__restrict__ X,
+    const int32_t *__restrict__ nn, int64_t N, const double *__restrict__ alpha_, const double *__restrict__ W_, int64_t ldw,
+    double *__restrict__ partial_)
 {
     constexpr int64_t R = KB_RATIO;
+    const int64_t e = blockIdx.y;
+    const KParams *__restrict__ kps = kps_ + e * 2 * nh;
+    const KParams *__restrict__ kps2 = kps2_ + e * 2 * nh;         // (only a product term reads it)
+    const double *__restrict__ alpha = alpha_ + e * ldw;
+    const double *__restrict__ W = W_ + e * ldw * ldw;
+    double *__restrict__ partial = partial_ + e * (int64_t)gridDim.x * (GR_MAXH + 1);
     const int64_t b = blockIdx.x;
     int64_t g = (int64_t)((sqrt(1.0 + 8.0 * (double)b / (double)R) - 1.0) * 0.5);
     while (g > 0 && R * g * (g + 1) / 2 > b) g--;
@@ -133,14 +147,17 @@ __global__ __launch_bounds__(KB_THREADS) void kgrad_diff_kernel(
 
 // One launch: nh <= GPT_GRAD_MAXH parameters of ONE term, kernel id1 (* id2 where id2 >= 0) at num_dim D; d_kps / d_kps2: 2 nh
 // KParams each in device memory (d_kps2 only for a product).  The N points dX / dn against the weights alpha alpha^T - W.
+// nbatch > 1: that many elements, element e with d_kps + 2 nh e, dalpha + e ldw, dW + e ldw^2 and dpartial + e
+// grad_reduce_blocks(N) (GR_MAXH + 1); the points are shared.
 int launch_kgrad_diff(hipStream_t st, int id1, int id2, int D, const KParams *d_kps, const KParams *d_kps2, int nh, const double *dX,
-                      const int32_t *dn, int64_t N, const double *dalpha, const double *dW, int64_t ldw, double *dpartial)
+                      const int32_t *dn, int64_t N, const double *dalpha, const double *dW, int64_t ldw, double *dpartial, int64_t nbatch)
 {
-    if (nh < 0 || nh > GR_MAXH || N <= 0 || !d_kps || (id2 >= 0 && !d_kps2)) return GPT_E_ARG;
+    if (nh < 0 || nh > GR_MAXH || N <= 0 || !d_kps || (id2 >= 0 && !d_kps2) || nbatch < 1 || nbatch > 65535 || (nbatch > 1 && ldw < N))
+        return GPT_E_ARG;
     auto for_kid = [&](auto k) {
         constexpr int KID = decltype(k)::value;
         return dispatch_dim<kid_max_dim(KID)>("ll_grad_diff", D, [&](auto d) {
-            hipLaunchKernelGGL((kgrad_diff_kernel<KID, decltype(d)::value>), dim3((unsigned)grad_reduce_blocks(N)), dim3(KB_THREADS), 0, st,
+            hipLaunchKernelGGL((kgrad_diff_kernel<KID, decltype(d)::value>), dim3((unsigned)grad_reduce_blocks(N), (unsigned)nbatch), dim3(KB_THREADS), 0, st,
                                d_kps, d_kps2, nh, dX, dn, N, dalpha, dW, ldw, dpartial);
             GPT_LAUNCH_CHECK();
             return GPT_OK;
@@ -153,4 +170,62 @@ int launch_kgrad_diff(hipStream_t st, int id1, int id2, int D, const KParams *d_
         gpt_set_error("ll_grad_diff: kernel_id %d is not a fit kernel", id1);
         return GPT_E_ARG;
     });
+}
+
+// alpha_b = U_b z_b over the N points of every element of a resident batch: U_b = L_b^-T (upper triangular, row stride ldu, element
+// stride su), z_b = L_b^-1 y_b the augmented row N of element b's factor (A + b sa + N lda).  One wave per row, the row's sum in
+// the lane order and by the shuffle tree below whatever the batch is; alpha + b sal, entries [N, sal) set to zero.
+__global__ __launch_bounds__(256) void kgrad_batch_alpha_kernel(const double *__restrict__ U, int64_t ldu, int64_t su,
+                                                                 const double *__restrict__ A, int64_t lda, int64_t sa, int64_t N,
+                                                                 double *__restrict__ alpha, int64_t sal)
+{
+    const int lane = threadIdx.x & 63;
+    const int64_t i = (int64_t)blockIdx.x * 4 + (threadIdx.x >> 6), b = blockIdx.y;
+    if (i >= sal) return;
+    double s = 0.0;
+    if (i < N) {
+        const double *row = U + b * su + i * ldu, *z = A + b * sa + N * lda;
+        for (int64_t k = i - (i & 63) + lane; k < N; k += 64)            // (U is upper triangular: columns < i hold zeros)
+            if (k >= i) s = fma(row[k], z[k], s);
+#pragma unroll
+        for (int off = 32; off > 0; off >>= 1) s += __shfl_xor(s, off, 64);
+    }
+    if (lane == 0) alpha[b * sal + i] = s;
+}
+
+int launch_kgrad_batch_alpha(hipStream_t st, const double *dU, int64_t ldu, int64_t su, const double *dA, int64_t lda, int64_t sa,
+                             int64_t N, int64_t nbatch, double *dalpha, int64_t sal)
+{
+    if (N <= 0 || sal < N || ldu < N || nbatch < 1 || nbatch > 65535) return GPT_E_ARG;
+    hipLaunchKernelGGL(kgrad_batch_alpha_kernel, dim3((unsigned)((sal + 3) / 4), (unsigned)nbatch), dim3(256), 0, st, dU, ldu, su, dA, lda,
+                       sa, N, dalpha, sal);
+    GPT_LAUNCH_CHECK();
+    return GPT_OK;
+}
+
+// out[b][j] = 1/2 sum over the nblk workgroups, in index order, of entry src[j] of element b's partial rows: partial holds, launch
+// group after launch group, nbatch x nblk rows of GR_MAXH + 1 sums; src[j] = group (GR_MAXH + 1) + slot names the group and slot of
+// output j < nout.  One thread per (b, j): the order of the additions is the host's on the single route and knows nothing of the
+// batch.
+__global__ __launch_bounds__(64) void kgrad_batch_finish_kernel(const double *__restrict__ partial, const int32_t *__restrict__ src,
+                                                                int nout, int64_t nblk, int64_t nbatch, double *__restrict__ out)
+{
+    const int64_t b = blockIdx.y;
+    const int j = blockIdx.x * 64 + threadIdx.x;
+    if (j >= nout) return;
+    const int64_t group = src[j] / (GR_MAXH + 1), slot = src[j] % (GR_MAXH + 1);
+    const double *p = partial + ((group * nbatch + b) * nblk) * (GR_MAXH + 1) + slot;
+    double sum = 0.0;
+    for (int64_t w = 0; w < nblk; w++) sum += p[w * (GR_MAXH + 1)];
+    out[b * nout + j] = 0.5 * sum;
+}
+
+int launch_kgrad_batch_finish(hipStream_t st, const double *dpartial, const int32_t *dsrc, int nout, int64_t nblk, int64_t nbatch,
+                              double *dout)
+{
+    if (nout < 1 || nblk < 1 || nbatch < 1 || nbatch > 65535) return GPT_E_ARG;
+    hipLaunchKernelGGL(kgrad_batch_finish_kernel, dim3((unsigned)((nout + 63) / 64), (unsigned)nbatch), dim3(64), 0, st, dpartial, dsrc, nout,
+                       nblk, nbatch, dout);
+    GPT_LAUNCH_CHECK();
+    return GPT_OK;
 }

@@ -666,16 +666,22 @@ class GaussianProcess(object):
         if self._fit_mode != "kernel":
             raise NotImplementedError("ll_gradient is not available for a fit by the %s route" % self._fit_mode)
         ctx = self._ctx
-        grad = np.zeros(len(self.free_params))
         slot, tix, pa, pb, denom = self._ll_gradient_stencil(rel_step)
         g_dev = ctx.ll_grad_diff(tix, pa, pb, denom)
+        return self._ll_gradient_assemble(slot, g_dev, lambda: ctx.get_alpha(len(self.y)))
+
+    def _ll_gradient_assemble(self, slot, g_dev, get_alpha):
+        """The gradient at the CURRENT hyperparameters from the device's entries ``g_dev`` (one per stencil entry, kernel parameter
+        ``slot[h]``; the noise trace last): the noise entry 2 sigma_n times the trace, the mean function's entries against
+        ``get_alpha()`` and the hyperprior's derivative.  Host only; shared by :meth:`ll_gradient` and :meth:`ll_gradient_batch`."""
+        grad = np.zeros(len(self.free_params))
         for s, v in zip(slot, g_dev[:-1]):
             grad[s] += v
         nk = len(self.k.free_params)
         if self._noise_is_free():
             grad[nk] = 2.0 * self.noise_k.params[0] * g_dev[-1]
         if self.mu is not None:
-            alpha = ctx.get_alpha(len(self.y))
+            alpha = get_alpha()
             free_idx = np.arange(0, len(self.mu.params), dtype=int)[~self.mu.fixed_params]
             for i, pi in enumerate(free_idx):
                 dmu = self.mu(self.X, self.n, hyper_deriv=int(pi))
@@ -683,6 +689,108 @@ class GaussianProcess(object):
                     dmu = self.T.dot(dmu)
                 grad[i + nk + len(self.noise_k.free_params)] = dmu.dot(alpha)
         return grad + self._hyperprior_gradient()
+
+    def _batch_gradient_refusal(self):
+        """Why :meth:`ll_gradient_batch` (``gpt_ll_grad_diff_batch``) cannot serve this model, or ``None``: a reason of
+        :meth:`_ll_gradient_refusal`, a linear transform, or more points than the batched evaluator takes."""
+        why = self._ll_gradient_refusal()
+        if why is not None:
+            return why
+        if self.T is not None:
+            return "a linear transform T (the batched gradient has no transformed pair pass)"
+        if self.X is not None and max(len(self.y), self.X.shape[0]) > self.batch_grid_max_n:
+            return "N = %d above batch_grid_max_n = %d (one evaluation fills the GPU there)" % (len(self.y), self.batch_grid_max_n)
+        return None
+
+    def ll_gradient_batch(self, param_list, rel_step=6e-6, exit_on_bounds=True):
+        """Log-posterior and its gradient at each free-parameter vector of ``param_list``: ``(ll (B,), grad (B, nfree))`` with
+        ``ll[i]`` what :meth:`ll_batch` gives -- ``-update_hyperparameters(p_i)`` bit for bit -- and ``grad[i]`` what
+        :meth:`ll_gradient` gives at ``p_i``, from ONE launch sequence per chunk of ``batch_grid`` points: the batched fit and,
+        while its factors are resident, ``gpt_ll_grad_diff_batch`` (``U = L^-T``, ``U U^T``, alpha and the pair passes with the
+        batch in a grid dimension, one host synchronisation).  The round of a multi-start optimiser in lockstep
+        (``optimize_hyperparameters(batch_starts=True)``).
+
+        A row the prior excludes (``exit_on_bounds``) or whose fit fails has ``ll = -inf`` and a NaN gradient.  A row whose
+        stencil differs in shape from the first one's (a parameter pinned between its bounds) and a chunk the library rejects go
+        through :meth:`update_hyperparameters` and :meth:`ll_gradient` one by one.  The GP's own hyperparameters are left as
+        they were.  ``NotImplementedError`` for what :meth:`ll_gradient` refuses, for a transform ``T`` and above
+        ``batch_grid_max_n`` points."""
+        why = self._batch_gradient_refusal()
+        if why is not None:
+            raise NotImplementedError("ll_gradient_batch is not available for %s" % why)
+        if self.X is None:
+            raise GPArgumentError("No data have been added to the GaussianProcess!")
+        param_list = [np.array(p, dtype=float) for p in param_list]
+        ll = np.full(len(param_list), -np.inf)
+        grad = np.full((len(param_list), len(self.free_params)), np.nan)
+        if not param_list:
+            return ll, grad
+        own, up_to_date = np.array(self.free_params[:], dtype=float), self.K_up_to_date
+        disturbed = [False]                                   # the single route ran: the GP's own factor is gone
+
+        def single(row):
+            disturbed[0] = True
+            v = self.update_hyperparameters(param_list[row], hyper_deriv_handling="value", exit_on_bounds=exit_on_bounds)
+            ll[row] = -1.0 * v
+            if np.isfinite(v):
+                try:
+                    grad[row] = self.ll_gradient(rel_step)
+                except Exception:
+                    warnings.warn("the device gradient failed at free hyperparameters %s, where the log-posterior is %.6g:\n%s"
+                                  % (param_list[row], -v, traceback.format_exc()), RuntimeWarning)
+
+        try:
+            # host part, in order (the kernel / mean objects are shared): every point's device model and stencil
+            jobs = []
+            for i, p in enumerate(param_list):
+                self._assign_free(p)
+                prior = self.hyperprior(self.params)
+                if exit_on_bounds and np.isinf(prior):
+                    continue
+                try:
+                    stencil = self._ll_gradient_stencil(rel_step)
+                except (np.linalg.LinAlgError, ValueError, ArithmeticError):
+                    stencil = None                              # (a stencil point whose device parameters need a solve that failed)
+                job = self._batch_job(i, (prior, stencil))
+                if job is not None:
+                    jobs.append(job)
+            ref = next(((j.extra[1][0], j.extra[1][1]) for j in jobs if j.extra[1] is not None), None)
+            ctx = self._resident_ctx()
+            NP, per = self._batch_element_bytes(False)
+
+            def done(chunk, llv, info):
+                same = np.array([j.extra[1] is not None and (j.extra[1][0], j.extra[1][1]) == ref for j in chunk])
+                keep = (np.asarray(info) == 0) & same
+                for j, l, bad in zip(chunk, llv, info):
+                    if bad == 0:
+                        ll[j.row] = l + j.extra[0]
+                out = alpha = None
+                if keep.any():
+                    # (rows that are not kept are not read by the library: they carry a kept row's stencil for the length checks)
+                    fill = chunk[int(np.argmax(keep))].extra[1]
+                    st = [j.extra[1] if k else fill for j, k in zip(chunk, keep)]
+                    try:
+                        out, alpha = ctx.ll_grad_diff_batch(ref[1], [s[2] for s in st], [s[3] for s in st], [s[4] for s in st], keep,
+                                                            want_alpha=self.mu is not None)
+                    except (ValueError, ArithmeticError, NotImplementedError):
+                        keep[:] = False                         # the library rejects the chunk: its rows one by one
+                for e, j in enumerate(chunk):
+                    if keep[e]:
+                        self._assign_free(param_list[j.row])
+                        grad[j.row] = self._ll_gradient_assemble(ref[0], out[e], lambda: alpha[e])
+                    elif info[e] == 0:
+                        single(j.row)
+
+            # (a lockstep optimisation holds the scratch over its rounds: returning and allocating gigabytes every round cost five
+            # times the rounds' own work at N = 4096 x 32 starts)
+            left = self._fit_batched(jobs, per + 16 * NP * NP, 0 if self._hold_batch_scratch else 24 * NP * NP, done,
+                                     lambda chunk: [single(j.row) for j in chunk])
+            for j in left:
+                single(j.row)
+        finally:
+            self._assign_free(own)
+            self.K_up_to_date = up_to_date and not disturbed[0]
+        return ll, grad
 
     def _device_grad_objective(self):
         """``(fun, jac)`` for scipy.optimize.minimize: ``fun`` is ``update_hyperparameters``, ``jac`` minus :meth:`ll_gradient`
@@ -709,6 +817,37 @@ class GaussianProcess(object):
                               % (x, -f0, traceback.format_exc()), RuntimeWarning)
                 raise
         return fun, jac
+
+    _hold_batch_scratch = False       # True while a lockstep optimisation runs: ll_gradient_batch keeps its device scratch between rounds
+
+    def _lockstep_starts(self, starts, opt_kwargs):
+        """The starts of ``optimize_hyperparameters(batch_starts=True)`` in lockstep (``gptools_amd.multistart``): every round's
+        pending points are one :meth:`ll_gradient_batch`.  Returns one result per start, ``None`` for a start whose run raised --
+        what the sequential loop's ``run`` returns.  The objective is :meth:`_device_grad_objective`'s: minus the log-posterior,
+        ``+inf`` with a zero gradient where the evaluation fails; a gradient that fails where the value is finite ends its start."""
+        from .multistart import lockstep_minimize
+
+        def evaluate(points):
+            ll, grad = self.ll_gradient_batch(points)
+            f = [-1.0 * v for v in ll]
+            for i, p in enumerate(points):
+                if np.isfinite(f[i]) and not np.all(np.isfinite(grad[i])):
+                    f[i] = RuntimeError("the device gradient failed at free hyperparameters %s, where the log-posterior is %.6g"
+                                        % (p, ll[i]))
+            return f, -1.0 * grad
+
+        self._hold_batch_scratch = True
+        try:
+            results, _ = lockstep_minimize(list(starts), evaluate, **opt_kwargs)
+        finally:
+            self._hold_batch_scratch = False
+            if 24 * self._batch_element_bytes(False)[0] ** 2 * min(len(starts), int(self.batch_grid)) > (2 << 30):
+                self._ctx.release_batch_scratch()            # a large scratch goes back to the device once the starts are done
+        if self.verbose:
+            for samp, r in zip(starts, results):
+                if r is None:
+                    warnings.warn("start %s dropped, the optimiser raised" % (samp,), RuntimeWarning)
+        return results
 
     # ---- hyperparameter update (ref: gptools/gaussian_process.py:1332-1416) -------------------
     def _assign_free(self, values):
@@ -1146,7 +1285,7 @@ class GaussianProcess(object):
 
     # ---- MAP estimate (ref: gptools/gaussian_process.py:623-783, :2443-2486) ------------------
     def optimize_hyperparameters(self, method="SLSQP", opt_kwargs={}, verbose=False, random_starts=None,
-                                 num_proc=None, max_tries=1, batch_fd=None, gradient=None):
+                                 num_proc=None, max_tries=1, batch_fd=None, gradient=None, batch_starts=False):
         """Maximise the log-posterior with ``scipy.optimize.minimize`` from ``random_starts`` draws
         of the hyperprior (0: start from the current values).  Every objective evaluation is one GPU
         fit.  ``num_proc`` is accepted for compatibility: a HIP context must not be shared across forked
@@ -1157,9 +1296,32 @@ class GaussianProcess(object):
         ``gradient="device"``: the optimiser is given ``jac`` = minus :meth:`ll_gradient` -- one fit, ``K_tot^-1`` and two passes
         over the pairs per free kernel parameter, for every model of native kernels -- instead of finite differences of the
         objective at one fit per free parameter (``None``, the default).  Independent of ``use_hyper_deriv`` (the analytic
-        gradient of squared-exponential models), with which it cannot be combined."""
+        gradient of squared-exponential models), with which it cannot be combined.
+
+        ``batch_starts=True`` (with ``gradient="device"``, more than one start and SLSQP, L-BFGS-B or TNC): the starts run in
+        lockstep (``gptools_amd.multistart``) -- one thread per start, and every round's pending points of ALL starts are one
+        :meth:`ll_gradient_batch`, a single launch sequence, instead of one fit and one gradient per start and evaluation.  The
+        starts, ``max_tries``, the choice of the best result, the warnings and the return value are those of the sequential loop.
+        ``NotImplementedError`` for a model :meth:`ll_gradient_batch` refuses; ``ValueError`` under a ``torch.distributed`` job
+        of more than one rank."""
         if gradient not in (None, "device"):
             raise ValueError("gradient must be None or 'device', got %r" % (gradient,))
+        if batch_starts:
+            nstarts = 1 if random_starts == 0 else (max(num_proc or 1, 1) if random_starts is None else int(random_starts))
+            chosen = (opt_kwargs or {}).get("method", method)
+            if gradient != "device":
+                raise ValueError("batch_starts=True needs gradient='device': the starts share one batched gradient per round")
+            if nstarts < 2:
+                raise ValueError("batch_starts=True needs more than one start (random_starts >= 2)")
+            if chosen not in ("SLSQP", "L-BFGS-B", "TNC"):
+                raise ValueError("batch_starts=True takes the methods SLSQP, L-BFGS-B and TNC, got %r" % (chosen,))
+            if self.use_hyper_deriv or "jac" in (opt_kwargs or {}):
+                raise ValueError("gradient='device' cannot be combined with use_hyper_deriv or a jac of the caller's")
+            if replicas.world_size() > 1:
+                raise ValueError("batch_starts=True is not available under a torch.distributed job of more than one rank")
+            why = self._batch_gradient_refusal()
+            if why is not None:
+                raise NotImplementedError("batch_starts=True is not available for %s" % why)
         if gradient == "device":
             if self.use_hyper_deriv or "jac" in (opt_kwargs or {}):
                 raise ValueError("gradient='device' cannot be combined with use_hyper_deriv or a jac of the caller's")
@@ -1199,9 +1361,9 @@ class GaussianProcess(object):
         # and the difference formula are scipy's own (approx_derivative is replayed), so the iterates are the same.
         fd_eps = {"L-BFGS-B": 1e-8, "TNC": 1e-8, "SLSQP": 1.4901161193847656e-08}
         partitioned = self._partitioned_possible()       # every evaluation is a collective: no local batching,
-        if gradient == "device":
+        if gradient == "device" and not batch_starts:
             objective, opt_kwargs["jac"] = self._device_grad_objective()
-        elif (batch_fd is not False and int(self.batch_concurrency) > 1 and not self.use_hyper_deriv and not partitioned
+        elif (not batch_starts and batch_fd is not False and int(self.batch_concurrency) > 1 and not self.use_hyper_deriv and not partitioned
                 and "jac" not in opt_kwargs and method in fd_eps and self._fast_fit_possible()):
             eps = (opt_kwargs.get("options") or {}).get("eps", fd_eps[method])
             objective, opt_kwargs["jac"] = self._batched_fd(eps, np.asarray(opt_kwargs["bounds"], dtype=float))
@@ -1227,6 +1389,8 @@ class GaussianProcess(object):
                 # one start per GPU: the ranks of the torch.distributed job replace the reference's process pool
                 param_samples = replicas.shared(np.asarray(param_samples))
                 outcomes = replicas.distributed_map(run, list(param_samples))
+            elif batch_starts:
+                outcomes = self._lockstep_starts(param_samples, opt_kwargs)
             else:
                 outcomes = [run(s) for s in param_samples]
             finished = [r for r in outcomes if r is not None]

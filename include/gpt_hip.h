@@ -455,6 +455,24 @@ int gpt_ll_grad(gpt_ctx *ctx, int nh, const int *term_idx, const int *local_idx,
 int gpt_ll_grad_diff(gpt_ctx *ctx, int nh, const int *term_idx, const double *params_a, const double *params_b,
                      const double *denom, double *out);
 
+/* gpt_ll_grad_diff for every element of the RESIDENT BATCH (the last successful gpt_fit_batch*), one launch sequence and one host
+ * synchronisation for all of them -- the gradient half of a multi-start optimiser's lockstep round.  nh and term_idx[nh] are shared
+ * by the elements (term_idx names terms of the batch's model); per element b the stencil points and steps:
+ *   params_a, params_b: [b][h], entry h its term's complete parameter vector as in gpt_ll_grad_diff (every element's row has the
+ *   same length, the sum over h of the terms' parameter counts);  denom: [b][h].
+ * keep (nbatch): 0 skips element b (pass keep[b] = (info_out[b] == 0)); its stencil is not read and its rows come back as NaN.
+ * Outputs (host): out (nbatch, nh + 1), row b the entries gpt_ll_grad_diff returns for element b, the noise trace
+ * 1/2 sum_i (alpha_i^2 - (K_tot^-1)_ii) last; alpha_out (nbatch, N) or NULL: alpha_b = K_tot,b^-1 y_b (the mean function's entries
+ * are the host's).  Every stencil point of every kept element is checked as in gpt_ll_grad_diff before anything is launched.
+ * An element's row does not depend on nbatch, on its place in the batch or on the other elements (same launch geometry and
+ * summation order whatever the batch is); repeated calls return the same bits.  The batch stays resident: gpt_predict_batch
+ * afterwards returns what it returned before.  Scratch (two nbatch x NP x NP matrices) in slots of its own, which
+ * gpt_release_batch_scratch frees.
+ * GPT_E_STATE: no batch resident (as gpt_predict_batch); GPT_E_NOTIMPL for a batch fitted with warps, while warp layers are set and
+ * with a linear transform (gpt_set_T). */
+int gpt_ll_grad_diff_batch(gpt_ctx *ctx, int nh, const int *term_idx, const double *params_a, const double *params_b,
+                           const double *denom, const int32_t *keep, double *out, double *alpha_out);
+
 /* Replaces  ref: gaussian_process.py:965-1006 for the T-free, untransformed case:
  *   Kstar = K(X, Xstar) ; mean = Kstar^T alpha ; v = L^-1 Kstar ; cov = K(Xstar,Xstar) - v^T v ;
  *   std = sqrt(diag(cov)).
