@@ -22,6 +22,8 @@ GIBBS_MAX_GAUSS = 8      # GPT_GIBBS_MAX_GAUSS: most Gaussians of KERNEL_GIBBS_E
 GIBBS_MAX_KNOTS = 11     # GPT_GIBBS_MAX_KNOTS: most knots of KERNEL_GIBBS_BSPLINE
 KERNEL_GIBBS_GP = 13
 GIBBS_MAX_GP_POINTS = 12 # GPT_GIBBS_MAX_GP_POINTS: most points of KERNEL_GIBBS_GP
+KERNEL_PERIODIC = 14
+PERIODIC_MAXORD = 16     # GPT_PERIODIC_MAXORD: largest combined derivative order of a pair in one dimension for KERNEL_PERIODIC
 GIBBS_ON_DIM_MAX_D = 3   # GPT_GIBBS_ON_DIM_MAX_D: largest num_dim at which a Gibbs kernel id may carry the dimension it acts on
 KERNEL_ON_DIM_STRIDE = 256
 
@@ -30,6 +32,13 @@ def kernel_on_dim(kernel_id, d):
     """GPT_KERNEL_ON_DIM(id, d): the 1-D Gibbs kernel ``kernel_id`` on dimension ``d`` of a model with more dimensions (a product
     factor, include/gpt_hip.h)."""
     return int(kernel_id) + KERNEL_ON_DIM_STRIDE * (int(d) + 1)
+
+
+def kernel_base_id(kernel_id):
+    """GPT_KERNEL_BASE_ID: the plain id of a kernel id with or without a dimension."""
+    return int(kernel_id) % KERNEL_ON_DIM_STRIDE if int(kernel_id) >= KERNEL_ON_DIM_STRIDE else int(kernel_id)
+
+
 MAX_DIM = 16
 WARP_LINEAR, WARP_BETA, WARP_MAX_LAYERS = 1, 2, 4
 

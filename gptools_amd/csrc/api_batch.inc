@@ -253,7 +253,7 @@ extern "C" int gpt_predict_batch(gpt_ctx *c, const double *Xstar, const int32_t 
     const int D = c->D, nbatch = c->rb_nbatch, nterms = model.nterms;
     const int64_t N = c->rb_N, NP = round_up(N + 1, 128), nleaf = NP / 128, bs = NP * NP, bws = nleaf * GPT_WS_BLOCK;
     const int64_t MP = round_up(M, 64), ldv = (int64_t)nbatch * NP;
-    GPT_TRY(check_test_orders(model, c->n_maxsum, false, nstar, M, D));
+    GPT_TRY(check_test_orders(model, c->n_maxsum, c->n_colmax, false, nstar, M, D));
     double noise_sum = 0.0;
     for (int b = 0; b < nbatch; b++)
         if (keep[b]) noise_sum += c->rb_nv[b];

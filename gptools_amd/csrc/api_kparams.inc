@@ -245,6 +245,33 @@ static int make_kparams(int kernel_id, const double *params, int nparams, int D,
         kp->sigma = params[0];
         kp->g_nt = m;
         for (int q = 1; q < nparams; q++) kp->g_raw[q - 1] = params[q];
+    } else if (kernel_id == GPT_KERNEL_PERIODIC) {
+        // PeriodicKernel: [sigma_f, l_1 .. l_D, p_1 .. p_D] (gpt_hip.h; periodic.hpp).  inv_var = 1 / l^2 (0 for l = +inf: the dimension
+        // is masked out), inv_l = 1 / p -- the unit the argument is reduced in -- and l the raw length scale
+        if (nparams != 2 * D + 1) {
+            gpt_set_error("kernel %d expects %d params, got %d", kernel_id, 2 * D + 1, nparams);
+            return GPT_E_ARG;
+        }
+        if (hyper_deriv >= 0) {
+            gpt_set_error("Hyperparameter derivatives have not been implemented!");
+            return GPT_E_NOTIMPL;
+        }
+        kp->sigma = params[0];
+        for (int d = 0; d < D; d++) {
+            const double l = params[1 + d], p = params[1 + D + d];
+            if (!std::isfinite(p) || !(p > 0.0) || std::isinf(1.0 / p)) {      // (a subnormal period: 1 / p overflows)
+                gpt_set_error("PeriodicKernel: the period of dimension %d must be finite and positive, got %g", d + 1, p);
+                return GPT_E_VALUE;
+            }
+            const double a = 1.0 / (l * l);
+            if (l != l || l == 0.0 || std::isinf(a)) {
+                gpt_set_error("PeriodicKernel: the length scale of dimension %d must not be NaN or zero (1 / l^2 finite), got %g", d + 1, l);
+                return GPT_E_VALUE;
+            }
+            kp->l[d] = l;
+            kp->inv_l[d] = 1.0 / p;
+            kp->inv_var[d] = a;
+        }
     } else if (kernel_id == GPT_KERNEL_DIAGNOISE || kernel_id == GPT_KERNEL_ZERO) {
         if (nparams != 1) {
             gpt_set_error("noise kernels expect 1 param, got %d", nparams);
@@ -339,9 +366,31 @@ static int check_warp_orders(const int32_t *n, int64_t M, int D)
     return GPT_OK;
 }
 
+// The periodic kernel runs its derivative recurrence per dimension: the COMBINED order of a pair in ONE dimension may reach
+// GPT_PERIODIC_MAXORD.  mi[d] / mj[d]: the largest order of coordinate d on either side of a Gram block (pairwise lists: see
+// check_pair_orders).
+static int check_periodic_colmax(const long *mi, const long *mj, int D)
+{
+    for (int d = 0; d < D; d++)
+        if (mi[d] + mj[d] > GPT_PERIODIC_MAXORD) {
+            gpt_set_error("PeriodicKernel: derivative orders of a pair sum to %ld in dimension %d, the device builder supports %d per dimension",
+                          mi[d] + mj[d], d + 1, GPT_PERIODIC_MAXORD);
+            return GPT_E_VALUE;
+        }
+    return GPT_OK;
+}
+static void order_colmax(const int32_t *n, int64_t M, int D, long *mx)
+{
+    for (int d = 0; d < D; d++) mx[d] = 0;
+    for (int64_t i = 0; i < M; i++)
+        for (int d = 0; d < D; d++)
+            if (n[i * D + d] > mx[d]) mx[d] = n[i * D + d];
+}
+static const char *const PERIODIC_GIBBS_MSG = "a Periodic x Gibbs product is not evaluated on the device";
+
 static bool native_fit_kernel(int kid)
 {
-    return kid == GPT_KERNEL_SE || kid == GPT_KERNEL_M52 || is_chain(kid) || gibbs_kid(kid);
+    return kid == GPT_KERNEL_SE || kid == GPT_KERNEL_M52 || is_chain(kid) || gibbs_kid(kid) || kid == GPT_KERNEL_PERIODIC;
 }
 
 // ------------------------------------------------------------------------------------------------
@@ -358,10 +407,11 @@ struct ModelKernel {
     bool any_prod = false, has_m52 = false, has_chain = false, has_gibbs = false;      // over all factors of all terms
     bool has_gb = false;      // ... a B-spline or nested-GP Gibbs kernel among them (gibbs_gb_kid): the batched launchers take the kernels with those branches
     bool has_on_dim = false;       // ... a Gibbs factor on one coordinate of num_dim > 1 (GPT_KERNEL_ON_DIM): likewise
+    bool has_per = false;          // ... a Periodic kernel (GPT_GFORM_PER): likewise, and the per-dimension order rule of the test points
     // the terms as the ABI named them (ids with their GPT_KERNEL_ON_DIM coordinate; abi_id2 < 0: no product) and their parameter counts
     // (np: the whole term, np1: its first factor): what gpt_ll_grad_diff needs to send a stencil point of ONE term through parse_model again
     int abi_id1[GPT_MAX_TERMS] = {}, abi_id2[GPT_MAX_TERMS] = {}, np[GPT_MAX_TERMS] = {}, np1[GPT_MAX_TERMS] = {};
-    int gibbs_form() const { return (has_gb ? GPT_GFORM_GB : 0) | (has_on_dim ? GPT_GFORM_ON_DIM : 0); }      // what those launchers take
+    int gibbs_form() const { return (has_gb ? GPT_GFORM_GB : 0) | (has_on_dim ? GPT_GFORM_ON_DIM : 0) | (has_per ? GPT_GFORM_PER : 0); }      // what those launchers take
     const KParams *second(int t) const { return f2[t].kernel_id >= 0 ? &f2[t] : nullptr; }
 };
 
@@ -402,7 +452,7 @@ static int parse_model(int D, long n_maxsum, const long *n_colmax, int nterms, c
 {
     if (nterms < 1 || nterms > GPT_MAX_TERMS || !ids || !params || !nparams || (ids2 && !nparams1)) return GPT_E_ARG;
     m->nterms = nterms;
-    m->any_prod = m->has_m52 = m->has_chain = m->has_gibbs = m->has_gb = m->has_on_dim = false;      // (the factors beyond nterms stay as they are: never read, zero in a fresh model)
+    m->any_prod = m->has_m52 = m->has_chain = m->has_gibbs = m->has_gb = m->has_on_dim = m->has_per = false;      // (the factors beyond nterms stay as they are: never read, zero in a fresh model)
     const double *p = params;
     for (int t = 0; t < nterms; t++) {
         // (plain ids from here on; the coordinate of a GPT_KERNEL_ON_DIM id goes to make_kparams with the id as the ABI gave it)
@@ -413,11 +463,18 @@ static int parse_model(int D, long n_maxsum, const long *n_colmax, int nterms, c
             return GPT_E_ARG;
         }
         if (!native_fit_kernel(k1) || (prod && !native_fit_kernel(k2))) {
-            gpt_set_error("gpt_fit: kernel ids must be SE, Matern52, RationalQuadratic, Matern or Gibbs");
+            gpt_set_error("gpt_fit: kernel ids must be SE, Matern52, RationalQuadratic, Matern, Gibbs or Periodic");
             return GPT_E_ARG;
         }
         GPT_TRY(check_train_orders(k1, k2, n_maxsum, train_gibbs_max(ids[t], D, n_maxsum, n_colmax),
                                    prod ? train_gibbs_max(ids2[t], D, n_maxsum, n_colmax) : 0));
+        if (k1 == GPT_KERNEL_PERIODIC || k2 == GPT_KERNEL_PERIODIC) {
+            if (gibbs_kid(k1) || gibbs_kid(k2)) {
+                gpt_set_error("gpt_fit: term %d: %s", t, PERIODIC_GIBBS_MSG);
+                return GPT_E_ARG;
+            }
+            GPT_TRY(check_periodic_colmax(n_colmax, n_colmax, D));      // a pair of training points meets 2 n_colmax[d] in dimension d
+        }
         const int n1 = prod ? nparams1[t] : nparams[t];
         if (n1 < 1 || (prod && n1 >= nparams[t])) {
             gpt_set_error("gpt_fit: term %d: %d parameters, %d of them the first factor's", t, nparams[t], n1);
@@ -437,6 +494,7 @@ static int parse_model(int D, long n_maxsum, const long *n_colmax, int nterms, c
         m->has_gibbs = m->has_gibbs || gibbs_kid(k1) || gibbs_kid(k2);
         m->has_gb = m->has_gb || gibbs_gb_kid(k1) || gibbs_gb_kid(k2);
         m->has_on_dim = m->has_on_dim || (D > 1 && (gibbs_kid(k1) || gibbs_kid(k2)));
+        m->has_per = m->has_per || k1 == GPT_KERNEL_PERIODIC || k2 == GPT_KERNEL_PERIODIC;
         p += nparams[t];
     }
     m->nparams = (int)(p - params);
@@ -446,8 +504,15 @@ static int parse_model(int D, long n_maxsum, const long *n_colmax, int nterms, c
 // Test points against the model and the resident training points: Matern52 and Gibbs factors limit the test points' own orders,
 // a RationalQuadratic / Matern factor or a product the orders of a (test, test) and of a (test, training) pair; `warp`: layers
 // are set (gpt_set_warp).
-static int check_test_orders(const ModelKernel &m, long n_maxsum, bool warp, const int32_t *nstar, int64_t M, int D)
+// (n_colmax: the training points' largest order per coordinate, for the periodic kernel's per-dimension rule)
+static int check_test_orders(const ModelKernel &m, long n_maxsum, const long *n_colmax, bool warp, const int32_t *nstar, int64_t M, int D)
 {
+    if (m.has_per) {
+        long ms[GPT_MAX_DIM], other[GPT_MAX_DIM];
+        order_colmax(nstar, M, D, ms);
+        for (int d = 0; d < D; d++) other[d] = ms[d] > n_colmax[d] ? ms[d] : n_colmax[d];      // a (test, test) or a (test, training) pair
+        GPT_TRY(check_periodic_colmax(ms, other, D));
+    }
     if (m.has_m52) GPT_TRY(check_m52_orders(nstar, M, D));
     if (m.has_gibbs)
         for (int t = 0; t < m.nterms; t++) {
@@ -482,6 +547,23 @@ static int check_pair_orders(const KParams &k1, const KParams *k2, const int32_t
         GPT_TRY(check_m52_orders(nj, P, D));
     }
     if (is_chain(id1) || k2) GPT_TRY(check_rq_orders(ni, M, nj, P, D, pairwise));
+    if (id1 == GPT_KERNEL_PERIODIC || id2 == GPT_KERNEL_PERIODIC) {
+        if (gibbs_kid(id1) || gibbs_kid(id2)) {
+            gpt_set_error("%s", PERIODIC_GIBBS_MSG);
+            return GPT_E_ARG;
+        }
+        long mi[GPT_MAX_DIM], mj[GPT_MAX_DIM];
+        if (pairwise) {                                   // row i of ni meets row i of nj: the combined orders themselves
+            for (int d = 0; d < D; d++) mi[d] = mj[d] = 0;
+            for (int64_t i = 0; i < M; i++)
+                for (int d = 0; d < D; d++)
+                    if (ni[i * D + d] + nj[i * D + d] > mi[d]) mi[d] = ni[i * D + d] + nj[i * D + d];
+        } else {
+            order_colmax(ni, M, D, mi);
+            order_colmax(nj, P, D, mj);
+        }
+        GPT_TRY(check_periodic_colmax(mi, mj, D));
+    }
     for (const KParams *k : {&k1, k2})
         if (k && gibbs_kid(k->kernel_id)) {
             GPT_TRY(check_gibbs_orders(ni, M, D, k->g_dim));

@@ -23,7 +23,7 @@ extern "C" int gpt_predict(gpt_ctx *c, const double *Xstar, const int32_t *nstar
     const int64_t Nx = c->Nx;
     const ModelKernel &model = c->model;
     const bool warp = c->warp.nlayers > 0;
-    GPT_TRY(check_test_orders(model, c->n_maxsum, warp, nstar, M, D));
+    GPT_TRY(check_test_orders(model, c->n_maxsum, c->n_colmax, warp, nstar, M, D));
     hipStream_t st = c->stream;
     double *dXs, *dKst, *dmean;
     int32_t *dns;

@@ -117,6 +117,12 @@ __host__ __device__ constexpr bool gibbs_gb_kid(int kid)
 // (GPT_KERNEL_ON_DIM, gpt_hip.h)
 #define GPT_GFORM_GB 1
 #define GPT_GFORM_ON_DIM 2
+// The periodic kernel (id 14) as a product factor or as a term whose id only the device sees (kdiag_batch / kss_sum) likewise has forms
+// of its own: the builders' GPT_KID_PRODUCT_PER and the PER forms of those two kernels, taken only for a product / a model that holds
+// a Periodic kernel (GPT_GFORM_PER; ModelKernel::has_per) -- every other instantiation is the code it was.  ONE form per num_dim: it
+// carries every branch of factor_pair (the GM and GB ones too), so a model may hold Periodic terms beside Gibbs terms.
+#define GPT_KID_PRODUCT_PER 108
+#define GPT_GFORM_PER 4
 
 // A cross-stream edge without an event: the kernel that completes a piece of work raises a 32-bit word in device
 // memory when its LAST workgroup is through (its results written with write-through stores and drained first) and the

@@ -65,19 +65,20 @@ int launch_kbuild_batch_cross(hipStream_t st, int kernel_id, int D, const KParam
 // GB: with the B-spline and nested-GP branches (GPT_KID_PRODUCT_GB's form; models that hold such a kernel only)
 // GM: with the Gibbs branches of GPT_KID_PRODUCT_GM -- every 1-D model, and at num_dim 2 .. GPT_GIBBS_ON_DIM_MAX_D the models with a
 // Gibbs factor on one coordinate (instantiations of their own: the kernels of every other model at those num_dim are the code they were)
-template <int D, bool GB = false, bool GM = (D == 1)>
+// PER: with the periodic kernel's branch (GPT_KID_PRODUCT_PER's form: GB and GM set too; models that hold a Periodic kernel only)
+template <int D, bool GB = false, bool GM = (D == 1), bool PER = false>
 __device__ __forceinline__ double batch_term_pair(const KParams *__restrict__ kps, const KParams *__restrict__ kps2, int64_t idx,
                                                   const double *xi, const double *xj, const int *ni, const int *nj)
 {
     // (D == 1: with the bucket / exp-Gauss Gibbs branches, GPT_KID_PRODUCT_GM's form; otherwise the functions the builders share)
-    if (kps2 != nullptr && kps2[idx].kernel_id >= 0) return prod_pair<D, GM, GB>(kps[idx], kps2[idx], xi, xj, ni, nj);
-    return factor_pair<D, GM, GB>(kps[idx], xi, xj, ni, nj);
+    if (kps2 != nullptr && kps2[idx].kernel_id >= 0) return prod_pair<D, GM, GB, PER>(kps[idx], kps2[idx], xi, xj, ni, nj);
+    return factor_pair<D, GM, GB, PER>(kps[idx], xi, xj, ni, nj);
 }
 
 // diag K**_b: out[b * ldo + a] = k_b((x_a, n_a), (x_a, n_a)), terms summed in order (as gpt_predict's pair launches do)
 // (GB, here and in kss_sum_kernel: the form for a 1-D model that holds a B-spline or nested-GP kernel; a flag of the kernel itself, not a shared
 // body behind two kernels -- through a wrapper the pointers lose __restrict__ and the code of every num_dim changes)
-template <int D, bool GB = false, bool GM = (D == 1)>
+template <int D, bool GB = false, bool GM = (D == 1), bool PER = false>
 __global__ __launch_bounds__(256) void kdiag_batch_kernel(int nterms, const KParams *__restrict__ kps, const KParams *__restrict__ kps2,
                                                           int64_t nbatch, const double *__restrict__ X, const int32_t *__restrict__ n,
                                                           int64_t M, double *__restrict__ out, int64_t ldo)
@@ -93,7 +94,7 @@ __global__ __launch_bounds__(256) void kdiag_batch_kernel(int nterms, const KPar
     }
     double v = 0.0;
     for (int t = 0; t < nterms; t++) {
-        const double p = batch_term_pair<D, GB, GM>(kps, kps2, (int64_t)t * nbatch + b, x, x, na, na);
+        const double p = batch_term_pair<D, GB, GM, PER>(kps, kps2, (int64_t)t * nbatch + b, x, x, na, na);
         v = t > 0 ? v + p : p;
     }
     out[b * ldo + a] = v;
@@ -101,7 +102,7 @@ __global__ __launch_bounds__(256) void kdiag_batch_kernel(int nterms, const KPar
 
 // Lower triangle of  C = sum over kept elements b of K**_b  (+ noise_sum on the diagonal of the rows hit[a] != 0): ONE pass over
 // the M x M triangle with the elements' KParams looped inside, 16 x 16 entries per workgroup; rows / columns in [M, MP) get 0.
-template <int D, bool GB = false, bool GM = (D == 1)>
+template <int D, bool GB = false, bool GM = (D == 1), bool PER = false>
 __global__ __launch_bounds__(256) void kss_sum_kernel(int nterms, const KParams *__restrict__ kps, const KParams *__restrict__ kps2,
                                                       int64_t nbatch, const int32_t *__restrict__ keep, const double *__restrict__ X,
                                                       const int32_t *__restrict__ n, int64_t M, int64_t MP, const int32_t *__restrict__ hit,
@@ -125,7 +126,7 @@ __global__ __launch_bounds__(256) void kss_sum_kernel(int nterms, const KParams 
             if (!keep[b]) continue;
             double kb = 0.0;
             for (int t = 0; t < nterms; t++) {
-                const double p = batch_term_pair<D, GB, GM>(kps, kps2, (int64_t)t * nbatch + b, xa, xc, na, nc);
+                const double p = batch_term_pair<D, GB, GM, PER>(kps, kps2, (int64_t)t * nbatch + b, xa, xc, na, nc);
                 kb = t > 0 ? kb + p : p;
             }
             v += kb;
@@ -152,6 +153,13 @@ int launch_kdiag_batch(hipStream_t st, int D, int nterms, const KParams *d_kps, 
                        const int32_t *dn, int64_t M, double *dout, int64_t ldo, int gform)
 {
     if (M <= 0 || nbatch <= 0) return GPT_OK;
+    if (gform & GPT_GFORM_PER)      // a model with a Periodic kernel: the one form with every branch, at every num_dim
+        return dispatch_dim<GPT_MAX_DIM>("kdiag_batch", D, [&](auto d) {
+            hipLaunchKernelGGL((kdiag_batch_kernel<decltype(d)::value, true, true, true>), dim3((unsigned)((M + 255) / 256), (unsigned)nbatch),
+                               dim3(256), 0, st, nterms, d_kps, d_kps2, nbatch, dX, dn, M, dout, ldo);
+            GPT_LAUNCH_CHECK();
+            return GPT_OK;
+        });
     if ((gform & GPT_GFORM_ON_DIM) && D > 1)
         return dispatch_on_dim("kdiag_batch", D, gform, [&](auto d, auto gb) {
             hipLaunchKernelGGL((kdiag_batch_kernel<decltype(d)::value, decltype(gb)::value, true>), dim3((unsigned)((M + 255) / 256), (unsigned)nbatch),
@@ -179,6 +187,13 @@ int launch_kss_sum(hipStream_t st, int D, int nterms, const KParams *d_kps, cons
 {
     if (MP <= 0) return GPT_OK;
     const unsigned nt = (unsigned)((MP + 15) / 16);
+    if (gform & GPT_GFORM_PER)
+        return dispatch_dim<GPT_MAX_DIM>("kss_sum", D, [&](auto d) {
+            hipLaunchKernelGGL((kss_sum_kernel<decltype(d)::value, true, true, true>), dim3(nt, nt), dim3(256), 0, st, nterms, d_kps, d_kps2,
+                               nbatch, d_keep, dX, dn, M, MP, d_hit, noise_sum, dC, ldc);
+            GPT_LAUNCH_CHECK();
+            return GPT_OK;
+        });
     if ((gform & GPT_GFORM_ON_DIM) && D > 1)
         return dispatch_on_dim("kss_sum", D, gform, [&](auto d, auto gb) {
             hipLaunchKernelGGL((kss_sum_kernel<decltype(d)::value, decltype(gb)::value, true>), dim3(nt, nt), dim3(256), 0, st, nterms, d_kps,

@@ -184,6 +184,7 @@ __global__ __launch_bounds__(KB_THREADS) void kbuild_kernel(
             if constexpr (KID == GPT_KERNEL_PRODUCT) v[c] = prod_pair<D>(kp, kp_two, xi, xj[c], nir, njr[c]);
             else if constexpr (KID == GPT_KID_PRODUCT_GM) v[c] = prod_pair<D, true>(kp, kp_two, xi, xj[c], nir, njr[c]);
             else if constexpr (KID == GPT_KID_PRODUCT_GB) v[c] = prod_pair<D, true, true>(kp, kp_two, xi, xj[c], nir, njr[c]);
+            else if constexpr (KID == GPT_KID_PRODUCT_PER) v[c] = prod_pair<D, true, true, true>(kp, kp_two, xi, xj[c], nir, njr[c]);
             else v[c] = any_pair<KID, D>(kp, xi, xj[c], nir, njr[c]);
             if constexpr (WARP) v[c] *= Si[i] * sj[c];
             // SumKernel (ref: gptools/kernel/core.py:549-584): later terms add to what the earlier passes stored
@@ -232,6 +233,7 @@ __global__ __launch_bounds__(256) void kpairs_kernel(KParams kp, const double *_
     if constexpr (KID == GPT_KERNEL_PRODUCT) v = prod_pair<D>(kp, kp_two, xi, xj, nir, njr);
     else if constexpr (KID == GPT_KID_PRODUCT_GM) v = prod_pair<D, true>(kp, kp_two, xi, xj, nir, njr);
     else if constexpr (KID == GPT_KID_PRODUCT_GB) v = prod_pair<D, true, true>(kp, kp_two, xi, xj, nir, njr);
+    else if constexpr (KID == GPT_KID_PRODUCT_PER) v = prod_pair<D, true, true, true>(kp, kp_two, xi, xj, nir, njr);
     else v = any_pair<KID, D>(kp, xi, xj, nir, njr);
     out[m] = accumulate ? out[m] + v : v;
 }
@@ -251,11 +253,12 @@ struct KidList {
 };
 // the kernels a model term can be (native_fit_kernel, api_kparams.inc): what the batched builders take
 using FitKids = KidList<GPT_KERNEL_SE, GPT_KERNEL_M52, GPT_KERNEL_RQ, GPT_KERNEL_MATERN, GPT_KERNEL_GIBBS_TANH, GPT_KERNEL_GIBBS_DTANH,
-                        GPT_KERNEL_GIBBS_CUBIC, GPT_KERNEL_GIBBS_QUINTIC, GPT_KERNEL_GIBBS_EXPGAUSS, GPT_KERNEL_GIBBS_BSPLINE, GPT_KERNEL_GIBBS_GP>;
+                        GPT_KERNEL_GIBBS_CUBIC, GPT_KERNEL_GIBBS_QUINTIC, GPT_KERNEL_GIBBS_EXPGAUSS, GPT_KERNEL_GIBBS_BSPLINE, GPT_KERNEL_GIBBS_GP,
+                        GPT_KERNEL_PERIODIC>;
 // ... and the noise kernels: the single-matrix builder and the pair list
 using AllKids = FitKids::plus<GPT_KERNEL_DIAGNOISE, GPT_KERNEL_ZERO>;
 // the builders' product instantiations (product_kid chooses)
-using ProductKids = KidList<GPT_KERNEL_PRODUCT, GPT_KID_PRODUCT_GM, GPT_KID_PRODUCT_GB>;
+using ProductKids = KidList<GPT_KERNEL_PRODUCT, GPT_KID_PRODUCT_GM, GPT_KID_PRODUCT_GB, GPT_KID_PRODUCT_PER>;
 
 // The product of the factors id1 * id2 at num_dim D: GPT_KID_PRODUCT_GM carries the bucket / exp-Gauss Gibbs branches and exists
 // at num_dim 1 only.  The single-matrix kernels take it only when a factor needs those branches (GPT_KERNEL_PRODUCT at num_dim 1
@@ -267,13 +270,17 @@ using ProductKids = KidList<GPT_KERNEL_PRODUCT, GPT_KID_PRODUCT_GM, GPT_KID_PROD
 // own, so GPT_KERNEL_PRODUCT at those num_dim stays the code it was for every product without a Gibbs factor.
 // gform: the GPT_GFORM_* bits of the factors (gibbs_form_of; batched: of the whole model, ModelKernel::gibbs_form());
 // gibbs_more: a factor is a bucket / exp-Gauss kernel (single-matrix launchers at num_dim 1 only).
+// GPT_KID_PRODUCT_PER (GPT_GFORM_PER: a factor, batched: some kernel of the model, is Periodic) is taken for nothing else; it exists at
+// every num_dim and carries every branch, so the products of a model that also holds Gibbs terms are in it too.
 inline int gibbs_form_of(int D, int id1, int id2)
 {
     return ((gibbs_gb_kid(id1) || gibbs_gb_kid(id2)) ? GPT_GFORM_GB : 0) |
-           ((D > 1 && (gibbs_kid(id1) || gibbs_kid(id2))) ? GPT_GFORM_ON_DIM : 0);
+           ((D > 1 && (gibbs_kid(id1) || gibbs_kid(id2))) ? GPT_GFORM_ON_DIM : 0) |
+           ((id1 == GPT_KERNEL_PERIODIC || id2 == GPT_KERNEL_PERIODIC) ? GPT_GFORM_PER : 0);
 }
 inline int product_kid(int D, int gform, bool gibbs_more, bool batched)
 {
+    if (gform & GPT_GFORM_PER) return GPT_KID_PRODUCT_PER;
     const bool gb = (gform & GPT_GFORM_GB) != 0;
     if (D > 1) return !(gform & GPT_GFORM_ON_DIM) ? GPT_KERNEL_PRODUCT : gb ? GPT_KID_PRODUCT_GB : GPT_KID_PRODUCT_GM;
     if (gb) return GPT_KID_PRODUCT_GB;

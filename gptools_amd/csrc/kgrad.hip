@@ -38,6 +38,7 @@ __device__ __forceinline__ double kgrad_term_pair(const KParams &k1, const KPara
     if constexpr (KID == GPT_KERNEL_PRODUCT) return prod_pair<D>(k1, *k2, xi, xj, ni, nj);
     else if constexpr (KID == GPT_KID_PRODUCT_GM) return prod_pair<D, true>(k1, *k2, xi, xj, ni, nj);
     else if constexpr (KID == GPT_KID_PRODUCT_GB) return prod_pair<D, true, true>(k1, *k2, xi, xj, ni, nj);
+    else if constexpr (KID == GPT_KID_PRODUCT_PER) return prod_pair<D, true, true, true>(k1, *k2, xi, xj, ni, nj);
     else return any_pair<KID, D>(k1, xi, xj, ni, nj);
 }
 
@@ -113,7 +114,7 @@ __global__ __launch_bounds__(KB_THREADS) void kgrad_diff_kernel(
         } else if (live && h < nh) {
             const KParams &ka = kps[2 * h], &kb = kps[2 * h + 1];
             const KParams *ka2 = nullptr, *kb2 = nullptr;
-            if constexpr (KID == GPT_KERNEL_PRODUCT || KID == GPT_KID_PRODUCT_GM || KID == GPT_KID_PRODUCT_GB) {
+            if constexpr (KID == GPT_KERNEL_PRODUCT || KID == GPT_KID_PRODUCT_GM || KID == GPT_KID_PRODUCT_GB || KID == GPT_KID_PRODUCT_PER) {
                 ka2 = kps2 + 2 * h;
                 kb2 = kps2 + 2 * h + 1;
             }

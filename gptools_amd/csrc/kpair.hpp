@@ -22,6 +22,7 @@
 #pragma once
 #include "common.hpp"
 #include "gibbs_lfunc.hpp"
+#include "periodic.hpp"
 
 #define GPT_SQRT5 2.2360679774997898
 #define GPT_FIVE_THIRDS 1.6666666666666667
@@ -731,6 +732,19 @@ static __device__ __noinline__ double gibbs_pair_gp(const KParams *kp, double xi
     return gibbs_pair<GPT_KERNEL_GIBBS_GP>(*kp, &xi, &xj, &ni, &nj);
 }
 
+// ---- PeriodicKernel (no counterpart in the reference; formulas and arithmetic: periodic.hpp) -------------------------------------
+//   k = sigma_f^2 exp(-sum_d 2 a_d sin^2(pi t_d)) prod_d (-1)^(nj_d) P_(n_d),   a_d = kp.inv_var[d] = 1 / l_d^2,  kp.inv_l[d] = 1 / p_d.
+// One exponential per pair (exp_neg: the argument is >= 0).  Its clamp drops a NaN of the argument, which is put back through
+// sigma_f^2 as in se_pair.  The host refuses a combined order beyond GPT_PERIODIC_MAXORD in one dimension (api_kparams.inc).
+static_assert(GPT_PER_MAXORD == GPT_PERIODIC_MAXORD, "periodic.hpp carries the ABI's limit");
+template <int D>
+__device__ __forceinline__ double periodic_pair(const KParams &kp, const double *xi, const double *xj, const int *ni, const int *nj)
+{
+    double e;
+    const double poly = gpt_periodic_chain<D>(kp.inv_l, kp.inv_var, xi, xj, ni, nj, &e);
+    return (((e != e) ? e : kp.sigma * kp.sigma) * exp_neg(e)) * poly;
+}
+
 template <int KID, int D>
 __device__ __forceinline__ double any_pair(const KParams &kp, const double *xi, const double *xj,
                                            const int *ni, const int *nj)
@@ -740,6 +754,7 @@ __device__ __forceinline__ double any_pair(const KParams &kp, const double *xi, 
     if (KID == GPT_KERNEL_DIAGNOISE) return noise_pair<D>(kp, xi, xj, ni, nj);
     if (KID == GPT_KERNEL_RQ) return rq_pair<D>(kp, xi, xj, ni, nj);
     if (KID == GPT_KERNEL_MATERN) return matern_pair<D>(kp, xi, xj, ni, nj);
+    if (KID == GPT_KERNEL_PERIODIC) return periodic_pair<D>(kp, xi, xj, ni, nj);
     if constexpr (gibbs_kid(KID)) return gibbs_pair<KID>(kp, xi, xj, ni, nj);
     return 0.0;
 }
@@ -779,7 +794,9 @@ __device__ __forceinline__ double gibbs_pair_on_dim(const KParams &kp, const dou
 
 // (GM / GB at D = 2 .. GPT_GIBBS_ON_DIM_MAX_D: the products with a Gibbs factor ON ONE COORDINATE, every Gibbs id of the form's set
 // through gibbs_pair_on_dim -- instantiations that did not exist before; without GM the switch at D > 1 is the code it was)
-template <int D, bool GM = false, bool GB = false>
+// PER: the periodic kernel's id as well (GPT_KID_PRODUCT_PER, the PER forms of kdiag_batch / kss_sum: only what the launchers choose
+// for a product or model WITH a Periodic kernel); in front of the switch like GB, so that without it the switch is the code it was
+template <int D, bool GM = false, bool GB = false, bool PER = false>
 __device__ __forceinline__ double factor_pair(const KParams &kp, const double *xi, const double *xj, const int *ni, const int *nj)
 {
     constexpr bool ON_DIM = GM && D > 1 && D <= GPT_GIBBS_ON_DIM_MAX_D;
@@ -792,6 +809,9 @@ __device__ __forceinline__ double factor_pair(const KParams &kp, const double *x
     if constexpr (GB && ON_DIM) {
         if (kp.kernel_id == GPT_KERNEL_GIBBS_BSPLINE) return gibbs_pair_on_dim<D, GPT_KERNEL_GIBBS_BSPLINE>(kp, xi, xj, ni, nj);
         if (kp.kernel_id == GPT_KERNEL_GIBBS_GP) return gibbs_pair_on_dim<D, GPT_KERNEL_GIBBS_GP>(kp, xi, xj, ni, nj);
+    }
+    if constexpr (PER) {
+        if (kp.kernel_id == GPT_KERNEL_PERIODIC) return periodic_pair<D>(kp, xi, xj, ni, nj);
     }
     switch (kp.kernel_id) {
     case GPT_KERNEL_SE: return se_pair<D>(kp, xi, xj, ni, nj);
@@ -812,7 +832,7 @@ __device__ __forceinline__ double factor_pair(const KParams &kp, const double *x
     }
 }
 
-template <int D, bool GM = false, bool GB = false>
+template <int D, bool GM = false, bool GB = false, bool PER = false>
 __device__ double prod_pair(const KParams &k1, const KParams &k2, const double *xi, const double *xj, const int *ni, const int *nj)
 {
     int r[2 * D], a[2 * D];
@@ -839,7 +859,7 @@ __device__ double prod_pair(const KParams &k1, const KParams &k2, const double *
                 n2j[s - D] = r[s] - a[s];
             }
         }
-        sum += w * (factor_pair<D, GM, GB>(k1, xi, xj, n1i, n1j) * factor_pair<D, GM, GB>(k2, xi, xj, n2i, n2j));
+        sum += w * (factor_pair<D, GM, GB, PER>(k1, xi, xj, n1i, n1j) * factor_pair<D, GM, GB, PER>(k2, xi, xj, n2i, n2j));
         int s = 0;
         while (s < 2 * D) {
             if (a[s] < r[s]) {

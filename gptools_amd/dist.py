@@ -702,6 +702,10 @@ class _PanelEngine(object):
         if kernel_id in (_lib.KERNEL_RQ, _lib.KERNEL_MATERN) and 2 * self._n_maxsum > 16:
             raise ValueError("RationalQuadratic / Matern kernel: derivative orders of a pair sum to %d, the device builder "
                              "supports 16" % (2 * self._n_maxsum))
+        if kernel_id == _lib.KERNEL_PERIODIC and 2 * self._n_maxsum > _lib.PERIODIC_MAXORD:
+            # (the library's rule is per dimension; the row sums kept here bound it from above)
+            raise ValueError("PeriodicKernel: derivative orders of a pair sum to %d, the device builder supports %d per dimension"
+                             % (2 * self._n_maxsum, _lib.PERIODIC_MAXORD))
         t_host0 = time.perf_counter()
         self._upload(y, err_y)
         if not self.compiled or self.trace:

@@ -7,3 +7,4 @@ from .rational_quadratic import *   # noqa: F401,F403
 from .gibbs import *           # noqa: F401,F403
 from .warping import *         # noqa: F401,F403
 from .masked import *          # noqa: F401,F403
+from .periodic import *        # noqa: F401,F403

@@ -17,6 +17,7 @@ Two routes of evaluation:
   - SE, Matern52, RationalQuadratic, Matern: the masked kernel is the same kernel at ``total_dim`` whose masked-out dimensions have
     an infinite length scale -- ``1/l = 1/l^2 = 0``, so the distance ignores them and a derivative order there multiplies the
     pair by zero (include/gpt_hip.h).
+  - Periodic: likewise, with the period 1 beside the infinite length scale in the masked-out dimensions.
   - a 1-D Gibbs kernel at ``total_dim <= 3``: the kernel id carries the dimension it acts on (``GPT_KERNEL_ON_DIM``); such a
     kernel is a product factor on the device, and on its own it is its product with the constant unit factor
     ``SE [1, inf .. inf]`` (:func:`unit_factor`).
@@ -121,6 +122,15 @@ class MaskedKernel(Kernel):
             ls = np.full(self.num_dim, np.inf)
             ls[self.mask] = p[lead:]
             return kid, np.concatenate((p[:lead], ls))
+        if kid == _lib.KERNEL_PERIODIC:
+            # [sigma_f, l .., p ..]: outside the mask l = inf (1 / l^2 = 0: the factor is exactly 1, its derivatives exactly 0) and
+            # p = 1, any legal period
+            d = base.num_dim
+            p = np.array(base.params, dtype=float)
+            ls, ps = np.full(self.num_dim, np.inf), np.ones(self.num_dim)
+            ls[self.mask] = p[1:1 + d]
+            ps[self.mask] = p[1 + d:]
+            return kid, np.concatenate((p[:1], ls, ps))
         if kid in _GIBBS and self.num_dim <= _lib.GIBBS_ON_DIM_MAX_D:
             return _lib.kernel_on_dim(kid, self.mask[0]), base._native_params()
         return None

@@ -64,7 +64,7 @@ extern "C" {
                                   * a pair 1e-6 apart at l = 0.3 (50: still 1.0), nu = 130 nan / inf for every pair closer than
                                   * 0.02, nu = 160 nan throughout) */
 
-#define GPT_KERNEL_PRODUCT 6     /* k1 * k2 of two of the kernels above (SE, Matern52, RQ, Matern), ref: kernel/core.py:587-671: the product
+#define GPT_KERNEL_PRODUCT 6     /* k1 * k2 of two of the kernels above (SE, Matern52, RQ, Matern) or GPT_KERNEL_PERIODIC, ref: kernel/core.py:587-671: the product
                                   * rule over the derivative orders of a pair, sum over sub-multi-indices a of prod_slots C(n, a)
                                   * k1^(a) k2^(n - a), evaluated per pair on the device (gpt_kpairs2 / gpt_kbuild2 / gpt_fit_terms);
                                   * combined derivative order of a pair <= GPT_RQ_MAXORD; no hyper-parameter derivatives
@@ -107,6 +107,21 @@ extern "C" {
                                   * (the parameters travel by value in the kernel arguments) is GPT_E_ARG.  A non-finite or non-positive
                                   * l is not refused: it gives NaN (or what the arithmetic gives) like the other length scales */
 #define GPT_GIBBS_MAX_GP_POINTS 12 /* most points of GPT_KERNEL_GIBBS_GP */
+#define GPT_KERNEL_PERIODIC 14   /* PeriodicKernel, the exp-sine-squared covariance (no counterpart in the reference), 2 D + 1 params
+                                  * [sigma_f, l_1 .. l_D, p_1 .. p_D]:
+                                  *   k = sigma_f^2 prod_d exp(-2 sin^2(pi tau_d / p_d) / l_d^2),  tau = x - x'.
+                                  * Derivative observations of any order up to a COMBINED order of GPT_PERIODIC_MAXORD per dimension,
+                                  * ni_d + nj_d <= 16 (GPT_E_VALUE beyond, before anything is launched: for training points from the
+                                  * largest order of each coordinate, 2 max_i n_id; for test points and pair lists from the orders
+                                  * given); other dimensions do not count, the kernel is separable.  A period that is not finite and
+                                  * positive, a length scale that is NaN, zero or so small that 1 / l^2 overflows: GPT_E_VALUE.
+                                  * l_d = +inf is legal and masks dimension d out (1 / l^2 = 0: the factor is exactly 1.0, every
+                                  * derivative in d exactly 0.0; MaskedKernel hands p_d = 1 there).  tau is reduced in units of the
+                                  * period, t = tau / p - rint(tau / p), before any sine is taken: the kernel is periodic to rounding.
+                                  * A product factor beside SE, Matern52, RationalQuadratic, Matern or another Periodic (the locally
+                                  * periodic model SE * Periodic), with the product's own cap on the summed orders of a pair; beside a
+                                  * Gibbs factor GPT_E_ARG.  No hyper-parameter derivatives (GPT_E_NOTIMPL); gpt_ll_grad_diff covers it */
+#define GPT_PERIODIC_MAXORD 16   /* largest ni_d + nj_d of one dimension for GPT_KERNEL_PERIODIC */
 
 /* MaskedKernel (ref: kernel/core.py:1011-1149): a kernel that acts on a subset of the num_dim coordinates and is exactly 0.0 for a
  * pair with a derivative order in any other coordinate.

@@ -1,9 +1,8 @@
 """Stand-alone K-builder rates (gpt_dev_kbuild, lower triangle + fused diagonal, HIP events, best of 8):
 python scratch/kb_alone.py [N]"""
-import sys, numpy as np, torch
-sys.path.insert(0, '/root/repo')
+import os, sys, numpy as np, torch
+sys.path.insert(0, os.path.join(os.path.dirname(os.path.abspath(__file__)), ".."))
 from gptools_amd import _lib
-import bench
 N = int(sys.argv[1]) if len(sys.argv) > 1 else 8192
 d = 3
 ctx = _lib.Context(0)
@@ -12,7 +11,9 @@ rs = np.random.RandomState(0)
 X = rs.rand(N, d)
 err = 0.05 * np.ones(N)
 st = torch.cuda.ExternalStream(int(ctx.stream))
-for kname, params in (("m52", np.array([1.0, 0.3, 0.3, 0.3])), ("se", np.array([1.0, 0.3, 0.3, 0.3]))):
+KERNELS = (("m52", _lib.KERNEL_M52, np.array([1.0, 0.3, 0.3, 0.3])), ("se", _lib.KERNEL_SE, np.array([1.0, 0.3, 0.3, 0.3])),
+           ("per", _lib.KERNEL_PERIODIC, np.array([1.0, 0.9, 0.9, 0.9, 0.3, 0.3, 0.3])))
+for kname, kid, params in KERNELS:
     for deriv in ("none", "quarter", "all"):
         n = np.zeros((N, d), dtype=np.int32)
         if deriv == "quarter": n[3 * N // 4:, 0] = 1
@@ -24,7 +25,7 @@ for kname, params in (("m52", np.array([1.0, 0.3, 0.3, 0.3])), ("se", np.array([
             for _ in range(8):
                 e0, e1 = torch.cuda.Event(enable_timing=True), torch.cuda.Event(enable_timing=True)
                 e0.record(st)
-                _lib.check(lib.gpt_dev_kbuild(ctx.handle, bench.KID[kname], _lib.dptr(params), len(params), dX.data_ptr(), dn.data_ptr(), N,
+                _lib.check(lib.gpt_dev_kbuild(ctx.handle, kid, _lib.dptr(params), len(params), dX.data_ptr(), dn.data_ptr(), N,
                                               dX.data_ptr(), dn.data_ptr(), N, d, -1, 1, None, 1, 0, 0, de.data_ptr(), 0.0, 2.2e-14, dK.data_ptr(), N))
                 e1.record(st)
                 st.synchronize()
