@@ -24,6 +24,8 @@ KERNEL_GIBBS_GP = 13
 GIBBS_MAX_GP_POINTS = 12 # GPT_GIBBS_MAX_GP_POINTS: most points of KERNEL_GIBBS_GP
 KERNEL_PERIODIC = 14
 PERIODIC_MAXORD = 16     # GPT_PERIODIC_MAXORD: largest combined derivative order of a pair in one dimension for KERNEL_PERIODIC
+KERNEL_SPECTRAL = 15
+SPECTRAL_MAXORD = 16     # GPT_SPECTRAL_MAXORD: likewise for KERNEL_SPECTRAL
 GIBBS_ON_DIM_MAX_D = 3   # GPT_GIBBS_ON_DIM_MAX_D: largest num_dim at which a Gibbs kernel id may carry the dimension it acts on
 KERNEL_ON_DIM_STRIDE = 256
 

@@ -272,6 +272,32 @@ static int make_kparams(int kernel_id, const double *params, int nparams, int D,
             kp->inv_l[d] = 1.0 / p;
             kp->inv_var[d] = a;
         }
+    } else if (kernel_id == GPT_KERNEL_SPECTRAL) {
+        // SpectralKernel, one component of the spectral mixture: [sigma_f, mu_1 .. mu_D, l_1 .. l_D] (gpt_hip.h; spectral.hpp).
+        // inv_var = 1 / l^2 (0 for l = +inf: no envelope in that dimension) and, in the place of the raw length scale, l[] = mu
+        if (nparams != 2 * D + 1) {
+            gpt_set_error("kernel %d expects %d params, got %d", kernel_id, 2 * D + 1, nparams);
+            return GPT_E_ARG;
+        }
+        if (hyper_deriv >= 0) {
+            gpt_set_error("Hyperparameter derivatives have not been implemented!");
+            return GPT_E_NOTIMPL;
+        }
+        kp->sigma = params[0];
+        for (int d = 0; d < D; d++) {
+            const double mu = params[1 + d], l = params[1 + D + d];
+            if (!std::isfinite(mu)) {
+                gpt_set_error("SpectralKernel: the frequency of dimension %d must be finite, got %g", d + 1, mu);
+                return GPT_E_VALUE;
+            }
+            const double a = 1.0 / (l * l);
+            if (l != l || l == 0.0 || std::isinf(a)) {
+                gpt_set_error("SpectralKernel: the length scale of dimension %d must not be NaN or zero (1 / l^2 finite), got %g", d + 1, l);
+                return GPT_E_VALUE;
+            }
+            kp->l[d] = mu;
+            kp->inv_var[d] = a;
+        }
     } else if (kernel_id == GPT_KERNEL_DIAGNOISE || kernel_id == GPT_KERNEL_ZERO) {
         if (nparams != 1) {
             gpt_set_error("noise kernels expect 1 param, got %d", nparams);
@@ -368,16 +394,23 @@ static int check_warp_orders(const int32_t *n, int64_t M, int D)
 
 // The periodic kernel runs its derivative recurrence per dimension: the COMBINED order of a pair in ONE dimension may reach
 // GPT_PERIODIC_MAXORD.  mi[d] / mj[d]: the largest order of coordinate d on either side of a Gram block (pairwise lists: see
-// check_pair_orders).
-static int check_periodic_colmax(const long *mi, const long *mj, int D)
+// check_pair_orders).  The spectral kernel has the same rule and the same limit (GPT_SPECTRAL_MAXORD); `who` names the kernel.
+static_assert(GPT_SPECTRAL_MAXORD == GPT_PERIODIC_MAXORD, "one per-dimension limit for both kernels (check_test_orders)");
+static int check_periodic_colmax(const long *mi, const long *mj, int D, const char *who = "PeriodicKernel")
 {
     for (int d = 0; d < D; d++)
         if (mi[d] + mj[d] > GPT_PERIODIC_MAXORD) {
-            gpt_set_error("PeriodicKernel: derivative orders of a pair sum to %ld in dimension %d, the device builder supports %d per dimension",
-                          mi[d] + mj[d], d + 1, GPT_PERIODIC_MAXORD);
+            gpt_set_error("%s: derivative orders of a pair sum to %ld in dimension %d, the device builder supports %d per dimension",
+                          who, mi[d] + mj[d], d + 1, GPT_PERIODIC_MAXORD);
             return GPT_E_VALUE;
         }
     return GPT_OK;
+}
+// (the kernels with that rule; both live in the builders' PER forms)
+static bool per_form_kid(int kid) { return kid == GPT_KERNEL_PERIODIC || kid == GPT_KERNEL_SPECTRAL; }
+static const char *per_form_name(int k1, int k2)
+{
+    return (k1 == GPT_KERNEL_PERIODIC || k2 == GPT_KERNEL_PERIODIC) ? "PeriodicKernel" : "SpectralKernel";
 }
 static void order_colmax(const int32_t *n, int64_t M, int D, long *mx)
 {
@@ -387,10 +420,11 @@ static void order_colmax(const int32_t *n, int64_t M, int D, long *mx)
             if (n[i * D + d] > mx[d]) mx[d] = n[i * D + d];
 }
 static const char *const PERIODIC_GIBBS_MSG = "a Periodic x Gibbs product is not evaluated on the device";
+static const char *const SPECTRAL_GIBBS_MSG = "a Spectral x Gibbs product is not evaluated on the device";
 
 static bool native_fit_kernel(int kid)
 {
-    return kid == GPT_KERNEL_SE || kid == GPT_KERNEL_M52 || is_chain(kid) || gibbs_kid(kid) || kid == GPT_KERNEL_PERIODIC;
+    return kid == GPT_KERNEL_SE || kid == GPT_KERNEL_M52 || is_chain(kid) || gibbs_kid(kid) || kid == GPT_KERNEL_PERIODIC || kid == GPT_KERNEL_SPECTRAL;
 }
 
 // ------------------------------------------------------------------------------------------------
@@ -407,7 +441,7 @@ struct ModelKernel {
     bool any_prod = false, has_m52 = false, has_chain = false, has_gibbs = false;      // over all factors of all terms
     bool has_gb = false;      // ... a B-spline or nested-GP Gibbs kernel among them (gibbs_gb_kid): the batched launchers take the kernels with those branches
     bool has_on_dim = false;       // ... a Gibbs factor on one coordinate of num_dim > 1 (GPT_KERNEL_ON_DIM): likewise
-    bool has_per = false;          // ... a Periodic kernel (GPT_GFORM_PER): likewise, and the per-dimension order rule of the test points
+    bool has_per = false;          // ... a Periodic or a Spectral kernel (GPT_GFORM_PER): likewise, and the per-dimension order rule of the test points
     // the terms as the ABI named them (ids with their GPT_KERNEL_ON_DIM coordinate; abi_id2 < 0: no product) and their parameter counts
     // (np: the whole term, np1: its first factor): what gpt_ll_grad_diff needs to send a stencil point of ONE term through parse_model again
     int abi_id1[GPT_MAX_TERMS] = {}, abi_id2[GPT_MAX_TERMS] = {}, np[GPT_MAX_TERMS] = {}, np1[GPT_MAX_TERMS] = {};
@@ -463,17 +497,17 @@ static int parse_model(int D, long n_maxsum, const long *n_colmax, int nterms, c
             return GPT_E_ARG;
         }
         if (!native_fit_kernel(k1) || (prod && !native_fit_kernel(k2))) {
-            gpt_set_error("gpt_fit: kernel ids must be SE, Matern52, RationalQuadratic, Matern, Gibbs or Periodic");
+            gpt_set_error("gpt_fit: kernel ids must be SE, Matern52, RationalQuadratic, Matern, Gibbs, Periodic or Spectral");
             return GPT_E_ARG;
         }
         GPT_TRY(check_train_orders(k1, k2, n_maxsum, train_gibbs_max(ids[t], D, n_maxsum, n_colmax),
                                    prod ? train_gibbs_max(ids2[t], D, n_maxsum, n_colmax) : 0));
-        if (k1 == GPT_KERNEL_PERIODIC || k2 == GPT_KERNEL_PERIODIC) {
+        if (per_form_kid(k1) || per_form_kid(k2)) {
             if (gibbs_kid(k1) || gibbs_kid(k2)) {
-                gpt_set_error("gpt_fit: term %d: %s", t, PERIODIC_GIBBS_MSG);
+                gpt_set_error("gpt_fit: term %d: %s", t, (k1 == GPT_KERNEL_SPECTRAL || k2 == GPT_KERNEL_SPECTRAL) ? SPECTRAL_GIBBS_MSG : PERIODIC_GIBBS_MSG);
                 return GPT_E_ARG;
             }
-            GPT_TRY(check_periodic_colmax(n_colmax, n_colmax, D));      // a pair of training points meets 2 n_colmax[d] in dimension d
+            GPT_TRY(check_periodic_colmax(n_colmax, n_colmax, D, per_form_name(k1, k2)));      // a pair of training points meets 2 n_colmax[d] in dimension d
         }
         const int n1 = prod ? nparams1[t] : nparams[t];
         if (n1 < 1 || (prod && n1 >= nparams[t])) {
@@ -494,7 +528,7 @@ static int parse_model(int D, long n_maxsum, const long *n_colmax, int nterms, c
         m->has_gibbs = m->has_gibbs || gibbs_kid(k1) || gibbs_kid(k2);
         m->has_gb = m->has_gb || gibbs_gb_kid(k1) || gibbs_gb_kid(k2);
         m->has_on_dim = m->has_on_dim || (D > 1 && (gibbs_kid(k1) || gibbs_kid(k2)));
-        m->has_per = m->has_per || k1 == GPT_KERNEL_PERIODIC || k2 == GPT_KERNEL_PERIODIC;
+        m->has_per = m->has_per || per_form_kid(k1) || per_form_kid(k2);
         p += nparams[t];
     }
     m->nparams = (int)(p - params);
@@ -511,7 +545,10 @@ static int check_test_orders(const ModelKernel &m, long n_maxsum, const long *n_
         long ms[GPT_MAX_DIM], other[GPT_MAX_DIM];
         order_colmax(nstar, M, D, ms);
         for (int d = 0; d < D; d++) other[d] = ms[d] > n_colmax[d] ? ms[d] : n_colmax[d];      // a (test, test) or a (test, training) pair
-        GPT_TRY(check_periodic_colmax(ms, other, D));
+        bool periodic = false;
+        for (int t = 0; t < m.nterms; t++)
+            periodic = periodic || m.f1[t].kernel_id == GPT_KERNEL_PERIODIC || m.f2[t].kernel_id == GPT_KERNEL_PERIODIC;
+        GPT_TRY(check_periodic_colmax(ms, other, D, periodic ? "PeriodicKernel" : "SpectralKernel"));
     }
     if (m.has_m52) GPT_TRY(check_m52_orders(nstar, M, D));
     if (m.has_gibbs)
@@ -547,9 +584,9 @@ static int check_pair_orders(const KParams &k1, const KParams *k2, const int32_t
         GPT_TRY(check_m52_orders(nj, P, D));
     }
     if (is_chain(id1) || k2) GPT_TRY(check_rq_orders(ni, M, nj, P, D, pairwise));
-    if (id1 == GPT_KERNEL_PERIODIC || id2 == GPT_KERNEL_PERIODIC) {
+    if (per_form_kid(id1) || per_form_kid(id2)) {
         if (gibbs_kid(id1) || gibbs_kid(id2)) {
-            gpt_set_error("%s", PERIODIC_GIBBS_MSG);
+            gpt_set_error("%s", (id1 == GPT_KERNEL_SPECTRAL || id2 == GPT_KERNEL_SPECTRAL) ? SPECTRAL_GIBBS_MSG : PERIODIC_GIBBS_MSG);
             return GPT_E_ARG;
         }
         long mi[GPT_MAX_DIM], mj[GPT_MAX_DIM];
@@ -562,7 +599,7 @@ static int check_pair_orders(const KParams &k1, const KParams *k2, const int32_t
             order_colmax(ni, M, D, mi);
             order_colmax(nj, P, D, mj);
         }
-        GPT_TRY(check_periodic_colmax(mi, mj, D));
+        GPT_TRY(check_periodic_colmax(mi, mj, D, per_form_name(id1, id2)));
     }
     for (const KParams *k : {&k1, k2})
         if (k && gibbs_kid(k->kernel_id)) {

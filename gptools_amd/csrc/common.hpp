@@ -121,6 +121,8 @@ __host__ __device__ constexpr bool gibbs_gb_kid(int kid)
 // of its own: the builders' GPT_KID_PRODUCT_PER and the PER forms of those two kernels, taken only for a product / a model that holds
 // a Periodic kernel (GPT_GFORM_PER; ModelKernel::has_per) -- every other instantiation is the code it was.  ONE form per num_dim: it
 // carries every branch of factor_pair (the GM and GB ones too), so a model may hold Periodic terms beside Gibbs terms.
+// The spectral kernel (id 15) shares these forms: a second test beside the periodic one, an out-of-line call, no instantiation of its own
+// (profiles/spectral_resource_usage.txt: what that changed for the PER forms, and that every other kernel is the code it was).
 #define GPT_KID_PRODUCT_PER 108
 #define GPT_GFORM_PER 4
 

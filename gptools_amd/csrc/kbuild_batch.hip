@@ -65,7 +65,7 @@ int launch_kbuild_batch_cross(hipStream_t st, int kernel_id, int D, const KParam
 // GB: with the B-spline and nested-GP branches (GPT_KID_PRODUCT_GB's form; models that hold such a kernel only)
 // GM: with the Gibbs branches of GPT_KID_PRODUCT_GM -- every 1-D model, and at num_dim 2 .. GPT_GIBBS_ON_DIM_MAX_D the models with a
 // Gibbs factor on one coordinate (instantiations of their own: the kernels of every other model at those num_dim are the code they were)
-// PER: with the periodic kernel's branch (GPT_KID_PRODUCT_PER's form: GB and GM set too; models that hold a Periodic kernel only)
+// PER: with the periodic kernel's branch (GPT_KID_PRODUCT_PER's form: GB and GM set too; models that hold a Periodic or a Spectral kernel only)
 template <int D, bool GB = false, bool GM = (D == 1), bool PER = false>
 __device__ __forceinline__ double batch_term_pair(const KParams *__restrict__ kps, const KParams *__restrict__ kps2, int64_t idx,
                                                   const double *xi, const double *xj, const int *ni, const int *nj)
@@ -153,7 +153,7 @@ int launch_kdiag_batch(hipStream_t st, int D, int nterms, const KParams *d_kps, 
                        const int32_t *dn, int64_t M, double *dout, int64_t ldo, int gform)
 {
     if (M <= 0 || nbatch <= 0) return GPT_OK;
-    if (gform & GPT_GFORM_PER)      // a model with a Periodic kernel: the one form with every branch, at every num_dim
+    if (gform & GPT_GFORM_PER)      // a model with a Periodic or a Spectral kernel: the one form with every branch, at every num_dim
         return dispatch_dim<GPT_MAX_DIM>("kdiag_batch", D, [&](auto d) {
             hipLaunchKernelGGL((kdiag_batch_kernel<decltype(d)::value, true, true, true>), dim3((unsigned)((M + 255) / 256), (unsigned)nbatch),
                                dim3(256), 0, st, nterms, d_kps, d_kps2, nbatch, dX, dn, M, dout, ldo);

@@ -254,7 +254,7 @@ struct KidList {
 // the kernels a model term can be (native_fit_kernel, api_kparams.inc): what the batched builders take
 using FitKids = KidList<GPT_KERNEL_SE, GPT_KERNEL_M52, GPT_KERNEL_RQ, GPT_KERNEL_MATERN, GPT_KERNEL_GIBBS_TANH, GPT_KERNEL_GIBBS_DTANH,
                         GPT_KERNEL_GIBBS_CUBIC, GPT_KERNEL_GIBBS_QUINTIC, GPT_KERNEL_GIBBS_EXPGAUSS, GPT_KERNEL_GIBBS_BSPLINE, GPT_KERNEL_GIBBS_GP,
-                        GPT_KERNEL_PERIODIC>;
+                        GPT_KERNEL_PERIODIC, GPT_KERNEL_SPECTRAL>;
 // ... and the noise kernels: the single-matrix builder and the pair list
 using AllKids = FitKids::plus<GPT_KERNEL_DIAGNOISE, GPT_KERNEL_ZERO>;
 // the builders' product instantiations (product_kid chooses)
@@ -270,13 +270,13 @@ using ProductKids = KidList<GPT_KERNEL_PRODUCT, GPT_KID_PRODUCT_GM, GPT_KID_PROD
 // own, so GPT_KERNEL_PRODUCT at those num_dim stays the code it was for every product without a Gibbs factor.
 // gform: the GPT_GFORM_* bits of the factors (gibbs_form_of; batched: of the whole model, ModelKernel::gibbs_form());
 // gibbs_more: a factor is a bucket / exp-Gauss kernel (single-matrix launchers at num_dim 1 only).
-// GPT_KID_PRODUCT_PER (GPT_GFORM_PER: a factor, batched: some kernel of the model, is Periodic) is taken for nothing else; it exists at
+// GPT_KID_PRODUCT_PER (GPT_GFORM_PER: a factor, batched: some kernel of the model, is Periodic or Spectral) is taken for nothing else; it exists at
 // every num_dim and carries every branch, so the products of a model that also holds Gibbs terms are in it too.
 inline int gibbs_form_of(int D, int id1, int id2)
 {
     return ((gibbs_gb_kid(id1) || gibbs_gb_kid(id2)) ? GPT_GFORM_GB : 0) |
            ((D > 1 && (gibbs_kid(id1) || gibbs_kid(id2))) ? GPT_GFORM_ON_DIM : 0) |
-           ((id1 == GPT_KERNEL_PERIODIC || id2 == GPT_KERNEL_PERIODIC) ? GPT_GFORM_PER : 0);
+           ((id1 == GPT_KERNEL_PERIODIC || id2 == GPT_KERNEL_PERIODIC || id1 == GPT_KERNEL_SPECTRAL || id2 == GPT_KERNEL_SPECTRAL) ? GPT_GFORM_PER : 0);
 }
 inline int product_kid(int D, int gform, bool gibbs_more, bool batched)
 {

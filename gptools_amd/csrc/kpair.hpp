@@ -23,6 +23,7 @@
 #include "common.hpp"
 #include "gibbs_lfunc.hpp"
 #include "periodic.hpp"
+#include "spectral.hpp"
 
 #define GPT_SQRT5 2.2360679774997898
 #define GPT_FIVE_THIRDS 1.6666666666666667
@@ -745,6 +746,27 @@ __device__ __forceinline__ double periodic_pair(const KParams &kp, const double 
     return (((e != e) ? e : kp.sigma * kp.sigma) * exp_neg(e)) * poly;
 }
 
+// ---- SpectralKernel, one component of the spectral mixture (no counterpart in the reference; formulas and arithmetic: spectral.hpp) ----
+//   k = sigma_f^2 (-1)^(sum nj) exp(-sum_d a_d tau_d^2 / 2) Re[exp(2 pi i sum_d mu_d tau_d) prod_d H_(n_d)],   a_d = kp.inv_var[d],  mu_d = kp.l[d].
+// One exponential (exp_neg: the argument is >= 0) and one sine / cosine per pair.  The clamp of exp_neg drops a NaN of the argument,
+// which is put back through sigma_f^2 as in se_pair.  The host refuses a combined order beyond GPT_SPECTRAL_MAXORD in one dimension.
+static_assert(GPT_SPEC_MAXORD == GPT_SPECTRAL_MAXORD, "spectral.hpp carries the ABI's limit");
+template <int D>
+__device__ __forceinline__ double spectral_pair(const KParams &kp, const double *xi, const double *xj, const int *ni, const int *nj)
+{
+    double e;
+    const double poly = gpt_spectral_chain<D>(kp.l, kp.inv_var, xi, xj, ni, nj, &e);
+    return (((e != e) ? e : kp.sigma * kp.sigma) * exp_neg(e)) * poly;
+}
+
+// ... as a product factor / by run-time id (the PER forms, which the periodic kernel had to itself before): OUT OF LINE, like the
+// B-spline -- inlined beside periodic_pair it took kss_sum / kdiag_batch<1, true, true, true> from 233 / 223 to 354 / 345 registers
+template <int D>
+static __device__ __noinline__ double spectral_pair_call(const KParams *kp, const double *xi, const double *xj, const int *ni, const int *nj)
+{
+    return spectral_pair<D>(*kp, xi, xj, ni, nj);
+}
+
 template <int KID, int D>
 __device__ __forceinline__ double any_pair(const KParams &kp, const double *xi, const double *xj,
                                            const int *ni, const int *nj)
@@ -755,6 +777,7 @@ __device__ __forceinline__ double any_pair(const KParams &kp, const double *xi, 
     if (KID == GPT_KERNEL_RQ) return rq_pair<D>(kp, xi, xj, ni, nj);
     if (KID == GPT_KERNEL_MATERN) return matern_pair<D>(kp, xi, xj, ni, nj);
     if (KID == GPT_KERNEL_PERIODIC) return periodic_pair<D>(kp, xi, xj, ni, nj);
+    if (KID == GPT_KERNEL_SPECTRAL) return spectral_pair<D>(kp, xi, xj, ni, nj);
     if constexpr (gibbs_kid(KID)) return gibbs_pair<KID>(kp, xi, xj, ni, nj);
     return 0.0;
 }
@@ -794,8 +817,8 @@ __device__ __forceinline__ double gibbs_pair_on_dim(const KParams &kp, const dou
 
 // (GM / GB at D = 2 .. GPT_GIBBS_ON_DIM_MAX_D: the products with a Gibbs factor ON ONE COORDINATE, every Gibbs id of the form's set
 // through gibbs_pair_on_dim -- instantiations that did not exist before; without GM the switch at D > 1 is the code it was)
-// PER: the periodic kernel's id as well (GPT_KID_PRODUCT_PER, the PER forms of kdiag_batch / kss_sum: only what the launchers choose
-// for a product or model WITH a Periodic kernel); in front of the switch like GB, so that without it the switch is the code it was
+// PER: the periodic and the spectral kernel's ids as well (GPT_KID_PRODUCT_PER, the PER forms of kdiag_batch / kss_sum: only what the launchers choose
+// for a product or model WITH a Periodic or a Spectral kernel); in front of the switch like GB, so that without it the switch is the code it was
 template <int D, bool GM = false, bool GB = false, bool PER = false>
 __device__ __forceinline__ double factor_pair(const KParams &kp, const double *xi, const double *xj, const int *ni, const int *nj)
 {
@@ -812,6 +835,7 @@ __device__ __forceinline__ double factor_pair(const KParams &kp, const double *x
     }
     if constexpr (PER) {
         if (kp.kernel_id == GPT_KERNEL_PERIODIC) return periodic_pair<D>(kp, xi, xj, ni, nj);
+        if (kp.kernel_id == GPT_KERNEL_SPECTRAL) return spectral_pair_call<D>(&kp, xi, xj, ni, nj);
     }
     switch (kp.kernel_id) {
     case GPT_KERNEL_SE: return se_pair<D>(kp, xi, xj, ni, nj);

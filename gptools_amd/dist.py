@@ -706,6 +706,9 @@ class _PanelEngine(object):
             # (the library's rule is per dimension; the row sums kept here bound it from above)
             raise ValueError("PeriodicKernel: derivative orders of a pair sum to %d, the device builder supports %d per dimension"
                              % (2 * self._n_maxsum, _lib.PERIODIC_MAXORD))
+        if kernel_id == _lib.KERNEL_SPECTRAL and 2 * self._n_maxsum > _lib.SPECTRAL_MAXORD:
+            raise ValueError("SpectralKernel: derivative orders of a pair sum to %d, the device builder supports %d per dimension"
+                             % (2 * self._n_maxsum, _lib.SPECTRAL_MAXORD))
         t_host0 = time.perf_counter()
         self._upload(y, err_y)
         if not self.compiled or self.trace:

@@ -38,7 +38,7 @@ __all__ = ["GaussianProcess"]
 
 _GIBBS = (_lib.KERNEL_GIBBS_TANH, _lib.KERNEL_GIBBS_DTANH, _lib.KERNEL_GIBBS_CUBIC, _lib.KERNEL_GIBBS_QUINTIC,
           _lib.KERNEL_GIBBS_EXPGAUSS, _lib.KERNEL_GIBBS_BSPLINE, _lib.KERNEL_GIBBS_GP)
-_NATIVE_FIT = (_lib.KERNEL_SE, _lib.KERNEL_M52, _lib.KERNEL_RQ, _lib.KERNEL_MATERN, _lib.KERNEL_PERIODIC) + _GIBBS
+_NATIVE_FIT = (_lib.KERNEL_SE, _lib.KERNEL_M52, _lib.KERNEL_RQ, _lib.KERNEL_MATERN, _lib.KERNEL_PERIODIC, _lib.KERNEL_SPECTRAL) + _GIBBS
 _DEVICE_WARPS = {linear_warp: _lib.WARP_LINEAR, beta_cdf_warp: _lib.WARP_BETA}
 
 

@@ -8,3 +8,4 @@ from .gibbs import *           # noqa: F401,F403
 from .warping import *         # noqa: F401,F403
 from .masked import *          # noqa: F401,F403
 from .periodic import *        # noqa: F401,F403
+from .spectral import *        # noqa: F401,F403

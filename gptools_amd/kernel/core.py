@@ -29,7 +29,7 @@ class Kernel(HyperparameterSet):
     """
 
     _gpt_kernel_id = None     # set by the kernels the HIP library implements natively
-    _gpt_hyper_deriv = True   # False: the class refuses hyper_deriv itself, with the library's message (PeriodicKernel)
+    _gpt_hyper_deriv = True   # False: the class refuses hyper_deriv itself, with the library's message (PeriodicKernel, SpectralKernel)
 
     def __init__(self, num_dim=1, num_params=0, initial_params=None, fixed_params=None, param_bounds=None,
                  param_names=None, enforce_bounds=False, hyperprior=None):
@@ -163,8 +163,8 @@ class ProductKernel(BinaryKernel):
     The reference walks the power set of the derivative multiset of every pair (positions distinct, so equal subsets
     recur); grouped by how many of the ``n`` derivatives of each of the 2 D slots (``ni`` then ``nj``) go to ``k1`` that
     is the general Leibniz rule, ``sum_a prod_slots C(n, a) * k1^(a) * k2^(n - a)`` -- the same sum with each distinct
-    term evaluated once.  With two native factors (SE, Matern52, RationalQuadratic, Matern, Periodic, the native Gibbs kernels;
-    not Periodic beside Gibbs) that sum
+    term evaluated once.  With two native factors (SE, Matern52, RationalQuadratic, Matern, Periodic, Spectral, the native Gibbs kernels;
+    not Periodic or Spectral beside Gibbs) that sum
     runs per pair on the device (``GPT_KERNEL_PRODUCT``: ``gpt_kpairs2`` here, the fused builder in ``GaussianProcess``); otherwise both
     factors are evaluated through their own ``__call__`` and combined on the host.  A ``MaskedKernel`` factor on its device route
     (masked.py) is a native factor."""
@@ -176,7 +176,7 @@ class ProductKernel(BinaryKernel):
         from .matern import Matern52Kernel
         ok = (_lib.KERNEL_SE, _lib.KERNEL_M52, _lib.KERNEL_RQ, _lib.KERNEL_MATERN, _lib.KERNEL_GIBBS_TANH,
               _lib.KERNEL_GIBBS_DTANH, _lib.KERNEL_GIBBS_CUBIC, _lib.KERNEL_GIBBS_QUINTIC, _lib.KERNEL_GIBBS_EXPGAUSS,
-              _lib.KERNEL_GIBBS_BSPLINE, _lib.KERNEL_GIBBS_GP, _lib.KERNEL_PERIODIC)
+              _lib.KERNEL_GIBBS_BSPLINE, _lib.KERNEL_GIBBS_GP, _lib.KERNEL_PERIODIC, _lib.KERNEL_SPECTRAL)
         from .masked import MaskedKernel
         f = []
         for k in (self.k1, self.k2):
@@ -193,9 +193,9 @@ class ProductKernel(BinaryKernel):
             if kid not in ok or type(k).__call__ not in (Kernel.__call__, Matern52Kernel.__call__):
                 return None
             f += [kid, k._native_params()]
-        # (a Periodic factor beside a Gibbs factor: the library has no such product form, the host combines the two)
+        # (a Periodic or a Spectral factor beside a Gibbs factor: the library has no such product form, the host combines the two)
         ids = [_lib.kernel_base_id(f[0]), _lib.kernel_base_id(f[2])]
-        if _lib.KERNEL_PERIODIC in ids and any(_lib.KERNEL_GIBBS_TANH <= i <= _lib.KERNEL_GIBBS_GP for i in ids):
+        if (_lib.KERNEL_PERIODIC in ids or _lib.KERNEL_SPECTRAL in ids) and any(_lib.KERNEL_GIBBS_TANH <= i <= _lib.KERNEL_GIBBS_GP for i in ids):
             return None
         return tuple(f)
 

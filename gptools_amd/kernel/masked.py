@@ -18,6 +18,7 @@ Two routes of evaluation:
     an infinite length scale -- ``1/l = 1/l^2 = 0``, so the distance ignores them and a derivative order there multiplies the
     pair by zero (include/gpt_hip.h).
   - Periodic: likewise, with the period 1 beside the infinite length scale in the masked-out dimensions.
+  - Spectral: likewise, with the frequency 0 beside the infinite length scale in the masked-out dimensions.
   - a 1-D Gibbs kernel at ``total_dim <= 3``: the kernel id carries the dimension it acts on (``GPT_KERNEL_ON_DIM``); such a
     kernel is a product factor on the device, and on its own it is its product with the constant unit factor
     ``SE [1, inf .. inf]`` (:func:`unit_factor`).
@@ -131,6 +132,15 @@ class MaskedKernel(Kernel):
             ls[self.mask] = p[1:1 + d]
             ps[self.mask] = p[1 + d:]
             return kid, np.concatenate((p[:1], ls, ps))
+        if kid == _lib.KERNEL_SPECTRAL:
+            # [sigma_f, mu .., l ..]: outside the mask mu = 0 and l = inf (no phase, no envelope: the dimension contributes exactly 1,
+            # its derivatives exactly 0)
+            d = base.num_dim
+            p = np.array(base.params, dtype=float)
+            mus, ls = np.zeros(self.num_dim), np.full(self.num_dim, np.inf)
+            mus[self.mask] = p[1:1 + d]
+            ls[self.mask] = p[1 + d:]
+            return kid, np.concatenate((p[:1], mus, ls))
         if kid in _GIBBS and self.num_dim <= _lib.GIBBS_ON_DIM_MAX_D:
             return _lib.kernel_on_dim(kid, self.mask[0]), base._native_params()
         return None

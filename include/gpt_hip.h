@@ -64,7 +64,7 @@ extern "C" {
                                   * a pair 1e-6 apart at l = 0.3 (50: still 1.0), nu = 130 nan / inf for every pair closer than
                                   * 0.02, nu = 160 nan throughout) */
 
-#define GPT_KERNEL_PRODUCT 6     /* k1 * k2 of two of the kernels above (SE, Matern52, RQ, Matern) or GPT_KERNEL_PERIODIC, ref: kernel/core.py:587-671: the product
+#define GPT_KERNEL_PRODUCT 6     /* k1 * k2 of two of the kernels above (SE, Matern52, RQ, Matern), GPT_KERNEL_PERIODIC or GPT_KERNEL_SPECTRAL, ref: kernel/core.py:587-671: the product
                                   * rule over the derivative orders of a pair, sum over sub-multi-indices a of prod_slots C(n, a)
                                   * k1^(a) k2^(n - a), evaluated per pair on the device (gpt_kpairs2 / gpt_kbuild2 / gpt_fit_terms);
                                   * combined derivative order of a pair <= GPT_RQ_MAXORD; no hyper-parameter derivatives
@@ -122,6 +122,22 @@ extern "C" {
                                   * periodic model SE * Periodic), with the product's own cap on the summed orders of a pair; beside a
                                   * Gibbs factor GPT_E_ARG.  No hyper-parameter derivatives (GPT_E_NOTIMPL); gpt_ll_grad_diff covers it */
 #define GPT_PERIODIC_MAXORD 16   /* largest ni_d + nj_d of one dimension for GPT_KERNEL_PERIODIC */
+#define GPT_KERNEL_SPECTRAL 15   /* SpectralKernel, ONE component of the spectral mixture kernel of Wilson & Adams (ICML 2013; no counterpart
+                                  * in the reference), 2 D + 1 params [sigma_f, mu_1 .. mu_D, l_1 .. l_D]:
+                                  *   k = sigma_f^2 exp(-sum_d tau_d^2 / (2 l_d^2)) cos(2 pi sum_d mu_d tau_d),  tau = x - x'
+                                  * -- one cosine of the dot product.  A mixture of Q components is a model of Q terms (gpt_fit_terms,
+                                  * up to GPT_MAX_TERMS).  mu = 0 is the squared exponential.  Derivative observations of any order up
+                                  * to a COMBINED order of GPT_SPECTRAL_MAXORD per dimension, ni_d + nj_d <= 16 (GPT_E_VALUE beyond,
+                                  * before anything is launched, by the rule of GPT_KERNEL_PERIODIC).  A frequency mu_d that is not
+                                  * finite, a length scale that is NaN, zero or so small that 1 / l^2 overflows: GPT_E_VALUE; mu_d may
+                                  * have any sign.  l_d = +inf is legal and drops the envelope in dimension d (1 / l^2 = 0; every
+                                  * l_d = +inf: the pure cosine kernel); mu_d = 0 and l_d = +inf masks dimension d out -- it contributes
+                                  * exactly 1.0 without a derivative order and exactly 0.0 with one (MaskedKernel).  The phase
+                                  * sum_d mu_d tau_d is kept in cycles and reduced by its nearest integer before any sine is taken.
+                                  * A product factor beside SE, Matern52, RationalQuadratic, Matern, Periodic or another Spectral,
+                                  * with the product's own cap on the summed orders of a pair; beside a Gibbs factor GPT_E_ARG.
+                                  * No hyper-parameter derivatives (GPT_E_NOTIMPL); gpt_ll_grad_diff covers it */
+#define GPT_SPECTRAL_MAXORD 16   /* largest ni_d + nj_d of one dimension for GPT_KERNEL_SPECTRAL */
 
 /* MaskedKernel (ref: kernel/core.py:1011-1149): a kernel that acts on a subset of the num_dim coordinates and is exactly 0.0 for a
  * pair with a derivative order in any other coordinate.

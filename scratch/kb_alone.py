@@ -12,7 +12,8 @@ X = rs.rand(N, d)
 err = 0.05 * np.ones(N)
 st = torch.cuda.ExternalStream(int(ctx.stream))
 KERNELS = (("m52", _lib.KERNEL_M52, np.array([1.0, 0.3, 0.3, 0.3])), ("se", _lib.KERNEL_SE, np.array([1.0, 0.3, 0.3, 0.3])),
-           ("per", _lib.KERNEL_PERIODIC, np.array([1.0, 0.9, 0.9, 0.9, 0.3, 0.3, 0.3])))
+           ("per", _lib.KERNEL_PERIODIC, np.array([1.0, 0.9, 0.9, 0.9, 0.3, 0.3, 0.3])),
+           ("spec", _lib.KERNEL_SPECTRAL, np.array([1.0, 0.9, 0.9, 0.9, 0.3, 0.3, 0.3])))
 for kname, kid, params in KERNELS:
     for deriv in ("none", "quarter", "all"):
         n = np.zeros((N, d), dtype=np.int32)
