@@ -85,6 +85,8 @@ SIGNATURES = {
     "gpt_ll_grad": (C.c_int, [_vp, C.c_int, _ip, _ip, _dp]),
     "gpt_ll_grad_diff": (C.c_int, [_vp, C.c_int, _ip, _dp, _dp, _dp, _dp]),
     "gpt_ll_grad_diff_batch": (C.c_int, [_vp, C.c_int, _ip, _dp, _dp, _dp, _ip, _dp, _dp]),
+    "gpt_loo": (C.c_int, [_vp, _dp, _dp, _dp]),
+    "gpt_loo_grad_diff": (C.c_int, [_vp, C.c_int, _ip, _dp, _dp, _dp, _dp, _dp, _dp, _dp, _dp]),
     "gpt_predict": (C.c_int, [_vp, _dp, _ip, _i64, C.c_int, _dp, _ip, _dp, _dp, _dp]),
     "gpt_host_alloc": (C.c_int, [_i64, C.POINTER(_vp)]),
     "gpt_host_free": (C.c_int, [_vp]),
@@ -581,27 +583,55 @@ class Context(object):
         term ``term_idx[h]`` with its complete parameter vector (both factors of a product) at the two stencil points,
         ``params_a[h]`` and ``params_b[h]``, and ``denom[h]`` = theta_b - theta_a; returns the gradient entries followed by the
         noise trace term, as :meth:`ll_grad`."""
+        ti, pa, pb, dn = self._pack_stencil("ll_grad_diff", term_idx, params_a, params_b, denom)
+        out = np.empty(len(ti) + 1)
+        check(self._lib.gpt_ll_grad_diff(self.handle, len(ti), iptr(ti), dptr(pa), dptr(pb), dptr(dn), dptr(out)))
+        return out
+
+    def _pack_stencil(self, who, term_idx, params_a, params_b, denom):
+        """The stencil arguments of :meth:`ll_grad_diff` / :meth:`loo_grad_diff` checked and flattened: ``(term_idx, params_a,
+        params_b, denom)`` as the exports read them."""
         ti, dn = i32(np.asarray(term_idx)), f64(np.asarray(denom, dtype=float))
         if not (len(ti) == len(params_a) == len(params_b) == len(dn)):
-            raise ValueError("ll_grad_diff: %d terms, %d / %d stencil points, %d steps"
-                             % (len(ti), len(params_a), len(params_b), len(dn)))
+            raise ValueError("%s: %d terms, %d / %d stencil points, %d steps"
+                             % (who, len(ti), len(params_a), len(params_b), len(dn)))
         # The library reads, per entry, as many doubles as the resident term has parameters (the export carries no lengths): the
         # counts are those of this context's last successful fit, and every vector is checked against them here
         counts = self._term_nparams
         if len(ti) and counts is None:
-            raise GPTBackendError("ll_grad_diff needs a factorisation made by fit / fit_sum / fit_terms on this context")
+            raise GPTBackendError("%s needs a factorisation made by fit / fit_sum / fit_terms on this context" % who)
         for h, t in enumerate(ti):
             if not 0 <= t < len(counts):
-                raise ValueError("ll_grad_diff: term_idx[%d] = %d, the resident model has %d terms" % (h, t, len(counts)))
+                raise ValueError("%s: term_idx[%d] = %d, the resident model has %d terms" % (who, h, t, len(counts)))
             for p in (params_a[h], params_b[h]):
                 if np.size(p) != counts[t]:
-                    raise ValueError("ll_grad_diff: entry %d holds %d parameters, term %d of the resident model has %d"
-                                     % (h, np.size(p), t, counts[t]))
+                    raise ValueError("%s: entry %d holds %d parameters, term %d of the resident model has %d"
+                                     % (who, h, np.size(p), t, counts[t]))
         pa = f64(np.concatenate([np.asarray(p, dtype=float).ravel() for p in params_a])) if len(ti) else f64(np.zeros(1))
         pb = f64(np.concatenate([np.asarray(p, dtype=float).ravel() for p in params_b])) if len(ti) else f64(np.zeros(1))
+        return ti, pa, pb, dn
+
+    def loo(self, N):
+        """gpt_loo: leave-one-out cross-validation from the resident factor over its ``N`` observations.  Returns ``(loo_ll, resid,
+        var)``: the leave-one-out log predictive probability, ``resid[i] = y_i - m_i`` and ``var[i] = s_i^2``, mean and variance
+        of the prediction at point i by the model that has not seen it."""
+        ll = C.c_double()
+        resid, var = np.empty(int(N)), np.empty(int(N))
+        check(self._lib.gpt_loo(self.handle, C.byref(ll), dptr(resid), dptr(var)))
+        return ll.value, resid, var
+
+    def loo_grad_diff(self, term_idx, params_a, params_b, denom, N):
+        """gpt_loo_grad_diff: the gradient of the leave-one-out log predictive probability by per-pair central differences; the
+        stencil arguments are :meth:`ll_grad_diff`'s, ``N`` the number of observations.  Returns ``(out, loo_ll, resid, var, u)``:
+        the gradient entries followed by the noise trace term, what :meth:`loo` returns, and ``u = K_tot^-1 resid`` (a mean
+        function's parameters take their derivative against it)."""
+        ti, pa, pb, dn = self._pack_stencil("loo_grad_diff", term_idx, params_a, params_b, denom)
         out = np.empty(len(ti) + 1)
-        check(self._lib.gpt_ll_grad_diff(self.handle, len(ti), iptr(ti), dptr(pa), dptr(pb), dptr(dn), dptr(out)))
-        return out
+        ll = C.c_double()
+        resid, var, u = np.empty(int(N)), np.empty(int(N)), np.empty(int(N))
+        check(self._lib.gpt_loo_grad_diff(self.handle, len(ti), iptr(ti), dptr(pa), dptr(pb), dptr(dn), dptr(out), C.byref(ll),
+                                          dptr(resid), dptr(var), dptr(u)))
+        return out, ll.value, resid, var, u
 
     def ll_grad_diff_batch(self, term_idx, params_a, params_b, denom, keep, want_alpha=False):
         """gpt_ll_grad_diff_batch: :meth:`ll_grad_diff` for every element of the resident batch (the last :meth:`fit_batch_terms`

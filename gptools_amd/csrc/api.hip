@@ -52,7 +52,8 @@ struct DevBuf {
 enum { SLOT_XI = 0, SLOT_XJ, SLOT_NI, SLOT_NJ, SLOT_OUT, SLOT_KST, SLOT_KSS, SLOT_XS, SLOT_NS, SLOT_VEC, SLOT_VEC2,
        SLOT_RHS, SLOT_LOW, SLOT_KFULL, SLOT_TK, SLOT_ZERO, SLOT_UINV, SLOT_WINV, SLOT_GPART, SLOT_BINV, SLOT_BTMP,
        SLOT_BINV2, SLOT_BINV3, SLOT_BINV3U, SLOT_BINVU, SLOT_BATCH_A, SLOT_BATCH_WS, SLOT_BATCH_MISC, SLOT_SPLITK,
-       SLOT_PB_V, SLOT_PB_COV, SLOT_PB_MISC, SLOT_XSW, SLOT_SS, SLOT_SI, SLOT_SJ, SLOT_WB_X, SLOT_WB_S, SLOT_WB_P, SLOT_GKP, SLOT_GB_U, SLOT_GB_W, SLOT_GB_MISC, SLOT_COUNT };
+       SLOT_PB_V, SLOT_PB_COV, SLOT_PB_MISC, SLOT_XSW, SLOT_SS, SLOT_SI, SLOT_SJ, SLOT_WB_X, SLOT_WB_S, SLOT_WB_P, SLOT_GKP, SLOT_GB_U, SLOT_GB_W, SLOT_GB_MISC,
+       SLOT_LOO_V, SLOT_LOO_VEC, SLOT_COUNT };
 
 struct gpt_ctx {
     int device = 0;
@@ -148,7 +149,7 @@ struct gpt_ctx {
     // (all three are always built for the whole padded order, floor(NP / width) blocks, whatever extent the caller needs:
     // gpt_ll_grad and the solves ask for different extents at N = 512 k - 128, and a valid flag says nothing about how far)
     unsigned alpha_counter = 0;        // value of the step counter of the wide back-substitution (d_edge[40], only ever raised)
-    int64_t debug_poison = 0;          // option "debug_poison": gpt_ll_grad fills its scratch matrices with NaN first (test aid)
+    int64_t debug_poison = 0;          // option "debug_poison": the gradients and gpt_loo* fill their scratch matrices with NaN first (test aid)
     int64_t edge_test_stall = 0;       // option "edge_test_stall": the next head flag is withheld once (test aid, see fit_terms_once)
     double *h_stage = nullptr;         // pinned staging ring for results that go to pageable host memory (2 x GPT_STAGE_BYTES)
     hipStream_t copy_stream = nullptr; // device-to-host copies that overlap the next block's compute (created on first use)
@@ -233,6 +234,7 @@ static int stream_follows(gpt_ctx *c, hipStream_t from, hipStream_t to, size_t i
 #include "api_fit.inc"      // data residency and the fit: gpt_set_data, gpt_set_T, gpt_fit, gpt_fit_sum, gpt_fit_terms, gpt_fit_matrix
 #include "api_batch.inc"      // batched small fits (gpt_fit_batch*), timings / GEMM profile read-out, gpt_get_L, alpha (gpt_get_alpha)
 #include "api_grad.inc"      // triangular inverses (gpt_dev_trinv) and the analytic LML gradient gpt_ll_grad
+#include "api_loo.inc"      // leave-one-out cross-validation: gpt_loo, gpt_loo_grad_diff
 #include "api_grad_batch.inc"      // gpt_ll_grad_diff_batch: the gradient half of a resident batch
 #include "api_solve.inc"      // many-right-hand-side solves against the resident factor: block inverses, right-TRSM by GEMMs, split-k; pinned host buffers
 #include "api_predict.inc"      // gpt_predict, gpt_cov_sample, gpt_solve_L / gpt_cho_solve, gpt_potrf_host / gpt_gemm_nt_host

@@ -1,6 +1,7 @@
 // api_grad.inc -- part of api.hip (ONE translation unit: included from there, in this order; the parts share struct gpt_ctx and
 // static helpers).  Triangular inverses (gpt_dev_trinv), the analytic LML gradient gpt_ll_grad and the per-pair differenced one,
-// gpt_ll_grad_diff; grad_weights is the half the two share.
+// gpt_ll_grad_diff; grad_weights is the half the two share, grad_trinv its first half (all that gpt_loo needs), and grad_diff_run
+// the body that gpt_ll_grad_diff shares with gpt_loo_grad_diff (api_loo.inc).
 // ------------------------------------------------------------------------------------------------
 // analytic gradient of the LML data term (ref: gptools/gaussian_process.py:1471-1520; SURVEY.md 8f-1)
 // ------------------------------------------------------------------------------------------------
@@ -181,15 +182,16 @@ static int trtri_u_gemm_b(gpt_ctx *c, hipStream_t st, int64_t lo, int64_t hi, co
 struct GradWeights {
     const double *Wp = nullptr, *ap = nullptr;
     int64_t Np = 0, ldwp = 0;
-    double *W = nullptr;
+    double *W = nullptr, *U = nullptr;      // U = L^-T (SLOT_UINV): dead for the LML once W exists, the leave-one-out terms read it
 };
 
-// The half that gpt_ll_grad and gpt_ll_grad_diff share: the triangular inverse, U U^T and the T branch, enqueued on the panel
-// stream `st` behind the main stream; the pair pass of either caller follows on `st`.  ge (GPT_GRAD_TIMING; else NULL): four
-// events, [0] .. [2] recorded here -- before the inverse, after it, after U U^T.
-static int grad_weights(gpt_ctx *c, hipStream_t st, hipEvent_t *ge, GradWeights *gw)
+// The first half of grad_weights, and all that the leave-one-out VALUE needs (gpt_loo, api_loo.inc): U = L^-T (NP x NP, SLOT_UINV)
+// on the panel stream `st` behind the main stream, with SLOT_WINV as the recursion's scratch matrix -- *Wout, whose content is
+// scratch afterwards.  alpha is enqueued on the main stream; the caller joins it (stream_follows main -> st) before reading it.
+// ge (GPT_GRAD_TIMING; else NULL): [0] and [1] recorded here, before and after the inverse.
+static int grad_trinv(gpt_ctx *c, hipStream_t st, hipEvent_t *ge, double **Uout, double **Wout)
 {
-    const int64_t N = c->N, NP = c->NP;
+    const int64_t NP = c->NP;
     // Everything here runs on the panel stream: it is not CU-masked (the main stream leaves 32 of the 256 CUs to it), and
     // nothing else is in flight.
     GPT_TRY(stream_follows(c, c->stream, st, 0));
@@ -233,8 +235,21 @@ static int grad_weights(gpt_ctx *c, hipStream_t st, hipEvent_t *ge, GradWeights 
         GPT_LAUNCH_CHECK();
         GPT_TRY(trtri_u(c, st, 0, NP, c->dA, NP, c->d_invd, U, NP));
     }
-    // (block rows of about NP/8: skinnier launches exploit more of U's zeros but run the GEMM far below its rate)
     if (ge) GPT_HIP_CHECK(hipEventRecord(ge[1], st));
+    *Uout = U;
+    *Wout = W;
+    return GPT_OK;
+}
+
+// The half that gpt_ll_grad, gpt_ll_grad_diff and gpt_loo_grad_diff share: the triangular inverse (grad_trinv), U U^T and the T
+// branch, enqueued on the panel stream `st` behind the main stream; the pair pass of the caller follows on `st`.  ge
+// (GPT_GRAD_TIMING; else NULL): four events, [0] .. [2] recorded here -- before the inverse, after it, after U U^T.
+static int grad_weights(gpt_ctx *c, hipStream_t st, hipEvent_t *ge, GradWeights *gw)
+{
+    const int64_t N = c->N, NP = c->NP;
+    double *U, *W;
+    GPT_TRY(grad_trinv(c, st, ge, &U, &W));
+    // (block rows of about NP/8: skinnier launches exploit more of U's zeros but run the GEMM far below its rate)
     int64_t nbdiv = 8;
     if (const char *e = getenv("GPT_GRAD_ROWS_DIV")) nbdiv = atoi(e) > 0 ? atoi(e) : 8;
     const int64_t nb = (NP / nbdiv >= 512) ? (NP / nbdiv) / 128 * 128 : 512;
@@ -285,6 +300,7 @@ static int grad_weights(gpt_ctx *c, hipStream_t st, hipEvent_t *ge, GradWeights 
     gw->Np = Np;
     gw->ldwp = ldwp;
     gw->W = W;
+    gw->U = U;
     return GPT_OK;
 }
 
@@ -404,19 +420,38 @@ extern "C" int gpt_ll_grad(gpt_ctx *c, int nh, const int *term_idx, const int *l
     return stream_follows(c, st, c->stream, 1);     // the main stream continues behind this (the block inverses stay valid for predict)
 }
 
-// The same gradient for ANY term of the resident model, by central differences of the pair function taken per pair (kgrad.hip):
-// parameter h is given as its term's complete parameter vector at the two stencil points, and every stencil point goes through
-// parse_model as a one-term model with the ids and parameter counts the fit was given -- whatever that refuses is refused here,
-// before anything is launched.  After K_tot^-1 a parameter costs two O(N^2) evaluations of its term instead of a factorisation.
-extern "C" int gpt_ll_grad_diff(gpt_ctx *c, int nh, const int *term_idx, const double *params_a, const double *params_b,
-                                const double *denom, double *out)
+
+// The leave-one-out half of grad_diff_run (api_loo.inc).  LooOut: the host outputs of the leave-one-out entry points, NULL members
+// are not written; LooDev: what loo_terms / loo_weights left on the device.
+struct LooOut {
+    double *ll = nullptr, *resid = nullptr, *var = nullptr, *u = nullptr;
+};
+struct LooDev {
+    double *d = nullptr, *r = nullptr, *se = nullptr, *term = nullptr, *u = nullptr, *sum = nullptr, *V = nullptr;
+};
+static int loo_terms(gpt_ctx *c, hipStream_t st, const double *U, LooDev *ld);
+static int loo_weights(gpt_ctx *c, hipStream_t st, double *U, double *W, LooDev *ld);
+static int loo_read_back(gpt_ctx *c, hipStream_t st, const LooDev &ld, const LooOut &lo);
+
+// The gradient of the LML -- or, with `loo`, of the leave-one-out objective -- for ANY term of the resident model, by central
+// differences of the pair function taken per pair (kgrad.hip): parameter h is given as its term's complete parameter vector at the
+// two stencil points, and every stencil point goes through parse_model as a one-term model with the ids and parameter counts the
+// fit was given -- whatever that refuses is refused here, before anything is launched.  After K_tot^-1 a parameter costs two O(N^2)
+// evaluations of its term instead of a factorisation.  The body of gpt_ll_grad_diff (loo == NULL: the weights alpha alpha^T - W)
+// and of gpt_loo_grad_diff (u alpha^T + alpha u^T - V, loo_weights): the same checks, the same launch groups.
+static int grad_diff_run(gpt_ctx *c, const char *who, int nh, const int *term_idx, const double *params_a, const double *params_b,
+                         const double *denom, double *out, const LooOut *loo)
 {
-    CTX_ENTER(c);
-    GPT_TRY(refuse_warp(c, "gpt_ll_grad_diff"));
+    GPT_TRY(refuse_warp(c, who));
     NEED_FACTOR(c);
     if (!c->have_kernel) {
-        gpt_set_error("gpt_ll_grad_diff needs a factorisation produced by gpt_fit / gpt_fit_sum / gpt_fit_terms");
+        gpt_set_error("%s needs a factorisation produced by gpt_fit / gpt_fit_sum / gpt_fit_terms", who);
         return GPT_E_STATE;
+    }
+    if (loo && c->dT) {
+        gpt_set_error("%s: not with a linear transform T -- dK_tot = T dK T^T needs the leave-one-out weights carried to the latent "
+                      "points, which is not implemented", who);
+        return GPT_E_NOTIMPL;
     }
     if (nh < 0 || (nh > 0 && (!term_idx || !params_a || !params_b || !denom)) || !out) return GPT_E_ARG;
     const ModelKernel &m = c->model;
@@ -428,7 +463,7 @@ extern "C" int gpt_ll_grad_diff(gpt_ctx *c, int nh, const int *term_idx, const d
     for (int h = 0; h < nh; h++) {
         if (term_idx[h] < 0 || term_idx[h] >= m.nterms) return GPT_E_ARG;
         if (!(denom[h] != 0.0) || std::isinf(denom[h])) {
-            gpt_set_error("gpt_ll_grad_diff: denom[%d] = %g", h, denom[h]);
+            gpt_set_error("%s: denom[%d] = %g", who, h, denom[h]);
             return GPT_E_ARG;
         }
         off[h + 1] = off[h] + (size_t)m.np[term_idx[h]];
@@ -452,6 +487,15 @@ extern "C" int gpt_ll_grad_diff(gpt_ctx *c, int nh, const int *term_idx, const d
     GPT_TRY(timer.init());
     GradWeights gw;
     GPT_TRY(grad_weights(c, st, timer.events(), &gw));
+    // the pair pass's weight matrix and second vector: W and none, or V and u
+    const double *pw = gw.Wp, *pu = nullptr;
+    LooDev ld;
+    if (loo) {
+        GPT_TRY(loo_terms(c, st, gw.U, &ld));
+        GPT_TRY(loo_weights(c, st, gw.U, gw.W, &ld));
+        pw = ld.V;
+        pu = ld.u;
+    }
     const int nblk = grad_reduce_blocks(gw.Np);
     double *dpart;
     KParams *dkp;
@@ -472,7 +516,7 @@ extern "C" int gpt_ll_grad_diff(gpt_ctx *c, int nh, const int *term_idx, const d
         int cnt = 0;
         while (b0 + cnt < total && cnt < GPT_GRAD_MAXH && term_of[b0 + cnt] == t) cnt++;
         GPT_TRY(launch_kgrad_diff(st, m.f1[t].kernel_id, m.second(t) ? m.f2[t].kernel_id : -1, c->D, dkp + 2 * b0, dkp + nk + 2 * b0, cnt,
-                                  c->dX, c->dn, gw.Np, gw.ap, gw.Wp, gw.ldwp, dpart));
+                                  c->dX, c->dn, gw.Np, gw.ap, pw, gw.ldwp, dpart, 1, pu));
         GPT_HIP_CHECK(hipMemcpyAsync(hpart.data(), dpart, hpart.size() * sizeof(double), hipMemcpyDeviceToHost, st));
         GPT_HIP_CHECK(hipStreamSynchronize(st));
         for (int q = 0; q < cnt; q++) {
@@ -490,6 +534,14 @@ extern "C" int gpt_ll_grad_diff(gpt_ctx *c, int nh, const int *term_idx, const d
         if (cnt <= 0) break;
     }
     if (c->dT) GPT_TRY(grad_noise_trace_T(c, st, gw.W, dpart, &out[nh]));
-    if (timer.on) GPT_TRY(grad_timing_report("gpt_ll_grad_diff", c->N, st, timer.ge));
+    if (loo) GPT_TRY(loo_read_back(c, st, ld, *loo));
+    if (timer.on) GPT_TRY(grad_timing_report(who, c->N, st, timer.ge));
     return stream_follows(c, st, c->stream, 1);
+}
+
+extern "C" int gpt_ll_grad_diff(gpt_ctx *c, int nh, const int *term_idx, const double *params_a, const double *params_b,
+                                const double *denom, double *out)
+{
+    CTX_ENTER(c);
+    return grad_diff_run(c, "gpt_ll_grad_diff", nh, term_idx, params_a, params_b, denom, out, nullptr);
 }

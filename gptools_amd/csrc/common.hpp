@@ -270,7 +270,8 @@ int launch_grad_reduce(hipStream_t st, const KParams &kp, int nh, const int *hl,
 // the pair pass of gpt_ll_grad_diff (kgrad.hip): nh <= GPT_GRAD_MAXH parameters of one term id1 (* id2 where id2 >= 0), 2 nh KParams in
 // device memory per factor (the term at the stencil points a, b of every parameter); dpartial as launch_grad_reduce
 int launch_kgrad_diff(hipStream_t st, int id1, int id2, int D, const KParams *d_kps, const KParams *d_kps2, int nh, const double *dX,
-                      const int32_t *dn, int64_t N, const double *dalpha, const double *dW, int64_t ldw, double *dpartial, int64_t nbatch = 1);
+                      const int32_t *dn, int64_t N, const double *dalpha, const double *dW, int64_t ldw, double *dpartial, int64_t nbatch = 1,
+                      const double *du = nullptr);      // du: the leave-one-out weights (gpt_loo_grad_diff), see kgrad.hip kgrad_weight
 // ... of a resident batch (gpt_ll_grad_diff_batch; kgrad.hip): launch_kgrad_diff with nbatch elements in the grid's second dimension
 // (element e: d_kps + 2 nh e, dalpha + e ldw, dW + e ldw^2, dpartial + e grad_reduce_blocks(N) (GPT_GRAD_MAXH + 1)), alpha_b = U_b z_b
 // and the sum of the partial rows in index order on the device
@@ -278,6 +279,11 @@ int launch_kgrad_batch_alpha(hipStream_t st, const double *dU, int64_t ldu, int6
                              int64_t N, int64_t nbatch, double *dalpha, int64_t sal);
 int launch_kgrad_batch_finish(hipStream_t st, const double *dpartial, const int32_t *dsrc, int nout, int64_t nblk, int64_t nbatch,
                               double *dout);
+// the leave-one-out entry points (kloo.hip): d_i = sum_{i <= k < N} U_ik^2, r = alpha / d, se = sqrt((1 + alpha^2 / d) / d) and the rows'
+// terms of L_LOO over the NP rows of U = L^-T (rows >= N: 1, 0, 0, 0), out1[0] the first N terms added in index order; A = W diag(se)
+int launch_loo_terms(hipStream_t st, const double *dU, int64_t ldu, const double *dalpha, int64_t N, int64_t NP, double *d, double *r,
+                     double *se, double *term, double *out1);
+int launch_loo_scale_cols(hipStream_t st, const double *dW, int64_t ldw, const double *se, int64_t n, double *dA, int64_t lda);
 int launch_add_diag(hipStream_t st, double *A, int64_t lda, int64_t n, const double *err, double diag_add, int64_t nbatch = 1,
                     int64_t bstride = 0);
 // Test aid (GPT_JITTER=<max microseconds> in the environment): a delay kernel of random length on `st`, called in front of

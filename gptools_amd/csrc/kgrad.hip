@@ -24,7 +24,9 @@
 // of the elements before it -- the strides follow from nh, ldw and the grid, so the kernel takes no further argument, and e is
 // wave-uniform: the element costs scalar registers only.  The single route is element 0 of a batch of one: the same instructions
 // on the same addresses, the same bits.  Tile geometry and summation order do not know the batch, so an element's partial sums
-// are the same whatever the batch around it is.  kgrad_batch_finish_kernel adds the partial sums of every element and launch
+// are the same whatever the batch around it is.  The LEAVE-ONE-OUT gradient (gpt_loo_grad_diff, api_loo.inc) is the same
+// pass with other weights, u_a alpha_b + alpha_a u_b - V_ab: a second vector u and V in the place of W, chosen at run time per launch
+// (kgrad_weight below).  kgrad_batch_finish_kernel adds the partial sums of every element and launch
 // group in index order, as the host does for the single route, and alpha of a batch comes from kgrad_batch_alpha_kernel.
 #include "kbuild_kernel.hpp"
 
@@ -42,6 +44,17 @@ __device__ __forceinline__ double kgrad_term_pair(const KParams &k1, const KPara
     else return any_pair<KID, D>(k1, xi, xj, ni, nj);
 }
 
+// The weight of pair (i, j), lane j: alpha_i alpha_j - W_ij for the LML (u == alpha, loo false: the expression this file has always
+// had there), u_i alpha_j + alpha_i u_j - V_ij for the leave-one-out objective (gpt_loo_grad_diff: W is V = W diag(e) W then).  `loo`
+// is the same in every lane of a launch -- one scalar branch per pair, not a template parameter: that would double every KID x D
+// instantiation.  On the diagonal this is the trace slot's entry, 2 u_i alpha_i - V_ii.
+__device__ __forceinline__ double kgrad_weight(bool loo, const double *__restrict__ alpha, const double *__restrict__ u,
+                                               const double *__restrict__ W, int64_t ldw, int64_t i, int64_t j, double aj, double uj)
+{
+    if (loo) return (u[i] * aj + alpha[i] * uj) - W[i * ldw + j];
+    return alpha[i] * aj - W[i * ldw + j];
+}
+
 // kps[2 h], kps[2 h + 1]: the term at the stencil points a, b of parameter h < nh <= GR_MAXH (kps2: the second factors of a product
 // term, else unused); partial: grad_reduce_blocks(N) x (GR_MAXH + 1), every entry written.  blockIdx.y: the element of a batch (see
 // the head of this file), 0 on the single route
@@ -49,7 +62,7 @@ template <int KID, int D>
 __global__ __launch_bounds__(KB_THREADS) void kgrad_diff_kernel(
     const KParams *__restrict__ kps_, const KParams *__restrict__ kps2_, int nh, const double *__restrict__ X,
     const int32_t *__restrict__ nn, int64_t N, const double *__restrict__ alpha_, const double *__restrict__ W_, int64_t ldw,
-    double *__restrict__ partial_)
+    double *__restrict__ partial_, const double *__restrict__ u_)
 {
     constexpr int64_t R = KB_RATIO;
     const int64_t e = blockIdx.y;
@@ -57,6 +70,8 @@ __global__ __launch_bounds__(KB_THREADS) void kgrad_diff_kernel(
     const KParams *__restrict__ kps2 = kps2_ + e * 2 * nh;         // (only a product term reads it)
     const double *__restrict__ alpha = alpha_ + e * ldw;
     const double *__restrict__ W = W_ + e * ldw * ldw;
+    const bool loo = u_ != nullptr;                                 // (a kernel argument: wave-uniform)
+    const double *__restrict__ u = loo ? u_ + e * ldw : alpha;
     double *__restrict__ partial = partial_ + e * (int64_t)gridDim.x * (GR_MAXH + 1);
     const int64_t b = blockIdx.x;
     int64_t g = (int64_t)((sqrt(1.0 + 8.0 * (double)b / (double)R) - 1.0) * 0.5);
@@ -75,7 +90,7 @@ __global__ __launch_bounds__(KB_THREADS) void kgrad_diff_kernel(
         xj[d] = X[jc * D + d];
         njr[d] = nn[jc * D + d];
     }
-    const double aj = alpha[jc];
+    const double aj = alpha[jc], uj = u[jc];
     __shared__ double red[KB_THREADS / 64][GR_MAXH + 1];
     const int lane = threadIdx.x & 63, wave = threadIdx.x >> 6;
 #pragma unroll 1
@@ -107,7 +122,7 @@ __global__ __launch_bounds__(KB_THREADS) void kgrad_diff_kernel(
                                                  gibbs_col_root(la, ca.rp, ca.rn), nir, njr[0], need_d);
                     const double vb = gibbs_core(s2b, xi, lb, Ab, gibbs_h_other<KID>(hb, cb.l), qb, xj[0], cb.l, cb.A, gibbs_h_other<KID>(cb.h, lb),
                                                  gibbs_col_root(lb, cb.rp, cb.rn), nir, njr[0], need_d);
-                    const double w = alpha[i] * aj - W[i * ldw + j];
+                    const double w = kgrad_weight(loo, alpha, u, W, ldw, i, j, aj, uj);
                     acc = fma((i == j) ? w : 2.0 * w, vb - va, acc);
                 }
             }
@@ -127,14 +142,14 @@ __global__ __launch_bounds__(KB_THREADS) void kgrad_diff_kernel(
                     xi[d] = X[i * D + d];
                     nir[d] = nn[i * D + d];
                 }
-                const double w = alpha[i] * aj - W[i * ldw + j];
+                const double w = kgrad_weight(loo, alpha, u, W, ldw, i, j, aj, uj);
                 const double w2 = (i == j) ? w : 2.0 * w;
                 const double dk = kgrad_term_pair<KID, D>(kb, kb2, xi, xj, nir, njr) - kgrad_term_pair<KID, D>(ka, ka2, xi, xj, nir, njr);
                 acc = fma(w2, dk, acc);
             }
         }
         // the noise trace: this lane's diagonal entry, if the tile holds it
-        if (live && h == GR_MAXH && j >= rbase && j < rend) acc += alpha[j] * aj - W[j * ldw + j];
+        if (live && h == GR_MAXH && j >= rbase && j < rend) acc += kgrad_weight(loo, alpha, u, W, ldw, j, j, aj, uj);
         for (int off = 32; off > 0; off >>= 1) acc += __shfl_down(acc, off);
         if (lane == 0) red[wave][h] = acc;
     }
@@ -149,9 +164,11 @@ __global__ __launch_bounds__(KB_THREADS) void kgrad_diff_kernel(
 // One launch: nh <= GPT_GRAD_MAXH parameters of ONE term, kernel id1 (* id2 where id2 >= 0) at num_dim D; d_kps / d_kps2: 2 nh
 // KParams each in device memory (d_kps2 only for a product).  The N points dX / dn against the weights alpha alpha^T - W.
 // nbatch > 1: that many elements, element e with d_kps + 2 nh e, dalpha + e ldw, dW + e ldw^2 and dpartial + e
-// grad_reduce_blocks(N) (GR_MAXH + 1); the points are shared.
+// grad_reduce_blocks(N) (GR_MAXH + 1); the points are shared.  du (N; NULL for the LML): the second vector of the leave-one-out
+// weights u alpha^T + alpha u^T - V, with V in the place of W (kgrad_weight).
 int launch_kgrad_diff(hipStream_t st, int id1, int id2, int D, const KParams *d_kps, const KParams *d_kps2, int nh, const double *dX,
-                      const int32_t *dn, int64_t N, const double *dalpha, const double *dW, int64_t ldw, double *dpartial, int64_t nbatch)
+                      const int32_t *dn, int64_t N, const double *dalpha, const double *dW, int64_t ldw, double *dpartial, int64_t nbatch,
+                      const double *du)
 {
     if (nh < 0 || nh > GR_MAXH || N <= 0 || !d_kps || (id2 >= 0 && !d_kps2) || nbatch < 1 || nbatch > 65535 || (nbatch > 1 && ldw < N))
         return GPT_E_ARG;
@@ -159,7 +176,7 @@ int launch_kgrad_diff(hipStream_t st, int id1, int id2, int D, const KParams *d_
         constexpr int KID = decltype(k)::value;
         return dispatch_dim<kid_max_dim(KID)>("ll_grad_diff", D, [&](auto d) {
             hipLaunchKernelGGL((kgrad_diff_kernel<KID, decltype(d)::value>), dim3((unsigned)grad_reduce_blocks(N), (unsigned)nbatch), dim3(KB_THREADS), 0, st,
-                               d_kps, d_kps2, nh, dX, dn, N, dalpha, dW, ldw, dpartial);
+                               d_kps, d_kps2, nh, dX, dn, N, dalpha, dW, ldw, dpartial, du);
             GPT_LAUNCH_CHECK();
             return GPT_OK;
         }, kid_dim_rule(KID));

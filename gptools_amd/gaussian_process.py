@@ -690,6 +690,147 @@ class GaussianProcess(object):
                 grad[i + nk + len(self.noise_k.free_params)] = dmu.dot(alpha)
         return grad + self._hyperprior_gradient()
 
+    # ---- leave-one-out cross-validation (gpt_loo, gpt_loo_grad_diff) ------------
+    def _loo(self):
+        """``(L_LOO, resid, var)`` of the current fit (``Context.loo``), cached with it."""
+        self.compute_K_L_alpha_ll()
+        return self._cached("loo", lambda: self._ctx.loo(len(self.y)))
+
+    def loo_predict(self, return_std=True):
+        """Leave-one-out predictions at the training observations (Rasmussen & Williams 5.4.2): ``m[i]`` is the mean at observation
+        i of the model fitted to all the others at the current hyperparameters and ``s[i]`` its standard deviation, the noise
+        of observation i included -- ``(y[i] - m[i]) / s[i]`` is standard normal if the model is right.  From the resident factor
+        (``gpt_loo``), no refits.  Returns ``m``, or ``(m, s)`` with ``return_std``, of length ``len(y)``.  Fits first if the
+        hyperparameters changed; every fit route serves, a transform ``T`` and a warped model included."""
+        _, resid, var = self._loo()
+        m = self.y - resid
+        return (m, np.sqrt(var)) if return_std else m
+
+    def loo_log_likelihood(self):
+        """The leave-one-out log predictive probability ``sum_i log N(y_i; m_i, s_i^2)`` at the current hyperparameters, without
+        the hyperprior (see :meth:`loo_predict`)."""
+        return self._loo()[0]
+
+    def _loo_gradient_refusal(self):
+        """Why ``gpt_loo_grad_diff`` cannot serve this model, or ``None``: a reason of :meth:`_ll_gradient_refusal`, or a linear
+        transform."""
+        why = self._ll_gradient_refusal()
+        if why is None and self.T is not None:
+            why = "a linear transform T (the leave-one-out weights would have to be carried to the latent points)"
+        return why
+
+    def _loo_value_and_gradient(self, rel_step):
+        """``(L_LOO, gradient of L_LOO + log hyperprior)`` at the current hyperparameters from ONE ``gpt_loo_grad_diff`` call."""
+        why = self._loo_gradient_refusal()
+        if why is not None:
+            raise NotImplementedError("loo_gradient is not available for %s" % why)
+        self.compute_K_L_alpha_ll()
+        if self._fit_mode != "kernel":
+            raise NotImplementedError("loo_gradient is not available for a fit by the %s route" % self._fit_mode)
+        slot, tix, pa, pb, denom = self._ll_gradient_stencil(rel_step)
+        g_dev, ll, resid, var, u = self._ctx.loo_grad_diff(tix, pa, pb, denom, len(self.y))
+        self._cache["loo"] = (ll, resid, var)
+        return ll, self._loo_gradient_assemble(slot, g_dev, u)
+
+    def loo_gradient(self, rel_step=6e-6):
+        """Gradient of :meth:`loo_log_likelihood` plus the log hyperprior with respect to the free hyperparameters at their current
+        values (``gpt_loo_grad_diff``): ``K_tot^-1`` and one further GEMM on the device, whatever the number of parameters, then per
+        free kernel parameter the two pair passes of :meth:`ll_gradient` against the leave-one-out weights.  Fits first if the
+        hyperparameters changed.  ``NotImplementedError`` where :meth:`ll_gradient` raises it, and for a transform ``T``."""
+        return self._loo_value_and_gradient(rel_step)[1]
+
+    def _loo_gradient_assemble(self, slot, g_dev, u):
+        """:meth:`_ll_gradient_assemble` for the leave-one-out objective: ``g_dev`` are ``gpt_loo_grad_diff``'s entries (the noise
+        trace last) and the mean function's entries are taken against ``u = K_tot^-1 resid`` where the LML has ``alpha``.  Host
+        only."""
+        grad = np.zeros(len(self.free_params))
+        for s, v in zip(slot, g_dev[:-1]):
+            grad[s] += v
+        nk = len(self.k.free_params)
+        if self._noise_is_free():
+            grad[nk] = 2.0 * self.noise_k.params[0] * g_dev[-1]
+        if self.mu is not None:
+            u = np.asarray(u, dtype=float).ravel()
+            free_idx = np.arange(0, len(self.mu.params), dtype=int)[~self.mu.fixed_params]
+            for i, pi in enumerate(free_idx):
+                dmu = self.mu(self.X, self.n, hyper_deriv=int(pi))
+                if self.T is not None:
+                    dmu = self.T.dot(dmu)
+                grad[i + nk + len(self.noise_k.free_params)] = dmu.dot(u)
+        return grad + self._hyperprior_gradient()
+
+    def _loo_objective(self, device):
+        """``(fun, jac)`` for scipy.optimize.minimize with ``objective="loo"``: ``fun`` is minus (``L_LOO`` + log hyperprior), ``+inf``
+        where the hyperprior excludes the point or the evaluation fails.  ``device``: value and ``jac`` of a point come from one
+        ``gpt_loo_grad_diff`` call (zeros where the value is ``+inf``); else ``jac`` is ``None`` and scipy differences ``fun``."""
+        last = {}
+
+        def evaluate(x):
+            x = np.array(x, dtype=float)
+            try:
+                self._assign_free(x)
+                prior = self.hyperprior(self.params)
+                if np.isinf(prior):
+                    raise GPImpossibleParamsError("the hyperprior excludes these hyperparameters")
+                if device:
+                    ll, grad = self._loo_value_and_gradient(6e-6)
+                else:
+                    ll, grad = self.loo_log_likelihood(), None
+                f, g = -1.0 * (ll + prior), (None if grad is None else -1.0 * grad)
+                if not np.isfinite(f) or (g is not None and not np.all(np.isfinite(g))):
+                    raise FloatingPointError("the leave-one-out objective is not finite")
+            except Exception as exc:
+                if self.verbose and not isinstance(exc, GPImpossibleParamsError):
+                    warnings.warn("evaluation failed at free hyperparameters %s and counts as +inf:\n%s"
+                                  % (x, traceback.format_exc()))
+                f, g = np.inf, np.zeros(len(x))
+            last["x"], last["f"], last["g"] = x, f, g
+            return f, g
+
+        def fun(x):
+            return evaluate(x)[0]
+
+        def jac(x):
+            if "x" in last and np.array_equal(last["x"], np.asarray(x, dtype=float)):
+                return last["g"]
+            return evaluate(x)[1]
+        return fun, (jac if device else None)
+
+    def remove_outliers(self, thresh=3, method="predict", **predict_kwargs):
+        """Drop the observations that sit ``thresh`` standard deviations or more from what the GP says about them, and return
+        them (ref: gaussian_process.py:543-621).
+
+        ``method="predict"``, the reference's rule: observation i is bad when ``abs(predict(X, n, noise=False)[i] - y[i]) /
+        err_y[i] >= thresh``; an observation with ``err_y == 0`` is never bad.  ``predict_kwargs`` go to :meth:`predict`.  The
+        rule ignores the GP's own uncertainty, and the mean it tests against has seen the point it judges.
+        ``method="loo"``: ``abs(y[i] - m[i]) / s[i] >= thresh`` with :meth:`loo_predict`'s leave-one-out mean and standard
+        deviation -- every point is judged by the model that has not seen it, the GP's uncertainty and the noise included.
+
+        Returns ``(X_bad, y_bad, err_y_bad, n_bad, bad_idxs)``; ``bad_idxs`` is a boolean array over the observations as they
+        were before the call.  The next evaluation refits on what is left.  With a transform ``T``: ``NotImplementedError``."""
+        if method not in ("predict", "loo"):
+            raise ValueError("method must be 'predict' or 'loo', got %r" % (method,))
+        if self.T is not None:
+            raise NotImplementedError("remove_outliers is not available with a linear transform T")
+        if method == "loo":
+            if predict_kwargs:
+                raise TypeError("method='loo' takes no predict arguments, got %s" % sorted(predict_kwargs))
+            m, s = self.loo_predict(return_std=True)
+            deltas = np.abs(self.y - m) / s
+        else:
+            mean = self.predict(self.X, n=self.n, noise=False, return_std=False, **predict_kwargs)
+            exact = self.err_y == 0
+            deltas = np.abs(np.asarray(mean, dtype=float).ravel() - self.y) / np.where(exact, 1.0, self.err_y)
+            deltas[exact] = 0.0
+        bad = deltas >= thresh
+        removed = (self.X[bad, :], self.y[bad], self.err_y[bad], self.n[bad, :], bad)
+        self.X, self.n, self.y, self.err_y = self.X[~bad, :], self.n[~bad, :], self.y[~bad], self.err_y[~bad]
+        self.K_up_to_date = False
+        self._data_on_device = False
+        self._dist_plan = None
+        self._data_version = getattr(self, "_data_version", 0) + 1
+        return removed
+
     def _batch_gradient_refusal(self):
         """Why :meth:`ll_gradient_batch` (``gpt_ll_grad_diff_batch``) cannot serve this model, or ``None``: a reason of
         :meth:`_ll_gradient_refusal`, a linear transform, or more points than the batched evaluator takes."""
@@ -1285,7 +1426,7 @@ class GaussianProcess(object):
 
     # ---- MAP estimate (ref: gptools/gaussian_process.py:623-783, :2443-2486) ------------------
     def optimize_hyperparameters(self, method="SLSQP", opt_kwargs={}, verbose=False, random_starts=None,
-                                 num_proc=None, max_tries=1, batch_fd=None, gradient=None, batch_starts=False):
+                                 num_proc=None, max_tries=1, batch_fd=None, gradient=None, batch_starts=False, objective="ll"):
         """Maximise the log-posterior with ``scipy.optimize.minimize`` from ``random_starts`` draws
         of the hyperprior (0: start from the current values).  Every objective evaluation is one GPU
         fit.  ``num_proc`` is accepted for compatibility: a HIP context must not be shared across forked
@@ -1303,9 +1444,28 @@ class GaussianProcess(object):
         :meth:`ll_gradient_batch`, a single launch sequence, instead of one fit and one gradient per start and evaluation.  The
         starts, ``max_tries``, the choice of the best result, the warnings and the return value are those of the sequential loop.
         ``NotImplementedError`` for a model :meth:`ll_gradient_batch` refuses; ``ValueError`` under a ``torch.distributed`` job
-        of more than one rank."""
+        of more than one rank.
+
+        ``objective="loo"``: maximise the leave-one-out log predictive probability plus the log hyperprior
+        (:meth:`loo_log_likelihood`) instead of the log-posterior (``"ll"``, the default).  With ``gradient="device"`` the value
+        and ``jac`` of a point come from one ``gpt_loo_grad_diff`` call (:meth:`loo_gradient`); with ``gradient=None`` scipy
+        differences the objective itself, one fit per evaluation.  ``ValueError`` together with ``batch_starts=True``,
+        ``use_hyper_deriv`` or a ``jac`` of the caller's; the hyperparameters the optimiser ends at are kept, ``ll`` is the
+        log-posterior there."""
         if gradient not in (None, "device"):
             raise ValueError("gradient must be None or 'device', got %r" % (gradient,))
+        if objective not in ("ll", "loo"):
+            raise ValueError("objective must be 'll' or 'loo', got %r" % (objective,))
+        loo = objective == "loo"
+        if loo:
+            if batch_starts:
+                raise ValueError("objective='loo' cannot be combined with batch_starts=True: there is no batched leave-one-out")
+            if self.use_hyper_deriv or "jac" in (opt_kwargs or {}):
+                raise ValueError("objective='loo' cannot be combined with use_hyper_deriv or a jac of the caller's")
+            if gradient == "device":
+                why = self._loo_gradient_refusal()
+                if why is not None:
+                    raise NotImplementedError("objective='loo' with gradient='device' is not available for %s" % why)
         if batch_starts:
             nstarts = 1 if random_starts == 0 else (max(num_proc or 1, 1) if random_starts is None else int(random_starts))
             chosen = (opt_kwargs or {}).get("method", method)
@@ -1355,22 +1515,26 @@ class GaussianProcess(object):
         if self.use_hyper_deriv:
             opt_kwargs["jac"] = True
 
-        objective = self.update_hyperparameters
+        target = self.update_hyperparameters
         # Finite-difference gradients (what scipy does itself when no `jac` is given) through ll_batch: the p
         # perturbed points of one gradient are independent evaluations, kept two in flight on the GPU.  The points
         # and the difference formula are scipy's own (approx_derivative is replayed), so the iterates are the same.
         fd_eps = {"L-BFGS-B": 1e-8, "TNC": 1e-8, "SLSQP": 1.4901161193847656e-08}
         partitioned = self._partitioned_possible()       # every evaluation is a collective: no local batching,
-        if gradient == "device" and not batch_starts:
-            objective, opt_kwargs["jac"] = self._device_grad_objective()
+        if loo:
+            target, loo_jac = self._loo_objective(gradient == "device")
+            if loo_jac is not None:
+                opt_kwargs["jac"] = loo_jac
+        elif gradient == "device" and not batch_starts:
+            target, opt_kwargs["jac"] = self._device_grad_objective()
         elif (not batch_starts and batch_fd is not False and int(self.batch_concurrency) > 1 and not self.use_hyper_deriv and not partitioned
                 and "jac" not in opt_kwargs and method in fd_eps and self._fast_fit_possible()):
             eps = (opt_kwargs.get("options") or {}).get("eps", fd_eps[method])
-            objective, opt_kwargs["jac"] = self._batched_fd(eps, np.asarray(opt_kwargs["bounds"], dtype=float))
+            target, opt_kwargs["jac"] = self._batched_fd(eps, np.asarray(opt_kwargs["bounds"], dtype=float))
 
         def run(samp):
             try:
-                return scipy.optimize.minimize(objective, samp, **opt_kwargs)
+                return scipy.optimize.minimize(target, samp, **opt_kwargs)
             except Exception:
                 if self.verbose:
                     warnings.warn("start %s dropped, the optimiser raised (free hyperparameters now %s):\n%s"
@@ -1405,7 +1569,7 @@ class GaussianProcess(object):
         if verbose:
             print("%d starts completed; the best one:" % len(finished))
             print(best)
-            print("log-posterior %.6g" % (-best.fun))
+            print("%s %.6g" % ("leave-one-out log probability + log prior" if loo else "log-posterior", -best.fun))
             for name, v in zip(self.free_param_names[:], best.x):
                 print("  %s = %.6g" % (str(name).replace("\\", ""), v))
         if not best.success:

@@ -235,7 +235,7 @@ int gpt_ctx_destroy(gpt_ctx *ctx);
  *   "timing"       0/1: record per-phase HIP events (gpt_last_timings)
  *   "profile_gemm" 0/1: HIP-event timing of each large GEMM launch (gpt_gemm_profile_read)
  *   "tile"         0 by launch size (default), 32, 64: force the GEMM macro-tile (bit-identical results either way)
- *   "debug_poison" 0/1 (test aid): gpt_ll_grad fills its scratch matrices with NaN before use
+ *   "debug_poison" 0/1 (test aid): gpt_ll_grad*, gpt_loo and gpt_loo_grad_diff fill their scratch matrices with NaN before use
  *   "edge_test_stall" 1 (test aid): the next evaluation's first flag is withheld once, so that the bounded wait, the repeat on
  *                  event edges and the switch of the process to event edges can be tested
  *   measured and off by default: "ramp", "inner" (1: left-looking panels, 2: once at most 4608 rows
@@ -503,6 +503,30 @@ int gpt_ll_grad_diff(gpt_ctx *ctx, int nh, const int *term_idx, const double *pa
  * with a linear transform (gpt_set_T). */
 int gpt_ll_grad_diff_batch(gpt_ctx *ctx, int nh, const int *term_idx, const double *params_a, const double *params_b,
                            const double *denom, const int32_t *keep, double *out, double *alpha_out);
+
+/* ---- leave-one-out cross-validation (Rasmussen & Williams 5.4.2) ----------------- */
+/* With W = K_tot^-1 over the N observations, alpha = W (y - T mu) and d_i = W_ii, from the resident factor:
+ *   resid[i] = alpha_i / d_i = y_i - m_i, m_i the prediction at point i of the model that has not seen it;
+ *   var[i]   = 1 / d_i, that prediction's variance (the noise of point i included);
+ *   *loo_ll  = sum_i [ 1/2 log d_i - 1/2 alpha_i^2 / d_i - 1/2 log 2 pi ], the leave-one-out log predictive probability.
+ * resid and var: N doubles each, or NULL.  The diagonal comes from the triangular inverse alone, d_i = sum_k (L^-T)_ik^2: ~N^3 / 3
+ * flop, no K_tot^-1.  Needs nothing but a resident factor: every fit serves (gpt_fit*, gpt_fit_matrix, with warp layers, with a
+ * transform T -- N is then the number of observations).  Deterministic: the terms are added in index order, repeated calls return
+ * the same bits. */
+int gpt_loo(gpt_ctx *ctx, double *loo_ll, double *resid, double *var);
+
+/* The gradient of that value with respect to kernel parameters, in the shape of gpt_ll_grad_diff -- same arguments, same checks,
+ * same launch groups -- with the weights of the pair pass replaced:
+ *   out[h]  = 1/2 * sum_ab (u_a alpha_b + alpha_a u_b - V_ab) * (k_b - k_a)[a][b] / denom[h]      for h < nh,
+ *   out[nh] = 1/2 * sum_i (2 u_i alpha_i - V_ii)      (times 2 sigma_n: the derivative for a DiagonalNoiseKernel),
+ * where u = W resid, V = W diag(e) W and e_i = (1 + alpha_i^2 / d_i) / d_i.  Also returns what gpt_loo returns (loo_ll, resid, var:
+ * each may be NULL) and u (N doubles or NULL): a mean function's parameter theta has the derivative u^T d mu / d theta.
+ * Cost: K_tot^-1 as gpt_ll_grad_diff, one more NP^3 flop for V = A A^T (A = W diag(sqrt e)) whatever nh is, then the O(N^2) pair
+ * passes.  Deterministic.
+ * Errors: those of gpt_ll_grad_diff, and GPT_E_NOTIMPL with a linear transform T resident (dK_tot = T dK T^T: the weights would
+ * have to be carried to the latent points). */
+int gpt_loo_grad_diff(gpt_ctx *ctx, int nh, const int *term_idx, const double *params_a, const double *params_b,
+                      const double *denom, double *out, double *loo_ll, double *resid, double *var, double *u);
 
 /* Replaces  ref: gaussian_process.py:965-1006 for the T-free, untransformed case:
  *   Kstar = K(X, Xstar) ; mean = Kstar^T alpha ; v = L^-1 Kstar ; cov = K(Xstar,Xstar) - v^T v ;
