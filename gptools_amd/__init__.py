@@ -11,4 +11,5 @@ from .utils import *               # noqa: F401,F403
 from .kernel import *              # noqa: F401,F403
 from .mean import *                # noqa: F401,F403
 from .gaussian_process import *    # noqa: F401,F403
+from .sparse import *              # noqa: F401,F403
 from .sampler import EnsembleSampler      # noqa: F401

@@ -43,6 +43,7 @@ def kernel_base_id(kernel_id):
 
 MAX_DIM = 16
 WARP_LINEAR, WARP_BETA, WARP_MAX_LAYERS = 1, 2, 4
+SPARSE_METHODS = {"fitc": 0, "vfe": 1, "dtc": 2}      # GPT_SPARSE_FITC / _VFE / _DTC
 
 _dp = C.POINTER(C.c_double)
 _ip = C.POINTER(C.c_int32)
@@ -120,6 +121,11 @@ SIGNATURES = {
     "gpt_dev_copy2d_on": (C.c_int, [_vp, _vp, _i64, _i64, _vp, _i64, _vp, _i64]),
     "gpt_dev_pad_block": (C.c_int, [_vp, _vp, _i64, _i64, _i64, _i64, _i64, _vp, C.c_double]),
     "gpt_dev_panel_scalars": (C.c_int, [_vp, _vp, _i64, _i64, _i64, _vp]),
+    "gpt_sparse_set_inducing": (C.c_int, [_vp, _dp, _ip, _i64]),
+    "gpt_sparse_fit": (C.c_int, [_vp, C.c_int, C.c_int, _ip, _ip, _dp, _ip, _ip, C.c_double, _dp, _dp, C.c_double, _i64, _dp, _dp]),
+    "gpt_sparse_predict": (C.c_int, [_vp, _dp, _ip, _i64, C.c_int, _dp, _ip, _dp, _dp, _dp]),
+    "gpt_sparse_get_c": (C.c_int, [_vp, _dp]),
+    "gpt_dev_sparse_gram": (C.c_int, [_vp, _vp, _i64, _i64, _i64, C.c_int, _vp, _i64]),
 }
 
 _lib = None
@@ -706,6 +712,43 @@ class Context(object):
         check(self._lib.gpt_predict(self.handle, dptr(Xstar), iptr(nstar), M, int(want), dptr(npar), iptr(nn),
                                     dptr(mean), dptr(std), dptr(cov)))
         return mean, std, cov
+
+    # ---- inducing-point approximations (gpt_sparse_*) ----------------------------------------------
+    def sparse_set_inducing(self, Z, nZ=None):
+        Z = f64(Z)
+        nZ = None if nZ is None else i32(nZ)
+        self._sparse_M = None
+        check(self._lib.gpt_sparse_set_inducing(self.handle, dptr(Z), iptr(nZ), Z.shape[0]))
+        self._sparse_M = Z.shape[0]
+
+    def sparse_fit(self, method, terms, noise_var, y, err_y, jitter, chunk_rows=0):
+        """gpt_sparse_fit: ``method`` one of ``SPARSE_METHODS``' values, ``terms`` as :meth:`fit_terms` takes them ->
+        ``(ll, parts)`` with ``parts`` the five sums of the header."""
+        ids, ids2, npar, npar1, flat = self._pack_terms(terms)
+        y, err_y = f64(y), f64(err_y)
+        ll = C.c_double()
+        parts = np.zeros(5)
+        check(self._lib.gpt_sparse_fit(self.handle, int(method), len(ids), iptr(ids), iptr(ids2), dptr(flat), iptr(npar), iptr(npar1),
+                                       float(noise_var), dptr(y), dptr(err_y), float(jitter), int(chunk_rows), C.byref(ll),
+                                       dptr(parts)))
+        return ll.value, parts
+
+    def sparse_predict(self, Xstar, nstar, want, noise_params=None, noise_n=None):
+        Xstar, nstar = f64(Xstar), i32(nstar)
+        M = Xstar.shape[0]
+        mean = np.empty(M)
+        std = np.empty(M) if want >= 1 else None
+        cov = np.empty((M, M)) if want == 2 else None
+        npar = None if noise_params is None else f64(noise_params)
+        nn = None if noise_n is None else i32(noise_n)
+        check(self._lib.gpt_sparse_predict(self.handle, dptr(Xstar), iptr(nstar), M, int(want), dptr(npar), iptr(nn), dptr(mean),
+                                           dptr(std), dptr(cov)))
+        return mean, std, cov
+
+    def sparse_get_c(self):
+        out = np.empty(int(self._sparse_M))
+        check(self._lib.gpt_sparse_get_c(self.handle, dptr(out)))
+        return out
 
     def cov_sample(self, diag_add, rand_vars):
         """``cholesky(cov + diag_add I) @ rand_vars`` for the covariance the last ``predict(..., want=2, device_cov=True)`` left

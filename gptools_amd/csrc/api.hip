@@ -53,7 +53,8 @@ enum { SLOT_XI = 0, SLOT_XJ, SLOT_NI, SLOT_NJ, SLOT_OUT, SLOT_KST, SLOT_KSS, SLO
        SLOT_RHS, SLOT_LOW, SLOT_KFULL, SLOT_TK, SLOT_ZERO, SLOT_UINV, SLOT_WINV, SLOT_GPART, SLOT_BINV, SLOT_BTMP,
        SLOT_BINV2, SLOT_BINV3, SLOT_BINV3U, SLOT_BINVU, SLOT_BATCH_A, SLOT_BATCH_WS, SLOT_BATCH_MISC, SLOT_SPLITK,
        SLOT_PB_V, SLOT_PB_COV, SLOT_PB_MISC, SLOT_XSW, SLOT_SS, SLOT_SI, SLOT_SJ, SLOT_WB_X, SLOT_WB_S, SLOT_WB_P, SLOT_GKP, SLOT_GB_U, SLOT_GB_W, SLOT_GB_MISC,
-       SLOT_LOO_V, SLOT_LOO_VEC, SLOT_COUNT };
+       SLOT_LOO_V, SLOT_LOO_VEC,
+       SLOT_SP_Z, SLOT_SP_LU, SLOT_SP_LB, SLOT_SP_V, SLOT_SP_W, SLOT_SP_G, SLOT_SP_PART, SLOT_SP_MISC, SLOT_SP_Y, SLOT_COUNT };
 
 struct gpt_ctx {
     int device = 0;
@@ -168,6 +169,15 @@ struct gpt_ctx {
     std::vector<double> rb_nv;            // element noise variances
     int64_t cov_M = 0;                 // > 0: SLOT_KSS holds the lower triangle of the predictive covariance of the last gpt_predict(want = 2, cov_out = NULL)
     ModelKernel model;               // the model kernel of the resident factorisation (gpt_fit, gpt_fit_sum, gpt_fit_terms)
+    // The INDUCING-POINT state (api_sparse.inc), beside the dense factor and independent of it: the inducing
+    // inputs (SLOT_SP_Z) and, after a gpt_sparse_fit that succeeded, L_u (SLOT_SP_LU), the augmented L_B with c in its row M
+    // (SLOT_SP_LB), each with its packed workspace behind the matrix.  gpt_set_data and gpt_sparse_set_inducing drop all of it.
+    int64_t sp_M = 0;                  // inducing points resident (0: none)
+    long sp_zmaxsum = 0, sp_zcolmax[GPT_MAX_DIM] = {};      // their largest order row sum / order per coordinate
+    bool sp_fitted = false;
+    ModelKernel sp_model;              // the model kernel of the resident sparse fit
+    int sp_ncu = 0;                    // compute units of the device (the Gram kernel's slice count), read on first use
+    std::vector<hipEvent_t> sp_events; // phase marks of a timed gpt_sparse_fit (option "timing")
     double timings[5] = {0, 0, 0, 0, 0};
     // per-launch HIP-event timing of the dominant (large) GEMM/SYRK launches, for the roofline line
     int prof_gemm = 0;
@@ -239,5 +249,6 @@ static int stream_follows(gpt_ctx *c, hipStream_t from, hipStream_t to, size_t i
 #include "api_solve.inc"      // many-right-hand-side solves against the resident factor: block inverses, right-TRSM by GEMMs, split-k; pinned host buffers
 #include "api_predict.inc"      // gpt_predict, gpt_cov_sample, gpt_solve_L / gpt_cho_solve, gpt_potrf_host / gpt_gemm_nt_host
 #include "api_dev.inc"      // device API (gpt_dev_*): raw device pointers on the context's streams, for the one-process-per-GPU engines
+#include "api_sparse.inc"      // inducing-point approximations (FITC / VFE / DTC): gpt_sparse_set_inducing, gpt_sparse_fit, gpt_sparse_predict
 #include "api_plan.inc"      // compiled schedules of the partitioned engines: gpt_plan_* (op list replay, RCCL called directly)
 #include "api_ensemble.inc"      // gpt_ensemble_run: the ensemble sampler's loop (ensemble.hpp) around the batched fit

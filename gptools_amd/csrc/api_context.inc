@@ -105,6 +105,7 @@ extern "C" int gpt_ctx_destroy(gpt_ctx *c)
     for (auto &b : c->slots)
         if (b.p) hipFree(b.p);
     for (auto e : c->events) hipEventDestroy(e);
+    for (auto e : c->sp_events) hipEventDestroy(e);
     for (auto &g : c->gprof) { hipEventDestroy(g.e0); hipEventDestroy(g.e1); }
     for (int i = 0; i < 5; i++)
         if (c->tev[i]) hipEventDestroy(c->tev[i]);

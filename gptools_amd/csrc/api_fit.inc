@@ -42,6 +42,8 @@ extern "C" int gpt_set_data(gpt_ctx *c, const double *X, const int32_t *n, int64
     invalidate_factor(c);
     c->have_kernel = false;
     c->batch_gen++;                     // (the resident batch was fitted to the old data)
+    c->sp_M = 0;                        // (the inducing points and the sparse fit belong to one data set: gpt_sparse_set_inducing)
+    c->sp_fitted = false;
     if (c->dT) hipFree(c->dT);          // a transform belongs to one data set
     c->dT = nullptr;
     c->Ny = 0;

@@ -319,4 +319,13 @@ int launch_zero2d(hipStream_t st, int64_t rows, int64_t cols, double *dst, int64
 int launch_pad_block(hipStream_t st, double *A, int64_t lda, int64_t c0, int64_t nb, int64_t n_valid, int64_t n_pad,
                      const double *dy, double big);
 int launch_row_sumsq(hipStream_t st, const double *row, int64_t w, double *acc);
+// the inducing-point path (ksparse.hip)
+int launch_sparse_lambda(hipStream_t st, double *V, int64_t ldv, int64_t rows, int64_t M, int method, const double *kdiag,
+                         const double *r, const double *err, double noise_var, double *rowval, int64_t ldr, int32_t *bad);
+int launch_sparse_rowsum(hipStream_t st, const double *rowval, int64_t ldr, int64_t rows, double *acc);
+int launch_sparse_gram(hipStream_t st, const double *V, int64_t ldv, int64_t rows, int64_t mg, int nslices, double *part, double *G,
+                       int64_t ldg);
+int launch_sparse_assemble_b(hipStream_t st, const double *G, int64_t ldg, int64_t M, double *B, int64_t bp, double big);
+int launch_sparse_var(hipStream_t st, const double *V, const double *W, int64_t ld, int64_t rows, int64_t M, const double *kdiag,
+                      double *var);
 int launch_panel_scalars(hipStream_t st, const double *P, int64_t ldp, int64_t w, int64_t zrow, double *acc);

@@ -1,0 +1,268 @@
+// ksparse.hip -- device kernels of the inducing-point (FITC / VFE / DTC) path, gfx950.
+//
+// One chunk of training rows arrives as V^T (rows x LDV, row-major): row i holds (L_u^-1 k(Z, x_i))^T in columns [0, M), zeros
+// behind.  sparse_lambda_kernel turns it into V~^T -- every row scaled by Lambda_i^-1/2, with r~_i = Lambda_i^-1/2 r_i in column M
+// -- and the hot path, sparse_gram_kernel, adds V~ V~^T over the chunk's rows to G (lower 64 x 64 tiles): the contraction index is
+// the ROW of the chunk, so both MFMA operands of a k-step are 16-double segments of the same four rows and nothing is transposed.
+// With the r~ column, row M of G is b = V Lambda^-1 r and G[M][M] = r^T Lambda^-1 r: the augmented factorisation of B = I + G
+// delivers c = L_B^-1 b in its row M.
+//
+// Determinism: every sum has a fixed order.  The Gram kernel splits the chunk's rows into S slices, workgroup (tile, slice) writes
+// its partial tile to a workspace and sparse_gram_reduce_kernel adds the S partials to G in slice order: no floating-point atomics.
+#include "common.hpp"
+
+// ---- per-row pass ------------------------------------------------------------------------------------------------------------------
+// method: 0 fitc (Lambda_i = k_i - q_i + s_i), 1 vfe, 2 dtc (Lambda_i = s_i); s_i = noise_var + err_i^2.
+// rowval[i] = log Lambda_i, rowval[ldr + i] = (k_i - q_i) / s_i (vfe, else 0).  A row whose Lambda_i is not a positive finite number
+// raises *bad and contributes nothing (its scale is 0): the host reads the word once, at the end of the fit.
+__global__ __launch_bounds__(256) void sparse_lambda_kernel(double *__restrict__ V, int64_t ldv, int64_t rows, int64_t M, int method,
+                                                            const double *__restrict__ kdiag, const double *__restrict__ r,
+                                                            const double *__restrict__ err, double noise_var,
+                                                            double *__restrict__ rowval, int64_t ldr, int32_t *__restrict__ bad)
+{
+    __shared__ double part[4];
+    __shared__ double scale;
+    const int64_t i = blockIdx.x;
+    if (i >= rows) return;
+    double *row = V + i * ldv;
+    const int lane = threadIdx.x & 63, wave = threadIdx.x >> 6;
+    double a0 = 0.0, a1 = 0.0;
+    int64_t c = threadIdx.x;
+    for (; c + 256 < M; c += 512) {
+        const double v0 = row[c], v1 = row[c + 256];
+        a0 = fma(v0, v0, a0);
+        a1 = fma(v1, v1, a1);
+    }
+    for (; c < M; c += 256) {
+        const double v0 = row[c];
+        a0 = fma(v0, v0, a0);
+    }
+    double acc = a0 + a1;
+    for (int off = 32; off > 0; off >>= 1) acc += __shfl_down(acc, off);
+    if (lane == 0) part[wave] = acc;
+    __syncthreads();
+    if (threadIdx.x == 0) {
+        const double q = (part[0] + part[1]) + (part[2] + part[3]);
+        const double e = err[i], s = noise_var + e * e, kmq = kdiag[i] - q;
+        const double lam = (method == 0) ? kmq + s : s;
+        const bool ok = lam > 0.0 && lam < INFINITY;
+        if (!ok) *bad = 1;
+        rowval[i] = ok ? log(lam) : 0.0;
+        rowval[ldr + i] = (ok && method == 1) ? kmq / s : 0.0;
+        scale = ok ? 1.0 / sqrt(lam) : 0.0;
+    }
+    __syncthreads();
+    const double sc = scale;
+    for (c = threadIdx.x; c < M; c += 256) row[c] *= sc;
+    if (threadIdx.x == 0) row[M] = r[i] * sc;
+}
+
+int launch_sparse_lambda(hipStream_t st, double *V, int64_t ldv, int64_t rows, int64_t M, int method, const double *kdiag,
+                         const double *r, const double *err, double noise_var, double *rowval, int64_t ldr, int32_t *bad)
+{
+    if (rows <= 0) return GPT_OK;
+    if (M < 0 || M >= ldv || rows > ldr) {
+        gpt_set_error("sparse_lambda: M = %lld does not leave a column for r in rows of %lld", (long long)M, (long long)ldv);
+        return GPT_E_ARG;
+    }
+    hipLaunchKernelGGL(sparse_lambda_kernel, dim3((unsigned)rows), dim3(256), 0, st, V, ldv, rows, M, method, kdiag, r, err, noise_var,
+                       rowval, ldr, bad);
+    GPT_LAUNCH_CHECK();
+    return GPT_OK;
+}
+
+// acc[0] += sum_i rowval[i], acc[1] += sum_i rowval[ldr + i] over the chunk's rows: one workgroup, a fixed order
+__global__ __launch_bounds__(256) void sparse_rowsum_kernel(const double *__restrict__ rowval, int64_t ldr, int64_t rows,
+                                                            double *__restrict__ acc)
+{
+    __shared__ double s0[4], s1[4];
+    double a = 0.0, b = 0.0;
+    for (int64_t i = threadIdx.x; i < rows; i += 256) {
+        a += rowval[i];
+        b += rowval[ldr + i];
+    }
+    for (int off = 32; off > 0; off >>= 1) {
+        a += __shfl_down(a, off);
+        b += __shfl_down(b, off);
+    }
+    if ((threadIdx.x & 63) == 0) {
+        s0[threadIdx.x >> 6] = a;
+        s1[threadIdx.x >> 6] = b;
+    }
+    __syncthreads();
+    if (threadIdx.x == 0) {
+        acc[0] += ((s0[0] + s0[1]) + s0[2]) + s0[3];
+        acc[1] += ((s1[0] + s1[1]) + s1[2]) + s1[3];
+    }
+}
+
+int launch_sparse_rowsum(hipStream_t st, const double *rowval, int64_t ldr, int64_t rows, double *acc)
+{
+    if (rows <= 0) return GPT_OK;
+    hipLaunchKernelGGL(sparse_rowsum_kernel, dim3(1), dim3(256), 0, st, rowval, ldr, rows, acc);
+    GPT_LAUNCH_CHECK();
+    return GPT_OK;
+}
+
+// ---- the weighted Gram -------------------------------------------------------------------------------------------------------------
+// Workgroup (tile t, slice s): tile t is the 64 x 64 block (ti, tj), tj <= ti, of the lower triangle in row-major tile order; slice s
+// the rows [s * slice_rows, min(rows, (s + 1) * slice_rows)) of the chunk.  Four waves in a 2 x 2 arrangement, 32 x 32 results each:
+// two A and two B fragments per k-step of four rows feed four v_mfma_f64_16x16x4_f64.  Operand lane map (fr = lane & 15, fk = lane >>
+// 4): A holds A[fr][fk], B holds B[fk][fr], result register q holds C[fk + 4 q][fr]; here A[i][k] = V[k][i0 + i], B[k][j] =
+// V[k][j0 + j], so lanes 0-15 of either operand read 16 consecutive doubles of row k.  Rows past the slice's end load as 0.0 (no
+// access), so a slice or chunk may end anywhere, below four rows too.  Columns: i0 + 63 < mg <= ldv by the launcher's check.
+// part: (nslices x ntiles) tiles of 4096 doubles, tile-local row-major; every workgroup writes its whole tile.
+#define SG_UNROLL 4
+__global__ __launch_bounds__(256) void sparse_gram_kernel(const double *__restrict__ V, int64_t ldv, int64_t rows, int64_t slice_rows,
+                                                          int ntiles, double *__restrict__ part)
+{
+    const int t = blockIdx.x, s = blockIdx.y;
+    // (ti, tj) from the row-major index of the lower triangle: ti (ti + 1) / 2 <= t
+    int ti = (int)((sqrt(8.0 * (double)t + 1.0) - 1.0) * 0.5);
+    while ((ti + 1) * (ti + 2) / 2 <= t) ti++;
+    while (ti * (ti + 1) / 2 > t) ti--;
+    const int tj = t - ti * (ti + 1) / 2;
+    const int lane = threadIdx.x & 63, wave = threadIdx.x >> 6;
+    const int fr = lane & 15, fk = lane >> 4;
+    const int64_t i0 = (int64_t)ti * 64 + (wave >> 1) * 32, j0 = (int64_t)tj * 64 + (wave & 1) * 32;
+    const int64_t k0 = (int64_t)s * slice_rows;
+    const int64_t k1 = (k0 + slice_rows < rows) ? k0 + slice_rows : rows;
+    f64x4 acc[2][2];
+#pragma unroll
+    for (int a = 0; a < 2; a++)
+#pragma unroll
+        for (int b = 0; b < 2; b++) acc[a][b] = f64x4{0.0, 0.0, 0.0, 0.0};
+    for (int64_t k = k0; k < k1; k += 4 * SG_UNROLL) {
+        double av[SG_UNROLL][2], bv[SG_UNROLL][2];
+#pragma unroll
+        for (int u = 0; u < SG_UNROLL; u++) {
+            const int64_t kr = k + 4 * u + fk;
+            const bool live = kr < k1;
+            const double *row = V + kr * ldv;
+            av[u][0] = live ? row[i0 + fr] : 0.0;
+            av[u][1] = live ? row[i0 + 16 + fr] : 0.0;
+            bv[u][0] = live ? row[j0 + fr] : 0.0;
+            bv[u][1] = live ? row[j0 + 16 + fr] : 0.0;
+        }
+#pragma unroll
+        for (int u = 0; u < SG_UNROLL; u++)
+#pragma unroll
+            for (int a = 0; a < 2; a++)
+#pragma unroll
+                for (int b = 0; b < 2; b++)
+                    acc[a][b] = __builtin_amdgcn_mfma_f64_16x16x4f64(av[u][a], bv[u][b], acc[a][b], 0, 0, 0);
+    }
+    double *out = part + ((int64_t)s * ntiles + t) * 4096;
+    const int li = (wave >> 1) * 32, lj = (wave & 1) * 32;
+#pragma unroll
+    for (int a = 0; a < 2; a++)
+#pragma unroll
+        for (int b = 0; b < 2; b++)
+#pragma unroll
+            for (int q = 0; q < 4; q++) out[(li + a * 16 + fk + 4 * q) * 64 + lj + b * 16 + fr] = acc[a][b][q];
+}
+
+// G tile (ti, tj) += part[0][t] + part[1][t] + ... in slice order; one thread per element
+__global__ __launch_bounds__(256) void sparse_gram_reduce_kernel(const double *__restrict__ part, int ntiles, int nslices,
+                                                                 double *__restrict__ G, int64_t ldg)
+{
+    const int t = blockIdx.x;
+    int ti = (int)((sqrt(8.0 * (double)t + 1.0) - 1.0) * 0.5);
+    while ((ti + 1) * (ti + 2) / 2 <= t) ti++;
+    while (ti * (ti + 1) / 2 > t) ti--;
+    const int tj = t - ti * (ti + 1) / 2;
+    const int e = blockIdx.y * 256 + threadIdx.x;          // element of the tile, row-major
+    const int64_t gi = (int64_t)ti * 64 + (e >> 6), gj = (int64_t)tj * 64 + (e & 63);
+    double v = G[gi * ldg + gj];
+    for (int s = 0; s < nslices; s++) v += part[((int64_t)s * ntiles + t) * 4096 + e];
+    G[gi * ldg + gj] = v;
+}
+
+// G (mg x mg, mg a multiple of 64, row stride ldg; lower tiles) += V^T V over the `rows` rows of V (row stride ldv >= mg).
+// nslices workgroups share a tile (chosen by the caller: api_sparse.inc sparse_slices); part holds nslices * ntiles * 4096 doubles.
+int launch_sparse_gram(hipStream_t st, const double *V, int64_t ldv, int64_t rows, int64_t mg, int nslices, double *part, double *G,
+                       int64_t ldg)
+{
+    if (rows <= 0) return GPT_OK;
+    if (mg <= 0 || mg % 64 || mg > ldv || mg > ldg || nslices < 1 || nslices > 65535 || mg / 64 > 2000) {
+        gpt_set_error("sparse_gram: order %lld (a multiple of 64, at most the row strides %lld / %lld), %d slices", (long long)mg,
+                      (long long)ldv, (long long)ldg, nslices);
+        return GPT_E_ARG;
+    }
+    const int nt = (int)(mg / 64), ntiles = nt * (nt + 1) / 2;
+    // whole k-steps of four rows per slice; no slice is empty
+    int64_t slice_rows = ((rows + nslices - 1) / nslices + 3) / 4 * 4;
+    const int ns = (int)((rows + slice_rows - 1) / slice_rows);
+    hipLaunchKernelGGL(sparse_gram_kernel, dim3((unsigned)ntiles, (unsigned)ns), dim3(256), 0, st, V, ldv, rows, slice_rows, ntiles, part);
+    GPT_LAUNCH_CHECK();
+    hipLaunchKernelGGL(sparse_gram_reduce_kernel, dim3((unsigned)ntiles, 16), dim3(256), 0, st, part, ntiles, ns, G, ldg);
+    GPT_LAUNCH_CHECK();
+    return GPT_OK;
+}
+
+// ---- B = I + G with the augmented row ------------------------------------------------------------------------------------------------
+// B (bp x bp, row stride bp; bp a multiple of 128, > M): rows / columns < M: I + G (lower; the upper triangle is zeroed); row M: b^T =
+// G[M][0..M) with `big` on the diagonal (the pivot stays positive whatever c.c is: solve.hip fill_pad_kernel); rows > M: unit diagonal.
+__global__ void sparse_assemble_b_kernel(const double *__restrict__ G, int64_t ldg, int64_t M, double *__restrict__ B, int64_t bp,
+                                         double big)
+{
+    const int64_t j = (int64_t)blockIdx.x * blockDim.x + threadIdx.x, i = blockIdx.y;
+    if (j >= bp) return;
+    double v = 0.0;
+    if (i < M) {
+        if (j <= i) v = G[i * ldg + j] + (i == j ? 1.0 : 0.0);
+    } else if (i == M) {
+        v = (j < M) ? G[i * ldg + j] : (j == M ? big : 0.0);
+    } else if (i == j) {
+        v = 1.0;
+    }
+    B[i * bp + j] = v;
+}
+
+int launch_sparse_assemble_b(hipStream_t st, const double *G, int64_t ldg, int64_t M, double *B, int64_t bp, double big)
+{
+    if (M < 1 || bp <= M || ldg <= M || bp > 65535) {
+        gpt_set_error("sparse_assemble_b: M = %lld, padded order %lld", (long long)M, (long long)bp);
+        return GPT_E_ARG;
+    }
+    hipLaunchKernelGGL(sparse_assemble_b_kernel, dim3((unsigned)((bp + 255) / 256), (unsigned)bp), dim3(256), 0, st, G, ldg, M, B, bp, big);
+    GPT_LAUNCH_CHECK();
+    return GPT_OK;
+}
+
+// ---- predictive variance ---------------------------------------------------------------------------------------------------------------
+// var[i] = kdiag[i] - sum_{j < M} V[i][j]^2 + sum_{j < M} W[i][j]^2: one workgroup per test row, a fixed order
+__global__ __launch_bounds__(256) void sparse_var_kernel(const double *__restrict__ V, const double *__restrict__ W, int64_t ld,
+                                                         int64_t rows, int64_t M, const double *__restrict__ kdiag,
+                                                         double *__restrict__ var)
+{
+    __shared__ double pv[4], pw[4];
+    const int64_t i = blockIdx.x;
+    if (i >= rows) return;
+    const double *v = V + i * ld, *w = W + i * ld;
+    double a = 0.0, b = 0.0;
+    for (int64_t c = threadIdx.x; c < M; c += 256) {
+        a = fma(v[c], v[c], a);
+        b = fma(w[c], w[c], b);
+    }
+    for (int off = 32; off > 0; off >>= 1) {
+        a += __shfl_down(a, off);
+        b += __shfl_down(b, off);
+    }
+    if ((threadIdx.x & 63) == 0) {
+        pv[threadIdx.x >> 6] = a;
+        pw[threadIdx.x >> 6] = b;
+    }
+    __syncthreads();
+    if (threadIdx.x == 0)
+        var[i] = (kdiag[i] - ((pv[0] + pv[1]) + (pv[2] + pv[3]))) + ((pw[0] + pw[1]) + (pw[2] + pw[3]));
+}
+
+int launch_sparse_var(hipStream_t st, const double *V, const double *W, int64_t ld, int64_t rows, int64_t M, const double *kdiag,
+                      double *var)
+{
+    if (rows <= 0) return GPT_OK;
+    hipLaunchKernelGGL(sparse_var_kernel, dim3((unsigned)rows), dim3(256), 0, st, V, W, ld, rows, M, kdiag, var);
+    GPT_LAUNCH_CHECK();
+    return GPT_OK;
+}

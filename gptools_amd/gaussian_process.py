@@ -1083,6 +1083,11 @@ class GaussianProcess(object):
             self._assign_free(keep)
             self.partitioned = keep_partitioned
 
+    def _ll_rows(self, param_list):
+        """The log-posterior at every row of ``param_list`` for the callers that walk many points (``compute_ll_matrix``, the
+        host-stepped sampler): :meth:`ll_batch`; a subclass without a batched evaluator answers row by row."""
+        return self.ll_batch(param_list)
+
     def _batch_job(self, row, extra):
         """The current hyperparameters as one element of a batched fit; ``None`` for a kernel whose device parameters need a solve
         that failed (the evaluation fails: the caller drops the row)."""
@@ -1274,7 +1279,7 @@ class GaussianProcess(object):
         axes = [np.linspace(lo, hi, c) for (lo, hi), c in zip(box[:nfree], counts)]
         mesh = np.meshgrid(*axes, indexing="ij")
         points = np.column_stack([m.ravel() for m in mesh])
-        ll_vals = self.ll_batch(list(points)).reshape([int(c) for c in counts[:nfree]])
+        ll_vals = self._ll_rows(list(points)).reshape([int(c) for c in counts[:nfree]])
         self.update_hyperparameters(here)
         return (ll_vals, axes)
 
@@ -1372,7 +1377,7 @@ class GaussianProcess(object):
         ndim = len(self.free_params)
 
         def lnprob(P):
-            return self.ll_batch(list(np.atleast_2d(P)))
+            return self._ll_rows(list(np.atleast_2d(P)))
         if sampler is None:
             sampler = EnsembleSampler(nwalkers, ndim, lnprob, a=sampler_a, random_state=random_state)
         else:
@@ -1625,7 +1630,7 @@ class GaussianProcess(object):
             want = 2 if need_cov else (1 if need_std else 0)
             mean, std, covariance = self._ctx.predict(Xstar, n, want, *self._prediction_noise(noise))
         else:
-            mean, std, covariance = self._predict_general(Xstar, n, noise, need_std)
+            mean, std, covariance = self._predict_general(Xstar, n, noise, need_std, need_cov)
         mean_func = None
         if self.mu is not None:
             mean_func = self.mu(Xstar, n)
@@ -2038,9 +2043,10 @@ class GaussianProcess(object):
             Q[:, _SIGN_FEATURES[feature](ends, where) < 0.0] *= -1.0
         return Q * np.sqrt(lam)[None, :]
 
-    def _predict_general(self, Xstar, n, noise, need_std):
+    def _predict_general(self, Xstar, n, noise, need_std, need_cov=True):
         """predict for fits that went through ``gpt_fit_matrix`` (``T`` present or a Python kernel):
-        covariance blocks from ``compute_Kij``, triangular solves on the GPU."""
+        covariance blocks from ``compute_Kij``, triangular solves on the GPU (the covariance comes with the std whether or not
+        ``need_cov`` asks for it)."""
         Kstar = self.compute_Kij(self.X, Xstar, self.n, n)
         if noise:
             Kstar = Kstar + self.compute_Kij(self.X, Xstar, self.n, n, noise=True)

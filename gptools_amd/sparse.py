@@ -1,0 +1,199 @@
+"""SparseGaussianProcess: inducing-point approximations (FITC, VFE, DTC) of the GP on the GPU.
+
+The same kernel, hyperparameters, priors and ``predict`` as :class:`GaussianProcess`, with ``M`` inducing inputs ``Z`` in place of
+the ``N x N`` covariance: ``O(N M^2)`` time and ``O(M^2 + chunk M)`` device memory (``gpt_sparse_fit`` / ``gpt_sparse_predict``,
+include/gpt_hip.h).  With ``s_i = sigma_noise^2 + err_y_i^2`` and ``jitter`` on the diagonal of ``K_uu``::
+
+    L_u = chol(k(Z,Z) + jitter I)      V = L_u^-1 k(Z,X)      q_i = sum_m V_mi^2      k_i = k(x_i,x_i)
+    Lambda_i = k_i - q_i + s_i (fitc)  Lambda_i = s_i (vfe, dtc)
+    B = I + V Lambda^-1 V^T            L_B = chol(B)          c = L_B^-1 V Lambda^-1 r         r = y - mu(X)
+    ll = -1/2 [sum log Lambda_i + 2 sum log (L_B)_mm + r^T Lambda^-1 r - c.c + N log 2 pi]  - 1/2 sum (k_i - q_i)/s_i (vfe only)
+
+What the dense class offers beyond value, optimisation over the value and prediction is refused here, never routed to the dense
+path: see the class docstring.
+"""
+import numpy as np
+
+from . import _lib, _ingest
+from .error_handling import GPArgumentError
+from .gaussian_process import GaussianProcess
+from .kernel import ZeroKernel, DiagonalNoiseKernel
+
+__all__ = ["SparseGaussianProcess"]
+
+
+class SparseGaussianProcess(GaussianProcess):
+    """Gaussian process regression through ``M`` fixed inducing inputs.
+
+    ``k``, ``noise_k``, ``X``, ``y``, ``err_y``, ``n``, ``mu``, ``diag_factor``, ``verbose``, ``device`` as
+    :class:`GaussianProcess`.  ``Z`` (M, D): the inducing inputs, ``n_Z`` their derivative orders (scalar or (M, D)); they are
+    fixed -- not hyperparameters -- and :meth:`set_inducing` replaces them.  ``method``: ``"fitc"``, ``"vfe"`` or ``"dtc"``.
+    ``jitter``: added to the diagonal of ``k(Z, Z)`` (absolute).  ``chunk_rows``: training rows per pass over the data, a
+    multiple of 64 (``None``: chosen by the library from a byte budget).
+
+    Supported: ``update_hyperparameters`` (value only), ``compute_K_L_alpha_ll`` (sets ``ll`` and ``ll_parts``),
+    ``optimize_hyperparameters`` (scipy on the value; ``random_starts`` one after another), ``compute_ll_matrix`` and the
+    host-stepped sampler (one evaluation per vector), ``predict`` and ``draw_sample`` (through the returned covariance).
+
+    Refused (``NotImplementedError`` / ``ValueError``): a covariance kernel the library does not evaluate itself, warped
+    kernels, a noise kernel that is not a ``DiagonalNoiseKernel``; ``T``, ``use_hyper_deriv``, ``partitioned``;
+    ``ll_gradient*``, ``loo_*``, ``objective="loo"``, ``gradient="device"``, ``batch_starts``, ``ll_batch``; the
+    library-stepped sampler, ``use_MCMC`` predictions; ``L`` and ``alpha`` (there is no ``N x N`` factor)."""
+
+    def __init__(self, k, Z, noise_k=None, n_Z=0, method="fitc", jitter=1e-6, chunk_rows=None, X=None, y=None, err_y=0, n=0,
+                 mu=None, diag_factor=1e2, verbose=False, device=0, T=None, use_hyper_deriv=False):
+        if T is not None:
+            raise NotImplementedError("SparseGaussianProcess does not take a linear transform T")
+        if use_hyper_deriv:
+            raise NotImplementedError("SparseGaussianProcess has no hyperparameter derivatives (use_hyper_deriv)")
+        if method not in _lib.SPARSE_METHODS:
+            raise ValueError("method must be one of %s, got %r" % (sorted(_lib.SPARSE_METHODS), method))
+        jitter = float(jitter)
+        if not jitter >= 0.0:
+            raise ValueError("jitter must be non-negative, got %r" % (jitter,))
+        if chunk_rows is not None and (int(chunk_rows) != chunk_rows or chunk_rows <= 0 or chunk_rows % 64):
+            raise ValueError("chunk_rows must be None or a positive multiple of 64, got %r" % (chunk_rows,))
+        self.method = method
+        self.jitter = jitter
+        self.chunk_rows = None if chunk_rows is None else int(chunk_rows)
+        self.ll_parts = None
+        super(SparseGaussianProcess, self).__init__(k, noise_k=noise_k, mu=mu, diag_factor=diag_factor, verbose=verbose,
+                                                    device=device)
+        self.set_inducing(Z, n_Z)
+        self._sparse_refusal()
+        if X is not None:
+            if y is None:
+                raise GPArgumentError("Must pass both X and y when constructing SparseGaussianProcess!")
+            self.add_data(X, y, err_y=err_y, n=n)
+        elif y is not None:
+            raise GPArgumentError("Must pass both X and y when constructing SparseGaussianProcess!")
+
+    # ---- inducing inputs, data -------------------------------------------------------------------
+    def set_inducing(self, Z, n_Z=0):
+        """Replace the inducing inputs ``Z`` (M, D) and their derivative orders ``n_Z`` (scalar or (M, D))."""
+        Z = _ingest.points(Z, self.num_dim, "Z")
+        if Z.shape[0] < 1 or not np.all(np.isfinite(Z)):
+            raise ValueError("Z must hold at least one point and finite entries only")
+        self.Z = Z
+        self.n_Z = _ingest.derivative_orders(n_Z, Z, self.num_dim, "n_Z", column_rule="row")
+        self.K_up_to_date = False
+        self._data_on_device = False
+
+    def add_data(self, X, y, err_y=0, n=0, T=None):
+        if T is not None:
+            raise NotImplementedError("SparseGaussianProcess does not take a linear transform T")
+        super(SparseGaussianProcess, self).add_data(X, y, err_y=err_y, n=n)
+
+    def _upload_data(self, ctx):
+        ctx.set_data(self.X, self.n)
+        ctx.sparse_set_inducing(self.Z, self.n_Z)
+
+    # ---- what this class does not do ---------------------------------------------------------------
+    def _sparse_refusal(self):
+        """Raise for a configuration the sparse path does not take; returns the device model's terms otherwise."""
+        if self.T is not None:
+            raise NotImplementedError("SparseGaussianProcess does not take a linear transform T")
+        if self.use_hyper_deriv:
+            raise NotImplementedError("SparseGaussianProcess has no hyperparameter derivatives (use_hyper_deriv)")
+        if self.partitioned:
+            raise NotImplementedError("SparseGaussianProcess has no partitioned evaluation (partitioned)")
+        if not isinstance(self.noise_k, (ZeroKernel, DiagonalNoiseKernel)):
+            raise NotImplementedError("SparseGaussianProcess takes a ZeroKernel or DiagonalNoiseKernel as noise_k, not %s"
+                                      % type(self.noise_k).__name__)
+        model = self._device_model()
+        if model is None:
+            raise NotImplementedError("the covariance kernel is not one the library evaluates itself (a Python-defined kernel, or "
+                                      "a tree of kernels it does not take): SparseGaussianProcess has no host route")
+        terms, layers = model
+        if layers:
+            raise NotImplementedError("SparseGaussianProcess does not take warped kernels (WarpedKernel)")
+        return terms
+
+    def _refuse(what):
+        def method(self, *args, **kwargs):
+            raise NotImplementedError("SparseGaussianProcess has no %s" % what)
+        method.__doc__ = "Refused: the sparse path has no %s." % what
+        return method
+
+    ll_gradient = _refuse("gradient of the sparse objective (ll_gradient)")
+    ll_gradient_batch = _refuse("gradient of the sparse objective (ll_gradient_batch)")
+    loo_predict = _refuse("leave-one-out cross-validation (loo_predict)")
+    loo_log_likelihood = _refuse("leave-one-out cross-validation (loo_log_likelihood)")
+    loo_gradient = _refuse("leave-one-out cross-validation (loo_gradient)")
+    ll_batch = _refuse("batched evaluator (ll_batch): evaluate one vector at a time with update_hyperparameters")
+    predict_MCMC = _refuse("predictions marginalised over hyperparameter samples (predict_MCMC)")
+    compute_from_MCMC = _refuse("predictions marginalised over hyperparameter samples (compute_from_MCMC)")
+    L = property(_refuse("N x N Cholesky factor (L)"))
+    alpha = property(_refuse("N-vector alpha: the predictive mean is a dot product with the M-vector c"))
+    del _refuse
+
+    def _library_stepping(self):
+        return "SparseGaussianProcess has no batched evaluator for the library to step", None
+
+    # ---- the fit -------------------------------------------------------------------------------------
+    def compute_K_L_alpha_ll(self, need_factor=True):
+        """Evaluate the sparse objective on the GPU and set ``ll`` (log-posterior: objective + log hyperprior) and
+        ``ll_parts`` (the five sums ``gpt_sparse_fit`` returns); no-op while ``K_up_to_date``.  Raises
+        ``numpy.linalg.LinAlgError`` if ``K_uu + jitter I`` or ``B`` is not positive definite."""
+        if self.K_up_to_date:
+            return
+        if self.X is None:
+            raise GPArgumentError("No data have been added to the SparseGaussianProcess!")
+        terms = self._sparse_refusal()
+        self._cache = {}
+        ctx = self._resident_ctx()
+        ctx.set_warp(None)
+        ll_data, parts = ctx.sparse_fit(_lib.SPARSE_METHODS[self.method], terms, self._noise_var(), self._y_alph(), self.err_y,
+                                        self.jitter, self.chunk_rows or 0)
+        self._fit_mode = "sparse"
+        self.ll_parts = parts
+        self.ll = ll_data + self.hyperprior(self.params)
+        self.K_up_to_date = True
+
+    def update_hyperparameters(self, new_params, hyper_deriv_handling="default", exit_on_bounds=True, inf_on_error=True):
+        """``-(ll + log prior)`` at the free hyperparameters ``new_params``; ``+inf`` where the prior excludes them or a matrix
+        is not positive definite (``inf_on_error``), as in the base class.  Value only."""
+        if hyper_deriv_handling not in ("default", "value"):
+            raise NotImplementedError("SparseGaussianProcess has no hyperparameter derivatives (hyper_deriv_handling=%r)"
+                                      % (hyper_deriv_handling,))
+        self._sparse_refusal()
+        return super(SparseGaussianProcess, self).update_hyperparameters(new_params, hyper_deriv_handling="value",
+                                                                         exit_on_bounds=exit_on_bounds,
+                                                                         inf_on_error=inf_on_error)
+
+    def _ll_rows(self, param_list):
+        keep = np.array(self.free_params[:], dtype=float)
+        try:
+            return np.array([-1.0 * self.update_hyperparameters(np.asarray(p, dtype=float)) for p in param_list])
+        finally:
+            self._assign_free(keep)
+
+    def optimize_hyperparameters(self, method="SLSQP", opt_kwargs={}, verbose=False, random_starts=None, num_proc=None,
+                                 max_tries=1, batch_fd=None, gradient=None, batch_starts=False, objective="ll"):
+        """``scipy.optimize.minimize`` on the value of the sparse objective (scipy differences it itself), the starts one after
+        another; arguments and return value as the base class.  ``gradient="device"``, ``batch_starts`` and
+        ``objective="loo"`` are refused."""
+        if gradient is not None:
+            raise NotImplementedError("SparseGaussianProcess has no gradient of the sparse objective (gradient=%r)" % (gradient,))
+        if batch_starts:
+            raise NotImplementedError("SparseGaussianProcess has no batched evaluator (batch_starts)")
+        if objective != "ll":
+            raise NotImplementedError("SparseGaussianProcess has no leave-one-out objective (objective=%r)" % (objective,))
+        self._sparse_refusal()
+        return super(SparseGaussianProcess, self).optimize_hyperparameters(
+            method=method, opt_kwargs=opt_kwargs, verbose=verbose, random_starts=random_starts, num_proc=num_proc,
+            max_tries=max_tries, batch_fd=False)
+
+    # ---- prediction ------------------------------------------------------------------------------------
+    def predict(self, Xstar, n=0, noise=False, return_std=True, return_cov=False, full_output=False, use_MCMC=False, **kwargs):
+        """Predictive mean (and std / covariance) of the sparse fit at ``Xstar``; arguments and return values as
+        :meth:`GaussianProcess.predict`.  For ``"fitc"`` the covariance is the standard FITC predictive.  ``use_MCMC`` is
+        refused."""
+        if use_MCMC:
+            raise NotImplementedError("SparseGaussianProcess has no predictions marginalised over hyperparameter samples (use_MCMC)")
+        return super(SparseGaussianProcess, self).predict(Xstar, n=n, noise=noise, return_std=return_std, return_cov=return_cov,
+                                                          full_output=full_output, **kwargs)
+
+    def _predict_general(self, Xstar, n, noise, need_std, need_cov=True):
+        want = 2 if need_cov else (1 if need_std else 0)
+        return self._ctx.sparse_predict(Xstar, n, want, *self._prediction_noise(noise))

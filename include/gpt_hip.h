@@ -672,6 +672,52 @@ int gpt_dev_pad_block(gpt_ctx *ctx, double *dA, int64_t lda, int64_t c0, int64_t
                       const double *d_y, double big);
 int gpt_dev_panel_scalars(gpt_ctx *ctx, const double *dP, int64_t ldp, int64_t w, int64_t zrow, double *d_acc);
 
+/* ---- inducing-point approximations: FITC, VFE, DTC -------------------------------------------------
+ * M inducing inputs Z (M, D) with derivative orders nZ (M, D; NULL: all zero) stand in for the N resident training points:
+ * O(N M^2) time, O(M^2 + chunk M) memory.  With s_i = noise_var + err_y_i^2 and the jitter on the diagonal of K_uu:
+ *   L_u = chol(k(Z, Z) + jitter I),  V = L_u^-1 k(Z, X),  q_i = sum_m V_mi^2,  k_i = k(x_i, x_i)
+ *   Lambda_i = k_i - q_i + s_i (fitc),  Lambda_i = s_i (vfe, dtc)
+ *   B = I + V Lambda^-1 V^T,  L_B = chol(B),  c = L_B^-1 V Lambda^-1 y
+ *   ll = -1/2 [sum log Lambda_i + 2 sum log (L_B)_mm + y^T Lambda^-1 y - c.c + N log 2 pi]  - 1/2 sum (k_i - q_i) / s_i (vfe only)
+ *   predict at x*:  v = L_u^-1 k(Z, x*),  w = L_B^-1 v,  mean = w.c,  cov = k(x*, x*') - v.v' + w.w'
+ * The sparse state lives beside the dense factor of the same context; neither touches the other.  gpt_set_data and
+ * gpt_sparse_set_inducing drop it.  With a linear transform (gpt_set_T) or warp layers (gpt_set_warp) set the calls answer
+ * GPT_E_NOTIMPL; without data or inducing points (gpt_sparse_predict / gpt_sparse_get_c: without a sparse fit that succeeded)
+ * GPT_E_STATE. */
+#define GPT_SPARSE_FITC 0
+#define GPT_SPARSE_VFE 1
+#define GPT_SPARSE_DTC 2
+
+/* Uploads the inducing inputs (after gpt_set_data; Z has the data's D columns) and drops any sparse fit. */
+int gpt_sparse_set_inducing(gpt_ctx *ctx, const double *Z, const int32_t *nZ, int64_t M);
+
+/* One evaluation.  The model as gpt_fit_terms takes it (same description, same order checks, applied to the training AND the
+ * inducing orders); y: the targets with the mean function subtracted.  chunk_rows: training rows per pass, a multiple of 64; 0
+ * picks what keeps the two chunk x (M padded) buffers within a fixed budget (512 MiB).  The chunks run in ascending order and every
+ * sum has a fixed order: the same call gives the same bits.
+ * parts_out (5 doubles, may be NULL): sum log Lambda_i, sum log (L_B)_mm, y^T Lambda^-1 y, c.c, sum (k_i - q_i) / s_i (0 unless vfe).
+ * Status > 0: that leading minor of K_uu + jitter I or of B is not positive definite (gpt_last_error says which);
+ * GPT_E_VALUE: a Lambda_i is not a positive finite number.  With the option "timing" set, gpt_last_timings afterwards returns
+ * the milliseconds of [0] the K_fu builds, [1] the right-side solves, [2] the row passes, [3] the Grams, [4] both factorisations.
+ * After a success L_u, L_B and c stay resident (nothing of size N does). */
+int gpt_sparse_fit(gpt_ctx *ctx, int method, int nterms, const int *kernel_ids, const int *kernel_ids2, const double *params,
+                   const int *nparams, const int *nparams1, double noise_var, const double *y, const double *err_y, double jitter,
+                   int64_t chunk_rows, double *ll_out, double *parts_out);
+
+/* Predictions of the resident sparse fit; arguments and `want` as gpt_predict (cov_out is required for want == 2).  The test
+ * points go through in chunks; want == 2 holds all Ms rows at once. */
+int gpt_sparse_predict(gpt_ctx *ctx, const double *Xstar, const int32_t *nstar, int64_t Ms, int want, const double *noise_params,
+                       const int32_t *noise_n, double *mean_out, double *std_out, double *cov_out);
+
+/* c (M doubles) of the resident sparse fit: what the predictive mean is a dot product with. */
+int gpt_sparse_get_c(gpt_ctx *ctx, double *c_out);
+
+/* Device API: the tall-skinny Gram of the sparse fit on raw device pointers, on the context's stream.
+ *   dG (mg x mg, row stride ldg; the 64 x 64 tiles on and below the diagonal) += dV^T dV,  dV (rows x mg, row stride ldv >= mg),
+ * mg a multiple of 64, any rows >= 1.  The rows are split into nslices slices (0: chosen so that tiles x slices is about six times
+ * the number of compute units), one workgroup per (tile, slice); the partial tiles are added in slice order (no atomics). */
+int gpt_dev_sparse_gram(gpt_ctx *ctx, const double *dV, int64_t ldv, int64_t rows, int64_t mg, int nslices, double *dG, int64_t ldg);
+
 /* ---- compiled schedules of the partitioned engines (round 6) ------------------------------------------------------------
  * The one-process-per-GPU block-cyclic Cholesky of gptools_amd/dist.py issues ~1000 operations per rank and evaluation; which
  * ones, on which buffers, in which order is static per (N, nb, world, rank).  The Python layer records its step loop once as an
