@@ -126,6 +126,10 @@ SIGNATURES = {
     "gpt_sparse_predict": (C.c_int, [_vp, _dp, _ip, _i64, C.c_int, _dp, _ip, _dp, _dp, _dp]),
     "gpt_sparse_get_c": (C.c_int, [_vp, _dp]),
     "gpt_dev_sparse_gram": (C.c_int, [_vp, _vp, _i64, _i64, _i64, C.c_int, _vp, _i64]),
+    "gpt_dev_sparse_lambda": (C.c_int, [_vp, _vp, _i64, _i64, _i64, C.c_int, _vp, _vp, _vp, C.c_double, _vp, _i64, _ip]),
+    "gpt_dev_sparse_rowsum": (C.c_int, [_vp, _vp, _i64, _i64, _vp]),
+    "gpt_dev_sparse_var": (C.c_int, [_vp, _vp, _vp, _i64, _i64, _i64, _vp, _vp]),
+    "gpt_dev_sparse_assemble_b": (C.c_int, [_vp, _vp, _i64, _i64, _vp, _i64, C.c_double]),
 }
 
 _lib = None

@@ -175,6 +175,7 @@ struct gpt_ctx {
     int64_t sp_M = 0;                  // inducing points resident (0: none)
     long sp_zmaxsum = 0, sp_zcolmax[GPT_MAX_DIM] = {};      // their largest order row sum / order per coordinate
     bool sp_fitted = false;
+    int64_t sp_chunk_rows = 0;         // the chunk_rows argument of the resident sparse fit: its predictions run in the same chunks
     ModelKernel sp_model;              // the model kernel of the resident sparse fit
     int sp_ncu = 0;                    // compute units of the device (the Gram kernel's slice count), read on first use
     std::vector<hipEvent_t> sp_events; // phase marks of a timed gpt_sparse_fit (option "timing")

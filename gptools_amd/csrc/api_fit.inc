@@ -44,6 +44,7 @@ extern "C" int gpt_set_data(gpt_ctx *c, const double *X, const int32_t *n, int64
     c->batch_gen++;                     // (the resident batch was fitted to the old data)
     c->sp_M = 0;                        // (the inducing points and the sparse fit belong to one data set: gpt_sparse_set_inducing)
     c->sp_fitted = false;
+    c->sp_chunk_rows = 0;
     if (c->dT) hipFree(c->dT);          // a transform belongs to one data set
     c->dT = nullptr;
     c->Ny = 0;

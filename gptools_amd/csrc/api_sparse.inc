@@ -1,6 +1,6 @@
 // api_sparse.inc -- part of api.hip (ONE translation unit: included from there, in this order; the parts share struct gpt_ctx and
 // static helpers).  Inducing-point approximations (FITC / VFE / DTC; DESIGN.md section 18): gpt_sparse_set_inducing, gpt_sparse_fit,
-// gpt_sparse_predict, gpt_sparse_get_c, gpt_dev_sparse_gram.
+// gpt_sparse_predict, gpt_sparse_get_c, gpt_dev_sparse_gram / _lambda / _rowsum / _var / _assemble_b.
 // ------------------------------------------------------------------------------------------------
 // Layout.  M inducing points.  MPU = M rounded up to 128 is the order of the factored K_uu + jitter I (unit diagonal on the padding
 // rows, so the padding columns of V^T = K_fu L_u^-T stay zero).  BP = (M + 1) rounded up to 128 is the order of the AUGMENTED B: rows
@@ -87,6 +87,7 @@ extern "C" int gpt_sparse_set_inducing(gpt_ctx *c, const double *Z, const int32_
 {
     CTX_ENTER(c);
     c->sp_fitted = false;
+    c->sp_chunk_rows = 0;
     c->sp_M = 0;
     if (!c->dX) {
         gpt_set_error("gpt_sparse_set_inducing: call gpt_set_data first");
@@ -163,6 +164,7 @@ extern "C" int gpt_sparse_fit(gpt_ctx *c, int method, int nterms, const int *ker
         return GPT_E_ARG;
     }
     c->sp_fitted = false;
+    c->sp_chunk_rows = 0;
     const int D = c->D;
     const int64_t N = c->Nx;
     long maxsum, colmax[GPT_MAX_DIM];
@@ -300,6 +302,7 @@ extern "C" int gpt_sparse_fit(gpt_ctx *c, int method, int nterms, const int *ker
         parts_out[4] = trace;
     }
     c->sp_model = model;
+    c->sp_chunk_rows = chunk_rows;
     c->sp_fitted = true;
     return GPT_OK;
 }
@@ -316,8 +319,10 @@ extern "C" int gpt_sparse_get_c(gpt_ctx *c, double *c_out)
     return GPT_OK;
 }
 
-// v = L_u^-1 k(Z, x*), w = L_B^-1 v, mean = w.c, cov = k(x*, x*') - v.v' + w.w'.  want <= 1: the test points go through in chunks of
-// the fit's size rule; want == 2 needs every pair of rows, so V and W hold all Ms rows (the result is Ms x Ms anyway).
+// v = L_u^-1 k(Z, x*), w = L_B^-1 v, mean = w.c, cov = k(x*, x*') - v.v' + w.w'.  want <= 1: the test points go through in the chunks
+// of the resident fit -- its chunk_rows argument (sp_chunk_rows), 0: the size rule -- so a caller who bounded the fit's memory by
+// chunk_rows bounds the prediction's too (two chunk x LDV buffers, V and W, where the fit holds one); want == 2 needs every pair of
+// rows, so V and W hold all Ms rows whatever chunk_rows was (the result is Ms x Ms anyway).
 extern "C" int gpt_sparse_predict(gpt_ctx *c, const double *Xstar, const int32_t *nstar, int64_t Ms, int want,
                                   const double *noise_params, const int32_t *noise_n, double *mean_out, double *std_out,
                                   double *cov_out)
@@ -337,7 +342,7 @@ extern "C" int gpt_sparse_predict(gpt_ctx *c, const double *Xstar, const int32_t
     const SparseDims sd = sparse_dims(c->sp_M);
     const int64_t M = sd.M, MPU = sd.MPU, BP = sd.BP, LDV = sd.LDV;
     int64_t chunk;
-    GPT_TRY(sparse_chunk(sd, 0, Ms, &chunk));
+    GPT_TRY(sparse_chunk(sd, c->sp_chunk_rows, Ms, &chunk));
     if (want == 2) chunk = round_up(Ms, 64);
     hipStream_t st = c->stream;
     const double *dLu = (const double *)c->slots[SLOT_SP_LU].p, *dLb = (const double *)c->slots[SLOT_SP_LB].p;
@@ -428,4 +433,51 @@ extern "C" int gpt_dev_sparse_gram(gpt_ctx *c, const double *dV, int64_t ldv, in
     double *dPart;
     GPT_TRY(ensure(c, SLOT_SP_PART, (size_t)nslices * ntiles * 4096 * sizeof(double), (void **)&dPart));
     return launch_sparse_gram(c->stream, dV, ldv, rows, mg, nslices, dPart, dG, ldg);
+}
+
+// The four other kernels of ksparse.hip on raw device pointers (device API, on the context's stream): one launcher each, nothing
+// added but the refusal of null pointers and of orders the launcher would read or write past (tests/test_gpu_sparse.py checks each
+// kernel alone through these).
+extern "C" int gpt_dev_sparse_lambda(gpt_ctx *c, double *dV, int64_t ldv, int64_t rows, int64_t M, int method, const double *d_kdiag,
+                                     const double *d_r, const double *d_err, double noise_var, double *d_rowval, int64_t ldr,
+                                     int32_t *d_bad)
+{
+    CTX_ENTER(c);
+    if (!dV || !d_kdiag || !d_r || !d_err || !d_rowval || !d_bad || rows <= 0 || M < 1 || method < GPT_SPARSE_FITC ||
+        method > GPT_SPARSE_DTC) {
+        gpt_set_error("gpt_dev_sparse_lambda: bad arguments (rows=%lld, M=%lld, method %d)", (long long)rows, (long long)M, method);
+        return GPT_E_ARG;
+    }
+    return launch_sparse_lambda(c->stream, dV, ldv, rows, M, method, d_kdiag, d_r, d_err, noise_var, d_rowval, ldr, d_bad);
+}
+
+extern "C" int gpt_dev_sparse_rowsum(gpt_ctx *c, const double *d_rowval, int64_t ldr, int64_t rows, double *d_acc)
+{
+    CTX_ENTER(c);
+    if (!d_rowval || !d_acc || rows <= 0 || rows > ldr) {
+        gpt_set_error("gpt_dev_sparse_rowsum: bad arguments (rows=%lld, row stride %lld)", (long long)rows, (long long)ldr);
+        return GPT_E_ARG;
+    }
+    return launch_sparse_rowsum(c->stream, d_rowval, ldr, rows, d_acc);
+}
+
+extern "C" int gpt_dev_sparse_var(gpt_ctx *c, const double *dV, const double *dW, int64_t ld, int64_t rows, int64_t M,
+                                  const double *d_kdiag, double *d_var)
+{
+    CTX_ENTER(c);
+    if (!dV || !dW || !d_kdiag || !d_var || rows <= 0 || M < 1 || M > ld) {
+        gpt_set_error("gpt_dev_sparse_var: bad arguments (rows=%lld, M=%lld, row stride %lld)", (long long)rows, (long long)M, (long long)ld);
+        return GPT_E_ARG;
+    }
+    return launch_sparse_var(c->stream, dV, dW, ld, rows, M, d_kdiag, d_var);
+}
+
+extern "C" int gpt_dev_sparse_assemble_b(gpt_ctx *c, const double *dG, int64_t ldg, int64_t M, double *dB, int64_t bp, double big)
+{
+    CTX_ENTER(c);
+    if (!dG || !dB) {
+        gpt_set_error("gpt_dev_sparse_assemble_b: bad arguments");
+        return GPT_E_ARG;
+    }
+    return launch_sparse_assemble_b(c->stream, dG, ldg, M, dB, bp, big);
 }

@@ -29,7 +29,8 @@ class SparseGaussianProcess(GaussianProcess):
     :class:`GaussianProcess`.  ``Z`` (M, D): the inducing inputs, ``n_Z`` their derivative orders (scalar or (M, D)); they are
     fixed -- not hyperparameters -- and :meth:`set_inducing` replaces them.  ``method``: ``"fitc"``, ``"vfe"`` or ``"dtc"``.
     ``jitter``: added to the diagonal of ``k(Z, Z)`` (absolute).  ``chunk_rows``: training rows per pass over the data, a
-    multiple of 64 (``None``: chosen by the library from a byte budget).
+    multiple of 64 (``None``: chosen by the library from a byte budget); predictions of the mean and the standard deviation send
+    their test points through chunks of the same size.
 
     Supported: ``update_hyperparameters`` (value only), ``compute_K_L_alpha_ll`` (sets ``ll`` and ``ll_parts``),
     ``optimize_hyperparameters`` (scipy on the value; ``random_starts`` one after another), ``compute_ll_matrix`` and the

@@ -704,8 +704,10 @@ int gpt_sparse_fit(gpt_ctx *ctx, int method, int nterms, const int *kernel_ids, 
                    const int *nparams, const int *nparams1, double noise_var, const double *y, const double *err_y, double jitter,
                    int64_t chunk_rows, double *ll_out, double *parts_out);
 
-/* Predictions of the resident sparse fit; arguments and `want` as gpt_predict (cov_out is required for want == 2).  The test
- * points go through in chunks; want == 2 holds all Ms rows at once. */
+/* Predictions of the resident sparse fit; arguments and `want` as gpt_predict (cov_out is required for want == 2).  For want <= 1
+ * the test points go through in the chunks of that fit: its chunk_rows argument (0: the same size rule), two chunk x (M padded)
+ * buffers where the fit holds one -- what bounded the fit's memory bounds the prediction's.  want == 2 holds all Ms rows at once,
+ * whatever chunk_rows was. */
 int gpt_sparse_predict(gpt_ctx *ctx, const double *Xstar, const int32_t *nstar, int64_t Ms, int want, const double *noise_params,
                        const int32_t *noise_n, double *mean_out, double *std_out, double *cov_out);
 
@@ -717,6 +719,25 @@ int gpt_sparse_get_c(gpt_ctx *ctx, double *c_out);
  * mg a multiple of 64, any rows >= 1.  The rows are split into nslices slices (0: chosen so that tiles x slices is about six times
  * the number of compute units), one workgroup per (tile, slice); the partial tiles are added in slice order (no atomics). */
 int gpt_dev_sparse_gram(gpt_ctx *ctx, const double *dV, int64_t ldv, int64_t rows, int64_t mg, int nslices, double *dG, int64_t ldg);
+
+/* Device API: the four other kernels of the sparse fit, one launch each, on raw device pointers and the context's stream.
+ * gpt_dev_sparse_lambda: the per-row pass over a chunk dV (rows x ldv row-major, ldv > M; row i holds V_.i in its columns [0, M)).
+ *   method: GPT_SPARSE_*.  q_i = sum_{m < M} V_mi^2, s_i = noise_var + d_err[i]^2, Lambda_i = d_kdiag[i] - q_i + s_i (fitc) or s_i;
+ *   d_rowval[i] = log Lambda_i, d_rowval[ldr + i] = (d_kdiag[i] - q_i) / s_i (vfe, else 0); the columns [0, M) of row i are scaled by
+ *   Lambda_i^-1/2 and column M is set to Lambda_i^-1/2 d_r[i]; the columns behind M are not touched.  A row whose Lambda_i is not a
+ *   positive finite number sets *d_bad = 1 (the word is never cleared here), gets 0 in both row values and in its columns [0, M].
+ *   rows <= ldr.
+ * gpt_dev_sparse_rowsum: d_acc[0] += sum_i d_rowval[i], d_acc[1] += sum_i d_rowval[ldr + i], i < rows <= ldr; a fixed order.
+ * gpt_dev_sparse_var: d_var[i] = d_kdiag[i] - sum_{m < M} dV[i][m]^2 + sum_{m < M} dW[i][m]^2 (both rows x ld row-major, M <= ld).
+ * gpt_dev_sparse_assemble_b: dB (bp x bp, row stride bp > M, every element written) from dG (row stride ldg > M, lower triangle and
+ *   row M read): rows < M hold I + G (the upper triangle zero), row M holds G[M][0..M) and `big` on the diagonal, the rows behind
+ *   it a unit diagonal. */
+int gpt_dev_sparse_lambda(gpt_ctx *ctx, double *dV, int64_t ldv, int64_t rows, int64_t M, int method, const double *d_kdiag,
+                          const double *d_r, const double *d_err, double noise_var, double *d_rowval, int64_t ldr, int32_t *d_bad);
+int gpt_dev_sparse_rowsum(gpt_ctx *ctx, const double *d_rowval, int64_t ldr, int64_t rows, double *d_acc);
+int gpt_dev_sparse_var(gpt_ctx *ctx, const double *dV, const double *dW, int64_t ld, int64_t rows, int64_t M, const double *d_kdiag,
+                       double *d_var);
+int gpt_dev_sparse_assemble_b(gpt_ctx *ctx, const double *dG, int64_t ldg, int64_t M, double *dB, int64_t bp, double big);
 
 /* ---- compiled schedules of the partitioned engines (round 6) ------------------------------------------------------------
  * The one-process-per-GPU block-cyclic Cholesky of gptools_amd/dist.py issues ~1000 operations per rank and evaluation; which

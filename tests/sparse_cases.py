@@ -49,7 +49,7 @@ SE2 = [1.1, 0.4, 0.6]
 NOISE = 0.1
 
 #: name -> model (terms: (oracle kernel, params) or (kernel 1, params 1, kernel 2, params 2) for a product), d, N, derivative rows,
-#: M, order-1 inducing rows, methods, chunk_rows (None: the default), heteroscedastic err_y
+#: M, order-1 inducing rows, methods, chunk_rows (None: the default), heteroscedastic err_y, optionally nstar (test points: NSTAR)
 CASES = {
     "se_300": dict(terms=[("se", SE2)], d=2, N=300, nder=60, M=40, zder=0, methods=("fitc", "vfe", "dtc"), chunks=(None, 128), het=False),
     "sum_prod_1100": dict(terms=[("se", SE2), ("m52", [0.7, 0.9, 1.3], "se", [1.0, 1.5, 0.8])], d=2, N=1100, nder=60, M=70, zder=0,
@@ -57,6 +57,24 @@ CASES = {
     "rq_257": dict(terms=[("rq", [1.0, 1.7, 0.4])], d=1, N=257, nder=0, M=33, zder=4, methods=("vfe",), chunks=(64,), het=False),
     "se3_130": dict(terms=[("se", [1.1, 0.4, 0.6, 0.9])], d=3, N=130, nder=0, M=129, zder=0, methods=("fitc",), chunks=(64,), het=False),
     "se1_64": dict(terms=[("se", [1.1, 0.35])], d=1, N=64, nder=0, M=1, zder=0, methods=("fitc",), chunks=(None,), het=False),
+    # M at the edges of the padded orders (MPU = M to 128, BP = LDV = M + 1 to 128, MG = M + 1 to 64) and past the 256-thread stride of
+    # the row kernels: 63 / 127 put the r~ column in the last column of the last Gram tile (127: BP = MPU), 64 / 128 give the
+    # augmented row a tile / a 128-block of its own (128: MPU < BP), 257 / 300 / 520 run the two-wide loop of sparse_lambda_kernel
+    # without / with a remainder pass / with a remainder pass that starts past 512.  sum_m257 is fitted with two methods because one
+    # method is one draw (module docstring).  With vfe alone the two routes measured 3.5e-13 apart in ll on one CPU and 7.2e-12
+    # apart on another (same numpy, another BLAS code path; ll = -611 stands behind r^T Lambda^-1 r - c.c = 15778 - 13826, and the
+    # dense route's c.c moved).  Against the Woodbury sums in numpy.longdouble: Woodbury 1.6e-12 on both CPUs, dense 1.9e-12 on
+    # the first and 5.6e-12 on the second, the device 1.3e-12.  fitc at the same matrices measures 5.0e-12, the scale of that error
+    "se_m63": dict(terms=[("se", SE2)], d=2, N=130, nder=20, M=63, zder=0, methods=("fitc", "vfe"), chunks=(64,), het=False),
+    "se_m64": dict(terms=[("se", SE2)], d=2, N=130, nder=20, M=64, zder=0, methods=("fitc",), chunks=(64,), het=False),
+    "se_m127": dict(terms=[("se", [1.1, 0.2, 0.3])], d=2, N=200, nder=20, M=127, zder=0, methods=("fitc", "vfe"), chunks=(64,), het=True,
+                    nstar=150),
+    "se_m128": dict(terms=[("se", [1.1, 0.2, 0.3])], d=2, N=200, nder=20, M=128, zder=0, methods=("fitc", "dtc"), chunks=(64,), het=True),
+    "m52_m300": dict(terms=[("m52", [1.0, 0.3, 0.4])], d=2, N=700, nder=60, M=300, zder=4, methods=("fitc", "vfe"), chunks=(256,), het=True),
+    "sum_m257": dict(terms=[("se", [1.1, 0.2, 0.25]), ("m52", [0.7, 0.9, 1.3], "se", [1.0, 1.5, 0.8])], d=2, N=400, nder=40, M=257, zder=0,
+                     methods=("fitc", "vfe"), chunks=(128,), het=True),
+    "m52_m520": dict(terms=[("m52", [1.0, 0.8, 0.8, 0.8])], d=3, N=900, nder=60, M=520, zder=0, methods=("fitc", "vfe"), chunks=(None,),
+                     het=False),
 }
 JITTER = 1e-6
 NSTAR, NSTAR_DER = 50, 4
@@ -71,8 +89,9 @@ def case_data(name):
     nZ = np.zeros((c["M"], c["d"]), dtype=int)
     if c["zder"]:
         nZ[-c["zder"]:, 0] = 1
-    Xs = rs.rand(NSTAR, c["d"])
-    ns = np.zeros((NSTAR, c["d"]), dtype=int)
+    nstar = c.get("nstar", NSTAR)
+    Xs = rs.rand(nstar, c["d"])
+    ns = np.zeros((nstar, c["d"]), dtype=int)
     ns[-NSTAR_DER:, 0] = 1
     err_y = 0.02 + 0.05 * rs.rand(c["N"]) if c["het"] else np.full(c["N"], 0.02)
     return dict(X=X, n=n, y=y, err_y=err_y, Z=Z, nZ=nZ, Xs=Xs, ns=ns)
@@ -230,4 +249,30 @@ HOST_ERR = {
         "ll": 9.4e-14, "sum_log_lambda": 1.17e-14, "sum_log_diag_LB": 3.02e-14, "r_lambda_r": 5.38e-14, "c_c": 5.28e-14, "trace": 0, "mean": 5.71e-13, "std": 2.31e-13, "cov": 1.89e-13, "mean_noise": 5.71e-13, "std_noise": 1.95e-13, "cov_noise": 1.89e-13},
     ("se1_64", "fitc"): {   # cond(K_uu + jitter I) = 1.0e+00, cond(B) = 1.0e+00
         "ll": 1.42e-15, "sum_log_lambda": 2.1e-15, "sum_log_diag_LB": 2.7e-15, "r_lambda_r": 1.25e-14, "c_c": 1.48e-14, "trace": 0, "mean": 7.14e-15, "std": 4.19e-16, "cov": 1.83e-16, "mean_noise": 7.14e-15, "std_noise": 3.83e-16, "cov_noise": 1.83e-16},
+    ("se_m63", "fitc"): {   # cond(K_uu + jitter I) = 4.4e+07, cond(B) = 1.1e+04
+        "ll": 7.89e-14, "sum_log_lambda": 5.02e-14, "sum_log_diag_LB": 7.25e-14, "r_lambda_r": 2.66e-13, "c_c": 3.33e-13, "trace": 0, "mean": 1.09e-11, "std": 3.99e-12, "cov": 7.69e-12, "mean_noise": 1.09e-11, "std_noise": 3.99e-12, "cov_noise": 7.69e-12},
+    ("se_m63", "vfe"): {   # cond(K_uu + jitter I) = 4.4e+07, cond(B) = 1.1e+04
+        "ll": 6.73e-14, "sum_log_lambda": 0, "sum_log_diag_LB": 1.46e-13, "r_lambda_r": 1.51e-16, "c_c": 1.84e-15, "trace": 1.21e-11, "mean": 8.85e-12, "std": 5.27e-12, "cov": 9.92e-12, "mean_noise": 8.85e-12, "std_noise": 5.27e-12, "cov_noise": 9.92e-12},
+    ("se_m64", "fitc"): {   # cond(K_uu + jitter I) = 4.5e+07, cond(B) = 1.1e+04
+        "ll": 3.53e-13, "sum_log_lambda": 7.4e-14, "sum_log_diag_LB": 1.39e-13, "r_lambda_r": 2.23e-13, "c_c": 2.07e-13, "trace": 0, "mean": 1.11e-11, "std": 3.18e-12, "cov": 6.12e-12, "mean_noise": 1.11e-11, "std_noise": 3.18e-12, "cov_noise": 6.12e-12},
+    ("se_m127", "fitc"): {   # cond(K_uu + jitter I) = 4.1e+07, cond(B) = 1.6e+04
+        "ll": 6.07e-13, "sum_log_lambda": 2.02e-13, "sum_log_diag_LB": 5.36e-13, "r_lambda_r": 1.02e-13, "c_c": 1.24e-13, "trace": 0, "mean": 9.09e-12, "std": 6.96e-13, "cov": 1.62e-12, "mean_noise": 9.09e-12, "std_noise": 6.96e-13, "cov_noise": 1.62e-12},
+    ("se_m127", "vfe"): {   # cond(K_uu + jitter I) = 4.1e+07, cond(B) = 1.7e+04
+        "ll": 1.58e-11, "sum_log_lambda": 0, "sum_log_diag_LB": 5.81e-15, "r_lambda_r": 1.16e-16, "c_c": 4.76e-14, "trace": 7.29e-11, "mean": 6.43e-12, "std": 2.96e-12, "cov": 5.92e-12, "mean_noise": 6.43e-12, "std_noise": 2.96e-12, "cov_noise": 5.92e-12},
+    ("se_m128", "fitc"): {   # cond(K_uu + jitter I) = 4.1e+07, cond(B) = 1.6e+04
+        "ll": 1.2e-12, "sum_log_lambda": 1.12e-13, "sum_log_diag_LB": 8.85e-14, "r_lambda_r": 2.96e-13, "c_c": 3.58e-13, "trace": 0, "mean": 8.13e-12, "std": 5.22e-12, "cov": 2.97e-12, "mean_noise": 8.13e-12, "std_noise": 5.22e-12, "cov_noise": 2.97e-12},
+    ("se_m128", "dtc"): {   # cond(K_uu + jitter I) = 4.1e+07, cond(B) = 1.7e+04
+        "ll": 2.45e-12, "sum_log_lambda": 0, "sum_log_diag_LB": 1.58e-13, "r_lambda_r": 1.16e-16, "c_c": 9.2e-14, "trace": 0, "mean": 5.88e-12, "std": 4.51e-12, "cov": 2.79e-12, "mean_noise": 5.88e-12, "std_noise": 4.51e-12, "cov_noise": 2.79e-12},
+    ("m52_m300", "fitc"): {   # cond(K_uu + jitter I) = 9.6e+07, cond(B) = 2.0e+04
+        "ll": 5.14e-13, "sum_log_lambda": 1.29e-14, "sum_log_diag_LB": 2.41e-13, "r_lambda_r": 4.98e-14, "c_c": 3.8e-14, "trace": 0, "mean": 2.82e-11, "std": 1.25e-12, "cov": 2.36e-12, "mean_noise": 2.82e-11, "std_noise": 1.25e-12, "cov_noise": 2.36e-12},
+    ("m52_m300", "vfe"): {   # cond(K_uu + jitter I) = 9.6e+07, cond(B) = 2.5e+04
+        "ll": 7.74e-12, "sum_log_lambda": 0, "sum_log_diag_LB": 1.08e-13, "r_lambda_r": 1.32e-16, "c_c": 4.5e-14, "trace": 1.26e-12, "mean": 4.21e-11, "std": 1.78e-12, "cov": 3.39e-12, "mean_noise": 4.21e-11, "std_noise": 1.78e-12, "cov_noise": 3.39e-12},
+    ("sum_m257", "fitc"): {   # cond(K_uu + jitter I) = 1.6e+08, cond(B) = 2.4e+04
+        "ll": 5.02e-12, "sum_log_lambda": 1.66e-13, "sum_log_diag_LB": 7.34e-13, "r_lambda_r": 6.5e-13, "c_c": 2.99e-13, "trace": 0, "mean": 6.38e-11, "std": 1.31e-11, "cov": 2.62e-11, "mean_noise": 6.38e-11, "std_noise": 1.31e-11, "cov_noise": 2.62e-11},
+    ("sum_m257", "vfe"): {   # cond(K_uu + jitter I) = 1.6e+08, cond(B) = 2.5e+04
+        "ll": 3.5e-13, "sum_log_lambda": 0, "sum_log_diag_LB": 1.16e-13, "r_lambda_r": 0, "c_c": 5.51e-14, "trace": 8.4e-11, "mean": 5.49e-11, "std": 1.56e-11, "cov": 3.11e-11, "mean_noise": 5.49e-11, "std_noise": 1.56e-11, "cov_noise": 3.11e-11},
+    ("m52_m520", "fitc"): {   # cond(K_uu + jitter I) = 1.9e+08, cond(B) = 5.1e+04
+        "ll": 1.06e-12, "sum_log_lambda": 8.1e-15, "sum_log_diag_LB": 1.36e-13, "r_lambda_r": 1.69e-14, "c_c": 5.78e-14, "trace": 0, "mean": 1.94e-11, "std": 2.02e-12, "cov": 3.52e-12, "mean_noise": 1.94e-11, "std_noise": 2.02e-12, "cov_noise": 3.52e-12},
+    ("m52_m520", "vfe"): {   # cond(K_uu + jitter I) = 1.9e+08, cond(B) = 5.2e+04
+        "ll": 9.01e-13, "sum_log_lambda": 0, "sum_log_diag_LB": 7.32e-14, "r_lambda_r": 0, "c_c": 5.6e-14, "trace": 1.89e-12, "mean": 1.75e-11, "std": 2.57e-12, "cov": 4.53e-12, "mean_noise": 1.75e-11, "std_noise": 2.57e-12, "cov_noise": 4.53e-12},
 }

@@ -168,7 +168,8 @@ def test_exports_and_bindings():
     from gptools_amd import _lib
     hdr = open(os.path.join(ROOT, "include", "gpt_hip.h")).read()
     hdr = re.sub(r"/\*.*?\*/", "", hdr, flags=re.S)
-    for name in ("gpt_sparse_set_inducing", "gpt_sparse_fit", "gpt_sparse_predict", "gpt_sparse_get_c", "gpt_dev_sparse_gram"):
+    for name in ("gpt_sparse_set_inducing", "gpt_sparse_fit", "gpt_sparse_predict", "gpt_sparse_get_c", "gpt_dev_sparse_gram",
+                 "gpt_dev_sparse_lambda", "gpt_dev_sparse_rowsum", "gpt_dev_sparse_var", "gpt_dev_sparse_assemble_b"):
         m = re.search(r"\bint\s+%s\s*\(([^)]*)\)" % name, hdr)
         assert m, name
         params = [" ".join(p.split()) for p in m.group(1).split(",")]
