@@ -130,6 +130,12 @@ SIGNATURES = {
     "gpt_dev_sparse_rowsum": (C.c_int, [_vp, _vp, _i64, _i64, _vp]),
     "gpt_dev_sparse_var": (C.c_int, [_vp, _vp, _vp, _i64, _i64, _i64, _vp, _vp]),
     "gpt_dev_sparse_assemble_b": (C.c_int, [_vp, _vp, _i64, _i64, _vp, _i64, C.c_double]),
+    "gpt_sparse_grad_diff": (C.c_int, [_vp, C.c_int, _ip, _dp, _dp, _dp, _dp, _dp, _dp, _dp]),
+    "gpt_dev_sparse_grad_rows": (C.c_int, [_vp, _vp, _vp, _i64, _i64, _i64, C.c_int, _vp, _vp, _vp, C.c_double, _vp, _vp, _vp, _vp, _i64,
+                                           _vp, _vp, _vp]),
+    "gpt_dev_sparse_gram2": (C.c_int, [_vp, _vp, _vp, _i64, _i64, _i64, C.c_int, _vp, _i64]),
+    "gpt_dev_sparse_grad_pairs": (C.c_int, [_vp, C.c_int, C.c_int, C.c_int, C.c_int, C.c_int, _dp, _dp, C.c_int, C.c_int, _vp, _vp, _i64,
+                                            _vp, _vp, _i64, _vp, _i64, _vp, _dp]),
 }
 
 _lib = None
@@ -598,7 +604,7 @@ class Context(object):
         check(self._lib.gpt_ll_grad_diff(self.handle, len(ti), iptr(ti), dptr(pa), dptr(pb), dptr(dn), dptr(out)))
         return out
 
-    def _pack_stencil(self, who, term_idx, params_a, params_b, denom):
+    def _pack_stencil(self, who, term_idx, params_a, params_b, denom, counts=None):
         """The stencil arguments of :meth:`ll_grad_diff` / :meth:`loo_grad_diff` checked and flattened: ``(term_idx, params_a,
         params_b, denom)`` as the exports read them."""
         ti, dn = i32(np.asarray(term_idx)), f64(np.asarray(denom, dtype=float))
@@ -607,7 +613,8 @@ class Context(object):
                              % (who, len(ti), len(params_a), len(params_b), len(dn)))
         # The library reads, per entry, as many doubles as the resident term has parameters (the export carries no lengths): the
         # counts are those of this context's last successful fit, and every vector is checked against them here
-        counts = self._term_nparams
+        # (``counts``: those of the resident sparse fit, for sparse_grad_diff)
+        counts = self._term_nparams if counts is None else counts
         if len(ti) and counts is None:
             raise GPTBackendError("%s needs a factorisation made by fit / fit_sum / fit_terms on this context" % who)
         for h, t in enumerate(ti):
@@ -732,10 +739,30 @@ class Context(object):
         y, err_y = f64(y), f64(err_y)
         ll = C.c_double()
         parts = np.zeros(5)
+        self._sparse_nparams = None
         check(self._lib.gpt_sparse_fit(self.handle, int(method), len(ids), iptr(ids), iptr(ids2), dptr(flat), iptr(npar), iptr(npar1),
                                        float(noise_var), dptr(y), dptr(err_y), float(jitter), int(chunk_rows), C.byref(ll),
                                        dptr(parts)))
+        self._sparse_nparams = [int(v) for v in npar]
         return ll.value, parts
+
+    def sparse_grad_diff(self, term_idx, params_a, params_b, denom, y, err_y, want_alpha=False):
+        """gpt_sparse_grad_diff: the gradient of the resident sparse fit's objective by per-pair central differences.  The stencil
+        arguments are :meth:`ll_grad_diff`'s, against the terms of the last :meth:`sparse_fit`; ``y`` and ``err_y`` as that fit took
+        them.  Returns ``(out, alpha)``: the entries of the kernel parameters followed by the derivative with respect to the noise
+        variance, and ``alpha = (Q_ff + Lambda)^-1 y`` (``None`` unless ``want_alpha``)."""
+        counts = getattr(self, "_sparse_nparams", None)
+        if counts is None:
+            counts = []              # (no sparse fit on this context: the library answers GPT_E_STATE)
+        ti, pa, pb, dn = self._pack_stencil("sparse_grad_diff", term_idx, params_a, params_b, denom, counts=counts)
+        y, err_y = f64(y), f64(err_y)
+        if y.shape != err_y.shape or y.ndim != 1:
+            raise ValueError("sparse_grad_diff: y and err_y must be vectors of one length, got %s and %s" % (y.shape, err_y.shape))
+        out = np.empty(len(ti) + 1)
+        alpha = np.empty(len(y)) if want_alpha else None
+        check(self._lib.gpt_sparse_grad_diff(self.handle, len(ti), iptr(ti), dptr(pa), dptr(pb), dptr(dn), dptr(y), dptr(err_y), dptr(out),
+                                             dptr(alpha)))
+        return out, alpha
 
     def sparse_predict(self, Xstar, nstar, want, noise_params=None, noise_n=None):
         Xstar, nstar = f64(Xstar), i32(nstar)

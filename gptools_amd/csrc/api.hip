@@ -54,7 +54,8 @@ enum { SLOT_XI = 0, SLOT_XJ, SLOT_NI, SLOT_NJ, SLOT_OUT, SLOT_KST, SLOT_KSS, SLO
        SLOT_BINV2, SLOT_BINV3, SLOT_BINV3U, SLOT_BINVU, SLOT_BATCH_A, SLOT_BATCH_WS, SLOT_BATCH_MISC, SLOT_SPLITK,
        SLOT_PB_V, SLOT_PB_COV, SLOT_PB_MISC, SLOT_XSW, SLOT_SS, SLOT_SI, SLOT_SJ, SLOT_WB_X, SLOT_WB_S, SLOT_WB_P, SLOT_GKP, SLOT_GB_U, SLOT_GB_W, SLOT_GB_MISC,
        SLOT_LOO_V, SLOT_LOO_VEC,
-       SLOT_SP_Z, SLOT_SP_LU, SLOT_SP_LB, SLOT_SP_V, SLOT_SP_W, SLOT_SP_G, SLOT_SP_PART, SLOT_SP_MISC, SLOT_SP_Y, SLOT_COUNT };
+       SLOT_SP_Z, SLOT_SP_LU, SLOT_SP_LB, SLOT_SP_V, SLOT_SP_W, SLOT_SP_G, SLOT_SP_PART, SLOT_SP_MISC, SLOT_SP_Y,
+       SLOT_SP_S1, SLOT_SP_S2, SLOT_SP_GM, SLOT_SP_GVEC, SLOT_SP_GPART, SLOT_COUNT };
 
 struct gpt_ctx {
     int device = 0;
@@ -177,6 +178,8 @@ struct gpt_ctx {
     bool sp_fitted = false;
     int64_t sp_chunk_rows = 0;         // the chunk_rows argument of the resident sparse fit: its predictions run in the same chunks
     ModelKernel sp_model;              // the model kernel of the resident sparse fit
+    int sp_method = 0;                 // ... its method, noise variance and jitter: what gpt_sparse_grad_diff needs beyond the model
+    double sp_noise_var = 0.0, sp_jitter = 0.0;
     int sp_ncu = 0;                    // compute units of the device (the Gram kernel's slice count), read on first use
     std::vector<hipEvent_t> sp_events; // phase marks of a timed gpt_sparse_fit (option "timing")
     double timings[5] = {0, 0, 0, 0, 0};
@@ -251,5 +254,6 @@ static int stream_follows(gpt_ctx *c, hipStream_t from, hipStream_t to, size_t i
 #include "api_predict.inc"      // gpt_predict, gpt_cov_sample, gpt_solve_L / gpt_cho_solve, gpt_potrf_host / gpt_gemm_nt_host
 #include "api_dev.inc"      // device API (gpt_dev_*): raw device pointers on the context's streams, for the one-process-per-GPU engines
 #include "api_sparse.inc"      // inducing-point approximations (FITC / VFE / DTC): gpt_sparse_set_inducing, gpt_sparse_fit, gpt_sparse_predict
+#include "api_sparse_grad.inc"      // the gradient of the sparse objective: gpt_sparse_grad_diff and the device API of its kernels
 #include "api_plan.inc"      // compiled schedules of the partitioned engines: gpt_plan_* (op list replay, RCCL called directly)
 #include "api_ensemble.inc"      // gpt_ensemble_run: the ensemble sampler's loop (ensemble.hpp) around the batched fit

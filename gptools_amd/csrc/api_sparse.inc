@@ -26,8 +26,9 @@ static SparseDims sparse_dims(int64_t M)
     return d;
 }
 
-// rows per chunk: the caller's (a positive multiple of 64), or what keeps two chunk x LDV buffers within GPT_SPARSE_CHUNK_BYTES
-static int sparse_chunk(const SparseDims &d, int64_t chunk_rows, int64_t n, int64_t *out)
+// rows per chunk: the caller's (a positive multiple of 64), or what keeps nbuf chunk x LDV buffers within GPT_SPARSE_CHUNK_BYTES (two for a
+// fit or a prediction, four for the gradient: api_sparse_grad.inc)
+static int sparse_chunk(const SparseDims &d, int64_t chunk_rows, int64_t n, int64_t *out, int64_t nbuf = 2)
 {
     if (chunk_rows < 0 || chunk_rows % 64) {
         gpt_set_error("gpt_sparse: chunk_rows must be 0 (chosen by size) or a positive multiple of 64, got %lld", (long long)chunk_rows);
@@ -35,7 +36,7 @@ static int sparse_chunk(const SparseDims &d, int64_t chunk_rows, int64_t n, int6
     }
     int64_t ch = chunk_rows;
     if (ch == 0) {
-        ch = GPT_SPARSE_CHUNK_BYTES / (2 * d.LDV * (int64_t)sizeof(double)) / 64 * 64;
+        ch = GPT_SPARSE_CHUNK_BYTES / (nbuf * d.LDV * (int64_t)sizeof(double)) / 64 * 64;
         if (ch < 64) ch = 64;
     }
     if (ch > round_up(n, 64)) ch = round_up(n, 64);
@@ -302,6 +303,9 @@ extern "C" int gpt_sparse_fit(gpt_ctx *c, int method, int nterms, const int *ker
         parts_out[4] = trace;
     }
     c->sp_model = model;
+    c->sp_method = method;
+    c->sp_noise_var = noise_var;
+    c->sp_jitter = jitter;
     c->sp_chunk_rows = chunk_rows;
     c->sp_fitted = true;
     return GPT_OK;

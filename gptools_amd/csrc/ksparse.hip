@@ -9,6 +9,10 @@
 //
 // Determinism: every sum has a fixed order.  The Gram kernel splits the chunk's rows into S slices, workgroup (tile, slice) writes
 // its partial tile to a workspace and sparse_gram_reduce_kernel adds the S partials to G in slice order: no floating-point atomics.
+//
+// The gradient of the objective (gpt_sparse_grad_diff) adds, at the end of this file, its per-row pass
+// (sparse_grad_rows_kernel), the rank-one part of A_fu, the two-operand Gram V diag(e) V^T for weights of either sign
+// (sparse_gram2_kernel, reduced by the same sparse_gram_reduce_kernel) and two small kernels of order M.
 #include "common.hpp"
 
 // ---- per-row pass ------------------------------------------------------------------------------------------------------------------
@@ -263,6 +267,235 @@ int launch_sparse_var(hipStream_t st, const double *V, const double *W, int64_t 
 {
     if (rows <= 0) return GPT_OK;
     hipLaunchKernelGGL(sparse_var_kernel, dim3((unsigned)rows), dim3(256), 0, st, V, W, ld, rows, M, kdiag, var);
+    GPT_LAUNCH_CHECK();
+    return GPT_OK;
+}
+
+// ---- the gradient of the objective (gpt_sparse_grad_diff, api_sparse_grad.inc) -----------------------------------------
+// Per-row pass of the gradient's second sweep over the chunks.  Row i of V holds v_i^T = (L_u^-1 k(Z, x_i))^T, row i of W holds
+// w_i^T = (L_B^-1 v_i)^T (columns < M of either); t = L_B^-T c.  With s_i = noise_var + err_i^2 and Lambda_i as in the fit:
+//     q_i = |v_i|^2      alpha_i = (r_i - v_i.t) / Lambda_i      W_ii = alpha_i^2 - 1 / Lambda_i + |w_i|^2 / Lambda_i^2
+//     e_i = W_ii (fitc), -1 / s_i (vfe), 0 (dtc)                 g_i = W_ii / 2 (+ (k_i - q_i) / (2 s_i^2) for vfe)
+// Written: alpha[i], e[i], gval[i] = g_i (gval[ldr + i] = 0: the layout sparse_rowsum_kernel adds up in a fixed order), and the two
+// scaled copies of the row, S1[i] = v_i / Lambda_i and S2[i] = e_i v_i, columns [M, ld) zero -- the operands of the chunk's GEMMs and
+// of the signed Gram.  q_i is summed exactly as sparse_lambda_kernel sums it: a row the fit accepted has the same Lambda_i here.  A
+// row whose Lambda_i is not a positive finite number raises *bad and contributes nothing (alpha, e, g and both copies are zero).
+__global__ __launch_bounds__(256) void sparse_grad_rows_kernel(const double *__restrict__ V, const double *__restrict__ W, int64_t ld,
+                                                               int64_t rows, int64_t M, int method, const double *__restrict__ kdiag,
+                                                               const double *__restrict__ r, const double *__restrict__ err,
+                                                               double noise_var, const double *__restrict__ t,
+                                                               double *__restrict__ alpha, double *__restrict__ e_out,
+                                                               double *__restrict__ gval, int64_t ldr, double *__restrict__ S1,
+                                                               double *__restrict__ S2, int32_t *__restrict__ bad)
+{
+    __shared__ double pq[4], pt[4], pw[4];
+    __shared__ double sc1, sc2;
+    const int64_t i = blockIdx.x;
+    if (i >= rows) return;
+    const double *v = V + i * ld, *w = W + i * ld;
+    const int lane = threadIdx.x & 63, wave = threadIdx.x >> 6;
+    double a0 = 0.0, a1 = 0.0, bt = 0.0, bw = 0.0;
+    int64_t c = threadIdx.x;
+    for (; c + 256 < M; c += 512) {
+        const double v0 = v[c], v1 = v[c + 256];
+        a0 = fma(v0, v0, a0);
+        a1 = fma(v1, v1, a1);
+    }
+    for (; c < M; c += 256) {
+        const double v0 = v[c];
+        a0 = fma(v0, v0, a0);
+    }
+    for (c = threadIdx.x; c < M; c += 256) {
+        bt = fma(v[c], t[c], bt);
+        bw = fma(w[c], w[c], bw);
+    }
+    double acc = a0 + a1;
+    for (int off = 32; off > 0; off >>= 1) {
+        acc += __shfl_down(acc, off);
+        bt += __shfl_down(bt, off);
+        bw += __shfl_down(bw, off);
+    }
+    if (lane == 0) {
+        pq[wave] = acc;
+        pt[wave] = bt;
+        pw[wave] = bw;
+    }
+    __syncthreads();
+    if (threadIdx.x == 0) {
+        const double q = (pq[0] + pq[1]) + (pq[2] + pq[3]), vt = (pt[0] + pt[1]) + (pt[2] + pt[3]), ww = (pw[0] + pw[1]) + (pw[2] + pw[3]);
+        const double er = err[i], s = noise_var + er * er, kmq = (method == 2) ? 0.0 : kdiag[i] - q;
+        const double lam = (method == 0) ? kmq + s : s;
+        const bool ok = lam > 0.0 && lam < INFINITY;
+        if (!ok) *bad = 1;
+        const double il = ok ? 1.0 / lam : 0.0;
+        const double al = ok ? (r[i] - vt) * il : 0.0;
+        const double wii = (al * al - il) + ww * il * il;
+        const double e = !ok ? 0.0 : (method == 0) ? wii : (method == 1) ? -1.0 / s : 0.0;
+        double g = 0.5 * wii;
+        if (method == 1) g += 0.5 * kmq / (s * s);
+        alpha[i] = al;
+        e_out[i] = e;
+        gval[i] = ok ? g : 0.0;
+        gval[ldr + i] = 0.0;
+        sc1 = il;
+        sc2 = e;
+    }
+    __syncthreads();
+    const double s1 = sc1, s2 = sc2;
+    double *o1 = S1 + i * ld, *o2 = S2 + i * ld;
+    for (c = threadIdx.x; c < ld; c += 256) {
+        const double vc = (c < M) ? v[c] : 0.0;
+        o1[c] = vc * s1;
+        o2[c] = vc * s2;
+    }
+}
+
+int launch_sparse_grad_rows(hipStream_t st, const double *V, const double *W, int64_t ld, int64_t rows, int64_t M, int method,
+                            const double *kdiag, const double *r, const double *err, double noise_var, const double *t, double *alpha,
+                            double *e_out, double *gval, int64_t ldr, double *S1, double *S2, int32_t *bad)
+{
+    if (rows <= 0) return GPT_OK;
+    if (M < 1 || M > ld || rows > ldr) {
+        gpt_set_error("sparse_grad_rows: M = %lld in rows of %lld, %lld rows with a value stride of %lld", (long long)M, (long long)ld,
+                      (long long)rows, (long long)ldr);
+        return GPT_E_ARG;
+    }
+    hipLaunchKernelGGL(sparse_grad_rows_kernel, dim3((unsigned)rows), dim3(256), 0, st, V, W, ld, rows, M, method, kdiag, r, err, noise_var,
+                       t, alpha, e_out, gval, ldr, S1, S2, bad);
+    GPT_LAUNCH_CHECK();
+    return GPT_OK;
+}
+
+// A[i][m] += alpha[i] * beta[m], i < rows, m < M: the rank-one part of a chunk's A_fu
+__global__ __launch_bounds__(256) void sparse_rank1_kernel(double *__restrict__ A, int64_t lda, int64_t rows, int64_t M,
+                                                           const double *__restrict__ alpha, const double *__restrict__ beta)
+{
+    const int64_t m = (int64_t)blockIdx.y * 256 + threadIdx.x, i = blockIdx.x;
+    if (m < M && i < rows) A[i * lda + m] = fma(alpha[i], beta[m], A[i * lda + m]);
+}
+
+int launch_sparse_rank1(hipStream_t st, double *A, int64_t lda, int64_t rows, int64_t M, const double *alpha, const double *beta)
+{
+    if (rows <= 0 || M <= 0) return GPT_OK;
+    if (M > lda || (M + 255) / 256 > 65535) return GPT_E_ARG;
+    hipLaunchKernelGGL(sparse_rank1_kernel, dim3((unsigned)rows, (unsigned)((M + 255) / 256)), dim3(256), 0, st, A, lda, rows, M, alpha, beta);
+    GPT_LAUNCH_CHECK();
+    return GPT_OK;
+}
+
+// The signed-weight Gram: sparse_gram_kernel with TWO operands, tile (ti, tj) += sum_k A[k][i0 + i] V[k][j0 + j] -- A holds the rows
+// e_k v_k, and e_k changes sign, so the rows cannot be scaled by a square root and fed to the one-operand kernel.  The same tiles,
+// slices, lane maps and partial-tile layout; sparse_gram_reduce_kernel adds the slices.  A kernel of its own: the fit's stays the
+// code it was.
+__global__ __launch_bounds__(256) void sparse_gram2_kernel(const double *__restrict__ A, const double *__restrict__ V, int64_t ldv,
+                                                           int64_t rows, int64_t slice_rows, int ntiles, double *__restrict__ part)
+{
+    const int t = blockIdx.x, s = blockIdx.y;
+    int ti = (int)((sqrt(8.0 * (double)t + 1.0) - 1.0) * 0.5);
+    while ((ti + 1) * (ti + 2) / 2 <= t) ti++;
+    while (ti * (ti + 1) / 2 > t) ti--;
+    const int tj = t - ti * (ti + 1) / 2;
+    const int lane = threadIdx.x & 63, wave = threadIdx.x >> 6;
+    const int fr = lane & 15, fk = lane >> 4;
+    const int64_t i0 = (int64_t)ti * 64 + (wave >> 1) * 32, j0 = (int64_t)tj * 64 + (wave & 1) * 32;
+    const int64_t k0 = (int64_t)s * slice_rows;
+    const int64_t k1 = (k0 + slice_rows < rows) ? k0 + slice_rows : rows;
+    f64x4 acc[2][2];
+#pragma unroll
+    for (int a = 0; a < 2; a++)
+#pragma unroll
+        for (int b = 0; b < 2; b++) acc[a][b] = f64x4{0.0, 0.0, 0.0, 0.0};
+    for (int64_t k = k0; k < k1; k += 4 * SG_UNROLL) {
+        double av[SG_UNROLL][2], bv[SG_UNROLL][2];
+#pragma unroll
+        for (int u = 0; u < SG_UNROLL; u++) {
+            const int64_t kr = k + 4 * u + fk;
+            const bool live = kr < k1;
+            const double *ra = A + kr * ldv, *rb = V + kr * ldv;
+            av[u][0] = live ? ra[i0 + fr] : 0.0;
+            av[u][1] = live ? ra[i0 + 16 + fr] : 0.0;
+            bv[u][0] = live ? rb[j0 + fr] : 0.0;
+            bv[u][1] = live ? rb[j0 + 16 + fr] : 0.0;
+        }
+#pragma unroll
+        for (int u = 0; u < SG_UNROLL; u++)
+#pragma unroll
+            for (int a = 0; a < 2; a++)
+#pragma unroll
+                for (int b = 0; b < 2; b++)
+                    acc[a][b] = __builtin_amdgcn_mfma_f64_16x16x4f64(av[u][a], bv[u][b], acc[a][b], 0, 0, 0);
+    }
+    double *out = part + ((int64_t)s * ntiles + t) * 4096;
+    const int li = (wave >> 1) * 32, lj = (wave & 1) * 32;
+#pragma unroll
+    for (int a = 0; a < 2; a++)
+#pragma unroll
+        for (int b = 0; b < 2; b++)
+#pragma unroll
+            for (int q = 0; q < 4; q++) out[(li + a * 16 + fk + 4 * q) * 64 + lj + b * 16 + fr] = acc[a][b][q];
+}
+
+// G (mg x mg, lower 64 x 64 tiles) += A^T V over the `rows` rows of A and V (both with row stride ldv >= mg): launch_sparse_gram's
+// checks, slices and reduce
+int launch_sparse_gram2(hipStream_t st, const double *A, const double *V, int64_t ldv, int64_t rows, int64_t mg, int nslices, double *part,
+                        double *G, int64_t ldg)
+{
+    if (rows <= 0) return GPT_OK;
+    if (mg <= 0 || mg % 64 || mg > ldv || mg > ldg || nslices < 1 || nslices > 65535 || mg / 64 > 2000) {
+        gpt_set_error("sparse_gram2: order %lld (a multiple of 64, at most the row strides %lld / %lld), %d slices", (long long)mg,
+                      (long long)ldv, (long long)ldg, nslices);
+        return GPT_E_ARG;
+    }
+    const int nt = (int)(mg / 64), ntiles = nt * (nt + 1) / 2;
+    int64_t slice_rows = ((rows + nslices - 1) / nslices + 3) / 4 * 4;
+    const int ns = (int)((rows + slice_rows - 1) / slice_rows);
+    hipLaunchKernelGGL(sparse_gram2_kernel, dim3((unsigned)ntiles, (unsigned)ns), dim3(256), 0, st, A, V, ldv, rows, slice_rows, ntiles, part);
+    GPT_LAUNCH_CHECK();
+    hipLaunchKernelGGL(sparse_gram_reduce_kernel, dim3((unsigned)ntiles, 16), dim3(256), 0, st, part, ntiles, ns, G, ldg);
+    GPT_LAUNCH_CHECK();
+    return GPT_OK;
+}
+
+// dst (np x np, row stride ldd) = the lower triangle of src's leading n x n block, zeros elsewhere: L_B without its augmented rows
+__global__ void sparse_tril_kernel(const double *__restrict__ src, int64_t lds, int64_t n, double *__restrict__ dst, int64_t ldd, int64_t np)
+{
+    const int64_t j = (int64_t)blockIdx.x * blockDim.x + threadIdx.x, i = blockIdx.y;
+    if (j >= np) return;
+    dst[i * ldd + j] = (i < n && j <= i) ? src[i * lds + j] : 0.0;
+}
+
+int launch_sparse_tril(hipStream_t st, const double *src, int64_t lds, int64_t n, double *dst, int64_t ldd, int64_t np)
+{
+    if (n < 1 || np < n || np > 65535 || ldd < np) return GPT_E_ARG;
+    hipLaunchKernelGGL(sparse_tril_kernel, dim3((unsigned)((np + 255) / 256), (unsigned)np), dim3(256), 0, st, src, lds, n, dst, ldd, np);
+    GPT_LAUNCH_CHECK();
+    return GPT_OK;
+}
+
+// Mid (np x np, symmetric, both triangles) = I - Binv + E over the leading M x M block, zeros elsewhere.  mode 0 (fitc): E = the lower
+// tiles of the signed Gram V diag(e) V^T (entry (i, j) read at (max, min)); mode 1 (vfe): E = -(B - I), B given whole; mode 2 (dtc): 0.
+__global__ void sparse_grad_mid_kernel(const double *__restrict__ Binv, int64_t ldb, const double *__restrict__ E, int64_t lde, int64_t M,
+                                       int mode, double *__restrict__ Mid, int64_t np)
+{
+    const int64_t j = (int64_t)blockIdx.x * blockDim.x + threadIdx.x, i = blockIdx.y;
+    if (j >= np) return;
+    double v = 0.0;
+    if (i < M && j < M) {
+        const double id = (i == j) ? 1.0 : 0.0;
+        const int64_t hi = i > j ? i : j, lo = i > j ? j : i;
+        v = id - Binv[hi * ldb + lo];
+        if (mode == 0) v += E[hi * lde + lo];
+        else if (mode == 1) v -= E[hi * lde + lo] - id;
+    }
+    Mid[i * np + j] = v;
+}
+
+int launch_sparse_grad_mid(hipStream_t st, const double *Binv, int64_t ldb, const double *E, int64_t lde, int64_t M, int mode, double *Mid,
+                           int64_t np)
+{
+    if (M < 1 || np < M || np > 65535 || (mode != 2 && !E)) return GPT_E_ARG;
+    hipLaunchKernelGGL(sparse_grad_mid_kernel, dim3((unsigned)((np + 255) / 256), (unsigned)np), dim3(256), 0, st, Binv, ldb, E, lde, M, mode,
+                       Mid, np);
     GPT_LAUNCH_CHECK();
     return GPT_OK;
 }

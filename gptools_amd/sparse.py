@@ -12,6 +12,9 @@ include/gpt_hip.h).  With ``s_i = sigma_noise^2 + err_y_i^
 What the dense class offers beyond value, optimisation over the value and prediction is refused here, never routed to the dense
 path: see the class docstring.
 """
+import traceback
+import warnings
+
 import numpy as np
 
 from . import _lib, _ingest
@@ -33,12 +36,13 @@ class SparseGaussianProcess(GaussianProcess):
     their test points through chunks of the same size.
 
     Supported: ``update_hyperparameters`` (value only), ``compute_K_L_alpha_ll`` (sets ``ll`` and ``ll_parts``),
-    ``optimize_hyperparameters`` (scipy on the value; ``random_starts`` one after another), ``compute_ll_matrix`` and the
+    :meth:`sparse_gradient` (the gradient of the objective, ``gpt_sparse_grad_diff``), ``optimize_hyperparameters`` (scipy on the
+    value, or with ``gradient="sparse"`` on the value and that gradient; ``random_starts`` one after another), ``compute_ll_matrix`` and the
     host-stepped sampler (one evaluation per vector), ``predict`` and ``draw_sample`` (through the returned covariance).
 
     Refused (``NotImplementedError`` / ``ValueError``): a covariance kernel the library does not evaluate itself, warped
     kernels, a noise kernel that is not a ``DiagonalNoiseKernel``; ``T``, ``use_hyper_deriv``, ``partitioned``;
-    ``ll_gradient*``, ``loo_*``, ``objective="loo"``, ``gradient="device"``, ``batch_starts``, ``ll_batch``; the
+    ``ll_gradient*`` (see :meth:`sparse_gradient`), ``loo_*``, ``objective="loo"``, ``gradient="device"``, ``batch_starts``, ``ll_batch``; the
     library-stepped sampler, ``use_MCMC`` predictions; ``L`` and ``alpha`` (there is no ``N x N`` factor)."""
 
     def __init__(self, k, Z, noise_k=None, n_Z=0, method="fitc", jitter=1e-6, chunk_rows=None, X=None, y=None, err_y=0, n=0,
@@ -116,8 +120,8 @@ class SparseGaussianProcess(GaussianProcess):
         method.__doc__ = "Refused: the sparse path has no %s." % what
         return method
 
-    ll_gradient = _refuse("gradient of the sparse objective (ll_gradient)")
-    ll_gradient_batch = _refuse("gradient of the sparse objective (ll_gradient_batch)")
+    ll_gradient = _refuse("dense-path gradient (ll_gradient): the gradient of the sparse objective is sparse_gradient")
+    ll_gradient_batch = _refuse("batched gradient of the sparse objective (ll_gradient_batch): sparse_gradient takes one point at a time")
     loo_predict = _refuse("leave-one-out cross-validation (loo_predict)")
     loo_log_likelihood = _refuse("leave-one-out cross-validation (loo_log_likelihood)")
     loo_gradient = _refuse("leave-one-out cross-validation (loo_gradient)")
@@ -162,6 +166,40 @@ class SparseGaussianProcess(GaussianProcess):
                                                                          exit_on_bounds=exit_on_bounds,
                                                                          inf_on_error=inf_on_error)
 
+    # ---- the gradient (gpt_sparse_grad_diff) ---------------------------------------------
+    def sparse_gradient(self, rel_step=6e-6):
+        """Gradient of the sparse objective plus the log hyperprior with respect to the free hyperparameters at their current
+        values (``gpt_sparse_grad_diff``): one more pass over the data in chunks, whatever the number of parameters -- per free
+        kernel parameter the term's central difference, eps = ``rel_step`` max(1, abs(theta)), is taken per pair (x_i, z_m),
+        (z_m, z_m') and (x_i, x_i) before it meets its weight.  The noise parameter, the mean function's parameters and the
+        hyperprior's derivative as in :meth:`GaussianProcess.ll_gradient`.  Fits first if the hyperparameters changed; they and
+        ``K_up_to_date`` are afterwards what they were.  The inducing inputs are fixed: no entry for ``Z``."""
+        self._sparse_refusal()
+        self.compute_K_L_alpha_ll()
+        slot, tix, pa, pb, denom = self._ll_gradient_stencil(rel_step)
+        g_dev, alpha = self._ctx.sparse_grad_diff(tix, pa, pb, denom, self._y_alph(), self.err_y, want_alpha=self.mu is not None)
+        return self._ll_gradient_assemble(slot, g_dev, lambda: alpha)
+
+    def _sparse_grad_jac(self):
+        """``jac`` for scipy beside ``update_hyperparameters`` as ``fun``: minus :meth:`sparse_gradient`, zeros where the value is
+        ``+inf`` -- the objective of ``GaussianProcess._device_grad_objective``.  The value at the point is the fit's if scipy has
+        just evaluated it there (the hyperparameters are still its), one more evaluation otherwise."""
+        def jac(x):
+            x = np.array(x, dtype=float)
+            if self.K_up_to_date and np.array_equal(np.asarray(self.free_params[:], dtype=float), x):
+                f0 = -1.0 * self.ll
+            else:
+                f0 = self.update_hyperparameters(x)
+            if not np.isfinite(f0):
+                return np.zeros(len(x))
+            try:
+                return -1.0 * self.sparse_gradient()
+            except Exception:
+                warnings.warn("the gradient of the sparse objective failed at free hyperparameters %s, where the log-posterior is "
+                              "%.6g:\n%s" % (x, -f0, traceback.format_exc()), RuntimeWarning)
+                raise
+        return jac
+
     def _ll_rows(self, param_list):
         keep = np.array(self.free_params[:], dtype=float)
         try:
@@ -171,16 +209,24 @@ class SparseGaussianProcess(GaussianProcess):
 
     def optimize_hyperparameters(self, method="SLSQP", opt_kwargs={}, verbose=False, random_starts=None, num_proc=None,
                                  max_tries=1, batch_fd=None, gradient=None, batch_starts=False, objective="ll"):
-        """``scipy.optimize.minimize`` on the value of the sparse objective (scipy differences it itself), the starts one after
-        another; arguments and return value as the base class.  ``gradient="device"``, ``batch_starts`` and
+        """``scipy.optimize.minimize`` on the sparse objective, the starts one after another; arguments and return value as the base
+        class.  ``gradient=None``: scipy differences the value itself, one fit per free parameter and step;
+        ``gradient="sparse"``: scipy is given ``jac`` = minus :meth:`sparse_gradient`, one fit and one gradient pass per step
+        (``+inf`` with a zero gradient where the value fails).  ``gradient="device"`` (the dense path's), ``batch_starts`` and
         ``objective="loo"`` are refused."""
-        if gradient is not None:
-            raise NotImplementedError("SparseGaussianProcess has no gradient of the sparse objective (gradient=%r)" % (gradient,))
+        if gradient not in (None, "sparse"):
+            raise NotImplementedError("SparseGaussianProcess has no dense-path gradient (gradient=%r): the gradient of the sparse "
+                                      "objective is gradient='sparse'" % (gradient,))
         if batch_starts:
             raise NotImplementedError("SparseGaussianProcess has no batched evaluator (batch_starts)")
         if objective != "ll":
             raise NotImplementedError("SparseGaussianProcess has no leave-one-out objective (objective=%r)" % (objective,))
         self._sparse_refusal()
+        if gradient == "sparse":
+            if "jac" in (opt_kwargs or {}):
+                raise ValueError("gradient='sparse' cannot be combined with a jac of the caller's")
+            self._ctx                          # (no device: GPTBackendError here, not a +inf objective at every start)
+            opt_kwargs = dict(opt_kwargs or {}, jac=self._sparse_grad_jac())
         return super(SparseGaussianProcess, self).optimize_hyperparameters(
             method=method, opt_kwargs=opt_kwargs, verbose=verbose, random_starts=random_starts, num_proc=num_proc,
             max_tries=max_tries, batch_fd=False)

@@ -739,6 +739,47 @@ int gpt_dev_sparse_var(gpt_ctx *ctx, const double *dV, const double *dW, int64_t
                        double *d_var);
 int gpt_dev_sparse_assemble_b(gpt_ctx *ctx, const double *dG, int64_t ldg, int64_t M, double *dB, int64_t bp, double big);
 
+/* The gradient of the resident sparse fit's objective by per-pair central differences, the stencil
+ * arguments those of gpt_ll_grad_diff: entry h < nh names term term_idx[h] of the fitted model with that term's complete parameter
+ * vector at the two stencil points (params_a / params_b, entry after entry) and denom[h] = theta_b - theta_a; every stencil point goes
+ * through the order checks of the fit as a one-term model.  y, err_y: as given to gpt_sparse_fit (the fit keeps no copy).
+ *   t = L_B^-T c,  beta = L_u^-T t,  alpha_i = (y_i - v_i.t) / Lambda_i  (alpha = (Q_ff + Lambda)^-1 y),  w_i = L_B^-1 v_i
+ *   W_ii = alpha_i^2 - 1 / Lambda_i + |w_i|^2 / Lambda_i^2,   e_i = W_ii (fitc), -1 / s_i (vfe), 0 (dtc)
+ *   A_fu[i,:] = alpha_i beta^T - (1 / Lambda_i) v_i^T B^-1 L_u^-1 - e_i v_i^T L_u^-1
+ *   A_uu = -1/2 (beta beta^T - L_u^-T (I - B^-1 + V diag(e) V^T) L_u^-1)
+ *   d ll = sum A_uu dK_uu + sum A_fu dK_fu + 1/2 sum_i e_i dk_i + sum_i g_i ds_i,   g_i = W_ii / 2 (+ (k_i - q_i) / (2 s_i^2), vfe)
+ * out[h], h < nh: the entry of the kernel parameter; out[nh] = sum_i g_i, the derivative with respect to noise_var.  alpha_out (N
+ * doubles, may be NULL): alpha, what a mean function's parameters take their derivative against.  The jitter is a constant.
+ * One more pass over the training rows in chunks -- the fit's chunk_rows, or the size rule for FOUR chunk x (M padded) buffers -- in
+ * ascending order with fixed summation orders: the same call gives the same bits.  L_u, L_B, c and the dense factor of the context
+ * are read, never written.  GPT_E_STATE without a sparse fit that succeeded, GPT_E_NOTIMPL with gpt_set_T or warp layers,
+ * GPT_E_ARG for a zero or infinite denom, GPT_E_VALUE if a Lambda_i is not a positive finite number. */
+int gpt_sparse_grad_diff(gpt_ctx *ctx, int nh, const int *term_idx, const double *params_a, const double *params_b, const double *denom,
+                         const double *y, const double *err_y, double *out, double *alpha_out);
+
+/* Device API: the kernels of that gradient alone, on raw device pointers and the context's stream.
+ * gpt_dev_sparse_grad_rows: the per-row pass.  dV, dW (rows x ld row-major, M <= ld): row i holds v_i and w_i in its columns [0, M);
+ *   d_t: M doubles.  Per row q_i = |v_i|^2, Lambda_i as gpt_dev_sparse_lambda, alpha_i, W_ii, e_i, g_i as above (d_kdiag is not read
+ *   for dtc); written: d_alpha[i], d_e[i], d_gval[i] = g_i and d_gval[ldr + i] = 0 (the layout gpt_dev_sparse_rowsum adds up), and
+ *   the scaled copies dS1[i] = v_i / Lambda_i, dS2[i] = e_i v_i with zeros in the columns [M, ld).  A row whose Lambda_i is not a
+ *   positive finite number sets *d_bad = 1 and gets zeros throughout.  rows <= ldr.
+ * gpt_dev_sparse_gram2: gpt_dev_sparse_gram with two operands, dG += dA^T dV (both rows x ldv): the signed-weight Gram V diag(e) V^T
+ *   from dA = dS2.  The same tiles, slices and slice-ordered sum.
+ * gpt_dev_sparse_grad_pairs: the rectangular pair pass for ONE term, kernel_id (* kernel_id2 where >= 0) of num_dim D with nparams
+ *   parameters (nparams1 of them the first factor's): out[h] = sum_im dA[i][m] (k_b - k_a)(x_i, z_m) + 1/2 sum_i d_e[i] (k_b - k_a)(x_i,
+ *   x_i) with k_a / k_b the term at params_a / params_b (host, nh x nparams each), h < nh (GPT_GRAD_MAXH per launch); not divided by
+ *   a step.  dX (rows x D) and dZ (M x D) with orders dnx / dnz, max_order the largest order sum among them; dA rows x lda, M <= lda;
+ *   d_e NULL: no diagonal part.  Partial sums are added in index order: the same call gives the same bits. */
+int gpt_dev_sparse_grad_rows(gpt_ctx *ctx, const double *dV, const double *dW, int64_t ld, int64_t rows, int64_t M, int method,
+                             const double *d_kdiag, const double *d_r, const double *d_err, double noise_var, const double *d_t,
+                             double *d_alpha, double *d_e, double *d_gval, int64_t ldr, double *dS1, double *dS2, int32_t *d_bad);
+int gpt_dev_sparse_gram2(gpt_ctx *ctx, const double *dA, const double *dV, int64_t ldv, int64_t rows, int64_t mg, int nslices, double *dG,
+                         int64_t ldg);
+int gpt_dev_sparse_grad_pairs(gpt_ctx *ctx, int kernel_id, int kernel_id2, int D, int max_order, int nh, const double *params_a,
+                              const double *params_b, int nparams, int nparams1, const double *dX, const int32_t *dnx, int64_t rows,
+                              const double *dZ, const int32_t *dnz, int64_t M, const double *dA, int64_t lda, const double *d_e,
+                              double *out);
+
 /* ---- compiled schedules of the partitioned engines (round 6) ------------------------------------------------------------
  * The one-process-per-GPU block-cyclic Cholesky of gptools_amd/dist.py issues ~1000 operations per rank and evaluation; which
  * ones, on which buffers, in which order is static per (N, nb, world, rank).  The Python layer records its step loop once as an
