@@ -247,6 +247,7 @@ static int stream_follows(gpt_ctx *c, hipStream_t from, hipStream_t to, size_t i
 #include "api_kernels.inc"      // Kernel.__call__ and compute_Kij: gpt_kpairs, gpt_kbuild, gpt_kpairs2, gpt_kbuild2
 #include "api_fit.inc"      // data residency and the fit: gpt_set_data, gpt_set_T, gpt_fit, gpt_fit_sum, gpt_fit_terms, gpt_fit_matrix
 #include "api_batch.inc"      // batched small fits (gpt_fit_batch*), timings / GEMM profile read-out, gpt_get_L, alpha (gpt_get_alpha)
+#include "grad_stencil.inc"      // the stencil of the differenced gradients: one parser of its points, one walk of the launch groups
 #include "api_grad.inc"      // triangular inverses (gpt_dev_trinv) and the analytic LML gradient gpt_ll_grad
 #include "api_loo.inc"      // leave-one-out cross-validation: gpt_loo, gpt_loo_grad_diff
 #include "api_grad_batch.inc"      // gpt_ll_grad_diff_batch: the gradient half of a resident batch

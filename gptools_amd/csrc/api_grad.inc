@@ -350,6 +350,28 @@ static int grad_timing_report(const char *who, int64_t N, hipStream_t st, hipEve
     return GPT_OK;
 }
 
+// The partial rows of one launch of a pair pass -- nblk workgroups x (GPT_GRAD_MAXH + 1) slots -- copied to the host, and the sum of a
+// slot over the workgroups in index order, left to right: what gpt_ll_grad, grad_diff_run and the Z-Z pass of gpt_sparse_grad_diff
+// turn into an entry.  fetch() synchronises `st`.
+struct GradPartials {
+    int nblk;
+    std::vector<double> h;
+    explicit GradPartials(int nblk_) : nblk(nblk_), h((size_t)nblk_ * (GPT_GRAD_MAXH + 1)) {}
+    size_t bytes() const { return h.size() * sizeof(double); }
+    int fetch(hipStream_t st, const double *dpart)
+    {
+        GPT_HIP_CHECK(hipMemcpyAsync(h.data(), dpart, bytes(), hipMemcpyDeviceToHost, st));
+        GPT_HIP_CHECK(hipStreamSynchronize(st));
+        return GPT_OK;
+    }
+    double sum(int q) const
+    {
+        double s = 0.0;
+        for (int b = 0; b < nblk; b++) s += h[(size_t)b * (GPT_GRAD_MAXH + 1) + q];
+        return s;
+    }
+};
+
 extern "C" int gpt_ll_grad(gpt_ctx *c, int nh, const int *term_idx, const int *local_idx, double *out)
 {
     CTX_ENTER(c);
@@ -379,8 +401,8 @@ extern "C" int gpt_ll_grad(gpt_ctx *c, int nh, const int *term_idx, const int *l
     double *dpart;
     // sum_ab (alpha_a alpha_b - W_ab) dK_h[a][b], per kernel term, GPT_GRAD_MAXH parameters per launch
     const int nblk = grad_reduce_blocks(Np);
-    GPT_TRY(ensure(c, SLOT_GPART, (size_t)nblk * (GPT_GRAD_MAXH + 1) * sizeof(double), (void **)&dpart));
-    std::vector<double> hpart((size_t)nblk * (GPT_GRAD_MAXH + 1));
+    GradPartials hpart(nblk);
+    GPT_TRY(ensure(c, SLOT_GPART, hpart.bytes(), (void **)&dpart));
     bool have_trace = false;
     const int nterms = c->model.nterms;
     for (int t = 0; t < nterms || !have_trace; t++) {
@@ -399,17 +421,10 @@ extern "C" int gpt_ll_grad(gpt_ctx *c, int nh, const int *term_idx, const int *l
             ks.symmetric = 1;
             GPT_TRY(launch_grad_reduce(st, ks, cnt > 0 ? cnt : 0, cnt > 0 ? hs.data() + b0 : nullptr, c->dX, c->dn, Np,
                                        ap, Wp, ldwp, dpart));
-            GPT_HIP_CHECK(hipMemcpyAsync(hpart.data(), dpart, hpart.size() * sizeof(double), hipMemcpyDeviceToHost, st));
-            GPT_HIP_CHECK(hipStreamSynchronize(st));
-            for (int q = 0; q < cnt; q++) {
-                double sum = 0.0;
-                for (int b = 0; b < nblk; b++) sum += hpart[(size_t)b * (GPT_GRAD_MAXH + 1) + q];
-                out[where[b0 + q]] = 0.5 * sum;
-            }
+            GPT_TRY(hpart.fetch(st, dpart));
+            for (int q = 0; q < cnt; q++) out[where[b0 + q]] = 0.5 * hpart.sum(q);
             if (!have_trace) {
-                double sum = 0.0;
-                for (int b = 0; b < nblk; b++) sum += hpart[(size_t)b * (GPT_GRAD_MAXH + 1) + GPT_GRAD_MAXH];
-                out[nh] = 0.5 * sum;
+                out[nh] = 0.5 * hpart.sum(GPT_GRAD_MAXH);
                 have_trace = true;
             }
             if (cnt <= 0) break;
@@ -455,33 +470,9 @@ static int grad_diff_run(gpt_ctx *c, const char *who, int nh, const int *term_id
     }
     if (nh < 0 || (nh > 0 && (!term_idx || !params_a || !params_b || !denom)) || !out) return GPT_E_ARG;
     const ModelKernel &m = c->model;
-    // the stencil points, term by term (the parameters of one launch belong to one term): kp1 / kp2 hold [a, b] per parameter in
-    // launch order, where[] the caller's index of each
-    std::vector<KParams> kp1, kp2;
-    std::vector<int> where, term_of;
-    std::vector<size_t> off((size_t)nh + 1, 0);
-    for (int h = 0; h < nh; h++) {
-        if (term_idx[h] < 0 || term_idx[h] >= m.nterms) return GPT_E_ARG;
-        if (!(denom[h] != 0.0) || std::isinf(denom[h])) {
-            gpt_set_error("%s: denom[%d] = %g", who, h, denom[h]);
-            return GPT_E_ARG;
-        }
-        off[h + 1] = off[h] + (size_t)m.np[term_idx[h]];
-    }
-    for (int t = 0; t < m.nterms; t++)
-        for (int h = 0; h < nh; h++) {
-            if (term_idx[h] != t) continue;
-            const bool prod = m.abi_id2[t] >= 0;
-            for (const double *p : {params_a + off[h], params_b + off[h]}) {
-                ModelKernel one;
-                GPT_TRY(parse_model(c->D, c->n_maxsum, c->n_colmax, 1, &m.abi_id1[t], prod ? &m.abi_id2[t] : nullptr, p, &m.np[t],
-                                    prod ? &m.np1[t] : nullptr, &one));
-                kp1.push_back(one.f1[0]);
-                kp2.push_back(one.f2[0]);
-            }
-            where.push_back(h);
-            term_of.push_back(t);
-        }
+    GradStencil gs;
+    GPT_TRY(grad_stencil_build(who, c->D, c->n_maxsum, c->n_colmax, m, nh, term_idx, params_a, params_b, denom, &gs));
+    const std::vector<KParams> &kp1 = gs.kp1, &kp2 = gs.kp2;
     hipStream_t st = c->panel_stream;
     GradTimer timer;
     GPT_TRY(timer.init());
@@ -499,7 +490,8 @@ static int grad_diff_run(gpt_ctx *c, const char *who, int nh, const int *term_id
     const int nblk = grad_reduce_blocks(gw.Np);
     double *dpart;
     KParams *dkp;
-    GPT_TRY(ensure(c, SLOT_GPART, (size_t)nblk * (GPT_GRAD_MAXH + 1) * sizeof(double), (void **)&dpart));
+    GradPartials hpart(nblk);
+    GPT_TRY(ensure(c, SLOT_GPART, hpart.bytes(), (void **)&dpart));
     const size_t nk = kp1.size() > 0 ? kp1.size() : 1;      // (nh == 0: one launch for the trace, which reads no KParams)
     GPT_TRY(ensure(c, SLOT_GKP, 2 * nk * sizeof(KParams), (void **)&dkp));
     if (!kp1.empty()) {
@@ -507,32 +499,21 @@ static int grad_diff_run(gpt_ctx *c, const char *who, int nh, const int *term_id
         GPT_HIP_CHECK(hipMemcpyAsync(dkp + nk, kp2.data(), kp2.size() * sizeof(KParams), hipMemcpyHostToDevice, st));
         GPT_HIP_CHECK(hipStreamSynchronize(st));      // (pageable sources: the vectors may not change before the copies are through)
     }
-    std::vector<double> hpart((size_t)nblk * (GPT_GRAD_MAXH + 1));
+    // one launch group: its entries, and the noise trace from the first one
     bool have_trace = false;
-    const int total = (int)where.size();
-    for (int b0 = 0; b0 < total || !have_trace;) {
-        // the parameters [b0, b0 + cnt): one term, GPT_GRAD_MAXH at most
-        const int t = b0 < total ? term_of[b0] : 0;
-        int cnt = 0;
-        while (b0 + cnt < total && cnt < GPT_GRAD_MAXH && term_of[b0 + cnt] == t) cnt++;
+    auto group = [&](int b0, int cnt, int t) -> int {
         GPT_TRY(launch_kgrad_diff(st, m.f1[t].kernel_id, m.second(t) ? m.f2[t].kernel_id : -1, c->D, dkp + 2 * b0, dkp + nk + 2 * b0, cnt,
                                   c->dX, c->dn, gw.Np, gw.ap, pw, gw.ldwp, dpart, 1, pu));
-        GPT_HIP_CHECK(hipMemcpyAsync(hpart.data(), dpart, hpart.size() * sizeof(double), hipMemcpyDeviceToHost, st));
-        GPT_HIP_CHECK(hipStreamSynchronize(st));
-        for (int q = 0; q < cnt; q++) {
-            double sum = 0.0;
-            for (int b = 0; b < nblk; b++) sum += hpart[(size_t)b * (GPT_GRAD_MAXH + 1) + q];
-            out[where[b0 + q]] = 0.5 * sum / denom[where[b0 + q]];
-        }
+        GPT_TRY(hpart.fetch(st, dpart));
+        for (int q = 0; q < cnt; q++) out[gs.where[b0 + q]] = 0.5 * hpart.sum(q) / denom[gs.where[b0 + q]];
         if (!have_trace) {
-            double sum = 0.0;
-            for (int b = 0; b < nblk; b++) sum += hpart[(size_t)b * (GPT_GRAD_MAXH + 1) + GPT_GRAD_MAXH];
-            out[nh] = 0.5 * sum;
+            out[nh] = 0.5 * hpart.sum(GPT_GRAD_MAXH);
             have_trace = true;
         }
-        b0 += cnt;
-        if (cnt <= 0) break;
-    }
+        return GPT_OK;
+    };
+    GPT_TRY(for_each_group(gs, group));
+    if (!have_trace) GPT_TRY(group(0, 0, 0));                 // (nh == 0: one launch for the trace alone)
     if (c->dT) GPT_TRY(grad_noise_trace_T(c, st, gw.W, dpart, &out[nh]));
     if (loo) GPT_TRY(loo_read_back(c, st, ld, *loo));
     if (timer.on) GPT_TRY(grad_timing_report(who, c->N, st, timer.ge));

@@ -54,26 +54,17 @@ extern "C" int gpt_ll_grad_diff_batch(gpt_ctx *c, int nh, const int *term_idx, c
     const int64_t N = c->rb_N, NP = round_up(N + 1, 128), nleaf = NP / 128, bs = NP * NP, bws = nleaf * GPT_WS_BLOCK;
     const double qnan = NAN;
     // the entries term by term, GPT_GRAD_MAXH of one term to a launch group (nh == 0: one group for the trace, which reads no KParams)
-    std::vector<int> where, term_of;
-    std::vector<size_t> off((size_t)nh + 1, 0);
-    for (int h = 0; h < nh; h++) {
-        if (term_idx[h] < 0 || term_idx[h] >= m.nterms) return GPT_E_ARG;
-        off[h + 1] = off[h] + (size_t)m.np[term_idx[h]];
-    }
-    for (int t = 0; t < m.nterms; t++)
-        for (int h = 0; h < nh; h++)
-            if (term_idx[h] == t) {
-                where.push_back(h);
-                term_of.push_back(t);
-            }
+    // (the steps are the elements' own, denom[b][h]: checked below, element by element, as the stencil points are parsed)
+    GradStencil gs;
+    GPT_TRY(grad_stencil_layout("gpt_ll_grad_diff_batch", m, nh, term_idx, nullptr, &gs));
+    const std::vector<int> &where = gs.where, &term_of = gs.term_of;
+    const std::vector<size_t> &off = gs.off;
     struct Group { int first, cnt, term; };
     std::vector<Group> groups;
-    for (int b0 = 0; b0 < nh;) {
-        int cnt = 0;
-        while (b0 + cnt < nh && cnt < GPT_GRAD_MAXH && term_of[b0 + cnt] == term_of[b0]) cnt++;
-        groups.push_back(Group{b0, cnt, term_of[b0]});
-        b0 += cnt;
-    }
+    for_each_group(gs, [&](int b0, int cnt, int t) {
+        groups.push_back(Group{b0, cnt, t});
+        return GPT_OK;
+    });
     if (groups.empty()) groups.push_back(Group{0, 0, 0});
     std::vector<int> group_of((size_t)nh, 0);
     std::vector<int32_t> src((size_t)round_up(nout, 2), 0);
@@ -102,15 +93,12 @@ extern "C" int gpt_ll_grad_diff_batch(gpt_ctx *c, int nh, const int *term_idx, c
                 gpt_set_error("gpt_ll_grad_diff_batch: denom[%d][%d] = %g", b, h, dn);
                 return GPT_E_ARG;
             }
-            const bool prod = m.abi_id2[t] >= 0;
-            int s = 0;
-            for (const double *p : {params_a + (size_t)b * off[nh] + off[h], params_b + (size_t)b * off[nh] + off[h]}) {
-                ModelKernel one;
-                GPT_TRY(parse_model(c->D, c->n_maxsum, c->n_colmax, 1, &m.abi_id1[t], prod ? &m.abi_id2[t] : nullptr, p, &m.np[t],
-                                    prod ? &m.np1[t] : nullptr, &one));
-                kp[at(b, idx, s)] = one.f1[0];
-                if (m.any_prod) kp[nk + at(b, idx, s)] = one.f2[0];
-                s++;
+            KParams f1[2], f2[2];
+            const size_t o = (size_t)b * off[nh] + off[h];
+            GPT_TRY(grad_stencil_entry(c->D, c->n_maxsum, c->n_colmax, m, t, params_a + o, params_b + o, f1, f2));
+            for (int s = 0; s < 2; s++) {
+                kp[at(b, idx, s)] = f1[s];
+                if (m.any_prod) kp[nk + at(b, idx, s)] = f2[s];
             }
         }
     }

@@ -1,6 +1,6 @@
 // api_sparse.inc -- part of api.hip (ONE translation unit: included from there, in this order; the parts share struct gpt_ctx and
 // static helpers).  Inducing-point approximations (FITC / VFE / DTC; DESIGN.md section 18): gpt_sparse_set_inducing, gpt_sparse_fit,
-// gpt_sparse_predict, gpt_sparse_get_c, gpt_dev_sparse_gram / _lambda / _rowsum / _var / _assemble_b.
+// gpt_sparse_predict, gpt_sparse_get_c, gpt_dev_sparse_gram / _gram2 / _lambda / _rowsum / _var / _assemble_b.
 // ------------------------------------------------------------------------------------------------
 // Layout.  M inducing points.  MPU = M rounded up to 128 is the order of the factored K_uu + jitter I (unit diagonal on the padding
 // rows, so the padding columns of V^T = K_fu L_u^-T stay zero).  BP = (M + 1) rounded up to 128 is the order of the AUGMENTED B: rows
@@ -50,7 +50,7 @@ static int sparse_chunk(const SparseDims &d, int64_t chunk_rows, int64_t n, int6
 static int sparse_slices(gpt_ctx *c, int64_t mg, int64_t rows, int *out)
 {
     if (c->sp_ncu <= 0) GPT_HIP_CHECK(hipDeviceGetAttribute(&c->sp_ncu, hipDeviceAttributeMultiprocessorCount, c->device));
-    const int64_t nt = mg / 64, ntiles = nt * (nt + 1) / 2;
+    const int64_t ntiles = sparse_gram_tiles(mg);
     int64_t s = (6 * (int64_t)c->sp_ncu + ntiles / 2) / ntiles;
     if (s > (rows + 3) / 4) s = (rows + 3) / 4;
     if (s < 1) s = 1;
@@ -83,6 +83,45 @@ static int sparse_refusals(const gpt_ctx *c, const char *who, bool need_fit)
 
 static double *sparse_Z(const gpt_ctx *c) { return (double *)c->slots[SLOT_SP_Z].p; }
 static int32_t *sparse_nZ(const gpt_ctx *c) { return reinterpret_cast<int32_t *>(sparse_Z(c) + c->sp_M * c->D); }
+
+// The resident state of a sparse fit as pointers: SLOT_SP_LU holds L_u (MPU x MPU) and behind it the packed workspaces of its leaves,
+// SLOT_SP_LB L_B (BP x BP), its workspaces and c (M); SLOT_SP_Z the inducing inputs and their derivative orders.  The fit writes
+// through these pointers (after it has sized the slots), every other entry point only reads.
+struct SparseResident {
+    SparseDims d;
+    double *Lu, *ws_u, *Lb, *ws_b, *c;
+    const double *Z;
+    const int32_t *nZ;
+};
+
+static SparseResident sparse_resident(const gpt_ctx *c)
+{
+    SparseResident r;
+    r.d = sparse_dims(c->sp_M);
+    r.Lu = (double *)c->slots[SLOT_SP_LU].p;
+    r.ws_u = r.Lu + r.d.MPU * r.d.MPU;
+    r.Lb = (double *)c->slots[SLOT_SP_LB].p;
+    r.ws_b = r.Lb + r.d.BP * r.d.BP;
+    r.c = r.ws_b + (r.d.BP / 128) * GPT_WS_BLOCK;
+    r.Z = sparse_Z(c);
+    r.nZ = sparse_nZ(c);
+    return r;
+}
+
+// y and err_y of the N training points into SLOT_SP_Y, [y | err_y], on `st` (pageable sources: the caller synchronises before it returns)
+static int sparse_upload_y(gpt_ctx *c, hipStream_t st, const double *y, const double *err_y, int64_t N, double **dY)
+{
+    GPT_TRY(ensure(c, SLOT_SP_Y, (size_t)2 * N * sizeof(double), (void **)dY));
+    GPT_HIP_CHECK(hipMemcpyAsync(*dY, y, (size_t)N * sizeof(double), hipMemcpyHostToDevice, st));
+    GPT_HIP_CHECK(hipMemcpyAsync(*dY + N, err_y, (size_t)N * sizeof(double), hipMemcpyHostToDevice, st));
+    return GPT_OK;
+}
+
+// The workspace of a Gram of order mg in nslices slices: one 64 x 64 partial tile per (slice, lower tile)
+static int sparse_part(gpt_ctx *c, int nslices, int64_t mg, double **dPart)
+{
+    return ensure(c, SLOT_SP_PART, (size_t)nslices * sparse_gram_tiles(mg) * 4096 * sizeof(double), (void **)dPart);
+}
 
 extern "C" int gpt_sparse_set_inducing(gpt_ctx *c, const double *Z, const int32_t *nZ, int64_t M)
 {
@@ -149,6 +188,31 @@ static int sparse_kdiag(hipStream_t st, const ModelKernel &model, const double *
     return GPT_OK;
 }
 
+// The front end of one chunk of `rows` points (dXc, dnc), as the fit, the prediction and the gradient run it: V^T = K_fu L_u^-T into dV
+// (rows rounded up to 64, x LDV) and, with dW given, W^T = V^T L_B^-T into dW.  L_B is the augmented factor: column M of W comes out
+// as -(w.c) / 1e150 and the columns behind it stay zero; only the columns < M are read.  Enqueues on `st` and nothing else: no
+// synchronisation, no allocation.  mark(0) after the build, mark(1) after the solve by L_u: the fit's phase marks.
+template <class Mark>
+static int sparse_chunk_vw(gpt_ctx *c, hipStream_t st, const ModelKernel &model, const SparseResident &r, const double *dXc, const int32_t *dnc,
+                           int64_t rows, double *dV, double *dW, Mark &&mark)
+{
+    const int64_t CP = round_up(rows, 64), LDV = r.d.LDV;
+    GPT_TRY(launch_zero2d(st, CP, LDV, dV, LDV));
+    GPT_TRY(kbuild_terms(st, model, 0, dXc, dnc, rows, r.Z, r.nZ, r.d.M, 0, 0, 0, nullptr, 0.0, 0.0, dV, LDV));
+    GPT_TRY(mark(0));
+    GPT_TRY(trsm_rlt(c, st, CP, r.d.MPU, r.Lu, r.d.MPU, r.ws_u, dV, LDV));
+    GPT_TRY(mark(1));
+    if (!dW) return GPT_OK;
+    GPT_TRY(launch_copy2d(st, CP, LDV, dV, LDV, dW, LDV));
+    return trsm_rlt(c, st, CP, r.d.BP, r.Lb, r.d.BP, r.ws_b, dW, LDV);
+}
+
+static int sparse_chunk_vw(gpt_ctx *c, hipStream_t st, const ModelKernel &model, const SparseResident &r, const double *dXc, const int32_t *dnc,
+                           int64_t rows, double *dV, double *dW)
+{
+    return sparse_chunk_vw(c, st, model, r, dXc, dnc, rows, dV, dW, [](int) { return GPT_OK; });
+}
+
 extern "C" int gpt_sparse_fit(gpt_ctx *c, int method, int nterms, const int *kernel_ids, const int *kernel_ids2, const double *params,
                               const int *nparams, const int *nparams1, double noise_var, const double *y, const double *err_y,
                               double jitter, int64_t chunk_rows, double *ll_out, double *parts_out)
@@ -183,24 +247,20 @@ extern "C" int gpt_sparse_fit(gpt_ctx *c, int method, int nterms, const int *ker
     }
     int nslices;
     GPT_TRY(sparse_slices(c, MG, chunk < N ? chunk : N, &nslices));
-    const int64_t ntiles = (MG / 64) * (MG / 64 + 1) / 2;
     hipStream_t st = c->stream;
     double *dLu, *dLb, *dV, *dG, *dPart, *dMisc, *dY;
     GPT_TRY(ensure(c, SLOT_SP_LU, ((size_t)MPU * MPU + (size_t)(MPU / 128) * GPT_WS_BLOCK) * sizeof(double), (void **)&dLu));
     GPT_TRY(ensure(c, SLOT_SP_LB, ((size_t)BP * BP + (size_t)(BP / 128) * GPT_WS_BLOCK + BP) * sizeof(double), (void **)&dLb));
     GPT_TRY(ensure(c, SLOT_SP_V, (size_t)chunk * LDV * sizeof(double), (void **)&dV));
     GPT_TRY(ensure(c, SLOT_SP_G, (size_t)MG * MG * sizeof(double), (void **)&dG));
-    GPT_TRY(ensure(c, SLOT_SP_PART, (size_t)nslices * ntiles * 4096 * sizeof(double), (void **)&dPart));
+    GPT_TRY(sparse_part(c, nslices, MG, &dPart));
     // misc: [0, 8) the running sums (0: sum log Lambda, 1: the VFE trace term, 2: r^T Lambda^-1 r as the Gram left it);
     // [8, 16) three 32-bit words: info of K_uu, info of B, "a Lambda_i was not positive"; then k(x_i, x_i), the two per-row values
     // (chunk each) and MPU zeros (the err of K_uu's diagonal epilogue)
     GPT_TRY(ensure(c, SLOT_SP_MISC, (size_t)(16 + 3 * chunk + MPU) * sizeof(double), (void **)&dMisc));
-    GPT_TRY(ensure(c, SLOT_SP_Y, (size_t)2 * N * sizeof(double), (void **)&dY));
-    double *ws_u = dLu + MPU * MPU, *ws_b = dLb + BP * BP, *d_c = ws_b + (BP / 128) * GPT_WS_BLOCK;
+    const SparseResident res = sparse_resident(c);                   // (after the slots are sized: the fit writes through it)
     int32_t *d_words = reinterpret_cast<int32_t *>(dMisc + 8);
     double *dkd = dMisc + 16, *drow = dkd + chunk, *dzero = drow + 2 * chunk;
-    const double *dZ = sparse_Z(c);
-    const int32_t *dnZ = sparse_nZ(c);
     EvalScope scope(c, true);                                        // counted like an evaluation in flight, on event edges
     // phase timing (option "timing"): events at the phase boundaries of every chunk, summed after the fit into gpt_last_timings:
     // [0] K_fu build, [1] right-side solve, [2] the row pass (k_i, Lambda, scaling, sums), [3] the Gram, [4] the two factorisations
@@ -219,15 +279,14 @@ extern "C" int gpt_sparse_fit(gpt_ctx *c, int method, int nterms, const int *ker
         nev++;
         return GPT_OK;
     };
-    GPT_HIP_CHECK(hipMemcpyAsync(dY, y, (size_t)N * sizeof(double), hipMemcpyHostToDevice, st));
-    GPT_HIP_CHECK(hipMemcpyAsync(dY + N, err_y, (size_t)N * sizeof(double), hipMemcpyHostToDevice, st));
+    GPT_TRY(sparse_upload_y(c, st, y, err_y, N, &dY));
     GPT_HIP_CHECK(hipMemsetAsync(dMisc, 0, (size_t)(16 + 3 * chunk + MPU) * sizeof(double), st));
     // ---- L_u = chol(k(Z, Z) + jitter I)
     GPT_TRY(mark(-1));
     GPT_TRY(launch_zero2d(st, MPU, MPU, dLu, MPU));
-    GPT_TRY(kbuild_terms(st, model, 1, dZ, dnZ, M, dZ, dnZ, M, 1, 0, 0, dzero, 0.0, jitter, dLu, MPU));
+    GPT_TRY(kbuild_terms(st, model, 1, res.Z, res.nZ, M, res.Z, res.nZ, M, 1, 0, 0, dzero, 0.0, jitter, dLu, MPU));
     GPT_TRY(launch_fill_pad(st, dLu, MPU, M, MPU, nullptr, 0.0));      // unit diagonal on the padding rows
-    GPT_TRY(potrf_run(c, MPU, dLu, MPU, ws_u, d_words + 0));
+    GPT_TRY(potrf_run(c, MPU, dLu, MPU, res.ws_u, d_words + 0));
     GPT_TRY(mark(4));
     GPT_HIP_CHECK(hipMemcpyAsync(c->h_info, d_words + 0, sizeof(int32_t), hipMemcpyDeviceToHost, st));
     GPT_HIP_CHECK(hipStreamSynchronize(st));
@@ -239,29 +298,25 @@ extern "C" int gpt_sparse_fit(gpt_ctx *c, int method, int nterms, const int *ker
     // ---- the chunks, in ascending order
     GPT_TRY(launch_zero2d(st, MG, MG, dG, MG));
     for (int64_t r0 = 0; r0 < N; r0 += chunk) {
-        const int64_t rows = (N - r0 < chunk) ? N - r0 : chunk, CP = round_up(rows, 64);
+        const int64_t rows = (N - r0 < chunk) ? N - r0 : chunk;
         const double *dXc = c->dX + r0 * D;
         const int32_t *dnc = c->dn + r0 * D;
         GPT_TRY(mark(-1));
-        GPT_TRY(launch_zero2d(st, CP, LDV, dV, LDV));
-        GPT_TRY(kbuild_terms(st, model, 0, dXc, dnc, rows, dZ, dnZ, M, 0, 0, 0, nullptr, 0.0, 0.0, dV, LDV));
-        GPT_TRY(mark(0));
-        GPT_TRY(trsm_rlt(c, st, CP, MPU, dLu, MPU, ws_u, dV, LDV));
-        GPT_TRY(mark(1));
+        GPT_TRY(sparse_chunk_vw(c, st, model, res, dXc, dnc, rows, dV, nullptr, mark));
         if (method != GPT_SPARSE_DTC) GPT_TRY(sparse_kdiag(st, model, dXc, dnc, rows, dkd));
         GPT_TRY(launch_sparse_lambda(st, dV, LDV, rows, M, method, dkd, dY + r0, dY + N + r0, noise_var, drow, chunk, d_words + 2));
         GPT_TRY(launch_sparse_rowsum(st, drow, chunk, rows, dMisc));
         GPT_TRY(mark(2));
-        GPT_TRY(launch_sparse_gram(st, dV, LDV, rows, MG, nslices, dPart, dG, MG));
+        GPT_TRY(launch_sparse_gram(st, nullptr, dV, LDV, rows, MG, nslices, dPart, dG, MG));
         GPT_TRY(mark(3));
     }
     // ---- B = I + G, augmented; L_B, c
     GPT_TRY(mark(-1));
     GPT_TRY(launch_sparse_assemble_b(st, dG, MG, M, dLb, BP, 1e300));
-    GPT_TRY(potrf_run(c, BP, dLb, BP, ws_b, d_words + 1));
+    GPT_TRY(potrf_run(c, BP, dLb, BP, res.ws_b, d_words + 1));
     GPT_TRY(mark(4));
     GPT_TRY(launch_logdet_dot(st, dLb, BP, M, d_words + 1, c->d_scal, c->h_scal));
-    GPT_TRY(launch_copy2d(st, 1, M, dLb + M * BP, BP, d_c, M));
+    GPT_TRY(launch_copy2d(st, 1, M, dLb + M * BP, BP, res.c, M));
     GPT_TRY(launch_copy2d(st, 1, 1, dG + M * MG + M, MG, dMisc + 2, 1));
     double sums[3];
     int32_t words[3];
@@ -316,9 +371,8 @@ extern "C" int gpt_sparse_get_c(gpt_ctx *c, double *c_out)
     CTX_ENTER(c);
     GPT_TRY(sparse_refusals(c, "gpt_sparse_get_c", true));
     if (!c_out) return GPT_E_ARG;
-    const SparseDims sd = sparse_dims(c->sp_M);
-    const double *d_c = (const double *)c->slots[SLOT_SP_LB].p + sd.BP * sd.BP + (sd.BP / 128) * GPT_WS_BLOCK;
-    GPT_HIP_CHECK(hipMemcpyAsync(c_out, d_c, (size_t)sd.M * sizeof(double), hipMemcpyDeviceToHost, c->stream));
+    const SparseResident res = sparse_resident(c);
+    GPT_HIP_CHECK(hipMemcpyAsync(c_out, res.c, (size_t)res.d.M * sizeof(double), hipMemcpyDeviceToHost, c->stream));
     GPT_HIP_CHECK(hipStreamSynchronize(c->stream));
     return GPT_OK;
 }
@@ -343,16 +397,12 @@ extern "C" int gpt_sparse_predict(gpt_ctx *c, const double *Xstar, const int32_t
     long maxsum, colmax[GPT_MAX_DIM];
     sparse_order_bounds(c, &maxsum, colmax);
     GPT_TRY(check_test_orders(model, maxsum, colmax, false, nstar, Ms, D));
-    const SparseDims sd = sparse_dims(c->sp_M);
-    const int64_t M = sd.M, MPU = sd.MPU, BP = sd.BP, LDV = sd.LDV;
+    const SparseResident res = sparse_resident(c);
+    const int64_t M = res.d.M, MPU = res.d.MPU, LDV = res.d.LDV;
     int64_t chunk;
-    GPT_TRY(sparse_chunk(sd, c->sp_chunk_rows, Ms, &chunk));
+    GPT_TRY(sparse_chunk(res.d, c->sp_chunk_rows, Ms, &chunk));
     if (want == 2) chunk = round_up(Ms, 64);
     hipStream_t st = c->stream;
-    const double *dLu = (const double *)c->slots[SLOT_SP_LU].p, *dLb = (const double *)c->slots[SLOT_SP_LB].p;
-    const double *ws_u = dLu + MPU * MPU, *ws_b = dLb + BP * BP, *d_c = ws_b + (BP / 128) * GPT_WS_BLOCK;
-    const double *dZ = sparse_Z(c);
-    const int32_t *dnZ = sparse_nZ(c);
     double *dXs, *dV, *dW, *dvec;
     int32_t *dns;
     GPT_TRY(ensure(c, SLOT_XS, (size_t)Ms * D * sizeof(double), (void **)&dXs));
@@ -366,17 +416,11 @@ extern "C" int gpt_sparse_predict(gpt_ctx *c, const double *Xstar, const int32_t
     KParams kn;
     if (noise_params) GPT_TRY(make_kparams(GPT_KERNEL_DIAGNOISE, noise_params, 1, D, -1, 1, noise_n, &kn));
     for (int64_t r0 = 0; r0 < Ms; r0 += chunk) {
-        const int64_t rows = (Ms - r0 < chunk) ? Ms - r0 : chunk, CP = round_up(rows, 64);
+        const int64_t rows = (Ms - r0 < chunk) ? Ms - r0 : chunk;
         const double *dXc = dXs + r0 * D;
         const int32_t *dnc = dns + r0 * D;
-        GPT_TRY(launch_zero2d(st, CP, LDV, dV, LDV));
-        GPT_TRY(kbuild_terms(st, model, 0, dXc, dnc, rows, dZ, dnZ, M, 0, 0, 0, nullptr, 0.0, 0.0, dV, LDV));
-        GPT_TRY(trsm_rlt(c, st, CP, MPU, dLu, MPU, ws_u, dV, LDV));
-        GPT_TRY(launch_copy2d(st, CP, LDV, dV, LDV, dW, LDV));
-        // (L_B is the augmented factor: column M of W comes out as -(w.c) / 1e150 and the columns behind it stay zero; only the
-        // columns < M are read below)
-        GPT_TRY(trsm_rlt(c, st, CP, BP, dLb, BP, ws_b, dW, LDV));
-        GPT_TRY(launch_gemv_n(st, rows, M, dW, LDV, d_c, dmean));
+        GPT_TRY(sparse_chunk_vw(c, st, model, res, dXc, dnc, rows, dV, dW));
+        GPT_TRY(launch_gemv_n(st, rows, M, dW, LDV, res.c, dmean));
         GPT_HIP_CHECK(hipMemcpyAsync(mean_out + r0, dmean, (size_t)rows * sizeof(double), hipMemcpyDeviceToHost, st));
         if (want == 1) {
             GPT_TRY(sparse_kdiag(st, model, dXc, dnc, rows, dkd));
@@ -423,20 +467,33 @@ extern "C" int gpt_sparse_predict(gpt_ctx *c, const double *Xstar, const int32_t
 }
 
 // The Gram kernel on raw device pointers (device API, on the context's stream): dG (mg x mg, lower 64 x 64 tiles) += dV^T dV over
-// `rows` rows.  nslices = 0: the fit's own choice.  The partial tiles go to the context's workspace.
-extern "C" int gpt_dev_sparse_gram(gpt_ctx *c, const double *dV, int64_t ldv, int64_t rows, int64_t mg, int nslices, double *dG,
-                                   int64_t ldg)
+// `rows` rows.  nslices = 0: the fit's own choice.  The partial tiles go to the context's workspace.  gpt_dev_sparse_gram2 (the gradient's
+// signed-weight Gram, DESIGN.md 18.8): dG += dA^T dV, both rows x ldv.  One body: `two` says which entry point speaks.
+static int dev_sparse_gram(gpt_ctx *c, bool two, const double *dA, const double *dV, int64_t ldv, int64_t rows, int64_t mg, int nslices,
+                           double *dG, int64_t ldg)
 {
     CTX_ENTER(c);
-    if (!dV || !dG || rows <= 0 || mg <= 0 || mg % 64) {
-        gpt_set_error("gpt_dev_sparse_gram: bad arguments (rows=%lld, order %lld: a positive multiple of 64)", (long long)rows, (long long)mg);
+    if ((two && !dA) || !dV || !dG || rows <= 0 || mg <= 0 || mg % 64) {
+        gpt_set_error("%s: bad arguments (rows=%lld, order %lld: a positive multiple of 64)", two ? "gpt_dev_sparse_gram2" : "gpt_dev_sparse_gram",
+                      (long long)rows, (long long)mg);
         return GPT_E_ARG;
     }
     if (nslices <= 0) GPT_TRY(sparse_slices(c, mg, rows, &nslices));
-    const int64_t ntiles = (mg / 64) * (mg / 64 + 1) / 2;
     double *dPart;
-    GPT_TRY(ensure(c, SLOT_SP_PART, (size_t)nslices * ntiles * 4096 * sizeof(double), (void **)&dPart));
-    return launch_sparse_gram(c->stream, dV, ldv, rows, mg, nslices, dPart, dG, ldg);
+    GPT_TRY(sparse_part(c, nslices, mg, &dPart));
+    return launch_sparse_gram(c->stream, two ? dA : nullptr, dV, ldv, rows, mg, nslices, dPart, dG, ldg);
+}
+
+extern "C" int gpt_dev_sparse_gram(gpt_ctx *c, const double *dV, int64_t ldv, int64_t rows, int64_t mg, int nslices, double *dG,
+                                   int64_t ldg)
+{
+    return dev_sparse_gram(c, false, nullptr, dV, ldv, rows, mg, nslices, dG, ldg);
+}
+
+extern "C" int gpt_dev_sparse_gram2(gpt_ctx *c, const double *dA, const double *dV, int64_t ldv, int64_t rows, int64_t mg, int nslices,
+                                    double *dG, int64_t ldg)
+{
+    return dev_sparse_gram(c, true, dA, dV, ldv, rows, mg, nslices, dG, ldg);
 }
 
 // The four other kernels of ksparse.hip on raw device pointers (device API, on the context's stream): one launcher each, nothing

@@ -1,6 +1,8 @@
 // api_sparse_grad.inc -- part of api.hip (ONE translation unit: included from there, in this order; the parts share struct gpt_ctx and
 // static helpers).  The gradient of the inducing-point objective (DESIGN.md section 18.8): gpt_sparse_grad_diff, and the device API of
-// its kernels, gpt_dev_sparse_grad_rows / _gram2 / _grad_pairs.
+// its kernels, gpt_dev_sparse_grad_rows / _grad_pairs (gpt_dev_sparse_gram2 stands beside gpt_dev_sparse_gram, api_sparse.inc).  The
+// stencil is read by grad_stencil.inc, as for the dense gradients; the chunk front end, the view of the resident factors and the upload
+// of y are api_sparse.inc's, shared with the fit and the prediction.
 // ------------------------------------------------------------------------------------------------
 // With the notation of api_sparse.inc, r = y - mu(X), s_i = noise_var + err_y_i^2:
 //     t = L_B^-T c     beta = L_u^-T t     alpha_i = (r_i - v_i.t) / Lambda_i     w_i = L_B^-1 v_i
@@ -13,38 +15,6 @@
 // One second pass over the chunks of the fit: four chunk x LDV buffers (V^T; W^T, then A_fu in its place; the two scaled copies of
 // V^T), so the size rule gives the gradient half the fit's rows per chunk; device memory stays O(M^2 + chunk M).
 // ------------------------------------------------------------------------------------------------
-
-// The stencil points of nh entries, term by term, as grad_diff_run parses them (api_grad.inc): kp1 / kp2 hold [a, b] per parameter in
-// launch order, where[] the caller's index of each, term_of[] its term
-static int sparse_grad_stencil(const char *who, int D, long maxsum, const long *colmax, const ModelKernel &m, int nh, const int *term_idx,
-                               const double *params_a, const double *params_b, const double *denom, std::vector<KParams> *kp1,
-                               std::vector<KParams> *kp2, std::vector<int> *where, std::vector<int> *term_of)
-{
-    std::vector<size_t> off((size_t)nh + 1, 0);
-    for (int h = 0; h < nh; h++) {
-        if (term_idx[h] < 0 || term_idx[h] >= m.nterms) return GPT_E_ARG;
-        if (!(denom[h] != 0.0) || std::isinf(denom[h])) {
-            gpt_set_error("%s: denom[%d] = %g", who, h, denom[h]);
-            return GPT_E_ARG;
-        }
-        off[h + 1] = off[h] + (size_t)m.np[term_idx[h]];
-    }
-    for (int t = 0; t < m.nterms; t++)
-        for (int h = 0; h < nh; h++) {
-            if (term_idx[h] != t) continue;
-            const bool prod = m.abi_id2[t] >= 0;
-            for (const double *p : {params_a + off[h], params_b + off[h]}) {
-                ModelKernel one;
-                GPT_TRY(parse_model(D, maxsum, colmax, 1, &m.abi_id1[t], prod ? &m.abi_id2[t] : nullptr, p, &m.np[t],
-                                    prod ? &m.np1[t] : nullptr, &one));
-                kp1->push_back(one.f1[0]);
-                kp2->push_back(one.f2[0]);
-            }
-            where->push_back(h);
-            term_of->push_back(t);
-        }
-    return GPT_OK;
-}
 
 extern "C" int gpt_sparse_grad_diff(gpt_ctx *c, int nh, const int *term_idx, const double *params_a, const double *params_b,
                                     const double *denom, const double *y, const double *err_y, double *out, double *alpha_out)
@@ -60,23 +30,20 @@ extern "C" int gpt_sparse_grad_diff(gpt_ctx *c, int nh, const int *term_idx, con
     const int64_t N = c->Nx;
     long maxsum, colmax[GPT_MAX_DIM];
     sparse_order_bounds(c, &maxsum, colmax);
-    std::vector<KParams> kp1, kp2;
-    std::vector<int> where, term_of;
-    GPT_TRY(sparse_grad_stencil("gpt_sparse_grad_diff", D, maxsum, colmax, model, nh, term_idx, params_a, params_b, denom, &kp1, &kp2, &where,
-                                &term_of));
+    GradStencil gs;
+    GPT_TRY(grad_stencil_build("gpt_sparse_grad_diff", D, maxsum, colmax, model, nh, term_idx, params_a, params_b, denom, &gs));
+    const std::vector<KParams> &kp1 = gs.kp1, &kp2 = gs.kp2;
+    const std::vector<int> &where = gs.where;
     const int total = (int)where.size();
-    const SparseDims sd = sparse_dims(c->sp_M);
-    const int64_t M = sd.M, MPU = sd.MPU, BP = sd.BP, LDV = sd.LDV, ME = round_up(M, 64);
+    const SparseResident res = sparse_resident(c);
+    const int64_t M = res.d.M, MPU = res.d.MPU, BP = res.d.BP, LDV = res.d.LDV, ME = round_up(M, 64);
     int64_t chunk;
-    GPT_TRY(sparse_chunk(sd, c->sp_chunk_rows, N, &chunk, 4));
+    GPT_TRY(sparse_chunk(res.d, c->sp_chunk_rows, N, &chunk, 4));
     int nslices = 1;
     if (method == GPT_SPARSE_FITC) GPT_TRY(sparse_slices(c, ME, chunk < N ? chunk : N, &nslices));
-    const int64_t ntiles = (ME / 64) * (ME / 64 + 1) / 2;
     hipStream_t st = c->stream;
-    const double *dLu = (const double *)c->slots[SLOT_SP_LU].p, *dLb = (const double *)c->slots[SLOT_SP_LB].p;
-    const double *ws_u = dLu + MPU * MPU, *ws_b = dLb + BP * BP, *d_c = ws_b + (BP / 128) * GPT_WS_BLOCK;
-    const double *dZ = sparse_Z(c);
-    const int32_t *dnZ = sparse_nZ(c);
+    const double *dLu = res.Lu, *dLb = res.Lb, *ws_u = res.ws_u, *ws_b = res.ws_b, *d_c = res.c, *dZ = res.Z;
+    const int32_t *dnZ = res.nZ;
     double *dV, *dW, *dS1, *dS2, *dGM, *dvec, *dY, *dPart = nullptr, *dpart = nullptr, *dzz = nullptr;
     KParams *dkp = nullptr;
     GPT_TRY(ensure(c, SLOT_SP_V, (size_t)chunk * LDV * sizeof(double), (void **)&dV));
@@ -94,21 +61,18 @@ extern "C" int gpt_sparse_grad_diff(gpt_ctx *c, int nh, const int *term_idx, con
     double *dsum = dvec, *dacc = dvec + 4, *dt = dacc + nacc, *dbeta = dt + MPU, *dkd = dvec + head, *dalpha = dkd + chunk, *de = dalpha + chunk,
            *dgval = de + chunk;
     int32_t *d_bad = reinterpret_cast<int32_t *>(dvec + 2);
-    GPT_TRY(ensure(c, SLOT_SP_Y, (size_t)2 * N * sizeof(double), (void **)&dY));
-    const int nblk_zz = grad_reduce_blocks(M);
+    GradPartials hzz(grad_reduce_blocks(M));
     if (total > 0) {
         const int64_t nblk = kgrad_rect_blocks(chunk < N ? chunk : N, M);
         GPT_TRY(ensure(c, SLOT_SP_GPART, (size_t)nblk * GPT_GRAD_MAXH * sizeof(double), (void **)&dpart));
-        GPT_TRY(ensure(c, SLOT_GPART, (size_t)nblk_zz * (GPT_GRAD_MAXH + 1) * sizeof(double), (void **)&dzz));
+        GPT_TRY(ensure(c, SLOT_GPART, hzz.bytes(), (void **)&dzz));
         GPT_TRY(ensure(c, SLOT_GKP, 2 * kp1.size() * sizeof(KParams), (void **)&dkp));
-        if (method == GPT_SPARSE_FITC)
-            GPT_TRY(ensure(c, SLOT_SP_PART, (size_t)nslices * ntiles * 4096 * sizeof(double), (void **)&dPart));
+        if (method == GPT_SPARSE_FITC) GPT_TRY(sparse_part(c, nslices, ME, &dPart));
         GPT_HIP_CHECK(hipMemcpyAsync(dkp, kp1.data(), kp1.size() * sizeof(KParams), hipMemcpyHostToDevice, st));
         GPT_HIP_CHECK(hipMemcpyAsync(dkp + kp1.size(), kp2.data(), kp2.size() * sizeof(KParams), hipMemcpyHostToDevice, st));
     }
     const KParams *dkp2 = dkp ? dkp + kp1.size() : nullptr;
-    GPT_HIP_CHECK(hipMemcpyAsync(dY, y, (size_t)N * sizeof(double), hipMemcpyHostToDevice, st));
-    GPT_HIP_CHECK(hipMemcpyAsync(dY + N, err_y, (size_t)N * sizeof(double), hipMemcpyHostToDevice, st));
+    GPT_TRY(sparse_upload_y(c, st, y, err_y, N, &dY));
     GPT_HIP_CHECK(hipMemsetAsync(dvec, 0, head * sizeof(double), st));
     GPT_HIP_CHECK(hipStreamSynchronize(st));      // (pageable sources: the vectors may not change before the copies are through)
     // ---- once, at order M: U_B = L_B^-T (the identity through the right-side solve, as gpt_dev_trinv), t = U_B c, beta = U_u t
@@ -138,11 +102,7 @@ extern "C" int gpt_sparse_grad_diff(gpt_ctx *c, int nh, const int *term_idx, con
         const int64_t rows = (N - r0 < chunk) ? N - r0 : chunk, CP = round_up(rows, 64);
         const double *dXc = c->dX + r0 * D;
         const int32_t *dnc = c->dn + r0 * D;
-        GPT_TRY(launch_zero2d(st, CP, LDV, dV, LDV));
-        GPT_TRY(kbuild_terms(st, model, 0, dXc, dnc, rows, dZ, dnZ, M, 0, 0, 0, nullptr, 0.0, 0.0, dV, LDV));
-        GPT_TRY(trsm_rlt(c, st, CP, MPU, dLu, MPU, ws_u, dV, LDV));
-        GPT_TRY(launch_copy2d(st, CP, LDV, dV, LDV, dW, LDV));
-        GPT_TRY(trsm_rlt(c, st, CP, BP, dLb, BP, ws_b, dW, LDV));      // (column M: the augmented row's, not read)
+        GPT_TRY(sparse_chunk_vw(c, st, model, res, dXc, dnc, rows, dV, dW));
         if (method != GPT_SPARSE_DTC) GPT_TRY(sparse_kdiag(st, model, dXc, dnc, rows, dkd));
         GPT_TRY(launch_sparse_grad_rows(st, dV, dW, LDV, rows, M, method, dkd, dY + r0, dY + N + r0, c->sp_noise_var, dt, dalpha, de, dgval,
                                         chunk, dS1, dS2, d_bad));
@@ -153,15 +113,11 @@ extern "C" int gpt_sparse_grad_diff(gpt_ctx *c, int nh, const int *term_idx, con
         GPT_TRY(gemm_nt(c, st, CP, MPU, MPU, -1.0, dS1, LDV, P2, MPU, 0.0, dW, LDV, 0));
         if (method != GPT_SPARSE_DTC) GPT_TRY(gemm_nt(c, st, CP, MPU, MPU, -1.0, dS2, LDV, Uu, MPU, 1.0, dW, LDV, 0));
         GPT_TRY(launch_sparse_rank1(st, dW, LDV, rows, M, dalpha, dbeta));
-        for (int b0 = 0; b0 < total;) {
-            const int t = term_of[b0];
-            int cnt = 0;
-            while (b0 + cnt < total && cnt < GPT_GRAD_MAXH && term_of[b0 + cnt] == t) cnt++;
-            GPT_TRY(launch_kgrad_rect_diff(st, model.f1[t].kernel_id, model.second(t) ? model.f2[t].kernel_id : -1, D, dkp + 2 * b0, dkp2 + 2 * b0,
-                                           cnt, dXc, dnc, rows, dZ, dnZ, M, dW, LDV, method != GPT_SPARSE_DTC ? de : nullptr, dpart, dacc + b0));
-            b0 += cnt;
-        }
-        if (method == GPT_SPARSE_FITC) GPT_TRY(launch_sparse_gram2(st, dS2, dV, LDV, rows, ME, nslices, dPart, dE, ME));
+        GPT_TRY(for_each_group(gs, [&](int b0, int cnt, int t) {
+            return launch_kgrad_rect_diff(st, model.f1[t].kernel_id, model.second(t) ? model.f2[t].kernel_id : -1, D, dkp + 2 * b0, dkp2 + 2 * b0,
+                                          cnt, dXc, dnc, rows, dZ, dnZ, M, dW, LDV, method != GPT_SPARSE_DTC ? de : nullptr, dpart, dacc + b0);
+        }));
+        if (method == GPT_SPARSE_FITC) GPT_TRY(launch_sparse_gram(st, dS2, dV, LDV, rows, ME, nslices, dPart, dE, ME));
     }
     std::vector<double> hacc(nacc, 0.0), zz((size_t)total, 0.0);
     if (total > 0) {
@@ -176,22 +132,13 @@ extern "C" int gpt_sparse_grad_diff(gpt_ctx *c, int nh, const int *term_idx, con
         }
         GPT_TRY(gemm_nt(c, st, MPU, MPU, MPU, 1.0, Uu, MPU, T2, MPU, 0.0, T0, MPU, 0));
         GPT_TRY(gemm_nt(c, st, MPU, MPU, MPU, 1.0, T0, MPU, Uu, MPU, 0.0, T1, MPU, 1));
-        std::vector<double> hpart((size_t)nblk_zz * (GPT_GRAD_MAXH + 1));
-        for (int b0 = 0; b0 < total;) {
-            const int t = term_of[b0];
-            int cnt = 0;
-            while (b0 + cnt < total && cnt < GPT_GRAD_MAXH && term_of[b0 + cnt] == t) cnt++;
+        GPT_TRY(for_each_group(gs, [&](int b0, int cnt, int t) -> int {
             GPT_TRY(launch_kgrad_diff(st, model.f1[t].kernel_id, model.second(t) ? model.f2[t].kernel_id : -1, D, dkp + 2 * b0, dkp2 + 2 * b0, cnt,
                                       dZ, dnZ, M, dbeta, T1, MPU, dzz, 1, nullptr));
-            GPT_HIP_CHECK(hipMemcpyAsync(hpart.data(), dzz, hpart.size() * sizeof(double), hipMemcpyDeviceToHost, st));
-            GPT_HIP_CHECK(hipStreamSynchronize(st));
-            for (int q = 0; q < cnt; q++) {
-                double sum = 0.0;
-                for (int b = 0; b < nblk_zz; b++) sum += hpart[(size_t)b * (GPT_GRAD_MAXH + 1) + q];
-                zz[b0 + q] = 0.5 * sum;
-            }
-            b0 += cnt;
-        }
+            GPT_TRY(hzz.fetch(st, dzz));
+            for (int q = 0; q < cnt; q++) zz[b0 + q] = 0.5 * hzz.sum(q);
+            return GPT_OK;
+        }));
         GPT_HIP_CHECK(hipMemcpyAsync(hacc.data(), dacc, (size_t)total * sizeof(double), hipMemcpyDeviceToHost, st));
     }
     double sums[2];
@@ -226,22 +173,6 @@ extern "C" int gpt_dev_sparse_grad_rows(gpt_ctx *c, const double *dV, const doub
                                    dS2, d_bad);
 }
 
-// dG (mg x mg, lower 64 x 64 tiles) += dA^T dV over `rows` rows (both rows x ldv).  nslices = 0: the fit's own choice.
-extern "C" int gpt_dev_sparse_gram2(gpt_ctx *c, const double *dA, const double *dV, int64_t ldv, int64_t rows, int64_t mg, int nslices,
-                                    double *dG, int64_t ldg)
-{
-    CTX_ENTER(c);
-    if (!dA || !dV || !dG || rows <= 0 || mg <= 0 || mg % 64) {
-        gpt_set_error("gpt_dev_sparse_gram2: bad arguments (rows=%lld, order %lld: a positive multiple of 64)", (long long)rows, (long long)mg);
-        return GPT_E_ARG;
-    }
-    if (nslices <= 0) GPT_TRY(sparse_slices(c, mg, rows, &nslices));
-    const int64_t ntiles = (mg / 64) * (mg / 64 + 1) / 2;
-    double *dPart;
-    GPT_TRY(ensure(c, SLOT_SP_PART, (size_t)nslices * ntiles * 4096 * sizeof(double), (void **)&dPart));
-    return launch_sparse_gram2(c->stream, dA, dV, ldv, rows, mg, nslices, dPart, dG, ldg);
-}
-
 // The rectangular pair pass alone: out[h] = sum_im dA[i][m] (k_b - k_a)(x_i, z_m) + 1/2 sum_i d_e[i] (k_b - k_a)(x_i, x_i), h < nh (any
 // number: GPT_GRAD_MAXH per launch), for ONE term kernel_id (* kernel_id2 where >= 0) of num_dim D with nparams parameters (nparams1 of
 // them the first factor's) at the stencil points params_a / params_b (nh x nparams each, host).  max_order: the largest sum of
@@ -258,15 +189,17 @@ extern "C" int gpt_dev_sparse_grad_pairs(gpt_ctx *c, int kernel_id, int kernel_i
     }
     long colmax[GPT_MAX_DIM];
     for (int d = 0; d < GPT_MAX_DIM; d++) colmax[d] = max_order;
-    std::vector<KParams> kp1, kp2;
-    for (int h = 0; h < nh; h++)
-        for (const double *p : {params_a + (size_t)h * nparams, params_b + (size_t)h * nparams}) {
-            ModelKernel one;
-            GPT_TRY(parse_model(D, max_order, colmax, 1, &kernel_id, kernel_id2 >= 0 ? &kernel_id2 : nullptr, p, &nparams,
-                                kernel_id2 >= 0 ? &nparams1 : nullptr, &one));
-            kp1.push_back(one.f1[0]);
-            kp2.push_back(one.f2[0]);
-        }
+    // nh entries of a model of this one term: no steps to check, and the launch order is the caller's
+    ModelKernel one_term;
+    one_term.nterms = 1;
+    one_term.abi_id1[0] = kernel_id;
+    one_term.abi_id2[0] = kernel_id2;
+    one_term.np[0] = nparams;
+    one_term.np1[0] = nparams1;
+    const std::vector<int> term_idx((size_t)nh, 0);
+    GradStencil gs;
+    GPT_TRY(grad_stencil_build("gpt_dev_sparse_grad_pairs", D, max_order, colmax, one_term, nh, term_idx.data(), params_a, params_b, nullptr, &gs));
+    const std::vector<KParams> &kp1 = gs.kp1, &kp2 = gs.kp2;
     hipStream_t st = c->stream;
     KParams *dkp;
     double *dpart, *dacc;
@@ -279,11 +212,10 @@ extern "C" int gpt_dev_sparse_grad_pairs(gpt_ctx *c, int kernel_id, int kernel_i
     GPT_HIP_CHECK(hipMemsetAsync(dacc, 0, (size_t)nh * sizeof(double), st));
     GPT_HIP_CHECK(hipStreamSynchronize(st));
     const KParams &f1 = kp1[0], &f2 = kp2[0];
-    for (int b0 = 0; b0 < nh; b0 += GPT_GRAD_MAXH) {
-        const int cnt = nh - b0 < GPT_GRAD_MAXH ? nh - b0 : GPT_GRAD_MAXH;
-        GPT_TRY(launch_kgrad_rect_diff(st, f1.kernel_id, f2.kernel_id >= 0 ? f2.kernel_id : -1, D, dkp + 2 * b0, dkp + kp1.size() + 2 * b0, cnt, dX,
-                                       dnx, rows, dZ, dnz, M, dA, lda, d_e, dpart, dacc + b0));
-    }
+    GPT_TRY(for_each_group(gs, [&](int b0, int cnt, int) {
+        return launch_kgrad_rect_diff(st, f1.kernel_id, f2.kernel_id >= 0 ? f2.kernel_id : -1, D, dkp + 2 * b0, dkp + kp1.size() + 2 * b0, cnt, dX,
+                                      dnx, rows, dZ, dnz, M, dA, lda, d_e, dpart, dacc + b0);
+    }));
     GPT_HIP_CHECK(hipMemcpyAsync(out, dacc, (size_t)nh * sizeof(double), hipMemcpyDeviceToHost, st));
     GPT_HIP_CHECK(hipStreamSynchronize(st));
     return GPT_OK;

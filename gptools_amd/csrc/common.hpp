@@ -323,20 +323,21 @@ int launch_row_sumsq(hipStream_t st, const double *row, int64_t w, double *acc);
 int launch_sparse_lambda(hipStream_t st, double *V, int64_t ldv, int64_t rows, int64_t M, int method, const double *kdiag,
                          const double *r, const double *err, double noise_var, double *rowval, int64_t ldr, int32_t *bad);
 int launch_sparse_rowsum(hipStream_t st, const double *rowval, int64_t ldr, int64_t rows, double *acc);
-int launch_sparse_gram(hipStream_t st, const double *V, int64_t ldv, int64_t rows, int64_t mg, int nslices, double *part, double *G,
-                       int64_t ldg);
+// (A == NULL: G += V^T V, the fit's instantiation; else G += A^T V, the gradient's signed-weight Gram)
+int launch_sparse_gram(hipStream_t st, const double *A, const double *V, int64_t ldv, int64_t rows, int64_t mg, int nslices, double *part,
+                       double *G, int64_t ldg);
+// the lower 64 x 64 tiles of a Gram of order mg
+inline int64_t sparse_gram_tiles(int64_t mg) { return (mg / 64) * (mg / 64 + 1) / 2; }
 int launch_sparse_assemble_b(hipStream_t st, const double *G, int64_t ldg, int64_t M, double *B, int64_t bp, double big);
 int launch_sparse_var(hipStream_t st, const double *V, const double *W, int64_t ld, int64_t rows, int64_t M, const double *kdiag,
                       double *var);
-// ... and the gradient of its objective (gpt_sparse_grad_diff): the per-row pass, the rank-one part of A_fu, the
-// two-operand (signed-weight) Gram, L_B without its augmented rows, the middle factor of A_uu (ksparse.hip) and the rectangular pair
+// ... and the gradient of its objective (gpt_sparse_grad_diff): the per-row pass, the rank-one part of A_fu,
+// L_B without its augmented rows, the middle factor of A_uu (ksparse.hip) and the rectangular pair
 // pass with its running sums (kgrad_rect.hip)
 int launch_sparse_grad_rows(hipStream_t st, const double *V, const double *W, int64_t ld, int64_t rows, int64_t M, int method,
                             const double *kdiag, const double *r, const double *err, double noise_var, const double *t, double *alpha,
                             double *e_out, double *gval, int64_t ldr, double *S1, double *S2, int32_t *bad);
 int launch_sparse_rank1(hipStream_t st, double *A, int64_t lda, int64_t rows, int64_t M, const double *alpha, const double *beta);
-int launch_sparse_gram2(hipStream_t st, const double *A, const double *V, int64_t ldv, int64_t rows, int64_t mg, int nslices, double *part,
-                        double *G, int64_t ldg);
 int launch_sparse_tril(hipStream_t st, const double *src, int64_t lds, int64_t n, double *dst, int64_t ldd, int64_t np);
 int launch_sparse_grad_mid(hipStream_t st, const double *Binv, int64_t ldb, const double *E, int64_t lde, int64_t M, int mode, double *Mid,
                            int64_t np);

@@ -12,6 +12,25 @@
 #define KB_ROWS 32
 #define KB_RATIO (KB_COLS / KB_ROWS)
 
+// the product instantiations (ProductKids below): k1 * k2 in the form the id names
+constexpr bool is_product_kid(int kid)
+{
+    return kid == GPT_KERNEL_PRODUCT || kid == GPT_KID_PRODUCT_GM || kid == GPT_KID_PRODUCT_GB || kid == GPT_KID_PRODUCT_PER;
+}
+
+// The term KID at one pair: a native kernel, or the product k1 * k2 in the form KID names (k2 is read for a product only).  The pair
+// passes of the gradients (kgrad.hip, kgrad_rect.hip) evaluate their terms through this.
+template <int KID, int D>
+__device__ __forceinline__ double term_pair(const KParams &k1, const KParams *__restrict__ k2, const double *xi, const double *xj,
+                                            const int *ni, const int *nj)
+{
+    if constexpr (KID == GPT_KERNEL_PRODUCT) return prod_pair<D>(k1, *k2, xi, xj, ni, nj);
+    else if constexpr (KID == GPT_KID_PRODUCT_GM) return prod_pair<D, true>(k1, *k2, xi, xj, ni, nj);
+    else if constexpr (KID == GPT_KID_PRODUCT_GB) return prod_pair<D, true, true>(k1, *k2, xi, xj, ni, nj);
+    else if constexpr (KID == GPT_KID_PRODUCT_PER) return prod_pair<D, true, true, true>(k1, *k2, xi, xj, ni, nj);
+    else return any_pair<KID, D>(k1, xi, xj, ni, nj);
+}
+
 // BATCH: element blockIdx.z of a batch of independent matrices over the same points -- its hyperparameters kps[z], its
 // noise variance nvs[z], its matrix K + z * bstride (gpt_fit_batch); `kp_one` / `noise_one` are unused then.
 // WARP (gpt_set_warp): Xi / Xj hold WARPED points and Si / Sj the points' chain-rule slopes (warp.hpp: exactly 1.0 for a value
@@ -309,6 +328,21 @@ int dispatch_kid(KidList<KIDS...>, int kid, F &&f, R &&refuse)
     int rc = GPT_OK;
     const bool hit = ((kid == KIDS && (rc = f(std::integral_constant<int, KIDS>()), true)) || ...);
     return hit ? rc : refuse();
+}
+
+// One model term given by its factors' ids on a single matrix -- id1, or the product id1 * id2 where id2 >= 0 -- at num_dim D: the
+// product instantiation its factors ask for (product_kid), else the fit kernel id1; `who` names the launcher in the refusal.  What
+// the pair passes of the gradients launch through (kgrad.hip, kgrad_rect.hip).
+template <class F>
+int dispatch_term_kid(const char *who, int id1, int id2, int D, F &&for_kid)
+{
+    if (id2 >= 0)
+        return dispatch_kid(ProductKids(), product_kid(D, gibbs_form_of(D, id1, id2), gibbs_more_kid(id1) || gibbs_more_kid(id2), false), for_kid,
+                            [] { return GPT_E_ARG; });
+    return dispatch_kid(FitKids(), id1, for_kid, [&] {
+        gpt_set_error("%s: kernel_id %d is not a fit kernel", who, id1);
+        return GPT_E_ARG;
+    });
 }
 
 template <class F, int... I>

@@ -16,8 +16,9 @@
 // eight times.  For the cheap pair functions the pass is then bound by that traffic (Matern-5/2, N = 16384: 0.47 ms per
 // parameter); next to K_tot^-1 (57 ms there) it does not show.  The 1-D Gibbs kernels hoist their length scales out of the pair
 // loop as the builder does.
-// Instantiated through the dispatch the builders share (kbuild_kernel.hpp): FitKids for a plain term, ProductKids by product_kid
-// for a product term -- the form its factors' gform asks for.  A translation unit of its own: the builders' code objects stay
+// Instantiated through the dispatch the builders share (kbuild_kernel.hpp, dispatch_term_kid): FitKids for a plain term, ProductKids
+// by product_kid for a product term -- the form its factors' gform asks for; a term at one pair is term_pair, there too (both shared
+// with the rectangular pass, kgrad_rect.hip).  A translation unit of its own: the builders' code objects stay
 // what they were.
 // A BATCH (gpt_ll_grad_diff_batch, the gradient half of a resident batch): the element is the grid's second dimension.  Element e
 // reads its own stencil points kps[2 nh e ..], its own alpha + e ldw and W + e ldw^2 and writes its own partial rows behind those
@@ -31,18 +32,6 @@
 #include "kbuild_kernel.hpp"
 
 #define GR_MAXH GPT_GRAD_MAXH
-
-// the term KID at one pair: a native kernel, or the product k1 * k2 in the form KID names
-template <int KID, int D>
-__device__ __forceinline__ double kgrad_term_pair(const KParams &k1, const KParams *__restrict__ k2, const double *xi, const double *xj,
-                                                  const int *ni, const int *nj)
-{
-    if constexpr (KID == GPT_KERNEL_PRODUCT) return prod_pair<D>(k1, *k2, xi, xj, ni, nj);
-    else if constexpr (KID == GPT_KID_PRODUCT_GM) return prod_pair<D, true>(k1, *k2, xi, xj, ni, nj);
-    else if constexpr (KID == GPT_KID_PRODUCT_GB) return prod_pair<D, true, true>(k1, *k2, xi, xj, ni, nj);
-    else if constexpr (KID == GPT_KID_PRODUCT_PER) return prod_pair<D, true, true, true>(k1, *k2, xi, xj, ni, nj);
-    else return any_pair<KID, D>(k1, xi, xj, ni, nj);
-}
 
 // The weight of pair (i, j), lane j: alpha_i alpha_j - W_ij for the LML (u == alpha, loo false: the expression this file has always
 // had there), u_i alpha_j + alpha_i u_j - V_ij for the leave-one-out objective (gpt_loo_grad_diff: W is V = W diag(e) W then).  `loo`
@@ -129,7 +118,7 @@ __global__ __launch_bounds__(KB_THREADS) void kgrad_diff_kernel(
         } else if (live && h < nh) {
             const KParams &ka = kps[2 * h], &kb = kps[2 * h + 1];
             const KParams *ka2 = nullptr, *kb2 = nullptr;
-            if constexpr (KID == GPT_KERNEL_PRODUCT || KID == GPT_KID_PRODUCT_GM || KID == GPT_KID_PRODUCT_GB || KID == GPT_KID_PRODUCT_PER) {
+            if constexpr (is_product_kid(KID)) {
                 ka2 = kps2 + 2 * h;
                 kb2 = kps2 + 2 * h + 1;
             }
@@ -144,7 +133,7 @@ __global__ __launch_bounds__(KB_THREADS) void kgrad_diff_kernel(
                 }
                 const double w = kgrad_weight(loo, alpha, u, W, ldw, i, j, aj, uj);
                 const double w2 = (i == j) ? w : 2.0 * w;
-                const double dk = kgrad_term_pair<KID, D>(kb, kb2, xi, xj, nir, njr) - kgrad_term_pair<KID, D>(ka, ka2, xi, xj, nir, njr);
+                const double dk = term_pair<KID, D>(kb, kb2, xi, xj, nir, njr) - term_pair<KID, D>(ka, ka2, xi, xj, nir, njr);
                 acc = fma(w2, dk, acc);
             }
         }
@@ -181,13 +170,7 @@ int launch_kgrad_diff(hipStream_t st, int id1, int id2, int D, const KParams *d_
             return GPT_OK;
         }, kid_dim_rule(KID));
     };
-    if (id2 >= 0)
-        return dispatch_kid(ProductKids(), product_kid(D, gibbs_form_of(D, id1, id2), gibbs_more_kid(id1) || gibbs_more_kid(id2), false), for_kid,
-                            [] { return GPT_E_ARG; });
-    return dispatch_kid(FitKids(), id1, for_kid, [&] {
-        gpt_set_error("ll_grad_diff: kernel_id %d is not a fit kernel", id1);
-        return GPT_E_ARG;
-    });
+    return dispatch_term_kid("ll_grad_diff", id1, id2, D, for_kid);
 }
 
 // alpha_b = U_b z_b over the N points of every element of a resident batch: U_b = L_b^-T (upper triangular, row stride ldu, element

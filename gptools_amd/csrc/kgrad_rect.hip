@@ -3,9 +3,9 @@
 //     sum_im A[i][m] (k_b - k_a)(x_i, z_m)  +  1/2 sum_i e_i (k_b - k_a)(x_i, x_i),
 // A the chunk's adjoint A_fu (rows x lda, row-major) and k_a / k_b the term at the two stencil points of parameter h.  As in kgrad.hip
 // the difference is taken PER PAIR, before the weight, the stencil points' KParams live in device memory and are read by reference with
-// wave-uniform indices, the parameters of a launch are walked by a loop that is not unrolled, and the instantiations come from the
-// dispatch the builders share (kbuild_kernel.hpp: FitKids, ProductKids by product_kid).  A translation unit of its own: the builders'
-// and kgrad.hip's code objects stay what they were.
+// wave-uniform indices, the parameters of a launch are walked by a loop that is not unrolled, a term is evaluated through term_pair
+// and the instantiations come from dispatch_term_kid (both kbuild_kernel.hpp, both shared with kgrad.hip: FitKids, ProductKids by
+// product_kid).  A translation unit of its own: the builders' and kgrad.hip's code objects stay what they were.
 // Geometry.  kgrad_diff_kernel's tiles (32 rows x 256 columns of the lower triangle, a lane per column) do not fit: M is often <= 64, and
 // three of a workgroup's four waves would own no column at all.  Here a tile is KR_ROWS = 64 rows x 64 columns: the 64 lanes of EVERY
 // wave are the tile's 64 consecutive columns m -- a lane keeps its z_m in registers, and a row of A is read as one 512-byte line,
@@ -21,17 +21,6 @@
 
 #define KR_MAXH GPT_GRAD_MAXH
 #define KR_ROWS 64
-
-template <int KID, int D>
-__device__ __forceinline__ double krect_term_pair(const KParams &k1, const KParams *__restrict__ k2, const double *xi, const double *xj,
-                                                  const int *ni, const int *nj)
-{
-    if constexpr (KID == GPT_KERNEL_PRODUCT) return prod_pair<D>(k1, *k2, xi, xj, ni, nj);
-    else if constexpr (KID == GPT_KID_PRODUCT_GM) return prod_pair<D, true>(k1, *k2, xi, xj, ni, nj);
-    else if constexpr (KID == GPT_KID_PRODUCT_GB) return prod_pair<D, true, true>(k1, *k2, xi, xj, ni, nj);
-    else if constexpr (KID == GPT_KID_PRODUCT_PER) return prod_pair<D, true, true, true>(k1, *k2, xi, xj, ni, nj);
-    else return any_pair<KID, D>(k1, xi, xj, ni, nj);
-}
 
 // kps[2 h], kps[2 h + 1]: the term at the stencil points a, b of parameter h < nh <= KR_MAXH (kps2: the second factors of a product
 // term, else unused).  e == NULL: no diagonal part.  partial: (gridDim.y * gridDim.x) x KR_MAXH, every entry written.
@@ -74,7 +63,7 @@ __global__ __launch_bounds__(256) void kgrad_rect_diff_kernel(const KParams *__r
         if (h < nh) {
             const KParams &ka = kps[2 * h], &kb = kps[2 * h + 1];
             const KParams *ka2 = nullptr, *kb2 = nullptr;
-            if constexpr (KID == GPT_KERNEL_PRODUCT || KID == GPT_KID_PRODUCT_GM || KID == GPT_KID_PRODUCT_GB || KID == GPT_KID_PRODUCT_PER) {
+            if constexpr (is_product_kid(KID)) {
                 ka2 = kps2 + 2 * h;
                 kb2 = kps2 + 2 * h + 1;
             }
@@ -88,11 +77,11 @@ __global__ __launch_bounds__(256) void kgrad_rect_diff_kernel(const KParams *__r
                         nir[d] = nx[i * D + d];
                     }
                     const double w = A[i * lda + j];
-                    const double dk = krect_term_pair<KID, D>(kb, kb2, xi, zj, nir, nzj) - krect_term_pair<KID, D>(ka, ka2, xi, zj, nir, nzj);
+                    const double dk = term_pair<KID, D>(kb, kb2, xi, zj, nir, nzj) - term_pair<KID, D>(ka, ka2, xi, zj, nir, nzj);
                     acc = fma(w, dk, acc);
                 }
             if (diag) {
-                const double dk = krect_term_pair<KID, D>(kb, kb2, xd, xd, nd, nd) - krect_term_pair<KID, D>(ka, ka2, xd, xd, nd, nd);
+                const double dk = term_pair<KID, D>(kb, kb2, xd, xd, nd, nd) - term_pair<KID, D>(ka, ka2, xd, xd, nd, nd);
                 acc = fma(ed, dk, acc);
             }
         }
@@ -144,15 +133,7 @@ int launch_kgrad_rect_diff(hipStream_t st, int id1, int id2, int D, const KParam
             return GPT_OK;
         }, kid_dim_rule(KID));
     };
-    int rc;
-    if (id2 >= 0)
-        rc = dispatch_kid(ProductKids(), product_kid(D, gibbs_form_of(D, id1, id2), gibbs_more_kid(id1) || gibbs_more_kid(id2), false), for_kid,
-                          [] { return GPT_E_ARG; });
-    else
-        rc = dispatch_kid(FitKids(), id1, for_kid, [&] {
-            gpt_set_error("sparse_grad_diff: kernel_id %d is not a fit kernel", id1);
-            return GPT_E_ARG;
-        });
+    const int rc = dispatch_term_kid("sparse_grad_diff", id1, id2, D, for_kid);
     if (rc != GPT_OK) return rc;
     hipLaunchKernelGGL(kgrad_rect_finish_kernel, dim3((unsigned)nh), dim3(256), 0, st, dpartial, kgrad_rect_blocks(rows, M), dacc);
     GPT_LAUNCH_CHECK();

@@ -11,11 +11,44 @@
 // its partial tile to a workspace and sparse_gram_reduce_kernel adds the S partials to G in slice order: no floating-point atomics.
 //
 // The gradient of the objective (gpt_sparse_grad_diff) adds, at the end of this file, its per-row pass
-// (sparse_grad_rows_kernel), the rank-one part of A_fu, the two-operand Gram V diag(e) V^T for weights of either sign
-// (sparse_gram2_kernel, reduced by the same sparse_gram_reduce_kernel) and two small kernels of order M.
+// (sparse_grad_rows_kernel, which forms q_i and Lambda_i through the functions the fit's row pass forms them with), the rank-one part
+// of A_fu and two small kernels of order M; its Gram V diag(e) V^T, for weights of either sign, is the two-operand instantiation of
+// sparse_gram_kernel.
 #include "common.hpp"
 
 // ---- per-row pass ------------------------------------------------------------------------------------------------------------------
+// What the fit's row pass and the gradient's (sparse_grad_rows_kernel, below) must form alike, bit for bit -- a row the fit accepted has
+// the same Lambda_i in the gradient that differentiates it.  This thread's share of q_i = |v_i|^2 over the columns [0, M) of a row:
+// two accumulators at a stride of 512, joined at the end.  The wave and workgroup reductions behind it are each kernel's own.
+__device__ __forceinline__ double sparse_row_sumsq(const double *__restrict__ row, int64_t M)
+{
+    double a0 = 0.0, a1 = 0.0;
+    int64_t c = threadIdx.x;
+    for (; c + 256 < M; c += 512) {
+        const double v0 = row[c], v1 = row[c + 256];
+        a0 = fma(v0, v0, a0);
+        a1 = fma(v1, v1, a1);
+    }
+    for (; c < M; c += 256) {
+        const double v0 = row[c];
+        a0 = fma(v0, v0, a0);
+    }
+    return a0 + a1;
+}
+
+// Lambda_i from kmq = k_i - q_i (entered for fitc only: vfe and dtc may pass anything -- the fit's row pass passes a k_i nobody wrote
+// for dtc, the gradient's passes 0) and s_i; ok: a positive finite number.  (fitc as a bool, not the method: with the method as an
+// argument the compiler lays out the gradient's row pass otherwise.)
+struct SparseLambda {
+    double lam;
+    bool ok;
+};
+__device__ __forceinline__ SparseLambda sparse_lambda_of(bool fitc, double kmq, double s)
+{
+    const double lam = fitc ? kmq + s : s;
+    return SparseLambda{lam, lam > 0.0 && lam < INFINITY};
+}
+
 // method: 0 fitc (Lambda_i = k_i - q_i + s_i), 1 vfe, 2 dtc (Lambda_i = s_i); s_i = noise_var + err_i^2.
 // rowval[i] = log Lambda_i, rowval[ldr + i] = (k_i - q_i) / s_i (vfe, else 0).  A row whose Lambda_i is not a positive finite number
 // raises *bad and contributes nothing (its scale is 0): the host reads the word once, at the end of the fit.
@@ -30,26 +63,16 @@ __global__ __launch_bounds__(256) void sparse_lambda_kernel(double *__restrict__
     if (i >= rows) return;
     double *row = V + i * ldv;
     const int lane = threadIdx.x & 63, wave = threadIdx.x >> 6;
-    double a0 = 0.0, a1 = 0.0;
-    int64_t c = threadIdx.x;
-    for (; c + 256 < M; c += 512) {
-        const double v0 = row[c], v1 = row[c + 256];
-        a0 = fma(v0, v0, a0);
-        a1 = fma(v1, v1, a1);
-    }
-    for (; c < M; c += 256) {
-        const double v0 = row[c];
-        a0 = fma(v0, v0, a0);
-    }
-    double acc = a0 + a1;
+    double acc = sparse_row_sumsq(row, M);
     for (int off = 32; off > 0; off >>= 1) acc += __shfl_down(acc, off);
     if (lane == 0) part[wave] = acc;
     __syncthreads();
     if (threadIdx.x == 0) {
         const double q = (part[0] + part[1]) + (part[2] + part[3]);
         const double e = err[i], s = noise_var + e * e, kmq = kdiag[i] - q;
-        const double lam = (method == 0) ? kmq + s : s;
-        const bool ok = lam > 0.0 && lam < INFINITY;
+        const SparseLambda L = sparse_lambda_of(method == 0, kmq, s);
+        const double lam = L.lam;
+        const bool ok = L.ok;
         if (!ok) *bad = 1;
         rowval[i] = ok ? log(lam) : 0.0;
         rowval[ldr + i] = (ok && method == 1) ? kmq / s : 0.0;
@@ -57,7 +80,7 @@ __global__ __launch_bounds__(256) void sparse_lambda_kernel(double *__restrict__
     }
     __syncthreads();
     const double sc = scale;
-    for (c = threadIdx.x; c < M; c += 256) row[c] *= sc;
+    for (int64_t c = threadIdx.x; c < M; c += 256) row[c] *= sc;
     if (threadIdx.x == 0) row[M] = r[i] * sc;
 }
 
@@ -116,16 +139,29 @@ int launch_sparse_rowsum(hipStream_t st, const double *rowval, int64_t ldr, int6
 // V[k][j0 + j], so lanes 0-15 of either operand read 16 consecutive doubles of row k.  Rows past the slice's end load as 0.0 (no
 // access), so a slice or chunk may end anywhere, below four rows too.  Columns: i0 + 63 < mg <= ldv by the launcher's check.
 // part: (nslices x ntiles) tiles of 4096 doubles, tile-local row-major; every workgroup writes its whole tile.
+// TWO: the signed-weight Gram of the gradient, tile (ti, tj) += sum_k A[k][i0 + i] V[k][j0 + j] with A a second
+// matrix of V's shape -- A holds the rows e_k v_k, and e_k changes sign, so the rows cannot be scaled by a square root and fed in
+// as one operand.  Without TWO, A is not read and both operands come from V: the fit's instantiation, the code it was before the
+// gradient existed.  A template flag, not a run-time test, for that reason.
 #define SG_UNROLL 4
-__global__ __launch_bounds__(256) void sparse_gram_kernel(const double *__restrict__ V, int64_t ldv, int64_t rows, int64_t slice_rows,
-                                                          int ntiles, double *__restrict__ part)
+
+// (ti, tj), tj <= ti, from the row-major index t of the lower triangle's tiles: ti (ti + 1) / 2 <= t
+__device__ __forceinline__ void sparse_tile_of(int t, int *ti_out, int *tj_out)
 {
-    const int t = blockIdx.x, s = blockIdx.y;
-    // (ti, tj) from the row-major index of the lower triangle: ti (ti + 1) / 2 <= t
     int ti = (int)((sqrt(8.0 * (double)t + 1.0) - 1.0) * 0.5);
     while ((ti + 1) * (ti + 2) / 2 <= t) ti++;
     while (ti * (ti + 1) / 2 > t) ti--;
-    const int tj = t - ti * (ti + 1) / 2;
+    *ti_out = ti;
+    *tj_out = t - ti * (ti + 1) / 2;
+}
+
+template <bool TWO>
+__global__ __launch_bounds__(256) void sparse_gram_kernel(const double *__restrict__ A, const double *__restrict__ V, int64_t ldv,
+                                                          int64_t rows, int64_t slice_rows, int ntiles, double *__restrict__ part)
+{
+    const int t = blockIdx.x, s = blockIdx.y;
+    int ti, tj;
+    sparse_tile_of(t, &ti, &tj);
     const int lane = threadIdx.x & 63, wave = threadIdx.x >> 6;
     const int fr = lane & 15, fk = lane >> 4;
     const int64_t i0 = (int64_t)ti * 64 + (wave >> 1) * 32, j0 = (int64_t)tj * 64 + (wave & 1) * 32;
@@ -142,11 +178,11 @@ __global__ __launch_bounds__(256) void sparse_gram_kernel(const double *__restri
         for (int u = 0; u < SG_UNROLL; u++) {
             const int64_t kr = k + 4 * u + fk;
             const bool live = kr < k1;
-            const double *row = V + kr * ldv;
-            av[u][0] = live ? row[i0 + fr] : 0.0;
-            av[u][1] = live ? row[i0 + 16 + fr] : 0.0;
-            bv[u][0] = live ? row[j0 + fr] : 0.0;
-            bv[u][1] = live ? row[j0 + 16 + fr] : 0.0;
+            const double *rb = V + kr * ldv, *ra = TWO ? A + kr * ldv : rb;
+            av[u][0] = live ? ra[i0 + fr] : 0.0;
+            av[u][1] = live ? ra[i0 + 16 + fr] : 0.0;
+            bv[u][0] = live ? rb[j0 + fr] : 0.0;
+            bv[u][1] = live ? rb[j0 + 16 + fr] : 0.0;
         }
 #pragma unroll
         for (int u = 0; u < SG_UNROLL; u++)
@@ -171,10 +207,8 @@ __global__ __launch_bounds__(256) void sparse_gram_reduce_kernel(const double *_
                                                                  double *__restrict__ G, int64_t ldg)
 {
     const int t = blockIdx.x;
-    int ti = (int)((sqrt(8.0 * (double)t + 1.0) - 1.0) * 0.5);
-    while ((ti + 1) * (ti + 2) / 2 <= t) ti++;
-    while (ti * (ti + 1) / 2 > t) ti--;
-    const int tj = t - ti * (ti + 1) / 2;
+    int ti, tj;
+    sparse_tile_of(t, &ti, &tj);
     const int e = blockIdx.y * 256 + threadIdx.x;          // element of the tile, row-major
     const int64_t gi = (int64_t)ti * 64 + (e >> 6), gj = (int64_t)tj * 64 + (e & 63);
     double v = G[gi * ldg + gj];
@@ -182,22 +216,25 @@ __global__ __launch_bounds__(256) void sparse_gram_reduce_kernel(const double *_
     G[gi * ldg + gj] = v;
 }
 
-// G (mg x mg, mg a multiple of 64, row stride ldg; lower tiles) += V^T V over the `rows` rows of V (row stride ldv >= mg).
-// nslices workgroups share a tile (chosen by the caller: api_sparse.inc sparse_slices); part holds nslices * ntiles * 4096 doubles.
-int launch_sparse_gram(hipStream_t st, const double *V, int64_t ldv, int64_t rows, int64_t mg, int nslices, double *part, double *G,
-                       int64_t ldg)
+// G (mg x mg, mg a multiple of 64, row stride ldg; lower tiles) += V^T V (A == NULL) or A^T V over the `rows` rows of V and A (row
+// stride ldv >= mg).  nslices workgroups share a tile (chosen by the caller: api_sparse.inc sparse_slices); part holds nslices *
+// sparse_gram_tiles(mg) * 4096 doubles.
+int launch_sparse_gram(hipStream_t st, const double *A, const double *V, int64_t ldv, int64_t rows, int64_t mg, int nslices, double *part,
+                       double *G, int64_t ldg)
 {
     if (rows <= 0) return GPT_OK;
     if (mg <= 0 || mg % 64 || mg > ldv || mg > ldg || nslices < 1 || nslices > 65535 || mg / 64 > 2000) {
-        gpt_set_error("sparse_gram: order %lld (a multiple of 64, at most the row strides %lld / %lld), %d slices", (long long)mg,
-                      (long long)ldv, (long long)ldg, nslices);
+        gpt_set_error("%s: order %lld (a multiple of 64, at most the row strides %lld / %lld), %d slices", A ? "sparse_gram2" : "sparse_gram",
+                      (long long)mg, (long long)ldv, (long long)ldg, nslices);
         return GPT_E_ARG;
     }
-    const int nt = (int)(mg / 64), ntiles = nt * (nt + 1) / 2;
+    const int ntiles = (int)sparse_gram_tiles(mg);
     // whole k-steps of four rows per slice; no slice is empty
     int64_t slice_rows = ((rows + nslices - 1) / nslices + 3) / 4 * 4;
     const int ns = (int)((rows + slice_rows - 1) / slice_rows);
-    hipLaunchKernelGGL(sparse_gram_kernel, dim3((unsigned)ntiles, (unsigned)ns), dim3(256), 0, st, V, ldv, rows, slice_rows, ntiles, part);
+    const dim3 grid((unsigned)ntiles, (unsigned)ns);
+    if (A) hipLaunchKernelGGL(sparse_gram_kernel<true>, grid, dim3(256), 0, st, A, V, ldv, rows, slice_rows, ntiles, part);
+    else hipLaunchKernelGGL(sparse_gram_kernel<false>, grid, dim3(256), 0, st, A, V, ldv, rows, slice_rows, ntiles, part);
     GPT_LAUNCH_CHECK();
     hipLaunchKernelGGL(sparse_gram_reduce_kernel, dim3((unsigned)ntiles, 16), dim3(256), 0, st, part, ntiles, ns, G, ldg);
     GPT_LAUNCH_CHECK();
@@ -278,8 +315,9 @@ int launch_sparse_var(hipStream_t st, const double *V, const double *W, int64_t 
 //     e_i = W_ii (fitc), -1 / s_i (vfe), 0 (dtc)                 g_i = W_ii / 2 (+ (k_i - q_i) / (2 s_i^2) for vfe)
 // Written: alpha[i], e[i], gval[i] = g_i (gval[ldr + i] = 0: the layout sparse_rowsum_kernel adds up in a fixed order), and the two
 // scaled copies of the row, S1[i] = v_i / Lambda_i and S2[i] = e_i v_i, columns [M, ld) zero -- the operands of the chunk's GEMMs and
-// of the signed Gram.  q_i is summed exactly as sparse_lambda_kernel sums it: a row the fit accepted has the same Lambda_i here.  A
-// row whose Lambda_i is not a positive finite number raises *bad and contributes nothing (alpha, e, g and both copies are zero).
+// of the signed Gram.  q_i and Lambda_i come from the functions sparse_lambda_kernel forms them with (sparse_row_sumsq,
+// sparse_lambda_of; kmq is 0 for dtc, whose k_i nobody writes): a row the fit accepted has the same Lambda_i here.  A row whose Lambda_i
+// is not a positive finite number raises *bad and contributes nothing (alpha, e, g and both copies are zero).
 __global__ __launch_bounds__(256) void sparse_grad_rows_kernel(const double *__restrict__ V, const double *__restrict__ W, int64_t ld,
                                                                int64_t rows, int64_t M, int method, const double *__restrict__ kdiag,
                                                                const double *__restrict__ r, const double *__restrict__ err,
@@ -294,22 +332,11 @@ __global__ __launch_bounds__(256) void sparse_grad_rows_kernel(const double *__r
     if (i >= rows) return;
     const double *v = V + i * ld, *w = W + i * ld;
     const int lane = threadIdx.x & 63, wave = threadIdx.x >> 6;
-    double a0 = 0.0, a1 = 0.0, bt = 0.0, bw = 0.0;
-    int64_t c = threadIdx.x;
-    for (; c + 256 < M; c += 512) {
-        const double v0 = v[c], v1 = v[c + 256];
-        a0 = fma(v0, v0, a0);
-        a1 = fma(v1, v1, a1);
-    }
-    for (; c < M; c += 256) {
-        const double v0 = v[c];
-        a0 = fma(v0, v0, a0);
-    }
-    for (c = threadIdx.x; c < M; c += 256) {
+    double acc = sparse_row_sumsq(v, M), bt = 0.0, bw = 0.0;
+    for (int64_t c = threadIdx.x; c < M; c += 256) {
         bt = fma(v[c], t[c], bt);
         bw = fma(w[c], w[c], bw);
     }
-    double acc = a0 + a1;
     for (int off = 32; off > 0; off >>= 1) {
         acc += __shfl_down(acc, off);
         bt += __shfl_down(bt, off);
@@ -324,8 +351,9 @@ __global__ __launch_bounds__(256) void sparse_grad_rows_kernel(const double *__r
     if (threadIdx.x == 0) {
         const double q = (pq[0] + pq[1]) + (pq[2] + pq[3]), vt = (pt[0] + pt[1]) + (pt[2] + pt[3]), ww = (pw[0] + pw[1]) + (pw[2] + pw[3]);
         const double er = err[i], s = noise_var + er * er, kmq = (method == 2) ? 0.0 : kdiag[i] - q;
-        const double lam = (method == 0) ? kmq + s : s;
-        const bool ok = lam > 0.0 && lam < INFINITY;
+        const SparseLambda L = sparse_lambda_of(method == 0, kmq, s);
+        const double lam = L.lam;
+        const bool ok = L.ok;
         if (!ok) *bad = 1;
         const double il = ok ? 1.0 / lam : 0.0;
         const double al = ok ? (r[i] - vt) * il : 0.0;
@@ -343,7 +371,7 @@ __global__ __launch_bounds__(256) void sparse_grad_rows_kernel(const double *__r
     __syncthreads();
     const double s1 = sc1, s2 = sc2;
     double *o1 = S1 + i * ld, *o2 = S2 + i * ld;
-    for (c = threadIdx.x; c < ld; c += 256) {
+    for (int64_t c = threadIdx.x; c < ld; c += 256) {
         const double vc = (c < M) ? v[c] : 0.0;
         o1[c] = vc * s1;
         o2[c] = vc * s2;
@@ -379,79 +407,6 @@ int launch_sparse_rank1(hipStream_t st, double *A, int64_t lda, int64_t rows, in
     if (rows <= 0 || M <= 0) return GPT_OK;
     if (M > lda || (M + 255) / 256 > 65535) return GPT_E_ARG;
     hipLaunchKernelGGL(sparse_rank1_kernel, dim3((unsigned)rows, (unsigned)((M + 255) / 256)), dim3(256), 0, st, A, lda, rows, M, alpha, beta);
-    GPT_LAUNCH_CHECK();
-    return GPT_OK;
-}
-
-// The signed-weight Gram: sparse_gram_kernel with TWO operands, tile (ti, tj) += sum_k A[k][i0 + i] V[k][j0 + j] -- A holds the rows
-// e_k v_k, and e_k changes sign, so the rows cannot be scaled by a square root and fed to the one-operand kernel.  The same tiles,
-// slices, lane maps and partial-tile layout; sparse_gram_reduce_kernel adds the slices.  A kernel of its own: the fit's stays the
-// code it was.
-__global__ __launch_bounds__(256) void sparse_gram2_kernel(const double *__restrict__ A, const double *__restrict__ V, int64_t ldv,
-                                                           int64_t rows, int64_t slice_rows, int ntiles, double *__restrict__ part)
-{
-    const int t = blockIdx.x, s = blockIdx.y;
-    int ti = (int)((sqrt(8.0 * (double)t + 1.0) - 1.0) * 0.5);
-    while ((ti + 1) * (ti + 2) / 2 <= t) ti++;
-    while (ti * (ti + 1) / 2 > t) ti--;
-    const int tj = t - ti * (ti + 1) / 2;
-    const int lane = threadIdx.x & 63, wave = threadIdx.x >> 6;
-    const int fr = lane & 15, fk = lane >> 4;
-    const int64_t i0 = (int64_t)ti * 64 + (wave >> 1) * 32, j0 = (int64_t)tj * 64 + (wave & 1) * 32;
-    const int64_t k0 = (int64_t)s * slice_rows;
-    const int64_t k1 = (k0 + slice_rows < rows) ? k0 + slice_rows : rows;
-    f64x4 acc[2][2];
-#pragma unroll
-    for (int a = 0; a < 2; a++)
-#pragma unroll
-        for (int b = 0; b < 2; b++) acc[a][b] = f64x4{0.0, 0.0, 0.0, 0.0};
-    for (int64_t k = k0; k < k1; k += 4 * SG_UNROLL) {
-        double av[SG_UNROLL][2], bv[SG_UNROLL][2];
-#pragma unroll
-        for (int u = 0; u < SG_UNROLL; u++) {
-            const int64_t kr = k + 4 * u + fk;
-            const bool live = kr < k1;
-            const double *ra = A + kr * ldv, *rb = V + kr * ldv;
-            av[u][0] = live ? ra[i0 + fr] : 0.0;
-            av[u][1] = live ? ra[i0 + 16 + fr] : 0.0;
-            bv[u][0] = live ? rb[j0 + fr] : 0.0;
-            bv[u][1] = live ? rb[j0 + 16 + fr] : 0.0;
-        }
-#pragma unroll
-        for (int u = 0; u < SG_UNROLL; u++)
-#pragma unroll
-            for (int a = 0; a < 2; a++)
-#pragma unroll
-                for (int b = 0; b < 2; b++)
-                    acc[a][b] = __builtin_amdgcn_mfma_f64_16x16x4f64(av[u][a], bv[u][b], acc[a][b], 0, 0, 0);
-    }
-    double *out = part + ((int64_t)s * ntiles + t) * 4096;
-    const int li = (wave >> 1) * 32, lj = (wave & 1) * 32;
-#pragma unroll
-    for (int a = 0; a < 2; a++)
-#pragma unroll
-        for (int b = 0; b < 2; b++)
-#pragma unroll
-            for (int q = 0; q < 4; q++) out[(li + a * 16 + fk + 4 * q) * 64 + lj + b * 16 + fr] = acc[a][b][q];
-}
-
-// G (mg x mg, lower 64 x 64 tiles) += A^T V over the `rows` rows of A and V (both with row stride ldv >= mg): launch_sparse_gram's
-// checks, slices and reduce
-int launch_sparse_gram2(hipStream_t st, const double *A, const double *V, int64_t ldv, int64_t rows, int64_t mg, int nslices, double *part,
-                        double *G, int64_t ldg)
-{
-    if (rows <= 0) return GPT_OK;
-    if (mg <= 0 || mg % 64 || mg > ldv || mg > ldg || nslices < 1 || nslices > 65535 || mg / 64 > 2000) {
-        gpt_set_error("sparse_gram2: order %lld (a multiple of 64, at most the row strides %lld / %lld), %d slices", (long long)mg,
-                      (long long)ldv, (long long)ldg, nslices);
-        return GPT_E_ARG;
-    }
-    const int nt = (int)(mg / 64), ntiles = nt * (nt + 1) / 2;
-    int64_t slice_rows = ((rows + nslices - 1) / nslices + 3) / 4 * 4;
-    const int ns = (int)((rows + slice_rows - 1) / slice_rows);
-    hipLaunchKernelGGL(sparse_gram2_kernel, dim3((unsigned)ntiles, (unsigned)ns), dim3(256), 0, st, A, V, ldv, rows, slice_rows, ntiles, part);
-    GPT_LAUNCH_CHECK();
-    hipLaunchKernelGGL(sparse_gram_reduce_kernel, dim3((unsigned)ntiles, 16), dim3(256), 0, st, part, ntiles, ns, G, ldg);
     GPT_LAUNCH_CHECK();
     return GPT_OK;
 }

@@ -262,6 +262,74 @@ def test_a_stencil_point_the_fit_would_refuse_is_refused_before_any_launch(g):
     assert np.array_equal(gp.ll_gradient(), g1)
 
 
+def test_a_bad_stencil_is_refused_alike_by_the_four_differenced_gradients():
+    """The same bad stencil to gpt_ll_grad_diff, gpt_loo_grad_diff, gpt_ll_grad_diff_batch (a batch of one) and gpt_sparse_grad_diff,
+    each called on the library itself (the wrappers of _lib.Context refuse some of these before the library sees them): a term the
+    model does not have, a step of 0, a step of inf, and a stencil point the fit refuses.  N = 40, M = 5; SE + general Matern, because
+    no parameter value of a squared-exponential term is refused by the fit: the Matern term's nu = 70 is, as in the test above.
+    The status is the same from all four.  Where the library names the caller -- the two bad steps -- each message starts with its own
+    entry point's name; the fit's refusal of nu is the fit's own text, the same from all four; a term out of range sets no text."""
+    import ctypes as C
+    from gptools_amd import _lib
+    lib = _lib.load()
+    N, M, d = 40, 5, 2
+    X, n, y = inputs(N, d, nder=0)
+    err_y = np.full(N, 0.02)
+    Z = np.random.RandomState(5).rand(M, d)
+    p_se, p_mat = [1.1, 0.4, 0.6], [1.0, 1.3, 0.35, 0.3]
+    ids, terms = [_lib.KERNEL_SE, _lib.KERNEL_MATERN], [(_lib.KERNEL_SE, p_se), (_lib.KERNEL_MATERN, p_mat)]
+    dense, batch = _lib.Context(), _lib.Context()
+    dense.set_data(X, n)
+    dense.fit_sum(ids, [p_se, p_mat], 0.01, y, err_y, 1e-12)
+    dense.sparse_set_inducing(Z)
+    dense.sparse_fit(_lib.SPARSE_METHODS["fitc"], terms, 0.01, y, err_y, 1e-8)
+    batch.set_data(X, n)
+    _, _, info = batch.fit_batch_sum(ids, [p_se + p_mat], [3, 4], [0.01], [y], err_y, 1e-12)
+    assert info[0] == 0
+    keep = _lib.i32([1])
+    ll = C.c_double()
+    v = [np.empty(N) for _ in range(3)]
+
+    def calls(ti, pa, pb, dn):
+        ti, pa, pb, dn = _lib.i32(ti), _lib.f64(pa), _lib.f64(pb), _lib.f64(dn)
+        nh, out = len(ti), np.empty(len(ti) + 1)
+        head = (nh, _lib.iptr(ti), _lib.dptr(pa), _lib.dptr(pb), _lib.dptr(dn))
+        return [("gpt_ll_grad_diff", lambda: lib.gpt_ll_grad_diff(dense.handle, *head, _lib.dptr(out))),
+                ("gpt_loo_grad_diff", lambda: lib.gpt_loo_grad_diff(dense.handle, *head, _lib.dptr(out), C.byref(ll), _lib.dptr(v[0]),
+                                                                   _lib.dptr(v[1]), _lib.dptr(v[2]))),
+                ("gpt_ll_grad_diff_batch", lambda: lib.gpt_ll_grad_diff_batch(batch.handle, *head, _lib.iptr(keep), _lib.dptr(out), None)),
+                ("gpt_sparse_grad_diff", lambda: lib.gpt_sparse_grad_diff(dense.handle, *head, _lib.dptr(y), _lib.dptr(err_y),
+                                                                         _lib.dptr(out), None))]
+
+    def answers(ti, pa, pb, dn):
+        got = []
+        for name, call in calls(ti, pa, pb, dn):
+            rc = call()
+            got.append((name, rc, _lib.last_error()))
+            print("%s: status %d, %r" % got[-1])
+        return got
+
+    a, b = [1.1, 0.4, 0.6 - 1e-5], [1.1, 0.4, 0.6 + 1e-5]
+    # a good stencil first: every entry point answers GPT_OK (the bad ones below differ from it in one place each)
+    assert [rc for _, rc, _ in answers([0], a, b, [2e-5])] == [_lib.GPT_OK] * 4
+    # a term the model does not have
+    assert [rc for _, rc, _ in answers([2], a, b, [2e-5])] == [_lib.GPT_E_ARG] * 4
+    assert [rc for _, rc, _ in answers([-1], a, b, [2e-5])] == [_lib.GPT_E_ARG] * 4
+    # a step of 0, a step of inf
+    for step in (0.0, np.inf):
+        got = answers([0], a, b, [step])
+        assert [rc for _, rc, _ in got] == [_lib.GPT_E_ARG] * 4
+        for name, _, msg in got:
+            assert msg.startswith(name + ": denom["), (name, msg)
+    # a stencil point the fit refuses: the Matern term's nu
+    a, b = [1.0, 70.0, 0.35, 0.3], [1.0, 1.3, 0.35, 0.3]
+    got = answers([1], a, b, [-68.7])
+    assert [rc for _, rc, _ in got] == [got[0][1]] * 4 and got[0][1] in (_lib.GPT_E_ARG, _lib.GPT_E_VALUE)
+    assert len({msg for _, _, msg in got}) == 1 and "nu" in got[0][2]
+    # ... and the good stencil still goes through
+    assert [rc for _, rc, _ in answers([0], [1.1, 0.4, 0.6 - 1e-5], [1.1, 0.4, 0.6 + 1e-5], [2e-5])] == [_lib.GPT_OK] * 4
+
+
 def test_optimiser_with_the_device_gradient_reaches_the_default_routes_optimum(g):
     """Matern-5/2, N = 300, SLSQP from the same start: the log-posteriors of gradient="device" and of the default route (finite
     differences of the objective) agree within the optimiser's ftol, SLSQP's own 1e-6, absolute as SLSQP applies it.

@@ -352,6 +352,27 @@ def test_two_operand_gram_alone(rows, mg, nslices, wide):
     assert np.array_equal(got[:, :mg][low], want[low]) and np.array_equal(got[:, :mg][~low], Gw[:, :mg][~low])
 
 
+@pytest.mark.parametrize("rows,mg,nslices", [(5, 64, 2), (130, 128, 7), (70, 192, 3)])
+def test_two_operand_gram_with_equal_operands_is_the_one_operand_gram(rows, mg, nslices):
+    """gpt_dev_sparse_gram2(A = V) and gpt_dev_sparse_gram(V) onto copies of one G, on data that is not integer: the same bits in all of
+    G.  The two share their tiles, slices, lane maps and the layout of the partial tiles, so every sum is taken in the same order."""
+    import torch
+    from gptools_amd import _lib
+    lib = _lib.load()
+    rs = np.random.RandomState(1000 * rows + mg)
+    ldv = mg + 64
+    V, G = rs.standard_normal((rows, ldv)), rs.standard_normal((mg, mg))
+    ctx = _lib.Context()
+    dV, dG1, dG2 = torch.tensor(V, device="cuda"), torch.tensor(G, device="cuda"), torch.tensor(G, device="cuda")
+    torch.cuda.synchronize()
+    _lib.check(lib.gpt_dev_sparse_gram(ctx.handle, dV.data_ptr(), ldv, rows, mg, nslices, dG1.data_ptr(), mg))
+    _lib.check(lib.gpt_dev_sparse_gram2(ctx.handle, dV.data_ptr(), dV.data_ptr(), ldv, rows, mg, nslices, dG2.data_ptr(), mg))
+    ctx.synchronize()
+    g1, g2 = dG1.cpu().numpy(), dG2.cpu().numpy()
+    assert not np.array_equal(g1, G)
+    assert np.array_equal(g1, g2)
+
+
 U = 2.0 ** -53
 
 
