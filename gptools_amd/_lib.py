@@ -136,6 +136,9 @@ SIGNATURES = {
     "gpt_dev_sparse_gram2": (C.c_int, [_vp, _vp, _vp, _i64, _i64, _i64, C.c_int, _vp, _i64]),
     "gpt_dev_sparse_grad_pairs": (C.c_int, [_vp, C.c_int, C.c_int, C.c_int, C.c_int, C.c_int, _dp, _dp, C.c_int, C.c_int, _vp, _vp, _i64,
                                             _vp, _vp, _i64, _vp, _i64, _vp, _dp]),
+    "gpt_sparse_grad_z": (C.c_int, [_vp, C.c_int, _ip, _dp, _dp, _dp, _dp, _dp, _dp, _dp, _dp]),
+    "gpt_dev_sparse_grad_dz_pairs": (C.c_int, [_vp, C.c_int, C.c_int, C.c_int, C.c_int, _dp, C.c_int, C.c_int, _vp, _vp, _i64, _vp, _vp, _i64,
+                                               _vp, _i64, C.c_int, _dp]),
 }
 
 _lib = None
@@ -730,7 +733,7 @@ class Context(object):
         nZ = None if nZ is None else i32(nZ)
         self._sparse_M = None
         check(self._lib.gpt_sparse_set_inducing(self.handle, dptr(Z), iptr(nZ), Z.shape[0]))
-        self._sparse_M = Z.shape[0]
+        self._sparse_M, self._sparse_D = Z.shape[0], Z.shape[1]
 
     def sparse_fit(self, method, terms, noise_var, y, err_y, jitter, chunk_rows=0):
         """gpt_sparse_fit: ``method`` one of ``SPARSE_METHODS``' values, ``terms`` as :meth:`fit_terms` takes them ->
@@ -746,23 +749,38 @@ class Context(object):
         self._sparse_nparams = [int(v) for v in npar]
         return ll.value, parts
 
+    def _sparse_grad(self, who, term_idx, params_a, params_b, denom, y, err_y, want_alpha, want_dz):
+        """The one body of :meth:`sparse_grad_diff` and :meth:`sparse_grad_z` (``want_dz``): ``(out, alpha, dZ or None)``."""
+        counts = getattr(self, "_sparse_nparams", None)
+        if counts is None:
+            counts = []              # (no sparse fit on this context: the library answers GPT_E_STATE)
+        ti, pa, pb, dn = self._pack_stencil(who, term_idx, params_a, params_b, denom, counts=counts)
+        y, err_y = f64(y), f64(err_y)
+        if y.shape != err_y.shape or y.ndim != 1:
+            raise ValueError("%s: y and err_y must be vectors of one length, got %s and %s" % (who, y.shape, err_y.shape))
+        out = np.empty(len(ti) + 1)
+        alpha = np.empty(len(y)) if want_alpha else None
+        args = (self.handle, len(ti), iptr(ti), dptr(pa), dptr(pb), dptr(dn), dptr(y), dptr(err_y), dptr(out), dptr(alpha))
+        if not want_dz:
+            check(self._lib.gpt_sparse_grad_diff(*args))
+            return out, alpha, None
+        M = getattr(self, "_sparse_M", None)      # (no inducing inputs on this context: the library answers GPT_E_STATE)
+        dz = np.full((int(M), int(self._sparse_D)) if M else (1, 1), np.nan)
+        check(self._lib.gpt_sparse_grad_z(*(args + (dptr(dz),))))
+        return out, alpha, dz
+
     def sparse_grad_diff(self, term_idx, params_a, params_b, denom, y, err_y, want_alpha=False):
         """gpt_sparse_grad_diff: the gradient of the resident sparse fit's objective by per-pair central differences.  The stencil
         arguments are :meth:`ll_grad_diff`'s, against the terms of the last :meth:`sparse_fit`; ``y`` and ``err_y`` as that fit took
         them.  Returns ``(out, alpha)``: the entries of the kernel parameters followed by the derivative with respect to the noise
         variance, and ``alpha = (Q_ff + Lambda)^-1 y`` (``None`` unless ``want_alpha``)."""
-        counts = getattr(self, "_sparse_nparams", None)
-        if counts is None:
-            counts = []              # (no sparse fit on this context: the library answers GPT_E_STATE)
-        ti, pa, pb, dn = self._pack_stencil("sparse_grad_diff", term_idx, params_a, params_b, denom, counts=counts)
-        y, err_y = f64(y), f64(err_y)
-        if y.shape != err_y.shape or y.ndim != 1:
-            raise ValueError("sparse_grad_diff: y and err_y must be vectors of one length, got %s and %s" % (y.shape, err_y.shape))
-        out = np.empty(len(ti) + 1)
-        alpha = np.empty(len(y)) if want_alpha else None
-        check(self._lib.gpt_sparse_grad_diff(self.handle, len(ti), iptr(ti), dptr(pa), dptr(pb), dptr(dn), dptr(y), dptr(err_y), dptr(out),
-                                             dptr(alpha)))
-        return out, alpha
+        return self._sparse_grad("sparse_grad_diff", term_idx, params_a, params_b, denom, y, err_y, want_alpha, False)[:2]
+
+    def sparse_grad_z(self, term_idx, params_a, params_b, denom, y, err_y, want_alpha=False):
+        """gpt_sparse_grad_z: :meth:`sparse_grad_diff` and, from the same pass over the data, the gradient of the objective with
+        respect to the inducing inputs.  Returns ``(out, alpha, dZ)``: the first two as :meth:`sparse_grad_diff` returns them, bit for
+        bit, ``dZ`` an (M, D) array (no entry of the stencil is needed for it: ``term_idx`` may be empty)."""
+        return self._sparse_grad("sparse_grad_z", term_idx, params_a, params_b, denom, y, err_y, want_alpha, True)
 
     def sparse_predict(self, Xstar, nstar, want, noise_params=None, noise_n=None):
         Xstar, nstar = f64(Xstar), i32(nstar)

@@ -55,7 +55,7 @@ enum { SLOT_XI = 0, SLOT_XJ, SLOT_NI, SLOT_NJ, SLOT_OUT, SLOT_KST, SLOT_KSS, SLO
        SLOT_PB_V, SLOT_PB_COV, SLOT_PB_MISC, SLOT_XSW, SLOT_SS, SLOT_SI, SLOT_SJ, SLOT_WB_X, SLOT_WB_S, SLOT_WB_P, SLOT_GKP, SLOT_GB_U, SLOT_GB_W, SLOT_GB_MISC,
        SLOT_LOO_V, SLOT_LOO_VEC,
        SLOT_SP_Z, SLOT_SP_LU, SLOT_SP_LB, SLOT_SP_V, SLOT_SP_W, SLOT_SP_G, SLOT_SP_PART, SLOT_SP_MISC, SLOT_SP_Y,
-       SLOT_SP_S1, SLOT_SP_S2, SLOT_SP_GM, SLOT_SP_GVEC, SLOT_SP_GPART, SLOT_COUNT };
+       SLOT_SP_S1, SLOT_SP_S2, SLOT_SP_GM, SLOT_SP_GVEC, SLOT_SP_GPART, SLOT_SP_DZPART, SLOT_SP_DZ, SLOT_COUNT };
 
 struct gpt_ctx {
     int device = 0;

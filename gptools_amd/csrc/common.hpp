@@ -345,4 +345,13 @@ int64_t kgrad_rect_blocks(int64_t rows, int64_t M);
 int launch_kgrad_rect_diff(hipStream_t st, int id1, int id2, int D, const KParams *d_kps, const KParams *d_kps2, int nh, const double *dX,
                            const int32_t *dnx, int64_t rows, const double *dZ, const int32_t *dnz, int64_t M, const double *dA, int64_t lda,
                            const double *de, double *dpartial, double *dacc);
+// the pair pass of gpt_sparse_grad_z (kgrad_dz.hip): ddz[m][d] += sum_i dA[i][m] k(x_i, z_m; n_i, n_m + e_d) for ONE term id1
+// (* id2 where id2 >= 0) at its parameters k1 (k2); skip_diag: without the pairs i == m (the Z-Z pass, X := Z).  dpartial:
+// kgrad_dz_tiles(rows) x M x D doubles
+int64_t kgrad_dz_tiles(int64_t rows);
+int launch_kgrad_dz(hipStream_t st, int id1, int id2, int D, const KParams &k1, const KParams *k2, const double *dX, const int32_t *dnx,
+                    int64_t rows, const double *dZ, const int32_t *dnz, int64_t M, const double *dA, int64_t lda, int skip_diag,
+                    double *dpartial, double *ddz);
+// 2 A_uu = S - beta beta^T whole (ksparse.hip): S read in its lower triangle
+int launch_sparse_auu2(hipStream_t st, const double *S, int64_t lds, int64_t M, const double *beta, double *dst, int64_t ldd);
 int launch_panel_scalars(hipStream_t st, const double *P, int64_t ldp, int64_t w, int64_t zrow, double *acc);

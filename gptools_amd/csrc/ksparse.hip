@@ -454,3 +454,25 @@ int launch_sparse_grad_mid(hipStream_t st, const double *Binv, int64_t ldb, cons
     GPT_LAUNCH_CHECK();
     return GPT_OK;
 }
+
+// dst (M x M, row stride ldd, both triangles) = S - beta beta^T = 2 A_uu, S given in its lower triangle (entry (i, j) read at (max, min)):
+// the weights of the Z-Z pass of gpt_sparse_grad_z (kgrad_dz.hip)
+__global__ void sparse_auu2_kernel(const double *__restrict__ S, int64_t lds, int64_t M, const double *__restrict__ beta,
+                                   double *__restrict__ dst, int64_t ldd)
+{
+    const int64_t j = (int64_t)blockIdx.x * blockDim.x + threadIdx.x, i = blockIdx.y;
+    if (j >= M) return;
+    const int64_t hi = i > j ? i : j, lo = i > j ? j : i;
+    dst[i * ldd + j] = S[hi * lds + lo] - beta[i] * beta[j];
+}
+
+int launch_sparse_auu2(hipStream_t st, const double *S, int64_t lds, int64_t M, const double *beta, double *dst, int64_t ldd)
+{
+    if (M < 1 || M > 65535 || lds < M || ldd < M || !S || !beta || !dst) {
+        gpt_set_error("sparse_auu2: bad arguments (M=%lld, row strides %lld and %lld)", (long long)M, (long long)lds, (long long)ldd);
+        return GPT_E_ARG;
+    }
+    hipLaunchKernelGGL(sparse_auu2_kernel, dim3((unsigned)((M + 255) / 256), (unsigned)M), dim3(256), 0, st, S, lds, M, beta, dst, ldd);
+    GPT_LAUNCH_CHECK();
+    return GPT_OK;
+}

@@ -26,17 +26,20 @@ __all__ = ["SparseGaussianProcess"]
 
 
 class SparseGaussianProcess(GaussianProcess):
-    """Gaussian process regression through ``M`` fixed inducing inputs.
+    """Gaussian process regression through ``M`` inducing inputs.
 
     ``k``, ``noise_k``, ``X``, ``y``, ``err_y``, ``n``, ``mu``, ``diag_factor``, ``verbose``, ``device`` as
     :class:`GaussianProcess`.  ``Z`` (M, D): the inducing inputs, ``n_Z`` their derivative orders (scalar or (M, D)); they are
-    fixed -- not hyperparameters -- and :meth:`set_inducing` replaces them.  ``method``: ``"fitc"``, ``"vfe"`` or ``"dtc"``.
+    not hyperparameters: :meth:`set_inducing` replaces them, :meth:`inducing_gradient` differentiates the objective with respect
+    to ``Z`` and :meth:`optimize_inducing` moves ``Z`` to maximise it (``n_Z`` stays what it is).  ``method``: ``"fitc"``, ``"vfe"`` or ``"dtc"``.
     ``jitter``: added to the diagonal of ``k(Z, Z)`` (absolute).  ``chunk_rows``: training rows per pass over the data, a
     multiple of 64 (``None``: chosen by the library from a byte budget); predictions of the mean and the standard deviation send
     their test points through chunks of the same size.
 
     Supported: ``update_hyperparameters`` (value only), ``compute_K_L_alpha_ll`` (sets ``ll`` and ``ll_parts``),
-    :meth:`sparse_gradient` (the gradient of the objective, ``gpt_sparse_grad_diff``), ``optimize_hyperparameters`` (scipy on the
+    :meth:`sparse_gradient` (the gradient of the objective, ``gpt_sparse_grad_diff``), :meth:`inducing_gradient` and
+    :meth:`optimize_inducing` (``gpt_sparse_grad_z``: ``n_Z = 0`` for every kernel; derivative rows among ``Z`` are refused for a
+    Matern52 factor and, in its coordinate, for a Gibbs factor), ``optimize_hyperparameters`` (scipy on the
     value, or with ``gradient="sparse"`` on the value and that gradient; ``random_starts`` one after another), ``compute_ll_matrix`` and the
     host-stepped sampler (one evaluation per vector), ``predict`` and ``draw_sample`` (through the returned covariance).
 
@@ -75,14 +78,15 @@ class SparseGaussianProcess(GaussianProcess):
 
     # ---- inducing inputs, data -------------------------------------------------------------------
     def set_inducing(self, Z, n_Z=0):
-        """Replace the inducing inputs ``Z`` (M, D) and their derivative orders ``n_Z`` (scalar or (M, D))."""
+        """Replace the inducing inputs ``Z`` (M, D) and their derivative orders ``n_Z`` (scalar or (M, D)).  On a context that
+        holds the data only ``Z`` is sent again (the library drops its sparse fit with it); ``X`` stays where it is."""
         Z = _ingest.points(Z, self.num_dim, "Z")
         if Z.shape[0] < 1 or not np.all(np.isfinite(Z)):
             raise ValueError("Z must hold at least one point and finite entries only")
         self.Z = Z
         self.n_Z = _ingest.derivative_orders(n_Z, Z, self.num_dim, "n_Z", column_rule="row")
         self.K_up_to_date = False
-        self._data_on_device = False
+        self._inducing_on_device = False
 
     def add_data(self, X, y, err_y=0, n=0, T=None):
         if T is not None:
@@ -92,6 +96,16 @@ class SparseGaussianProcess(GaussianProcess):
     def _upload_data(self, ctx):
         ctx.set_data(self.X, self.n)
         ctx.sparse_set_inducing(self.Z, self.n_Z)
+
+    def _resident_ctx(self):
+        """The instance's context with the data and the inducing inputs on it: each uploaded unless resident (an upload of the data
+        sends ``Z`` after it)."""
+        fresh = not self._data_on_device
+        ctx = super(SparseGaussianProcess, self)._resident_ctx()
+        if not fresh and not getattr(self, "_inducing_on_device", False):
+            ctx.sparse_set_inducing(self.Z, self.n_Z)
+        self._inducing_on_device = True
+        return ctx
 
     # ---- what this class does not do ---------------------------------------------------------------
     def _sparse_refusal(self):
@@ -167,18 +181,101 @@ class SparseGaussianProcess(GaussianProcess):
                                                                          inf_on_error=inf_on_error)
 
     # ---- the gradient (gpt_sparse_grad_diff) ---------------------------------------------
-    def sparse_gradient(self, rel_step=6e-6):
+    def sparse_gradient(self, rel_step=6e-6, inducing=False):
         """Gradient of the sparse objective plus the log hyperprior with respect to the free hyperparameters at their current
         values (``gpt_sparse_grad_diff``): one more pass over the data in chunks, whatever the number of parameters -- per free
         kernel parameter the term's central difference, eps = ``rel_step`` max(1, abs(theta)), is taken per pair (x_i, z_m),
         (z_m, z_m') and (x_i, x_i) before it meets its weight.  The noise parameter, the mean function's parameters and the
         hyperprior's derivative as in :meth:`GaussianProcess.ll_gradient`.  Fits first if the hyperparameters changed; they and
-        ``K_up_to_date`` are afterwards what they were.  The inducing inputs are fixed: no entry for ``Z``."""
+        ``K_up_to_date`` are afterwards what they were.  The result has no entry for ``Z``; with ``inducing=True`` the return value is
+        ``(gradient, dZ)``, ``dZ`` as :meth:`inducing_gradient` returns it, both from ONE library call (``gpt_sparse_grad_z``)."""
         self._sparse_refusal()
         self.compute_K_L_alpha_ll()
         slot, tix, pa, pb, denom = self._ll_gradient_stencil(rel_step)
-        g_dev, alpha = self._ctx.sparse_grad_diff(tix, pa, pb, denom, self._y_alph(), self.err_y, want_alpha=self.mu is not None)
-        return self._ll_gradient_assemble(slot, g_dev, lambda: alpha)
+        if not inducing:
+            g_dev, alpha = self._ctx.sparse_grad_diff(tix, pa, pb, denom, self._y_alph(), self.err_y, want_alpha=self.mu is not None)
+            return self._ll_gradient_assemble(slot, g_dev, lambda: alpha)
+        g_dev, alpha, dZ = self._ctx.sparse_grad_z(tix, pa, pb, denom, self._y_alph(), self.err_y, want_alpha=self.mu is not None)
+        return self._ll_gradient_assemble(slot, g_dev, lambda: alpha), self._finite_dz(dZ)
+
+    # ---- the inducing inputs (gpt_sparse_grad_z; DESIGN.md 18.9) ------------------------------------------
+    @staticmethod
+    def _finite_dz(dZ):
+        if not np.all(np.isfinite(dZ)):
+            raise FloatingPointError("d ll / d Z holds %d non-finite entries: the kernel's derivative does not exist at a pair the "
+                                     "pass meets (a Matern kernel of small order where a training point coincides with an inducing "
+                                     "input)" % int((~np.isfinite(dZ)).sum()))
+        return dZ
+
+    def inducing_gradient(self):
+        """``d ll / d Z`` as an (M, D) array (``gpt_sparse_grad_z``): the gradient of the sparse objective with respect to every
+        coordinate of the inducing inputs from one more pass over the data -- the derivative of a covariance entry with respect to
+        a coordinate of ``z_m`` is the kernel with that point's derivative order raised by one, so nothing is differenced.  The log
+        hyperprior does not depend on ``Z``.  Fits first if needed; hyperparameters and ``K_up_to_date`` are afterwards what they
+        were.  ``FloatingPointError`` if an entry is not finite."""
+        self._sparse_refusal()
+        self.compute_K_L_alpha_ll()
+        _, _, dZ = self._ctx.sparse_grad_z([], [], [], [], self._y_alph(), self.err_y)
+        return self._finite_dz(dZ)
+
+    def _inducing_box(self, bounds):
+        """(M D, 2): the box of every coordinate of ``Z``, row-major as ``Z.ravel()``.  ``None``: the bounding box of ``X`` in the
+        coordinate's dimension; a (D, 2) array: one box per dimension; (M, D, 2): one per coordinate."""
+        M, D = self.Z.shape
+        if bounds is None:
+            if self.X is None:
+                raise GPArgumentError("No data have been added to the SparseGaussianProcess!")
+            bounds = np.stack([np.asarray(self.X, dtype=float).min(0), np.asarray(self.X, dtype=float).max(0)], axis=1)
+        box = np.asarray(bounds, dtype=float)
+        if box.shape == (D, 2):
+            box = np.broadcast_to(box, (M, D, 2))
+        if box.shape != (M, D, 2) or not np.all(box[..., 0] <= box[..., 1]):
+            raise ValueError("bounds must be None, a (D, 2) or an (M, D, 2) array of (low, high) pairs with low <= high")
+        return box.reshape(M * D, 2).copy()
+
+    def optimize_inducing(self, method="L-BFGS-B", joint=False, bounds=None, opt_kwargs={}):
+        """Move the inducing inputs to maximise the sparse objective: ``scipy.optimize.minimize`` on minus the log-posterior over
+        ``vec(Z)`` -- with ``joint=True`` over ``[free hyperparameters, vec(Z)]``, the hyperparameters within their own bounds --
+        with the gradient of :meth:`inducing_gradient` / :meth:`sparse_gradient` as ``jac``: one fit and one gradient pass per
+        step.  ``bounds``: the box of ``Z`` (``None``: every coordinate within the bounding box of ``X`` in its dimension; a (D, 2)
+        or (M, D, 2) array overrides it).  A fit that fails counts as ``+inf`` with a zero gradient.  On return ``Z`` (and, with
+        ``joint``, the hyperparameters) are the optimum found; ``n_Z`` is not changed.  If the optimiser raises, ``Z`` and the
+        hyperparameters are put back.  Returns scipy's result."""
+        import scipy.optimize
+        self._sparse_refusal()
+        if "jac" in (opt_kwargs or {}) or "bounds" in (opt_kwargs or {}):
+            raise ValueError("optimize_inducing supplies jac and bounds itself")
+        M, D = self.Z.shape
+        Z0, theta0 = self.Z.copy(), np.array(self.free_params[:], dtype=float)
+        nfree = len(theta0) if joint else 0
+        zbox = self._inducing_box(bounds)
+        box = np.vstack([np.array(self.free_param_bounds[:], dtype=float).reshape(-1, 2), zbox]) if joint else zbox
+        box[:, 0], box[:, 1] = np.where(np.isnan(box[:, 0]), -np.inf, box[:, 0]), np.where(np.isnan(box[:, 1]), np.inf, box[:, 1])
+        x0 = np.concatenate([theta0[:nfree], np.clip(Z0.ravel(), zbox[:, 0], zbox[:, 1])])
+        self._ctx                              # (no device: GPTBackendError here, not a +inf objective at every step)
+
+        def assign(x):
+            self.set_inducing(x[nfree:].reshape(M, D), self.n_Z)
+            return self.update_hyperparameters(x[:nfree] if joint else theta0)
+
+        def fun(x):
+            x = np.array(x, dtype=float)
+            f0 = assign(x)
+            if not np.isfinite(f0):
+                return np.inf, np.zeros(len(x))
+            if joint:
+                g, dZ = self.sparse_gradient(inducing=True)
+            else:
+                g, dZ = np.zeros(0), self.inducing_gradient()
+            return f0, -1.0 * np.concatenate([g, dZ.ravel()])
+        try:
+            res = scipy.optimize.minimize(fun, x0, method=method, jac=True, bounds=[tuple(b) for b in box], **dict(opt_kwargs or {}))
+            assign(np.array(res.x, dtype=float))
+        except Exception:
+            self.set_inducing(Z0, self.n_Z)
+            self._assign_free(theta0)
+            raise
+        return res
 
     def _sparse_grad_jac(self):
         """``jac`` for scipy beside ``update_hyperparameters`` as ``fun``: minus :meth:`sparse_gradient`, zeros where the value is

@@ -780,6 +780,29 @@ int gpt_dev_sparse_grad_pairs(gpt_ctx *ctx, int kernel_id, int kernel_id2, int D
                               const double *dZ, const int32_t *dnz, int64_t M, const double *dA, int64_t lda, const double *d_e,
                               double *out);
 
+/* gpt_sparse_grad_diff and, from the same pass, the gradient with respect to the inducing inputs.  The
+ * derivative of a covariance entry with respect to coordinate d of z_m is the pair function with z_m's derivative order raised by one
+ * in dimension d, so with the adjoints above
+ *   dz_out[m][d] = sum_i A_fu[i,m] k(x_i, z_m; n_i, n_m + e_d) + 2 sum_{m' != m} A_uu[m',m] k(z_m', z_m; n_m', n_m + e_d)
+ * summed over the model's terms at the fitted parameters: M x D doubles, row-major, host; nothing is divided by a step (the pair
+ * m' = m is left out: K_uu[m][m] does not depend on z_m).  out and alpha_out are gpt_sparse_grad_diff's, bit for bit; nh = 0 gives
+ * out[0] = sum_i g_i and dz_out.  The pass meets the orders n_Z + e_d: the fitted model is held to the order rules of the fit at
+ * the raised orders before anything is launched -- n_Z = 0 works for every kernel; derivative rows among Z are refused for a
+ * Matern52 factor (GPT_E_VALUE) and, in its coordinate, for a Gibbs factor (GPT_E_NOTIMPL); the other statuses are
+ * gpt_sparse_grad_diff's.  Fixed summation orders, no floating-point atomics: the same call gives the same bits.  A non-finite
+ * entry of dz_out is returned as it is. */
+int gpt_sparse_grad_z(gpt_ctx *ctx, int nh, const int *term_idx, const double *params_a, const double *params_b, const double *denom,
+                      const double *y, const double *err_y, double *out, double *alpha_out, double *dz_out);
+
+/* Device API: the pair pass of gpt_sparse_grad_z alone for ONE term, kernel_id (* kernel_id2 where >= 0) of num_dim D at `params`
+ * (host; nparams of them, nparams1 the first factor's): out[m][d] = sum_i dA[i][m] k(x_i, z_m; n_i, n_m + e_d), M x D doubles on the
+ * host, written, not accumulated.  dX (rows x D) and dZ (M x D) with orders dnx / dnz; max_order: the largest order sum of a point
+ * of the pass, the raised n_Z + e_d included; dA rows x lda, M <= lda; skip_diag != 0: without the pairs i == m (X := Z).  Row
+ * tiles of 64 are added in index order: the same call gives the same bits. */
+int gpt_dev_sparse_grad_dz_pairs(gpt_ctx *ctx, int kernel_id, int kernel_id2, int D, int max_order, const double *params, int nparams,
+                                 int nparams1, const double *dX, const int32_t *dnx, int64_t rows, const double *dZ, const int32_t *dnz,
+                                 int64_t M, const double *dA, int64_t lda, int skip_diag, double *out);
+
 /* ---- compiled schedules of the partitioned engines (round 6) ------------------------------------------------------------
  * The one-process-per-GPU block-cyclic Cholesky of gptools_amd/dist.py issues ~1000 operations per rank and evaluation; which
  * ones, on which buffers, in which order is static per (N, nb, world, rank).  The Python layer records its step loop once as an
