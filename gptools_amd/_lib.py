@@ -139,6 +139,12 @@ SIGNATURES = {
     "gpt_sparse_grad_z": (C.c_int, [_vp, C.c_int, _ip, _dp, _dp, _dp, _dp, _dp, _dp, _dp, _dp]),
     "gpt_dev_sparse_grad_dz_pairs": (C.c_int, [_vp, C.c_int, C.c_int, C.c_int, C.c_int, _dp, C.c_int, C.c_int, _vp, _vp, _i64, _vp, _vp, _i64,
                                                _vp, _i64, C.c_int, _dp]),
+    "gpt_sparse_select_inducing": (C.c_int, [_vp, C.c_int, _ip, _ip, _dp, _ip, _ip, _ip, _i64, _i64, C.c_double, _ip, _dp, _dp,
+                                             C.POINTER(_i64)]),
+    "gpt_dev_greedy_parts": (_i64, [_i64]),
+    "gpt_dev_greedy_update": (C.c_int, [_vp, _vp, _i64, _i64, _i64, _vp, _vp, _vp, _vp, _vp, _vp, _vp, _vp]),
+    "gpt_dev_greedy_pick": (C.c_int, [_vp, _i64, _i64, C.c_double, _vp, _vp, _i64, _vp, _vp, C.c_int, _vp, _i64, _vp, _vp, _vp, _vp, _vp, _vp,
+                                      _vp, _vp]),
 }
 
 _lib = None
@@ -798,6 +804,37 @@ class Context(object):
         out = np.empty(int(self._sparse_M))
         check(self._lib.gpt_sparse_get_c(self.handle, dptr(out)))
         return out
+
+    def sparse_select_inducing(self, terms, M, candidates=None, tol=0.0):
+        """gpt_sparse_select_inducing on the resident data: ``terms`` as :meth:`fit_terms` takes them, ``candidates`` strictly ascending
+        row indices (``None``: every row whose derivative orders are all zero) -> ``(indices, dmax, trace)`` cut to the ``count`` pivots
+        the stop rule let through: ``count`` row indices, ``count`` values of dmax, ``count + 1`` of the trace."""
+        ids, ids2, npar, npar1, flat = self._pack_terms(terms)
+        M = int(M)
+        cand = None if candidates is None else i32(candidates)
+        idx = np.full(max(M, 1), -1, dtype=np.int32)
+        dmax, trace = np.full(max(M, 1), np.nan), np.full(max(M, 1) + 1, np.nan)
+        count = _i64(0)
+        check(self._lib.gpt_sparse_select_inducing(self.handle, len(ids), iptr(ids), iptr(ids2), dptr(flat), iptr(npar), iptr(npar1),
+                                                   iptr(cand), 0 if cand is None else len(cand), M, float(tol), iptr(idx), dptr(dmax),
+                                                   dptr(trace), C.byref(count)))
+        n = int(count.value)
+        return idx[:n].astype(np.int64), dmax[:n], trace[:n + 1]
+
+    def dev_greedy_parts(self, rows):
+        """gpt_dev_greedy_parts: the partials (workgroups) of ``rows`` candidate rows."""
+        return int(self._lib.gpt_dev_greedy_parts(int(rows)))
+
+    def dev_greedy_update(self, dL, ld, rows, j, d_col, d_resid, d_mark, d_prow, d_scal, d_words, d_part, d_pidx):
+        """gpt_dev_greedy_update on raw device pointers (integers), on the context's stream; the caller synchronises."""
+        check(self._lib.gpt_dev_greedy_update(self.handle, dL, int(ld), int(rows), int(j), d_col, d_resid, d_mark, d_prow, d_scal, d_words,
+                                              d_part, d_pidx))
+
+    def dev_greedy_pick(self, j, M, tol, d_part, d_pidx, nparts, d_cand, dX, D, dL, ld, d_mark, d_scal, d_words, d_idx, d_dmax, d_trace,
+                        d_xp, d_prow):
+        """gpt_dev_greedy_pick on raw device pointers (integers; ``d_cand`` may be ``None``), on the context's stream."""
+        check(self._lib.gpt_dev_greedy_pick(self.handle, int(j), int(M), float(tol), d_part, d_pidx, int(nparts), d_cand, dX, int(D), dL,
+                                            int(ld), d_mark, d_scal, d_words, d_idx, d_dmax, d_trace, d_xp, d_prow))
 
     def cov_sample(self, diag_add, rand_vars):
         """``cholesky(cov + diag_add I) @ rand_vars`` for the covariance the last ``predict(..., want=2, device_cov=True)`` left

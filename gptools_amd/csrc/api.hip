@@ -55,7 +55,8 @@ enum { SLOT_XI = 0, SLOT_XJ, SLOT_NI, SLOT_NJ, SLOT_OUT, SLOT_KST, SLOT_KSS, SLO
        SLOT_PB_V, SLOT_PB_COV, SLOT_PB_MISC, SLOT_XSW, SLOT_SS, SLOT_SI, SLOT_SJ, SLOT_WB_X, SLOT_WB_S, SLOT_WB_P, SLOT_GKP, SLOT_GB_U, SLOT_GB_W, SLOT_GB_MISC,
        SLOT_LOO_V, SLOT_LOO_VEC,
        SLOT_SP_Z, SLOT_SP_LU, SLOT_SP_LB, SLOT_SP_V, SLOT_SP_W, SLOT_SP_G, SLOT_SP_PART, SLOT_SP_MISC, SLOT_SP_Y,
-       SLOT_SP_S1, SLOT_SP_S2, SLOT_SP_GM, SLOT_SP_GVEC, SLOT_SP_GPART, SLOT_SP_DZPART, SLOT_SP_DZ, SLOT_COUNT };
+       SLOT_SP_S1, SLOT_SP_S2, SLOT_SP_GM, SLOT_SP_GVEC, SLOT_SP_GPART, SLOT_SP_DZPART, SLOT_SP_DZ,
+       SLOT_SP_SEL_L, SLOT_SP_SEL_X, SLOT_SP_SEL_MISC, SLOT_COUNT };
 
 struct gpt_ctx {
     int device = 0;
@@ -173,6 +174,7 @@ struct gpt_ctx {
     // The INDUCING-POINT state (api_sparse.inc), beside the dense factor and independent of it: the inducing
     // inputs (SLOT_SP_Z) and, after a gpt_sparse_fit that succeeded, L_u (SLOT_SP_LU), the augmented L_B with c in its row M
     // (SLOT_SP_LB), each with its packed workspace behind the matrix.  gpt_set_data and gpt_sparse_set_inducing drop all of it.
+    // The greedy selection of inducing inputs (api_sparse_select.inc) keeps no state here: it works in SLOT_SP_SEL_* and reads the data only.
     int64_t sp_M = 0;                  // inducing points resident (0: none)
     long sp_zmaxsum = 0, sp_zcolmax[GPT_MAX_DIM] = {};      // their largest order row sum / order per coordinate
     bool sp_fitted = false;
@@ -255,6 +257,7 @@ static int stream_follows(gpt_ctx *c, hipStream_t from, hipStream_t to, size_t i
 #include "api_predict.inc"      // gpt_predict, gpt_cov_sample, gpt_solve_L / gpt_cho_solve, gpt_potrf_host / gpt_gemm_nt_host
 #include "api_dev.inc"      // device API (gpt_dev_*): raw device pointers on the context's streams, for the one-process-per-GPU engines
 #include "api_sparse.inc"      // inducing-point approximations (FITC / VFE / DTC): gpt_sparse_set_inducing, gpt_sparse_fit, gpt_sparse_predict
+#include "api_sparse_select.inc"      // greedy conditional-variance choice of the inducing inputs: gpt_sparse_select_inducing, gpt_dev_greedy_*
 #include "api_sparse_grad.inc"      // the gradient of the sparse objective: gpt_sparse_grad_diff and the device API of its kernels
 #include "api_plan.inc"      // compiled schedules of the partitioned engines: gpt_plan_* (op list replay, RCCL called directly)
 #include "api_ensemble.inc"      // gpt_ensemble_run: the ensemble sampler's loop (ensemble.hpp) around the batched fit

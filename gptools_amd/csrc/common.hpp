@@ -354,4 +354,17 @@ int launch_kgrad_dz(hipStream_t st, int id1, int id2, int D, const KParams &k1, 
                     double *dpartial, double *ddz);
 // 2 A_uu = S - beta beta^T whole (ksparse.hip): S read in its lower triangle
 int launch_sparse_auu2(hipStream_t st, const double *S, int64_t lds, int64_t M, const double *beta, double *dst, int64_t ldd);
+// greedy conditional-variance selection of inducing inputs (kgreedy.hip): a column-major factor (column stride ld >= rows),
+// one partial per GREEDY_WG rows -- part[b] the largest residual, pidx[b] the lowest row at it, part[nparts + b] the sum of max(., 0) --
+// scal / words as GPT_GREEDY_S_* / GPT_GREEDY_W_* (gpt_hip.h) index them
+#define GREEDY_WG GPT_GREEDY_ROWS_PER_PART
+#define GREEDY_UNROLL 16
+int64_t greedy_blocks(int64_t rows);
+int launch_greedy_init(hipStream_t st, int64_t rows, const double *resid, int32_t *mark, double *part, int32_t *pidx);
+int launch_greedy_update(hipStream_t st, const double *L, int64_t ld, int64_t rows, int64_t j, double *col, double *resid, const int32_t *mark,
+                         const double *prow, const double *scal, const int32_t *words, double *part, int32_t *pidx);
+int launch_greedy_pick(hipStream_t st, int64_t j, int64_t M, double tol, const double *part, const int32_t *pidx, int64_t nparts,
+                       const int32_t *cand, const double *X, int D, const double *L, int64_t ld, int32_t *mark, double *scal, int32_t *words,
+                       int32_t *idx, double *dmax, double *trace, double *xp, double *prow);
+int launch_greedy_gather(hipStream_t st, const double *X, const int32_t *cand, int64_t ncand, int D, double *Xc, int32_t *nc);
 int launch_panel_scalars(hipStream_t st, const double *P, int64_t ldp, int64_t w, int64_t zrow, double *acc);

@@ -683,8 +683,13 @@ __device__ __forceinline__ double gibbs_core(double s2, double xi, double a, dou
     const double t = fma(0.5 * y0, fma(-(s * y0), y0, 1.0), y0);
     const double u = t * t;
     const double d = xi - xj;
+    // sqrt(2 a b / (a^2 + b^2)) is EXACTLY 1 for equal length scales (the reference's quotient 2 l l / (l l + l l) is 1 to the last bit), where
+    // the product of the hoisted roots with t is 1 only within a few u: k(x, x) = sigma_f^2 then has the same bits at every x, as on the
+    // host -- the greedy selection of inducing inputs (kgreedy.hip) compares these variances as doubles at its step 0.  (a = b = 0
+    // stays the 0 * inf it was.)
+    const double pref = (a == b && a != 0.0) ? 1.0 : ra * rb * t;
     // exp_neg drops a NaN of d^2 u; every such NaN (s, d) is in ra rb t as well
-    const double k = (s2 * (ra * rb * t)) * exp_neg(d * d * u);
+    const double k = (s2 * pref) * exp_neg(d * d * u);
     if (!need_d) return k;
     const double du = d * u;
     const double w = fma(2.0 * du, du, -u);

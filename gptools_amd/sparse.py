@@ -22,7 +22,77 @@ from .error_handling import GPArgumentError
 from .gaussian_process import GaussianProcess
 from .kernel import ZeroKernel, DiagonalNoiseKernel
 
-__all__ = ["SparseGaussianProcess"]
+__all__ = ["SparseGaussianProcess", "greedy_inducing"]
+
+
+def _device_terms(gp):
+    """The terms of ``gp``'s covariance kernel as the library takes them (:meth:`GaussianProcess._device_model`); raises for a
+    kernel the sparse path does not take: the class and :func:`greedy_inducing` resolve, and refuse, through this."""
+    model = gp._device_model()
+    if model is None:
+        raise NotImplementedError("the covariance kernel is not one the library evaluates itself (a Python-defined kernel, or "
+                                  "a tree of kernels it does not take): SparseGaussianProcess has no host route")
+    terms, layers = model
+    if layers:
+        raise NotImplementedError("SparseGaussianProcess does not take warped kernels (WarpedKernel)")
+    return terms
+
+
+def _greedy_select(ctx, terms, X, n, M, candidates, max_candidates, seed, tol):
+    """Greedy conditional-variance selection on a context that holds ``X`` and ``n`` (``gpt_sparse_select_inducing``): resolves the
+    candidate rows, returns ``(Z, info)`` and warns if the stop rule ended the selection early."""
+    M = int(M)
+    cand = None
+    if candidates is not None:
+        if max_candidates is not None:
+            raise ValueError("pass candidates or max_candidates, not both")
+        cand = np.asarray(candidates)
+        if cand.ndim != 1 or cand.size < 1 or not np.issubdtype(cand.dtype, np.integer):
+            raise ValueError("candidates must be a non-empty vector of row indices")
+        cand = np.sort(cand.astype(np.int64))
+        if np.any(cand[1:] == cand[:-1]):
+            raise ValueError("candidates holds a row more than once")
+        if cand[0] < 0 or cand[-1] >= X.shape[0]:
+            raise ValueError("candidates must lie within [0, %d)" % X.shape[0])
+    elif max_candidates is not None:
+        if int(max_candidates) != max_candidates or max_candidates < 1:
+            raise ValueError("max_candidates must be a positive integer, got %r" % (max_candidates,))
+        pool = np.flatnonzero(np.all(np.asarray(n) == 0, axis=1))
+        if int(max_candidates) < pool.size:
+            cand = np.sort(np.random.RandomState(seed).choice(pool, int(max_candidates), replace=False))
+    indices, dmax, trace = ctx.sparse_select_inducing(terms, M, cand, tol)
+    if len(indices) < M:
+        warnings.warn("greedy selection stopped after %d of %d inducing inputs: the largest remaining conditional variance is not "
+                      "above tol = %g times the first (%.3g), or not a positive finite number; the remaining trace is %.3g"
+                      % (len(indices), M, tol, dmax[0], trace[-1]), RuntimeWarning)
+    return np.array(X[indices], dtype=float), {"indices": indices, "dmax": dmax, "trace": trace}
+
+
+def greedy_inducing(k, X, M, n=0, candidates=None, max_candidates=None, seed=0, tol=0.0, device=0):
+    """Choose ``M`` inducing inputs among the rows of ``X`` by greedy conditional-variance selection (the partial pivoted Cholesky of
+    ``K_ff``) on the GPU: each step adds the row whose variance, conditioned on the rows chosen so far, is
+    largest (ties: the lowest row; for a stationary kernel the first pivot is therefore the lowest candidate).  It needs no ``y``, no
+    noise level and no optimiser, costs ``O(N M^2)`` and holds an ``N x M`` factor on the device.
+
+    ``k``: a covariance kernel :class:`SparseGaussianProcess` takes (resolved and refused as there), at its current parameters.
+    ``n``: the derivative orders of ``X``; only rows whose orders are all zero are candidates.  ``candidates``: row indices to choose
+    among (sorted here; duplicates are refused).  ``max_candidates``: choose among a seeded (``seed``) subsample without replacement
+    of that many order-zero rows -- for data whose ``N x M`` factor would not fit.  ``tol``: stop once the largest remaining
+    conditional variance is at most ``tol`` times the first (a warning; fewer than ``M`` rows come back).
+
+    Returns ``(Z, info)``: ``Z = X[info["indices"]]``; ``info["dmax"][j]`` the conditional variance of pivot ``j`` when it was chosen;
+    ``info["trace"][j]`` the sum of the candidates' conditional variances after ``j`` pivots (length ``count + 1``) -- the quantity
+    the VFE objective penalises, ``tr(K_ff - K_fu K_uu^-1 K_uf)``: it tells how large ``M`` must be."""
+    probe = GaussianProcess(k, device=device)
+    terms = _device_terms(probe)
+    X = _ingest.points(X, probe.num_dim)
+    n = _ingest.derivative_orders(n, X, probe.num_dim, column_rule="not-column")
+    ctx = _lib.Context(device)
+    try:
+        ctx.set_data(X, n)
+        return _greedy_select(ctx, terms, X, n, M, candidates, max_candidates, seed, tol)
+    finally:
+        ctx.close()
 
 
 class SparseGaussianProcess(GaussianProcess):
@@ -30,8 +100,9 @@ class SparseGaussianProcess(GaussianProcess):
 
     ``k``, ``noise_k``, ``X``, ``y``, ``err_y``, ``n``, ``mu``, ``diag_factor``, ``verbose``, ``device`` as
     :class:`GaussianProcess`.  ``Z`` (M, D): the inducing inputs, ``n_Z`` their derivative orders (scalar or (M, D)); they are
-    not hyperparameters: :meth:`set_inducing` replaces them, :meth:`inducing_gradient` differentiates the objective with respect
-    to ``Z`` and :meth:`optimize_inducing` moves ``Z`` to maximise it (``n_Z`` stays what it is).  ``method``: ``"fitc"``, ``"vfe"`` or ``"dtc"``.
+    not hyperparameters: :meth:`set_inducing` replaces them, :meth:`select_inducing` (or :func:`greedy_inducing`, before there is
+    an instance) chooses them among the rows of ``X`` by greedy conditional-variance selection, :meth:`inducing_gradient`
+    differentiates the objective with respect to ``Z`` and :meth:`optimize_inducing` moves ``Z`` to maximise it (``n_Z`` stays what it is).  ``method``: ``"fitc"``, ``"vfe"`` or ``"dtc"``.
     ``jitter``: added to the diagonal of ``k(Z, Z)`` (absolute).  ``chunk_rows``: training rows per pass over the data, a
     multiple of 64 (``None``: chosen by the library from a byte budget); predictions of the mean and the standard deviation send
     their test points through chunks of the same size.
@@ -93,6 +164,21 @@ class SparseGaussianProcess(GaussianProcess):
             raise NotImplementedError("SparseGaussianProcess does not take a linear transform T")
         super(SparseGaussianProcess, self).add_data(X, y, err_y=err_y, n=n)
 
+    def select_inducing(self, M, candidates=None, max_candidates=None, seed=0, tol=0.0, set=True):
+        """Choose ``M`` inducing inputs among the rows of the instance's data by greedy conditional-variance selection at the
+        current hyperparameters (``gpt_sparse_select_inducing`` on the resident data; arguments and ``(Z, info)`` as
+        :func:`greedy_inducing`).  ``set=True``: ``set_inducing(Z, 0)`` with the result.  If the stop rule ends the selection early
+        it warns and ``Z`` has ``count`` rows.  A resident fit is not disturbed by the selection itself."""
+        if self.X is None:
+            raise GPArgumentError("No data have been added to the SparseGaussianProcess!")
+        terms = self._sparse_refusal()
+        ctx = self._resident_ctx()
+        ctx.set_warp(None)
+        Z, info = _greedy_select(ctx, terms, self.X, self.n, M, candidates, max_candidates, seed, tol)
+        if set:
+            self.set_inducing(Z, 0)
+        return Z, info
+
     def _upload_data(self, ctx):
         ctx.set_data(self.X, self.n)
         ctx.sparse_set_inducing(self.Z, self.n_Z)
@@ -119,14 +205,7 @@ class SparseGaussianProcess(GaussianProcess):
         if not isinstance(self.noise_k, (ZeroKernel, DiagonalNoiseKernel)):
             raise NotImplementedError("SparseGaussianProcess takes a ZeroKernel or DiagonalNoiseKernel as noise_k, not %s"
                                       % type(self.noise_k).__name__)
-        model = self._device_model()
-        if model is None:
-            raise NotImplementedError("the covariance kernel is not one the library evaluates itself (a Python-defined kernel, or "
-                                      "a tree of kernels it does not take): SparseGaussianProcess has no host route")
-        terms, layers = model
-        if layers:
-            raise NotImplementedError("SparseGaussianProcess does not take warped kernels (WarpedKernel)")
-        return terms
+        return _device_terms(self)
 
     def _refuse(what):
         def method(self, *args, **kwargs):

@@ -803,6 +803,53 @@ int gpt_dev_sparse_grad_dz_pairs(gpt_ctx *ctx, int kernel_id, int kernel_id2, in
                                  int nparams1, const double *dX, const int32_t *dnx, int64_t rows, const double *dZ, const int32_t *dnz,
                                  int64_t M, const double *dA, int64_t lda, int skip_diag, double *out);
 
+/* Greedy conditional-variance choice of M inducing inputs among rows of the resident data: the partial
+ * pivoted Cholesky of K_ff.  The model arguments are gpt_sparse_fit's, parsed against the training orders.  cand: ncand row indices,
+ * strictly ascending, every one a row whose derivative orders are all zero; NULL: every such row of the data (ncand is ignored).
+ *   d_i = k(x_i, x_i);  for j = 0 .. M-1:  p_j = the unselected candidate with the largest d_i (equal as doubles: the lowest row),
+ *   dmax_j = d_{p_j};  stop (count = j) if j > 0 and dmax_j <= tol * dmax_0, or if dmax_j is not a positive finite number;
+ *   l_i = (k(x_i, x_{p_j}) - sum_{t<j} L[i,t] L[p_j,t]) / sqrt(dmax_j),  L[i,j] = l_i,  d_i -= l_i^2  for EVERY candidate i;
+ *   trace_{j+1} = sum over the unselected candidates of max(d_i, 0)   (trace_0 = sum of the initial d_i).
+ * A selected row is excluded by its mark, never by its residual.  For a stationary kernel step 0 is a complete tie: the first pivot is
+ * the lowest candidate.  idx_out (M), dmax_out (M), trace_out (M + 1), *count_out: host; the entries at and past count (trace: past
+ * count) are -1 / NaN.  trace_count is tr(K_ff - K_fu K_uu^-1 K_uf) over the candidates, the quantity the VFE objective penalises.
+ * The whole loop is enqueued on the context's stream without a host synchronisation between the steps -- per step one pick launch,
+ * the builder's launches for the column k(x_p, .) (the pair (x_p, x_i), pivot first: the builder's bits) and one update launch -- and
+ * read back once.  Device memory: the factor, (ncand rounded up to 64) x M doubles, column-major, in a slot of its own; neither the
+ * dense factor nor the resident sparse state is touched.  Fixed summation orders: the same call gives the same bits.
+ * GPT_E_STATE without gpt_set_data; GPT_E_NOTIMPL with gpt_set_T or warp layers; GPT_E_ARG for M < 1, M > ncand, M > 65000, tol < 0,
+ * a candidate list that is not strictly ascending or out of range, or a candidate with a non-zero order; GPT_E_NOMEM (the byte
+ * count in the message); GPT_E_VALUE if dmax_0 is not a positive finite number. */
+int gpt_sparse_select_inducing(gpt_ctx *ctx, int nterms, const int *kernel_ids, const int *kernel_ids2, const double *params,
+                               const int *nparams, const int *nparams1, const int32_t *cand, int64_t ncand, int64_t M, double tol,
+                               int32_t *idx_out, double *dmax_out, double *trace_out, int64_t *count_out);
+
+/* Device API: the two kernels of that loop alone, on raw device pointers and the context's stream (csrc/kgreedy.hip).
+ * Shared state: d_scal, two doubles ([GPT_GREEDY_S_DMAX] the current pivot's dmax, [GPT_GREEDY_S_DMAX0] dmax_0); d_words, four int32
+ * ([GPT_GREEDY_W_STOP] raised by the stop rule: both kernels then return at once, [GPT_GREEDY_W_COUNT] pivots chosen so far,
+ * [GPT_GREEDY_W_PIVOT] the current pivot's row, [GPT_GREEDY_W_BAD] dmax_0 was not a positive finite number); partials, one per
+ * GPT_GREEDY_ROWS_PER_PART rows, nparts = gpt_dev_greedy_parts(rows): d_part[b] the largest residual among workgroup b's unselected
+ * rows (-inf: none), d_pidx[b] the lowest row at that value (INT32_MAX: none), d_part[nparts + b] the sum of max(residual, 0) there.
+ * gpt_dev_greedy_update: step j for rows < rows <= ld of the column-major factor dL (columns [0, j) read): s_i = sum_{t<j}
+ *   dL[i + t ld] d_prow[t]; d_col[i] = l_i = (d_col[i] - s_i) / sqrt(d_scal[0]) -- a division; d_resid[i] -= l_i^2; the partials
+ *   over the rows with d_mark[i] == 0.  d_col is column j wherever the caller keeps it (dL + j ld in the library).
+ * gpt_dev_greedy_pick: reduces nparts partials, writes d_trace[j]; with j < M applies the stop rule or writes d_idx[j] = d_cand[p]
+ *   (d_cand NULL: p), d_dmax[j], d_mark[p] = 1, the scalars and words, d_xp[0 .. D) = dX[p], d_prow[t] = dL[p + t ld], t < j. */
+#define GPT_GREEDY_ROWS_PER_PART 256
+#define GPT_GREEDY_S_DMAX 0
+#define GPT_GREEDY_S_DMAX0 1
+#define GPT_GREEDY_W_STOP 0
+#define GPT_GREEDY_W_COUNT 1
+#define GPT_GREEDY_W_PIVOT 2
+#define GPT_GREEDY_W_BAD 3
+int64_t gpt_dev_greedy_parts(int64_t rows);
+int gpt_dev_greedy_update(gpt_ctx *ctx, const double *dL, int64_t ld, int64_t rows, int64_t j, double *d_col, double *d_resid,
+                          const int32_t *d_mark, const double *d_prow, const double *d_scal, const int32_t *d_words, double *d_part,
+                          int32_t *d_pidx);
+int gpt_dev_greedy_pick(gpt_ctx *ctx, int64_t j, int64_t M, double tol, const double *d_part, const int32_t *d_pidx, int64_t nparts,
+                        const int32_t *d_cand, const double *dX, int D, const double *dL, int64_t ld, int32_t *d_mark, double *d_scal,
+                        int32_t *d_words, int32_t *d_idx, double *d_dmax, double *d_trace, double *d_xp, double *d_prow);
+
 /* ---- compiled schedules of the partitioned engines (round 6) ------------------------------------------------------------
  * The one-process-per-GPU block-cyclic Cholesky of gptools_amd/dist.py issues ~1000 operations per rank and evaluation; which
  * ones, on which buffers, in which order is static per (N, nb, world, rank).  The Python layer records its step loop once as an
