@@ -130,6 +130,13 @@ SIGNATURES = {
     "gpt_dev_sparse_rowsum": (C.c_int, [_vp, _vp, _i64, _i64, _vp]),
     "gpt_dev_sparse_var": (C.c_int, [_vp, _vp, _vp, _i64, _i64, _i64, _vp, _vp]),
     "gpt_dev_sparse_assemble_b": (C.c_int, [_vp, _vp, _i64, _i64, _vp, _i64, C.c_double]),
+    "gpt_sparse_fit_batch": (C.c_int, [_vp, C.c_int, C.c_int, C.c_int, _ip, _ip, _dp, _ip, _ip, _dp, _dp, _dp, C.c_double, _i64, _dp, _dp,
+                                       _ip, _ip]),
+    "gpt_dev_sparse_lambda_batch": (C.c_int, [_vp, _i64, _vp, _i64, _i64, _i64, _i64, C.c_int, _vp, _i64, _vp, _i64, _vp, _vp, _vp, _i64, _i64,
+                                              _vp]),
+    "gpt_dev_sparse_rowsum_batch": (C.c_int, [_vp, _i64, _vp, _i64, _i64, _i64, _vp, _i64]),
+    "gpt_dev_sparse_gram_batch": (C.c_int, [_vp, _i64, _vp, _i64, _i64, _i64, _i64, C.c_int, _vp, _i64, _i64]),
+    "gpt_dev_sparse_assemble_b_batch": (C.c_int, [_vp, _i64, _vp, _i64, _i64, _i64, _vp, _i64, _i64, C.c_double]),
     "gpt_sparse_grad_diff": (C.c_int, [_vp, C.c_int, _ip, _dp, _dp, _dp, _dp, _dp, _dp, _dp]),
     "gpt_dev_sparse_grad_rows": (C.c_int, [_vp, _vp, _vp, _i64, _i64, _i64, C.c_int, _vp, _vp, _vp, C.c_double, _vp, _vp, _vp, _vp, _i64,
                                            _vp, _vp, _vp]),
@@ -754,6 +761,27 @@ class Context(object):
                                        dptr(parts)))
         self._sparse_nparams = [int(v) for v in npar]
         return ll.value, parts
+
+    def sparse_fit_batch(self, method, terms_list, noise_var, y, err_y, jitter, chunk_rows=0):
+        """gpt_sparse_fit_batch: ``terms_list[b]`` is element b's model in the form :meth:`fit_terms` takes (the same kernels in every
+        element, only the parameters differ), ``noise_var`` (B,), ``y`` (B, N), shared ``err_y`` (N,) -> ``(ll (B,), parts (B, 5),
+        info (B,) int32, which (B,) int32)``.  ``which[b]``: 0 element b is good, 1 ``K_uu + jitter I`` is not positive definite (``info[b]``
+        the leading minor), 2 a Lambda_i is not a positive finite number, 3 ``B`` is not positive definite.  An element's ``ll`` and
+        ``parts`` are the bits :meth:`sparse_fit` returns for it alone with the same ``chunk_rows``.  The resident single sparse fit
+        is not disturbed."""
+        ids, ids2, npar, npar1, _ = self._pack_terms(terms_list[0])
+        params = f64(np.array([self._flat_params(terms) for terms in terms_list]))
+        noise_var, y, err_y = f64(noise_var), f64(np.atleast_2d(y)), f64(err_y)
+        B = params.shape[0]
+        if (noise_var.shape != (B,) or y.shape[0] != B or err_y.ndim != 1 or y.shape[1] != err_y.shape[0]
+                or params.shape[1] != int(npar.sum())):
+            raise ValueError("sparse_fit_batch: one parameter set per element, noise_var (B,), y (B, N), err_y (N,) expected")
+        ll, parts = np.empty(B), np.zeros((B, 5))
+        info, which = np.zeros(B, dtype=np.int32), np.zeros(B, dtype=np.int32)
+        check(self._lib.gpt_sparse_fit_batch(self.handle, B, int(method), len(ids), iptr(ids), iptr(ids2), dptr(params), iptr(npar),
+                                             iptr(npar1), dptr(noise_var), dptr(y), dptr(err_y), float(jitter), int(chunk_rows), dptr(ll),
+                                             dptr(parts), iptr(info), iptr(which)))
+        return ll, parts, info, which
 
     def _sparse_grad(self, who, term_idx, params_a, params_b, denom, y, err_y, want_alpha, want_dz):
         """The one body of :meth:`sparse_grad_diff` and :meth:`sparse_grad_z` (``want_dz``): ``(out, alpha, dZ or None)``."""

@@ -56,7 +56,8 @@ enum { SLOT_XI = 0, SLOT_XJ, SLOT_NI, SLOT_NJ, SLOT_OUT, SLOT_KST, SLOT_KSS, SLO
        SLOT_LOO_V, SLOT_LOO_VEC,
        SLOT_SP_Z, SLOT_SP_LU, SLOT_SP_LB, SLOT_SP_V, SLOT_SP_W, SLOT_SP_G, SLOT_SP_PART, SLOT_SP_MISC, SLOT_SP_Y,
        SLOT_SP_S1, SLOT_SP_S2, SLOT_SP_GM, SLOT_SP_GVEC, SLOT_SP_GPART, SLOT_SP_DZPART, SLOT_SP_DZ,
-       SLOT_SP_SEL_L, SLOT_SP_SEL_X, SLOT_SP_SEL_MISC, SLOT_COUNT };
+       SLOT_SP_SEL_L, SLOT_SP_SEL_X, SLOT_SP_SEL_MISC,
+       SLOT_SPB_LU, SLOT_SPB_LB, SLOT_SPB_V, SLOT_SPB_G, SLOT_SPB_PART, SLOT_SPB_MISC, SLOT_COUNT };
 
 struct gpt_ctx {
     int device = 0;
@@ -257,6 +258,7 @@ static int stream_follows(gpt_ctx *c, hipStream_t from, hipStream_t to, size_t i
 #include "api_predict.inc"      // gpt_predict, gpt_cov_sample, gpt_solve_L / gpt_cho_solve, gpt_potrf_host / gpt_gemm_nt_host
 #include "api_dev.inc"      // device API (gpt_dev_*): raw device pointers on the context's streams, for the one-process-per-GPU engines
 #include "api_sparse.inc"      // inducing-point approximations (FITC / VFE / DTC): gpt_sparse_set_inducing, gpt_sparse_fit, gpt_sparse_predict
+#include "api_sparse_batch.inc"      // gpt_sparse_fit_batch: a batch of sparse fits in one launch sequence, gpt_dev_sparse_*_batch
 #include "api_sparse_select.inc"      // greedy conditional-variance choice of the inducing inputs: gpt_sparse_select_inducing, gpt_dev_greedy_*
 #include "api_sparse_grad.inc"      // the gradient of the sparse objective: gpt_sparse_grad_diff and the device API of its kernels
 #include "api_plan.inc"      // compiled schedules of the partitioned engines: gpt_plan_* (op list replay, RCCL called directly)

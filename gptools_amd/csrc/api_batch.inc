@@ -51,6 +51,39 @@ extern "C" int gpt_fit_batch_terms(gpt_ctx *c, int nbatch, int nterms, const int
                           ll_data_out, logdet_half_out, info_out);
 }
 
+// The factorisation of nbatch matrices of order NP (a multiple of 128), element b at dA + b bs with the leaves' packed workspaces at dws +
+// b bws and its info word at dinfo[b] (zero on entry): the leaf loop of gpt_fit_batch*, shared with gpt_sparse_fit_batch
+// (api_sparse_batch.inc), which factors its K_uu + jitter I and its B through it.
+static int batch_leaf_loop(hipStream_t st, int64_t NP, double *dA, int64_t bs, double *dws, int64_t bws, int32_t *dinfo, int nbatch)
+{
+    // LEFT-looking over the 128-column leaves: leaf j first receives the update of ALL leaves before it in one launch
+    // (k = 128 j; element by element the same sums in the same order as the right-looking rank-128 updates of gpt_fit, whose
+    // accumulators also start from C and walk k upwards: bit-identical), then its diagonal block and TRSM.  A right-looking
+    // batch re-reads and re-writes every element of every trailing matrix once per leaf (16 bytes per 256 flops at k = 128):
+    // 0.77 of the 1.31 ms of a 64 x N = 1024 batch were those updates; here every element of the factor is written once.
+    // (GPT_BATCH_RIGHT=1: the right-looking form, for comparison)
+    // Measured, 64 elements: N = 1024 1.376 against 1.412 ms, N = 2048 5.79 against 6.22 ms, N = 256 0.247 against 0.237 ms.
+    // Larger N (round 3, bit-identical throughout): N = 3000 x 32 elements 7.8 ms (4100 evaluations/s against 1109 one by one and
+    // 1848 with two contexts in two threads), N = 4096 x 32 18.2 ms (1755 / 774 / 1168), N = 8192 x 8 34.3 ms (233 / 224 / 248: a
+    // single evaluation fills the chip there -- GaussianProcess.ll_batch takes this path up to N = 4096).
+    static const bool force_right = getenv("GPT_BATCH_RIGHT") != nullptr;
+    const bool right_looking = force_right || NP <= 512;
+    for (int64_t lc = 0; lc < NP; lc += 128) {
+        if (!right_looking && lc > 0)
+            GPT_TRY(launch_gemm_nt(st, NP - lc, 128, lc, -1.0, dA + lc * NP, NP, dA + lc * NP, NP, 1.0, dA + lc * NP + lc, NP, 1, 0, 0,
+                                   nullptr, nullptr, 0, EdgeSig(), EdgeSig(), 0, nbatch, bs));
+        GPT_TRY(launch_potf2_diag(st, dA + lc * NP + lc, NP, dws + (lc / 128) * GPT_WS_BLOCK, dinfo, lc, EdgeSig(), nbatch, bs, bws));
+        const int64_t r1 = lc + 128, m = NP - r1;
+        if (m <= 0) break;
+        GPT_TRY(launch_trsm_panel(st, m, dA + lc * NP + lc, NP, dws + (lc / 128) * GPT_WS_BLOCK, dA + r1 * NP + lc, NP, nullptr,
+                                  EdgeSig(), nbatch, bs, bws));
+        if (right_looking)
+            GPT_TRY(launch_gemm_nt(st, m, m, 128, -1.0, dA + r1 * NP + lc, NP, dA + r1 * NP + lc, NP, 1.0, dA + r1 * NP + r1, NP, 1, 0, 0,
+                                   nullptr, nullptr, 0, EdgeSig(), EdgeSig(), 0, nbatch, bs));
+    }
+    return GPT_OK;
+}
+
 static int fit_batch_impl(gpt_ctx *c, int nbatch, int nterms, const int *kernel_ids, const int *kernel_ids2, const double *params,
                           const int *nparams_t, const int *nparams1_t, const double *noise_var, const double *y, const double *err_y,
                           double diag_add, double *ll_data_out, double *logdet_half_out, int32_t *info_out)
@@ -158,31 +191,7 @@ static int fit_batch_impl(gpt_ctx *c, int nbatch, int nterms, const int *kernel_
                                         bX, c->dn, N, t + 1 == nterms ? dmisc : nullptr, diag_add, dA, NP, bs,     //  diagonal epilogue)
                                         t > 0 ? 1 : 0, 0, term_kp2(t), xstr, bS, sstr, m0.gibbs_form()));
     }
-    // LEFT-looking over the 128-column leaves: leaf j first receives the update of ALL leaves before it in one launch
-    // (k = 128 j; element by element the same sums in the same order as the right-looking rank-128 updates of gpt_fit, whose
-    // accumulators also start from C and walk k upwards: bit-identical), then its diagonal block and TRSM.  A right-looking
-    // batch re-reads and re-writes every element of every trailing matrix once per leaf (16 bytes per 256 flops at k = 128):
-    // 0.77 of the 1.31 ms of a 64 x N = 1024 batch were those updates; here every element of the factor is written once.
-    // (GPT_BATCH_RIGHT=1: the right-looking form, for comparison)
-    // Measured, 64 elements: N = 1024 1.376 against 1.412 ms, N = 2048 5.79 against 6.22 ms, N = 256 0.247 against 0.237 ms.
-    // Larger N (round 3, bit-identical throughout): N = 3000 x 32 elements 7.8 ms (4100 evaluations/s against 1109 one by one and
-    // 1848 with two contexts in two threads), N = 4096 x 32 18.2 ms (1755 / 774 / 1168), N = 8192 x 8 34.3 ms (233 / 224 / 248: a
-    // single evaluation fills the chip there -- GaussianProcess.ll_batch takes this path up to N = 4096).
-    static const bool force_right = getenv("GPT_BATCH_RIGHT") != nullptr;
-    const bool right_looking = force_right || NP <= 512;
-    for (int64_t lc = 0; lc < NP; lc += 128) {
-        if (!right_looking && lc > 0)
-            GPT_TRY(launch_gemm_nt(st, NP - lc, 128, lc, -1.0, dA + lc * NP, NP, dA + lc * NP, NP, 1.0, dA + lc * NP + lc, NP, 1, 0, 0,
-                                   nullptr, nullptr, 0, EdgeSig(), EdgeSig(), 0, nbatch, bs));
-        GPT_TRY(launch_potf2_diag(st, dA + lc * NP + lc, NP, dws + (lc / 128) * GPT_WS_BLOCK, dinfo, lc, EdgeSig(), nbatch, bs, bws));
-        const int64_t r1 = lc + 128, m = NP - r1;
-        if (m <= 0) break;
-        GPT_TRY(launch_trsm_panel(st, m, dA + lc * NP + lc, NP, dws + (lc / 128) * GPT_WS_BLOCK, dA + r1 * NP + lc, NP, nullptr,
-                                  EdgeSig(), nbatch, bs, bws));
-        if (right_looking)
-            GPT_TRY(launch_gemm_nt(st, m, m, 128, -1.0, dA + r1 * NP + lc, NP, dA + r1 * NP + lc, NP, 1.0, dA + r1 * NP + r1, NP, 1, 0, 0,
-                                   nullptr, nullptr, 0, EdgeSig(), EdgeSig(), 0, nbatch, bs));
-    }
+    GPT_TRY(batch_leaf_loop(st, NP, dA, bs, dws, bws, dinfo, nbatch));
     GPT_TRY(launch_batch_logdet_dot(st, dA, NP, bs, N, nbatch, dinfo, h + off_res));
     GPT_HIP_CHECK(hipStreamSynchronize(st));
     for (int b = 0; b < nbatch; b++) {

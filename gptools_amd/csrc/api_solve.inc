@@ -397,7 +397,8 @@ extern "C" int gpt_release_batch_scratch(gpt_ctx *c)
     GPT_HIP_CHECK(hipStreamSynchronize(c->stream));
     GPT_HIP_CHECK(hipStreamSynchronize(c->panel_stream));
     c->batch_gen++;                                                   // (no batch resident any more)
-    for (int slot : {SLOT_BATCH_A, SLOT_BATCH_WS, SLOT_BATCH_MISC, SLOT_PB_V, SLOT_PB_COV, SLOT_PB_MISC, SLOT_GB_U, SLOT_GB_W, SLOT_GB_MISC}) {
+    for (int slot : {SLOT_BATCH_A, SLOT_BATCH_WS, SLOT_BATCH_MISC, SLOT_PB_V, SLOT_PB_COV, SLOT_PB_MISC, SLOT_GB_U, SLOT_GB_W, SLOT_GB_MISC,
+                     SLOT_SPB_LU, SLOT_SPB_LB, SLOT_SPB_V, SLOT_SPB_G, SLOT_SPB_PART, SLOT_SPB_MISC}) {
         DevBuf &b = c->slots[slot];
         if (b.p) GPT_HIP_CHECK(hipFree(b.p));
         b.p = nullptr;

@@ -331,6 +331,19 @@ inline int64_t sparse_gram_tiles(int64_t mg) { return (mg / 64) * (mg / 64 + 1) 
 int launch_sparse_assemble_b(hipStream_t st, const double *G, int64_t ldg, int64_t M, double *B, int64_t bp, double big);
 int launch_sparse_var(hipStream_t st, const double *V, const double *W, int64_t ld, int64_t rows, int64_t M, const double *kdiag,
                       double *var);
+// ... for a batch of fits (gpt_sparse_fit_batch): the element in a grid dimension, element b on V + b vstride, kdiag + b
+// kstride, r + b rstride, rowval + b rvstride, bad[b], acc + b astride, part + b pstride, G + b gstride, B + b bstride; an element's bits
+// are those of the launchers above
+int launch_sparse_lambda_batch(hipStream_t st, int64_t nbatch, double *V, int64_t ldv, int64_t vstride, int64_t rows, int64_t M, int method,
+                               const double *kdiag, int64_t kstride, const double *r, int64_t rstride, const double *err,
+                               const double *noise_var, double *rowval, int64_t ldr, int64_t rvstride, int32_t *bad);
+int launch_sparse_rowsum_batch(hipStream_t st, int64_t nbatch, const double *rowval, int64_t ldr, int64_t rvstride, int64_t rows, double *acc,
+                               int64_t astride);
+int launch_sparse_gram_batch(hipStream_t st, int64_t nbatch, const double *V, int64_t ldv, int64_t vstride, int64_t rows, int64_t mg, int nslices,
+                             double *part, int64_t pstride, double *G, int64_t ldg, int64_t gstride);
+int launch_sparse_assemble_b_batch(hipStream_t st, int64_t nbatch, const double *G, int64_t ldg, int64_t gstride, int64_t M, double *B, int64_t bp,
+                                   int64_t bstride, double big);
+int launch_sparse_unit_pad_batch(hipStream_t st, int64_t nbatch, double *A, int64_t lda, int64_t bstride, int64_t n_valid, int64_t n_pad);
 // ... and the gradient of its objective (gpt_sparse_grad_diff): the per-row pass, the rank-one part of A_fu,
 // L_B without its augmented rows, the middle factor of A_uu (ksparse.hip) and the rectangular pair
 // pass with its running sums (kgrad_rect.hip)

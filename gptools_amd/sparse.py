@@ -19,7 +19,7 @@ import numpy as np
 
 from . import _lib, _ingest
 from .error_handling import GPArgumentError
-from .gaussian_process import GaussianProcess
+from .gaussian_process import GaussianProcess, _BatchJob, _terms_shape
 from .kernel import ZeroKernel, DiagonalNoiseKernel
 
 __all__ = ["SparseGaussianProcess", "greedy_inducing"]
@@ -111,12 +111,13 @@ class SparseGaussianProcess(GaussianProcess):
     :meth:`sparse_gradient` (the gradient of the objective, ``gpt_sparse_grad_diff``), :meth:`inducing_gradient` and
     :meth:`optimize_inducing` (``gpt_sparse_grad_z``: ``n_Z = 0`` for every kernel; derivative rows among ``Z`` are refused for a
     Matern52 factor and, in its coordinate, for a Gibbs factor), ``optimize_hyperparameters`` (scipy on the
-    value, or with ``gradient="sparse"`` on the value and that gradient; ``random_starts`` one after another), ``compute_ll_matrix`` and the
-    host-stepped sampler (one evaluation per vector), ``predict`` and ``draw_sample`` (through the returned covariance).
+    value, or with ``gradient="sparse"`` on the value and that gradient; ``random_starts`` one after another),
+    :meth:`sparse_ll_batch` (many hyperparameter vectors per launch sequence, ``gpt_sparse_fit_batch``), ``compute_ll_matrix`` and the
+    host-stepped sampler (through it), ``predict`` and ``draw_sample`` (through the returned covariance).
 
     Refused (``NotImplementedError`` / ``ValueError``): a covariance kernel the library does not evaluate itself, warped
     kernels, a noise kernel that is not a ``DiagonalNoiseKernel``; ``T``, ``use_hyper_deriv``, ``partitioned``;
-    ``ll_gradient*`` (see :meth:`sparse_gradient`), ``loo_*``, ``objective="loo"``, ``gradient="device"``, ``batch_starts``, ``ll_batch``; the
+    ``ll_gradient*`` (see :meth:`sparse_gradient`), ``loo_*``, ``objective="loo"``, ``gradient="device"``, ``batch_starts``, ``ll_batch`` (see :meth:`sparse_ll_batch`); the
     library-stepped sampler, ``use_MCMC`` predictions; ``L`` and ``alpha`` (there is no ``N x N`` factor)."""
 
     def __init__(self, k, Z, noise_k=None, n_Z=0, method="fitc", jitter=1e-6, chunk_rows=None, X=None, y=None, err_y=0, n=0,
@@ -218,7 +219,7 @@ class SparseGaussianProcess(GaussianProcess):
     loo_predict = _refuse("leave-one-out cross-validation (loo_predict)")
     loo_log_likelihood = _refuse("leave-one-out cross-validation (loo_log_likelihood)")
     loo_gradient = _refuse("leave-one-out cross-validation (loo_gradient)")
-    ll_batch = _refuse("batched evaluator (ll_batch): evaluate one vector at a time with update_hyperparameters")
+    ll_batch = _refuse("dense-path batched evaluator (ll_batch): the batched evaluator of the sparse objective is sparse_ll_batch")
     predict_MCMC = _refuse("predictions marginalised over hyperparameter samples (predict_MCMC)")
     compute_from_MCMC = _refuse("predictions marginalised over hyperparameter samples (compute_from_MCMC)")
     L = property(_refuse("N x N Cholesky factor (L)"))
@@ -376,7 +377,119 @@ class SparseGaussianProcess(GaussianProcess):
                 raise
         return jac
 
+    # ---- many hyperparameter vectors per launch sequence (gpt_sparse_fit_batch) ------------
+    #: most elements of one launch sequence of :meth:`sparse_ll_batch`; 1: one ``gpt_sparse_fit`` per vector, the loop.  :meth:`_ll_rows`
+    #: (``compute_ll_matrix``, the host-stepped sampler) batches at EVERY shape: measured on MI355X with 32 vectors (DESIGN.md 18.11,
+    #: SE, d = 2, fitc, N = 4096 ... 262144 x M = 64 ... 4096) the batch is faster than the loop at all sixteen shapes -- 6.6x at N =
+    #: 4096 / M = 64, 1.2x to 1.6x at M = 4096, the least 1.07x at N = 262144 / M = 64 -- so no shape stays on the loop.
+    sparse_batch_grid = 32
+
+    def _sparse_batch_element_bytes(self):
+        """``(chunk, bytes)``: the rows per pass of a fit of this shape and the device memory ONE element of ``gpt_sparse_fit_batch``
+        takes.  With MPU = M to 128, BP = LDV = M + 1 to 128, MG = M + 1 to 64 and T = (MG / 64)(MG / 64 + 1) / 2 lower tiles::
+
+            bytes = 8 [ chunk LDV                       the chunk buffer
+                      + MPU^2 + 9216 (MPU / 128)        L_u and its leaves' workspaces
+                      + BP^2 + 9216 (BP / 128)          B and its leaves' workspaces
+                      + MG^2                            G
+                      + 4096 S T                        the Gram partials, S slices
+                      + 3 chunk + N ]                   k_i, the two per-row values; y
+
+        ``chunk`` is ``chunk_rows``, or 512 MiB / (2 LDV 8) rounded down to 64, at most N rounded up to 64.  S T is about six times the
+        compute units; the library knows their number, this bound takes 256 of them: S = min((1536 + T / 2) / T, rows / 4 rounded up,
+        1024), at least 1."""
+        M, N = int(self.Z.shape[0]), int(self.X.shape[0])
+        MPU, BP, MG = -(-M // 128) * 128, -(-(M + 1) // 128) * 128, -(-(M + 1) // 64) * 64
+        chunk = self.chunk_rows or max(64, (512 << 20) // (2 * BP * 8) // 64 * 64)
+        chunk = min(chunk, -(-N // 64) * 64)
+        T = (MG // 64) * (MG // 64 + 1) // 2
+        S = max(1, min((1536 + T // 2) // T, -(-min(chunk, N) // 4), 1024))
+        per = 8 * (chunk * BP + MPU * MPU + 9216 * (MPU // 128) + BP * BP + 9216 * (BP // 128) + MG * MG + 4096 * S * T + 3 * chunk + N)
+        return chunk, per
+
+    def sparse_ll_batch(self, param_list, exit_on_bounds=True):
+        """Log-posterior at each free-parameter vector of ``param_list`` -- what ``-update_hyperparameters(p)`` returns for every
+        ``p``, bit for bit -- from ONE launch sequence per chunk of the list (``gpt_sparse_fit_batch``): ``-inf`` where the prior
+        excludes the vector (``exit_on_bounds``), where ``K_uu + jitter I`` or ``B`` is not positive definite and where a Lambda_i is
+        not a positive finite number.  The host part runs per vector in order (prior, device terms, noise variance, ``y - mu(X)``);
+        the list then goes through chunks of at most ``sparse_batch_grid`` elements, or as many as fit ``batch_grid_bytes`` and half
+        of the free device memory at :meth:`_sparse_batch_element_bytes` an element.  A chunk that answers ``MemoryError`` is
+        halved, a chunk the library rejects and a list whose elements are not one model shape are evaluated row by row.  An
+        element's bits do not depend on how the list was cut.  The batch's device scratch (at most ``batch_grid_bytes``) stays allocated
+        for the next call; ``self._ctx.release_batch_scratch()`` frees it.  Hyperparameters and ``K_up_to_date`` are afterwards what they were
+        (``K_up_to_date`` is dropped if a row-by-row evaluation replaced the resident fit)."""
+        param_list = [np.asarray(p, dtype=float) for p in param_list]
+        out = np.full(len(param_list), -np.inf)
+        if not param_list:
+            return out
+        if self.X is None:
+            raise GPArgumentError("No data have been added to the SparseGaussianProcess!")
+        self._sparse_refusal()
+        keep, fitted = np.array(self.free_params[:], dtype=float), self.K_up_to_date
+        try:
+            jobs = []
+            for i, p in enumerate(param_list):
+                self._assign_free(p)
+                prior = self.hyperprior(self.params)
+                if exit_on_bounds and np.isinf(prior):
+                    continue                                        # impossible parameters: stays -inf
+                try:
+                    terms = _device_terms(self)
+                except np.linalg.LinAlgError:
+                    continue                                        # (device parameters that need a solve that failed)
+                jobs.append(_BatchJob(i, terms, [], self._noise_var(), np.array(self._y_alph(), dtype=float), prior))
+            if jobs and not self._sparse_fit_jobs(jobs, param_list, exit_on_bounds, out):
+                fitted = False
+        finally:
+            self._assign_free(keep)
+            self.K_up_to_date = fitted
+        return out
+
+    def _sparse_fit_jobs(self, jobs, param_list, exit_on_bounds, out):
+        """The chunk loop of :meth:`sparse_ll_batch`; returns whether the resident single fit is still the one it was (no row went
+        through ``update_hyperparameters``)."""
+        def rows_one_by_one(chunk):
+            for j in chunk:
+                out[j.row] = -1.0 * self.update_hyperparameters(param_list[j.row], exit_on_bounds=exit_on_bounds)
+
+        G = int(self.sparse_batch_grid)
+        if G <= 1 or any(_terms_shape(j.terms) != _terms_shape(jobs[0].terms) for j in jobs):
+            rows_one_by_one(jobs)
+            return False
+        ctx = self._resident_ctx()
+        ctx.set_warp(None)
+        _, per = self._sparse_batch_element_bytes()
+        G = max(1, min(G, min(int(self.batch_grid_bytes), ctx.mem_info()[0] // 2) // per))
+        method, err_y, intact, s0 = _lib.SPARSE_METHODS[self.method], np.asarray(self.err_y, dtype=float), True, 0
+        while s0 < len(jobs):
+            chunk = jobs[s0:s0 + G]
+            try:
+                ll, _, _, which = ctx.sparse_fit_batch(method, [j.terms for j in chunk], np.array([j.noise_var for j in chunk]),
+                                                       np.array([j.y_alph for j in chunk]), err_y, self.jitter, self.chunk_rows or 0)
+                for j, l, w in zip(chunk, ll, which):
+                    if w == 0:
+                        out[j.row] = l + j.extra
+            except MemoryError:
+                ctx.release_batch_scratch()
+                if G > 1:
+                    G //= 2
+                    continue
+                rows_one_by_one(chunk)                              # (not even one element fits beside what is resident)
+                intact = False
+            except (ValueError, ArithmeticError):
+                rows_one_by_one(chunk)                              # an argument of ONE element fails the whole call
+                intact = False
+            s0 += len(chunk)
+        # (the batch's scratch stays on the device -- at most batch_grid_bytes: a sampler comes back thousands of times, and freeing and
+        #  allocating gigabytes per call costs more than the fits; release_batch_scratch() of the context gives it back)
+        return intact
+
     def _ll_rows(self, param_list):
+        """The log-posterior at every row of ``param_list`` (``compute_ll_matrix``, the host-stepped sampler): through
+        :meth:`sparse_ll_batch` (see ``sparse_batch_grid`` for the measurement behind it), one ``update_hyperparameters`` per row
+        with ``sparse_batch_grid = 1``; the same bits either way."""
+        if int(self.sparse_batch_grid) > 1:
+            return self.sparse_ll_batch(param_list)
         keep = np.array(self.free_params[:], dtype=float)
         try:
             return np.array([-1.0 * self.update_hyperparameters(np.asarray(p, dtype=float)) for p in param_list])

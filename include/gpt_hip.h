@@ -739,6 +739,39 @@ int gpt_dev_sparse_var(gpt_ctx *ctx, const double *dV, const double *dW, int64_t
                        double *d_var);
 int gpt_dev_sparse_assemble_b(gpt_ctx *ctx, const double *dG, int64_t ldg, int64_t M, double *dB, int64_t bp, double big);
 
+/* nbatch evaluations of the sparse objective of the resident data and inducing inputs in ONE launch sequence (DESIGN.md section
+ * 18.11): every kernel of gpt_sparse_fit's chain carries the batch in a grid dimension.  Every element has the first element's
+ * kernel ids; params: nbatch x ptot (ptot = sum of nparams), noise_var: nbatch, y: nbatch x N (the mean function's parameters may
+ * differ per element), err_y: N, shared.  method, jitter and chunk_rows as gpt_sparse_fit; the chunks are those gpt_sparse_fit
+ * walks for the same chunk_rows, with one chunk x (M padded) buffer per element.
+ * ll_out[b] and parts_out[5 b ...] (parts_out may be NULL) carry THE BITS gpt_sparse_fit returns for element b alone with the same
+ * chunk_rows: they do not depend on nbatch or on the element's place in the batch.
+ * An element that fails does not fail the call: info_out[b] is 0 or the leading minor that failed (1 ... M), which_out[b] names
+ * the matrix -- 0 none, 1 K_uu + jitter I, 2 a Lambda_i is not a positive finite number (info 0), 3 B; ll_out[b] of such an element
+ * is not meaningful; the other elements keep their bits.  An argument of one element that the parser refuses fails the whole call
+ * with the parser's status.  GPT_E_STATE / GPT_E_NOTIMPL / GPT_E_ARG as gpt_sparse_fit, GPT_E_ARG for nbatch outside 1 ... 65535,
+ * GPT_E_NOMEM where the batch's slots do not fit (the caller halves nbatch).
+ * The batch lives in slots of its own (gpt_release_batch_scratch frees them): the resident single sparse fit and the dense factor
+ * of the context survive the call. */
+int gpt_sparse_fit_batch(gpt_ctx *ctx, int nbatch, int method, int nterms, const int *kernel_ids, const int *kernel_ids2,
+                         const double *params, const int *nparams, const int *nparams1, const double *noise_var, const double *y,
+                         const double *err_y, double jitter, int64_t chunk_rows, double *ll_out, double *parts_out, int32_t *info_out,
+                         int32_t *which_out);
+
+/* Device API: the batched forms of the four kernel groups, element b of nbatch on dV + b vstride (vstride >= rows ldv), d_kdiag + b
+ * kstride, d_r + b rstride, d_noise_var[b] (a device array), d_rowval + b rvstride (rvstride >= 2 ldr), d_bad[b], d_acc + b astride,
+ * dG + b gstride, dB + b bstride; d_err is shared.  Per element the arithmetic, the slice partition (that of gpt_dev_sparse_gram for
+ * the same rows, mg and nslices) and every summation order are those of the single launchers above: the same bits. */
+int gpt_dev_sparse_lambda_batch(gpt_ctx *ctx, int64_t nbatch, double *dV, int64_t ldv, int64_t vstride, int64_t rows, int64_t M, int method,
+                                const double *d_kdiag, int64_t kstride, const double *d_r, int64_t rstride, const double *d_err,
+                                const double *d_noise_var, double *d_rowval, int64_t ldr, int64_t rvstride, int32_t *d_bad);
+int gpt_dev_sparse_rowsum_batch(gpt_ctx *ctx, int64_t nbatch, const double *d_rowval, int64_t ldr, int64_t rvstride, int64_t rows,
+                                double *d_acc, int64_t astride);
+int gpt_dev_sparse_gram_batch(gpt_ctx *ctx, int64_t nbatch, const double *dV, int64_t ldv, int64_t vstride, int64_t rows, int64_t mg,
+                              int nslices, double *dG, int64_t ldg, int64_t gstride);
+int gpt_dev_sparse_assemble_b_batch(gpt_ctx *ctx, int64_t nbatch, const double *dG, int64_t ldg, int64_t gstride, int64_t M, double *dB,
+                                    int64_t bp, int64_t bstride, double big);
+
 /* The gradient of the resident sparse fit's objective by per-pair central differences, the stencil
  * arguments those of gpt_ll_grad_diff: entry h < nh names term term_idx[h] of the fitted model with that term's complete parameter
  * vector at the two stencil points (params_a / params_b, entry after entry) and denom[h] = theta_b - theta_a; every stencil point goes
