@@ -120,7 +120,53 @@ static int sparse_upload_y(gpt_ctx *c, hipStream_t st, const double *y, const do
 // The workspace of a Gram of order mg in nslices slices: one 64 x 64 partial tile per (slice, lower tile)
 static int sparse_part(gpt_ctx *c, int nslices, int64_t mg, double **dPart)
 {
-    return ensure(c, SLOT_SP_PART, (size_t)nslices * sparse_gram_tiles(mg) * 4096 * sizeof(double), (void **)dPart);
+    return ensure(c, SLOT_SP_PART, (size_t)sparse_gram_part_doubles(mg, nslices) * sizeof(double), (void **)dPart);
+}
+
+// What gpt_sparse_fit and gpt_sparse_fit_batch refuse alike: a method out of range, a negative (or NaN) jitter or noise variance
+// (noise_var: one per element)
+static int sparse_fit_refusals(const char *who, int method, double jitter, const double *noise_var, int nbatch)
+{
+    if (method != GPT_SPARSE_FITC && method != GPT_SPARSE_VFE && method != GPT_SPARSE_DTC) {
+        gpt_set_error("%s: method must be GPT_SPARSE_FITC, GPT_SPARSE_VFE or GPT_SPARSE_DTC, got %d", who, method);
+        return GPT_E_ARG;
+    }
+    bool nv_ok = true;
+    for (int b = 0; b < nbatch; b++) nv_ok = nv_ok && noise_var[b] >= 0.0;
+    if (!(jitter >= 0.0) || !nv_ok) {
+        gpt_set_error("%s: jitter and every noise_var must be non-negative", who);
+        return GPT_E_ARG;
+    }
+    return GPT_OK;
+}
+
+// The leading minor a failed factorisation of order > M reports, as the fits return it: at most M (a word > M: only the augmented /
+// padding pivots failed)
+static int32_t sparse_clamp_info(int32_t info, int64_t M) { return info > M ? (int32_t)M : info; }
+
+// What one fit's numbers say, for the single fit and for every element of a batch: which step failed first, in the order the fit meets
+// them -- 1 K_uu + jitter I (info_u), 2 a Lambda_i was not positive and finite (bad), 3 B (info_b), 0 none -- with `info` the leading
+// minor of 1 and 3 (sparse_clamp_info); and the objective with its five parts, formed whatever failed.  sums: sum log Lambda, the VFE
+// trace term, r^T Lambda^-1 r.  The ONE statement of the expression: the batch's bit rule (DESIGN.md 18.11) rests on it.
+struct SparseOutcome {
+    double ll, parts[5];
+    int32_t which, info;
+};
+static SparseOutcome sparse_outcome(int method, int64_t N, int64_t M, const double *sums, double logdet_lb, double cc, int32_t info_u, int32_t bad,
+                                    int32_t info_b)
+{
+    SparseOutcome o;
+    o.which = info_u != 0 ? 1 : bad != 0 ? 2 : info_b != 0 ? 3 : 0;
+    o.info = sparse_clamp_info(o.which == 1 ? info_u : o.which == 3 ? info_b : 0, M);
+    const double sum_log_lambda = sums[0], trace = sums[1], rlr = sums[2];
+    o.ll = -0.5 * ((((sum_log_lambda + 2.0 * logdet_lb) + rlr) - cc) + (double)N * log(2.0 * M_PI));
+    if (method == GPT_SPARSE_VFE) o.ll -= 0.5 * trace;
+    o.parts[0] = sum_log_lambda;
+    o.parts[1] = logdet_lb;
+    o.parts[2] = rlr;
+    o.parts[3] = cc;
+    o.parts[4] = trace;
+    return o;
 }
 
 extern "C" int gpt_sparse_set_inducing(gpt_ctx *c, const double *Z, const int32_t *nZ, int64_t M)
@@ -220,14 +266,7 @@ extern "C" int gpt_sparse_fit(gpt_ctx *c, int method, int nterms, const int *ker
     CTX_ENTER(c);
     GPT_TRY(sparse_refusals(c, "gpt_sparse_fit", false));
     if (!y || !err_y || !kernel_ids2 || !nparams1 || !ll_out) return GPT_E_ARG;
-    if (method != GPT_SPARSE_FITC && method != GPT_SPARSE_VFE && method != GPT_SPARSE_DTC) {
-        gpt_set_error("gpt_sparse_fit: method must be GPT_SPARSE_FITC, GPT_SPARSE_VFE or GPT_SPARSE_DTC, got %d", method);
-        return GPT_E_ARG;
-    }
-    if (!(jitter >= 0.0) || !(noise_var >= 0.0)) {
-        gpt_set_error("gpt_sparse_fit: jitter and noise_var must be non-negative");
-        return GPT_E_ARG;
-    }
+    GPT_TRY(sparse_fit_refusals("gpt_sparse_fit", method, jitter, &noise_var, 1));
     c->sp_fitted = false;
     c->sp_chunk_rows = 0;
     const int D = c->D;
@@ -291,7 +330,7 @@ extern "C" int gpt_sparse_fit(gpt_ctx *c, int method, int nterms, const int *ker
     GPT_HIP_CHECK(hipMemcpyAsync(c->h_info, d_words + 0, sizeof(int32_t), hipMemcpyDeviceToHost, st));
     GPT_HIP_CHECK(hipStreamSynchronize(st));
     if (*c->h_info != 0) {
-        const int info = *c->h_info > M ? (int)M : (int)*c->h_info;
+        const int info = sparse_clamp_info(*c->h_info, M);
         gpt_set_error("K_uu + jitter I: %d-th leading minor of the array is not positive definite", info);
         return info;
     }
@@ -332,31 +371,20 @@ extern "C" int gpt_sparse_fit(gpt_ctx *c, int method, int nterms, const int *ker
                 c->timings[ev_phase[i]] += ms;
             }
     }
-    if (words[2] != 0) {
+    const int32_t info_b = (int32_t)c->h_scal[2];
+    const SparseOutcome o = sparse_outcome(method, N, M, sums, c->h_scal[0], c->h_scal[1], 0, words[2], info_b);
+    if (o.which == 2) {
         gpt_set_error("gpt_sparse_fit: a Lambda_i is not a positive finite number (k_i - q_i + noise_var + err_y_i^2 for fitc, "
                       "noise_var + err_y_i^2 for vfe / dtc)");
         return GPT_E_VALUE;
     }
-    const int32_t info = (int32_t)c->h_scal[2];
-    if (info != 0) {
-        if (info > M) {          // only the augmented / padding pivots failed: c.c overflowed
-            gpt_set_error("B = I + V Lambda^-1 V^T: factorisation failed in the augmented row (non-finite data?)");
-            return (int)M;
-        }
-        gpt_set_error("B = I + V Lambda^-1 V^T: %d-th leading minor of the array is not positive definite", (int)info);
-        return (int)info;
+    if (o.which == 3) {
+        if (info_b > M) gpt_set_error("B = I + V Lambda^-1 V^T: factorisation failed in the augmented row (non-finite data?)");      // c.c overflowed
+        else gpt_set_error("B = I + V Lambda^-1 V^T: %d-th leading minor of the array is not positive definite", (int)o.info);
+        return (int)o.info;
     }
-    const double sum_log_lambda = sums[0], trace = sums[1], rlr = sums[2], logdet_lb = c->h_scal[0], cc = c->h_scal[1];
-    double ll = -0.5 * ((((sum_log_lambda + 2.0 * logdet_lb) + rlr) - cc) + (double)N * log(2.0 * M_PI));
-    if (method == GPT_SPARSE_VFE) ll -= 0.5 * trace;
-    *ll_out = ll;
-    if (parts_out) {
-        parts_out[0] = sum_log_lambda;
-        parts_out[1] = logdet_lb;
-        parts_out[2] = rlr;
-        parts_out[3] = cc;
-        parts_out[4] = trace;
-    }
+    *ll_out = o.ll;
+    if (parts_out) memcpy(parts_out, o.parts, sizeof(o.parts));
     c->sp_model = model;
     c->sp_method = method;
     c->sp_noise_var = noise_var;

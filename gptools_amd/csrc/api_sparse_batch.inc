@@ -10,14 +10,16 @@
 //   SLOT_SPB_MISC  the small inputs and per-row values (below).
 // The chain is gpt_sparse_fit's with every kernel carrying the batch in a grid dimension: the batched builders (kbuild_batch.hip), the
 // leaf loop of gpt_fit_batch* (batch_leaf_loop), trsm_rlt's recursion on batched launches, the batched row pass, sums, Gram and assembly
-// (ksparse.hip) and launch_batch_logdet_dot.  Same kernels or kernels with the same arithmetic, the same chunk boundaries, the same
-// slice partition, the same summation orders and the same host expression: an element's ll and parts carry the bits gpt_sparse_fit
-// returns for it alone.  A failed element (K_uu, a Lambda_i, B) runs through the same launches on whatever its numbers have become; its
-// words say so at the end and nobody else reads its buffers.
+// (ksparse.hip: the single fit's kernel sources, run with strides) and launch_batch_logdet_dot.  Same kernels or kernels with the same
+// arithmetic, the same chunk boundaries, the one slice partition (sparse_gram_slicing), the same summation orders and the one host
+// expression (sparse_outcome, api_sparse.inc): an element's ll and parts carry the bits gpt_sparse_fit returns for it alone.  A failed
+// element (K_uu, a Lambda_i, B) runs through the same launches on whatever its numbers have become; its words say so at the end and
+// nobody else reads its buffers.
 // ------------------------------------------------------------------------------------------------
 
 // B_b (m x n per element, bstride apart) <- B_b L_b^-T, n a multiple of 128: trsm_rlt with every launch batched (L_b lstride apart, its
-// leaves' workspaces wstride apart)
+// leaves' workspaces wstride apart).  A copy of trsm_rlt's recursion, on purpose for now: the single form goes through gemm_nt(c, ...) with
+// its flop accounting and schedule state, and folding the two belongs to a change of its own.
 static int trsm_rlt_batch(hipStream_t st, int64_t nbatch, int64_t m, int64_t n, const double *L, int64_t ldl, int64_t lstride, const double *invd,
                           int64_t wstride, double *B, int64_t ldb, int64_t bstride)
 {
@@ -41,16 +43,7 @@ extern "C" int gpt_sparse_fit_batch(gpt_ctx *c, int nbatch, int method, int nter
         return GPT_E_ARG;
     }
     if (!y || !err_y || !kernel_ids2 || !nparams1 || !noise_var || !ll_out || !info_out || !which_out) return GPT_E_ARG;
-    if (method != GPT_SPARSE_FITC && method != GPT_SPARSE_VFE && method != GPT_SPARSE_DTC) {
-        gpt_set_error("gpt_sparse_fit_batch: method must be GPT_SPARSE_FITC, GPT_SPARSE_VFE or GPT_SPARSE_DTC, got %d", method);
-        return GPT_E_ARG;
-    }
-    bool nv_ok = true;
-    for (int b = 0; b < nbatch; b++) nv_ok = nv_ok && noise_var[b] >= 0.0;
-    if (!(jitter >= 0.0) || !nv_ok) {
-        gpt_set_error("gpt_sparse_fit_batch: jitter and every noise_var must be non-negative");
-        return GPT_E_ARG;
-    }
+    GPT_TRY(sparse_fit_refusals("gpt_sparse_fit_batch", method, jitter, noise_var, nbatch));
     const int D = c->D;
     const int64_t N = c->Nx;
     long maxsum, colmax[GPT_MAX_DIM];
@@ -100,7 +93,7 @@ extern "C" int gpt_sparse_fit_batch(gpt_ctx *c, int nbatch, int method, int nter
     }
     // device slots of the batch
     const int64_t us = MPU * MPU, uws = (MPU / 128) * GPT_WS_BLOCK, bs = BP * BP, bws = (BP / 128) * GPT_WS_BLOCK, vs = chunk * LDV, gs = MG * MG;
-    const int64_t ps = (int64_t)nslices * sparse_gram_tiles(MG) * 4096;
+    const int64_t ps = sparse_gram_part_doubles(MG, nslices);
     double *dLu, *dLb, *dV, *dG, *dPart, *dmisc;
     GPT_TRY(ensure(c, SLOT_SPB_LU, nb * (size_t)(us + uws) * sizeof(double), (void **)&dLu));
     GPT_TRY(ensure(c, SLOT_SPB_LB, nb * (size_t)(bs + bws) * sizeof(double), (void **)&dLb));
@@ -167,30 +160,11 @@ extern "C" int gpt_sparse_fit_batch(gpt_ctx *c, int nbatch, int method, int nter
     const int32_t *hw = reinterpret_cast<const int32_t *>(h + off_words);
     for (int b = 0; b < nbatch; b++) {
         const double *res = h + off_res + 4 * (size_t)b, *sums = h + off_sums + 4 * (size_t)b;
-        int32_t info = 0, which = 0;
-        if (hw[b] != 0) {
-            which = 1;
-            info = hw[b] > M ? (int32_t)M : hw[b];
-        } else if (hw[2 * nb + b] != 0) {
-            which = 2;
-        } else if ((int32_t)res[2] != 0) {
-            which = 3;
-            info = (int32_t)res[2] > M ? (int32_t)M : (int32_t)res[2];      // (> M: only the augmented / padding pivots failed)
-        }
-        const double sum_log_lambda = sums[0], trace = sums[1], rlr = sums[2], logdet_lb = res[0], cc = res[1];
-        double ll = -0.5 * ((((sum_log_lambda + 2.0 * logdet_lb) + rlr) - cc) + (double)N * log(2.0 * M_PI));
-        if (method == GPT_SPARSE_VFE) ll -= 0.5 * trace;
-        ll_out[b] = ll;
-        info_out[b] = info;
-        which_out[b] = which;
-        if (parts_out) {
-            double *p = parts_out + 5 * (size_t)b;
-            p[0] = sum_log_lambda;
-            p[1] = logdet_lb;
-            p[2] = rlr;
-            p[3] = cc;
-            p[4] = trace;
-        }
+        const SparseOutcome o = sparse_outcome(method, N, M, sums, res[0], res[1], hw[b], hw[2 * nb + b], (int32_t)res[2]);
+        ll_out[b] = o.ll;
+        info_out[b] = o.info;
+        which_out[b] = o.which;
+        if (parts_out) memcpy(parts_out + 5 * (size_t)b, o.parts, sizeof(o.parts));
     }
     return GPT_OK;
 }
@@ -233,7 +207,7 @@ extern "C" int gpt_dev_sparse_gram_batch(gpt_ctx *c, int64_t nbatch, const doubl
         return GPT_E_ARG;
     }
     if (nslices <= 0) GPT_TRY(sparse_slices(c, mg, rows, &nslices));
-    const int64_t ps = (int64_t)nslices * sparse_gram_tiles(mg) * 4096;
+    const int64_t ps = sparse_gram_part_doubles(mg, nslices);
     double *dPart;
     GPT_TRY(ensure(c, SLOT_SPB_PART, (size_t)nbatch * ps * sizeof(double), (void **)&dPart));
     return launch_sparse_gram_batch(c->stream, nbatch, dV, ldv, vstride, rows, mg, nslices, dPart, ps, dG, ldg, gstride);

@@ -328,12 +328,25 @@ int launch_sparse_gram(hipStream_t st, const double *A, const double *V, int64_t
                        double *G, int64_t ldg);
 // the lower 64 x 64 tiles of a Gram of order mg
 inline int64_t sparse_gram_tiles(int64_t mg) { return (mg / 64) * (mg / 64 + 1) / 2; }
+// how a Gram over `rows` rows asked for in nslices slices is cut: whole k-steps of four rows per slice and no slice empty, so ns <=
+// nslices slices of slice_rows rows.  The bits of G depend on it (the partials are added in slice order): the one statement of the rule
+struct SparseSlicing {
+    int64_t slice_rows;
+    int ns;
+};
+inline SparseSlicing sparse_gram_slicing(int64_t rows, int nslices)
+{
+    const int64_t slice_rows = ((rows + nslices - 1) / nslices + 3) / 4 * 4;
+    return SparseSlicing{slice_rows, (int)((rows + slice_rows - 1) / slice_rows)};
+}
+// ... and the doubles of its workspace `part`: one 64 x 64 partial tile per (slice, lower tile), sized for nslices
+inline int64_t sparse_gram_part_doubles(int64_t mg, int nslices) { return (int64_t)nslices * sparse_gram_tiles(mg) * 4096; }
 int launch_sparse_assemble_b(hipStream_t st, const double *G, int64_t ldg, int64_t M, double *B, int64_t bp, double big);
 int launch_sparse_var(hipStream_t st, const double *V, const double *W, int64_t ld, int64_t rows, int64_t M, const double *kdiag,
                       double *var);
 // ... for a batch of fits (gpt_sparse_fit_batch): the element in a grid dimension, element b on V + b vstride, kdiag + b
-// kstride, r + b rstride, rowval + b rvstride, bad[b], acc + b astride, part + b pstride, G + b gstride, B + b bstride; an element's bits
-// are those of the launchers above
+// kstride, r + b rstride, rowval + b rvstride, bad[b], acc + b astride, part + b pstride, G + b gstride, B + b bstride.  Each pair of
+// launchers goes through one helper and one kernel source (ksparse.hip), so an element's bits are those of the launchers above
 int launch_sparse_lambda_batch(hipStream_t st, int64_t nbatch, double *V, int64_t ldv, int64_t vstride, int64_t rows, int64_t M, int method,
                                const double *kdiag, int64_t kstride, const double *r, int64_t rstride, const double *err,
                                const double *noise_var, double *rowval, int64_t ldr, int64_t rvstride, int32_t *bad);

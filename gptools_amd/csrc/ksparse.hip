@@ -52,10 +52,11 @@ __device__ __forceinline__ SparseLambda sparse_lambda_of(bool fitc, double kmq, 
 // method: 0 fitc (Lambda_i = k_i - q_i + s_i), 1 vfe, 2 dtc (Lambda_i = s_i); s_i = noise_var + err_i^2.
 // rowval[i] = log Lambda_i, rowval[ldr + i] = (k_i - q_i) / s_i (vfe, else 0).  A row whose Lambda_i is not a positive finite number
 // raises *bad and contributes nothing (its scale is 0): the host reads the word once, at the end of the fit.
-__global__ __launch_bounds__(256) void sparse_lambda_kernel(double *__restrict__ V, int64_t ldv, int64_t rows, int64_t M, int method,
-                                                            const double *__restrict__ kdiag, const double *__restrict__ r,
-                                                            const double *__restrict__ err, double noise_var,
-                                                            double *__restrict__ rowval, int64_t ldr, int32_t *__restrict__ bad)
+// The ONE body of the row pass, inlined into its two kernels below: every pointer is the element's own already.
+__device__ __forceinline__ void sparse_lambda_rows(double *__restrict__ V, int64_t ldv, int64_t rows, int64_t M, int method,
+                                                   const double *__restrict__ kdiag, const double *__restrict__ r,
+                                                   const double *__restrict__ err, double noise_var, double *__restrict__ rowval,
+                                                   int64_t ldr, int32_t *__restrict__ bad)
 {
     __shared__ double part[4];
     __shared__ double scale;
@@ -84,25 +85,75 @@ __global__ __launch_bounds__(256) void sparse_lambda_kernel(double *__restrict__
     if (threadIdx.x == 0) row[M] = r[i] * sc;
 }
 
-int launch_sparse_lambda(hipStream_t st, double *V, int64_t ldv, int64_t rows, int64_t M, int method, const double *kdiag,
-                         const double *r, const double *err, double noise_var, double *rowval, int64_t ldr, int32_t *bad)
+// The single fit's: one chunk, noise_var by value, one word.
+__global__ __launch_bounds__(256) void sparse_lambda_kernel(double *__restrict__ V, int64_t ldv, int64_t rows, int64_t M, int method,
+                                                            const double *__restrict__ kdiag, const double *__restrict__ r,
+                                                            const double *__restrict__ err, double noise_var,
+                                                            double *__restrict__ rowval, int64_t ldr, int32_t *__restrict__ bad)
 {
-    if (rows <= 0) return GPT_OK;
-    if (M < 0 || M >= ldv || rows > ldr) {
-        gpt_set_error("sparse_lambda: M = %lld does not leave a column for r in rows of %lld", (long long)M, (long long)ldv);
+    sparse_lambda_rows(V, ldv, rows, M, method, kdiag, r, err, noise_var, rowval, ldr, bad);
+}
+
+// A batch's: element b = blockIdx.y on V + b vstride, kdiag + b kstride, r + b rstride, rowval + b rvstride with
+// noise_var[b] and bad[b]; err is shared.  A bad row raises bad[b] only and zeroes its own row.
+__global__ __launch_bounds__(256) void sparse_lambda_batch_kernel(double *__restrict__ V, int64_t ldv, int64_t vstride, int64_t rows, int64_t M,
+                                                                  int method, const double *__restrict__ kdiag, int64_t kstride,
+                                                                  const double *__restrict__ r, int64_t rstride,
+                                                                  const double *__restrict__ err, const double *__restrict__ noise_var,
+                                                                  double *__restrict__ rowval, int64_t ldr, int64_t rvstride,
+                                                                  int32_t *__restrict__ bad)
+{
+    const int64_t b = blockIdx.y;
+    sparse_lambda_rows(V + b * vstride, ldv, rows, M, method, kdiag + b * kstride, r + b * rstride, err, noise_var[b], rowval + b * rvstride,
+                       ldr, bad + b);
+}
+
+// Both launchers: the checks, the grid (rows, elements).  noise_var_b NULL: the single kernel with noise_var_1 (nbatch is 1 then).
+static int sparse_lambda_launch(hipStream_t st, const char *who, int64_t nbatch, double *V, int64_t ldv, int64_t vstride, int64_t rows, int64_t M,
+                                int method, const double *kdiag, int64_t kstride, const double *r, int64_t rstride, const double *err,
+                                const double *noise_var_b, double noise_var_1, double *rowval, int64_t ldr, int64_t rvstride, int32_t *bad)
+{
+    if (rows <= 0 || nbatch <= 0) return GPT_OK;
+    if (M < 0 || M >= ldv || rows > ldr || nbatch > 65535 || vstride < rows * ldv || rvstride < 2 * ldr) {
+        gpt_set_error("%s: M = %lld does not leave a column for r in rows of %lld, or %lld rows (value stride %lld), %lld elements %lld / %lld apart",
+                      who, (long long)M, (long long)ldv, (long long)rows, (long long)ldr, (long long)nbatch, (long long)vstride,
+                      (long long)rvstride);
         return GPT_E_ARG;
     }
-    hipLaunchKernelGGL(sparse_lambda_kernel, dim3((unsigned)rows), dim3(256), 0, st, V, ldv, rows, M, method, kdiag, r, err, noise_var,
-                       rowval, ldr, bad);
+    const dim3 grid((unsigned)rows, (unsigned)nbatch);
+    if (noise_var_b)
+        hipLaunchKernelGGL(sparse_lambda_batch_kernel, grid, dim3(256), 0, st, V, ldv, vstride, rows, M, method, kdiag, kstride, r, rstride, err,
+                           noise_var_b, rowval, ldr, rvstride, bad);
+    else
+        hipLaunchKernelGGL(sparse_lambda_kernel, grid, dim3(256), 0, st, V, ldv, rows, M, method, kdiag, r, err, noise_var_1, rowval, ldr, bad);
     GPT_LAUNCH_CHECK();
     return GPT_OK;
 }
 
-// acc[0] += sum_i rowval[i], acc[1] += sum_i rowval[ldr + i] over the chunk's rows: one workgroup, a fixed order
-__global__ __launch_bounds__(256) void sparse_rowsum_kernel(const double *__restrict__ rowval, int64_t ldr, int64_t rows,
-                                                            double *__restrict__ acc)
+int launch_sparse_lambda(hipStream_t st, double *V, int64_t ldv, int64_t rows, int64_t M, int method, const double *kdiag,
+                         const double *r, const double *err, double noise_var, double *rowval, int64_t ldr, int32_t *bad)
+{
+    return sparse_lambda_launch(st, "sparse_lambda", 1, V, ldv, rows * ldv, rows, M, method, kdiag, 0, r, 0, err, nullptr, noise_var, rowval, ldr,
+                                2 * ldr, bad);
+}
+
+int launch_sparse_lambda_batch(hipStream_t st, int64_t nbatch, double *V, int64_t ldv, int64_t vstride, int64_t rows, int64_t M, int method,
+                               const double *kdiag, int64_t kstride, const double *r, int64_t rstride, const double *err,
+                               const double *noise_var, double *rowval, int64_t ldr, int64_t rvstride, int32_t *bad)
+{
+    if (!noise_var) return GPT_E_ARG;
+    return sparse_lambda_launch(st, "sparse_lambda_batch", nbatch, V, ldv, vstride, rows, M, method, kdiag, kstride, r, rstride, err, noise_var,
+                                0.0, rowval, ldr, rvstride, bad);
+}
+
+// acc[0] += sum_i rowval[i], acc[1] += sum_i rowval[ldr + i] over the chunk's rows: one workgroup per element (blockIdx.x, on rowval +
+// b rvstride and acc + b astride), a fixed order
+__global__ __launch_bounds__(256) void sparse_rowsum_kernel(const double *__restrict__ rowval, int64_t ldr, int64_t rvstride, int64_t rows,
+                                                            double *__restrict__ acc, int64_t astride)
 {
     __shared__ double s0[4], s1[4];
+    rowval += (int64_t)blockIdx.x * rvstride;
+    acc += (int64_t)blockIdx.x * astride;
     double a = 0.0, b = 0.0;
     for (int64_t i = threadIdx.x; i < rows; i += 256) {
         a += rowval[i];
@@ -123,12 +174,29 @@ __global__ __launch_bounds__(256) void sparse_rowsum_kernel(const double *__rest
     }
 }
 
-int launch_sparse_rowsum(hipStream_t st, const double *rowval, int64_t ldr, int64_t rows, double *acc)
+static int sparse_rowsum_launch(hipStream_t st, const char *who, int64_t nbatch, const double *rowval, int64_t ldr, int64_t rvstride, int64_t rows,
+                                double *acc, int64_t astride)
 {
-    if (rows <= 0) return GPT_OK;
-    hipLaunchKernelGGL(sparse_rowsum_kernel, dim3(1), dim3(256), 0, st, rowval, ldr, rows, acc);
+    if (rows <= 0 || nbatch <= 0) return GPT_OK;
+    if (rows > ldr || rvstride < 2 * ldr || astride < 2) {
+        gpt_set_error("%s: %lld rows with a value stride of %lld, elements %lld / %lld apart", who, (long long)rows, (long long)ldr,
+                      (long long)rvstride, (long long)astride);
+        return GPT_E_ARG;
+    }
+    hipLaunchKernelGGL(sparse_rowsum_kernel, dim3((unsigned)nbatch), dim3(256), 0, st, rowval, ldr, rvstride, rows, acc, astride);
     GPT_LAUNCH_CHECK();
     return GPT_OK;
+}
+
+int launch_sparse_rowsum(hipStream_t st, const double *rowval, int64_t ldr, int64_t rows, double *acc)
+{
+    return sparse_rowsum_launch(st, "sparse_rowsum", 1, rowval, ldr, 2 * ldr, rows, acc, 2);
+}
+
+int launch_sparse_rowsum_batch(hipStream_t st, int64_t nbatch, const double *rowval, int64_t ldr, int64_t rvstride, int64_t rows, double *acc,
+                               int64_t astride)
+{
+    return sparse_rowsum_launch(st, "sparse_rowsum_batch", nbatch, rowval, ldr, rvstride, rows, acc, astride);
 }
 
 // ---- the weighted Gram -------------------------------------------------------------------------------------------------------------
@@ -143,6 +211,9 @@ int launch_sparse_rowsum(hipStream_t st, const double *rowval, int64_t ldr, int6
 // matrix of V's shape -- A holds the rows e_k v_k, and e_k changes sign, so the rows cannot be scaled by a square root and fed in
 // as one operand.  Without TWO, A is not read and both operands come from V: the fit's instantiation, the code it was before the
 // gradient existed.  A template flag, not a run-time test, for that reason.
+// BATCH: workgroup (tile, slice, element b = blockIdx.z) on V + b vstride and part + b pstride, the element's own (slices x tiles) partial
+// tiles (gpt_sparse_fit_batch).  Without BATCH neither blockIdx.z nor a stride is read: a flag for the reason TWO is
+// one.  Instantiated: <false, false> the fit's, <true, false> the gradient's, <false, true> the batch's.
 #define SG_UNROLL 4
 
 // (ti, tj), tj <= ti, from the row-major index t of the lower triangle's tiles: ti (ti + 1) / 2 <= t
@@ -155,11 +226,17 @@ __device__ __forceinline__ void sparse_tile_of(int t, int *ti_out, int *tj_out)
     *tj_out = t - ti * (ti + 1) / 2;
 }
 
-template <bool TWO>
+template <bool TWO, bool BATCH>
 __global__ __launch_bounds__(256) void sparse_gram_kernel(const double *__restrict__ A, const double *__restrict__ V, int64_t ldv,
-                                                          int64_t rows, int64_t slice_rows, int ntiles, double *__restrict__ part)
+                                                          int64_t rows, int64_t slice_rows, int ntiles, double *__restrict__ part,
+                                                          int64_t vstride, int64_t pstride)
 {
+    static_assert(!(TWO && BATCH), "the signed-weight Gram has no batched form: A carries no element stride");
     const int t = blockIdx.x, s = blockIdx.y;
+    if (BATCH) {
+        V += (int64_t)blockIdx.z * vstride;
+        part += (int64_t)blockIdx.z * pstride;
+    }
     int ti, tj;
     sparse_tile_of(t, &ti, &tj);
     const int lane = threadIdx.x & 63, wave = threadIdx.x >> 6;
@@ -202,11 +279,14 @@ __global__ __launch_bounds__(256) void sparse_gram_kernel(const double *__restri
             for (int q = 0; q < 4; q++) out[(li + a * 16 + fk + 4 * q) * 64 + lj + b * 16 + fr] = acc[a][b][q];
 }
 
-// G tile (ti, tj) += part[0][t] + part[1][t] + ... in slice order; one thread per element
-__global__ __launch_bounds__(256) void sparse_gram_reduce_kernel(const double *__restrict__ part, int ntiles, int nslices,
-                                                                 double *__restrict__ G, int64_t ldg)
+// G tile (ti, tj) += part[0][t] + part[1][t] + ... in slice order; one thread per entry, grid (tiles, 16, elements): element b =
+// blockIdx.z on part + b pstride and G + b gstride
+__global__ __launch_bounds__(256) void sparse_gram_reduce_kernel(const double *__restrict__ part, int64_t pstride, int ntiles, int nslices,
+                                                                 double *__restrict__ G, int64_t ldg, int64_t gstride)
 {
     const int t = blockIdx.x;
+    part += (int64_t)blockIdx.z * pstride;
+    G += (int64_t)blockIdx.z * gstride;
     int ti, tj;
     sparse_tile_of(t, &ti, &tj);
     const int e = blockIdx.y * 256 + threadIdx.x;          // element of the tile, row-major
@@ -216,39 +296,59 @@ __global__ __launch_bounds__(256) void sparse_gram_reduce_kernel(const double *_
     G[gi * ldg + gj] = v;
 }
 
-// G (mg x mg, mg a multiple of 64, row stride ldg; lower tiles) += V^T V (A == NULL) or A^T V over the `rows` rows of V and A (row
-// stride ldv >= mg).  nslices workgroups share a tile (chosen by the caller: api_sparse.inc sparse_slices); part holds nslices *
-// sparse_gram_tiles(mg) * 4096 doubles.
-int launch_sparse_gram(hipStream_t st, const double *A, const double *V, int64_t ldv, int64_t rows, int64_t mg, int nslices, double *part,
-                       double *G, int64_t ldg)
+// G_b (mg x mg, mg a multiple of 64, row stride ldg, elements gstride apart; lower tiles) += V_b^T V_b (A == NULL) or A^T V (one
+// element) over the `rows` rows of V_b = V + b vstride and A (row stride ldv >= mg).  nslices workgroups share a tile (chosen by the
+// caller: api_sparse.inc sparse_slices) in the partition sparse_gram_slicing gives for (rows, nslices) -- not a function of nbatch;
+// part holds nbatch x pstride doubles, pstride >= sparse_gram_part_doubles(mg, nslices).  Both launchers: the checks, the partition,
+// the grids; `batch` says whose instantiation runs (the batch keeps its own at nbatch = 1 too).
+static int sparse_gram_launch(hipStream_t st, const char *who, bool batch, int64_t nbatch, const double *A, const double *V, int64_t ldv,
+                              int64_t vstride, int64_t rows, int64_t mg, int nslices, double *part, int64_t pstride, double *G, int64_t ldg,
+                              int64_t gstride)
 {
-    if (rows <= 0) return GPT_OK;
-    if (mg <= 0 || mg % 64 || mg > ldv || mg > ldg || nslices < 1 || nslices > 65535 || mg / 64 > 2000) {
-        gpt_set_error("%s: order %lld (a multiple of 64, at most the row strides %lld / %lld), %d slices", A ? "sparse_gram2" : "sparse_gram",
-                      (long long)mg, (long long)ldv, (long long)ldg, nslices);
+    if (rows <= 0 || nbatch <= 0) return GPT_OK;
+    if (mg <= 0 || mg % 64 || mg > ldv || mg > ldg || nslices < 1 || nslices > 65535 || mg / 64 > 2000 || nbatch > 65535 ||
+        (!batch && nbatch != 1) || (A && batch) || vstride < rows * ldv || gstride < mg * ldg || pstride < sparse_gram_part_doubles(mg, nslices)) {
+        gpt_set_error("%s: order %lld (a multiple of 64, at most the row strides %lld / %lld), %d slices, %lld elements %lld / %lld / %lld apart",
+                      who, (long long)mg, (long long)ldv, (long long)ldg, nslices, (long long)nbatch, (long long)vstride, (long long)pstride,
+                      (long long)gstride);
         return GPT_E_ARG;
     }
     const int ntiles = (int)sparse_gram_tiles(mg);
-    // whole k-steps of four rows per slice; no slice is empty
-    int64_t slice_rows = ((rows + nslices - 1) / nslices + 3) / 4 * 4;
-    const int ns = (int)((rows + slice_rows - 1) / slice_rows);
-    const dim3 grid((unsigned)ntiles, (unsigned)ns);
-    if (A) hipLaunchKernelGGL(sparse_gram_kernel<true>, grid, dim3(256), 0, st, A, V, ldv, rows, slice_rows, ntiles, part);
-    else hipLaunchKernelGGL(sparse_gram_kernel<false>, grid, dim3(256), 0, st, A, V, ldv, rows, slice_rows, ntiles, part);
+    const SparseSlicing sl = sparse_gram_slicing(rows, nslices);
+    const dim3 grid((unsigned)ntiles, (unsigned)sl.ns, (unsigned)nbatch);
+    auto kernel = A ? sparse_gram_kernel<true, false> : batch ? sparse_gram_kernel<false, true> : sparse_gram_kernel<false, false>;
+    hipLaunchKernelGGL(kernel, grid, dim3(256), 0, st, A, V, ldv, rows, sl.slice_rows, ntiles, part, vstride, pstride);
     GPT_LAUNCH_CHECK();
-    hipLaunchKernelGGL(sparse_gram_reduce_kernel, dim3((unsigned)ntiles, 16), dim3(256), 0, st, part, ntiles, ns, G, ldg);
+    hipLaunchKernelGGL(sparse_gram_reduce_kernel, dim3((unsigned)ntiles, 16, (unsigned)nbatch), dim3(256), 0, st, part, pstride, ntiles, sl.ns, G,
+                       ldg, gstride);
     GPT_LAUNCH_CHECK();
     return GPT_OK;
+}
+
+int launch_sparse_gram(hipStream_t st, const double *A, const double *V, int64_t ldv, int64_t rows, int64_t mg, int nslices, double *part,
+                       double *G, int64_t ldg)
+{
+    return sparse_gram_launch(st, A ? "sparse_gram2" : "sparse_gram", false, 1, A, V, ldv, rows * ldv, rows, mg, nslices, part,
+                              sparse_gram_part_doubles(mg, nslices), G, ldg, mg * ldg);
+}
+
+int launch_sparse_gram_batch(hipStream_t st, int64_t nbatch, const double *V, int64_t ldv, int64_t vstride, int64_t rows, int64_t mg, int nslices,
+                             double *part, int64_t pstride, double *G, int64_t ldg, int64_t gstride)
+{
+    return sparse_gram_launch(st, "sparse_gram_batch", true, nbatch, nullptr, V, ldv, vstride, rows, mg, nslices, part, pstride, G, ldg, gstride);
 }
 
 // ---- B = I + G with the augmented row ------------------------------------------------------------------------------------------------
 // B (bp x bp, row stride bp; bp a multiple of 128, > M): rows / columns < M: I + G (lower; the upper triangle is zeroed); row M: b^T =
 // G[M][0..M) with `big` on the diagonal (the pivot stays positive whatever c.c is: solve.hip fill_pad_kernel); rows > M: unit diagonal.
-__global__ void sparse_assemble_b_kernel(const double *__restrict__ G, int64_t ldg, int64_t M, double *__restrict__ B, int64_t bp,
-                                         double big)
+// Grid (columns / 256, rows, elements): element b = blockIdx.z on G + b gstride and B + b bstride.
+__global__ void sparse_assemble_b_kernel(const double *__restrict__ G, int64_t ldg, int64_t gstride, int64_t M, double *__restrict__ B, int64_t bp,
+                                         int64_t bstride, double big)
 {
     const int64_t j = (int64_t)blockIdx.x * blockDim.x + threadIdx.x, i = blockIdx.y;
     if (j >= bp) return;
+    G += (int64_t)blockIdx.z * gstride;
+    B += (int64_t)blockIdx.z * bstride;
     double v = 0.0;
     if (i < M) {
         if (j <= i) v = G[i * ldg + j] + (i == j ? 1.0 : 0.0);
@@ -260,15 +360,30 @@ __global__ void sparse_assemble_b_kernel(const double *__restrict__ G, int64_t l
     B[i * bp + j] = v;
 }
 
-int launch_sparse_assemble_b(hipStream_t st, const double *G, int64_t ldg, int64_t M, double *B, int64_t bp, double big)
+static int sparse_assemble_b_launch(hipStream_t st, const char *who, int64_t nbatch, const double *G, int64_t ldg, int64_t gstride, int64_t M,
+                                    double *B, int64_t bp, int64_t bstride, double big)
 {
-    if (M < 1 || bp <= M || ldg <= M || bp > 65535) {
-        gpt_set_error("sparse_assemble_b: M = %lld, padded order %lld", (long long)M, (long long)bp);
+    if (nbatch <= 0) return GPT_OK;
+    if (M < 1 || bp <= M || ldg <= M || bp > 65535 || nbatch > 65535 || gstride < (M + 1) * ldg || bstride < bp * bp) {
+        gpt_set_error("%s: M = %lld, padded order %lld, %lld elements %lld / %lld apart", who, (long long)M, (long long)bp, (long long)nbatch,
+                      (long long)gstride, (long long)bstride);
         return GPT_E_ARG;
     }
-    hipLaunchKernelGGL(sparse_assemble_b_kernel, dim3((unsigned)((bp + 255) / 256), (unsigned)bp), dim3(256), 0, st, G, ldg, M, B, bp, big);
+    hipLaunchKernelGGL(sparse_assemble_b_kernel, dim3((unsigned)((bp + 255) / 256), (unsigned)bp, (unsigned)nbatch), dim3(256), 0, st, G, ldg,
+                       gstride, M, B, bp, bstride, big);
     GPT_LAUNCH_CHECK();
     return GPT_OK;
+}
+
+int launch_sparse_assemble_b(hipStream_t st, const double *G, int64_t ldg, int64_t M, double *B, int64_t bp, double big)
+{
+    return sparse_assemble_b_launch(st, "sparse_assemble_b", 1, G, ldg, (M + 1) * ldg, M, B, bp, bp * bp, big);
+}
+
+int launch_sparse_assemble_b_batch(hipStream_t st, int64_t nbatch, const double *G, int64_t ldg, int64_t gstride, int64_t M, double *B, int64_t bp,
+                                   int64_t bstride, double big)
+{
+    return sparse_assemble_b_launch(st, "sparse_assemble_b_batch", nbatch, G, ldg, gstride, M, B, bp, bstride, big);
 }
 
 // ---- predictive variance ---------------------------------------------------------------------------------------------------------------
@@ -478,230 +593,11 @@ int launch_sparse_auu2(hipStream_t st, const double *S, int64_t lds, int64_t M, 
 }
 
 // ---- batched fits (gpt_sparse_fit_batch, api_sparse_batch.inc) ----------------------------------------------------------
-// The fit's four kernel groups with the element of a batch in a grid dimension: element b works on its own chunk buffer V + b vstride,
-// its own k(x_i, x_i), residual, per-row values, running sums, partial tiles, G and B.  Kernels of their own -- the single fit's stay the
-// code they were -- whose bodies form every number through the same expressions in the same order (sparse_row_sumsq, sparse_lambda_of,
-// the MFMA sequence of sparse_gram_kernel<false>, the slice order of the reduce), so an element carries the bits it has alone.
-
-// The row pass: sparse_lambda_kernel with noise_var[b], kdiag + b kstride, r + b rstride, rowval + b rvstride and one "bad Lambda"
-// word per element; err is shared.  A bad row raises bad[b] only and zeroes its own row.
-__global__ __launch_bounds__(256) void sparse_lambda_batch_kernel(double *__restrict__ V, int64_t ldv, int64_t vstride, int64_t rows, int64_t M,
-                                                                  int method, const double *__restrict__ kdiag, int64_t kstride,
-                                                                  const double *__restrict__ r, int64_t rstride,
-                                                                  const double *__restrict__ err, const double *__restrict__ noise_var,
-                                                                  double *__restrict__ rowval, int64_t ldr, int64_t rvstride,
-                                                                  int32_t *__restrict__ bad)
-{
-    __shared__ double part[4];
-    __shared__ double scale;
-    const int64_t i = blockIdx.x, b = blockIdx.y;
-    if (i >= rows) return;
-    double *row = V + b * vstride + i * ldv;
-    const int lane = threadIdx.x & 63, wave = threadIdx.x >> 6;
-    double acc = sparse_row_sumsq(row, M);
-    for (int off = 32; off > 0; off >>= 1) acc += __shfl_down(acc, off);
-    if (lane == 0) part[wave] = acc;
-    __syncthreads();
-    if (threadIdx.x == 0) {
-        const double q = (part[0] + part[1]) + (part[2] + part[3]);
-        const double e = err[i], s = noise_var[b] + e * e, kmq = kdiag[b * kstride + i] - q;
-        const SparseLambda L = sparse_lambda_of(method == 0, kmq, s);
-        const double lam = L.lam;
-        const bool ok = L.ok;
-        if (!ok) bad[b] = 1;
-        double *rv = rowval + b * rvstride;
-        rv[i] = ok ? log(lam) : 0.0;
-        rv[ldr + i] = (ok && method == 1) ? kmq / s : 0.0;
-        scale = ok ? 1.0 / sqrt(lam) : 0.0;
-    }
-    __syncthreads();
-    const double sc = scale;
-    for (int64_t c = threadIdx.x; c < M; c += 256) row[c] *= sc;
-    if (threadIdx.x == 0) row[M] = r[b * rstride + i] * sc;
-}
-
-int launch_sparse_lambda_batch(hipStream_t st, int64_t nbatch, double *V, int64_t ldv, int64_t vstride, int64_t rows, int64_t M, int method,
-                               const double *kdiag, int64_t kstride, const double *r, int64_t rstride, const double *err,
-                               const double *noise_var, double *rowval, int64_t ldr, int64_t rvstride, int32_t *bad)
-{
-    if (rows <= 0 || nbatch <= 0) return GPT_OK;
-    if (M < 0 || M >= ldv || rows > ldr || nbatch > 65535 || vstride < rows * ldv || rvstride < 2 * ldr) {
-        gpt_set_error("sparse_lambda_batch: M = %lld in rows of %lld, %lld rows (value stride %lld), %lld elements %lld / %lld apart", (long long)M,
-                      (long long)ldv, (long long)rows, (long long)ldr, (long long)nbatch, (long long)vstride, (long long)rvstride);
-        return GPT_E_ARG;
-    }
-    hipLaunchKernelGGL(sparse_lambda_batch_kernel, dim3((unsigned)rows, (unsigned)nbatch), dim3(256), 0, st, V, ldv, vstride, rows, M, method,
-                       kdiag, kstride, r, rstride, err, noise_var, rowval, ldr, rvstride, bad);
-    GPT_LAUNCH_CHECK();
-    return GPT_OK;
-}
-
-// The running sums: one workgroup per element, the summation order of sparse_rowsum_kernel
-__global__ __launch_bounds__(256) void sparse_rowsum_batch_kernel(const double *__restrict__ rowval, int64_t ldr, int64_t rvstride, int64_t rows,
-                                                                  double *__restrict__ acc, int64_t astride)
-{
-    __shared__ double s0[4], s1[4];
-    rowval += (int64_t)blockIdx.x * rvstride;
-    acc += (int64_t)blockIdx.x * astride;
-    double a = 0.0, b = 0.0;
-    for (int64_t i = threadIdx.x; i < rows; i += 256) {
-        a += rowval[i];
-        b += rowval[ldr + i];
-    }
-    for (int off = 32; off > 0; off >>= 1) {
-        a += __shfl_down(a, off);
-        b += __shfl_down(b, off);
-    }
-    if ((threadIdx.x & 63) == 0) {
-        s0[threadIdx.x >> 6] = a;
-        s1[threadIdx.x >> 6] = b;
-    }
-    __syncthreads();
-    if (threadIdx.x == 0) {
-        acc[0] += ((s0[0] + s0[1]) + s0[2]) + s0[3];
-        acc[1] += ((s1[0] + s1[1]) + s1[2]) + s1[3];
-    }
-}
-
-int launch_sparse_rowsum_batch(hipStream_t st, int64_t nbatch, const double *rowval, int64_t ldr, int64_t rvstride, int64_t rows, double *acc,
-                               int64_t astride)
-{
-    if (rows <= 0 || nbatch <= 0) return GPT_OK;
-    if (rows > ldr || rvstride < 2 * ldr || astride < 2) {
-        gpt_set_error("sparse_rowsum_batch: %lld rows with a value stride of %lld, elements %lld / %lld apart", (long long)rows, (long long)ldr,
-                      (long long)rvstride, (long long)astride);
-        return GPT_E_ARG;
-    }
-    hipLaunchKernelGGL(sparse_rowsum_batch_kernel, dim3((unsigned)nbatch), dim3(256), 0, st, rowval, ldr, rvstride, rows, acc, astride);
-    GPT_LAUNCH_CHECK();
-    return GPT_OK;
-}
-
-// The Gram: workgroup (tile, slice, element), the body of sparse_gram_kernel<false> on V + b vstride; part + b pstride holds the element's
-// (slices x tiles) partial tiles
-__global__ __launch_bounds__(256) void sparse_gram_batch_kernel(const double *__restrict__ V, int64_t ldv, int64_t vstride, int64_t rows,
-                                                                int64_t slice_rows, int ntiles, double *__restrict__ part, int64_t pstride)
-{
-    const int t = blockIdx.x, s = blockIdx.y;
-    V += (int64_t)blockIdx.z * vstride;
-    part += (int64_t)blockIdx.z * pstride;
-    int ti, tj;
-    sparse_tile_of(t, &ti, &tj);
-    const int lane = threadIdx.x & 63, wave = threadIdx.x >> 6;
-    const int fr = lane & 15, fk = lane >> 4;
-    const int64_t i0 = (int64_t)ti * 64 + (wave >> 1) * 32, j0 = (int64_t)tj * 64 + (wave & 1) * 32;
-    const int64_t k0 = (int64_t)s * slice_rows;
-    const int64_t k1 = (k0 + slice_rows < rows) ? k0 + slice_rows : rows;
-    f64x4 acc[2][2];
-#pragma unroll
-    for (int a = 0; a < 2; a++)
-#pragma unroll
-        for (int b = 0; b < 2; b++) acc[a][b] = f64x4{0.0, 0.0, 0.0, 0.0};
-    for (int64_t k = k0; k < k1; k += 4 * SG_UNROLL) {
-        double av[SG_UNROLL][2], bv[SG_UNROLL][2];
-#pragma unroll
-        for (int u = 0; u < SG_UNROLL; u++) {
-            const int64_t kr = k + 4 * u + fk;
-            const bool live = kr < k1;
-            const double *rb = V + kr * ldv;
-            av[u][0] = live ? rb[i0 + fr] : 0.0;
-            av[u][1] = live ? rb[i0 + 16 + fr] : 0.0;
-            bv[u][0] = live ? rb[j0 + fr] : 0.0;
-            bv[u][1] = live ? rb[j0 + 16 + fr] : 0.0;
-        }
-#pragma unroll
-        for (int u = 0; u < SG_UNROLL; u++)
-#pragma unroll
-            for (int a = 0; a < 2; a++)
-#pragma unroll
-                for (int b = 0; b < 2; b++)
-                    acc[a][b] = __builtin_amdgcn_mfma_f64_16x16x4f64(av[u][a], bv[u][b], acc[a][b], 0, 0, 0);
-    }
-    double *out = part + ((int64_t)s * ntiles + t) * 4096;
-    const int li = (wave >> 1) * 32, lj = (wave & 1) * 32;
-#pragma unroll
-    for (int a = 0; a < 2; a++)
-#pragma unroll
-        for (int b = 0; b < 2; b++)
-#pragma unroll
-            for (int q = 0; q < 4; q++) out[(li + a * 16 + fk + 4 * q) * 64 + lj + b * 16 + fr] = acc[a][b][q];
-}
-
-// G_b tile (ti, tj) += the element's partials in slice order; grid (tiles, 16, elements)
-__global__ __launch_bounds__(256) void sparse_gram_reduce_batch_kernel(const double *__restrict__ part, int64_t pstride, int ntiles, int nslices,
-                                                                       double *__restrict__ G, int64_t ldg, int64_t gstride)
-{
-    const int t = blockIdx.x;
-    part += (int64_t)blockIdx.z * pstride;
-    G += (int64_t)blockIdx.z * gstride;
-    int ti, tj;
-    sparse_tile_of(t, &ti, &tj);
-    const int e = blockIdx.y * 256 + threadIdx.x;
-    const int64_t gi = (int64_t)ti * 64 + (e >> 6), gj = (int64_t)tj * 64 + (e & 63);
-    double v = G[gi * ldg + gj];
-    for (int s = 0; s < nslices; s++) v += part[((int64_t)s * ntiles + t) * 4096 + e];
-    G[gi * ldg + gj] = v;
-}
-
-// G_b (mg x mg, row stride ldg, elements gstride apart) += V_b^T V_b over the `rows` rows of V_b = V + b vstride.  The slice partition is
-// launch_sparse_gram's for the same (rows, nslices): it does not depend on nbatch.  part: nbatch x pstride doubles, pstride >= nslices *
-// sparse_gram_tiles(mg) * 4096.
-int launch_sparse_gram_batch(hipStream_t st, int64_t nbatch, const double *V, int64_t ldv, int64_t vstride, int64_t rows, int64_t mg, int nslices,
-                             double *part, int64_t pstride, double *G, int64_t ldg, int64_t gstride)
-{
-    if (rows <= 0 || nbatch <= 0) return GPT_OK;
-    if (mg <= 0 || mg % 64 || mg > ldv || mg > ldg || nslices < 1 || nslices > 65535 || mg / 64 > 2000 || nbatch > 65535 ||
-        vstride < rows * ldv || gstride < mg * ldg || pstride < (int64_t)nslices * sparse_gram_tiles(mg) * 4096) {
-        gpt_set_error("sparse_gram_batch: order %lld (a multiple of 64, at most the row strides %lld / %lld), %d slices, %lld elements %lld / "
-                      "%lld / %lld apart", (long long)mg, (long long)ldv, (long long)ldg, nslices, (long long)nbatch, (long long)vstride,
-                      (long long)pstride, (long long)gstride);
-        return GPT_E_ARG;
-    }
-    const int ntiles = (int)sparse_gram_tiles(mg);
-    int64_t slice_rows = ((rows + nslices - 1) / nslices + 3) / 4 * 4;
-    const int ns = (int)((rows + slice_rows - 1) / slice_rows);
-    hipLaunchKernelGGL(sparse_gram_batch_kernel, dim3((unsigned)ntiles, (unsigned)ns, (unsigned)nbatch), dim3(256), 0, st, V, ldv, vstride, rows,
-                       slice_rows, ntiles, part, pstride);
-    GPT_LAUNCH_CHECK();
-    hipLaunchKernelGGL(sparse_gram_reduce_batch_kernel, dim3((unsigned)ntiles, 16, (unsigned)nbatch), dim3(256), 0, st, part, pstride, ntiles, ns, G,
-                       ldg, gstride);
-    GPT_LAUNCH_CHECK();
-    return GPT_OK;
-}
-
-// B_b = I + G_b with the augmented row, per element as sparse_assemble_b_kernel; grid (columns / 256, rows, elements)
-__global__ void sparse_assemble_b_batch_kernel(const double *__restrict__ G, int64_t ldg, int64_t gstride, int64_t M, double *__restrict__ B,
-                                               int64_t bp, int64_t bstride, double big)
-{
-    const int64_t j = (int64_t)blockIdx.x * blockDim.x + threadIdx.x, i = blockIdx.y;
-    if (j >= bp) return;
-    G += (int64_t)blockIdx.z * gstride;
-    B += (int64_t)blockIdx.z * bstride;
-    double v = 0.0;
-    if (i < M) {
-        if (j <= i) v = G[i * ldg + j] + (i == j ? 1.0 : 0.0);
-    } else if (i == M) {
-        v = (j < M) ? G[i * ldg + j] : (j == M ? big : 0.0);
-    } else if (i == j) {
-        v = 1.0;
-    }
-    B[i * bp + j] = v;
-}
-
-int launch_sparse_assemble_b_batch(hipStream_t st, int64_t nbatch, const double *G, int64_t ldg, int64_t gstride, int64_t M, double *B, int64_t bp,
-                                   int64_t bstride, double big)
-{
-    if (nbatch <= 0) return GPT_OK;
-    if (M < 1 || bp <= M || ldg <= M || bp > 65535 || nbatch > 65535 || gstride < (M + 1) * ldg || bstride < bp * bp) {
-        gpt_set_error("sparse_assemble_b_batch: M = %lld, padded order %lld, %lld elements %lld / %lld apart", (long long)M, (long long)bp,
-                      (long long)nbatch, (long long)gstride, (long long)bstride);
-        return GPT_E_ARG;
-    }
-    hipLaunchKernelGGL(sparse_assemble_b_batch_kernel, dim3((unsigned)((bp + 255) / 256), (unsigned)bp, (unsigned)nbatch), dim3(256), 0, st, G, ldg,
-                       gstride, M, B, bp, bstride, big);
-    GPT_LAUNCH_CHECK();
-    return GPT_OK;
-}
+// The fit's four kernel groups carry the element of a batch in a grid dimension -- element b on its own chunk buffer V + b vstride, its
+// own k(x_i, x_i), residual, per-row values, running sums, partial tiles, G and B -- and each is the single fit's source, above: the row
+// pass one inlined body under two kernels (noise_var by value / noise_var[b]), the Gram the BATCH flag of sparse_gram_kernel, the
+// running sums, the Gram's reduce and the assembly one plain kernel each that the single launchers run with one element.  An element
+// therefore carries the bits it has alone; what a batch adds is strides.  Only the kernel below has no single twin here.
 
 // A_b[i][i] = 1 for i in [n_valid, n_pad) of every element: the unit padding diagonal of the batch's K_uu + jitter I (the rows are zero
 // already), what launch_fill_pad leaves in the single fit's

@@ -460,3 +460,164 @@ def test_assemble_b_batch_alone(M):
         want[M, :M] = G[b, M, :M]
         want[M, M] = big
         assert np.array_equal(got[b, :bp * bp].reshape(bp, bp), want), b
+
+
+# ---- 8. strides and element offsets: the batched launchers against the single ones on padded layouts ------------------------------------
+# The single and the batched launcher of each group run one kernel source; what a batch adds is an element stride per buffer.  Seeded data
+# that is not integer, three elements, every stride a few rows or doubles above its lower bound, the gaps filled with a sentinel: every
+# element carries the bits the single launcher gives on that element alone, and no gap changes.  (Inputs' gaps hold NaN: a read of one
+# would show in the result.)
+SENTINEL = -7.25
+
+
+def _flat(nb, stride, fill):
+    return np.full(nb * stride, fill, dtype=float)
+
+
+def _dev(a):
+    import torch
+    return torch.tensor(np.ascontiguousarray(a, dtype=float), device="cuda")
+
+
+@pytest.mark.parametrize("rows,mg,nslices", [(5, 192, 0), (130, 128, 7), (257, 64, 0)])
+def test_gram_batch_on_padded_strides_is_the_single_gram(rows, mg, nslices):
+    """gpt_dev_sparse_gram_batch with vstride and gstride above rows x ldv and mg x ldg: element b of G equals gpt_dev_sparse_gram on that
+    element's V bit for bit -- hence its upper tiles and the columns behind mg are what they were -- and the gaps between the elements
+    of G keep the sentinel.  (5, 192): six tiles, two slices of four rows and of one; (130, 128, 7): seven slices, six of 20 rows and one of 10; (257, 64): one
+    tile, the fit's slice count."""
+    import torch
+    _lib = lib()
+    rs = np.random.RandomState(1000 + rows + mg)
+    nb, ldv, ldg = 3, mg + 64, mg + 8
+    vstride, gstride = (rows + 3) * ldv + 5, (mg + 2) * ldg + 3
+    V, G0 = _flat(nb, vstride, np.nan), _flat(nb, gstride, SENTINEL)
+    for b in range(nb):
+        V[b * vstride:b * vstride + rows * ldv] = rs.randn(rows * ldv)
+        G0[b * gstride:b * gstride + mg * ldg] = rs.randn(mg * ldg)
+    ctx = _lib.Context()
+    dV, dG = _dev(V), _dev(G0)
+    torch.cuda.synchronize()
+    _lib.check(_lib.load().gpt_dev_sparse_gram_batch(ctx.handle, nb, dV.data_ptr(), ldv, vstride, rows, mg, nslices, dG.data_ptr(), ldg, gstride))
+    ctx.synchronize()
+    got = dG.cpu().numpy()
+    low = np.zeros((mg, ldg), dtype=bool)
+    low[:, :mg] = np.tril(np.ones((mg // 64, mg // 64))).repeat(64, 0).repeat(64, 1) > 0
+    for b in range(nb):
+        el, el0 = got[b * gstride:b * gstride + mg * ldg].reshape(mg, ldg), G0[b * gstride:b * gstride + mg * ldg].reshape(mg, ldg)
+        assert np.all(got[b * gstride + mg * ldg:(b + 1) * gstride] == SENTINEL), b
+        assert same_bits(el[~low], el0[~low]), b
+        assert not same_bits(el[low], el0[low]), b
+        d1, dVb = _dev(el0), _dev(V[b * vstride:b * vstride + rows * ldv])
+        torch.cuda.synchronize()
+        _lib.check(_lib.load().gpt_dev_sparse_gram(ctx.handle, dVb.data_ptr(), ldv, rows, mg, nslices, d1.data_ptr(), ldg))
+        ctx.synchronize()
+        assert same_bits(el, d1.cpu().numpy()), b
+
+
+@pytest.mark.parametrize("method", [0, 1, 2])
+@pytest.mark.parametrize("M", [1, 256, 257, 513])
+def test_row_pass_batch_on_padded_strides_is_the_single_row_pass(M, method):
+    """gpt_dev_sparse_lambda_batch with vstride, kstride, rstride and rvstride each above its lower bound (rows x ldv, rows, rows, 2 ldr):
+    every element's rows, its two per-row values and its word equal gpt_dev_sparse_lambda's on the element alone, bit for bit; the
+    gaps of V and of rowval and the word behind the last element keep their sentinel.  Row 2 of element 1 has a Lambda that is not
+    positive (s_2 = -0.25 + 0.5^2 = 0, and k_2 far below q_2 for fitc): word 1 alone is raised, by both launchers.  M = 1: the r~ column
+    next to one entry; 256 / 257 / 513: the edges of the row sum's two loops."""
+    import torch
+    _lib = lib()
+    rs = np.random.RandomState(2000 + 3 * M + method)
+    nb, rows, ldr, ldv = 3, 5, 8, M + 3
+    vstride, kstride, rstride, rvstride = (rows + 1) * ldv + 2, rows + 3, rows + 2, 2 * ldr + 5
+    V, kd, r = _flat(nb, vstride, SENTINEL), _flat(nb, kstride, np.nan), _flat(nb, rstride, np.nan)
+    for b in range(nb):
+        Vb = rs.randn(rows, ldv)
+        V[b * vstride:b * vstride + rows * ldv] = Vb.ravel()
+        kd[b * kstride:b * kstride + rows] = (Vb[:, :M] ** 2).sum(1) + rs.uniform(0.5, 2.0, size=rows)
+        r[b * rstride:b * rstride + rows] = rs.randn(rows)
+    kd[1 * kstride + 2] = -1e6
+    err = np.array([0.9, 0.8, 0.5, 0.7, 0.6])
+    nv = np.array([0.3, -0.25, 1.7])
+    ctx = _lib.Context()
+    dV, dk, dr, de, dn = _dev(V), _dev(kd), _dev(r), _dev(err), _dev(nv)
+    drow = _dev(_flat(nb, rvstride, SENTINEL))
+    dbad = torch.zeros(nb + 1, dtype=torch.int32, device="cuda")
+    torch.cuda.synchronize()
+    _lib.check(_lib.load().gpt_dev_sparse_lambda_batch(ctx.handle, nb, dV.data_ptr(), ldv, vstride, rows, M, method, dk.data_ptr(), kstride,
+                                                       dr.data_ptr(), rstride, de.data_ptr(), dn.data_ptr(), drow.data_ptr(), ldr, rvstride,
+                                                       _ip(dbad)))
+    ctx.synchronize()
+    got, row, bad = dV.cpu().numpy(), drow.cpu().numpy(), dbad.cpu().numpy()
+    assert np.array_equal(bad, [0, 1, 0, 0])
+    for b in range(nb):
+        assert np.all(got[b * vstride + rows * ldv:(b + 1) * vstride] == SENTINEL), b
+        rb = row[b * rvstride:(b + 1) * rvstride]
+        assert np.all(rb[rows:ldr] == SENTINEL) and np.all(rb[ldr + rows:] == SENTINEL), b
+        dV1 = _dev(V[b * vstride:b * vstride + rows * ldv])
+        d1 = _dev(np.full(2 * ldr, SENTINEL))
+        b1 = torch.zeros(1, dtype=torch.int32, device="cuda")
+        torch.cuda.synchronize()
+        _lib.check(_lib.load().gpt_dev_sparse_lambda(ctx.handle, dV1.data_ptr(), ldv, rows, M, method, dk[b * kstride:].data_ptr(),
+                                                     dr[b * rstride:].data_ptr(), de.data_ptr(), float(nv[b]), d1.data_ptr(), ldr, _ip(b1)))
+        ctx.synchronize()
+        assert same_bits(got[b * vstride:b * vstride + rows * ldv], dV1.cpu().numpy()), b
+        assert same_bits(rb[:2 * ldr], d1.cpu().numpy()), b
+        assert int(b1.cpu()[0]) == bad[b], b
+    el1 = got[vstride:vstride + rows * ldv].reshape(rows, ldv)
+    assert not el1[2, :M + 1].any() and el1[[0, 1, 3, 4], :M].all()          # the bad row is zeroed, its neighbours are scaled
+
+
+@pytest.mark.parametrize("rows", [1, 257])
+def test_rowsum_batch_on_padded_strides_is_the_single_rowsum(rows):
+    """gpt_dev_sparse_rowsum_batch with rvstride above 2 ldr and astride = 4, as the fit lays its sums out: slots 0 and 1 of every
+    element equal gpt_dev_sparse_rowsum's on the element alone bit for bit (onto what the slots held), slots 2 and 3 keep their sentinel.
+    One row; one past the workgroup's 256 threads."""
+    import torch
+    _lib = lib()
+    rs = np.random.RandomState(3000 + rows)
+    nb, ldr = 3, rows + 5
+    rvstride = 2 * ldr + 7
+    rv = rs.randn(nb * rvstride)
+    acc0 = np.full((nb, 4), SENTINEL)
+    acc0[:, :2] = rs.randn(nb, 2)
+    ctx = _lib.Context()
+    drow, dacc = _dev(rv), _dev(acc0)
+    torch.cuda.synchronize()
+    _lib.check(_lib.load().gpt_dev_sparse_rowsum_batch(ctx.handle, nb, drow.data_ptr(), ldr, rvstride, rows, dacc.data_ptr(), 4))
+    ctx.synchronize()
+    got = dacc.cpu().numpy()
+    assert np.all(got[:, 2:] == SENTINEL)
+    for b in range(nb):
+        d1 = _dev(acc0[b, :2])
+        torch.cuda.synchronize()
+        _lib.check(_lib.load().gpt_dev_sparse_rowsum(ctx.handle, drow[b * rvstride:].data_ptr(), ldr, rows, d1.data_ptr()))
+        ctx.synchronize()
+        assert same_bits(got[b, :2], d1.cpu().numpy()) and not same_bits(got[b, :2], acc0[b, :2]), b
+
+
+@pytest.mark.parametrize("M", [1, 127, 128])
+def test_assemble_b_batch_on_padded_strides_is_the_single_assembly(M):
+    """gpt_dev_sparse_assemble_b_batch with gstride above (M + 1) ldg and bstride above bp^2: every element's B equals
+    gpt_dev_sparse_assemble_b's on the element's G bit for bit, the gaps between the elements of B keep their sentinel.  127: the
+    augmented row is the last of the only 128-block; 128: it opens a second one."""
+    import torch
+    _lib = lib()
+    rs = np.random.RandomState(4000 + M)
+    nb, big = 3, 1e300
+    bp, mg = (M + 128) // 128 * 128, (M + 64) // 64 * 64
+    ldg = mg + 2
+    gstride, bstride = (mg + 2) * ldg + 3, bp * bp + 5
+    G = rs.randn(nb * gstride)
+    ctx = _lib.Context()
+    dG, dB = _dev(G), _dev(_flat(nb, bstride, SENTINEL))
+    torch.cuda.synchronize()
+    _lib.check(_lib.load().gpt_dev_sparse_assemble_b_batch(ctx.handle, nb, dG.data_ptr(), ldg, gstride, M, dB.data_ptr(), bp, bstride, big))
+    ctx.synchronize()
+    got = dB.cpu().numpy()
+    for b in range(nb):
+        assert np.all(got[b * bstride + bp * bp:(b + 1) * bstride] == SENTINEL), b
+        d1 = _dev(np.full(bp * bp, SENTINEL))
+        torch.cuda.synchronize()
+        _lib.check(_lib.load().gpt_dev_sparse_assemble_b(ctx.handle, dG[b * gstride:].data_ptr(), ldg, M, d1.data_ptr(), bp, big))
+        ctx.synchronize()
+        one = d1.cpu().numpy()
+        assert same_bits(got[b * bstride:b * bstride + bp * bp], one), b
+        assert one[M * bp + M] == big and one[0] == G[b * gstride] + 1.0
